@@ -10,6 +10,7 @@ is measured in that reference-faithful mode.  The `hoisted` object reports the p
 mode, where the perception feature is memoised per image tensor (one ResNet pass per scene).
 
 Contract: python bench.py --gpus N --steps K --warmup W  ->  one JSON line on rank 0.
+--dump-outputs DIR additionally writes the trajectories the timed loops returned (DIR/<name>.npy, fp32; fixed inputs).
 Multi-GPU: scenes are independent, every rank samples its own 64 scenes, no collective on the data
 path ("scaling": "weak"); the barrier only brackets the timed region.
 """
@@ -676,6 +677,9 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="N = 1: run the FREE_GUIDANCE training leg under parallel.DataParallel(force=True) on a one-rank RCCL group "
                          "(train_free.gradient_buckets.overlap_rank0 then reports the bucket reductions against backward)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed sampling loops returned in their last step (the float32 "
+                         "trajectories of rank 0's scenes) as DIR/<name>.npy, for comparing two builds output for output")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--short-sampling", action="store_true", help=argparse.SUPPRESS)   # tests: skip the hoisted / graph legs
     args = ap.parse_args()
@@ -761,9 +765,10 @@ def main():
         model._feat_cache = None   # hoisted mode: the timed region pays for its own perception pass
         barrier()
         t0 = time.perf_counter()
-        run(n_steps)
+        trajs = run(n_steps)
         barrier()
-        return max_over_ranks(time.perf_counter() - t0, world, dev)
+        dt_, per_rank_ = max_over_ranks(time.perf_counter() - t0, world, dev)
+        return dt_, per_rank_, trajs
 
     # the perception pass alone (HIP events on the caller's stream around 8 back-to-back passes on the tick's image tensor), as the
     # product runs it: two sub-batches on streams of their own (csrc/conv2d.hip), on the pass stream (modeling/perception.py)
@@ -773,10 +778,15 @@ def main():
             model.perception(d["imgs"])
             pass_ms = round(time_events(lambda: model.perception(d["imgs"]), 8, warm=1), 4)
     model.cache_perception = False          # reference-faithful: perception re-run every step
-    dt, per_rank = timed(args.steps, args.warmup)
+    dt, per_rank, trajs = timed(args.steps, args.warmup)
     model.cache_perception = True           # product default: one perception pass per scene
     steps_h = args.steps if args.short_sampling else max(args.steps, N_INFER)
-    dt_h, per_rank_h = timed(steps_h, args.warmup)
+    dt_h, per_rank_h, trajs_h = timed(steps_h, args.warmup)
+    # --dump-outputs: what the caller of each timed loop receives after its last step (B x H x D, fp32); the inputs are fixed
+    # (procedural weights seed 0, synthetic batch seed = rank), so two builds can be compared array for array
+    dumped = ({"trajectories": trajs.float().cpu().numpy(), "trajectories_hoisted": trajs_h.float().cpu().numpy()}
+              if args.dump_outputs else {})
+    del trajs, trajs_h
 
     # the same hoisted loop as ONE HIP graph per 50-step tick (sampling.GraphedSampler: perception pass, 50 x (UNet +
     # scheduler step), clamp and scaling captured once, replayed bit-identically): no host work between launches
@@ -885,6 +895,15 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
             res["speedup_vs_cpu_baseline"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
+        if args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+            res["dumped_outputs"] = {"dir": args.dump_outputs,
+                                     "arrays": {name: {"shape": list(arr.shape), "dtype": str(arr.dtype)} for name, arr in dumped.items()},
+                                     "note": "trajectories: the reference-faithful loop after its `steps` timed steps (the `value` path); "
+                                             "trajectories_hoisted: the hoisted loop after its `hoisted.steps` timed steps"}
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(res) + "\n").encode())
     if world > 1:
