@@ -664,15 +664,19 @@ __global__ void __launch_bounds__(NT) trajpred_backward_kernel(const TrajArgs a)
     }
 }
 
-// Fused classifier guidance for one sample (GUIDANCE.STEP = 1):
-//   x = cat([0; state_pred(action[:-1])], action);  choose h* by TargetGuidance's rule;
-//   g_x = 2 (x[h*, :2] - target) at (h*, :2);  g_a = d(state)/d(action)^T g_x[1:, :4];
-//   x[:, :4] -= scale/15 * std * g_x[:, :4];  x[:, 4:] -= scale * std * g_a;  clip(-1, 1)
+// widest state head adx_trajpred_create takes (transition_dim - 3 for transition_dim 4..11)
+constexpr int kMaxOutDim = 8;
+
+// Fused classifier guidance for one sample (GUIDANCE.STEP = 1), od = state width:
+//   x = cat([0; state_pred(action[:-1])], action);  choose h* by TargetGuidance's rule on x[..., :2];
+//   g_x = 2 (x[h*, :2] - target) at (h*, :2);  g_a = d(x[:, :2])/d(action)^T g_x  (through state_pred, plus the direct
+//   term when od == 1: x[..., 1] is then action[..., 0]);
+//   x[:, :od] -= scale/15 * std * g_x[:, :od];  x[:, od:] -= scale * std * g_a;  clip(-1, 1)
 template <int TP>
 __global__ void __launch_bounds__(NT) guided_output_kernel(const TrajArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const Lds<TP> l = carve<TP>(smem, a.big + (size_t)blockIdx.x * big_floats<TP>());
-  __shared__ float st[TP + 1][4];
+  __shared__ float st[TP + 1][kMaxOutDim];
   __shared__ int hstar;
   __shared__ float gxy[2];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -691,23 +695,25 @@ __global__ void __launch_bounds__(NT) guided_output_kernel(const TrajArgs a) {
     st[h][j] = acc;
   }
   __syncthreads();
+  // column c < 2 of x = [state | action] at row h: the loss reads these two
+  auto xc = [&](int h, int c) { return c < od ? st[h][c] : act[(int64_t)h * a.act_st + (c - od)]; };
   if (tid == 0) {
     const float tx = a.target[2 * b], ty = a.target[2 * b + 1];
-    const float x0 = st[0][0], y0 = st[0][1];
+    const float x0 = xc(0, 0), y0 = xc(0, 1);
     const float t2a = sqrtf((tx - x0) * (tx - x0) + (ty - y0) * (ty - y0));
-    const float fx = st[H - 1][0] - x0, fy = st[H - 1][1] - y0;
+    const float fx = xc(H - 1, 0) - x0, fy = xc(H - 1, 1) - y0;
     const float f2a = sqrtf(fx * fx + fy * fy);
     int best = 0;
     if (!(f2a < t2a)) {
       float bd = INFINITY;
       for (int h = 0; h < H; ++h) {
-        const float dx = st[h][0] - tx, dy = st[h][1] - ty;
+        const float dx = xc(h, 0) - tx, dy = xc(h, 1) - ty;
         const float d = dx * dx + dy * dy;
         if (d < bd) { bd = d; best = h; }   // first minimum, like torch.argmin
       }
     }
     hstar = best;
-    const float dx = st[best][0] - tx, dy = st[best][1] - ty;
+    const float dx = xc(best, 0) - tx, dy = xc(best, 1) - ty;
     gxy[0] = 2.f * dx;
     gxy[1] = 2.f * dy;
     if (a.loss != nullptr) a.loss[b] = dx * dx + dy * dy;
@@ -715,7 +721,8 @@ __global__ void __launch_bounds__(NT) guided_output_kernel(const TrajArgs a) {
   __syncthreads();
   const int hs = hstar;
   const float g0 = gxy[0], g1 = gxy[1];
-  // gradient w.r.t. the action through the state path (row h* of x is state row h*-1; row 0 is the dummy zero)
+  // gradient w.r.t. the action through the state path (row h* of x is state row h*-1; row 0 is the dummy zero); only the
+  // state columns among x[..., :2] feed it (backward_core asks for j < od)
   if (hs > 0) {
     backward_core<TP>(l, a, b, tid, dr_off, [&](int t, int j) { return (t == hs - 1 && j < 2) ? (j == 0 ? g0 : g1) : 0.f; });
   } else {
@@ -731,6 +738,10 @@ __global__ void __launch_bounds__(NT) guided_output_kernel(const TrajArgs a) {
     if (j < od) {
       v = st[h][j];
       if (h == hs && j < 2) v -= s_state * (j == 0 ? g0 : g1);
+    } else if (od == 1 && j == 1 && h == hs) {
+      // x[h*, 1] is action[h*, 0] itself: its direct gradient adds to the one through state_pred (rows 0..T alike)
+      v = act[(int64_t)h * a.act_st];
+      v -= s_act * ((h < T ? l.O[h * IN_DIM] : 0.f) + g1);
     } else {
       v = act[(int64_t)h * a.act_st + (j - od)];
       if (h < T) v -= s_act * l.O[h * IN_DIM + (j - od)];
@@ -753,7 +764,8 @@ struct adx_trajpred {
 extern "C" {
 
 int adx_trajpred_create(int32_t out_dim, adx_trajpred** out) {
-  ADX_REQUIRE(out != nullptr && out_dim >= 2 && out_dim <= 4, "adx_trajpred_create: out_dim %d must be 2..4", out_dim);
+  ADX_REQUIRE(out != nullptr && out_dim >= 1 && out_dim <= kMaxOutDim, "adx_trajpred_create: out_dim %d must be 1..%d", out_dim,
+              kMaxOutDim);
   adx_trajpred* t = new adx_trajpred();
   t->L = make_layout(out_dim);
   *out = t;

@@ -244,7 +244,14 @@ static int build(adx_unet* u) {
   ADX_REQUIRE(c.n_mults >= 1 && c.n_mults <= 8, "unet: n_mults %d out of range", c.n_mults);
   ADX_REQUIRE(c.guidance >= 0 && c.guidance <= 2, "unet: guidance %d out of range", c.guidance);
   ADX_REQUIRE(c.dim >= 16 && c.dim % 16 == 0, "unet: dim %d must be a multiple of 16", c.dim);
-  ADX_REQUIRE(c.transition_dim >= 4, "unet: transition_dim %d too small", c.transition_dim);
+  // CLASSIFIER_GUIDANCE: state_pred's width is transition_dim - 3 (temporal.py:187), which adx_trajpred_create takes as 1..8
+  if (c.guidance == 2)
+    ADX_REQUIRE(c.transition_dim >= 4 && c.transition_dim <= 11,
+                "unet: transition_dim %d out of range: CLASSIFIER_GUIDANCE takes 4..11", c.transition_dim);
+  else
+    ADX_REQUIRE(c.transition_dim >= 1 && c.transition_dim <= 16,
+                "unet: transition_dim %d out of range: %s takes 1..16", c.transition_dim,
+                c.guidance == 1 ? "FREE_GUIDANCE" : "NO_GUIDANCE");
   const int n = c.n_mults;
   u->n_levels = n;
   ADX_REQUIRE(c.horizon % (1 << (n - 1)) == 0, "unet: horizon %d not divisible by %d", c.horizon, 1 << (n - 1));

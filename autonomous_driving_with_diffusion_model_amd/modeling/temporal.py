@@ -33,6 +33,14 @@ from .perception import PerceptionResNet34
 from .spec import unet_entries
 from .trajpredict import TrajPredict
 
+# transition_dim (D, the trajectory's channel count) each guidance mode takes (csrc/unet.hip checks the same ranges);
+# classifier guidance needs a state of D - 3 >= 1 columns before the 3 action columns
+TRANSITION_DIM_RANGE = {
+    GuidanceType.NO_GUIDANCE: (1, 16),
+    GuidanceType.FREE_GUIDANCE: (1, 16),
+    GuidanceType.CLASSIFIER_GUIDANCE: (4, 11),
+}
+
 
 class _UnetTrainFn(torch.autograd.Function):
     """Temporal stack with gradients: adx_unet_forward_train keeps a tape in a per-call workspace,
@@ -104,6 +112,11 @@ class TemporalMapUnet(nn.Module):
             # (temporal.py:168 builds LinearAttention(dim_out) for a dim_in tensor)
             raise NotImplementedError("USE_ATTN=True is not supported (it raises in the reference's up path too)")
         self.horizon, self.transition_dim, self.dim = int(horizon), int(transition_dim), int(dim)
+        lo, hi = TRANSITION_DIM_RANGE[use_cond]
+        if not lo <= self.transition_dim <= hi:
+            raise ValueError(f"transition_dim {self.transition_dim} out of range: {use_cond.name} takes {lo}..{hi}"
+                             + (" (state_pred's width transition_dim - 3 is 1..8)"
+                                if use_cond == GuidanceType.CLASSIFIER_GUIDANCE else ""))
         self.dim_mults = tuple(int(m) for m in dim_mults)
         self.use_cond = use_cond
         dims = [transition_dim, *[dim * m for m in self.dim_mults]]

@@ -95,6 +95,8 @@ class TrajPredict(nn.Module):
         if (in_dim, hidden_dim, num_heads, num_layers) != (3, 64, 4, 2):
             raise NotImplementedError("TrajPredict kernels are built for in_dim 3, hidden 64, 4 heads, 2 layers "
                                       "(the only configuration TemporalMapUnet instantiates, temporal.py:187-189)")
+        if not 1 <= out_dim <= 8:
+            raise ValueError(f"TrajPredict out_dim {out_dim} out of range: the kernels take 1..8")
         self.in_dim, self.out_dim, self.pred_len = in_dim, out_dim, pred_len
         self.hidden_dim, self.num_heads, self.num_layers = hidden_dim, num_heads, num_layers
         self._entries = traj_predict_entries("", in_dim, out_dim, hidden_dim, num_layers)
