@@ -48,6 +48,9 @@ class UnetIO(C.Structure):
                 ("rows", i32), ("out", vp), ("time_embed", vp), ("x_rows", i32), ("time_bias", vp)]
 
 
+UNET_ATTENTION = 1          # adx_unet_create_ex flag (ADX_UNET_ATTENTION)
+
+
 class Conv2dDesc(C.Structure):
     _fields_ = [("cin", i32), ("cout", i32), ("k", i32), ("stride", i32), ("pad", i32)]
 
@@ -69,6 +72,7 @@ _SIGS = {
     "adx_tconv_forward": (i32, [C.POINTER(TConvDesc), C.POINTER(TConvIO), vp]),
     "adx_embed_forward": (i32, [C.POINTER(EmbedWeights), i32, vp, i32, vp, vp, i32, i32, vp, vp, vp]),
     "adx_unet_create": (i32, [C.POINTER(UnetConfig), C.POINTER(vp)]),
+    "adx_unet_create_ex": (i32, [C.POINTER(UnetConfig), i32, C.POINTER(vp)]),
     "adx_unet_destroy": (None, [vp]),
     "adx_unet_num_params": (i32, [vp]),
     "adx_unet_packed_bytes": (C.c_size_t, [vp]),
@@ -86,6 +90,10 @@ _SIGS = {
     "adx_gn_mish_backward": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "adx_tconv_wgrad": (i32, [C.POINTER(TConvDesc), C.POINTER(TConvIO), vp, vp, vp]),
     "adx_bias_grad": (i32, [vp, vp, i32, i32, i32, vp]),
+    "adx_chan_layernorm_forward": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "adx_chan_layernorm_backward": (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "adx_linattn_forward": (i32, [vp, vp, i32, i32, i32, vp]),
+    "adx_linattn_backward": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "adx_resnet_create": (i32, [i32, C.POINTER(vp)]),
     "adx_resnet_destroy": (None, [vp]),
     "adx_resnet_num_tensors": (i32, [vp]),

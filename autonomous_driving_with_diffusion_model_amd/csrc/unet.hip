@@ -62,6 +62,19 @@ struct Builder {
     L.o_b = take(cout);
     return L;
   }
+  // Residual(PreNorm(c, LinearAttention(c))): to_qkv.weight, to_out.weight, to_out.bias, norm.g, norm.b (PreNorm registers
+  // fn before norm, modeling/helpers.py:143-147)
+  AttnLayer attn_block(int c, int len) {
+    AttnLayer A;
+    A.c = c; A.len = pow2_ceil(len); A.len_valid = len;
+    A.qkv.d = conv_desc(0, 1, 1, 0, c, 0, 3 * kAttnHidden, len, len, 0);
+    A.qkv.p_w = next_param++;
+    A.qkv.o_w = take(tconv_packed_floats(&A.qkv.d));
+    A.out = plain(0, 1, 1, 0, kAttnHidden, 0, c, len, len);
+    A.p_g = next_param++; A.p_b = next_param++;
+    A.o_g = take(c); A.o_b = take(c);
+    return A;
+  }
   ResBlock res_block(int c0, int c1, int cout, int len) {
     ResBlock B;
     B.c0 = c0; B.c1 = c1; B.cout = cout; B.len = pow2_ceil(len);     // pitch of the activation buffers
@@ -239,8 +252,10 @@ static void plan_chain(ChainPlan* cp, const ResBlock& b0, const ResBlock& b1, co
   cp->valid = true;
 }
 
-static int build(adx_unet* u) {
+static int build(adx_unet* u, int flags) {
   const adx_unet_config& c = u->cfg;
+  ADX_REQUIRE((flags & ~ADX_UNET_ATTENTION) == 0, "unet: unknown flags 0x%x", (unsigned)flags);
+  const bool attention = (flags & ADX_UNET_ATTENTION) != 0;
   ADX_REQUIRE(c.n_mults >= 1 && c.n_mults <= 8, "unet: n_mults %d out of range", c.n_mults);
   ADX_REQUIRE(c.guidance >= 0 && c.guidance <= 2, "unet: guidance %d out of range", c.guidance);
   ADX_REQUIRE(c.dim >= 16 && c.dim % 16 == 0, "unet: dim %d must be a multiple of 16", c.dim);
@@ -255,6 +270,17 @@ static int build(adx_unet* u) {
   const int n = c.n_mults;
   u->n_levels = n;
   ADX_REQUIRE(c.horizon % (1 << (n - 1)) == 0, "unet: horizon %d not divisible by %d", c.horizon, 1 << (n - 1));
+  if (attention) {
+    // the reference builds each up level's LinearAttention for dim_out channels and applies it to the level's dim_in-channel
+    // output (modeling/temporal.py:168,226-231): its forward runs only where dim_in == dim_out at every up level, i.e. with
+    // all dim_mults equal; with one level it has no up path and cannot build final_conv (final_up_dim stays None)
+    bool uniform = n >= 2;
+    for (int i = 1; i < n; ++i) uniform = uniform && c.dim_mults[i] == c.dim_mults[0];
+    ADX_REQUIRE(uniform, "unet: attention (MODEL.USE_ATTN) needs n_mults >= 2 and all dim_mults equal: the reference applies "
+                         "LinearAttention(dim_out) to each up level's dim_in-channel output, so its forward fails whenever "
+                         "dim_in != dim_out (and it cannot build a one-level model at all)");
+    ADX_REQUIRE(pow2_ceil(c.horizon) <= 64, "unet: attention supports horizons up to 64, got %d", c.horizon);
+  }
   Builder B{u};
   // parameter order == TemporalMapUnet.__init__ registration order (temporal.py:87-194)
   if (c.guidance == 1) {
@@ -266,11 +292,13 @@ static int build(adx_unet* u) {
   for (int i = 0; i < n; ++i) dims[i + 1] = c.dim * c.dim_mults[i];
   int len = c.horizon;
   std::vector<int> level_len(n);
+  std::vector<AttnLayer> down_attn, up_attn;
   for (int i = 0; i < n; ++i) {
     const int ci = dims[i], co = dims[i + 1];
     level_len[i] = len;
     u->blocks.push_back(B.res_block(ci, 0, co, len));
     u->blocks.push_back(B.res_block(co, 0, co, len));
+    if (attention) down_attn.push_back(B.attn_block(co, len));
     if (i < n - 1) {
       u->downs.push_back(B.plain(0, 3, 2, 1, co, 0, co, len, len / 2));
       len /= 2;
@@ -284,6 +312,7 @@ static int build(adx_unet* u) {
     const int ci = dims[n - 1 - i], co = dims[n - i];  // reversed(in_out[1:])
     up_blocks.push_back(B.res_block(co, co, ci, ulen));
     up_blocks.push_back(B.res_block(ci, 0, ci, ulen));
+    if (attention) up_attn.push_back(B.attn_block(ci, ulen));
     up_convs.push_back(B.plain(1, 4, 2, 1, ci, 0, ci, ulen, ulen * 2));
     ulen *= 2;
   }
@@ -291,7 +320,14 @@ static int build(adx_unet* u) {
   // the time-bias column offsets follow execution order only by convention; keep the
   // registration-order offsets assigned by res_block() above
   ResBlock m1 = B.res_block(mid, 0, mid, len);
+  AttnLayer mid_attn;
+  if (attention) mid_attn = B.attn_block(mid, len);
   ResBlock m2 = B.res_block(mid, 0, mid, len);
+  if (attention) {       // execution order: downs, mid, ups
+    u->attn = down_attn;
+    u->attn.push_back(mid_attn);
+    u->attn.insert(u->attn.end(), up_attn.begin(), up_attn.end());
+  }
   u->blocks.push_back(m1);
   u->blocks.push_back(m2);
   for (auto& b : up_blocks) u->blocks.push_back(b);
@@ -332,6 +368,7 @@ static int build(adx_unet* u) {
     ResBlock& b0 = u->blocks[2 * i];
     ResBlock& b1 = u->blocks[2 * i + 1];
     ConvLayer* dn = i < n - 1 ? &u->downs[i] : nullptr;
+    if (attention) continue;      // the attention block sits between block 1 and the down conv: the level runs layer by layer
     plan_chain(&u->down_chains[i], b0, b1, dn, nullptr, nullptr, false, i);
     if (u->down_chains[i].valid) give_images(u->down_chains[i]);
   }
@@ -339,6 +376,7 @@ static int build(adx_unet* u) {
     ResBlock& b0 = u->blocks[2 * n + 2 + 2 * i];
     ResBlock& b1 = u->blocks[2 * n + 2 + 2 * i + 1];
     const bool last = i == n - 2;
+    if (attention) continue;
     plan_chain(&u->up_chains[i], b0, b1, &u->ups[i], last ? &u->head0 : nullptr, last ? &u->head1 : nullptr, true, i);
     if (u->up_chains[i].valid) give_images(u->up_chains[i]);
   }
@@ -351,7 +389,7 @@ static int build(adx_unet* u) {
     ResBlock& m2 = u->blocks[2 * n + 1];
     ConvLayer* run[7] = {&b0.b, &b1.a, &b1.b, &m1.a, &m1.b, &m2.a, &m2.b};
     const adx_tconv_desc& d0 = b0.b.d;
-    bool ok = debug_switches().unet_pipe && !u->down_chains[n - 1].valid && b0.has_r && !b1.has_r && !m1.has_r && !m2.has_r &&
+    bool ok = debug_switches().unet_pipe && !attention && !u->down_chains[n - 1].valid && b0.has_r && !b1.has_r && !m1.has_r && !m2.has_r &&
               d0.lin == b0.len;
     for (ConvLayer* L : run) {
       const adx_tconv_desc& d = L->d;
@@ -379,6 +417,11 @@ static int build(adx_unet* u) {
   }
   for (auto& l : u->downs) { int rc = tconv_check(&l.d); if (rc != ADX_OK) return rc; }
   for (auto& l : u->ups) { int rc = tconv_check(&l.d); if (rc != ADX_OK) return rc; }
+  for (auto& a : u->attn) {
+    int rc = tconv_check(&a.qkv.d);
+    if (rc == ADX_OK) rc = tconv_check(&a.out.d);
+    if (rc != ADX_OK) return rc;
+  }
   int rc = tconv_check(&u->head0.d);
   if (rc == ADX_OK) rc = tconv_check(&u->head1.d);
   if (rc == ADX_OK) rc = tconv_check(&u->tlin.d);
@@ -495,11 +538,13 @@ using namespace adx;
 
 extern "C" {
 
-int adx_unet_create(const adx_unet_config* cfg, adx_unet** out) {
+int adx_unet_create(const adx_unet_config* cfg, adx_unet** out) { return adx_unet_create_ex(cfg, 0, out); }
+
+int adx_unet_create_ex(const adx_unet_config* cfg, int32_t flags, adx_unet** out) {
   ADX_REQUIRE(cfg != nullptr && out != nullptr, "adx_unet_create: null argument");
   adx_unet* u = new adx_unet();
   u->cfg = *cfg;
-  const int rc = build(u);
+  const int rc = build(u, flags);
   if (rc != ADX_OK) {
     delete u;
     return rc;
@@ -540,6 +585,12 @@ int adx_unet_pack(adx_unet* u, const float* const* P, int32_t n_params, const fl
   for (auto& l : u->ups) if (rc == ADX_OK) rc = pack_layer(l, P, base, s);
   if (rc == ADX_OK) rc = pack_layer(u->head0, P, base, s);
   if (rc == ADX_OK) rc = pack_layer(u->head1, P, base, s);
+  for (auto& a : u->attn) {
+    if (rc == ADX_OK) rc = pack_layer(a.qkv, P, base, s);
+    if (rc == ADX_OK) rc = pack_layer(a.out, P, base, s);
+    if (rc == ADX_OK) rc = copy_f(base + a.o_g, P[a.p_g], a.c, s);
+    if (rc == ADX_OK) rc = copy_f(base + a.o_b, P[a.p_b], a.c, s);
+  }
   // the chains' parameter blocks: [bias | gamma | beta | residual bias] x cout_pad per stage (zero where a stage has none)
   for (const std::vector<ChainPlan>* cps : {&u->down_chains, &u->up_chains})
     for (const ChainPlan& cp : *cps) {
@@ -613,12 +664,25 @@ static size_t act_floats(const adx_unet* u, int rows) {
   return align64(m * rows);
 }
 
+// the attention blocks' scratch (behind the split scratch; none without attention): LayerNorm output, q|k|v, core output
+static void attn_floats(const adx_unet* u, int rows, size_t* xn, size_t* qkv, size_t* o) {
+  *xn = *qkv = *o = 0;
+  for (auto& a : u->attn) {
+    *xn = std::max(*xn, align64((size_t)rows * a.c * a.len));
+    *qkv = std::max(*qkv, align64((size_t)rows * 3 * kAttnHidden * a.len));
+    *o = std::max(*o, align64((size_t)rows * kAttnHidden * a.len));
+  }
+}
+
 size_t adx_unet_workspace_bytes(const adx_unet* u, int32_t rows) {
   if (!u || rows < 1) return 0;
   const int dim = u->cfg.dim;
   size_t f = align64((size_t)rows * dim) + align64((size_t)rows * 2 * dim) + align64((size_t)rows * u->sum_c);
   f += act_floats(u, rows) * (size_t)(kRing + u->n_levels);
   f += kSplitScratchFloats + kTicketWords;
+  size_t axn, aqkv, ao;
+  attn_floats(u, rows, &axn, &aqkv, &ao);
+  f += axn + aqkv + ao;
   return f * sizeof(float);
 }
 
@@ -667,6 +731,11 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     ~ScratchScope() { t_split_scratch = nullptr; t_split_tickets = nullptr; }
   };
   float* const split_scratch = take(kSplitScratchFloats);
+  size_t axn_f, aqkv_f, ao_f;
+  attn_floats(u, rows, &axn_f, &aqkv_f, &ao_f);
+  float* const attn_xn = axn_f ? take(axn_f) : nullptr;
+  float* const attn_qkv = aqkv_f ? take(aqkv_f) : nullptr;
+  float* const attn_o = ao_f ? take(ao_f) : nullptr;
   constexpr bool tickets_on = true;
   ScratchScope scratch_scope(split_scratch, tickets_on ? split_tickets : nullptr);
   bool tickets_pending = tickets_on;      // still to be cleared by this call
@@ -713,6 +782,21 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     const Act hin = dense(h, B.cout, B.len);
     return run_conv(B.b, base, hin, nullptr, nullptr, 0, &res, dst, (int64_t)B.cout * B.len, B.len, 1, rows, s);
   };
+
+  // the attention block: LayerNorm, to_qkv, core, to_out (+ bias + x), four launches
+  auto run_attn = [&](const AttnLayer& A, const Act& x, float* dst) -> int {
+    int r = chan_layernorm_forward(x.p, x.sb, x.sc, x.sl, base + A.o_g, base + A.o_b, attn_xn, nullptr, nullptr, rows, A.c, A.len,
+                                   A.len_valid, s);
+    if (r != ADX_OK) return r;
+    r = run_conv(A.qkv, base, dense(attn_xn, A.c, A.len), nullptr, nullptr, 0, nullptr, attn_qkv, (int64_t)3 * kAttnHidden * A.len,
+                 A.len, 1, rows, s);
+    if (r != ADX_OK) return r;
+    r = linattn_core_forward(attn_qkv, attn_o, rows, A.len, A.len_valid, s);
+    if (r != ADX_OK) return r;
+    return run_conv(A.out, base, dense(attn_o, kAttnHidden, A.len), nullptr, nullptr, 0, &x, dst, (int64_t)A.c * A.len, A.len, 1,
+                    rows, s);
+  };
+  const bool attention = !u->attn.empty();
 
   // one launch for a whole level (tconv_chain.hip) where the plan allows it
   constexpr int chain_rows = 0;     // 16 / 32 pin the rows per workgroup (measured: the rule below wins)
@@ -832,7 +916,14 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     rc = run_block(B0, cur, nullptr, y0);
     if (rc != ADX_OK) return rc;
     const Act a0 = dense(y0, B0.cout, B0.len);
-    rc = run_block(B1, a0, nullptr, skips[i]);  // the level output doubles as the skip (temporal.py:219)
+    if (attention) {      // the attention output is the level's output and the skip
+      float* y1 = next_buf();
+      rc = run_block(B1, a0, nullptr, y1);
+      if (rc != ADX_OK) return rc;
+      rc = run_attn(u->attn[i], dense(y1, B1.cout, B1.len), skips[i]);
+    } else {
+      rc = run_block(B1, a0, nullptr, skips[i]);  // the level output doubles as the skip (temporal.py:219)
+    }
     if (rc != ADX_OK) return rc;
     cur = dense(skips[i], B1.cout, B1.len);
     if (i < n - 1) {
@@ -849,6 +940,12 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     rc = run_block(B, cur, nullptr, y);
     if (rc != ADX_OK) return rc;
     cur = dense(y, B.cout, B.len);
+    if (k == 0 && attention) {       // mid_attn
+      float* ya = next_buf();
+      rc = run_attn(u->attn[n], cur, ya);
+      if (rc != ADX_OK) return rc;
+      cur = dense(ya, B.cout, B.len);
+    }
   }
   bool head_done = false;
   for (int i = 0; i < n - 1; ++i) {
@@ -878,7 +975,13 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     float* y1 = next_buf();
     rc = run_block(B1, a0, nullptr, y1);
     if (rc != ADX_OK) return rc;
-    const Act a1 = dense(y1, B1.cout, B1.len);
+    Act a1 = dense(y1, B1.cout, B1.len);
+    if (attention) {
+      float* ya = next_buf();
+      rc = run_attn(u->attn[n + 1 + i], a1, ya);
+      if (rc != ADX_OK) return rc;
+      a1 = dense(ya, B1.cout, B1.len);
+    }
     const ConvLayer& up = u->ups[i];
     float* y2 = next_buf();
     rc = run_conv(up, base, a1, nullptr, nullptr, 0, nullptr, y2, (int64_t)up.d.cout * up.d.lout, up.d.lout, 1, rows, s);

@@ -29,6 +29,24 @@ struct ResBlock {
   int c0 = 0, c1 = 0, cout = 0, len = 0;
 };
 
+// The attention block of MODEL.USE_ATTN (attn.hip): y = x + to_out(core(to_qkv(LayerNorm(x)))); to_qkv (no bias) and to_out
+// (bias, residual x in the epilogue) are ordinary 1x1 convs
+struct AttnLayer {
+  ConvLayer qkv, out;
+  int p_g = -1, p_b = -1;           // norm.g, norm.b ([1, C, 1])
+  size_t o_g = 0, o_b = 0;
+  int c = 0, len = 0, len_valid = 0;  // channels, padded length (the activation pitch), real length
+};
+
+int chan_layernorm_forward(const float* x, int64_t sb, int64_t sc, int64_t sl, const float* g, const float* b, float* xn,
+                           float* mean, float* rstd, int B, int C, int L, int L_valid, hipStream_t s);
+int chan_layernorm_backward(const float* dy, const float* x, int64_t sb, int64_t sc, int64_t sl, const float* mean,
+                            const float* rstd, const float* g, float* dx, float* dg, float* db, int B, int C, int L, int L_valid,
+                            bool accumulate, hipStream_t s);
+int linattn_core_forward(const float* qkv, float* o, int B, int L, int L_valid, hipStream_t s);
+int linattn_core_backward(const float* qkv, const float* dout, float* dqkv, int B, int L, int L_valid, hipStream_t s);
+constexpr int kAttnHidden = 128;    // LinearAttention: 4 heads x 32 channels; to_qkv makes 3 x 128
+
 // A run of layers executed by ONE launch of tconv_chain.hip: the two residual blocks of a level + its down / up conv
 // (+ final_conv on the last up level).  The plan is what does not depend on the call; chain_args() turns it into the
 // kernel's argument block for a batch and a choice of samples per workgroup.
@@ -67,5 +85,7 @@ struct adx_unet {
   // the deepest level's same-shaped layer run (block 0's second conv, block 1, both mid blocks: seven convs) as ONE pipeline
   // launch at small batches (tconv_pipe.hip); pipe_ok: the configuration qualifies (decided once, at creation)
   bool pipe_ok = false;
+  // MODEL.USE_ATTN: one block per down level, then mid_attn, then one per up level (execution order); empty when off
+  std::vector<adx::AttnLayer> attn;
 };
 

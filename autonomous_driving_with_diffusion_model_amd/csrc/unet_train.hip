@@ -38,7 +38,12 @@ struct TAct {  // activation view [rows][c][len]
 };
 
 struct TapeOp {
-  const ConvLayer* L = nullptr;
+  enum Kind { kConv, kLayerNorm, kAttnCore };
+  Kind kind = kConv;
+  const ConvLayer* L = nullptr;      // kConv
+  const AttnLayer* A = nullptr;      // kLayerNorm (x0 -> y, with mean / rstd), kAttnCore (q|k|v x0 -> y)
+  float* mean = nullptr;
+  float* rstd = nullptr;
   TAct x0, x1, res, y;
   bool has_x1 = false, has_res = false;
   float* pre = nullptr;
@@ -82,6 +87,7 @@ static size_t max_act(const adx_unet* u, int rows) {
   for (auto& b : u->blocks) m = std::max(m, (size_t)(b.c0 + b.c1) * b.len), m = std::max(m, (size_t)b.cout * b.len);
   for (auto& l : u->ups) m = std::max(m, (size_t)l.d.cout * l.d.lout);
   m = std::max(m, (size_t)u->head0.d.cout * u->head0.d.lout);
+  for (auto& a : u->attn) m = std::max(m, (size_t)std::max(a.c, 3 * kAttnHidden) * a.len);
   return align64t(m * rows);
 }
 
@@ -102,7 +108,8 @@ extern "C" {
 size_t adx_unet_train_workspace_bytes(const adx_unet* u, int32_t rows) {
   if (!u || rows < 1) return 0;
   const size_t a = max_act(u, rows);
-  const size_t n_conv = u->blocks.size() * 3 + u->downs.size() + u->ups.size() + 2;
+  // an attention block counts as four launches: LayerNorm, to_qkv, core, to_out
+  const size_t n_conv = u->blocks.size() * 3 + u->downs.size() + u->ups.size() + 2 + 4 * u->attn.size();
   size_t f = a * (n_conv * 4 + 16);                                   // y, pre, grad, dc/cat scratch per launch
   f += align64t((size_t)rows * u->sum_c) * 2 + align64t((size_t)rows * 2 * u->cfg.dim) * 2 + align64t((size_t)rows * u->cfg.dim) * 2;
   f += n_conv * align64t((size_t)rows * 8 * 2);                       // GN stats
@@ -115,6 +122,7 @@ size_t adx_unet_train_workspace_bytes(const adx_unet* u, int32_t rows) {
   for (auto& l : u->downs) img(l.d);
   for (auto& l : u->ups) img(l.d);
   img(u->head0.d); img(u->head1.d);
+  for (auto& a : u->attn) { img(a.qkv.d); img(a.out.d); }
   f += wall + align64t((size_t)u->sum_c * 2 * u->cfg.dim * 2);
   return f * sizeof(float);
 }
@@ -142,6 +150,7 @@ int adx_unet_forward_train(adx_unet* u, const void* packed, void* workspace, siz
     for (auto& b : u->blocks) ok = ok && trainable(b.a.d) && trainable(b.b.d) && (!b.has_r || trainable(b.r.d));
     for (auto& l : u->downs) ok = ok && trainable(l.d);
     for (auto& l : u->ups) ok = ok && trainable(l.d);
+    for (auto& a : u->attn) ok = ok && trainable(a.qkv.d) && trainable(a.out.d);
     ADX_REQUIRE(ok, "adx_unet_forward_train: this configuration has GroupNorm groups that are not a power of two wide or hold "
                     "fewer than 64 elements; such layers run in sampling only (csrc/tconv_generic.hip), training needs "
                     "MODEL.DIM in {32, 64, 128, ...} and a horizon of at least 16");
@@ -218,6 +227,26 @@ int adx_unet_forward_train(adx_unet* u, const void* packed, void* workspace, siz
     if (B.has_r) res = conv(B.r, x0, x1, -1, nullptr, nullptr, x_needs_grad);
     return conv(B.b, h, nullptr, -1, &res, nullptr, true);
   };
+  // the attention block: LayerNorm and core are taped ops of their own, to_qkv and to_out taped convs (to_out: residual x)
+  auto attn = [&](const AttnLayer& A, const TAct& x) -> TAct {
+    TapeOp ln;
+    ln.kind = TapeOp::kLayerNorm; ln.A = &A; ln.x0 = x;
+    ln.y = dense_act(ws.take((size_t)rows * A.c * A.len), A.c, A.len);
+    ln.mean = ws.take((size_t)rows * A.len);
+    ln.rstd = ws.take((size_t)rows * A.len);
+    if (rc == ADX_OK && ws.ok)
+      rc = chan_layernorm_forward(x.p, x.sb, x.sc, x.sl, base + A.o_g, base + A.o_b, const_cast<float*>(ln.y.p), ln.mean, ln.rstd,
+                                  rows, A.c, A.len, A.len_valid, s);
+    tape->ops.push_back(ln);
+    const TAct qkv = conv(A.qkv, ln.y, nullptr, -1, nullptr, nullptr, true);
+    TapeOp core;
+    core.kind = TapeOp::kAttnCore; core.A = &A; core.x0 = qkv;
+    core.y = dense_act(ws.take((size_t)rows * kAttnHidden * A.len), kAttnHidden, A.len);
+    if (rc == ADX_OK && ws.ok) rc = linattn_core_forward(qkv.p, const_cast<float*>(core.y.p), rows, A.len, A.len_valid, s);
+    tape->ops.push_back(core);
+    return conv(A.out, core.y, nullptr, -1, &x, nullptr, true);
+  };
+  const bool attention = !u->attn.empty();
 
   TAct cur;
   cur.p = io->x; cur.sb = (int64_t)H * D; cur.sc = 1; cur.sl = D; cur.c = D; cur.len = H;
@@ -227,13 +256,18 @@ int adx_unet_forward_train(adx_unet* u, const void* packed, void* workspace, siz
   for (int i = 0; i < n; ++i) {
     const TAct a0 = block(u->blocks[bi++], cur, nullptr, i > 0);  // the noisy trajectory needs no gradient
     cur = block(u->blocks[bi++], a0, nullptr, true);
+    if (attention) cur = attn(u->attn[i], cur);
     skips[i] = cur;
     if (i < n - 1) cur = conv(u->downs[i], cur, nullptr, -1, nullptr, nullptr, true);
   }
-  for (int k = 0; k < 2; ++k) cur = block(u->blocks[bi++], cur, nullptr, true);
+  for (int k = 0; k < 2; ++k) {
+    cur = block(u->blocks[bi++], cur, nullptr, true);
+    if (k == 0 && attention) cur = attn(u->attn[n], cur);      // mid_attn
+  }
   for (int i = 0; i < n - 1; ++i) {
     const TAct a0 = block(u->blocks[bi++], cur, &skips[n - 1 - i], true);
-    const TAct a1 = block(u->blocks[bi++], a0, nullptr, true);
+    TAct a1 = block(u->blocks[bi++], a0, nullptr, true);
+    if (attention) a1 = attn(u->attn[n + 1 + i], a1);
     cur = conv(u->ups[i], a1, nullptr, -1, nullptr, nullptr, true);
   }
   const TAct hh = conv(u->head0, cur, nullptr, -1, nullptr, nullptr, true);
@@ -309,7 +343,7 @@ int adx_unet_backward(adx_unet* u, const void* packed, void* workspace, size_t w
     int rq = ADX_OK;
     for (size_t oi = 0; oi < tape->ops.size() && rq == ADX_OK; ++oi) {
       const TapeOp& op = tape->ops[oi];
-      if (!op.need_dx) continue;
+      if (op.kind != TapeOp::kConv || !op.need_dx) continue;
       const adx_tconv_desc g = dgrad_desc(op.L->d);
       gimg[oi] = ws.take(tconv_packed_floats(&g));
       if (!ws.ok) break;
@@ -326,6 +360,7 @@ int adx_unet_backward(adx_unet* u, const void* packed, void* workspace, size_t w
   // every small gradient tensor that is accumulated atomically (conv weights, GroupNorm affine, conv bias) is zeroed
   // here in a handful of launches instead of one memset each inside the loop
   for (const TapeOp& op : tape->ops) {
+    if (op.kind != TapeOp::kConv) continue;
     const ConvLayer& L = *op.L;
     const adx_tconv_desc& d = L.d;
     batch_fill_add(grads[L.p_w], (size_t)d.cout * (d.c0 + d.c1) * d.taps);
@@ -338,6 +373,23 @@ int adx_unet_backward(adx_unet* u, const void* packed, void* workspace, size_t w
   int rc = batch_fill_flush(s);
   for (size_t oi = tape->ops.size(); oi-- > 0 && rc == ADX_OK;) {
     const TapeOp& op = tape->ops[oi];
+    if (op.kind != TapeOp::kConv) {
+      // the attention block's LayerNorm / core: dy is the dense gradient of their output (the data gradient of the conv behind)
+      auto it = gmap.find(op.y.p);
+      ADX_REQUIRE(it != gmap.end() && it->second.has, "adx_unet_backward: launch %zu has no output gradient", oi);
+      const AttnLayer& A = *op.A;
+      Slot& xs = slot(op.x0);
+      if (op.kind == TapeOp::kLayerNorm) {
+        // the block input already holds the residual's share (to_out ran first in reverse): add to it
+        rc = chan_layernorm_backward(it->second.g, op.x0.p, op.x0.sb, op.x0.sc, op.x0.sl, op.mean, op.rstd, base + A.o_g, xs.g,
+                                     grads[A.p_g], grads[A.p_b], rows, A.c, A.len, A.len_valid, xs.has, s);
+      } else {
+        ADX_REQUIRE(!xs.has, "adx_unet_backward: q|k|v of an attention block has a second consumer");
+        rc = linattn_core_backward(op.x0.p, it->second.g, xs.g, rows, A.len, A.len_valid, s);
+      }
+      xs.has = true;
+      continue;
+    }
     const ConvLayer& L = *op.L;
     const adx_tconv_desc& d = L.d;
     const int cin = d.c0 + d.c1;

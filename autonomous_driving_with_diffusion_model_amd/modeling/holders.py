@@ -33,6 +33,10 @@ def _init_tensor(e: Entry, all_keys) -> torch.Tensor:
         return torch.zeros(shape)
     if leaf == "running_var":
         return torch.ones(shape)
+    if key.endswith("fn.norm.g"):          # the attention block's LayerNorm (modeling/helpers.py:131-135)
+        return torch.ones(shape)
+    if key.endswith("fn.norm.b"):
+        return torch.zeros(shape)
     is_norm = (key[: -len(leaf)] + "running_mean") in all_keys or ".block.2." in key or ".norm" in key
     if is_norm:
         return torch.ones(shape) if leaf == "weight" else torch.zeros(shape)

@@ -56,6 +56,12 @@ def _res_block(p, cin, cout, embed):
     return e
 
 
+def _attention(p, c):
+    """Residual(PreNorm(c, LinearAttention(c))): PreNorm registers fn before norm (modeling/helpers.py:120-175)."""
+    return [Entry(p + "fn.fn.to_qkv.weight", (384, c, 1)), Entry(p + "fn.fn.to_out.weight", (c, 128, 1)),
+            Entry(p + "fn.fn.to_out.bias", (c,)), Entry(p + "fn.norm.g", (1, c, 1)), Entry(p + "fn.norm.b", (1, c, 1))]
+
+
 def resnet34_entries(p: str, out_dim: int) -> List[Entry]:
     e = [Entry(p + "conv1.weight", (64, 3, 7, 7))] + _bn(p + "bn1.", 64)
     inplanes = 64
@@ -91,8 +97,9 @@ def level_channels(transition_dim: int, dim: int, dim_mults: Sequence[int]) -> L
 
 
 def unet_entries(use_cond: str = "NO_GUIDANCE", transition_dim: int = 7, dim: int = 64,
-                 dim_mults: Sequence[int] = (1, 2, 4, 8)) -> List[Entry]:
-    """Everything registered by TemporalMapUnet.__init__, perception included."""
+                 dim_mults: Sequence[int] = (1, 2, 4, 8), attention: bool = False) -> List[Entry]:
+    """Everything registered by TemporalMapUnet.__init__, perception included.  attention: MODEL.USE_ATTN, whose blocks
+    are downs.{i}.2, mid_attn (between the mid blocks) and ups.{i}.2, each built for the level's dim_out channels."""
     in_out = level_channels(transition_dim, dim, dim_mults)
     embed = 2 * dim
     e = resnet34_entries("perception.", dim)
@@ -102,16 +109,23 @@ def unet_entries(use_cond: str = "NO_GUIDANCE", transition_dim: int = 7, dim: in
     n = len(in_out)
     for i, (ci, co) in enumerate(in_out):
         e += _res_block(f"downs.{i}.0.", ci, co, embed) + _res_block(f"downs.{i}.1.", co, co, embed)
+        if attention:
+            e += _attention(f"downs.{i}.2.", co)
         if i < n - 1:
             e += _conv1d(f"downs.{i}.3.conv.", co, co, 3)
     final_up = None
     for i, (ci, co) in enumerate(reversed(in_out[1:])):
         e += _res_block(f"ups.{i}.0.", 2 * co, ci, embed) + _res_block(f"ups.{i}.1.", ci, ci, embed)
+        if attention:
+            e += _attention(f"ups.{i}.2.", co)
         # ConvTranspose1d weight layout is [Cin, Cout, k]; the reference upsamples at all 3 levels
         e += [Entry(f"ups.{i}.3.conv.weight", (ci, ci, 4)), Entry(f"ups.{i}.3.conv.bias", (ci,))]
         final_up = ci
     mid = in_out[-1][1]
-    e += _res_block("mid_block1.", mid, mid, embed) + _res_block("mid_block2.", mid, mid, embed)
+    e += _res_block("mid_block1.", mid, mid, embed)
+    if attention:
+        e += _attention("mid_attn.", mid)
+    e += _res_block("mid_block2.", mid, mid, embed)
     if use_cond == "CLASSIFIER_GUIDANCE":
         e += _conv1d_block("act_conv.0.", final_up, final_up) + _conv1d("act_conv.1.", final_up, 3, 1)
         e += traj_predict_entries("state_pred.", 3, transition_dim - 3, 64, 2)

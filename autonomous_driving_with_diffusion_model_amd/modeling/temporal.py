@@ -107,10 +107,17 @@ class TemporalMapUnet(nn.Module):
         super().__init__()
         if diffuser_building_block != "concat":
             raise NotImplementedError  # modeling/temporal.py:71-74
-        if attention:
-            # MODEL.USE_ATTN defaults to False and the reference's up path is broken with it
-            # (temporal.py:168 builds LinearAttention(dim_out) for a dim_in tensor)
-            raise NotImplementedError("USE_ATTN=True is not supported (it raises in the reference's up path too)")
+        self.attention = bool(attention)
+        mults = tuple(int(m) for m in dim_mults)
+        if self.attention and (len(mults) < 2 or len(set(mults)) != 1):
+            # the reference builds each up level's LinearAttention(dim_out) and applies it to that level's dim_in-channel
+            # output (modeling/temporal.py:168,226-231): its forward fails wherever dim_in != dim_out, and with one level
+            # it cannot build final_conv at all
+            raise NotImplementedError(
+                f"USE_ATTN=True needs at least two equal DIM_MULTS, got {mults}: the reference applies each up level's "
+                "LinearAttention(dim_out) to a dim_in-channel tensor, so its forward fails whenever dim_in != dim_out")
+        if self.attention and int(horizon) > 64:
+            raise NotImplementedError(f"USE_ATTN=True supports horizons up to 64, got {int(horizon)}")
         self.horizon, self.transition_dim, self.dim = int(horizon), int(transition_dim), int(dim)
         lo, hi = TRANSITION_DIM_RANGE[use_cond]
         if not lo <= self.transition_dim <= hi:
@@ -123,7 +130,7 @@ class TemporalMapUnet(nn.Module):
         if int(os.environ.get("LOCAL_RANK", "-1")) <= 0:
             print(f"[ models/temporal ] Channel dimensions: {list(zip(dims[:-1], dims[1:]))}")
 
-        entries = unet_entries(use_cond.name, self.transition_dim, self.dim, self.dim_mults)
+        entries = unet_entries(use_cond.name, self.transition_dim, self.dim, self.dim_mults, self.attention)
         # registration order: perception, [cond_mlp], time_mlp, downs, ups, mid_block1, mid_block2, heads
         self.perception = PerceptionResNet34(self.dim)
         rest = [e for e in entries if not e.key.startswith("perception.")]
@@ -154,7 +161,8 @@ class TemporalMapUnet(nn.Module):
                 cfg.dim_mults[i] = m
             cfg.guidance = self.use_cond.value
             h = L.vp()
-            L.check(L.lib().adx_unet_create(C.byref(cfg), C.byref(h)), "adx_unet_create")
+            flags = L.UNET_ATTENTION if self.attention else 0
+            L.check(L.lib().adx_unet_create_ex(C.byref(cfg), flags, C.byref(h)), "adx_unet_create_ex")
             self._handle = h
         return self._handle
 

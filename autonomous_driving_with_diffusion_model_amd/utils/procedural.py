@@ -36,6 +36,10 @@ def procedural_tensor(name: str, shape: Tuple[int, ...], seed: int = 0) -> torch
         return _uniform(name, seed, shape, -0.1, 0.1)
     if leaf == "running_var":
         return _uniform(name, seed, shape, 0.8, 1.2)
+    if name.endswith("fn.norm.g"):       # the attention block's LayerNorm affine, [1, C, 1]
+        return _uniform(name, seed, shape, 0.9, 1.1)
+    if name.endswith("fn.norm.b"):
+        return _uniform(name, seed, shape, -0.1, 0.1)
     if len(shape) == 1:
         # norm scales sit near 1, every other vector (biases) near 0
         is_scale = leaf == "weight"

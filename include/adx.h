@@ -132,6 +132,14 @@ typedef struct adx_unet_config {
 } adx_unet_config;
 
 int adx_unet_create(const adx_unet_config* cfg, adx_unet** out);
+/* adx_unet_create with option flags.  ADX_UNET_ATTENTION: MODEL.USE_ATTN, the LayerNorm + LinearAttention block
+ * (modeling/helpers.py:120-175) after each down level's and up level's second residual block and between the mid blocks.
+ * Accepted only with n_mults >= 2, all dim_mults equal and a horizon of at most 64: the reference builds the up levels'
+ * attention for dim_out channels and applies it to dim_in (temporal.py:168,226-231), so its forward fails on every other
+ * configuration.  Its parameters are registered as downs.{i}.2, mid_attn, ups.{i}.2: to_qkv.weight, to_out.weight,
+ * to_out.bias, norm.g, norm.b. */
+#define ADX_UNET_ATTENTION 1
+int adx_unet_create_ex(const adx_unet_config* cfg, int32_t flags, adx_unet** out);
 void adx_unet_destroy(adx_unet* u);
 /* number of parameter tensors expected by adx_unet_pack (the non-perception parameters,
  * in named_parameters() order; TrajPredict's are accepted but handled by adx_trajpred_*) */
@@ -198,6 +206,18 @@ int adx_gn_mish_backward(const float* dy, int64_t dy_sb, int64_t dy_sc, int64_t 
 /* op level: dW[cout][cin][taps] of a (kind 0) temporal conv from its input (io->x0/x1) and d(conv out) */
 int adx_tconv_wgrad(const adx_tconv_desc* d, const adx_tconv_io* io, const float* dc, float* dw, adx_stream s);
 int adx_bias_grad(const float* dc, float* db, int32_t B, int32_t C, int32_t L, adx_stream s);
+/* op level, the attention block's own kernels (csrc/attn.hip); L is the padded length (<= 64 for the core), L_valid the
+ * real one (0: L).  LayerNorm over channels of x [B][C][L] (strided) -> dense xn [B][C][L] and, when not NULL, the
+ * per-(sample, position) mean and rstd [B][L] the backward needs. */
+int adx_chan_layernorm_forward(const float* x, int64_t sb, int64_t sc, int64_t sl, const float* g, const float* b, float* xn,
+                               float* mean, float* rstd, int32_t B, int32_t C, int32_t L, int32_t L_valid, adx_stream s);
+/* dy dense [B][C][L] -> dx dense [B][C][L] (written, or added to with accumulate != 0), dg and db [C] (written) */
+int adx_chan_layernorm_backward(const float* dy, const float* x, int64_t sb, int64_t sc, int64_t sl, const float* mean,
+                                const float* rstd, const float* g, float* dx, float* dg, float* db, int32_t B, int32_t C,
+                                int32_t L, int32_t L_valid, int32_t accumulate, adx_stream s);
+/* qkv dense [B][384][L] (to_qkv's output) -> o dense [B][128][L]; the backward takes dO [B][128][L] -> dqkv [B][384][L] */
+int adx_linattn_forward(const float* qkv, float* o, int32_t B, int32_t L, int32_t L_valid, adx_stream s);
+int adx_linattn_backward(const float* qkv, const float* dout, float* dqkv, int32_t B, int32_t L, int32_t L_valid, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
  * Perception: ResNet-34 forward (eval mode, BatchNorm folded at pack time),
