@@ -1769,4 +1769,36 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
   return rc;
 }
 
+int adx_resnet_tape_describe(const adx_resnet_tape* tape, const void* workspace, int32_t index, int32_t* n_records, int32_t* ints,
+                             int64_t* offs) {
+  ADX_REQUIRE(tape && workspace && n_records && ints && offs, "adx_resnet_tape_describe: null argument");
+  ADX_REQUIRE(!tape->recs.empty() && tape->fwd_floats > 0, "adx_resnet_tape_describe: the tape holds no forward");
+  ADX_REQUIRE(index >= -1 && index < (int32_t)tape->recs.size(), "adx_resnet_tape_describe: index %d out of range (-1 .. %d)",
+              index, (int)tape->recs.size() - 1);
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(workspace), hi = lo + tape->fwd_floats * sizeof(float);
+  auto off = [&](const void* p) -> int64_t {
+    if (p == nullptr) return -1;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    return a >= lo && a < hi ? (int64_t)(a - lo) : -2;
+  };
+  *n_records = (int32_t)tape->recs.size();
+  for (int i = 0; i < 12; ++i) ints[i] = 0;
+  for (int i = 0; i < 7; ++i) offs[i] = -1;
+  if (index < 0) {
+    const int32_t v[10] = {(int32_t)tape->recs.size(), tape->batch, tape->h, tape->w, tape->ph, tape->pw, tape->poh, tape->pow_,
+                           tape->fh, tape->fw_};
+    for (int i = 0; i < 10; ++i) ints[i] = v[i];
+    offs[0] = off(tape->pool_code); offs[1] = off(tape->pool_out); offs[2] = off(tape->final_map);
+    return ADX_OK;
+  }
+  const adx_resnet_tape::Rec& q = tape->recs[index];
+  ADX_REQUIRE(q.L != nullptr, "adx_resnet_tape_describe: record %d is incomplete", index);
+  const int32_t v[12] = {q.L->cin, q.L->cout, q.L->k, q.L->stride, q.L->pad, q.H, q.W, q.OH, q.OW,
+                         !q.relu ? 0 : (q.identity != nullptr ? 1 : 2), q.x_cells ? 1 : 0, q.out_cells ? 1 : 0};
+  for (int i = 0; i < 12; ++i) ints[i] = v[i];
+  const void* p[7] = {q.x, q.raw, q.out, q.identity, q.mean, q.rstd, q.bits};
+  for (int i = 0; i < 7; ++i) offs[i] = off(p[i]);
+  return ADX_OK;
+}
+
 }  // extern "C"

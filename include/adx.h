@@ -311,6 +311,20 @@ int32_t adx_resnet_tensor_group(const adx_resnet* r, int32_t tensor);
 int adx_resnet_backward_events(adx_resnet* r, const float* const* tensors, float* const* grads, int32_t n_tensors,
                                void* workspace, size_t workspace_bytes, adx_resnet_tape* tape, const float* d_feature,
                                void* const* events, int32_t n_events, adx_stream s);
+/* For tests only: a read-only description of a tape filled by adx_resnet_forward_train, so that a test can read what the
+ * forward kept (and what the backward will condition on) out of the caller's workspace.  Locations are BYTE OFFSETS into
+ * `workspace` (the forward's); -1 = none, -2 = outside the forward's part of the workspace (the stem's input: the image).
+ * *n_records = the number of conv records (forward launch order: 0 = the stem, then per BasicBlock conv1, [downsample], conv2).
+ * index >= 0, record `index`:
+ *   ints[12] = {cin, cout, k, stride, pad, H, W, OH, OW, relu, x_cells, out_cells}
+ *              relu: 0 none, 1 after the residual add, 2 straight after BatchNorm (the backward re-derives that mask from raw)
+ *   offs[7]  = {x, raw, out, identity, mean, rstd, bits}   (bits: byte [n][c / 8][pixel], bit c % 8, of the output's mask)
+ * index == -1, the tape:
+ *   ints[12] = {n_records, batch, h, w, ph, pw, poh, pow, fh, fw, 0, 0}   (stem map, pooled map, final map sizes)
+ *   offs[7]  = {pool_code, pool_out, final_map, -1, -1, -1, -1}           (pool_code: first-maximum tap ty * 3 + tx per window)
+ * Refuses (ADX_ERR_*) a null tape / workspace / output, a tape with no forward and an index out of range. */
+int adx_resnet_tape_describe(const adx_resnet_tape* tape, const void* workspace, int32_t index, int32_t* n_records,
+                             int32_t* ints, int64_t* offs);
 
 /* ------------------------------------------------------------------------------------
  * Classifier guidance: TrajPredict state head (modeling/helpers.py:22-59; hidden 64, 4 heads,
