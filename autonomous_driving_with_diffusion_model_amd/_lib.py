@@ -116,6 +116,7 @@ _SIGS = {
     "adx_conv2d_forward": (i32, [C.POINTER(Conv2dDesc), vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "adx_conv2d_cells_supported": (i32, [C.POINTER(Conv2dDesc), i32, i32, i32]),
     "adx_conv2d_forward_cells": (i32, [C.POINTER(Conv2dDesc), vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "adx_conv2d_stem_pool": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "adx_conv2d_wgrad_scratch_bytes": (C.c_size_t, []),
     "adx_conv2d_wgrad": (i32, [C.POINTER(Conv2dDesc), vp, vp, vp, i32, i32, i32, vp, vp]),
     "adx_conv2d_wgrad_ex": (i32, [C.POINTER(Conv2dDesc), vp, vp, vp, i32, i32, i32, vp, i32, vp]),

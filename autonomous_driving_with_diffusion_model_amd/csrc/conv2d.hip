@@ -542,6 +542,19 @@ int adx_conv2d_forward_cells(const adx_conv2d_desc* d, const void* x, const floa
                            (hipStream_t)stream, nullptr, 0, nullptr, 0, nullptr, fmt);
 }
 
+int adx_conv2d_stem_pool(const void* x, int32_t x_u8, const float* packed_w, const float* scale, const float* shift,
+                         const float* mean, const float* stdv, void* y, int32_t n, int32_t h, int32_t w, int32_t y_cells,
+                         adx_stream stream) {
+  ConvSpec L{};
+  L.cin = 3; L.cout = 64; L.k = 7; L.stride = 2; L.pad = 3; L.cc = 4; L.cin_pad = 4;
+  ADX_REQUIRE(x && packed_w && scale && shift && y, "adx_conv2d_stem_pool: null tensor");
+  ADX_REQUIRE(n >= 1 && h >= 1 && w >= 1, "adx_conv2d_stem_pool: bad shape %d x %d x %d", n, h, w);
+  ADX_REQUIRE(conv2d_hs_eligible(L), "adx_conv2d_stem_pool: the fused stem + pool is a split-fp16 kernel (unavailable with ADX_CONV_EXACT=1)");
+  ADX_REQUIRE(!x_u8 || (mean && stdv), "adx_conv2d_stem_pool: uint8 frames need mean / std");
+  return conv2d_hs_stem_pool(L, x_u8 ? nullptr : (const float*)x, packed_w, scale, shift, (float*)y, n, h, w, (hipStream_t)stream,
+                             x_u8 ? (const uint8_t*)x : nullptr, mean, stdv, y_cells ? 1 : 0);
+}
+
 int adx_resnet_create(int32_t out_dim, adx_resnet** out) {
   ADX_REQUIRE(out != nullptr && out_dim >= 1 && out_dim <= 4096, "adx_resnet_create: bad argument");
   adx_resnet* r = new adx_resnet();

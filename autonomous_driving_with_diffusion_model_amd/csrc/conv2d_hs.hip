@@ -1014,59 +1014,131 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
 // output pixel -- is then 8 CONSECUTIVE input columns of one patch row, i.e. 16 contiguous bytes of the fp16 patch
 // image [plane][channel][row][column] (read as 4 dwords: the start column 2*ox is only 4-byte aligned), and one
 // MFMA (K = 16) covers two combos.  11 k-steps x 3 products per 32x32 tile; 84 % of the k slots are real work.
-// One workgroup owns a band of 8 output rows of one image and walks its 32-column tiles: the 45 KB split weight
-// image is loaded into LDS once per band, the patch of tile i+1 is fetched while tile i is multiplied.
-// max with torch's NaN rule (a NaN in the window wins)
-__device__ __forceinline__ float pool_max3(float a, float b, float c) {
-  float m = a;
-  m = (b > m || b != b) ? b : m;
-  m = (c > m || c != c) ? c : m;
-  return m;
-}
-
+// Both stem kernels below share this layout, the weight image (conv2d_hs_stem_pack_kernel) and the k-step order, so
+// a stem value is bit for bit the same whichever of them computes it.
 constexpr int kStemSteps = 11;
 constexpr int kStemPP = 72;                               // patch row pitch in halves (70 columns are staged)
+constexpr int kStemPH = 21;                               // patch rows of a band of 8 stem rows
 
-// POOL = true additionally applies MaxPool2d(3, 2, 1) (modeling/resnet.py:197) before anything is written: the stem's
-// own output (944 MB at B=64, 3x256x900 -- the largest tensor of the network) is then never stored nor re-read.  A
-// workgroup produces a band of 4 pooled rows, one per wave: the wave multiplies the three stem rows of its pooled
-// row one after the other (64 accumulators each, folded into a running maximum), so the vertical maximum needs no
-// exchange at the price of computing the shared odd rows twice (+50 % MFMAs, still cheaper than the traffic it
-// removes); the horizontal maximum takes the neighbouring lanes (shuffles) and, at a tile's left edge, the last
-// column of the previous tile (parked in LDS while the workgroup walks its band).  One patch copy (the next tile
-// waits in registers), so two workgroups still fit a CU.
-template <bool POOL, bool U8>
+// One 32x32x(64 channels) stem tile of one stem row (patch row prow of the staged band), accumulated in the k-step order
+// that both stem kernels share: the fragments of step s+1 are read under the MFMAs of step s.
+struct StemFrags { f16x8 A[2][2], B[2]; };
+__device__ __forceinline__ void stem_tile(const u32x4* wa0, const uint32_t* pb0, int khalf, f32x16 (&accm)[2], f32x16 (&accl)[2]) {
+  constexpr int CP = kStemPH * kStemPP, PLANEH = 3 * CP;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { accm[m][i] = 0.f; accl[m][i] = 0.f; }
+  auto fetch = [&](StemFrags& f, int step) {
+    // this lane's (channel, kernel row): combo 2*step + khalf; the 22nd combo has zero weights, re-reads the 21st
+    const int c0 = 2 * step, c1 = 2 * step + 1 > 20 ? 20 : 2 * step + 1;
+    const int off0 = ((c0 / 7) * CP + (c0 % 7) * kStemPP) / 2, off1 = ((c1 / 7) * CP + (c1 % 7) * kStemPP) / 2;
+    const uint32_t* pb = pb0 + (khalf ? off1 : off0);
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m) f.A[pl][m] = __builtin_bit_cast(f16x8, wa0[(step * 2 + pl) * 128 + m * 32]);
+      const uint32_t* q = pb + pl * (PLANEH / 2);
+      u32x4 v;
+      v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+      f.B[pl] = __builtin_bit_cast(f16x8, v);
+    }
+  };
+  StemFrags fr[2];
+  fetch(fr[0], 0);
+#pragma unroll
+  for (int step = 0; step < kStemSteps; ++step) {
+    if (step + 1 < kStemSteps) fetch(fr[(step + 1) & 1], step + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    const StemFrags& f = fr[step & 1];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      accm[m] = hs_mfma(f.A[0][m], f.B[0], accm[m]);
+      accl[m] = hs_mfma(f.A[0][m], f.B[1], accl[m]);
+      accl[m] = hs_mfma(f.A[1][m], f.B[0], accl[m]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// The band's patch: 3 channels x kStemPH rows x 35 column pairs, split into [plane][channel][row][pitch] halves.  Thread t < 245
+// owns column pair t % 35 of the rows (channel, row) = t / 35 + 7 k, k < 9: its geometry costs one division per thread, not one
+// per cell, and a cell's (channel, row) is two compares off its k (no chain of dependent address updates).
+constexpr int kStemStageItems = 3 * kStemPH / 7;
+template <bool U8>
+struct StemStager {
+  float pv[kStemStageItems][2];
+  __device__ __forceinline__ void load(const Conv2dArgs& a, __amdgpu_buffer_rsrc_t xrsrc, int r0, int ix, int iy0) {
+    constexpr uint32_t kOutside = 0xC0000000u;
+    const bool act = r0 < 7;
+    const bool ok0 = act && ix >= 0 && ix < a.W, ok1 = act && ix + 1 >= 0 && ix + 1 < a.W;
+    const size_t hw = (size_t)a.H * a.W;
+#pragma unroll
+    for (int k = 0; k < kStemStageItems; ++k) {
+      const int rc = r0 + 7 * k;
+      const int c = (rc >= kStemPH) + (rc >= 2 * kStemPH), iy = iy0 + rc - kStemPH * c;
+      const bool rok = iy >= 0 && iy < a.H;
+      const bool v0 = rok && ok0, v1 = rok && ok1;
+      if (U8) {
+        // uint8 HWC frame: byte (iy, ix, c); outside the frame the NORMALISED tensor is zero-padded, so the value is 0
+        // there, not normalise(0).  Same operation order as image_normalize_kernel (IEEE division, no contraction).
+#pragma clang fp contract(off)
+        const uint32_t brow = (uint32_t)(iy * a.W) * 3u + (uint32_t)c;
+        const uint32_t b0 = __builtin_amdgcn_raw_buffer_load_b8(xrsrc, v0 ? brow + (uint32_t)ix * 3u : kOutside, 0, 0);
+        const uint32_t b1 = __builtin_amdgcn_raw_buffer_load_b8(xrsrc, v1 ? brow + (uint32_t)(ix + 1) * 3u : kOutside, 0, 0);
+        const float mean = c == 0 ? a.u8_mean[0] : (c == 1 ? a.u8_mean[1] : a.u8_mean[2]);
+        const float stdv = c == 0 ? a.u8_std[0] : (c == 1 ? a.u8_std[1] : a.u8_std[2]);
+        pv[k][0] = v0 ? ((float)b0 / 255.0f - mean) / stdv : 0.f;
+        pv[k][1] = v1 ? ((float)b1 / 255.0f - mean) / stdv : 0.f;
+      } else {
+        const uint32_t grow = (uint32_t)(c * (int)hw + iy * a.W) * 4u;
+        pv[k][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, v0 ? grow + (uint32_t)ix * 4u : kOutside, 0, 0));
+        pv[k][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, v1 ? grow + (uint32_t)(ix + 1) * 4u : kOutside, 0, 0));
+      }
+    }
+  }
+  __device__ __forceinline__ void store(uint32_t* pd, int r0, int pp) const {
+    constexpr int PLANEH = 3 * kStemPH * kStemPP;
+    if (r0 >= 7) return;
+#pragma unroll
+    for (int k = 0; k < kStemStageItems; ++k) {
+      f16x2 h, l;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const _Float16 hj = (_Float16)pv[k][j];
+        h[j] = hj;
+        l[j] = (_Float16)((pv[k][j] - (float)hj) * kLoScale);
+      }
+      // (channel, row) r0 + 7 k is row r0 + 7 k of the [channel][row] stack: the pitch is uniform across channels
+      const int dw = ((r0 + 7 * k) * kStemPP) / 2 + pp;
+      pd[dw] = __builtin_bit_cast(uint32_t, h);
+      pd[PLANEH / 2 + dw] = __builtin_bit_cast(uint32_t, l);
+    }
+  }
+};
+
+// The plain stem (training forward, ops.conv2d at k = 7): one workgroup owns a band of 8 output rows of one image and walks
+// its 32-column tiles; wave w computes rows 2 w, 2 w + 1.  The 45 KB split weight image is loaded into LDS once per band,
+// the patch of tile i+1 is fetched while tile i is multiplied (two patch copies).
 __global__ void __launch_bounds__(256, 2) conv2d_hs_stem_kernel(const Conv2dArgs a) {
-  constexpr int NT = 256;
-  constexpr int PH = POOL ? 25 : 21;                       // patch rows (9 / 8 stem rows)
-  constexpr int PBUF = POOL ? 1 : 2;
-  constexpr int CP = PH * kStemPP;                         // halves per channel plane
+  constexpr int CP = kStemPH * kStemPP;                    // halves per channel plane
   constexpr int PLANEH = 3 * CP;                           // halves per split plane
-  constexpr int ITEMS = 3 * PH * 35;                       // (channel, row, column pair) cells per tile
-  constexpr int PIT = (ITEMS + NT - 1) / NT;
-  constexpr int NROW = POOL ? 3 : 1;                       // passes per tile: stem rows folded into one pooled row
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   u32x4* wl = reinterpret_cast<u32x4*>(smem_raw);                         // [step][plane][k-half][64]
-  uint32_t* patch = reinterpret_cast<uint32_t*>(wl + kStemSteps * 256);   // PBUF x [plane][channel][row][pitch/2] dwords
-  float* ss = reinterpret_cast<float*>(patch + PBUF * PLANEH);            // a buffer = 2 planes x PLANEH/2 dwords
+  uint32_t* patch = reinterpret_cast<uint32_t*>(wl + kStemSteps * 256);   // 2 x [plane][channel][row][pitch/2] dwords
+  float* ss = reinterpret_cast<float*>(patch + 2 * PLANEH);               // a buffer = 2 planes x PLANEH/2 dwords
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, khalf = lane >> 5;
   int bid = blockIdx.x, seg = 0;
   if (a.stem_nseg > 1) { seg = bid % a.stem_nseg; bid /= a.stem_nseg; }
   const int n = bid / a.tiles_y, ty = bid - n * a.tiles_y;
-  // this workgroup's tiles [tx_own, tx_end); with the pooling fused in, a segment that does not start at the left edge
-  // first computes the tile before it without storing anything: the pool's left neighbour column comes from there
-  const int tx_own = a.stem_nseg > 1 ? seg * a.stem_seg_tiles : 0;
-  const int tx_end = a.stem_nseg > 1 ? min(a.tiles_x, tx_own + a.stem_seg_tiles) : a.tiles_x;
-  const int tx_begin = POOL && tx_own > 0 ? tx_own - 1 : tx_own;
-  const int oy0 = POOL ? ty * 8 - 1 : ty * 8, iy0 = oy0 * 2 - 3;          // first stem row of the band
+  const int tx_begin = a.stem_nseg > 1 ? seg * a.stem_seg_tiles : 0;
+  const int tx_end = a.stem_nseg > 1 ? min(a.tiles_x, tx_begin + a.stem_seg_tiles) : a.tiles_x;
+  const int oy0 = ty * 8, iy0 = oy0 * 2 - 3;               // first stem row of the band
   const size_t hw = (size_t)a.H * a.W;
-  const float* xin = a.x + (size_t)n * 3 * hw;
-  constexpr uint32_t kOutside = 0xC0000000u;
   const __amdgpu_buffer_rsrc_t xrsrc =
-      U8 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.x_u8 + (size_t)n * 3 * hw), 0, (int)(3 * hw), 0x00020000)
-         : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xin), 0, (int)(3 * hw * sizeof(float)), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x + (size_t)n * 3 * hw), 0, (int)(3 * hw * sizeof(float)), 0x00020000);
 
   {
     const u32x4* wsrc = reinterpret_cast<const u32x4*>(a.w);
@@ -1077,80 +1149,143 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_stem_kernel(const Conv2dArgs
     const int c = tid & (kHsCout - 1);
     ss[tid] = a.scale == nullptr ? (tid < kHsCout ? 1.f : 0.f) : (tid < kHsCout ? a.scale[c] : a.shift[c]);
   }
-  // POOL: vertical maxima of the previous tile's last column (left neighbour of lane 0): [wave][32 registers][k-half]
-  float* cbuf = ss + 2 * kHsCout + wave * 64 + khalf;
-  float* cpark = l31 == 31 ? cbuf : ss + 2 * kHsCout + 4 * 64 + (lane & 1);   // 64 dummy words behind the four waves' columns
-  if (POOL && l31 == 0) {
-#pragma unroll
-    for (int i = 0; i < 32; ++i) cbuf[2 * i] = -INFINITY;
-  }
-
-  // cell k of this thread: (channel, patch row, column pair); its geometry is recomputed where it is used (a few
-  // integer ops per tile) instead of living in registers beside the accumulators
-  auto decode = [&](int k, int& c, int& py, int& pp) {
-    int e = tid + NT * k;
-    asm volatile("" : "+v"(e));    // opaque: otherwise the geometry is hoisted out of the tile loop and spilled
-    c = e / (PH * 35);
-    const int rem = e - c * (PH * 35);
-    py = rem / 35;
-    pp = rem - py * 35;
-  };
-  float pv[PIT][2];
-  auto load_p = [&](int tx) {
-    const int ix0 = tx * 64 - 3;
-#pragma unroll
-    for (int k = 0; k < PIT; ++k) {
-      int c, py, pp;
-      decode(k, c, py, pp);
-      const int ix = ix0 + 2 * pp, iy = iy0 + py;
-      const bool rok = tid + NT * k < ITEMS && iy >= 0 && iy < a.H;
-      const bool ok0 = rok && ix >= 0 && ix < a.W, ok1 = rok && ix + 1 >= 0 && ix + 1 < a.W;
-      if (U8) {
-        // uint8 HWC frame: byte (iy, ix, c); outside the frame the NORMALISED tensor is zero-padded, so the value is 0
-        // there, not normalise(0).  Same operation order as image_normalize_kernel (IEEE division, no contraction).
-#pragma clang fp contract(off)
-        const uint32_t brow = (uint32_t)(iy * a.W) * 3u + (uint32_t)c;
-        const uint32_t b0 = __builtin_amdgcn_raw_buffer_load_b8(xrsrc, ok0 ? brow + (uint32_t)ix * 3u : kOutside, 0, 0);
-        const uint32_t b1 = __builtin_amdgcn_raw_buffer_load_b8(xrsrc, ok1 ? brow + (uint32_t)(ix + 1) * 3u : kOutside, 0, 0);
-        const float mean = c == 0 ? a.u8_mean[0] : (c == 1 ? a.u8_mean[1] : a.u8_mean[2]);
-        const float stdv = c == 0 ? a.u8_std[0] : (c == 1 ? a.u8_std[1] : a.u8_std[2]);
-        pv[k][0] = ok0 ? ((float)b0 / 255.0f - mean) / stdv : 0.f;
-        pv[k][1] = ok1 ? ((float)b1 / 255.0f - mean) / stdv : 0.f;
-      } else {
-        const uint32_t grow = (uint32_t)(c * (int)hw + iy * a.W) * 4u;
-        pv[k][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, ok0 ? grow + (uint32_t)ix * 4u : kOutside, 0, 0));
-        pv[k][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrsrc, ok1 ? grow + (uint32_t)(ix + 1) * 4u : kOutside, 0, 0));
-      }
-    }
-  };
-  auto store_p = [&](int buf) {
-    uint32_t* pd = patch + buf * PLANEH;
-#pragma unroll
-    for (int k = 0; k < PIT; ++k) {
-      if (PIT * NT == ITEMS || tid + NT * k < ITEMS) {
-        f16x2 h, l;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const _Float16 hj = (_Float16)pv[k][j];
-          h[j] = hj;
-          l[j] = (_Float16)((pv[k][j] - (float)hj) * kLoScale);
-        }
-        int c, py, pp;
-        decode(k, c, py, pp);
-        const int dw = (c * CP + py * kStemPP) / 2 + pp;
-        pd[dw] = __builtin_bit_cast(uint32_t, h);
-        pd[PLANEH / 2 + dw] = __builtin_bit_cast(uint32_t, l);
-      }
-    }
-  };
-
+  const int r0 = tid / 35, pp = tid - r0 * 35;              // staging geometry (StemStager)
+  StemStager<false> sg;
   const u32x4* wa0 = wl + khalf * 64 + l31;
-  // output geometry: the stem map (a.OH x a.OW) or, pooled, its MaxPool2d(3, 2, 1) image
-  const int PHo = POOL ? (a.OH - 1) / 2 + 1 : a.OH, PWo = POOL ? (a.OW - 1) / 2 + 1 : a.OW;
-  const size_t img = (size_t)n * a.Cout * PHo * PWo;
+  const size_t img = (size_t)n * a.Cout * a.OH * a.OW;
   // stores through a buffer descriptor: channel offset in an SGPR, the lane's pixel in one VGPR (out of range = dropped)
+  const uint32_t plane_ob = (uint32_t)(a.OH * a.OW) * (uint32_t)sizeof(float);
+  const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(a.y + img, 0, (int)(a.Cout * plane_ob), 0x00020000);
+  constexpr uint32_t kOutside = 0xC0000000u;
+
+  sg.load(a, xrsrc, r0, tx_begin * 64 - 3 + 2 * pp, iy0);
+  sg.store(patch + (tx_begin & 1) * PLANEH, r0, pp);
+  __syncthreads();
+  for (int tx = tx_begin; tx < tx_end; ++tx) {
+    if (tx + 1 < tx_end) sg.load(a, xrsrc, r0, (tx + 1) * 64 - 3 + 2 * pp, iy0);
+    const int ox = tx * kTileW + l31;
+    // both rows of the wave in one pass: the A fragments of a k-step serve four products each
+    const uint32_t* pb0 = patch + (tx & 1) * PLANEH + wave * 4 * (kStemPP / 2) + l31;
+    f32x16 accm[2][2], accl[2][2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { accm[r][m][i] = 0.f; accl[r][m][i] = 0.f; }
+#pragma unroll 1
+    for (int step = 0; step < kStemSteps; ++step) {
+      const int c0 = 2 * step, c1 = 2 * step + 1 > 20 ? 20 : 2 * step + 1;     // as stem_tile
+      const int off0 = ((c0 / 7) * CP + (c0 % 7) * kStemPP) / 2, off1 = ((c1 / 7) * CP + (c1 % 7) * kStemPP) / 2;
+      const uint32_t* pb = pb0 + (khalf ? off1 : off0);
+      f16x8 A[2][2], B[2][2];
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) A[pl][m] = __builtin_bit_cast(f16x8, wa0[(step * 2 + pl) * 128 + m * 32]);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const uint32_t* q = pb + pl * (PLANEH / 2) + r * 2 * (kStemPP / 2);
+          u32x4 v;
+          v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+          B[pl][r] = __builtin_bit_cast(f16x8, v);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          accm[r][m] = hs_mfma(A[0][m], B[0][r], accm[r][m]);
+          accl[r][m] = hs_mfma(A[0][m], B[1][r], accl[r][m]);
+          accl[r][m] = hs_mfma(A[1][m], B[0][r], accl[r][m]);
+        }
+    }
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      const int oy = oy0 + wave * 2 + rr;
+      const uint32_t voff = (oy < a.OH && ox < a.OW) ? (uint32_t)(oy * a.OW + ox) * 4u + (uint32_t)(4 * khalf) * plane_ob : kOutside;
+#pragma unroll
+      for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int cu = half * 32 + (r & 3) + 8 * (r >> 2);
+          const int cl = cu + 4 * khalf;
+          float v = accm[rr][half][r] + accl[rr][half][r] * (1.f / kLoScale);
+          v = v * ss[cl] + ss[kHsCout + cl];
+          if (a.relu) v = v > 0.f ? v : 0.f;
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), yrsrc, voff, cu * plane_ob, 0);
+        }
+    }
+    if (tx + 1 < tx_end) sg.store(patch + ((tx + 1) & 1) * PLANEH, r0, pp);
+    __syncthreads();
+  }
+}
+
+// The stem + BN + ReLU + MaxPool2d(3, 2, 1) (modeling/resnet.py:197) in one launch: only the pooled map is written, the
+// stem's own output (944 MB at B = 64, 3x256x900 -- the largest tensor of the network) is never stored nor re-read.
+// Every stem row is computed ONCE.  A workgroup owns a strip of 32 stem columns of one image and walks it down in bands
+// of 8 stem rows = 4 pooled rows; wave w computes stem rows 2p and 2p + 1 of pooled row p = 4 band + w.
+//  * horizontally a strip's columns are 30 tx - 1 .. 30 tx + 30 (neighbouring strips overlap by two columns): pooled
+//    column 15 tx + i is the maximum over lanes 2i, 2i + 1, 2i + 2 of one 32-lane group, taken with two DPP shifts before
+//    anything leaves the registers.  450 stem columns are 15 strips of 30, as many MFMA columns as 32-column tiles had;
+//  * vertically pooled row p also needs stem row 2p - 1: the odd row of wave w - 1, or for wave 0 the odd row of the
+//    previous band's wave 3.  Each wave parks its odd row's horizontal maxima (15 columns x 64 channels) in LDS; after
+//    one barrier wave w >= 1 folds in wave w - 1's, and wave 0 takes wave 3's as the start of its next row.  A walk that
+//    does not start at the top (few images: the strip is cut into segments) first computes only the odd rows of the band
+//    in front of it.
+// Every value that reaches a maximum is >= 0 or the padding's -inf (the ReLU maps a NaN stem value to 0, as `v > 0 ? v : 0`
+// does), so the maxima are plain v_max / v_max3: torch's rule that a NaN in the window wins has nothing to decide.
+// One patch copy: the next band is fetched into registers under the MFMAs and split into LDS behind the exchange barrier,
+// so the walk costs two barriers per band.  45 KB weights + 18 KB patch + 16 KB exchange: two workgroups per CU.
+constexpr int kStemPoolCols = 15;            // pooled columns per strip
+template <bool U8>
+__global__ void __launch_bounds__(256, 2) conv2d_hs_stem_pool_kernel(const Conv2dArgs a) {
+  constexpr int PLANEH = 3 * kStemPH * kStemPP;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  u32x4* wl = reinterpret_cast<u32x4*>(smem_raw);                         // [step][plane][k-half][64]
+  uint32_t* patch = reinterpret_cast<uint32_t*>(wl + kStemSteps * 256);   // [plane][channel][row][pitch/2] dwords
+  float* ss = reinterpret_cast<float*>(patch + PLANEH);
+  float* xch = ss + 2 * kHsCout;                                          // [wave][32 registers][k-half][16 pooled columns]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, khalf = lane >> 5;
+  int bid = blockIdx.x, seg = 0;
+  if (a.stem_nseg > 1) { seg = bid % a.stem_nseg; bid /= a.stem_nseg; }
+  const int n = bid / a.tiles_x, tx = bid - n * a.tiles_x;
+  const int b_own = a.stem_nseg > 1 ? seg * a.stem_seg_tiles : 0;
+  const int b_end = a.stem_nseg > 1 ? min(a.tiles_y, b_own + a.stem_seg_tiles) : a.tiles_y;
+  const int b_begin = b_own > 0 ? b_own - 1 : 0;
+  const int sx0 = tx * 2 * kStemPoolCols - 1;               // the strip's first stem column
+  const size_t hw = (size_t)a.H * a.W;
+  const __amdgpu_buffer_rsrc_t xrsrc =
+      U8 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.x_u8 + (size_t)n * 3 * hw), 0, (int)(3 * hw), 0x00020000)
+         : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x + (size_t)n * 3 * hw), 0, (int)(3 * hw * sizeof(float)), 0x00020000);
+
+  {
+    const u32x4* wsrc = reinterpret_cast<const u32x4*>(a.w);
+#pragma unroll
+    for (int k = 0; k < kStemSteps; ++k) wl[tid + 256 * k] = wsrc[tid + 256 * k];
+  }
+  if (tid < 2 * kHsCout) {
+    const int c = tid & (kHsCout - 1);
+    ss[tid] = a.scale == nullptr ? (tid < kHsCout ? 1.f : 0.f) : (tid < kHsCout ? a.scale[c] : a.shift[c]);
+  }
+  const int r0 = tid / 35, pp = tid - r0 * 35;              // staging geometry (StemStager)
+  const int ix = 2 * sx0 - 3 + 2 * pp;
+  StemStager<U8> sg;
+  const u32x4* wa0 = wl + khalf * 64 + l31;
+  const uint32_t* pb0 = patch + wave * 4 * (kStemPP / 2) + l31;           // stem row 2 w of the band: patch row 4 w
+
+  const int PHo = (a.OH - 1) / 2 + 1, PWo = (a.OW - 1) / 2 + 1;
+  const size_t img = (size_t)n * a.Cout * PHo * PWo;
   const uint32_t plane_ob = (uint32_t)(PHo * PWo) * (uint32_t)sizeof(float);
   const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(a.y + img, 0, (int)(a.Cout * plane_ob), 0x00020000);
+  constexpr uint32_t kOutside = 0xC0000000u;
+  const int sx = sx0 + l31, pq = tx * kStemPoolCols + (l31 >> 1);
+  const bool col_in = sx >= 0 && sx < a.OW;
+  const bool col_st = (l31 & 1) != 0 && l31 < 2 * kStemPoolCols && pq < PWo;   // lane 2i + 1: centre of pooled column i
+  // this lane's exchange word of register 0 in wave w's slot: + w * 1024, register j at + 32 j
+  float* xl = xch + khalf * 16 + (l31 >> 1);
 
 #ifdef ADX_HS_TRACE
   // phase totals of this workgroup (tools/stem_trace.py); its records sit behind those of the 3x3 kernel
@@ -1158,169 +1293,100 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_stem_kernel(const Conv2dArgs
   unsigned long long* tr = g_hs_trace + (size_t)(8192 + (blockIdx.x & 8191)) * 8;
   if (threadIdx.x == 0) tr[0] = __builtin_readcyclecounter();
 #endif
-  load_p(tx_begin);
-  store_p(PBUF == 2 ? tx_begin & 1 : 0);
+  sg.load(a, xrsrc, r0, ix, b_begin * 16 - 3);
+  sg.store(patch, r0, pp);
   __syncthreads();
 #ifdef ADX_HS_TRACE
   if (threadIdx.x == 0) tr[1] = __builtin_readcyclecounter();
 #endif
-  for (int tx = tx_begin; tx < tx_end; ++tx) {
+  float vm[32];                       // running maximum of this wave's pooled row (wave 0: carried in from the band above)
+#pragma unroll
+  for (int j = 0; j < 32; ++j) vm[j] = -INFINITY;
+  for (int b = b_begin; b < b_end; ++b) {
 #ifdef ADX_HS_TRACE
     tr_t = (long long)__builtin_readcyclecounter();
 #endif
-    if (tx + 1 < tx_end) load_p(tx + 1);
-    const int ox = tx * kTileW + l31;
-    float vm[2][16];                 // POOL: running vertical maximum of this wave's pooled row
-#pragma unroll 1
-    for (int pass = 0; pass < NROW; ++pass) {
-      // stem rows of this pass: POOL: row 2 (4 ty + w) - 1 + pass (one row); else rows 8 ty + 2 w, + 1
-      const int prow = POOL ? (2 * wave + pass) * 2 : wave * 2 * 2;     // first patch row
-      const uint32_t* pb0 = patch + (PBUF == 2 ? (tx & 1) * PLANEH : 0) + prow * (kStemPP / 2) + l31;
-      constexpr int NR = POOL ? 1 : 2;
-      f32x16 accm[NR][2], accl[NR][2];
-#pragma unroll
-      for (int r = 0; r < NR; ++r)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) { accm[r][m][i] = 0.f; accl[r][m][i] = 0.f; }
-      struct Frags { f16x8 A[2][2], B[2][NR]; };
-      auto fetch = [&](Frags& f, int step) {
-        // this lane's (channel, kernel row): combo 2*step + khalf; the 22nd combo has zero weights, re-reads the 21st
-        const int c0 = 2 * step, c1 = 2 * step + 1 > 20 ? 20 : 2 * step + 1;
-        const int off0 = ((c0 / 7) * CP + (c0 % 7) * kStemPP) / 2, off1 = ((c1 / 7) * CP + (c1 % 7) * kStemPP) / 2;
-        const uint32_t* pb = pb0 + (khalf ? off1 : off0);
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-#pragma unroll
-          for (int m = 0; m < 2; ++m) f.A[pl][m] = __builtin_bit_cast(f16x8, wa0[(step * 2 + pl) * 128 + m * 32]);
-#pragma unroll
-          for (int r = 0; r < NR; ++r) {
-            const uint32_t* q = pb + pl * (PLANEH / 2) + r * 2 * (kStemPP / 2);
-            u32x4 v;
-            v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
-            f.B[pl][r] = __builtin_bit_cast(f16x8, v);
-          }
-        }
-      };
-      auto mfmas = [&](const Frags& f) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-#pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            accm[r][m] = hs_mfma(f.A[0][m], f.B[0][r], accm[r][m]);
-            accl[r][m] = hs_mfma(f.A[0][m], f.B[1][r], accl[r][m]);
-            accl[r][m] = hs_mfma(f.A[1][m], f.B[0][r], accl[r][m]);
-          }
-      };
-      if (POOL) {
-        // one stem row per pass = 6 MFMAs per k-step: the fragments of step s+1 are read under the MFMAs of step s
-        // (with the 128 accumulators of the two-row variant the second fragment set does not fit: it spills)
-        Frags fr[2];
-        fetch(fr[0], 0);
-#pragma unroll
-        for (int step = 0; step < kStemSteps; ++step) {
-          if (step + 1 < kStemSteps) fetch(fr[(step + 1) & 1], step + 1);
-          __builtin_amdgcn_sched_barrier(0);
-          mfmas(fr[step & 1]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      } else {
-#pragma unroll 1
-        for (int step = 0; step < kStemSteps; ++step) {
-          Frags f;
-          fetch(f, step);
-          mfmas(f);
-        }
-      }
-      if (!POOL) {
-#pragma unroll
-        for (int rr = 0; rr < NR; ++rr) {
-          const int oy = oy0 + wave * 2 + rr;
-          const uint32_t voff = (oy < a.OH && ox < a.OW) ? (uint32_t)(oy * a.OW + ox) * 4u + (uint32_t)(4 * khalf) * plane_ob : kOutside;
-#pragma unroll
-          for (int half = 0; half < 2; ++half)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int cu = half * 32 + (r & 3) + 8 * (r >> 2);
-              const int cl = cu + 4 * khalf;
-              float v = accm[rr][half][r] + accl[rr][half][r] * (1.f / kLoScale);
-              v = v * ss[cl] + ss[kHsCout + cl];
-              if (a.relu) v = v > 0.f ? v : 0.f;
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), yrsrc, voff, cu * plane_ob, 0);
-            }
-        }
-      } else {
-        // BN + ReLU; rows / columns outside the stem map are the pool's padding
-        const int oy = oy0 + 2 * wave + pass;
-        const bool in = oy >= 0 && oy < a.OH && ox < a.OW;
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int cl = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-            float t = (accm[0][half][r] + accl[0][half][r] * (1.f / kLoScale)) * ss[cl] + ss[kHsCout + cl];
-            if (a.relu) t = t > 0.f ? t : 0.f;
-            t = in ? t : -INFINITY;
-            vm[half][r] = pass == 0 ? t : pool_max3(vm[half][r], t, -INFINITY);
-          }
-      }
-    }
-#ifdef ADX_HS_TRACE
-    { const long long t = (long long)__builtin_readcyclecounter(); tr_c += t - tr_t; tr_t = t; }
-#endif
-    if (POOL) {
-      // horizontal: pooled column 16 tx + i sits on lane 2 i; left neighbour of lane 0 = previous tile's lane 31
-      const int pr = ty * 4 + wave, pq = tx * 16 + (l31 >> 1);
-      const bool st = pr < PHo && (l31 & 1) == 0 && pq < PWo && tx >= tx_own;
-      const uint32_t voff = st ? (uint32_t)(pr * PWo + pq) * 4u + (uint32_t)(4 * khalf) * plane_ob : kOutside;
-      float mm[2][16];          // a.y_cells: the pooled values, stored as cells below
-      // the previous tile's last column (written by lane 31 one tile ago): all 32 values in flight at once, read by EVERY lane
-      // (a broadcast; only lane 0 of a 32-lane group uses them).  As `l31 == 0 ? cbuf[..] : up` each read sat in a branch of its
-      // own with a full LDS round trip behind it, 32 times per tile (round 6: 550 -> 516 us per launch at B = 64; stepping the
-      // staging geometry from cell to cell instead of dividing per cell, tried with it, costs +24 %: profiles/README.md)
-      float lf[2][16];
-#pragma unroll
-      for (int half = 0; half < 2; ++half)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lf[half][r] = cbuf[2 * (half * 16 + r)];
+    const bool pre = b < b_own;       // the band in front of a segment: only its last odd row is wanted
+    if (b + 1 < b_end) sg.load(a, xrsrc, r0, ix, (b + 1) * 16 - 3);
+    // one stem row: the even one (rr = 0), then the odd one (rr = 1: also parked for pooled row p + 1).  Two straight-line
+    // copies: a runtime rr splits the epilogue at every parked value and serialises its LDS reads.
+    auto stem_row = [&](auto odd) {
+      constexpr int rr = decltype(odd)::value ? 1 : 0;
+      f32x16 accm[2], accl[2];
+      stem_tile(wa0, pb0 + rr * 2 * (kStemPP / 2), khalf, accm, accl);
+      // BN + ReLU; rows / columns outside the stem map are the pool's padding; then the horizontal maximum.  ReLU and padding as
+      // min(max(t, 0), hi) with hi = +inf inside, -inf outside (v_max returns 0 for a NaN t)
+      const int oy = b * 8 + 2 * wave + rr;
+      const float hi = oy < a.OH && col_in ? INFINITY : -INFINITY;
+      float hv[32];
 #pragma unroll
       for (int half = 0; half < 2; ++half)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          // neighbours by DPP wavefront shifts (one VALU op each; the 32-lane groups' ends are overridden below)
-          const int vi = __builtin_bit_cast(int, vm[half][r]);
-          const float up = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, vi, 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-          const float dn = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, vi, 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
-          const float left = l31 == 0 ? lf[half][r] : up;
-          const float right = l31 == 31 ? -INFINITY : dn;
-          const float m = pool_max3(left, vm[half][r], right);
-          cpark[2 * (half * 16 + r)] = vm[half][r];      // lane 31 parks its column for the next tile, the others hit a dummy row
-          mm[half][r] = m;
+          const int cl = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+          float t = (accm[half][r] + accl[half][r] * (1.f / kLoScale)) * ss[cl] + ss[kHsCout + cl];
+          t = __builtin_fminf(__builtin_fmaxf(t, 0.f), hi);
+          // neighbours by DPP wavefront shifts; lanes whose shift crosses a 32-lane group are not pooled-column centres
+          const int ti = __builtin_bit_cast(int, t);
+          const float left = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(ti, 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
+          const float right = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(ti, 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
+          const int j = half * 16 + r;
+          hv[j] = __builtin_fmaxf(__builtin_fmaxf(left, t), right);
+          vm[j] = __builtin_fmaxf(vm[j], hv[j]);
         }
-      if (!a.y_cells) {         // (one uniform branch around all 32 stores, not one per value)
+      if constexpr (rr == 1) {        // the odd row, for pooled row p + 1: written by the pooled-column centres
+        if (l31 & 1) {
 #pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int cu = half * 32 + (r & 3) + 8 * (r >> 2);       // + 4 * khalf, which rides in voff
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, mm[half][r]), yrsrc, voff, cu * plane_ob, 0);
-          }
-      } else {          // the pooled map as a cell tensor (conv2d_hs3x3_kernel: XCELLS): layer1's first conv copies cells
-        const uint32_t cplane = (uint32_t)(PHo * PWo) * 16u;
-        const uint32_t vcell = st ? (uint32_t)(pr * PWo + pq) * 16u + (uint32_t)khalf * 2u * cplane : kOutside;
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-          cells_store32<false>(mm[half], nullptr, nullptr, 0, nullptr, false, yrsrc, vcell, (uint32_t)(half * 4) * 2u * cplane, cplane);
+          for (int j = 0; j < 32; ++j) xl[wave * 1024 + 32 * j] = hv[j];
+        }
       }
+    };
+    if (!pre) stem_row(std::false_type{});
+    stem_row(std::true_type{});
+#ifdef ADX_HS_TRACE
+    { const long long t = (long long)__builtin_readcyclecounter(); tr_c += t - tr_t; tr_t = t; }
+#endif
+    __syncthreads();                  // odd rows parked; every wave is done with the patch
+    {
+      const float* src = xl + ((wave + 3) & 3) * 1024;
+      float up[32];
+#pragma unroll
+      for (int j = 0; j < 32; ++j) up[j] = src[32 * j];
+      if (wave != 0) {
+#pragma unroll
+        for (int j = 0; j < 32; ++j) vm[j] = __builtin_fmaxf(up[j], vm[j]);
+      }
+      const int pr = b * 4 + wave;
+      if (!pre && pr < PHo) {
+        const bool st = col_st;
+        if (!a.y_cells) {
+          const uint32_t voff = st ? (uint32_t)(pr * PWo + pq) * 4u + (uint32_t)(4 * khalf) * plane_ob : kOutside;
+#pragma unroll
+          for (int half = 0; half < 2; ++half)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int cu = half * 32 + (r & 3) + 8 * (r >> 2);       // + 4 * khalf, which rides in voff
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, vm[half * 16 + r]), yrsrc, voff, cu * plane_ob, 0);
+            }
+        } else {      // the pooled map as a cell tensor (conv2d_hs3x3_kernel: XCELLS): layer1's first conv copies cells
+          const uint32_t cplane = (uint32_t)(PHo * PWo) * 16u;
+          const uint32_t vcell = st ? (uint32_t)(pr * PWo + pq) * 16u + (uint32_t)khalf * 2u * cplane : kOutside;
+#pragma unroll
+          for (int half = 0; half < 2; ++half) {
+            float mm[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mm[r] = vm[half * 16 + r];
+            cells_store32<false>(mm, nullptr, nullptr, 0, nullptr, false, yrsrc, vcell, (uint32_t)(half * 4) * 2u * cplane, cplane);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 32; ++j) vm[j] = wave == 0 ? up[j] : -INFINITY;
     }
 #ifdef ADX_HS_TRACE
     { const long long t = (long long)__builtin_readcyclecounter(); tr_e += t - tr_t; tr_t = t; }
 #endif
-    if (tx + 1 < tx_end) {
-      if (PBUF == 1) __syncthreads();        // every wave is done with the only patch copy
-      store_p(PBUF == 2 ? (tx + 1) & 1 : 0);
-    }
+    if (b + 1 < b_end) sg.store(patch, r0, pp);
     __syncthreads();
 #ifdef ADX_HS_TRACE
     { const long long t = (long long)__builtin_readcyclecounter(); tr_s += t - tr_t; tr_t = t; }
@@ -1489,21 +1555,18 @@ static int hs_launch_t(Conv2dArgs a, hipStream_t s) {
   return ADX_OK;
 }
 
-template <bool POOL, bool U8 = false>
 static int hs_stem_launch(Conv2dArgs a, hipStream_t s) {
-  constexpr int PH = POOL ? 25 : 21, PBUF = POOL ? 1 : 2;
-  constexpr size_t lds = (size_t)kStemSteps * 4096 + (size_t)PBUF * 4 * 3 * PH * kStemPP + 2 * kHsCout * sizeof(float) +
-                         (POOL ? (4 * 64 + 2) * sizeof(float) : 0);     // parked columns + the dummy words of the other lanes
+  constexpr size_t lds = (size_t)kStemSteps * 4096 + (size_t)2 * 4 * 3 * kStemPH * kStemPP + 2 * kHsCout * sizeof(float);
   static_assert(lds <= 80 * 1024, "two workgroups per CU need <= 80 KB each");
   static std::atomic<uint64_t> attr{0};
   if (DeviceOnce once{attr}; once) {
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs_stem_kernel<POOL, U8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs_stem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds));
     once.commit();
   }
   a.tiles_x = ceil_div(a.OW, kTileW); a.cout_tiles = 1;
-  a.tiles_y = POOL ? ceil_div((a.OH - 1) / 2 + 1, 4) : ceil_div(a.OH, 8);
-  // few images: split the bands' tile walks so that the grid covers the chip (one 256x900 frame: 16 bands of 15 tiles)
+  a.tiles_y = ceil_div(a.OH, 8);
+  // few images: split the bands' tile walks so that the grid covers the chip
   const int bands = a.tiles_y * a.N;
   a.stem_seg_tiles = 0; a.stem_nseg = 1;
   if (bands < 128 && a.tiles_x > 1) {
@@ -1512,7 +1575,36 @@ static int hs_stem_launch(Conv2dArgs a, hipStream_t s) {
     a.stem_nseg = ceil_div(a.tiles_x, a.stem_seg_tiles);
     if (a.stem_nseg <= 1) { a.stem_seg_tiles = 0; a.stem_nseg = 1; }
   }
-  conv2d_hs_stem_kernel<POOL, U8><<<dim3((unsigned)(bands * a.stem_nseg)), dim3(256), lds, s>>>(a);
+  conv2d_hs_stem_kernel<<<dim3((unsigned)(bands * a.stem_nseg)), dim3(256), lds, s>>>(a);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
+}
+
+template <bool U8>
+static int hs_stem_pool_launch(Conv2dArgs a, hipStream_t s) {
+  constexpr size_t lds = (size_t)kStemSteps * 4096 + (size_t)4 * 3 * kStemPH * kStemPP + 2 * kHsCout * sizeof(float) +
+                         (size_t)4 * 1024 * sizeof(float);     // weights, one patch copy, BN, the four waves' parked odd rows
+  static_assert(lds <= 80 * 1024, "two workgroups per CU need <= 80 KB each");
+  static std::atomic<uint64_t> attr{0};
+  if (DeviceOnce once{attr}; once) {
+    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs_stem_pool_kernel<U8>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    once.commit();
+  }
+  // strips of 15 pooled columns, bands of 4 pooled rows
+  a.tiles_x = ceil_div((a.OW - 1) / 2 + 1, kStemPoolCols); a.cout_tiles = 1;
+  a.tiles_y = ceil_div((a.OH - 1) / 2 + 1, 4);
+  // few images: cut the strips' walks into segments of stem_seg_tiles bands so that the grid covers the chip (one 256x900
+  // frame: 15 strips of 16 bands); a segment below the top recomputes one odd stem row per wave of the band above it
+  const int strips = a.tiles_x * a.N;
+  a.stem_seg_tiles = 0; a.stem_nseg = 1;
+  if (strips < 256 && a.tiles_y > 1) {
+    const int want = std::min(a.tiles_y, std::max(1, 512 / strips));
+    a.stem_seg_tiles = ceil_div(a.tiles_y, want);
+    a.stem_nseg = ceil_div(a.tiles_y, a.stem_seg_tiles);
+    if (a.stem_nseg <= 1) { a.stem_seg_tiles = 0; a.stem_nseg = 1; }
+  }
+  conv2d_hs_stem_pool_kernel<U8><<<dim3((unsigned)(strips * a.stem_nseg)), dim3(256), lds, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
@@ -1534,7 +1626,7 @@ int conv2d_hs_stem_pool(const ConvSpec& L, const float* x, const float* w, const
   a.KH = 7; a.KW = 7; a.stride = 2; a.pad = 3; a.relu = 1;
   a.cin_pad = L.cin_pad; a.cc = L.cc;
   a.y_cells = y_cells;
-  return frames_u8 != nullptr ? hs_stem_launch<true, true>(a, s) : hs_stem_launch<true>(a, s);
+  return frames_u8 != nullptr ? hs_stem_pool_launch<true>(a, s) : hs_stem_pool_launch<false>(a, s);
 }
 
 int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const float* x, const float* w1, const float* scale1,
@@ -1871,7 +1963,7 @@ int conv2d_hs_launch(const ConvSpec& L, Conv2dArgs a, hipStream_t s) {
   const bool ds = a.w_ds != nullptr;
   if (hs_is_stem(L) && !ds) {
     ADX_REQUIRE(a.x_amax == nullptr && a.res == nullptr, "conv2d_hs stem: no residual / dynamic range");
-    return hs_stem_launch<false>(a, s);
+    return hs_stem_launch(a, s);
   }
   if (L.k == 3 && L.stride == 1 && !ds) {
     const int mode = hs3x3_mode(L, a);

@@ -211,3 +211,22 @@ def image_transform(frames_u8: torch.Tensor, mean=IMAGENET_MEAN, std=IMAGENET_ST
     L.check(L.lib().adx_image_normalize(f.data_ptr(), out.data_ptr(), n, h, w, m, s, L.stream_ptr(f.device)),
             "adx_image_normalize")
     return out
+
+
+def stem_pool(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, *, cells: bool = False,
+              mean=IMAGENET_MEAN, std=IMAGENET_STD, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inference executor's fused stem: conv 7x7 stride 2 (3 -> 64, weights packed by conv2d) + BN (scale, shift) + ReLU +
+    MaxPool2d(3, 2, 1) in one launch.  x: fp32 [N, 3, H, W], or uint8 camera frames [N, H, W, 3] (normalised with mean / std
+    on the fly, as image_transform).  Returns the pooled map, fp32 [N, 64, PH, PW] or (cells=True) its cell tensor (uint8)."""
+    u8 = x.dtype == torch.uint8
+    assert x.is_cuda and x.is_contiguous() and x.dim() == 4 and (x.shape[3] == 3 if u8 else (x.dtype == torch.float32 and x.shape[1] == 3))
+    n, h, w = (x.shape[0], x.shape[1], x.shape[2]) if u8 else (x.shape[0], x.shape[2], x.shape[3])
+    oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    ph, pw = (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
+    if out is None:
+        out = (torch.empty(n * 64 * ph * pw * 4, dtype=torch.uint8, device=x.device) if cells else
+               torch.empty((n, 64, ph, pw), dtype=torch.float32, device=x.device))
+    m, s = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    L.check(L.lib().adx_conv2d_stem_pool(x.data_ptr(), int(u8), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), m, s,
+                                         out.data_ptr(), n, h, w, int(cells), L.stream_ptr(x.device)), "adx_conv2d_stem_pool")
+    return out

@@ -266,6 +266,15 @@ int adx_conv2d_cells_supported(const adx_conv2d_desc* d, int32_t n, int32_t h, i
 int adx_conv2d_forward_cells(const adx_conv2d_desc* d, const void* x, const float* packed_w, const float* scale,
                              const float* shift, const void* res, void* y, int32_t n, int32_t h, int32_t w, int32_t relu,
                              int32_t fmt, adx_stream s);
+/* The ResNet's stem as the inference executor runs it, for tests: Conv2d(3, 64, 7, 2, 3) + BatchNorm (scale, shift: [64])
+ * + ReLU + MaxPool2d(3, 2, 1) in one launch; only the pooled map is written.  x: fp32 NCHW [n][3][h][w], or with x_u8 = 1
+ * uint8 camera frames [n][h][w][3] normalised on the fly as (v / 255 - mean) / std (mean, std: three host floats).
+ * packed_w: adx_conv2d_pack's image of the stem weights.  y: fp32 [n][64][ph][pw] (ph = (oh - 1) / 2 + 1 of the stem map's
+ * oh = (h - 1) / 2 + 1, pw likewise), or with y_cells = 1 the same map as a cell tensor (adx_conv2d_forward_cells).
+ * Refused under ADX_CONV_EXACT=1 (it is a split-fp16 kernel). */
+int adx_conv2d_stem_pool(const void* x, int32_t x_u8, const float* packed_w, const float* scale, const float* shift,
+                         const float* mean, const float* stdv, void* y, int32_t n, int32_t h, int32_t w, int32_t y_cells,
+                         adx_stream s);
 /* Weight gradient of the same convolution (torch.nn.grad.conv2d_weight; train.py:242 reaches it through
  * loss.backward()): dw [cout][cin][k][k] = sum over batch and pixels of dy (x) x.  dy is [n][cout][oh][ow].
  * scratch: NULL, or >= adx_conv2d_wgrad_scratch_bytes() of device memory in which the range of dy is estimated
