@@ -27,6 +27,12 @@
 //     rank 0 drains those stores before it publishes its own records, and every reader of the tensor has seen records that were
 //     published after rank 0's (two hand-offs later at the earliest).  The finisher (one workgroup) forms and writes the last
 //     layer's output.
+// Hardware assumption (not a documented guarantee): a 16-byte unit is in memory "whole or not at all" -- an aligned 16-byte sc1
+// store (buffer_store_dwordx4) is seen by an aligned 16-byte sc1 load (buffer_load_dwordx4) on another XCD either completely or
+// not at all, never with the tag of the new store beside payload words of the old one.  The CDNA ISA does not state this for
+// 16-byte accesses; the programming guide's own recipe for a tagged hand-off uses 8-byte {tag, value} granules.  The check that
+// would show a torn unit: tests/test_gpu_pipe_handoff.py sets the payload words of every unit to NaN between forwards and keeps
+// the tag, so a consumer that took a new tag with an old payload returns NaN.  Passing it is evidence, not proof.
 // Deadlock-free without a cooperative launch: a stage waits only for workgroups with LOWER ids, which every XCD dispatches first;
 // every spin is bounded (a timeout leaves the result wrong, never the GPU hung).  Arithmetic = tconv_hs.hip's split-fp16 scheme
 // (x = hi + 2^-11 lo, three v_mfma_f32_16x16x32_f16 per product, fp32 accumulation); fixed summation order: bit-reproducible.

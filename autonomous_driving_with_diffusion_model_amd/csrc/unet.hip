@@ -470,6 +470,7 @@ constexpr size_t kPipeTailFloats = (size_t)192 << 10;
 static thread_local float* t_split_scratch = nullptr;
 constexpr size_t kTicketWords = 256;
 constexpr int kEpochSlot = 240;          // ticket word that receives the forward's number (the pipeline's stage tags)
+constexpr bool kSplitTickets = true;     // the split reductions count their partial tiles in the ticket words
 static thread_local uint32_t* t_split_tickets = nullptr;     // kTicketWords words (adx_tconv_io::tickets), cleared by every forward
 
 static int run_conv(const ConvLayer& L, const float* base, const Act& x0, const Act* x1, const float* tbias,
@@ -674,16 +675,86 @@ static void attn_floats(const adx_unet* u, int rows, size_t* xn, size_t* qkv, si
   }
 }
 
-size_t adx_unet_workspace_bytes(const adx_unet* u, int32_t rows) {
-  if (!u || rows < 1) return 0;
+// Where a forward of `rows` rows keeps each of its regions in the caller's workspace, in floats from its start, in the order
+// the forward takes them.  adx_unet_forward, adx_unet_workspace_bytes and adx_unet_pipe_describe all read this one function.
+struct WsLayout {
+  size_t tickets, te, mc, tb, act, bufs, skips, scratch, attn_xn, attn_qkv, attn_o, end;   // bufs: kRing x act; skips: n_levels x act
+  // the pipeline run's part of the scratch tail (tconv_pipe.hip): seven stages' records, then the block outputs ya, yb, yc
+  int C, L, P;
+  size_t records, rec_floats, ya, yb, yc, y_floats;
+};
+
+static WsLayout ws_layout(const adx_unet* u, int rows) {
+  WsLayout w;
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off += align64(n); return o; };
   const int dim = u->cfg.dim;
-  size_t f = align64((size_t)rows * dim) + align64((size_t)rows * 2 * dim) + align64((size_t)rows * u->sum_c);
-  f += act_floats(u, rows) * (size_t)(kRing + u->n_levels);
-  f += kSplitScratchFloats + kTicketWords;
+  w.tickets = take(kTicketWords);
+  w.te = take((size_t)rows * dim);
+  w.mc = take((size_t)rows * 2 * dim);
+  w.tb = take((size_t)rows * u->sum_c);
+  w.act = act_floats(u, rows);
+  w.bufs = off;
+  for (int k = 0; k < kRing; ++k) take(w.act);
+  w.skips = off;
+  for (int k = 0; k < u->n_levels; ++k) take(w.act);
+  w.scratch = take(kSplitScratchFloats);
   size_t axn, aqkv, ao;
   attn_floats(u, rows, &axn, &aqkv, &ao);
-  f += axn + aqkv + ao;
-  return f * sizeof(float);
+  w.attn_xn = take(axn);
+  w.attn_qkv = take(aqkv);
+  w.attn_o = take(ao);
+  w.end = off;
+  const ResBlock& B0 = u->blocks[2 * (u->n_levels - 1)];
+  w.C = B0.cout; w.L = B0.len; w.P = B0.cout / kPipeCh;
+  w.rec_floats = pipe_record_floats(7, w.P);
+  w.y_floats = (size_t)rows * w.L * w.C;
+  w.records = w.scratch + (kSplitScratchFloats - kPipeTailFloats);
+  w.ya = w.records + align64(w.rec_floats);
+  w.yb = w.ya + align64(w.y_floats);
+  w.yc = w.yb + align64(w.y_floats);
+  return w;
+}
+
+// the deepest level's seven convs fit one pipeline launch at `rows` rows (decided on the host from the configuration alone)
+static bool pipe_shape_fits(const adx_unet* u, int rows) {
+  const ResBlock& B0 = u->blocks[2 * (u->n_levels - 1)];
+  return u->pipe_ok && pipe_shape_ok(B0.cout, B0.len, rows, B0.b.d.taps, B0.b.d.pad, B0.b.d.groups);
+}
+
+// ... and a forward of this process on the current device takes that launch: also the ticket words and the device's forward-number
+// counter must exist (the counter is allocated by the first adx_unet_pack on the device)
+static bool pipe_takes_launch(const adx_unet* u, int rows) {
+  return kSplitTickets && pipe_shape_fits(u, rows) && pipe_epoch_counter(false) != nullptr;
+}
+
+size_t adx_unet_workspace_bytes(const adx_unet* u, int32_t rows) {
+  if (!u || rows < 1) return 0;
+  return ws_layout(u, rows).end * sizeof(float);
+}
+
+int adx_unet_pipe_describe(const adx_unet* u, int32_t rows, int32_t* ints, int64_t* offs) {
+  ADX_REQUIRE(u && ints && offs, "adx_unet_pipe_describe: null argument");
+  ADX_REQUIRE(rows >= 1, "adx_unet_pipe_describe: rows must be >= 1, got %d", rows);
+  const WsLayout w = ws_layout(u, rows);
+  const bool fits = pipe_shape_fits(u, rows);
+  const int64_t f = (int64_t)sizeof(float);
+  const int32_t v[8] = {fits ? 1 : 0, pipe_takes_launch(u, rows) ? 1 : 0, w.C, w.L, w.P, (int32_t)kTicketWords, kEpochSlot, 0};
+  for (int i = 0; i < 8; ++i) ints[i] = v[i];
+  const int64_t o[12] = {(int64_t)w.tickets * f,
+                         (int64_t)w.scratch * f,
+                         (int64_t)kSplitScratchFloats * f,
+                         (int64_t)(kSplitScratchFloats - kPipeTailFloats) * f,
+                         fits ? (int64_t)w.records * f : -1,
+                         fits ? (int64_t)w.rec_floats * f : -1,
+                         fits ? (int64_t)w.ya * f : -1,
+                         fits ? (int64_t)w.yb * f : -1,
+                         fits ? (int64_t)w.yc * f : -1,
+                         fits ? (int64_t)w.y_floats * f : -1,
+                         (int64_t)w.end * f,
+                         0};
+  for (int i = 0; i < 12; ++i) offs[i] = o[i];
+  return ADX_OK;
 }
 
 int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx_unet_io* io, adx_stream stream) {
@@ -711,34 +782,29 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
   hipStream_t s = (hipStream_t)stream;
   const float* base = (const float*)packed;
   float* ws = (float*)workspace;
-  size_t off = 0;
-  auto take = [&](size_t n) { float* p = ws + off; off += align64(n); return p; };
+  const WsLayout wl = ws_layout(u, rows);
   // the ticket words come first: their place does not depend on `rows`.  Every forward CLEARS them before their first user
   // runs -- nothing rests on what the caller's buffer held (uninitialised memory, a launch that never finished): where the
   // forward opens with a chained level that launch's workgroup 0 does it (ChainArgs::zero_words, no extra node in a captured
   // step), otherwise a 1 KB memset node goes first
-  uint32_t* const split_tickets = reinterpret_cast<uint32_t*>(take(kTicketWords));
-  float* te = take((size_t)rows * dim);
-  float* mc = take((size_t)rows * 2 * dim);
-  float* tb = take((size_t)rows * u->sum_c);
-  const size_t af = act_floats(u, rows);
+  uint32_t* const split_tickets = reinterpret_cast<uint32_t*>(ws + wl.tickets);
+  float* te = ws + wl.te;
+  float* mc = ws + wl.mc;
+  float* tb = ws + wl.tb;
   float* bufs[kRing];
-  for (auto& b : bufs) b = take(af);
+  for (int k = 0; k < kRing; ++k) bufs[k] = ws + wl.bufs + (size_t)k * wl.act;
   std::vector<float*> skips(u->n_levels);
-  for (auto& p : skips) p = take(af);
+  for (int k = 0; k < u->n_levels; ++k) skips[k] = ws + wl.skips + (size_t)k * wl.act;
   struct ScratchScope {   // handed to every conv of this call through make_io
     ScratchScope(float* p, uint32_t* t) { t_split_scratch = p; t_split_tickets = t; }
     ~ScratchScope() { t_split_scratch = nullptr; t_split_tickets = nullptr; }
   };
-  float* const split_scratch = take(kSplitScratchFloats);
-  size_t axn_f, aqkv_f, ao_f;
-  attn_floats(u, rows, &axn_f, &aqkv_f, &ao_f);
-  float* const attn_xn = axn_f ? take(axn_f) : nullptr;
-  float* const attn_qkv = aqkv_f ? take(aqkv_f) : nullptr;
-  float* const attn_o = ao_f ? take(ao_f) : nullptr;
-  constexpr bool tickets_on = true;
-  ScratchScope scratch_scope(split_scratch, tickets_on ? split_tickets : nullptr);
-  bool tickets_pending = tickets_on;      // still to be cleared by this call
+  float* const split_scratch = ws + wl.scratch;
+  float* const attn_xn = wl.attn_qkv > wl.attn_xn ? ws + wl.attn_xn : nullptr;
+  float* const attn_qkv = wl.attn_o > wl.attn_qkv ? ws + wl.attn_qkv : nullptr;
+  float* const attn_o = wl.end > wl.attn_o ? ws + wl.attn_o : nullptr;
+  ScratchScope scratch_scope(split_scratch, kSplitTickets ? split_tickets : nullptr);
+  bool tickets_pending = kSplitTickets;   // still to be cleared by this call
   if (tickets_pending && !(io->time_bias != nullptr && u->down_chains[0].valid)) {
     const int rc0 = pipe_tickets_reset(split_tickets, (int)kTicketWords, kEpochSlot, s);     // zeroes them and draws this forward's number
     if (rc0 != ADX_OK) return rc0;
@@ -853,8 +919,7 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
       if (rc != ADX_OK) return rc;
       continue;
     }
-    if (i == n - 1 && u->pipe_ok && tickets_on && split_scratch != nullptr && pipe_epoch_counter(false) != nullptr &&
-        pipe_shape_ok(B0.cout, B0.len, rows, B0.b.d.taps, B0.b.d.pad, B0.b.d.groups)) {
+    if (i == n - 1 && pipe_takes_launch(u, rows)) {
       // Small batch: block 0's second conv, block 1 and both mid blocks -- seven same-shaped convs -- as ONE pipeline launch
       // (tconv_pipe.hip).  Block 0's first conv + 1x1 residual conv stay the pair / mixed launch they were.
       const int C = B0.cout, Lp = B0.len;
@@ -876,12 +941,11 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
       pa.groups = B0.b.d.groups; pa.taps = B0.b.d.taps; pa.pad = B0.b.d.pad; pa.eps = B0.b.d.eps;
       pipe_live_taps(pa.taps, pa.pad, Lp, &pa.tap0, &pa.ntap);
       // the tail of this call's scratch: records of the seven stages, then the three block outputs only later residuals read
-      const size_t rec_floats = pipe_record_floats(7, pa.P);
-      ADX_REQUIRE(align64(rec_floats) + 3 * align64((size_t)rows * Lp * C) <= kPipeTailFloats, "adx_unet_forward: pipeline tail too small");
-      pa.records = split_scratch + (kSplitScratchFloats - kPipeTailFloats);
-      float* ya = pa.records + align64(rec_floats);
-      float* yb = ya + align64((size_t)rows * Lp * C);
-      float* yc = yb + align64((size_t)rows * Lp * C);
+      ADX_REQUIRE(wl.yc + align64(wl.y_floats) <= wl.scratch + kSplitScratchFloats, "adx_unet_forward: pipeline tail too small");
+      pa.records = ws + wl.records;
+      float* ya = ws + wl.ya;
+      float* yb = ws + wl.yb;
+      float* yc = ws + wl.yc;
       pa.fault = pipe_fault_word();
       pa.epoch = split_tickets + kEpochSlot;                      // this forward's number, left there by the launch that cleared the tickets
       for (int k = 0; k < 7; ++k) {

@@ -180,6 +180,22 @@ int32_t adx_unet_time_bias_width(const adx_unet* u);
 size_t adx_unet_time_conditioning_workspace_bytes(const adx_unet* u, int32_t rows);
 int adx_unet_time_conditioning(adx_unet* u, const void* packed, void* workspace, const adx_unet_io* io, float* time_embed,
                                float* time_bias, adx_stream s);
+/* For tests only: a read-only description of where a forward of `rows` rows keeps the hand-off state of the deepest level's
+ * pipeline launch (csrc/tconv_pipe.hip) in the caller's workspace -- computed by the function the forward itself lays the
+ * workspace out with.  Locations are BYTE OFFSETS into the workspace; -1 = the forward of `rows` rows has no such region.
+ *   ints[8]  = {shape_ok, runs, C, L, P, n_tickets, epoch_slot, 0}
+ *              shape_ok: the configuration and `rows` fit the pipeline launch (decided on the host);
+ *              runs: a forward of this process on the current device takes it -- shape_ok, ADX_UNET_PIPE not 0, and the
+ *              device's forward-number counter exists (made by the first adx_unet_pack on the device);
+ *              C, L: channels and positions of the deepest level; P = C / 16 workgroups per stage;
+ *              n_tickets (256) 32-bit ticket words at offs[0], of which word epoch_slot (240) holds the forward's number
+ *   offs[12] = {tickets, scratch, scratch_bytes, ksplit_bytes, records, record_bytes, ya, yb, yc, y_bytes, workspace_bytes, 0}
+ *              scratch: the split-reduction scratch, of which the first ksplit_bytes are handed to the K-split launches and
+ *              the rest is the pipeline's alone; records: the seven stages' tagged 16-byte units {d0, d1, d2, tag};
+ *              ya, yb, yc: the block outputs later stages of the same launch read, y_bytes each (records .. y_bytes: -1
+ *              unless shape_ok); workspace_bytes = adx_unet_workspace_bytes(u, rows).
+ * Refuses (ADX_ERR_*) a null handle or output and rows < 1. */
+int adx_unet_pipe_describe(const adx_unet* u, int32_t rows, int32_t* ints, int64_t* offs);
 
 /* ------------------------------------------------------------------------------------
  * Training step T1 (train.py:242-251), temporal stack: forward that keeps a tape, and backward.

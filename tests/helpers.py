@@ -109,3 +109,20 @@ def close_traj(a, b, tol=1e-4, magic=23.315):
     close(a[..., :2], b[..., :2], magic * tol)
     if a.shape[-1] > 2:
         close(a[..., 2:], b[..., 2:], tol)
+
+
+PIPE_INTS = ("shape_ok", "runs", "C", "L", "P", "n_tickets", "epoch_slot")
+PIPE_OFFS = ("tickets", "scratch", "scratch_bytes", "ksplit_bytes", "records", "record_bytes", "ya", "yb", "yc", "y_bytes",
+             "workspace_bytes")
+
+
+def pipe_layout(handle, rows: int) -> dict:
+    """adx_unet_pipe_describe as a dict: where a forward of `rows` rows keeps the deepest level's hand-off state (byte
+    offsets into its workspace, -1: none) and whether it takes the pipeline launch (include/adx.h)."""
+    from autonomous_driving_with_diffusion_model_amd import _lib as L
+    ints, offs = (L.i32 * 8)(), (L.i64 * 12)()
+    L.check(L.lib().adx_unet_pipe_describe(handle, rows, ints, offs), "adx_unet_pipe_describe")
+    out = dict(zip(PIPE_INTS, list(ints)))
+    out.update(zip(PIPE_OFFS, list(offs)))
+    out["epoch"] = out["tickets"] + 4 * out["epoch_slot"]
+    return out

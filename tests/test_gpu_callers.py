@@ -237,7 +237,8 @@ def test_pipeline_launch_completes_with_the_gpu_shared_between_processes(tmp_pat
     """csrc/tconv_pipe.hip is a launch of 225 workgroups in which later stages spin on earlier ones -- without a cooperative launch.
     Three processes sample on this one GPU at once (one scene, H = 16: every step of every process issues that launch), so the
     pipeline's workgroups are not all resident together; every tick of every process must still complete and reproduce the
-    bits of that process's first, eagerly launched tick, and the processes must agree with each other."""
+    bits of that process's eagerly launched tick of the same input (the ticks cycle through three), and the processes must agree
+    with each other on every input."""
     import subprocess
     procs, outs = [], []
     for i in range(3):
@@ -248,5 +249,8 @@ def test_pipeline_launch_completes_with_the_gpu_shared_between_processes(tmp_pat
     for p, lg in zip(procs, logs):
         assert p.returncode == 0, lg[-3000:]
     res = [torch.load(o) for o in outs]
-    assert all(r["all_equal"] and r["finite"] for r in res), [(r["all_equal"], r["finite"]) for r in res]
+    assert all(r["all_equal"] and r["finite"] for r in res), [(r["all_equal"], r["finite"], r["mismatched_ticks"]) for r in res]
     assert torch.equal(res[0]["first"], res[1]["first"]) and torch.equal(res[0]["first"], res[2]["first"])
+    assert all(r["distinct"] for r in res)            # the three inputs give three different trajectories
+    for k in range(3):                                # and every process agrees on every input
+        assert all(torch.equal(res[0]["refs"][k], r["refs"][k]) for r in res[1:]), k

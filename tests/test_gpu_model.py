@@ -614,13 +614,14 @@ def test_levels_layer_by_layer_vs_oracle():
 
 
 @pytest.mark.parametrize("use_cond,rows", [("NO_GUIDANCE", 1), ("FREE_GUIDANCE", 2), ("NO_GUIDANCE", 3), ("FREE_GUIDANCE", 8),
-                                           ("CLASSIFIER_GUIDANCE", 4), ("NO_GUIDANCE", 9)])
+                                           ("CLASSIFIER_GUIDANCE", 4), ("NO_GUIDANCE", 5), ("NO_GUIDANCE", 9)])
 def test_pipeline_launch_of_the_deepest_level_vs_oracle(use_cond, rows):
-    """csrc/tconv_pipe.hip: at MODEL.HORIZON = 16 (two positions at the deepest level) and up to 8 rows, block 0's second conv,
+    """csrc/tconv_pipe.hip: at MODEL.HORIZON = 16 (two positions at the deepest level) and up to 5 rows, block 0's second conv,
     block 1 and both mid blocks -- seven Conv1d(512, 512, 5) + GroupNorm + Mish -- run as ONE launch: 7 x 32 workgroups that
     hand raw conv sums on through memory, the consumer applying GroupNorm / Mish / time bias / residual.  Whole forwards against
-    the oracle for every row count the tile holds (9 rows: back on the launch chain), twice each (a second call must not
-    depend on the first one's counters), modeling/temporal.py:197-245."""
+    the oracle for every row count the launch takes (6 rows and more do not fit its LDS: back on the launch chain, which the
+    layout export must say), twice each (a second call must not depend on the first one's counters), modeling/temporal.py:197-245."""
+    from helpers import pipe_layout
     m, _ = make_model(use_cond, 16)
     d = P.synthetic_batch(rows, 16, image_hw=(32, 32), seed=90 + rows)
     feat = P._uniform("pipe.feat", 90 + rows, (rows, 64), -3.0, 3.0)
@@ -636,6 +637,7 @@ def test_pipeline_launch_of_the_deepest_level_vs_oracle(use_cond, rows):
             y = m(d["trajs"].to(DEV), d["imgs"].to(DEV), d["t"].to(DEV), **kw)
             outs.append((y[0] if isinstance(y, tuple) else y).cpu())
     assert torch.equal(outs[0], outs[1])
+    assert pipe_layout(m._native(), rows)["runs"] == (1 if rows <= 5 else 0), rows     # the path this test is named after ran
     w = want if want.shape[-1] == outs[0].shape[-1] else want[..., -outs[0].shape[-1]:]
     close(outs[0], w, 2e-5)
 
