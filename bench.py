@@ -6,11 +6,15 @@ One "step" = one `model.forward` (ResNet-34 perception on the 64 images + Tempor
 2x64 CFG batch) + one `scheduler.step` (CFG combine + DDIM update + `[:,0,:3]=0`) advancing all 64
 trajectories by one timestep, i.e. exactly the per-step work of the reference's sampling loop
 (interact.py:131-164, which re-runs the perception every step: modeling/temporal.py:203).  `value`
-is measured in that reference-faithful mode.  The `hoisted` object reports the product's default
-mode, where the perception feature is memoised per image tensor (one ResNet pass per scene).
+is measured in that reference-faithful mode.
 
-Contract: python bench.py --gpus N --steps K --warmup W  ->  one JSON line on rank 0.
---dump-outputs DIR additionally writes the trajectories the timed loops returned (DIR/<name>.npy, fp32; fixed inputs).
+Contract: python bench.py --gpus N --steps K --warmup W  ->  one JSON line on rank 0.  Such a plain run does only what
+`value` needs: set-up, W warm-up steps, the K timed steps, the line.
+--dump-outputs DIR additionally writes the trajectories the timed loops returned (DIR/<name>.npy, fp32; fixed inputs); the
+hoisted loop (below) runs for its array and is reported as `hoisted`.
+--full adds everything else the benchmark measures: `hoisted` (the product's default mode, where the perception feature is
+memoised per image tensor: one ResNet pass per scene), `hoisted_graph`, the training legs, the roofline probes, the
+deployed B = 1 leg and the CPU baseline (the --no-* options leave parts of it out).
 Multi-GPU: scenes are independent, every rank samples its own 64 scenes, no collective on the data
 path ("scaling": "weak"); the barrier only brackets the timed region.
 """
@@ -669,20 +673,25 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the hoisted and graph sampling legs, the training legs, the roofline probes, "
+                         "the deployed B = 1 leg and the CPU baseline; the options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--train-steps", type=int, default=20, help="timed optimizer steps per training leg")
     ap.add_argument("--no-deployed", action="store_true")
     ap.add_argument("--force-collectives", action="store_true",
-                    help="N = 1: run the FREE_GUIDANCE training leg under parallel.DataParallel(force=True) on a one-rank RCCL group "
-                         "(train_free.gradient_buckets.overlap_rank0 then reports the bucket reductions against backward)")
+                    help="with --full, N = 1: run the FREE_GUIDANCE training leg under parallel.DataParallel(force=True) on a one-rank "
+                         "RCCL group (train_free.gradient_buckets.overlap_rank0 then reports the bucket reductions against backward)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed sampling loops returned in their last step (the float32 "
                          "trajectories of rank 0's scenes) as DIR/<name>.npy, for comparing two builds output for output")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--short-sampling", action="store_true", help=argparse.SUPPRESS)   # tests: skip the hoisted / graph legs
     args = ap.parse_args()
+    if args.force_collectives and not args.full:
+        ap.error("--force-collectives applies to the training leg, which only a --full run has")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))       # no launcher around us: become one (the parent stays off the GPU)
@@ -773,46 +782,51 @@ def main():
     # the perception pass alone (HIP events on the caller's stream around 8 back-to-back passes on the tick's image tensor), as the
     # product runs it: two sub-batches on streams of their own (csrc/conv2d.hip), on the pass stream (modeling/perception.py)
     pass_ms = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         with torch.no_grad():
             model.perception(d["imgs"])
             pass_ms = round(time_events(lambda: model.perception(d["imgs"]), 8, warm=1), 4)
     model.cache_perception = False          # reference-faithful: perception re-run every step
     dt, per_rank, trajs = timed(args.steps, args.warmup)
-    model.cache_perception = True           # product default: one perception pass per scene
-    steps_h = args.steps if args.short_sampling else max(args.steps, N_INFER)
-    dt_h, per_rank_h, trajs_h = timed(steps_h, args.warmup)
     # --dump-outputs: what the caller of each timed loop receives after its last step (B x H x D, fp32); the inputs are fixed
     # (procedural weights seed 0, synthetic batch seed = rank), so two builds can be compared array for array
-    dumped = ({"trajectories": trajs.float().cpu().numpy(), "trajectories_hoisted": trajs_h.float().cpu().numpy()}
-              if args.dump_outputs else {})
-    del trajs, trajs_h
+    dumped = {"trajectories": trajs.float().cpu().numpy()} if args.dump_outputs else {}
+    del trajs
+    hoisted = args.full or bool(args.dump_outputs)        # a plain run without --dump-outputs ends its GPU work here
+    if hoisted:
+        model.cache_perception = True       # product default: one perception pass per scene
+        steps_h = args.steps if args.short_sampling else max(args.steps, N_INFER)
+        dt_h, per_rank_h, trajs_h = timed(steps_h, args.warmup)
+        if args.dump_outputs:
+            dumped["trajectories_hoisted"] = trajs_h.float().cpu().numpy()
+        del trajs_h
 
-    # the same hoisted loop as ONE HIP graph per 50-step tick (sampling.GraphedSampler: perception pass, 50 x (UNet +
-    # scheduler step), clamp and scaling captured once, replayed bit-identically): no host work between launches
-    from autonomous_driving_with_diffusion_model_amd.sampling import GraphedSampler
-    gs = GraphedSampler(model, sch, cfg)
-    ticks = max(10, (max(args.steps, N_INFER) + N_INFER - 1) // N_INFER)     # >= 10 replays of ~25 ms: one sample is noise
-    if args.short_sampling:
-        ticks = 1
-    with torch.no_grad():
-        for _ in range(2):                   # capture + one replay
-            gs(d["imgs"], d["target"], d["init_trajs"])
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(ticks):
-            gs(d["imgs"], d["target"], d["init_trajs"])
-        barrier()
-        dt_g, per_rank_g = max_over_ranks(time.perf_counter() - t0, world, dev)
-    steps_g = ticks * N_INFER
-    del gs
+    if args.full:
+        # the same hoisted loop as ONE HIP graph per 50-step tick (sampling.GraphedSampler: perception pass, 50 x (UNet +
+        # scheduler step), clamp and scaling captured once, replayed bit-identically): no host work between launches
+        from autonomous_driving_with_diffusion_model_amd.sampling import GraphedSampler
+        gs = GraphedSampler(model, sch, cfg)
+        ticks = max(10, (max(args.steps, N_INFER) + N_INFER - 1) // N_INFER)     # >= 10 replays of ~25 ms: one sample is noise
+        if args.short_sampling:
+            ticks = 1
+        with torch.no_grad():
+            for _ in range(2):                   # capture + one replay
+                gs(d["imgs"], d["target"], d["init_trajs"])
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(ticks):
+                gs(d["imgs"], d["target"], d["init_trajs"])
+            barrier()
+            dt_g, per_rank_g = max_over_ranks(time.perf_counter() - t0, world, dev)
+        steps_g = ticks * N_INFER
+        del gs
 
     del model
     torch.cuda.empty_cache()
     # training legs: configs[1] (NO_GUIDANCE) on one GPU; configs[4]'s per-GPU workload (FREE_GUIDANCE incl. the cond=None
     # draw) at every world size -- with N > 1 ranks that IS configs[4] (8 x 64 = 512 global), so it is the only one run there
     train = train_free = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         try:
             if world == 1:
                 train = train_leg(dev, world, "NO_GUIDANCE", steps=args.train_steps)
@@ -836,7 +850,8 @@ def main():
     if rank == 0:
         res = {
             "metric": "denoising-steps/sec", "value": round(world * args.steps / dt, 3), "unit": "denoising-steps/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
+            "ms_per_step": round(1e3 * dt / args.steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "dtype_note": "fp32 inputs, outputs and accumulation; the 2-D convolutions multiply fp16 hi/lo split operands (3 MFMAs per product, error below fp32 accumulation's own: DESIGN.md section 3)",
             "parity_note": "north_star: fp32 trajectory outputs within 1e-4.  Measured at this workload (tests/test_gpu_fullsize.py, B = 64, "
@@ -854,25 +869,29 @@ def main():
                                    "guidance scale 7.5, 64 scenes per GPU (UNet batch 128), horizon 32, image 3x256x900, "
                                    "reference-faithful (ResNet-34 perception re-run every step)",
                        "batch_per_gpu": B, "horizon": H, "ddim_steps": N_INFER, "weights": "procedural (seed 0)"},
-            "hoisted": {"value": round(world * steps_h / dt_h, 3), "ms_per_step": round(1e3 * dt_h / steps_h, 4),
-                        "steps": steps_h, "note": "perception memoised per image tensor: one ResNet-34 pass per "
-                        "scene inside the timed region (and one pass of the time / condition embedding for all timesteps), "
-                        "then UNet + scheduler per step, launched eagerly",
-                        "trajectories_per_sec": round(world * B / (dt_h * N_INFER / steps_h), 2)},
-            "hoisted_graph": {"value": round(world * steps_g / dt_g, 3), "ms_per_step": round(1e3 * dt_g / steps_g, 4),
-                              "steps": steps_g, "note": "sampling.GraphedSampler: each 50-step tick (perception pass "
-                              "included) replayed as one HIP graph; bit-identical to the eager loop",
-                              "trajectories_per_sec": round(world * B * ticks / dt_g, 2)},
         }
+        if hoisted:
+            res["hoisted"] = {"value": round(world * steps_h / dt_h, 3), "ms_per_step": round(1e3 * dt_h / steps_h, 4),
+                              "steps": steps_h, "note": "perception memoised per image tensor: one ResNet-34 pass per "
+                              "scene inside the timed region (and one pass of the time / condition embedding for all timesteps), "
+                              "then UNet + scheduler per step, launched eagerly",
+                              "trajectories_per_sec": round(world * B / (dt_h * N_INFER / steps_h), 2)}
+        if args.full:
+            res["hoisted_graph"] = {"value": round(world * steps_g / dt_g, 3), "ms_per_step": round(1e3 * dt_g / steps_g, 4),
+                                    "steps": steps_g, "note": "sampling.GraphedSampler: each 50-step tick (perception pass "
+                                    "included) replayed as one HIP graph; bit-identical to the eager loop",
+                                    "trajectories_per_sec": round(world * B * ticks / dt_g, 2)}
         if world > 1:
             res["per_rank_ms_per_step"] = [round(1e3 * t / args.steps, 3) for t in per_rank]
-            res["hoisted"]["per_rank_ms_per_step"] = [round(1e3 * t / steps_h, 4) for t in per_rank_h]
-            res["hoisted_graph"]["per_rank_ms_per_step"] = [round(1e3 * t / steps_g, 4) for t in per_rank_g]
+            if hoisted:
+                res["hoisted"]["per_rank_ms_per_step"] = [round(1e3 * t / steps_h, 4) for t in per_rank_h]
+            if args.full:
+                res["hoisted_graph"]["per_rank_ms_per_step"] = [round(1e3 * t / steps_g, 4) for t in per_rank_g]
         if train is not None:
             res["train"] = train
         if train_free is not None:
             res["train_free"] = train_free
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             res["roofline"] = conv2d_roofline(dev)
             if pass_ms is not None:
                 conv_gf = sum(conv_flops(B, *c) for c in resnet_conv_table(*IMG)) / 1e9
@@ -887,12 +906,12 @@ def main():
                             "the pass also holds the stem + pool, three stride-2 launches and the pooling + fc).  `frac` / `avg_launch_ms` stay "
                             "per-launch figures on ONE stream: a launch that shares the chip has no duration of its own"}
             res["roofline_tconv"] = tconv_roofline(None, dev)
-        if world == 1 and not args.no_deployed:
+        if args.full and world == 1 and not args.no_deployed:
             try:
                 res["deployed_b1_h16"] = deployed_leg(dev)
             except Exception as e:
                 res["deployed_b1_h16"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
             res["speedup_vs_cpu_baseline"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
         if args.dump_outputs:

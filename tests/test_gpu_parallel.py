@@ -71,7 +71,7 @@ def test_two_ranks_real_model_free_guidance_train_steps(tmp_path, primitive):
 
 
 def test_bench_two_ranks_same_device_fullsize_free_train_leg():
-    """`bench.py --gpus 2` end to end on one GPU (ADX_BENCH_SAME_DEVICE=1: both ranks on cuda:0, gloo collectives): the
+    """`bench.py --gpus 2 --full` end to end on one GPU (ADX_BENCH_SAME_DEVICE=1: both ranks on cuda:0, gloo collectives): the
     launcher, the sharded sampling legs and -- the point -- BASELINE configs[4]'s per-GPU workload as the training leg:
     FREE_GUIDANCE at B = 64 per rank, H = 32, 3 x 256 x 900 under parallel.DataParallel with train.py:236-242's per-rank
     cond=None draw.  Every gradient must have been born in its bucket (nothing copied), every rank reports its own step
@@ -80,7 +80,7 @@ def test_bench_two_ranks_same_device_fullsize_free_train_leg():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["ADX_BENCH_SAME_DEVICE"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                         "--train-steps", "3", "--short-sampling", "--no-roofline"], env=env, capture_output=True, text=True,
                        timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -278,6 +278,18 @@ def test_bench_launches_its_own_ranks():
     assert r.returncode == 7, (r.returncode, r.stderr[-500:])
 
 
+def test_bench_force_collectives_needs_full():
+    """--force-collectives changes the training leg, which only `bench.py --full` runs: without --full it is refused before
+    any rank starts, not ignored."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-collectives"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr and r.stdout == "", (r.returncode, r.stderr[-500:])
+
+
 def _forced_worker(rank, world, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -1,4 +1,4 @@
-"""One-line summary of a bench.py JSON line: python tools/bench_summary.py gpurun_out/r05/bench.json"""
+"""One-line summary of a `bench.py --full` JSON line: python tools/bench_summary.py <file holding the line>"""
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 r = d["roofline"]

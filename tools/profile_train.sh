@@ -1,7 +1,9 @@
 export HIP_FORCE_DEV_KERNARG=1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_tr -- python3 tools/train_time.py > gpurun_out/prof_tr.log 2>&1
-f=$(ls -t gpurun_out/prof_tr/*/*kernel_stats.csv | head -1)
+OUT=${OUT:-profile_out}
+mkdir -p $OUT
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_tr -- python3 tools/train_time.py > $OUT/prof_tr.log 2>&1
+f=$(ls -t $OUT/prof_tr/*/*kernel_stats.csv | head -1)
 python3 - "$f" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
