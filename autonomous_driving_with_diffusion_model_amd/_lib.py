@@ -103,6 +103,12 @@ _SIGS = {
     "adx_resnet_workspace_bytes": (C.c_size_t, [vp, i32, i32, i32]),
     "adx_resnet_forward": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "adx_resnet_forward_u8": (i32, [vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i32, vp, vp]),
+    "adx_unet_status_words": (i32, [vp]),
+    "adx_unet_set_status": (i32, [vp, vp]),
+    "adx_unet_status_name": (C.c_char_p, [vp, i32]),
+    "adx_resnet_status_words": (i32, [vp]),
+    "adx_resnet_set_status": (i32, [vp, vp]),
+    "adx_resnet_status_name": (C.c_char_p, [vp, i32]),
     "adx_resnet_tape_create": (i32, [C.POINTER(vp)]),
     "adx_resnet_tape_destroy": (None, [vp]),
     "adx_resnet_train_workspace_bytes": (C.c_size_t, [vp, i32, i32, i32]),
@@ -154,6 +160,16 @@ _lib: Optional[C.CDLL] = None
 
 class AdxError(RuntimeError):
     pass
+
+
+class AdxRangeError(AdxError):
+    """A forward under `range_guard = "raise"` split a value outside fp16's range (|x| >= 65504 or NaN) into the
+    hi / lo operands of the split-fp16 kernels; `groups` names the layer groups whose status words are set."""
+
+    def __init__(self, groups):
+        self.groups = list(groups)
+        super().__init__(f"values outside the fp16 range of the split kernels (|x| >= 65504 or NaN) in {', '.join(self.groups)}; "
+                         "ADX_CHECK_RANGE=1 names the first tensor, ADX_CONV_EXACT=1 runs the perception pass on the exact-fp32 kernels")
 
 
 def lib() -> C.CDLL:

@@ -119,6 +119,20 @@ __device__ __forceinline__ float mish_f(float x) {
   return x * (n / (n + 2.f));
 }
 
+// Range status (include/adx.h: adx_resnet_set_status).  A value the split-fp16 kernels turn into fp16 hi / lo halves is
+// representable only for |x| < 65504; out_of_fp16 is that test, true for a NaN too: one compare with an abs modifier, no
+// branch.  A kernel's epilogue folds every value it splits or stores for a split kernel to read into a per-lane running
+// maximum of |x| that a NaN wins (fp16_amax: IEEE maximum, v_maximum3_f32 -- one instruction per two values), tests it once
+// and ends with range_flag: one ballot per wave, and the first flagged lane ORs 1 into the launch's status word with a vector
+// atomic (status == nullptr: nothing attached, nothing written).
+__device__ __forceinline__ bool out_of_fp16(float v) { return !(__builtin_fabsf(v) < 65504.f); }
+__device__ __forceinline__ float fp16_amax(float m, float v) { return __builtin_elementwise_maximum(m, __builtin_fabsf(v)); }
+__device__ __forceinline__ void range_flag(uint32_t* status, bool bad) {
+  if (status == nullptr) return;
+  const unsigned long long m = __ballot(bad);
+  if (m != 0ull && (int)(threadIdx.x & 63) == __ffsll(m) - 1) atomicOr(status, 1u);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -294,7 +294,7 @@ __global__ void __launch_bounds__(256) maxpool_kernel(const float* __restrict__ 
 // planes in flight per wave (the means are plain sequential-lane sums: deterministic)
 __global__ void __launch_bounds__(1024) avgpool_fc_kernel(const float* __restrict__ x, const float* __restrict__ fw,
                                                            const float* __restrict__ fb, float* __restrict__ out,
-                                                           int C, int HW, int out_dim) {
+                                                           int C, int HW, int out_dim, uint32_t* status) {
   __shared__ float pooled[512];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* src = x + (size_t)n * C * HW;
@@ -312,12 +312,18 @@ __global__ void __launch_bounds__(1024) avgpool_fc_kernel(const float* __restric
     }
   }
   __syncthreads();
+  bool bad = false;
   for (int j = wave; j < out_dim; j += 16) {
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += fw[(size_t)j * C + c] * pooled[c];
     s = wave_sum(s);
-    if (lane == 0) out[(size_t)n * out_dim + j] = s + fb[j];
+    if (lane == 0) {
+      const float o = s + fb[j];
+      out[(size_t)n * out_dim + j] = o;
+      bad |= out_of_fp16(o);
+    }
   }
+  range_flag(status, bad);
 }
 
 int maxpool_launch(const float* x, float* y, int planes, int H, int W, int OH, int OW, hipStream_t s) {
@@ -330,7 +336,7 @@ int maxpool_launch(const float* x, float* y, int planes, int H, int W, int OH, i
 // group per wave at a time, value = hi + lo / 2^11, the same lane-strided partial sums and wave reduction per channel
 __global__ void __launch_bounds__(1024) avgpool_fc_cells_kernel(const uint4* __restrict__ x, const float* __restrict__ fw,
                                                                  const float* __restrict__ fb, float* __restrict__ out,
-                                                                 int C, int HW, int out_dim) {
+                                                                 int C, int HW, int out_dim, uint32_t* status) {
   typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   __shared__ float pooled[512];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -351,24 +357,30 @@ __global__ void __launch_bounds__(1024) avgpool_fc_cells_kernel(const uint4* __r
     }
   }
   __syncthreads();
+  bool bad = false;
   for (int j = wave; j < out_dim; j += 16) {
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += fw[(size_t)j * C + c] * pooled[c];
     s = wave_sum(s);
-    if (lane == 0) out[(size_t)n * out_dim + j] = s + fb[j];
+    if (lane == 0) {
+      const float o = s + fb[j];
+      out[(size_t)n * out_dim + j] = o;
+      bad |= out_of_fp16(o);
+    }
   }
+  range_flag(status, bad);
 }
 
 int avgpool_fc_launch(const float* x, const float* fw, const float* fb, float* out, int batch, int C, int HW, int out_dim,
-                      hipStream_t s, int x_cells) {
+                      hipStream_t s, int x_cells, uint32_t* status) {
   ADX_REQUIRE(C <= 512, "avgpool_fc: at most 512 channels");
   if (x_cells) {
     ADX_REQUIRE(C % 8 == 0, "avgpool_fc: the cell layout holds channels in groups of eight");
-    avgpool_fc_cells_kernel<<<dim3(batch), dim3(1024), 0, s>>>(reinterpret_cast<const uint4*>(x), fw, fb, out, C, HW, out_dim);
+    avgpool_fc_cells_kernel<<<dim3(batch), dim3(1024), 0, s>>>(reinterpret_cast<const uint4*>(x), fw, fb, out, C, HW, out_dim, status);
     ADX_LAUNCH_CHECK();
     return ADX_OK;
   }
-  avgpool_fc_kernel<<<dim3(batch), dim3(1024), 0, s>>>(x, fw, fb, out, C, HW, out_dim);
+  avgpool_fc_kernel<<<dim3(batch), dim3(1024), 0, s>>>(x, fw, fb, out, C, HW, out_dim, status);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
@@ -390,6 +402,9 @@ static int conv2d_launch(const ConvSpec& L, const float* base, const float* x, c
 static thread_local float* t_split_scratch = nullptr;
 static thread_local size_t t_split_floats = 0;
 void conv2d_set_split_scratch(float* p, size_t floats) { t_split_scratch = p; t_split_floats = p != nullptr ? floats : 0; }
+static thread_local uint32_t* t_status = nullptr;
+void conv2d_set_status(uint32_t* word) { t_status = word; }
+uint32_t* conv2d_status() { return t_status; }
 
 int conv2d_launch_raw(const ConvSpec& L, const float* x, const float* w, const float* scale, const float* shift,
                       const float* res, float* y, int N, int H, int W, int relu, hipStream_t s, const uint32_t* x_amax,
@@ -404,6 +419,7 @@ int conv2d_launch_raw(const ConvSpec& L, const float* x, const float* w, const f
   a.cin_pad = L.cin_pad; a.cc = L.cc;
   a.x_u8 = nullptr;
   a.d2s_cin = 0; a.d2s_h = 0; a.d2s_w = 0; a.stem_seg_tiles = 0; a.stem_nseg = 1;
+  a.status = t_status;
   a.ksplit = 1; a.cper = 0; a.part = t_split_scratch; a.part_stride = t_split_floats;   // part_stride: capacity until the launch fixes it
   a.stats_part = nullptr; a.stats_p = 0;
   a.bs_raw = a.bs_out = a.bs_mean = a.bs_rstd = a.bs_gamma = a.bs_beta = nullptr; a.bs_mask = 0; a.bs_bits = nullptr; a.res_bits = nullptr;
@@ -606,6 +622,33 @@ void adx_resnet_destroy(adx_resnet* r) {
   delete r;
 }
 int adx_resnet_num_tensors(const adx_resnet* r) { return r ? r->n_tensors : 0; }
+
+int32_t adx_resnet_status_words(const adx_resnet* r) {
+  ADX_REQUIRE(r != nullptr, "adx_resnet_status_words: null handle");
+  return (int32_t)r->block_has_ds.size() + 3;
+}
+
+int adx_resnet_set_status(adx_resnet* r, uint32_t* words) {
+  ADX_REQUIRE(r != nullptr, "adx_resnet_set_status: null handle");
+  r->status = words;
+  return ADX_OK;
+}
+
+const char* adx_resnet_status_name(const adx_resnet* r, int32_t g) {
+  static const char* const kBlocks[16] = {"block0", "block1", "block2",  "block3",  "block4",  "block5",  "block6",  "block7",
+                                          "block8", "block9", "block10", "block11", "block12", "block13", "block14", "block15"};
+  if (r == nullptr) { set_error("adx_resnet_status_name: null handle"); return nullptr; }
+  const int nb = (int)r->block_has_ds.size();
+  if (g < 0 || g >= nb + 3) { set_error("adx_resnet_status_name: group %d outside [0, %d)", g, nb + 3); return nullptr; }
+  return g == 0 ? "stem" : g <= nb ? kBlocks[g - 1] : g == nb + 1 ? "fc" : "weights";
+}
+
+// the executor's launches between construction and destruction write the given status word (conv2d_set_status)
+struct StatusScope {
+  explicit StatusScope(uint32_t* w) { conv2d_set_status(w); }
+  void set(uint32_t* w) { conv2d_set_status(w); }
+  ~StatusScope() { conv2d_set_status(nullptr); }
+};
 size_t adx_resnet_packed_bytes(const adx_resnet* r) { return r ? r->packed_floats * sizeof(float) : 0; }
 
 int adx_resnet_pack(adx_resnet* r, const float* const* T, int32_t n, void* packed, adx_stream stream) {
@@ -614,6 +657,7 @@ int adx_resnet_pack(adx_resnet* r, const float* const* T, int32_t n, void* packe
   for (int i = 0; i < n; ++i) ADX_REQUIRE(T[i] != nullptr, "adx_resnet_pack: tensor %d is null", i);
   hipStream_t s = (hipStream_t)stream;
   float* base = (float*)packed;
+  StatusScope status_scope(r->status != nullptr ? r->status + r->block_has_ds.size() + 2 : nullptr);   // "weights"
   for (const ConvSpec& L : r->convs) {
     // a downsample conv that rides on its block's split-fp16 conv1 is packed in that kernel's layout
     const bool fused = L.fuse_with >= 0 && resnet_fuses_ds(r->convs[L.fuse_with], L);
@@ -723,6 +767,8 @@ static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspac
     ~ScratchScope() { conv2d_set_split_scratch(nullptr, 0); }
   } scratch_scope;
   const size_t nblocks = r->block_has_ds.size();
+  uint32_t* const words = r->status;       // range status (adx_resnet_set_status): [0] stem, [1 + b] block b, [1 + nblocks] fc
+  StatusScope status_scope(words);
 
   struct Cursor { size_t ci; int cur, H, W; bool cells; };
   constexpr int fuse = 1;         // stem + max-pool as one launch (0: two launches, the round-1 form)
@@ -732,6 +778,7 @@ static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspac
     const ConvSpec& c0 = r->convs[0];
     const float* im = img != nullptr ? img + (size_t)n0 * 3 * h * w : nullptr;
     const uint8_t* fr = frames_u8 != nullptr ? frames_u8 + (size_t)n0 * 3 * h * w : nullptr;
+    status_scope.set(words);
     float* pooled = buf[0] + (size_t)n0 * 64 * h2 * w2;
     bool pooled_cells = false;
     int rc;
@@ -764,6 +811,7 @@ static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspac
     size_t ci = st.ci;
     const int cur = st.cur, H = st.H, W = st.W;
     const bool cur_cells = st.cells;
+    status_scope.set(words != nullptr ? words + 1 + b : nullptr);
     const ConvSpec& c1 = r->convs[ci++];
     const ConvSpec& c2 = r->convs[ci++];
     const int mid = (cur + 1) % 3, outb = (cur + 2) % 3;
@@ -917,7 +965,7 @@ static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspac
   for (int k = 0; k < nsub && rc == ADX_OK; ++k) {
     const size_t off = (size_t)n0s[k] * 64 * h2 * w2;          // the sub-batch's region (run_block)
     rc = avgpool_fc_launch(buf[st[k].cur] + off, base + r->o_fcw, base + r->o_fcb, feature + (size_t)n0s[k] * r->out_dim, ns[k], 512,
-                           st[k].H * st[k].W, r->out_dim, streams[k], st[k].cells);
+                           st[k].H * st[k].W, r->out_dim, streams[k], st[k].cells, words != nullptr ? words + 1 + nblocks : nullptr);
   }
   // join even after an error: a side stream must not be left forked from a capturing stream
   for (int k = 1; k < nsub; ++k) {

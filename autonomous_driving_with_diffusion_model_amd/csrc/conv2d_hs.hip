@@ -39,10 +39,13 @@ namespace adx {
 // cell 2 i + khalf); then affine (sc / sh: LDS, indexed by the channel within the group's 64-channel slab), optional
 // residual (res8[i]: the eight values of cell 2 i + khalf, or null), ReLU, split, two 16-byte stores per cell.
 // so: SGPR byte offset of the group's first hi cell; cplane: bytes of one plane of cells; vcell: the lane's pixel * 16 +
-// khalf * 2 * cplane, or the out-of-range offset.
+// khalf * 2 * cplane, or the out-of-range offset.  amax: the lane's running maximum of |x| over the values it splits
+// (adx_common.h: fp16_amax) at a pixel of the map (vcell in range): one select per call, not per value.
 template <bool AFFINE = true>
 __device__ __forceinline__ void cells_store32(float (&v)[16], const float* sc, const float* sh, int cl0, const float (*res8)[8],
-                                              bool relu, __amdgpu_buffer_rsrc_t yrsrc, uint32_t vcell, uint32_t so, uint32_t cplane) {
+                                              bool relu, __amdgpu_buffer_rsrc_t yrsrc, uint32_t vcell, uint32_t so, uint32_t cplane,
+                                              float& amax) {
+  float lm = 0.f;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -59,6 +62,7 @@ __device__ __forceinline__ void cells_store32(float (&v)[16], const float* sc, c
       float t = AFFINE ? v[8 * i + j] * sc[cl0 + 16 * i + j] + sh[cl0 + 16 * i + j] : v[8 * i + j];
       if (res8 != nullptr) t += res8[i][j];
       o[j] = relu ? __builtin_fmaxf(t, 0.f) : t;
+      lm = fp16_amax(lm, o[j]);
     }
     u32x4 hi, lo;
     split8(o, 1.f, hi, lo);
@@ -71,6 +75,7 @@ __device__ __forceinline__ void cells_store32(float (&v)[16], const float* sc, c
     // across one wait state, wherever the scheduler puts it: nothing can write them before it.
     asm volatile("s_nop 0" ::"v"(hi), "v"(lo));
   }
+  amax = fp16_amax(amax, vcell < 0xC0000000u ? lm : 0.f);
 }
 
 // STRIDE/K: the convolution; ROWS: output rows per wave (tile = 4*ROWS rows x 32 columns x 64 channels);
@@ -354,6 +359,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_kernel(const Conv2dArgs a) {
     // residual); no residual and no depth-to-space store on this path (the host checks)
     const uint32_t cplane = (uint32_t)(a.OH * a.OW) * 16u;
     const uint32_t cell0 = (uint32_t)(cout0 >> 3) * 2u * cplane;
+    float amax = 0.f;
 #pragma unroll
     for (int rr = 0; rr < ROWS; ++rr) {
       const int oy = oy0 + wave * ROWS + rr;
@@ -364,15 +370,16 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_kernel(const Conv2dArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = (accm[rr][half][r] + accl[rr][half][r] * (1.f / kLoScale)) * xs_inv;
         cells_store32(v, ss, ss + kHsCout, half * 32 + 8 * khalf, nullptr, a.relu != 0, yrsrc, vcell,
-                      cell0 + (uint32_t)(half * 4) * 2u * cplane, cplane);
+                      cell0 + (uint32_t)(half * 4) * 2u * cplane, cplane, amax);
         if (DS) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) v[r] = (adm[rr][half][r] + adl[rr][half][r] * (1.f / kLoScale)) * xs_inv;
           cells_store32(v, ss + 2 * kHsCout, ss + 3 * kHsCout, half * 32 + 8 * khalf, nullptr, false, drsrc, vcell,
-                        cell0 + (uint32_t)(half * 4) * 2u * cplane, cplane);
+                        cell0 + (uint32_t)(half * 4) * 2u * cplane, cplane, amax);
         }
       }
     }
+    range_flag(a.status, out_of_fp16(amax));
     return;
   }
   uint32_t voff[ROWS];
@@ -392,8 +399,10 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_kernel(const Conv2dArgs a) {
         const int cu = half * 32 + (r & 3) + 8 * (r >> 2);     // + 4 * khalf, which rides in voff
         rv[rr][half][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, voff[rr], cbase_o + cu * plane_ob, 0));
       }
+  float amax = 0.f;         // range status (adx_common.h: fp16_amax)
 #pragma unroll
-  for (int rr = 0; rr < ROWS; ++rr)
+  for (int rr = 0; rr < ROWS; ++rr) {
+    float lm = 0.f;        // this row's values; only a pixel of the map counts
 #pragma unroll
     for (int half = 0; half < 2; ++half)
 #pragma unroll
@@ -404,13 +413,18 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_kernel(const Conv2dArgs a) {
         v = v * ss[cl] + ss[kHsCout + cl];
         v += rv[rr][half][r];
         if (a.relu) v = v > 0.f ? v : 0.f;
+        lm = fp16_amax(lm, v);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), yrsrc, voff[rr], cbase_o + cu * plane_ob, 0);
         if (DS) {    // downsample branch: BN only (resnet.py:230-231), no ReLU, no residual
           const float d = (adm[rr][half][r] + adl[rr][half][r] * (1.f / kLoScale)) * xs_inv;
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, d * ss[2 * kHsCout + cl] + ss[3 * kHsCout + cl]),
-                                                drsrc, voff[rr], cbase_o + cu * plane_ob, 0);
+          const float dv = d * ss[2 * kHsCout + cl] + ss[3 * kHsCout + cl];
+          lm = fp16_amax(lm, dv);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, dv), drsrc, voff[rr], cbase_o + cu * plane_ob, 0);
         }
       }
+    amax = fp16_amax(amax, voff[rr] != kOut ? lm : 0.f);
+  }
+  range_flag(a.status, out_of_fp16(amax));
 }
 
 // ---- 3x3 stride-1, deferred-store pipeline ---------------------------------------------------------------------
@@ -752,6 +766,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(out[2]) : "v"(l1), "s"(inv), "v"(h1));
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(out[3]) : "v"(l1), "s"(inv), "v"(h1));
   };
+  float amax = 0.f;        // range status (adx_common.h: fp16_amax); a.status is null for the partial sums of a split reduction
   if constexpr (YCELLS) {
     // cell output (cells_store32); the residual is fetched first: as cells, or as fp32 values at the channels the lane owns AFTER the swap
     const uint32_t khoff = (uint32_t)khalf * 2u * cplane;                  // this lane's cells are the odd ones: one cell further
@@ -803,7 +818,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
           }
         }
         cells_store32(v, sst, sst + 64 * CT, half * 32 + 8 * khalf, res8, a.relu != 0, yrsrc, vcell[rr],
-                      cell0 + (uint32_t)(half * 4) * 2u * cplane, cplane);
+                      cell0 + (uint32_t)(half * 4) * 2u * cplane, cplane, amax);
       }
   } else {
   uint32_t voff[2];
@@ -982,7 +997,8 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
   }
   auto finish = [&](auto relu) {       // two copies of the store loop: the ReLU is one v_max, not a compare + select
 #pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
+    for (int rr = 0; rr < 2; ++rr) {
+      float lm = 0.f;       // this row's values; only a pixel of the map counts
 #pragma unroll
       for (int half = 0; half < 2; ++half)
 #pragma unroll
@@ -993,13 +1009,17 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
           v = v * sst[cl] + sst[64 * CT + cl];
           v += rv[rr][half][r];
           if (decltype(relu)::value) v = __builtin_fmaxf(v, 0.f);   // a NaN becomes 0, like `v > 0 ? v : 0` did
+          lm = fp16_amax(lm, v);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), yrsrc, voff[rr], cbase_o + cu * plane_ob, 0);
         }
+      amax = fp16_amax(amax, inside[rr] ? lm : 0.f);
+    }
   };
   if constexpr (STATS != 2) {
     if (a.relu) finish(std::true_type{}); else finish(std::false_type{});
   }
   }
+  range_flag(a.status, out_of_fp16(amax));
   HS_TRACE(4);
 #ifdef ADX_HS_TRACE
   __builtin_amdgcn_s_waitcnt(0);
@@ -1068,6 +1088,7 @@ constexpr int kStemStageItems = 3 * kStemPH / 7;
 template <bool U8>
 struct StemStager {
   float pv[kStemStageItems][2];
+  float amax = 0.f;     // max |x| over the input values store() splits (adx_common.h: fp16_amax); outside the frame they are 0
   __device__ __forceinline__ void load(const Conv2dArgs& a, __amdgpu_buffer_rsrc_t xrsrc, int r0, int ix, int iy0) {
     constexpr uint32_t kOutside = 0xC0000000u;
     const bool act = r0 < 7;
@@ -1097,7 +1118,7 @@ struct StemStager {
       }
     }
   }
-  __device__ __forceinline__ void store(uint32_t* pd, int r0, int pp) const {
+  __device__ __forceinline__ void store(uint32_t* pd, int r0, int pp) {
     constexpr int PLANEH = 3 * kStemPH * kStemPP;
     if (r0 >= 7) return;
 #pragma unroll
@@ -1106,6 +1127,7 @@ struct StemStager {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const _Float16 hj = (_Float16)pv[k][j];
+        amax = fp16_amax(amax, pv[k][j]);
         h[j] = hj;
         l[j] = (_Float16)((pv[k][j] - (float)hj) * kLoScale);
       }
@@ -1302,6 +1324,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_stem_pool_kernel(const Conv2
   float vm[32];                       // running maximum of this wave's pooled row (wave 0: carried in from the band above)
 #pragma unroll
   for (int j = 0; j < 32; ++j) vm[j] = -INFINITY;
+  float oamax = 0.f;                  // max |x| over the stored pooled values (the input's: sg.amax)
   for (int b = b_begin; b < b_end; ++b) {
 #ifdef ADX_HS_TRACE
     tr_t = (long long)__builtin_readcyclecounter();
@@ -1366,6 +1389,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_stem_pool_kernel(const Conv2
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int cu = half * 32 + (r & 3) + 8 * (r >> 2);       // + 4 * khalf, which rides in voff
+              oamax = fp16_amax(oamax, st ? vm[half * 16 + r] : 0.f);     // (a lane that stores nothing may hold -inf)
               __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, vm[half * 16 + r]), yrsrc, voff, cu * plane_ob, 0);
             }
         } else {      // the pooled map as a cell tensor (conv2d_hs3x3_kernel: XCELLS): layer1's first conv copies cells
@@ -1375,8 +1399,8 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_stem_pool_kernel(const Conv2
           for (int half = 0; half < 2; ++half) {
             float mm[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) mm[r] = vm[half * 16 + r];
-            cells_store32<false>(mm, nullptr, nullptr, 0, nullptr, false, yrsrc, vcell, (uint32_t)(half * 4) * 2u * cplane, cplane);
+            for (int r = 0; r < 16; ++r) mm[r] = st ? vm[half * 16 + r] : 0.f;     // (stores of !st lanes are dropped)
+            cells_store32<false>(mm, nullptr, nullptr, 0, nullptr, false, yrsrc, vcell, (uint32_t)(half * 4) * 2u * cplane, cplane, oamax);
           }
         }
       }
@@ -1400,11 +1424,12 @@ __global__ void __launch_bounds__(256, 2) conv2d_hs_stem_pool_kernel(const Conv2
     tr[5] = __builtin_readcyclecounter();
   }
 #endif
+  range_flag(a.status, out_of_fp16(fp16_amax(sg.amax, oamax)));
 }
 
 // [64][3][7][7] fp32 -> [step][plane][k-half][64][8] fp16 with k = (combo = 2*step + k-half -> channel combo/7,
 // kernel row combo%7; element j = kernel column, the 8th and the 22nd combo are zero)
-__global__ void conv2d_hs_stem_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ p) {
+__global__ void conv2d_hs_stem_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ p, uint32_t* status) {
   const int idx = blockIdx.x * 256 + threadIdx.x;      // over [step][k-half][64][8]
   if (idx >= kStemSteps * 2 * 64 * 8) return;
   const int j = idx & 7, ml = (idx >> 3) & 63, h = (idx >> 9) & 1, step = idx >> 10;
@@ -1416,6 +1441,7 @@ __global__ void conv2d_hs_stem_pack_kernel(const float* __restrict__ w, _Float16
   const size_t cell = ((size_t)(step * 2 + 0) * 2 + h) * 64 + ml;
   p[cell * 8 + j] = hi;
   p[(cell + 128) * 8 + j] = lo;
+  range_flag(status, out_of_fp16(v));
 }
 
 static bool hs_is_stem(const ConvSpec& L) { return L.k == 7 && L.stride == 2 && L.pad == 3 && L.cin == 3 && L.cout == 64; }
@@ -1423,7 +1449,7 @@ static bool hs_is_stem(const ConvSpec& L) { return L.k == 7 && L.stride == 2 && 
 // fp32 [M][Kc][taps] (forward: M = cout, Kc = cin) or its data-gradient view (dgrad: M = original cin,
 // Kc = original cout, taps flipped) -> [M/64][Kc/16][tap][plane][k-half][64][8] fp16
 __global__ void conv2d_hs_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ p, int M, int Kc, int Kreal,
-                                      int taps, int dgrad, size_t total) {
+                                      int taps, int dgrad, size_t total, uint32_t* status) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;   // over [M/64][Kc/16][tap][k-half][64][8]
   if (idx >= total) return;
   const int j = idx & 7;
@@ -1442,6 +1468,7 @@ __global__ void conv2d_hs_pack_kernel(const float* __restrict__ w, _Float16* __r
   const size_t cell = ((((size_t)(ct * nchunks + chunk) * taps + tap) * 2 + 0) * 2 + h) * 64 + ml;
   p[cell * 8 + j] = hi;
   p[(cell + 128) * 8 + j] = lo;     // plane 1 is 2 * 64 cells further
+  range_flag(status, out_of_fp16(v));
 }
 
 // The same for up to kHsPackJobs weight tensors in ONE launch (the training step re-lays every conv weight every step: 36
@@ -1522,13 +1549,13 @@ bool conv2d_hs_pack_batchable(const ConvSpec& c, int dgrad) { return conv2d_hs_e
 
 int conv2d_hs_pack(const ConvSpec& c, const float* w, void* packed, int dgrad, hipStream_t s) {
   if (hs_is_stem(c) && !dgrad) {
-    conv2d_hs_stem_pack_kernel<<<dim3(ceil_div(kStemSteps * 2 * 64 * 8, 256)), dim3(256), 0, s>>>(w, (_Float16*)packed);
+    conv2d_hs_stem_pack_kernel<<<dim3(ceil_div(kStemSteps * 2 * 64 * 8, 256)), dim3(256), 0, s>>>(w, (_Float16*)packed, conv2d_status());
     ADX_LAUNCH_CHECK();
     return ADX_OK;
   }
   const size_t total = (size_t)c.cout * c.cin_pad * c.k * c.k;
   conv2d_hs_pack_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(
-      w, (_Float16*)packed, c.cout, c.cin_pad, c.cin, c.k * c.k, dgrad, total);
+      w, (_Float16*)packed, c.cout, c.cin_pad, c.cin, c.k * c.k, dgrad, total, conv2d_status());
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
@@ -1626,6 +1653,7 @@ int conv2d_hs_stem_pool(const ConvSpec& L, const float* x, const float* w, const
   a.KH = 7; a.KW = 7; a.stride = 2; a.pad = 3; a.relu = 1;
   a.cin_pad = L.cin_pad; a.cc = L.cc;
   a.y_cells = y_cells;
+  a.status = conv2d_status();
   return frames_u8 != nullptr ? hs_stem_pool_launch<true>(a, s) : hs_stem_pool_launch<false>(a, s);
 }
 
@@ -1643,6 +1671,7 @@ int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const floa
   a.cin_pad = c1.cin_pad; a.cc = c1.cc;
   a.x_cells = x_cells;
   a.y_cells = y_cells;
+  a.status = conv2d_status();
   (void)ds;
   return conv2d_hs_launch(c1, a, s);
 }
@@ -1652,9 +1681,9 @@ int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const floa
 __global__ void __launch_bounds__(256) conv2d_split_reduce_kernel(const float* __restrict__ part, size_t part_stride, int nparts,
                                                                   const float* __restrict__ scale, const float* __restrict__ shift,
                                                                   const float* __restrict__ res, float* __restrict__ y,
-                                                                  int cout, int plane4, size_t total4, int relu) {
+                                                                  int cout, int plane4, size_t total4, int relu, uint32_t* status) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total4) return;
+  if (i >= total4) return;      // (a whole wave, or the tail lanes of the last one: range_flag's ballot skips them)
   const int c = (int)((i / plane4) % cout);
   f32x4 v = reinterpret_cast<const f32x4*>(part)[i];
   for (int p0 = 1; p0 < nparts; p0 += 8) {        // eight loads in flight, added in index order
@@ -1673,6 +1702,10 @@ __global__ void __launch_bounds__(256) conv2d_split_reduce_kernel(const float* _
     for (int k = 0; k < 4; ++k) v[k] = __builtin_fmaxf(v[k], 0.f);
   }
   reinterpret_cast<f32x4*>(y)[i] = v;
+  float amax = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) amax = fp16_amax(amax, v[k]);
+  range_flag(status, out_of_fp16(amax));
 }
 
 // fp32-layout launches of a whole batch tile the virtual row too (conv2d_hs3x3_kernel: VR) -- training forward / data gradient
@@ -1775,12 +1808,12 @@ static int hs3x3_launch(Conv2dArgs a, hipStream_t s) {
     if (S > 1) {
       Conv2dArgs c = a;
       c.ksplit = S; c.cper = nchunks / S; c.part_stride = out_floats;
-      c.scale = nullptr; c.shift = nullptr; c.res = nullptr; c.relu = 0;
+      c.scale = nullptr; c.shift = nullptr; c.res = nullptr; c.relu = 0; c.status = nullptr;
       conv2d_hs3x3_kernel<MODE><<<dim3((unsigned)(grid * S)), dim3(NT), lds, s>>>(c);
       ADX_LAUNCH_CHECK();
       const size_t total4 = out_floats / 4;
       conv2d_split_reduce_kernel<<<dim3((unsigned)ceil_div((long)total4, 256L)), dim3(256), 0, s>>>(
-          a.part, out_floats, S, a.scale, a.shift, a.res, a.y, a.Cout, a.OH * a.OW / 4, total4, a.relu);
+          a.part, out_floats, S, a.scale, a.shift, a.res, a.y, a.Cout, a.OH * a.OW / 4, total4, a.relu, a.status);
       ADX_LAUNCH_CHECK();
       return ADX_OK;
     }

@@ -206,6 +206,7 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
+  bool bad = false;        // range flag over every tile's stored cells (adx_common.h: fp16_amax, range_flag)
   for (;;) {       // tiles of this workgroup
   // Everything per-lane the stage loop needs is RE-DERIVED here from the thread id through an opaque zero instead of living in
   // registers across the epilogue (which needs every register it can get: 128 accumulators + the residual cells): ~100 VALU
@@ -521,6 +522,7 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
     }
   const float* sc = ss + slab * 64;
   const float* sh = ss + 128 + slab * 64;
+  float am[2] = {0.f, 0.f};        // per row of the lane: max |x| over its stored values (adx_common.h: fp16_amax)
 #pragma unroll
   for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
@@ -547,6 +549,7 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
       for (int i = 0; i < 8; ++i) {
         const float tsum = o[i] + r8[i];
         o[i] = a.relu ? __builtin_fmaxf(tsum, 0.f) : tsum;
+        am[rr] = fp16_amax(am[rr], o[i]);
       }
       u32x4 hi, lo;
       split8(o, 1.f, hi, lo);
@@ -557,12 +560,15 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
       // store (conv2d_hs.hip: cells_store32); keep both operands alive across one wait state
       asm volatile("s_nop 0" ::"v"(hi), "v"(lo));
     }
+  // only pixels of the map count: the shared zero column of the virtual row and the lanes past the last image store nothing
+  bad |= ((vcell[0] != kOutside) & out_of_fp16(am[0])) | ((vcell[1] != kOutside) & out_of_fp16(am[1]));
   }
   // ---- on to this workgroup's next tile: its first chunk and first tap are in LDS already ----
   if (!has_next) break;
   if constexpr (TRAIN != 0) __syncthreads();        // every wave is done with this tile's statistics area (patch buffer 1)
   sp = sp_next; tx = ntx; ty = nty; oy0 = n_oy0; vx0 = n_vx0;
   }
+  range_flag(a.status, bad);
 }
 
 // a training-forward launch (cells in, fp32 + statistics out) the TRAIN variant serves

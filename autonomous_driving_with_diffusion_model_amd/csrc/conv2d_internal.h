@@ -79,6 +79,8 @@ struct Conv2dArgs {
   int vw;       // y_cells: columns of one image in the virtual row the column tiles run over (W + 1: the images side by side with
                 // one shared all-zero column between neighbours; W for a single image)
   float inv_vw; // 1 / vw
+  // inference executor only: the status word of the launch's layer group (adx_common.h: range_flag), or null
+  uint32_t* status = nullptr;
 };
 
 // activation formats of one launch of the inference executor (bits)
@@ -101,6 +103,9 @@ struct adx_resnet {
   hipStream_t side[kMaxSub - 1] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[kMaxSub - 1] = {nullptr, nullptr, nullptr};
   int side_device = -1;
+  // range status (include/adx.h: adx_resnet_set_status): nblocks + 3 caller-owned device words, or null --
+  // [0] stem (+ pool), [1 + b] BasicBlock b, [1 + nblocks] fc, [2 + nblocks] the weight images of adx_resnet_pack
+  uint32_t* status = nullptr;
 };
 
 namespace adx {
@@ -169,6 +174,10 @@ int conv2d_hs_dgrad_s2(const float* w, const float* dy, float* dx, int accumulat
 // scratch for split reductions of the launches issued by this thread until it is cleared (a region of the calling
 // executor's workspace, consumed in stream order)
 void conv2d_set_split_scratch(float* p, size_t floats);
+// the status word (include/adx.h: adx_resnet_set_status) the split-fp16 launches and weight packs issued by this thread set
+// until it is cleared (null: none); the inference executor points it at the word of the layer group it is issuing
+void conv2d_set_status(uint32_t* word);
+uint32_t* conv2d_status();
 // stem conv + BN + ReLU + MaxPool2d(3, 2, 1) in one pass: writes only the pooled map [N][64][PH][PW]
 int conv2d_hs_stem_pool(const ConvSpec& L, const float* x, const float* w, const float* scale, const float* shift,
                         float* pooled, int N, int H, int W, hipStream_t s, const uint8_t* frames_u8 = nullptr,
@@ -204,6 +213,6 @@ inline int conv_out_dim(int h, int k, int s, int p) { return (h + 2 * p - k) / s
 int conv2d_range_check(const char* what, int index, const float* t, size_t floats, bool cells, hipStream_t s);
 int maxpool_launch(const float* x, float* y, int planes, int H, int W, int OH, int OW, hipStream_t s);
 int avgpool_fc_launch(const float* x, const float* fw, const float* fb, float* out, int batch, int C, int HW, int out_dim,
-                      hipStream_t s, int x_cells = 0);
+                      hipStream_t s, int x_cells = 0, uint32_t* status = nullptr);
 
 }  // namespace adx

@@ -45,4 +45,9 @@ int tconv_hs_forward(const adx_tconv_desc* d, const adx_tconv_io* io, hipStream_
 int tconv_hs_forward_pair(const adx_tconv_desc* da, const adx_tconv_io* ioa, const adx_tconv_desc* db,
                           const adx_tconv_io* iob, hipStream_t s);
 
+// the range-status word (include/adx.h: adx_unet_set_status) the split-fp16 temporal launches and weight packs issued by this
+// thread set until it is cleared (null: none); adx_unet_forward / adx_unet_pack point it at the layer group they are issuing
+void tconv_set_status(uint32_t* word);
+uint32_t* tconv_status();
+
 }  // namespace adx

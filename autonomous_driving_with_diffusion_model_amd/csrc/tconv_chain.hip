@@ -88,6 +88,7 @@ __device__ __forceinline__ void ch_merge(float& m, float& s, float mo, float so,
 // Chain input: global [B][C][L] (two sources = skip concat, arbitrary strides) -> split cells, rows = (sample, position);
 // channels beyond the real ones (inputs are padded to >= 32) are zero cells
 __device__ __forceinline__ void ch_stage_input(const ChainArgs& ca, u32x4* cells, int b0, int tid) {
+  float amax = 0.f;     // every value split here: the launch's range status (adx_common.h: fp16_amax, range_flag)
   const int lin = ca.in_len, cin = ca.in_c0 + ca.in_c1;
   const int ncell = ca.in_cpad >> 3, pitch = 2 * ncell + 1;
   const int rows = ca.bt * lin;
@@ -116,7 +117,7 @@ __device__ __forceinline__ void ch_stage_input(const ChainArgs& ca, u32x4* cells
       for (int p = 0; p < 4; ++p) {
         float t8[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) t8[j] = v[j][p];
+        for (int j = 0; j < 8; ++j) { t8[j] = v[j][p]; amax = fp16_amax(amax, t8[j]); }
         h8 hi, lo;
         ch_split8(t8, hi, lo);
         u32x4* dst = cells + (sb * lin + 4 * q + p) * pitch + 2 * oc;
@@ -143,6 +144,8 @@ __device__ __forceinline__ void ch_stage_input(const ChainArgs& ca, u32x4* cells
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         if (!(8 * oc + j < cin && b < ca.batch)) t8[j] = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) amax = fp16_amax(amax, t8[j]);
       h8 hi, lo;
       ch_split8(t8, hi, lo);
       u32x4* dst = cells + row * pitch + 2 * oc;
@@ -151,6 +154,7 @@ __device__ __forceinline__ void ch_stage_input(const ChainArgs& ca, u32x4* cells
     }
   }
   for (int it = tid; it < pitch; it += kChNT) cells[rows * pitch + it] = u32x4{0u, 0u, 0u, 0u};   // the all-zero row
+  range_flag(ca.status, out_of_fp16(amax));
 }
 
 // buffer descriptor of one 16-channel tile's weight image ([step][plane][64 lanes] x 16 bytes; the residual conv's steps
@@ -382,12 +386,15 @@ __global__ void __launch_bounds__(kChNT) tconv_chain_kernel(const ChainArgs ca) 
     if (flags & kChCells) {
       u32x4* dcells = reinterpret_cast<u32x4*>(smem + st.dst);
       const int lg_nc = st.log2_nct + 1, dp = st.dst_pitch;
+      float amax = 0.f;   // the formed input of the next stage, split here: the launch's range status
       for (int it = tid; it < (st.rows_out << lg_nc); it += kChNT) {
         const int cell = it & ((1 << lg_nc) - 1), row = it >> lg_nc;
         const float* fr = F + row * fp + 8 * cell;
         const f32x4 a0 = *reinterpret_cast<const f32x4*>(fr);
         const f32x4 a1 = *reinterpret_cast<const f32x4*>(fr + 4);
         const float t8[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fp16_amax(amax, t8[j]);
         h8 hi, lo;
         ch_split8(t8, hi, lo);
         u32x4* dst = dcells + row * dp + 2 * cell;
@@ -395,6 +402,7 @@ __global__ void __launch_bounds__(kChNT) tconv_chain_kernel(const ChainArgs ca) 
         dst[1] = __builtin_bit_cast(u32x4, lo);
       }
       if (tid < dp) dcells[st.rows_out * dp + tid] = u32x4{0u, 0u, 0u, 0u};
+      range_flag(ca.status, out_of_fp16(amax));
       __syncthreads();
     }
     CH_STAMP(5 + 4 * si);

@@ -32,6 +32,11 @@
 
 namespace adx {
 
+static thread_local uint32_t* t_tconv_status = nullptr;
+void tconv_set_status(uint32_t* word) { t_tconv_status = word; }
+uint32_t* tconv_status() { return t_tconv_status; }
+
+
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -87,8 +92,11 @@ __device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo) {
 // Stage rows [0, nrows] x channels [c0, c0 + ckc) of this workgroup's samples into LDS as split cells.  Every global load
 // is UNCONDITIONAL (clamped address, value zeroed afterwards): a guarded load makes the compiler wait for it before the
 // next one is issued, i.e. eight dependent round trips per item instead of one.
+// Every value split here is folded into the range status of the launch (adx_common.h: fp16_amax, range_flag; zeros stand
+// in for channels / samples past the real ones).
 template <int NT>
 __device__ __forceinline__ void hs_stage(const TConvArgs& a, const HsArgs& ha, u32x4* cells, int c0, int ckc, int b0, int tid) {
+  float amax = 0.f;
   const int batch = a.io.batch;
   const int pitch = ha.pitch16;
   const int ncell = ckc >> 3;
@@ -121,7 +129,7 @@ __device__ __forceinline__ void hs_stage(const TConvArgs& a, const HsArgs& ha, u
       for (int p = 0; p < 4; ++p) {
         float t8[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) t8[j] = v[j][p];
+        for (int j = 0; j < 8; ++j) { t8[j] = v[j][p]; amax = fp16_amax(amax, t8[j]); }
         h8 hi, lo;
         split8(t8, hi, lo);
         u32x4* dst = cells + (sb * a.lin + 4 * q + p) * pitch + 2 * oc;
@@ -155,6 +163,8 @@ __device__ __forceinline__ void hs_stage(const TConvArgs& a, const HsArgs& ha, u
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         if (!(c0 + 8 * oc + j < a.cin && b < batch)) t8[j] = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) amax = fp16_amax(amax, t8[j]);
       h8 hi, lo;
       split8(t8, hi, lo);
       ADX_TSTAMP(10);
@@ -164,6 +174,7 @@ __device__ __forceinline__ void hs_stage(const TConvArgs& a, const HsArgs& ha, u
     }
   }
   for (int it = tid; it < 2 * ncell; it += NT) cells[ha.nrows * pitch + it] = u32x4{0u, 0u, 0u, 0u};
+  range_flag(a.status, out_of_fp16(amax));
 }
 
 // ---- sums over segments of 16 / 32 / 64 consecutive lanes: DPP inside a row of 16, LDS permute across rows ------------
@@ -960,6 +971,7 @@ static int hs_prepare(const adx_tconv_desc* d, const adx_tconv_io* io, HsTile* t
   HsArgs& ha = *hap;
   TConvArgs& a = ha.t;
   a.io = *io;
+  a.status = tconv_status();
   a.kind = d->kind; a.taps = d->taps; a.stride = d->stride; a.pad = d->pad;
   a.c0 = d->c0; a.cin = d->c0 + d->c1; a.cout = d->cout; a.lin = d->lin; a.lout = d->lout;
   a.lin_valid = d->lin; a.lout_valid = d->lout;

@@ -28,6 +28,7 @@ struct TConvArgs {
   int ncb, nkb;
   int bt, ct, log2_ct, pl, lp, rs, ck, ntiles, cin_pad;
   int dense;  // both inputs are plain [B][C][L] tensors with lin % 4 == 0: 16-byte staging loads
+  uint32_t* status = nullptr;   // split-fp16 kernels: the range-status word of the launch's layer group (adx_common.h: range_flag)
   int lin_valid, lout_valid;   // real lengths (<= lin, lout): adx_tconv_desc::lin_valid
 };
 

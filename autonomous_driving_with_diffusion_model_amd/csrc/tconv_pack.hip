@@ -1,5 +1,6 @@
 #include <vector>
 
+#include "tconv_internal.h"
 #include "tconv_pack.h"
 
 namespace adx {
@@ -10,6 +11,7 @@ constexpr int kMaxJobs = 56;          // 56 x 64 bytes + header: inside the 4 KB
 struct PackTable {
   PackJob job[kMaxJobs];
   int n;
+  uint32_t* status;     // range-status word of the split weight images ("weights"), or null
 };
 static_assert(sizeof(PackJob) == 64, "job layout");
 static_assert(sizeof(PackTable) <= 4000, "kernel-argument segment");
@@ -75,6 +77,7 @@ __global__ void __launch_bounds__(256) pack_many_kernel(const PackTable t) {
   _Float16* dst = reinterpret_cast<_Float16*>(J.out) + dst_blk * 1024 + ln * 8 + j;
   dst[0] = h;
   dst[512] = l;
+  range_flag(t.status, out_of_fp16(v));
 }
 
 thread_local bool g_open = false;
@@ -85,6 +88,7 @@ int launch_jobs(const PackJob* jobs, int n, hipStream_t s) {
   while (i < n) {
     PackTable t;
     t.n = 0;
+    t.status = tconv_status();
     uint32_t blocks = 0;
     while (i < n && t.n < kMaxJobs) {
       PackJob j = jobs[i++];

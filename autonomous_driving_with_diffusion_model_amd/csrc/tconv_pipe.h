@@ -26,6 +26,7 @@ struct PipeStage {
   int add_early;           // add_kind 2 only: the residual was written by an EARLIER launch (requested before the wait)
   int add_kind;            // 0 none; 1 time bias add[sample * add_stride + c]; 2 residual [rows][C][L]; 3 residual [rows x L][C]
   int pub_kind;            // 0 not written; 1 as [rows][C][L] (a skip / the run's output); 2 as [rows x L][C] (a later residual)
+  uint32_t* status;        // range-status word of this conv's layer group (adx_common.h: range_flag), or null
 };
 
 struct PipeArgs {

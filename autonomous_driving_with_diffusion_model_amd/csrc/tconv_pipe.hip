@@ -41,6 +41,7 @@
 #include <mutex>
 
 #include "adx_common.h"
+#include "tconv_internal.h"
 #include "tconv_pipe.h"
 
 namespace adx {
@@ -110,7 +111,7 @@ size_t pipe_packed_floats(int C, int taps, int pad, int L) {
 // weight image: [rank = cout / 16][step = (live tap, cin / 32)][plane hi | lo][lane][8 halfs]; lane (n = lane & 15, kg = lane >> 4)
 // holds W[16 rank + n][32 c32 + 8 kg + j][tap] -- the B fragment of v_mfma_f32_16x16x32_f16
 __global__ void __launch_bounds__(256) pipe_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ packed, int C, int taps,
-                                                         int tap0, int steps, size_t total) {
+                                                         int tap0, int steps, size_t total, uint32_t* status) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int j = idx & 7, lane = (idx >> 3) & 63, plane = (idx >> 9) & 1;
@@ -121,6 +122,7 @@ __global__ void __launch_bounds__(256) pipe_pack_kernel(const float* __restrict_
   const float v = w[((size_t)n * C + cin) * taps + tap0 + ti];
   const _Float16 hi = (_Float16)v;
   packed[idx] = plane == 0 ? hi : (_Float16)((v - (float)hi) * kPipeLoScale);
+  range_flag(status, out_of_fp16(v));
 }
 
 // the same image from the K-split kernel's image of the layer (tconv_hs.hip: [cout / 32][tap x cin / 16][plane][64 lanes][8 halfs],
@@ -172,7 +174,7 @@ int pipe_pack(const float* w, float* packed, int C, int taps, int pad, int L, hi
   const int steps = nt * (C / 32);
   const size_t total = (size_t)(C / kPipeCh) * steps * 2 * 64 * 8;
   pipe_pack_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s>>>(w, reinterpret_cast<_Float16*>(packed), C, taps, t0,
-                                                                              steps, total);
+                                                                              steps, total, tconv_status());
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
@@ -489,7 +491,8 @@ __global__ void __launch_bounds__(kPipeNT) tconv_pipe_kernel(const PipeArgs a) {
   }
   if (!conv) return;                                                      // the finisher is done: the kernel boundary publishes its stores
 
-  // ---- (5) split into hi / lo cells: item = (row, 8-channel octet) ---------------------------------------------------------------
+  // ---- (5) split into hi / lo cells: item = (row, 8-channel octet); every value folded into the stage's range status ------------
+  float amax = 0.f;
   for (int it = tid; it < M * ncell; it += kPipeNT) {
     const int m = it / ncell, oc = it - m * ncell;
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(xf + it * 8), v1 = *reinterpret_cast<const f32x4*>(xf + it * 8 + 4);
@@ -497,6 +500,7 @@ __global__ void __launch_bounds__(kPipeNT) tconv_pipe_kernel(const PipeArgs a) {
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
       const float x = jj < 4 ? v0[jj & 3] : v1[jj & 3];
+      amax = fp16_amax(amax, x);
       const _Float16 h = (_Float16)x;
       hi[jj] = h;
       lo[jj] = (_Float16)((x - (float)h) * kPipeLoScale);
@@ -504,6 +508,7 @@ __global__ void __launch_bounds__(kPipeNT) tconv_pipe_kernel(const PipeArgs a) {
     cells[m * pitch + 2 * oc] = __builtin_bit_cast(u32x4, hi);
     cells[m * pitch + 2 * oc + 1] = __builtin_bit_cast(u32x4, lo);
   }
+  range_flag(S.status, out_of_fp16(amax));
   __syncthreads();
   PIPE_STAMP(7);
 

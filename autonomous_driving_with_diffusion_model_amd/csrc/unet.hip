@@ -20,6 +20,13 @@
 
 namespace adx {
 
+// the temporal launches issued between construction and destruction write the given range-status word (tconv_set_status)
+struct TconvStatusScope {
+  explicit TconvStatusScope(uint32_t* w) { tconv_set_status(w); }
+  void set(uint32_t* w) { tconv_set_status(w); }
+  ~TconvStatusScope() { tconv_set_status(nullptr); }
+};
+
 static int pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 static adx_tconv_desc conv_desc(int kind, int taps, int stride, int pad, int c0, int c1, int cout, int lin, int lout,
@@ -560,6 +567,26 @@ void adx_unet_destroy(adx_unet* u) {
 
 int adx_unet_num_params(const adx_unet* u) { return u ? u->n_params : 0; }
 
+int32_t adx_unet_status_words(const adx_unet* u) {
+  ADX_REQUIRE(u != nullptr, "adx_unet_status_words: null handle");
+  return 2 * u->n_levels + 2;
+}
+
+int adx_unet_set_status(adx_unet* u, uint32_t* words) {
+  ADX_REQUIRE(u != nullptr, "adx_unet_set_status: null handle");
+  u->status = words;
+  return ADX_OK;
+}
+
+const char* adx_unet_status_name(const adx_unet* u, int32_t g) {
+  static const char* const kDown[8] = {"down0", "down1", "down2", "down3", "down4", "down5", "down6", "down7"};
+  static const char* const kUp[8] = {"up0", "up1", "up2", "up3", "up4", "up5", "up6", "up7"};
+  if (u == nullptr) { set_error("adx_unet_status_name: null handle"); return nullptr; }
+  const int n = u->n_levels;
+  if (g < 0 || g >= 2 * n + 2) { set_error("adx_unet_status_name: group %d outside [0, %d)", g, 2 * n + 2); return nullptr; }
+  return g < n ? kDown[g] : g == n ? "mid" : g < 2 * n ? kUp[g - n - 1] : g == 2 * n ? "head" : "weights";
+}
+
 size_t adx_unet_packed_bytes(const adx_unet* u) { return u ? u->packed_floats * sizeof(float) : 0; }
 
 int adx_unet_pack(adx_unet* u, const float* const* P, int32_t n_params, const float* freqs, void* packed,
@@ -573,6 +600,7 @@ int adx_unet_pack(adx_unet* u, const float* const* P, int32_t n_params, const fl
   float* base = (float*)packed;
   const int dim = u->cfg.dim;
   int rc = ADX_OK;
+  TconvStatusScope status_scope(u->status_word(2 * u->n_levels + 1));     // "weights"; outlives the pack queue's flush
   PackQueueScope pack_scope;   // every weight image of the stack in one table-driven launch (tconv_pack.h), flushed below
   for (auto& b : u->blocks) {
     if (rc == ADX_OK) rc = pack_layer(b.a, P, base, s);
@@ -804,6 +832,9 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
   float* const attn_qkv = wl.attn_o > wl.attn_qkv ? ws + wl.attn_qkv : nullptr;
   float* const attn_o = wl.end > wl.attn_o ? ws + wl.attn_o : nullptr;
   ScratchScope scratch_scope(split_scratch, kSplitTickets ? split_tickets : nullptr);
+  // range status: the trajectory x and the time bias count as down level 0 (the first launches that split them)
+  const int nl = u->n_levels;
+  TconvStatusScope status_scope(u->status_word(0));
   bool tickets_pending = kSplitTickets;   // still to be cleared by this call
   if (tickets_pending && !(io->time_bias != nullptr && u->down_chains[0].valid)) {
     const int rc0 = pipe_tickets_reset(split_tickets, (int)kTicketWords, kEpochSlot, s);     // zeroes them and draws this forward's number
@@ -891,6 +922,7 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     for (int k = 0; k < a.n_stages; ++k)
       if ((a.st[k].flags & kChOut) && dense4(*outs[(a.st[k].flags >> 12) & 1])) a.st[k].flags |= kChOutVec;
     a.batch = rows;
+    a.status = tconv_status();
     if (tickets_pending) {
       a.zero_words = split_tickets; a.n_zero = (int)kTicketWords;
       a.epoch_ctr = pipe_epoch_counter(false); a.epoch_slot = kEpochSlot;
@@ -905,6 +937,7 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
   for (int i = 0; i < n; ++i) {
     const ResBlock& B0 = u->blocks[bi++];
     const ResBlock& B1 = u->blocks[bi++];
+    status_scope.set(u->status_word(i));
     if (u->down_chains[i].valid) {
       const Act skip = dense(skips[i], B1.cout, B1.len);
       if (i < n - 1) {
@@ -951,6 +984,7 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
       for (int k = 0; k < 7; ++k) {
         pa.st[k].w = base + run[k]->o_pw;
         pa.st[k].bias = base + run[k]->o_b;
+        pa.st[k].status = u->status_word(k < 3 ? i : nl);       // convs 0-2: this level; 3-6: the mid blocks
       }
       for (int k = 1; k <= 7; ++k) {                               // stage k forms its input from conv k - 1's records
         pa.st[k].gamma = base + run[k - 1]->o_g;
@@ -998,6 +1032,7 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
       cur = dense(y, dn.d.cout, dn.d.lout);
     }
   }
+  status_scope.set(u->status_word(nl));
   for (int k = 0; k < 2 && !pipe_done; ++k) {  // mid_block1, mid_block2
     const ResBlock& B = u->blocks[bi++];
     float* y = next_buf();
@@ -1016,6 +1051,7 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     const ResBlock& B0 = u->blocks[bi++];
     const ResBlock& B1 = u->blocks[bi++];
     // h.pop(): the deepest skip first; h[0] is pushed but never popped (temporal.py:226-227)
+    status_scope.set(u->status_word(nl + 1 + i));     // (a chained last up level carries the head: its splits count here)
     const Act skip = dense(skips[n - 1 - i], B0.c1, B0.len);
     if (u->up_chains[i].valid) {
       const ChainPlan& cp = u->up_chains[i];
@@ -1053,6 +1089,7 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     cur = dense(y2, up.d.cout, up.d.lout);
   }
   if (!head_done) {  // final_conv / act_conv: Conv1dBlock + 1x1, written back as [rows][H][out_ch] (temporal.py:233-235,243-244)
+    status_scope.set(u->status_word(2 * nl));
     float* y = next_buf();
     const ConvLayer& h0 = u->head0;
     rc = run_conv(h0, base, cur, nullptr, nullptr, 0, nullptr, y, (int64_t)h0.d.cout * h0.d.lout, h0.d.lout, 1, rows, s);
@@ -1091,6 +1128,7 @@ int adx_unet_time_conditioning(adx_unet* u, const void* packed, void* workspace,
   float* ws = (float*)workspace;                    // te, mc (adx_unet_time_conditioning_workspace_bytes)
   float* te = ws;
   float* mc = ws + align64((size_t)rows * dim);
+  TconvStatusScope status_scope(u->status_word(0));     // the time bias counts as down level 0
   rc = time_conditioning(u, (const float*)packed, io, rows, te, mc, time_bias, s);
   if (rc != ADX_OK) return rc;
   if (time_embed != nullptr)

@@ -87,5 +87,9 @@ struct adx_unet {
   bool pipe_ok = false;
   // MODEL.USE_ATTN: one block per down level, then mid_attn, then one per up level (execution order); empty when off
   std::vector<adx::AttnLayer> attn;
+  // range status (include/adx.h: adx_unet_set_status): 2 n_levels + 2 caller-owned device words, or null -- [i] down level i,
+  // [n] mid, [n + 1 + i] up level i, [2 n] head, [2 n + 1] the split weight images of adx_unet_pack
+  uint32_t* status = nullptr;
+  uint32_t* status_word(int g) const { return status != nullptr ? status + g : nullptr; }
 };
 

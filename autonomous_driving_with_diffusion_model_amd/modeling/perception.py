@@ -120,6 +120,11 @@ class PerceptionResNet34(nn.Module):
         self._pass_seen = None
         self._pack_gen = 0            # moves whenever _ensure_packed re-lays the weight images (their key can repeat)
         self._frozen = None           # (weakref(img), token) while a frozen_image context is open
+        # range status (include/adx.h: adx_resnet_set_status): one int32 word per layer group on the device, set by the
+        # split-fp16 kernels when a value they split leaves fp16's range.  A plain attribute, not a buffer: state_dict keys
+        # and parameters() stay the reference's.  Allocated and attached by the first eval pass / pack outside a capture.
+        self._range_words = None
+        self._range_guard = "off"
 
     # -- native object management ------------------------------------------------------------
     def _native(self):
@@ -135,6 +140,78 @@ class PerceptionResNet34(nn.Module):
                 L.lib().adx_resnet_destroy(self._handle)
         except Exception:
             pass
+
+    # -- range status ------------------------------------------------------------------------------------------------------
+    @property
+    def range_guard(self) -> str:
+        """"off" (default): eval passes only record the range status.  "raise": an eager eval pass clears the status words,
+        runs, reads them and raises AdxRangeError naming the groups that left fp16's range (skipped under graph capture)."""
+        return self._range_guard
+
+    @range_guard.setter
+    def range_guard(self, v: str) -> None:
+        if v not in ("off", "raise"):
+            raise ValueError(f"range_guard must be 'off' or 'raise', got {v!r}")
+        self._range_guard = v
+
+    def range_group_names(self):
+        h = self._native()
+        n = L.lib().adx_resnet_status_words(h)
+        if n < 0:
+            L.check(n, "adx_resnet_status_words")
+        return ["perception." + L.lib().adx_resnet_status_name(h, g).decode() for g in range(n)]
+
+    def _attach_status(self, device) -> None:
+        """Allocate the status words on `device` (zeroed) and attach them to the handle.  Never inside a stream capture: the
+        zero fill would become part of the graph and clear the words on every replay."""
+        if self._range_words is not None and self._range_words.device == device:
+            return
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            return
+        h = self._native()
+        n = L.lib().adx_resnet_status_words(h)
+        if n < 0:
+            L.check(n, "adx_resnet_status_words")
+        words = torch.zeros(n, dtype=torch.int32, device=device)
+        L.check(L.lib().adx_resnet_set_status(h, words.data_ptr()), "adx_resnet_set_status")
+        self._range_words = words
+
+    def range_status(self):
+        """Names of the layer groups whose status word is set ([] when none is, or before the first eval pass), e.g.
+        ["perception.block4"].  Synchronises once, after the caller's stream has joined the pass stream."""
+        words = self._range_words
+        if words is None:
+            return []
+        self._join_pass_stream(words.device)
+        vals = words.cpu().tolist()               # the one synchronisation
+        names = self.range_group_names()
+        return [names[g] for g, v in enumerate(vals) if v != 0]
+
+    def _join_pass_stream(self, device) -> None:
+        if self._pass_stream is not None and self._pass_stream.device == device:
+            torch.cuda.current_stream(device).wait_stream(self._pass_stream)
+
+    def clear_range_status(self) -> None:
+        """Zero the status words with an asynchronous fill on the caller's stream (graph-safe: captured, it clears on every
+        replay).  Eagerly, the pass stream joins that fill, so a run-ahead pass cannot record into the words before it."""
+        words = self._range_words
+        if words is None:
+            return
+        words.zero_()
+        # (not while capturing: a wait would fork the pass stream into the capture; a captured pass never runs on it)
+        if (self._pass_stream is not None and self._pass_stream.device == words.device
+                and not torch.cuda.is_current_stream_capturing()):
+            self._pass_stream.wait_stream(torch.cuda.current_stream(words.device))
+
+    def _guarded(self, run):
+        if self._range_guard != "raise" or torch.cuda.is_current_stream_capturing():
+            return run()
+        self.clear_range_status()
+        out = run()
+        bad = self.range_status()
+        if bad:
+            raise L.AdxRangeError(bad)
+        return out
 
     def _backward_events(self, device):
         """One timing-enabled event per gradient group of adx_resnet_backward_events (created once per device; each is recorded
@@ -187,6 +264,7 @@ class PerceptionResNet34(nn.Module):
             return
         h = self._native()
         ts = [L.require_gpu_f32(t.detach(), "perception tensor") for t in self._tensors()]
+        self._attach_status(ts[0].device)       # the pack sets the "weights" word
         n = L.lib().adx_resnet_num_tensors(h)
         assert n == len(ts), (n, len(ts))
         nbytes = L.lib().adx_resnet_packed_bytes(h)
@@ -213,6 +291,10 @@ class PerceptionResNet34(nn.Module):
         if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
             raise L.AdxError("forward_frames expects a uint8 [N, H, W, 3] tensor on the GPU")
         f = frames_u8.contiguous()
+        return self._guarded(lambda: self._forward_frames(f, mean, std))
+
+    def _forward_frames(self, f, mean, std):
+        self._attach_status(f.device)
         self._ensure_packed()
         h = self._native()
         B, H, W, _ = f.shape
@@ -236,6 +318,10 @@ class PerceptionResNet34(nn.Module):
             raise ValueError(f"img must be [B, 3, H, W], got {tuple(img.shape)}")
         if self.training:
             return _PerceptionTrainFn.apply(img, self, *[p for _, p in self.named_parameters()])
+        return self._guarded(lambda: self._forward_eval(img))
+
+    def _forward_eval(self, img):
+        self._attach_status(img.device)
         self._ensure_packed()
         h = self._native()
         B, _, H, W = img.shape

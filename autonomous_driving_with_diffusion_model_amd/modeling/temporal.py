@@ -150,6 +150,10 @@ class TemporalMapUnet(nn.Module):
         self._ws_rows = 0
         self._freqs = None
         self._feat_cache = None  # (weakref(img), L.write_stamp(img), weights_key, feature)
+        # range status of the temporal stack (include/adx.h: adx_unet_set_status), as PerceptionResNet34._range_words: a plain
+        # attribute (state_dict unchanged), allocated and attached by the first pack outside a capture
+        self._range_words = None
+        self._range_guard = "off"
 
     # -- native object management --------------------------------------------------------------
     def _native(self):
@@ -194,6 +198,57 @@ class TemporalMapUnet(nn.Module):
         if hasattr(self, "state_pred"):
             self.state_pred.invalidate()
 
+    # -- range status of the split-fp16 kernels: the perception pass's groups and the temporal stack's ----------------------
+    @property
+    def range_guard(self) -> str:
+        """"off" (default) or "raise": an eager eval forward clears the status words, runs, reads them and raises AdxRangeError
+        naming the groups that left fp16's range (skipped under graph capture; GraphedSampler checks around its replays)."""
+        return self._range_guard
+
+    @range_guard.setter
+    def range_guard(self, v: str) -> None:
+        if v not in ("off", "raise"):
+            raise ValueError(f"range_guard must be 'off' or 'raise', got {v!r}")
+        self._range_guard = v
+
+    def range_group_names(self):
+        h = self._native()
+        n = L.lib().adx_unet_status_words(h)
+        if n < 0:
+            L.check(n, "adx_unet_status_words")
+        return self.perception.range_group_names() + ["unet." + L.lib().adx_unet_status_name(h, g).decode() for g in range(n)]
+
+    def _attach_status(self, device) -> None:
+        if self._range_words is not None and self._range_words.device == device:
+            return
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            return
+        h = self._native()
+        n = L.lib().adx_unet_status_words(h)
+        if n < 0:
+            L.check(n, "adx_unet_status_words")
+        words = torch.zeros(n, dtype=torch.int32, device=device)
+        L.check(L.lib().adx_unet_set_status(h, words.data_ptr()), "adx_unet_set_status")
+        self._range_words = words
+
+    def range_status(self):
+        """Names of the layer groups whose values left fp16's range since the last clear, e.g. ["perception.block4",
+        "unet.up1"].  One synchronisation, after the caller's stream has joined the perception pass stream."""
+        p = self.perception
+        parts = [w for w in (p._range_words, self._range_words) if w is not None]
+        if not parts:
+            return []
+        p._join_pass_stream(parts[0].device)
+        vals = torch.cat([w.to(parts[0].device) for w in parts]).cpu().tolist()     # the one synchronisation
+        names = (p.range_group_names() if p._range_words is not None else []) + \
+            (self.range_group_names()[len(p.range_group_names()):] if self._range_words is not None else [])
+        return [names[g] for g, v in enumerate(vals) if v != 0]
+
+    def clear_range_status(self) -> None:
+        self.perception.clear_range_status()
+        if self._range_words is not None:
+            self._range_words.zero_()
+
     def train(self, mode: bool = True):
         if mode != self.training:
             # EMAModel.copy_to / restore write through `.data` around evaluate() (train.py:307-318),
@@ -210,6 +265,7 @@ class TemporalMapUnet(nn.Module):
         return super().load_state_dict(*a, **k)
 
     def _ensure_packed(self, device):
+        self._attach_status(device)           # before the pack: it sets the "weights" word
         key = self._weights_key()
         if key == self._pack_key:
             return
@@ -322,6 +378,16 @@ class TemporalMapUnet(nn.Module):
 
     # -- forward ---------------------------------------------------------------------------------
     def forward(self, x, img, time, cond=None, return_action_and_time_only=False, *, time_cond=None):
+        if self._range_guard != "raise" or self.training or torch.cuda.is_current_stream_capturing():
+            return self._forward(x, img, time, cond, return_action_and_time_only, time_cond=time_cond)
+        self.clear_range_status()
+        out = self._forward(x, img, time, cond, return_action_and_time_only, time_cond=time_cond)
+        bad = self.range_status()
+        if bad:
+            raise L.AdxRangeError(bad)
+        return out
+
+    def _forward(self, x, img, time, cond=None, return_action_and_time_only=False, *, time_cond=None):
         """x [B, T, D]; img [B or 1, 3, H, W]; time int64 [B or 1]; cond None or [B, 2].
 
         time_cond = (TimeConditioning, step index): use the loop's precomputed table instead of (img, time, cond),

@@ -18,6 +18,7 @@ from typing import Callable, Optional
 
 import torch
 
+from ._lib import AdxRangeError
 from .misc.constant import GuidanceType
 
 
@@ -188,13 +189,15 @@ class GraphedSampler:
         self._pointers = self._model_pointers()
 
     def _model_pointers(self):
-        """Addresses of the model-owned buffers the captured launches read and write (workspaces and packed weight
-        images).  The model re-allocates them lazily (a later eager forward at a larger batch or image size, a weight
-        re-pack); a replay over stale addresses would touch freed memory, so `__call__` re-captures when any moved."""
+        """Addresses of the model-owned buffers the captured launches read and write (workspaces, packed weight images and
+        the range status words).  The model re-allocates them lazily (a later eager forward at a larger batch or image size, a
+        weight re-pack, a move to another device); a replay over stale addresses would touch freed memory, so `__call__`
+        re-captures when any moved."""
         m = self.model
         owners = [m, getattr(m, "perception", None), getattr(m, "state_pred", None)]
         return tuple(None if t is None else t.data_ptr()
-                     for o in owners if o is not None for t in (getattr(o, "_ws", None), getattr(o, "_packed", None)))
+                     for o in owners if o is not None
+                     for t in (getattr(o, "_ws", None), getattr(o, "_packed", None), getattr(o, "_range_words", None)))
 
     def reset(self) -> None:
         """Forget the captured graph (call after the model's weights changed: the weight images are packed outside
@@ -217,5 +220,14 @@ class GraphedSampler:
             self._init.copy_(init_trajs)
             if target is not None:
                 self._tgt.copy_(target)
+        # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
+        # check is skipped while the graph is captured
+        guard = getattr(self.model, "range_guard", "off") == "raise"
+        if guard:
+            self.model.clear_range_status()
         self._graph.replay()
+        if guard:
+            bad = self.model.range_status()
+            if bad:
+                raise AdxRangeError(bad)
         return self._out.clone()

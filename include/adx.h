@@ -144,6 +144,16 @@ void adx_unet_destroy(adx_unet* u);
 /* number of parameter tensors expected by adx_unet_pack (the non-perception parameters,
  * in named_parameters() order; TrajPredict's are accepted but handled by adx_trajpred_*) */
 int adx_unet_num_params(const adx_unet* u);
+/* Range status of the temporal stack, as adx_resnet_set_status for the perception pass: the split-fp16 temporal kernels
+ * (modeling/temporal.py:204-244 and helpers.py's Conv1dBlock / ResidualTemporalBlock in the reference, fp32 there) OR a
+ * nonzero value into the word of the layer group whose launch splits a value with |x| >= 65504 or a NaN -- in staging, or
+ * where a chained / pipelined launch forms the next conv's input.  The value counts where it is split, i.e. at the conv that
+ * reads it.  Groups: i "down<i>" (down level i; the trajectory x and the time bias count as down0), n "mid", n + 1 + i
+ * "up<i>" (a chained last up level carries the head: its splits count there), 2n "head", 2n + 1 "weights" (the split weight
+ * images of adx_unet_pack).  Written by adx_unet_forward, adx_unet_time_conditioning and adx_unet_pack, never by training. */
+int32_t adx_unet_status_words(const adx_unet* u);
+int adx_unet_set_status(adx_unet* u, uint32_t* words /* device, adx_unet_status_words(u) words, or NULL */);
+const char* adx_unet_status_name(const adx_unet* u, int32_t group);
 size_t adx_unet_packed_bytes(const adx_unet* u);
 int adx_unet_pack(adx_unet* u, const float* const* params, int32_t n_params, const float* freqs,
                   void* packed, adx_stream s);
@@ -262,6 +272,21 @@ int adx_resnet_forward(adx_resnet* r, const void* packed, void* workspace, const
 int adx_resnet_forward_u8(adx_resnet* r, const void* packed, void* workspace, const uint8_t* frames_hwc,
                           const float* mean /* [3] */, const float* stdv /* [3] */, int32_t batch, int32_t h, int32_t w,
                           float* feature /* [batch][out_dim] */, adx_stream s);
+/* Range status.  The split-fp16 kernels carry operands as x = hi + lo / 2^11 in fp16, so a value with |x| >= 65504 (or a
+ * NaN) that one of them splits becomes inf / NaN and travels on silently, where the reference's fp32 forward
+ * (modeling/resnet.py:87-102,163-296) stays finite.  With a status buffer attached, every launch of adx_resnet_forward /
+ * adx_resnet_forward_u8 / adx_resnet_pack ORs a nonzero value into the uint32 word of its layer group when it splits or
+ * stores such a value: no synchronisation, graph-capture safe, outputs bit-identical with and without the buffer.
+ * The words are sticky: only the caller clears them (e.g. hipMemsetAsync).  Groups, in this order:
+ *   0 "stem" (conv1 + bn1 + relu + maxpool; the input image's values count here), 1 + b "block<b>" (BasicBlock b, b < 16,
+ *   the numbering of ADX_CHECK_RANGE's message), 17 "fc" (avgpool + fc), 18 "weights" (the split weight images of
+ *   adx_resnet_pack).
+ * adx_resnet_status_words(r) = the number of words (<0 on a null handle); adx_resnet_set_status(r, words) attaches a
+ * device buffer of that many words (NULL detaches); adx_resnet_status_name(r, g) = group g's name (NULL on a bad index).
+ * The training forward (adx_resnet_forward_train) never writes the words; ADX_CHECK_RANGE=1 is unchanged. */
+int32_t adx_resnet_status_words(const adx_resnet* r);
+int adx_resnet_set_status(adx_resnet* r, uint32_t* words /* device, adx_resnet_status_words(r) words, or NULL */);
+const char* adx_resnet_status_name(const adx_resnet* r, int32_t group);
 
 /* Op-level 2-D convolution used by the perception executor (one launch): NCHW fp32,
  * y = [relu]( conv(x, w) * scale[c] + shift[c] [+ res] ); scale/shift = eval-mode BatchNorm2d
