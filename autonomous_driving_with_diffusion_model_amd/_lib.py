@@ -118,6 +118,12 @@ _SIGS = {
     "adx_resnet_tensor_group": (i32, [vp, i32]),
     "adx_resnet_backward_events": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, vp, C.c_size_t, vp, vp, C.POINTER(vp), i32, vp]),
     "adx_resnet_tape_describe": (i32, [vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]),
+    "adx_resnet_bn_layers": (i32, [vp]),
+    "adx_resnet_bn_tensor": (i32, [vp, i32]),
+    "adx_resnet_forward_train_ex": (i32, [vp, C.POINTER(vp), i32, vp, vp, C.c_size_t, vp, i32, i32, i32, vp, vp, i32, C.c_uint64,
+                                          vp]),
+    "adx_resnet_backward_ex": (i32, [vp, C.POINTER(vp), C.POINTER(vp), i32, vp, C.c_size_t, vp, vp, C.c_uint64, C.POINTER(vp), i32,
+                                     vp]),
     "adx_conv2d_packed_bytes": (C.c_size_t, [C.POINTER(Conv2dDesc)]),
     "adx_conv2d_pack": (i32, [C.POINTER(Conv2dDesc), vp, vp, vp]),
     "adx_conv2d_forward": (i32, [C.POINTER(Conv2dDesc), vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),

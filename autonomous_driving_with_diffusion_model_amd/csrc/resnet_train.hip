@@ -206,6 +206,25 @@ __device__ __forceinline__ void bn_finalize_channel(int c, double s0, double s1,
   }
 }
 
+// a FROZEN BatchNorm (its holder in eval mode inside a training forward, include/adx.h: adx_resnet_forward_train_ex): the
+// running statistics -> scale/shift for the apply pass and the tape's mean / rstd, which the backward's re-derived ReLU masks
+// and xhat read back.  Same bn_affine as the batch-statistics finalize; the running buffers are read, never written.
+__global__ void bn_frozen_finalize_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                          const float* __restrict__ running_mean, const float* __restrict__ running_var,
+                                          float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ mean,
+                                          float* __restrict__ rstd, int C) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const float m = running_mean[c];
+  const float r = (float)(1.0 / sqrt((double)running_var[c] + 1e-5));
+  float sc, sh;
+  bn_affine(gamma[c], beta[c], m, r, sc, sh);
+  scale[c] = sc;
+  shift[c] = sh;
+  mean[c] = m;
+  rstd[c] = r;
+}
+
 __global__ void __launch_bounds__(256) bn_apply_kernel(const float* __restrict__ raw, const float* __restrict__ scale,
                                                         const float* __restrict__ shift, const float* __restrict__ res,
                                                         float* __restrict__ out, int C, int HW, size_t total, int relu) {
@@ -318,7 +337,17 @@ __global__ void __launch_bounds__(256) bn_apply_groups_kernel(const float* __res
 constexpr size_t kStatsPartFloats = (size_t)1 << 20;   // per-workgroup partial sums of one conv launch ([C][2][tiles])
 constexpr size_t kAmaxPartials = 4096;   // workgroups of bn_bwd_apply_kernel = partial maxima handed to the dgrad conv
 
+// the affine parameters' gradients are the finished sums themselves (either slot may be null: a frozen parameter)
+__device__ __forceinline__ void bn_affine_grads(const double* __restrict__ sums, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                int C) {
+  for (int c = threadIdx.x; c < C; c += 256) {
+    if (dbeta != nullptr) dbeta[c] = (float)sums[2 * c];
+    if (dgamma != nullptr) dgamma[c] = (float)sums[2 * c + 1];
+  }
+}
+
 // draw = gamma*rstd * (dz - m1 - xhat*m2); also d gamma / d beta (one thread per channel does that part)
+// frozen: the BatchNorm normalised with its running statistics, which do not depend on the batch: m1 = m2 = 0
 __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restrict__ dout, const float* __restrict__ out,
                                                             const float* __restrict__ raw, const float* __restrict__ mean,
                                                             const float* __restrict__ rstd, const float* __restrict__ gamma,
@@ -326,12 +355,12 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restri
                                                             float* __restrict__ dz_out, int C, int HW, size_t total,
                                                             double count, int relu_mask, uint32_t* __restrict__ amax,
                                                             const float* __restrict__ beta, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta, const uint8_t* __restrict__ bits = nullptr) {
+                                                            float* __restrict__ dbeta, const uint8_t* __restrict__ bits = nullptr,
+                                                            int frozen = 0) {
   // grid-stride: a fixed number of workgroups, each leaving max |draw| of its share in amax[blockIdx.x] (bits:
   // monotonic for non-negative floats); the data-gradient conv reduces those partials for its dynamic range
   __shared__ uint32_t red[4];
-  if (blockIdx.x == 0 && dgamma != nullptr)          // the affine parameters' gradients are the finished sums themselves
-    for (int c = threadIdx.x; c < C; c += 256) { dbeta[c] = (float)sums[2 * c]; dgamma[c] = (float)sums[2 * c + 1]; }
+  if (blockIdx.x == 0 && (dgamma != nullptr || dbeta != nullptr)) bn_affine_grads(sums, dgamma, dbeta, C);
   uint32_t b = 0;
   const bool small = total <= 0xFFFFFFFFull;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -355,7 +384,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restri
     }
     if (dz_out != nullptr) dz_out[i] = dz;
     const float xh = (rw - mean[c]) * rstd[c];
-    const float m1 = (float)(sums[2 * c] / count), m2 = (float)(sums[2 * c + 1] / count);
+    const float m1 = frozen ? 0.f : (float)(sums[2 * c] / count), m2 = frozen ? 0.f : (float)(sums[2 * c + 1] / count);
     const float v = gamma[c] * rstd[c] * (dz - m1 - xh * m2);
     draw[i] = v;
     const uint32_t vb = __builtin_bit_cast(uint32_t, v) & 0x7FFFFFFFu;
@@ -383,10 +412,10 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_planes_kernel(const float* _
                                                                    float* __restrict__ dz_out, int C, int HW, int planes,
                                                                    double count, int relu_mask, uint32_t* __restrict__ amax,
                                                                    const float* __restrict__ beta, float* __restrict__ dgamma,
-                                                                   float* __restrict__ dbeta, const uint8_t* __restrict__ bits = nullptr) {
+                                                                   float* __restrict__ dbeta, const uint8_t* __restrict__ bits = nullptr,
+                                                                   int frozen = 0) {
   __shared__ uint32_t red[4];
-  if (blockIdx.x == 0 && dgamma != nullptr)
-    for (int c = threadIdx.x; c < C; c += 256) { dbeta[c] = (float)sums[2 * c]; dgamma[c] = (float)sums[2 * c + 1]; }
+  if (blockIdx.x == 0 && (dgamma != nullptr || dbeta != nullptr)) bn_affine_grads(sums, dgamma, dbeta, C);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int hw4 = HW >> 2;
   uint32_t b = 0;
@@ -395,7 +424,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_planes_kernel(const float* _
     const float mu = mean[c], rs = rstd[c], ga = gamma[c];
     float sc = 0.f, sh = 0.f;
     if (relu_mask == 2) bn_affine(ga, beta[c], mu, rs, sc, sh);
-    const float m1 = (float)(sums[2 * c] / count), m2 = (float)(sums[2 * c + 1] / count);
+    const float m1 = frozen ? 0.f : (float)(sums[2 * c] / count), m2 = frozen ? 0.f : (float)(sums[2 * c + 1] / count);
     const size_t base = (size_t)pl * hw4;
     const f32x4* d4 = reinterpret_cast<const f32x4*>(dout) + base;
     const f32x4* r4 = reinterpret_cast<const f32x4*>(raw) + base;
@@ -455,6 +484,8 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_planes_kernel(const float* _
 //     |draw_c| <= |gamma_c rstd_c| (D + |m1_c| + sqrt(count - 1) |m2_c|).
 // The scale moves the largest such bound into [2^14, 2^15): whatever the bound overshoots costs RANGE below (values smaller than
 // 2^-29 of the bound lose bits), never precision of the values that matter -- fp16 hi + lo keeps 22 bits across 29 octaves.
+// A frozen BatchNorm (running statistics, `frozen` != 0) has m1 = m2 = 0: draw = gamma rstd dz.  Samuelson's inequality does not
+// hold for xhat under running statistics, and it is not needed there: the bound above reduces to |gamma_c rstd_c| D.
 // bn_bwd_consts_kernel: one workgroup per record: per-channel constants [C][8] = {gamma rstd, m1, m2, mean, rstd, mask scale, mask
 // shift, 0}, the affine gradients (the finished sums), and {xs, 1 / xs}.
 __global__ void __launch_bounds__(256) bn_bwd_consts_kernel(const double* __restrict__ sums, const float* __restrict__ mean,
@@ -462,7 +493,7 @@ __global__ void __launch_bounds__(256) bn_bwd_consts_kernel(const double* __rest
                                                              const float* __restrict__ beta, const uint32_t* __restrict__ dmax,
                                                              double count, int C, float* __restrict__ consts,
                                                              float* __restrict__ xscale, float* __restrict__ dgamma,
-                                                             float* __restrict__ dbeta) {
+                                                             float* __restrict__ dbeta, int frozen = 0) {
   // D: the largest of the per-channel maxima (the data-gradient epilogue's path leaves the tensor's maximum in slot 0)
   __shared__ float red[4];
   float dm = 0.f;
@@ -479,10 +510,11 @@ __global__ void __launch_bounds__(256) bn_bwd_consts_kernel(const double* __rest
     const float mu = mean[c], rs = rstd[c], ga = gamma[c];
     float sc, sh;
     bn_affine(ga, beta[c], mu, rs, sc, sh);
-    const float m1 = (float)(sums[2 * c] / count), m2 = (float)(sums[2 * c + 1] / count);
+    const float m1 = frozen ? 0.f : (float)(sums[2 * c] / count), m2 = frozen ? 0.f : (float)(sums[2 * c + 1] / count);
     float* k = consts + (size_t)c * 8;
     k[0] = ga * rs; k[1] = m1; k[2] = m2; k[3] = mu; k[4] = rs; k[5] = sc; k[6] = sh; k[7] = 0.f;
-    if (dgamma != nullptr) { dbeta[c] = (float)sums[2 * c]; dgamma[c] = (float)sums[2 * c + 1]; }
+    if (dbeta != nullptr) dbeta[c] = (float)sums[2 * c];
+    if (dgamma != nullptr) dgamma[c] = (float)sums[2 * c + 1];
     bound = __builtin_fmaxf(bound, __builtin_fabsf(ga * rs) * (D + __builtin_fabsf(m1) + X * __builtin_fabsf(m2)));
   }
 #pragma unroll
@@ -722,7 +754,8 @@ __global__ void __launch_bounds__(256) stem_pool_bn_bwd_kernel(const uint8_t* __
                                                                 float* __restrict__ draw, int C, int H, int W, int OH, int OW,
                                                                 double count, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                                 uint32_t* __restrict__ amax = nullptr, int n_amax = 0,
-                                                                const float* __restrict__ pooled = nullptr) {
+                                                                const float* __restrict__ pooled = nullptr, int frozen = 0) {
+  // frozen (PASS 1): the stem's BatchNorm ran on its running statistics: m1 = m2 = 0 (PASS 0's sums still give d gamma, d beta)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t mx = 0;        // PASS 1: max |draw| of this workgroup (bit pattern), for the split-fp16 weight gradient's range
   const int pl = blockIdx.x, c = pl % C;
@@ -760,15 +793,14 @@ __global__ void __launch_bounds__(256) stem_pool_bn_bwd_kernel(const uint8_t* __
     }
     return;
   }
-  if (PASS == 1 && blockIdx.x == 0 && blockIdx.y == 0 && dgamma != nullptr)
-    for (int k = threadIdx.x; k < C; k += 256) { dbeta[k] = (float)sums[2 * k]; dgamma[k] = (float)sums[2 * k + 1]; }
+  if (PASS == 1 && blockIdx.x == 0 && blockIdx.y == 0 && (dgamma != nullptr || dbeta != nullptr)) bn_affine_grads(sums, dgamma, dbeta, C);
   const uint8_t* cp = code + (size_t)pl * OH * OW;
   const float* gp = dpool + (size_t)pl * OH * OW;
   const float mu = mean[c], rs = rstd[c], ga = gamma[c];
   float sc, sh;
   bn_affine(ga, beta[c], mu, rs, sc, sh);
   float m1 = 0.f, m2 = 0.f;
-  if (PASS == 1) { m1 = (float)(sums[2 * c] / count); m2 = (float)(sums[2 * c + 1] / count); }
+  if (PASS == 1 && !frozen) { m1 = (float)(sums[2 * c] / count); m2 = (float)(sums[2 * c + 1] / count); }
   double s0 = 0.0, s1 = 0.0;
   // PASS 1: a wave applies kStemBwdRows input rows one after the other (rows 4 apart: the workgroup's waves stay on neighbouring rows)
   const int row0 = PASS == 0 ? wave : blockIdx.y * 4 * kStemBwdRows + wave;
@@ -872,11 +904,12 @@ __global__ void __launch_bounds__(256) avgpool_fc_bwd_kernel(const float* __rest
     const float v = dpool[c];
     for (int i = lane; i < HW; i += 64) dst[(size_t)c * HW + i] = v;
   }
-  for (int i = tid; i < out_dim * kPoolSlice; i += 256) {
+  // (dfw / dfb null: a frozen fc)
+  for (int i = tid; i < out_dim * kPoolSlice && dfw != nullptr; i += 256) {
     const int j = i / kPoolSlice, c = i - j * kPoolSlice;
     atomicAdd(dfw + (size_t)j * C + c0 + c, df[j] * pooled[c]);
   }
-  if (c0 == 0)
+  if (c0 == 0 && dfb != nullptr)
     for (int j = tid; j < out_dim; j += 256) atomicAdd(dfb + j, df[j]);
 }
 
@@ -1223,11 +1256,41 @@ struct adx_resnet_tape {
   float* final_map = nullptr; int fh = 0, fw_ = 0;
   float* stats_part = nullptr;    // kStatsPartFloats floats of the forward's workspace: conv-epilogue partial sums (both passes)
   size_t fwd_floats = 0;
+  uint64_t frozen = 0;            // the forward's frozen-BatchNorm mask (adx_resnet_forward_train_ex); the backward must be given the same
 };
 
 using namespace adx;
 
+// BatchNorm layer l (bit l of a frozen mask) -> its conv's index in r->convs.  Layers are in record (forward launch) order: the
+// stem, then per BasicBlock conv1, [downsample], conv2 -- r->convs holds a block as conv1, conv2, [downsample]
+static std::vector<int> bn_layer_convs(const adx_resnet* r) {
+  std::vector<int> v{0};
+  int ci = 1;
+  for (size_t b = 0; b < r->block_has_ds.size(); ++b) {
+    v.push_back(ci);
+    if (r->block_has_ds[b]) v.push_back(ci + 2);
+    v.push_back(ci + 1);
+    ci += r->block_has_ds[b] ? 3 : 2;
+  }
+  return v;
+}
+
+// per conv: its BatchNorm is frozen under `mask`
+static std::vector<char> frozen_convs(const adx_resnet* r, uint64_t mask) {
+  const std::vector<int> lc = bn_layer_convs(r);
+  std::vector<char> f(r->convs.size(), 0);
+  for (size_t l = 0; l < lc.size() && l < 64; ++l) f[lc[l]] = (char)((mask >> l) & 1u);
+  return f;
+}
+
 extern "C" {
+
+int32_t adx_resnet_bn_layers(const adx_resnet* r) { return r ? (int32_t)r->convs.size() : 0; }
+
+int32_t adx_resnet_bn_tensor(const adx_resnet* r, int32_t layer) {
+  if (r == nullptr || layer < 0 || layer >= (int32_t)r->convs.size()) return -1;
+  return r->convs[bn_layer_convs(r)[layer]].t_g;
+}
 
 int adx_resnet_tape_create(adx_resnet_tape** out) {
   ADX_REQUIRE(out != nullptr, "adx_resnet_tape_create: null argument");
@@ -1268,15 +1331,34 @@ size_t adx_resnet_train_workspace_bytes(const adx_resnet* r, int32_t batch, int3
   return (f + 1024) * sizeof(float);
 }
 
+static bool frozen_mask_ok(const adx_resnet* r, uint64_t mask) {
+  const int n = adx_resnet_bn_layers(r);
+  return n >= 64 || (mask >> n) == 0;
+}
+
 // tensors / running buffers as in adx_resnet_pack (state_dict order without num_batches_tracked); the
 // running_mean / running_var entries are UPDATED in place (momentum 0.1) when update_running != 0.
 int adx_resnet_forward_train(adx_resnet* r, const float* const* T, int32_t n_tensors, void* packed, void* workspace,
                              size_t workspace_bytes, const float* img, int32_t batch, int32_t h, int32_t w,
                              float* feature, adx_resnet_tape* tape, int32_t update_running, adx_stream stream) {
+  return adx_resnet_forward_train_ex(r, T, n_tensors, packed, workspace, workspace_bytes, img, batch, h, w, feature, tape,
+                                     update_running, 0, stream);
+}
+
+// frozen_bn: bit l set -> BatchNorm layer l (adx_resnet_bn_tensor's order) normalises with its running statistics, which it
+// leaves untouched (bn_frozen_finalize_kernel: no statistics reduction, no update)
+int adx_resnet_forward_train_ex(adx_resnet* r, const float* const* T, int32_t n_tensors, void* packed, void* workspace,
+                                size_t workspace_bytes, const float* img, int32_t batch, int32_t h, int32_t w,
+                                float* feature, adx_resnet_tape* tape, int32_t update_running, uint64_t frozen_bn,
+                                adx_stream stream) {
   ADX_REQUIRE(r && T && packed && workspace && img && feature && tape, "adx_resnet_forward_train: null argument");
   ADX_REQUIRE(n_tensors == r->n_tensors, "adx_resnet_forward_train: expected %d tensors, got %d", r->n_tensors, n_tensors);
+  ADX_REQUIRE(frozen_mask_ok(r, frozen_bn), "adx_resnet_forward_train: frozen mask 0x%llx names a BatchNorm layer >= %d",
+              (unsigned long long)frozen_bn, adx_resnet_bn_layers(r));
   ADX_REQUIRE(batch >= 1 && h >= 32 && w >= 32, "adx_resnet_forward_train: image too small");
   hipStream_t s = (hipStream_t)stream;
+  const std::vector<char> frozen_conv = frozen_convs(r, frozen_bn);
+  tape->frozen = frozen_bn;
   float* base = (float*)packed;
   // weights change every step: re-lay them here (conv images only; BN is applied from batch statistics) -- the split-fp16
   // images of the 3x3 convs in ONE launch, the stem and the exact-fp32 1x1 images on their own
@@ -1339,7 +1421,12 @@ int adx_resnet_forward_train(adx_resnet* r, const float* const* T, int32_t n_ten
     double* sums = sums_all + (size_t)(&L - r->convs.data()) * 2 * 512;
     float* const run_m = update_running ? const_cast<float*>(T[L.t_m]) : nullptr;
     float* const run_v = update_running ? const_cast<float*>(T[L.t_v]) : nullptr;
-    if (stats_p > 0) {       // partial sums from the conv epilogue: reduce and finish the channel in one launch
+    if (frozen_conv[&L - r->convs.data()]) {
+      // frozen: the running statistics ARE the statistics -- no pass over the conv output, no reduction of the epilogue's
+      // partial sums (the launch above is the same as a train-mode layer's: a cell-layout input needs its statistics epilogue)
+      bn_frozen_finalize_kernel<<<dim3(ceil_div(L.cout, 256)), dim3(256), 0, s>>>(T[L.t_g], T[L.t_b], T[L.t_m], T[L.t_v], scale, shift,
+                                                                                  rec.mean, rec.rstd, L.cout);
+    } else if (stats_p > 0) {       // partial sums from the conv epilogue: reduce and finish the channel in one launch
       stats_reduce_finalize_kernel<<<dim3(L.cout), dim3(256), 0, s>>>(stats_part, sums, stats_p, T[L.t_g], T[L.t_b], scale, shift,
                                                                       rec.mean, rec.rstd, run_m, run_v, (double)batch * HW);
     } else {
@@ -1494,11 +1581,31 @@ int adx_resnet_backward(adx_resnet* r, const float* const* T, float* const* G, i
 int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* const* G, int32_t n_tensors, void* workspace,
                                size_t workspace_bytes, adx_resnet_tape* tape, const float* d_feature, void* const* events,
                                int32_t n_events, adx_stream stream) {
+  return adx_resnet_backward_ex(r, T, G, n_tensors, workspace, workspace_bytes, tape, d_feature, 0, events, n_events, stream);
+}
+
+// G: a NULL conv-weight / gamma / beta / fc slot is a frozen parameter: its gradient is not computed, and nothing below the lowest
+// record that still owns a gradient slot runs (no data gradient, BatchNorm backward or stem pass there).  frozen_bn: the mask the
+// tape's forward ran with; a frozen BatchNorm backpropagates through its affine map only (m1 = m2 = 0 in every apply form).
+int adx_resnet_backward_ex(adx_resnet* r, const float* const* T, float* const* G, int32_t n_tensors, void* workspace,
+                           size_t workspace_bytes, adx_resnet_tape* tape, const float* d_feature, uint64_t frozen_bn,
+                           void* const* events, int32_t n_events, adx_stream stream) {
   ADX_REQUIRE(r && T && G && workspace && tape && d_feature, "adx_resnet_backward: null argument");
-  ADX_REQUIRE(n_tensors == r->n_tensors && !tape->recs.empty(), "adx_resnet_backward: bad tape / tensor count");
+  ADX_REQUIRE(n_tensors == r->n_tensors, "adx_resnet_backward: bad tensor count");
+  ADX_REQUIRE(frozen_mask_ok(r, frozen_bn), "adx_resnet_backward: frozen mask 0x%llx names a BatchNorm layer >= %d",
+              (unsigned long long)frozen_bn, adx_resnet_bn_layers(r));
+  ADX_REQUIRE(tape->frozen == frozen_bn, "adx_resnet_backward: the tape's forward ran with frozen mask 0x%llx, the backward was given 0x%llx",
+              (unsigned long long)tape->frozen, (unsigned long long)frozen_bn);
+  ADX_REQUIRE(!tape->recs.empty(), "adx_resnet_backward: bad tape / tensor count");
   ADX_REQUIRE(events == nullptr || n_events == adx_resnet_backward_groups(r), "adx_resnet_backward_events: %d events, the backward has %d groups",
               n_events, adx_resnet_backward_groups(r));
   hipStream_t s = (hipStream_t)stream;
+  const std::vector<char> frozen_conv = frozen_convs(r, frozen_bn);
+  // the lowest record (forward order) that owns a gradient slot; -1: none (fc at most)
+  auto owns_grad = [&](const ConvSpec& L) { return G[L.t_w] != nullptr || G[L.t_g] != nullptr || G[L.t_b] != nullptr; };
+  int lowest = -1;
+  for (size_t i = 0; i < tape->recs.size() && lowest < 0; ++i)
+    if (owns_grad(*tape->recs[i].L)) lowest = (int)i;
   // group g's event is recorded behind the last launch that writes a gradient of group g (adx_resnet_tensor_group): a
   // reduction of those gradients can start on another stream while the layers below are still being differentiated
   auto mark = [&](int group) -> int {
@@ -1510,7 +1617,8 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
   const size_t n_convs = r->convs.size();
   double* sums_all = reinterpret_cast<double*>(ws.take(n_convs * 2 * 512 * 2));
   ADX_CHECK_HIP(hipMemsetAsync(sums_all, 0, sizeof(double) * n_convs * 2 * 512, s));
-  for (const ConvSpec& L : r->convs) batch_fill_add(G[L.t_w], (size_t)L.cout * L.cin * L.k * L.k);
+  for (const ConvSpec& L : r->convs)
+    if (G[L.t_w] != nullptr) batch_fill_add(G[L.t_w], (size_t)L.cout * L.cin * L.k * L.k);
   {
     const int rf = batch_fill_flush(s);
     if (rf != ADX_OK) return rf;
@@ -1542,9 +1650,9 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
   std::vector<const float*> dgrad_img(r->convs.size(), nullptr);
   {
     std::vector<HsPackJob> jobs;
-    for (auto& rec : tape->recs) {
-      const ConvSpec& L = *rec.L;
-      if (!(L.k == 3 && L.stride == 1)) continue;
+    for (size_t i = 0; i < tape->recs.size(); ++i) {
+      const ConvSpec& L = *tape->recs[i].L;
+      if (!(L.k == 3 && L.stride == 1) || lowest < 0 || (int)i < lowest) continue;     // (records below `lowest` never run)
       ConvSpec g{};
       g.cin = L.cout; g.cout = L.cin; g.k = L.k; g.stride = 1; g.pad = L.k - 1 - L.pad; g.cc = 16; g.cin_pad = L.cout; g.dgrad = 1;
       if (!conv2d_hs_pack_batchable(g, 1)) continue;
@@ -1566,13 +1674,24 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
   float* g_cur = gb[0];
   {
     const int HW = tape->fh * tape->fw_;
-    ADX_CHECK_HIP(hipMemsetAsync(G[r->t_fcw], 0, sizeof(float) * (size_t)r->out_dim * 512, s));
-    ADX_CHECK_HIP(hipMemsetAsync(G[r->t_fcb], 0, sizeof(float) * r->out_dim, s));
-    avgpool_fc_bwd_kernel<<<dim3(batch * (512 / kPoolSlice)), dim3(256), 0, s>>>(tape->final_map, T[r->t_fcw], d_feature, g_cur, G[r->t_fcw],
-                                                            G[r->t_fcb], 512, HW, r->out_dim);
-    ADX_LAUNCH_CHECK();
+    if (G[r->t_fcw] != nullptr) ADX_CHECK_HIP(hipMemsetAsync(G[r->t_fcw], 0, sizeof(float) * (size_t)r->out_dim * 512, s));
+    if (G[r->t_fcb] != nullptr) ADX_CHECK_HIP(hipMemsetAsync(G[r->t_fcb], 0, sizeof(float) * r->out_dim, s));
+    if (lowest >= 0 || G[r->t_fcw] != nullptr || G[r->t_fcb] != nullptr) {
+      avgpool_fc_bwd_kernel<<<dim3(batch * (512 / kPoolSlice)), dim3(256), 0, s>>>(tape->final_map, T[r->t_fcw], d_feature, g_cur, G[r->t_fcw],
+                                                              G[r->t_fcb], 512, HW, r->out_dim);
+      ADX_LAUNCH_CHECK();
+    }
     if (int rm = mark(0)) return rm;
   }
+  // every group's event is recorded, also where the group has nothing to write (a frozen or truncated part of the network): a
+  // reduction waiting on it must never wait for an event that does not fire
+  const int n_groups = adx_resnet_backward_groups(r);
+  auto mark_rest = [&](int from) -> int {
+    for (int g = from; g < n_groups; ++g)
+      if (int rm = mark(g)) return rm;
+    return ADX_OK;
+  };
+  if (lowest < 0) return mark_rest(1);
   // one conv+BN(+identity)(+ReLU) backward.  dout -> (dz for the identity path), d(conv input) accumulated
   // into dx (dx_has tells whether dx already holds a contribution).
   // `sums_ready`: the record whose BatchNorm-backward sums (sum dz, sum dz xhat) the last data-gradient conv already left in
@@ -1606,6 +1725,7 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
     // ReLU mask: straight after BN it is re-derived from the conv output (one tensor read less in both passes)
     const int mask = !rec.relu ? 0 : (rec.identity != nullptr ? 1 : 2);
     uint32_t* const dmax = dmax_all + (size_t)(&L - r->convs.data()) * 512;
+    const int frozen = frozen_conv[&L - r->convs.data()];
     if (sums_ready != &rec)
       channel_sums_kernel<1><<<dim3(batch * L.cout), dim3(256), 0, s>>>(dout, rec.out, rec.raw, rec.mean, rec.rstd, sums,
                                                                         L.cout, HW, mask, T[L.t_g], T[L.t_b], rec.bits, dmax);
@@ -1615,7 +1735,7 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
     if (draw_cells) {
       n_amax = -1;
       bn_bwd_consts_kernel<<<dim3(1), dim3(256), 0, s>>>(sums, rec.mean, rec.rstd, T[L.t_g], T[L.t_b], dmax, count, L.cout, bconsts, xscale,
-                                                         G[L.t_g], G[L.t_b]);
+                                                         G[L.t_g], G[L.t_b], frozen);
       const int groups = batch * (L.cout / 8), per = ceil_div(HW, 256);
       const dim3 grid((unsigned)std::min<long>((long)groups * per, 1L << 20));
 #define ADX_BWD_GROUPS(MASK, KEEP) \
@@ -1633,17 +1753,19 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
       n_amax = (int)std::min<size_t>(kAmaxPartials, (size_t)ceil_div(planes, 4));
       bn_bwd_apply_planes_kernel<<<dim3(n_amax), dim3(256), 0, s>>>(dout, rec.out, rec.raw, rec.mean, rec.rstd, T[L.t_g], sums,
                                                                     draw, dz_keep, L.cout, HW, planes, count, mask, amax, T[L.t_b],
-                                                                    G[L.t_g], G[L.t_b], rec.bits);
+                                                                    G[L.t_g], G[L.t_b], rec.bits, frozen);
     } else {
       n_amax = (int)std::min<size_t>(kAmaxPartials, (n + 255) / 256);
       bn_bwd_apply_kernel<<<dim3(n_amax), dim3(256), 0, s>>>(
           dout, rec.out, rec.raw, rec.mean, rec.rstd, T[L.t_g], sums, draw, dz_keep, L.cout, HW, n, count, mask, amax, T[L.t_b],
-          G[L.t_g], G[L.t_b], rec.bits);
+          G[L.t_g], G[L.t_b], rec.bits, frozen);
     }
     ADX_LAUNCH_CHECK();
     const uint32_t* const range = draw_cells ? reinterpret_cast<const uint32_t*>(xscale) : amax;      // (n_amax < 0: the scale itself)
-    int rc2 = conv2d_wgrad(rec.x, draw, G[L.t_w], batch, L.cin, rec.H, rec.W, L.cout, L.k, L.stride, L.pad, s, range, n_amax, false, wgrad9,
-                           rec.x_cells, draw_cells);
+    int rc2 = ADX_OK;
+    if (G[L.t_w] != nullptr)            // (null: a frozen conv weight)
+      rc2 = conv2d_wgrad(rec.x, draw, G[L.t_w], batch, L.cin, rec.H, rec.W, L.cout, L.k, L.stride, L.pad, s, range, n_amax, false, wgrad9,
+                         rec.x_cells, draw_cells);
     if (rc2 != ADX_OK || !need_dx) return rc2;
     // data gradient
     const ConvSpec g = dgrad_spec(L);
@@ -1705,6 +1827,15 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
     const adx_resnet_tape::Rec& c2 = tape->recs[--ri];
     const adx_resnet_tape::Rec* dsr = ds ? &tape->recs[--ri] : nullptr;
     const adx_resnet_tape::Rec& c1 = tape->recs[--ri];
+    const int group = 1 + (int)(r->block_has_ds.size() - 1 - b);
+    // truncated backward: a block none of whose records -- nor any below it -- owns a gradient slot is not differentiated (nor is
+    // anything below it: every block further down skips too); need_in: some record below this block needs d(block in)
+    if (lowest > (int)ri + (ds ? 2 : 1)) {
+      rc = mark(group);
+      continue;
+    }
+    const bool need_in = lowest < (int)ri;
+    const bool c1_run = need_in || owns_grad(*c1.L), ds_run = ds && (need_in || owns_grad(*dsr->L));
     // buffers: g_cur = d(block out).  dz2 (identity gradient), draw scratch, do1, dx
     float* others[4];
     int k = 0;
@@ -1713,30 +1844,33 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
     // A block without a downsample, not the first: the identity path's gradient -- d(block out) where the block's output was
     // positive -- is not written as a tensor (dz2): conv1's data gradient adds d(block out) IN PLACE through the mask bits
     const adx_resnet_tape::Rec* prev = b > 0 ? &tape->recs[ri - 1] : nullptr;
-    const bool masked_res = !ds && prev != nullptr && prev->relu && c2.bits != nullptr && tape->stats_part != nullptr &&
+    const bool masked_res = need_in && !ds && prev != nullptr && prev->relu && c2.bits != nullptr && tape->stats_part != nullptr &&
                             dgrad_img[c1.L - r->convs.data()] != nullptr &&
                             conv2d_hs3x3_dgrad_stats(dgrad_spec(*c1.L), batch, c1.OH, c1.OW,
                                                      draw_cells_of(c1, true) && (reinterpret_cast<uintptr_t>(draw) & 15) == 0, kStatsPartFloats);
-    rc = conv_bn_bwd(c2, g_cur, masked_res ? nullptr : dz2, draw, do1, false, true, &c1);   // -> do1 = d(o1) (c1's incoming gradient), dz2 = masked dout
+    // dz2 (the masked d(block out)) feeds the identity path: the downsample's backward, or d(block in) directly
+    const bool keep_dz2 = !masked_res && (ds ? ds_run : need_in);
+    rc = conv_bn_bwd(c2, g_cur, keep_dz2 ? dz2 : nullptr, draw, do1, false, c1_run, &c1);   // -> do1 = d(o1) (c1's incoming gradient), dz2 = masked dout
     if (rc != ADX_OK) break;
     float* dx = g_cur;                                                   // d(block out) is dead now: reuse for d(block in)
     if (masked_res) {
       rc = conv_bn_bwd(c1, do1, nullptr, draw, g_cur, true, true, prev, c2.bits);
     } else if (ds) {
-      rc = conv_bn_bwd(c1, do1, nullptr, draw, dx, false, true);         // main path: writes every pixel of d(block in)
+      if (c1_run) rc = conv_bn_bwd(c1, do1, nullptr, draw, dx, false, need_in);   // main path: writes every pixel of d(block in)
       if (rc != ADX_OK) break;
-      rc = conv_bn_bwd(*dsr, dz2, nullptr, draw, dx, true, true);        // identity path through the downsample conv adds to
-                                                                         // the even pixels (no clearing pass over dx)
+      if (ds_run) rc = conv_bn_bwd(*dsr, dz2, nullptr, draw, dx, true, need_in);  // identity path through the downsample conv adds
+                                                                                  // to the even pixels (no clearing pass over dx)
     } else {
       // identity gradient is dz2 itself: main path = conv(...) + res(dz2).  The result is the incoming gradient of the block
       // before this one (its conv2, ReLU after the residual add); block 0's flows into the max-pool instead
-      rc = conv_bn_bwd(c1, do1, nullptr, draw, dz2, true, true, b > 0 ? &tape->recs[ri - 1] : nullptr);
+      if (c1_run) rc = conv_bn_bwd(c1, do1, nullptr, draw, dz2, true, need_in, b > 0 ? &tape->recs[ri - 1] : nullptr);
       dx = dz2;
     }
     g_cur = dx;
-    if (rc == ADX_OK) rc = mark(1 + (int)(r->block_has_ds.size() - 1 - b));
+    if (rc == ADX_OK) rc = mark(group);
   }
   if (rc != ADX_OK) return rc;
+  if (lowest > 0) return mark_rest((int)r->block_has_ds.size() + 1);      // the stem owns no gradient slot
   // maxpool, then the stem (no data gradient: the image needs none)
   {
     // the max-pool backward is folded into the stem's two BatchNorm-backward passes (stem_pool_bn_bwd_kernel): d(stem map)
@@ -1760,10 +1894,11 @@ int adx_resnet_backward_events(adx_resnet* r, const float* const* T, float* cons
     if (stem_hs) ADX_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(uint32_t) * kAmaxPartials, s));
     stem_pool_bn_bwd_kernel<1><<<dim3(batch * 64, ceil_div(tape->ph, 4 * kStemBwdRows)), dim3(256), 0, s>>>(
         code, g_cur, st.raw, st.mean, st.rstd, T[L.t_g], T[L.t_b], sums, draw, 64, tape->ph, tape->pw, tape->poh, tape->pow_, count,
-        G[L.t_g], G[L.t_b], stem_hs ? amax : nullptr, (int)kAmaxPartials);
+        G[L.t_g], G[L.t_b], stem_hs ? amax : nullptr, (int)kAmaxPartials, nullptr, (int)frozen_conv[&L - r->convs.data()]);
     ADX_LAUNCH_CHECK();
-    rc = conv2d_wgrad(st.x, draw, G[L.t_w], batch, L.cin, st.H, st.W, L.cout, L.k, L.stride, L.pad, s, stem_hs ? amax : nullptr,
-                      stem_hs ? (int)kAmaxPartials : 0, false, wgrad9);
+    if (G[L.t_w] != nullptr)
+      rc = conv2d_wgrad(st.x, draw, G[L.t_w], batch, L.cin, st.H, st.W, L.cout, L.k, L.stride, L.pad, s, stem_hs ? amax : nullptr,
+                        stem_hs ? (int)kAmaxPartials : 0, false, wgrad9);
     if (rc == ADX_OK) rc = mark((int)r->block_has_ds.size() + 1);
   }
   return rc;

@@ -3,7 +3,8 @@ by Linear(512, dim) at modeling/temporal.py:83-84), executed by libadx.so.
 
 Eval mode: BatchNorm uses running statistics, applied as scale/shift in the conv epilogue.
 Train mode: batch statistics, running buffers updated in place (momentum 0.1, num_batches_tracked
-incremented), differentiable w.r.t. every parameter through `_PerceptionTrainFn`.
+incremented), differentiable w.r.t. every parameter through `_PerceptionTrainFn`.  A BatchNorm holder in eval mode inside a
+training forward is frozen (running statistics, buffers untouched); a parameter with requires_grad False gets no gradient.
 """
 from __future__ import annotations
 
@@ -20,7 +21,9 @@ from .spec import resnet34_entries
 
 class _PerceptionTrainFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, img, module, *params):
+    def forward(ctx, img, module, frozen, *params):
+        # frozen: bit l set -> BatchNorm layer l (adx_resnet_bn_tensor's order) has its holder in eval mode: it normalises with
+        # its running statistics and leaves them (and its num_batches_tracked) alone; 0 is the plain training forward
         h = module._native()
         B, _, H, W = img.shape
         ts = [L.require_gpu_f32(t.detach(), "perception tensor") for t in module._tensors()]
@@ -33,18 +36,25 @@ class _PerceptionTrainFn(torch.autograd.Function):
         tape = L.NativeTape(L.lib().adx_resnet_tape_create, L.lib().adx_resnet_tape_destroy, "adx_resnet_tape_create")
         out = torch.empty((B, module.out_dim), dtype=torch.float32, device=img.device)
         try:
-            L.check(L.lib().adx_resnet_forward_train(h, L.ptr_array(ts), len(ts), packed.data_ptr(), ws.data_ptr(), nbytes,
-                                                     img.data_ptr(), B, H, W, out.data_ptr(), tape.handle, 1,
-                                                     L.stream_ptr(img.device)), "adx_resnet_forward_train")
+            if frozen == 0:
+                L.check(L.lib().adx_resnet_forward_train(h, L.ptr_array(ts), len(ts), packed.data_ptr(), ws.data_ptr(), nbytes,
+                                                         img.data_ptr(), B, H, W, out.data_ptr(), tape.handle, 1,
+                                                         L.stream_ptr(img.device)), "adx_resnet_forward_train")
+            else:
+                L.check(L.lib().adx_resnet_forward_train_ex(h, L.ptr_array(ts), len(ts), packed.data_ptr(), ws.data_ptr(), nbytes,
+                                                            img.data_ptr(), B, H, W, out.data_ptr(), tape.handle, 1, frozen,
+                                                            L.stream_ptr(img.device)), "adx_resnet_forward_train_ex")
         except Exception:
             tape.release()
             raise
-        # num_batches_tracked of the 36 BatchNorm layers: one multi-tensor add, not 36 launches
-        counters = [b for b in module.buffers() if b.dtype == torch.int64]
+        # num_batches_tracked of the train-mode BatchNorm layers: one multi-tensor add, not 36 launches
+        counters = module._batch_counters(frozen)
         if counters:
             torch._foreach_add_(counters, 1)
-        module.invalidate()                 # running statistics moved: eval-mode image is stale
+        if frozen != (1 << len(module._bn_holders())) - 1:
+            module.invalidate()             # running statistics moved: eval-mode image is stale
         ctx.module, ctx.tape, ctx.ws, ctx.nbytes, ctx.ts, ctx.img = module, tape, ws, nbytes, ts, img
+        ctx.frozen = frozen
         return out
 
     @staticmethod
@@ -56,9 +66,12 @@ class _PerceptionTrainFn(torch.autograd.Function):
         g = L.require_gpu_f32(grad_out, "grad_out")
         named = dict(module.named_parameters())
         entries = [e for e in module._entries if e.dtype == "f32"]
+        # a parameter that does not require grad gets a NULL slot: the native backward skips its gradient and everything below
+        # the lowest layer that still needs one
+        want = {k: bool(ctx.needs_input_grad[3 + i]) for i, (k, _) in enumerate(module.named_parameters())}
         grads, slots = {}, []
         for e in entries:
-            if e.is_buffer:
+            if e.is_buffer or not want[e.key]:
                 slots.append(None)
             else:
                 grads[e.key] = L.grad_buffer(named[e.key])      # born in its communication bucket under DataParallel
@@ -77,13 +90,18 @@ class _PerceptionTrainFn(torch.autograd.Function):
             n_ev = len(events)
             earr = (L.vp * n_ev)(*[ev.cuda_event for ev in events])
         try:
-            L.check(L.lib().adx_resnet_backward_events(module._native(), L.ptr_array(ctx.ts), garr, len(slots), ctx.ws.data_ptr(),
-                                                       ctx.nbytes, ctx.tape.handle, g.data_ptr(), earr, n_ev, L.stream_ptr(g.device)),
-                    "adx_resnet_backward_events")
+            if ctx.frozen == 0:
+                L.check(L.lib().adx_resnet_backward_events(module._native(), L.ptr_array(ctx.ts), garr, len(slots), ctx.ws.data_ptr(),
+                                                           ctx.nbytes, ctx.tape.handle, g.data_ptr(), earr, n_ev,
+                                                           L.stream_ptr(g.device)), "adx_resnet_backward_events")
+            else:
+                L.check(L.lib().adx_resnet_backward_ex(module._native(), L.ptr_array(ctx.ts), garr, len(slots), ctx.ws.data_ptr(),
+                                                       ctx.nbytes, ctx.tape.handle, g.data_ptr(), ctx.frozen, earr, n_ev,
+                                                       L.stream_ptr(g.device)), "adx_resnet_backward_ex")
             if events is not None:
                 for i, e in enumerate(entries):
                     grp = module._tensor_groups[i]
-                    if not e.is_buffer and grp >= 0:
+                    if slots[i] is not None and grp >= 0:
                         # the group's event covers this gradient only where the native call wrote it INTO the bucket view; a
                         # buffer of its own (`.grad` already present: accumulation over several backwards; the view lent to
                         # another node of the graph) reaches the bucket through AccumulateGrad's add, which is queued on the
@@ -95,7 +113,7 @@ class _PerceptionTrainFn(torch.autograd.Function):
         finally:
             ctx.tape.release()
             ctx.ws = None            # 27 GB of taped activations at B = 64: free them with the tape
-        return (None, None, *[grads[k] for k, _ in module.named_parameters()])
+        return (None, None, None, *[grads.get(k) for k, _ in module.named_parameters()])
 
 
 class PerceptionResNet34(nn.Module):
@@ -312,13 +330,54 @@ class PerceptionResNet34(nn.Module):
             return out
         return self._on_pass_stream(f, run)
 
+    # -- fine-tuning: per-layer BatchNorm mode --------------------------------------------------------------------------
+    def _bn_holders(self):
+        """The 36 BatchNorm holder modules in the native layer order (adx_resnet_bn_tensor: layer -> its gamma slot)."""
+        if getattr(self, "_bn_list", None) is None:
+            h = self._native()
+            keys = [e.key for e in self._entries if e.dtype == "f32"]
+            mods = dict(self.named_modules())
+            self._bn_list = [mods[keys[L.lib().adx_resnet_bn_tensor(h, i)].rsplit(".", 1)[0]]
+                             for i in range(L.lib().adx_resnet_bn_layers(h))]
+        return self._bn_list
+
+    def frozen_mask(self) -> int:
+        """Bit l set: BatchNorm layer l's holder is in eval mode (`.eval()` on the layer or on a module above it) -- inside a
+        training forward it normalises with its running statistics and leaves them alone, as nn.BatchNorm2d does."""
+        mask = 0
+        for i, m in enumerate(self._bn_holders()):
+            if not m.training:
+                mask |= 1 << i
+        return mask
+
+    def _batch_counters(self, frozen: int):
+        """num_batches_tracked of the layers a training forward with mask `frozen` normalises with batch statistics."""
+        if frozen == 0:
+            return [b for b in self.buffers() if b.dtype == torch.int64]
+        return [m.num_batches_tracked for i, m in enumerate(self._bn_holders()) if not (frozen >> i) & 1]
+
+    def _train_pass(self, img, frozen: int):
+        return _PerceptionTrainFn.apply(img, self, frozen, *[p for _, p in self.named_parameters()])
+
     def forward(self, img: torch.Tensor) -> torch.Tensor:
         img = L.require_gpu_f32(img, "img")
         if img.dim() != 4 or img.shape[1] != 3:
             raise ValueError(f"img must be [B, 3, H, W], got {tuple(img.shape)}")
         if self.training:
-            return _PerceptionTrainFn.apply(img, self, *[p for _, p in self.named_parameters()])
+            return self._train_pass(img, self.frozen_mask())
         return self._guarded(lambda: self._forward_eval(img))
+
+    def forward_in_training(self, img: torch.Tensor) -> torch.Tensor:
+        """The encoder's pass inside the training forward of the model that owns it (TemporalMapUnet in train mode).  An encoder
+        put in eval mode there (`model.train(); model.perception.eval()`, the usual fine-tuning recipe) still trains whatever
+        requires grad: with grad enabled and a trainable parameter, the differentiable pass runs with the frozen layers taken from
+        the BatchNorm holders (all of them after a plain `perception.eval()`).  Otherwise this is `self(img)`."""
+        if self.training or not torch.is_grad_enabled() or not any(p.requires_grad for p in self.parameters()):
+            return self(img)
+        img = L.require_gpu_f32(img, "img")
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError(f"img must be [B, 3, H, W], got {tuple(img.shape)}")
+        return self._train_pass(img, self.frozen_mask())
 
     def _forward_eval(self, img):
         self._attach_status(img.device)

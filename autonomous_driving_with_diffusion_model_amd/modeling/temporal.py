@@ -394,7 +394,9 @@ class TemporalMapUnet(nn.Module):
         which are then not read; x may be [1, T, D] for a table of more rows (every row reads the one trajectory: the
         classifier-free pair of interact.py:131 without the torch.cat)."""
         if self.training:
-            feat = self.perception(img)          # train-mode perception: batch-statistics BatchNorm, autograd node
+            # train-mode perception: batch-statistics BatchNorm, autograd node; an encoder (or single BatchNorm layers) in eval mode
+            # normalises with running statistics and still trains what requires grad
+            feat = self.perception.forward_in_training(img)
             return self.unet_forward_train(x, feat, time, cond)
         x = L.require_gpu_f32(x, "x")
         if x.dim() != 3 or x.shape[1] != self.horizon or x.shape[2] != self.transition_dim:

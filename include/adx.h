@@ -361,7 +361,27 @@ int32_t adx_resnet_tensor_group(const adx_resnet* r, int32_t tensor);
 int adx_resnet_backward_events(adx_resnet* r, const float* const* tensors, float* const* grads, int32_t n_tensors,
                                void* workspace, size_t workspace_bytes, adx_resnet_tape* tape, const float* d_feature,
                                void* const* events, int32_t n_events, adx_stream s);
-/* For tests only: a read-only description of a tape filled by adx_resnet_forward_train, so that a test can read what the
+/* Fine-tuning: frozen BatchNorm statistics and frozen parameters.
+ * adx_resnet_bn_layers(r) = the number of BatchNorm layers (36); adx_resnet_bn_tensor(r, l) = layer l's gamma slot in
+ * adx_resnet_pack's list (-1 on a bad index).  Layers are in record order: the stem, then per BasicBlock conv1, [downsample],
+ * conv2 (adx_resnet_tape_describe's records).
+ * adx_resnet_forward_train_ex: bit l of `frozen_bn` set -> layer l normalises with running_mean / running_var (eps 1e-5) and
+ * leaves them untouched (nn.BatchNorm2d in eval mode inside a training forward); the other layers behave as in
+ * adx_resnet_forward_train, which is this call with frozen_bn = 0.  A bit >= adx_resnet_bn_layers(r) is refused.
+ * adx_resnet_backward_ex: the backward of such a tape, given the same mask (a different one is refused).  A frozen layer
+ * backpropagates through its affine map only: dx = gamma rstd_run dy, d gamma = sum dy xhat, d beta = sum dy.  In every
+ * adx_resnet_backward* call a NULL conv-weight, gamma, beta or fc slot is a frozen parameter: its gradient is not computed,
+ * and nothing below the lowest record that still owns a non-NULL slot runs.  Every group event is still recorded. */
+int32_t adx_resnet_bn_layers(const adx_resnet* r);
+int32_t adx_resnet_bn_tensor(const adx_resnet* r, int32_t layer);
+int adx_resnet_forward_train_ex(adx_resnet* r, const float* const* tensors, int32_t n_tensors, void* packed,
+                                void* workspace, size_t workspace_bytes, const float* img, int32_t batch, int32_t h,
+                                int32_t w, float* feature, adx_resnet_tape* tape, int32_t update_running, uint64_t frozen_bn,
+                                adx_stream s);
+int adx_resnet_backward_ex(adx_resnet* r, const float* const* tensors, float* const* grads, int32_t n_tensors,
+                           void* workspace, size_t workspace_bytes, adx_resnet_tape* tape, const float* d_feature,
+                           uint64_t frozen_bn, void* const* events, int32_t n_events, adx_stream s);
+/* For tests only:a read-only description of a tape filled by adx_resnet_forward_train, so that a test can read what the
  * forward kept (and what the backward will condition on) out of the caller's workspace.  Locations are BYTE OFFSETS into
  * `workspace` (the forward's); -1 = none, -2 = outside the forward's part of the workspace (the stem's input: the image).
  * *n_records = the number of conv records (forward launch order: 0 = the stem, then per BasicBlock conv1, [downsample], conv2).
