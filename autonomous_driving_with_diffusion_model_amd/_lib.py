@@ -83,6 +83,8 @@ _SIGS = {
     "adx_unet_time_conditioning_workspace_bytes": (C.c_size_t, [vp, i32]),
     "adx_unet_time_conditioning": (i32, [vp, vp, vp, C.POINTER(UnetIO), vp, vp, vp]),
     "adx_unet_pipe_describe": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i64)]),
+    "adx_unet_plan_describe": (i32, [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), i32]),
+    "adx_tconv_plan_describe": (i32, [C.POINTER(TConvDesc), i32, i64, i32, C.POINTER(i32), C.POINTER(i32), i32]),
     "adx_unet_tape_create": (i32, [C.POINTER(vp)]),
     "adx_unet_tape_destroy": (None, [vp]),
     "adx_unet_train_workspace_bytes": (C.c_size_t, [vp, i32]),

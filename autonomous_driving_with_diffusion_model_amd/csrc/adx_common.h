@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "../../include/adx.h"
+#include "plan.h"
 
 namespace adx {
 

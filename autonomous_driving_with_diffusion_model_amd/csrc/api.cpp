@@ -16,6 +16,25 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+static thread_local PlanSink* t_plan_sink = nullptr;
+PlanSink* plan_sink() { return t_plan_sink; }
+void plan_set_sink(PlanSink* s) { t_plan_sink = s; }
+
+int plan_emit(PlanSink* s, const PlanLaunch& l) {
+  ADX_REQUIRE(s->n < s->cap, "plan export: more than %d launches", s->cap);
+  s->rec[s->n++] = l;
+  return ADX_OK;
+}
+
+void plan_write(const PlanLaunch& l, const int layer[5], long long part_off, int32_t* o) {
+  const int row_tiles = l.bt > 0 ? (l.rows + l.bt - 1) / l.bt : 0;
+  const int32_t v[ADX_PLAN_INTS] = {layer[0], layer[1], layer[2], l.family, l.bt, row_tiles, l.bt > 0 ? l.rows % l.bt : 0, l.ctiles,
+                                    l.grid, l.ksplit, l.reduce, l.chunks, l.vec_stage, l.fast_epi, l.ntap, layer[3], layer[4],
+                                    l.ctiles_b, l.ck, l.cin_pad, (int32_t)l.part_floats, (int32_t)part_off, (int32_t)l.lds_bytes,
+                                    l.lout, l.cout, l.aux, 0, 0};
+  for (int i = 0; i < ADX_PLAN_INTS; ++i) o[i] = v[i];
+}
+
 const DebugSwitches& debug_switches() {
   static const DebugSwitches sw = [] {
     DebugSwitches d;
@@ -76,6 +95,40 @@ int adx_tconv_pack(const adx_tconv_desc* d, const float* w, float* packed, adx_s
 }
 int adx_tconv_forward(const adx_tconv_desc* d, const adx_tconv_io* io, adx_stream s) {
   return adx::tconv_forward(d, io, (hipStream_t)s);
+}
+int adx_tconv_plan_describe(const adx_tconv_desc* d, int32_t batch, int64_t scratch_floats, int32_t has_tickets, int32_t* n_records,
+                            int32_t* ints, int32_t max_records) {
+  ADX_REQUIRE(d != nullptr && n_records != nullptr && ints != nullptr, "adx_tconv_plan_describe: null argument");
+  ADX_REQUIRE(batch >= 1 && max_records >= 1, "adx_tconv_plan_describe: batch and max_records must be >= 1");
+  ADX_REQUIRE(scratch_floats >= 0 && (scratch_floats > 0 || has_tickets == 0), "adx_tconv_plan_describe: ticket words come with a scratch only");
+  // placeholder addresses (never read): dense 16-byte aligned tensors, as ops.tconv passes them
+  float* const fake = reinterpret_cast<float*>((uintptr_t)1 << 32);
+  adx_tconv_io io;
+  memset(&io, 0, sizeof(io));
+  io.x0 = fake; io.x0_sb = (int64_t)d->c0 * d->lin; io.x0_sc = d->lin; io.x0_sl = 1;
+  if (d->c1 > 0) { io.x1 = fake; io.x1_sb = (int64_t)d->c1 * d->lin; io.x1_sc = d->lin; io.x1_sl = 1; }
+  io.packed_w = fake; io.bias = fake;
+  if (d->groups > 0) { io.gamma = fake; io.beta = fake; }
+  io.y = fake; io.y_sb = (int64_t)d->cout * d->lout; io.y_sc = d->lout; io.y_sl = 1;
+  io.batch = batch;
+  if (scratch_floats > 0) {
+    io.scratch = fake; io.scratch_floats = scratch_floats;
+    if (has_tickets != 0) io.tickets = reinterpret_cast<uint32_t*>(fake);
+  }
+  adx::PlanLaunch rec[4];
+  adx::PlanSink sink;
+  sink.rec = rec; sink.cap = 4;
+  int rc;
+  {
+    adx::PlanScope scope(&sink);
+    rc = adx::tconv_forward(d, &io, nullptr);
+  }
+  if (rc != ADX_OK) return rc;
+  ADX_REQUIRE(sink.n <= max_records, "adx_tconv_plan_describe: %d launches, room for %d", sink.n, max_records);
+  const int layer[5] = {0, -1, 0, -1, -1};
+  for (int i = 0; i < sink.n; ++i) adx::plan_write(rec[i], layer, rec[i].part != nullptr ? 0 : -1, ints + (size_t)i * ADX_PLAN_INTS);
+  *n_records = sink.n;
+  return ADX_OK;
 }
 int adx_embed_forward(const adx_embed_weights* w, int32_t dim, const int64_t* t, int32_t t_rows, const float* cond,
                       const float* img_feature, int32_t feat_rows, int32_t rows, float* time_embed, float* mish_cond,

@@ -226,6 +226,11 @@ int chan_layernorm_forward(const float* x, int64_t sb, int64_t sc, int64_t sl, c
   const int Lv = L_valid > 0 ? L_valid : L;
   ADX_REQUIRE(x && g && b && xn && B >= 1 && C >= 1 && L >= 1 && Lv <= L && (mean == nullptr) == (rstd == nullptr),
               "chan_layernorm_forward: bad argument");
+  if (PlanSink* ps = plan_sink()) {      // the plan export (plan.h): record, do not launch
+    PlanLaunch l;
+    l.aux = 3; l.rows = B; l.grid = ceil_div(B * L, 4);
+    return plan_emit(ps, l);
+  }
   chan_layernorm_fwd_kernel<<<dim3(ceil_div(B * L, 4)), dim3(256), 0, s>>>(x, sb, sc, sl, g, b, xn, mean, rstd, B, C, L, Lv);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
@@ -250,6 +255,11 @@ int linattn_core_forward(const float* qkv, float* o, int B, int L, int L_valid, 
   ADX_REQUIRE(qkv && o && B >= 1, "linattn_core_forward: bad argument");
   const int rc = attn_check_len(L, Lv, "linattn_core_forward");
   if (rc != ADX_OK) return rc;
+  if (PlanSink* ps = plan_sink()) {      // the plan export (plan.h): record, do not launch
+    PlanLaunch l;
+    l.aux = 4; l.rows = B; l.grid = B * kHeads;
+    return plan_emit(ps, l);
+  }
   linattn_core_fwd_kernel<<<dim3(B * kHeads), dim3(256), 0, s>>>(qkv, o, L, Lv);
   ADX_LAUNCH_CHECK();
   return ADX_OK;

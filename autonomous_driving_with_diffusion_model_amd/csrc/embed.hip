@@ -222,6 +222,11 @@ int embed_forward(const adx_embed_weights* w, int dim, const int64_t* t, int t_r
               rows, t_rows, feat_rows);
   ADX_REQUIRE(t && feat && time_embed && mish_cond, "embed: null tensor");
   ADX_REQUIRE((w->cw0 == nullptr) == (w->cw2 == nullptr), "embed: cond_mlp weights must be all set or all null");
+  if (PlanSink* ps = plan_sink()) {      // the plan export (plan.h): record, do not launch
+    PlanLaunch l;
+    l.aux = 1; l.rows = rows; l.bt = 1; l.ctiles = 1; l.grid = rows;
+    return plan_emit(ps, l);
+  }
   embed_kernel<<<dim3(rows), dim3(256), 0, s>>>(*w, dim, t, t_rows, cond, feat, feat_rows, time_embed, mish_cond);
   ADX_LAUNCH_CHECK();
   return ADX_OK;

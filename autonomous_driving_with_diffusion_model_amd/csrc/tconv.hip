@@ -413,6 +413,13 @@ static int launch(const TConvArgs& a, int grid, size_t lds, int nw, hipStream_t 
   // ring depth: ~16 MFMAs (512 cycles) of work per slot x PF slots covers an L2 / Infinity Cache round trip
   constexpr int PF = NF >= 8 ? 2 : ((MF * NF >= 4) ? 4 : 8);
   constexpr int PF16 = NF >= 8 ? 2 : (MF * NF >= 8 ? 2 : 4);  // 1024-thread workgroups: <= 128 VGPRs per lane
+  if (PlanSink* ps = plan_sink()) {      // the plan export (plan.h): record, do not launch
+    PlanLaunch l;
+    l.family = kPlanExact; l.w = a.io.packed_w; l.rows = a.io.batch; l.bt = a.bt; l.ctiles = a.ntiles; l.grid = grid;
+    l.chunks = ceil_div(a.cin_pad, a.ck); l.vec_stage = a.dense; l.ntap = a.taps; l.ck = a.ck; l.cin_pad = a.cin_pad;
+    l.lds_bytes = (long long)lds; l.lout = a.lout; l.cout = a.cout;
+    return plan_emit(ps, l);
+  }
   static std::atomic<uint64_t> attr_set{0};  // dynamic LDS above 64 KB must be opted into once per kernel
   if (DeviceOnce once{attr_set}; once) {
     ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_kernel<MF, NF, PF16, 16>),

@@ -474,6 +474,13 @@ int chain_pack(const adx_tconv_desc* d, const float* w, const adx_tconv_desc* r,
 }
 
 int chain_launch(const ChainArgs& ca, int grid, size_t lds_bytes, hipStream_t s) {
+  if (PlanSink* ps = plan_sink()) {      // the plan export (plan.h): record, do not launch
+    PlanLaunch l;
+    l.family = kPlanChain; l.w = ca.packed + ca.st[0].w_off; l.rows = ca.batch; l.bt = ca.bt; l.ctiles = 1; l.grid = grid;
+    l.vec_stage = ca.in_vec; l.cin_pad = ca.in_cpad; l.ck = ca.in_cpad; l.lds_bytes = (long long)lds_bytes;
+    l.lout = 1 << ca.st[ca.n_stages - 1].log2_lout; l.cout = ca.st[ca.n_stages - 1].cout;
+    return plan_emit(ps, l);
+  }
   static std::atomic<uint64_t> attr_set{0};
   if (DeviceOnce once{attr_set}; once) {
     ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_chain_kernel),

@@ -164,6 +164,12 @@ int tconv_generic_forward(const adx_tconv_desc* d, const adx_tconv_io* io, hipSt
   generic_geometry(d, &a.ct, &a.ntiles, &lds);
   ADX_REQUIRE(lds <= kMaxGenericLds, "tconv (general-shape kernel): a sample's input of %d x %d floats does not fit the LDS",
               a.cin, a.lin);
+  if (PlanSink* ps = plan_sink()) {      // the plan export (plan.h): record, do not launch
+    PlanLaunch l;
+    l.family = kPlanGeneric; l.w = io->packed_w; l.rows = io->batch; l.bt = 1; l.ctiles = a.ntiles; l.grid = io->batch * a.ntiles;
+    l.ntap = a.taps; l.ck = a.cin; l.cin_pad = a.cin; l.lds_bytes = (long long)lds; l.lout = a.lout; l.cout = a.cout;
+    return plan_emit(ps, l);
+  }
   static std::atomic<uint64_t> attr_set{0};
   if (DeviceOnce once{attr_set}; once) {
     ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_generic_kernel),

@@ -902,8 +902,22 @@ static int hs_tile(const adx_tconv_desc* d, int batch, HsTile* t) {
   return ADX_OK;
 }
 
+// ---- the plan export (plan.h): what a launch function records instead of launching --------------------------------------
+static PlanLaunch hs_record(int family, const HsArgs& ha, int grid, size_t lds) {     // a K-split launch (or its reduce launch)
+  const TConvArgs& a = ha.t;
+  PlanLaunch l;
+  l.family = family; l.w = a.io.packed_w; l.rows = a.io.batch; l.bt = a.bt; l.ctiles = a.ntiles; l.grid = grid;
+  l.ksplit = ha.ksplit; l.reduce = ha.ksplit > 1 ? (ha.tickets != nullptr ? 1 : 2) : 0;
+  l.chunks = ceil_div(ha.ksplit > 1 ? std::min(ha.cper, a.cin_pad) : a.cin_pad, a.ck);      // the c0 loop of hs_main
+  l.vec_stage = ha.vec_stage; l.fast_epi = ha.fast_epi; l.ntap = ha.ntap; l.ck = a.ck; l.cin_pad = a.cin_pad;
+  l.part_floats = (long long)(ha.part_bytes / sizeof(float)); l.part = ha.part; l.lds_bytes = (long long)lds;
+  l.lout = a.lout; l.cout = a.cout;
+  return l;
+}
+
 template <int NF, int NW, int PF>
 static int hs_launch(const HsArgs& a, int grid, size_t lds, hipStream_t s) {
+  if (PlanSink* ps = plan_sink()) return plan_emit(ps, hs_record(kPlanKsplit, a, grid, lds));
   static std::atomic<uint64_t> attr_set{0};  // dynamic LDS above 64 KB must be opted into once per kernel
   if (DeviceOnce once{attr_set}; once) {
     ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_hs_kernel<NF, NW, PF>),
@@ -932,7 +946,14 @@ static bool hsd_prepare(const adx_tconv_desc* d, const HsArgs& ha, const HsTile&
   return true;
 }
 
+static PlanLaunch hsd_record(const HsdArgs& da, int grid, size_t lds) {      // a short-K launch: one chunk, every tap, no split
+  PlanLaunch l = hs_record(kPlanShortK, da.h, grid, lds);
+  l.ntap = da.h.t.taps;
+  return l;
+}
+
 static int hsd_launch(const HsdArgs& da, int grid, size_t lds, hipStream_t s) {
+  if (PlanSink* ps = plan_sink()) return plan_emit(ps, hsd_record(da, grid, lds));
   static std::atomic<uint64_t> attr_set{0};
   if (DeviceOnce once{attr_set}; once) {
     ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_hsd_kernel<kHsdPF, true>),
@@ -948,6 +969,11 @@ static int hsd_launch(const HsdArgs& da, int grid, size_t lds, hipStream_t s) {
 }
 
 static int hsd_launch_pair(const HsdPair& pr, int grid, size_t lds, hipStream_t s) {
+  if (PlanSink* ps = plan_sink()) {
+    PlanLaunch l = hsd_record(pr.a, grid, lds);
+    l.family = kPlanShortKPair; l.w_b = pr.b.h.t.io.packed_w; l.ctiles_b = pr.b.h.t.ntiles;
+    return plan_emit(ps, l);
+  }
   static std::atomic<uint64_t> attr_set{0};
   if (DeviceOnce once{attr_set}; once) {
     ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_hsd_pair_kernel<kHsdPF, true>),
@@ -1077,6 +1103,7 @@ int tconv_hs_forward(const adx_tconv_desc* d, const adx_tconv_io* io, hipStream_
   if (rc != ADX_OK) return rc;
   rc = p.t.nf == 2 ? hs_launch<2, 8, 4>(p.ha, p.grid, p.t.lds_bytes, s) : hs_launch<1, 8, 6>(p.ha, p.grid, p.t.lds_bytes, s);
   if (rc != ADX_OK || !p.reduce) return rc;
+  if (PlanSink* ps = plan_sink()) return plan_emit(ps, hs_record(kPlanReduce, p.ha, p.base_grid, 0));
   if (p.t.nf == 2) tconv_hs_reduce_kernel<2><<<dim3(p.base_grid), dim3(512), 0, s>>>(p.ha);
   else tconv_hs_reduce_kernel<1><<<dim3(p.base_grid), dim3(256), 0, s>>>(p.ha);
   ADX_LAUNCH_CHECK();
@@ -1085,6 +1112,11 @@ int tconv_hs_forward(const adx_tconv_desc* d, const adx_tconv_io* io, hipStream_
 
 template <int NF, int PF>
 static int hs_launch_mixed(const HsMixed& pr, int grid, size_t lds, hipStream_t s) {
+  if (PlanSink* ps = plan_sink()) {
+    PlanLaunch l = hs_record(kPlanMixed, pr.a, grid, lds);
+    l.w_b = pr.b.h.t.io.packed_w; l.ctiles_b = pr.b.h.t.ntiles;
+    return plan_emit(ps, l);
+  }
   static std::atomic<uint64_t> attr_set{0};
   if (DeviceOnce once{attr_set}; once) {
     ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_hs_mixed_kernel<NF, 8, PF, true>),

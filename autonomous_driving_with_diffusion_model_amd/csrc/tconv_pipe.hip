@@ -593,6 +593,11 @@ __global__ void __launch_bounds__(256) tickets_reset_kernel(unsigned* words, int
 
 int pipe_tickets_reset(unsigned* words, int n, int epoch_slot, hipStream_t s) {
   ADX_REQUIRE(words != nullptr && n <= 256 && epoch_slot >= 0 && epoch_slot < n, "pipe_tickets_reset: bad arguments");
+  if (PlanSink* ps = plan_sink()) {      // the plan export (plan.h): record, do not launch
+    PlanLaunch l;
+    l.aux = 2; l.grid = 1;
+    return plan_emit(ps, l);
+  }
   tickets_reset_kernel<<<dim3(1), dim3(256), 0, s>>>(words, n, pipe_epoch_counter(false), epoch_slot);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
@@ -636,6 +641,12 @@ int pipe_launch(const PipeArgs& a, hipStream_t s) {
   ADX_REQUIRE(pipe_shape_ok(a.C, a.L, a.rows, a.taps, a.pad, a.groups), "tconv_pipe: shape outside the kernel's rules");
   ADX_REQUIRE((a.C / a.groups) % 4 == 0, "tconv_pipe: GroupNorm group width must be a multiple of 4");
   const size_t lds = pipe_lds_bytes(a.C, a.rows * a.L, a.ntap);
+  if (PlanSink* ps = plan_sink()) {      // the plan export (plan.h): record, do not launch
+    PlanLaunch l;                        // one row tile holds the whole batch; n_conv x P channel workgroups + the finisher
+    l.family = kPlanPipe; l.w = a.st[0].w; l.rows = a.rows; l.bt = a.rows; l.ctiles = a.n_conv * a.P + 1; l.grid = a.n_conv * a.P + 1;
+    l.ntap = a.ntap; l.cin_pad = a.C; l.ck = a.C; l.lds_bytes = (long long)lds; l.lout = a.L; l.cout = a.C;
+    return plan_emit(ps, l);
+  }
   static std::atomic<uint64_t> attr{0};
   if (DeviceOnce once{attr}; once) {
     ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tconv_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

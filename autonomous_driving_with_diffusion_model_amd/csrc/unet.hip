@@ -506,7 +506,7 @@ static adx_tconv_io make_io(const ConvLayer& L, const float* base, const Act& x0
 
 // time_embed [rows][dim], mish_cond [rows][2 dim] and the time-bias matrix tb[rows][sum_c] = all 16 block Linears at once
 // (temporal.py:206-216 + the `time_mlp` of every ResidualTemporalMapBlock, helpers.py:121-123)
-static int time_conditioning(adx_unet* u, const float* base, const adx_unet_io* io, int rows, float* te, float* mc, float* tb,
+static int time_conditioning(const adx_unet* u, const float* base, const adx_unet_io* io, int rows, float* te, float* mc, float* tb,
                              hipStream_t s) {
   const int dim = u->cfg.dim;
   adx_embed_weights ew;
@@ -753,7 +753,9 @@ static bool pipe_shape_fits(const adx_unet* u, int rows) {
 // ... and a forward of this process on the current device takes that launch: also the ticket words and the device's forward-number
 // counter must exist (the counter is allocated by the first adx_unet_pack on the device)
 static bool pipe_takes_launch(const adx_unet* u, int rows) {
-  return kSplitTickets && pipe_shape_fits(u, rows) && pipe_epoch_counter(false) != nullptr;
+  if (!kSplitTickets || !pipe_shape_fits(u, rows)) return false;
+  const PlanSink* ps = plan_sink();      // adx_unet_plan_describe may ask for the plan of a process that has packed (plan.h)
+  return (ps != nullptr && ps->assume_packed) || pipe_epoch_counter(false) != nullptr;
 }
 
 size_t adx_unet_workspace_bytes(const adx_unet* u, int32_t rows) {
@@ -785,6 +787,11 @@ int adx_unet_pipe_describe(const adx_unet* u, int32_t rows, int32_t* ints, int64
   return ADX_OK;
 }
 
+// Issues one eval forward's launches in order.  adx_unet_forward calls it behind its state checks; adx_unet_plan_describe calls
+// it on placeholder addresses with a plan recorder installed (plan.h), and every launch function then records instead of
+// launching -- so nothing here may read device memory or the tensors, only their addresses and strides.
+static int forward_launches(const adx_unet* u, const void* packed, void* workspace, const adx_unet_io* io, hipStream_t s);
+
 int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx_unet_io* io, adx_stream stream) {
   ADX_REQUIRE(u && packed && workspace && io, "adx_unet_forward: null argument");
   if (!u->packed_once) {
@@ -797,6 +804,10 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
               "output was set to NaN");
     return ADX_ERR_STATE;
   }
+  return forward_launches(u, packed, workspace, io, (hipStream_t)stream);
+}
+
+static int forward_launches(const adx_unet* u, const void* packed, void* workspace, const adx_unet_io* io, hipStream_t s) {
   const int rows = io->rows, dim = u->cfg.dim, H = u->cfg.horizon, D = u->cfg.transition_dim;
   ADX_REQUIRE(rows >= 1, "adx_unet_forward: rows must be >= 1");
   if (io->time_bias == nullptr) {
@@ -807,7 +818,6 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
   }
   const int x_rows = io->x_rows > 0 ? io->x_rows : rows;
   ADX_REQUIRE(x_rows == rows || x_rows == 1, "adx_unet_forward: x_rows must be rows (%d) or 1, got %d", rows, x_rows);
-  hipStream_t s = (hipStream_t)stream;
   const float* base = (const float*)packed;
   float* ws = (float*)workspace;
   const WsLayout wl = ws_layout(u, rows);
@@ -979,7 +989,7 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
       float* ya = ws + wl.ya;
       float* yb = ws + wl.yb;
       float* yc = ws + wl.yc;
-      pa.fault = pipe_fault_word();
+      pa.fault = plan_sink() != nullptr ? nullptr : pipe_fault_word();      // (the word is pinned host memory: a plan export allocates nothing)
       pa.epoch = split_tickets + kEpochSlot;                      // this forward's number, left there by the launch that cleared the tickets
       for (int k = 0; k < 7; ++k) {
         pa.st[k].w = base + run[k]->o_pw;
@@ -1102,6 +1112,86 @@ int adx_unet_forward(adx_unet* u, const void* packed, void* workspace, const adx
     ADX_CHECK_HIP(hipMemcpyAsync(io->time_embed, te, (size_t)rows * dim * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
   (void)D;
+  return ADX_OK;
+}
+
+int adx_unet_plan_describe(const adx_unet* u, int32_t rows, int32_t flags, int32_t* n_records, int32_t* ints, int32_t max_records) {
+  ADX_REQUIRE(u && n_records && ints, "adx_unet_plan_describe: null argument");
+  ADX_REQUIRE(rows >= 1 && max_records >= 1, "adx_unet_plan_describe: rows and max_records must be >= 1, got %d and %d", rows, max_records);
+  ADX_REQUIRE((flags & ~(ADX_PLAN_ASSUME_PACKED | ADX_PLAN_TIME_BIAS)) == 0, "adx_unet_plan_describe: unknown flags 0x%x", (unsigned)flags);
+  // placeholder addresses, never read: 256-byte aligned like the tensors and buffers the callers pass
+  auto fake = [](int k) { return reinterpret_cast<float*>((uintptr_t)(k + 1) << 36); };
+  const float* const base = fake(0);
+  float* const ws = fake(1);
+  adx_unet_io io;
+  memset(&io, 0, sizeof(io));
+  io.x = fake(2); io.out = fake(3); io.rows = rows;
+  if (flags & ADX_PLAN_TIME_BIAS) {
+    io.time_bias = fake(4);
+  } else {
+    io.img_feature = fake(4); io.feat_rows = rows;
+    io.t = reinterpret_cast<const int64_t*>(fake(5)); io.t_rows = rows;
+    if (u->cfg.guidance == 1) io.cond = fake(6);
+  }
+  std::vector<PlanLaunch> rec(512);
+  PlanSink sink;
+  sink.rec = rec.data(); sink.cap = (int)rec.size(); sink.assume_packed = (flags & ADX_PLAN_ASSUME_PACKED) != 0;
+  int rc;
+  {
+    PlanScope scope(&sink);
+    rc = forward_launches(u, base, ws, &io, nullptr);
+  }
+  if (rc != ADX_OK) return rc;
+  ADX_REQUIRE(sink.n <= max_records, "adx_unet_plan_describe: %d launches, room for %d", sink.n, max_records);
+  // name each launch's layer from its weight image: {group (adx_unet_status_name), block within the group or -1, conv}
+  struct Named { const float* w; int group, block, conv; };
+  std::vector<Named> names;
+  const int n = u->n_levels;
+  auto conv_names = [&](const ConvLayer& L, int group, int block, int conv) { names.push_back(Named{base + L.o_w, group, block, conv}); };
+  for (size_t b = 0; b < u->blocks.size(); ++b) {
+    const int group = (int)b / 2;      // two blocks per group, in execution order: down i = i, mid = n, up i = n + 1 + i
+    const ResBlock& B = u->blocks[b];
+    conv_names(B.a, group, (int)b % 2, ADX_PLAN_CONV_A);
+    conv_names(B.b, group, (int)b % 2, ADX_PLAN_CONV_B);
+    if (B.has_r) conv_names(B.r, group, (int)b % 2, ADX_PLAN_CONV_R);
+  }
+  for (size_t i = 0; i < u->downs.size(); ++i) conv_names(u->downs[i], (int)i, -1, ADX_PLAN_CONV_DOWN);
+  for (size_t i = 0; i < u->ups.size(); ++i) conv_names(u->ups[i], n + 1 + (int)i, -1, ADX_PLAN_CONV_UP);
+  conv_names(u->head0, 2 * n, -1, ADX_PLAN_CONV_HEAD0);
+  conv_names(u->head1, 2 * n, -1, ADX_PLAN_CONV_HEAD1);
+  conv_names(u->tlin, 0, -1, ADX_PLAN_CONV_TLIN);
+  for (size_t j = 0; j < u->attn.size(); ++j) {
+    conv_names(u->attn[j].qkv, (int)j, -1, ADX_PLAN_CONV_QKV);
+    conv_names(u->attn[j].out, (int)j, -1, ADX_PLAN_CONV_ATTN_OUT);
+  }
+  for (int i = 0; i < n; ++i)
+    if (u->down_chains[i].valid) names.push_back(Named{base + u->down_chains[i].st[0].L->o_cw, i, -1, ADX_PLAN_CONV_LEVEL});
+  for (int i = 0; i < n - 1; ++i)
+    if (u->up_chains[i].valid) names.push_back(Named{base + u->up_chains[i].st[0].L->o_cw, n + 1 + i, -1, ADX_PLAN_CONV_LEVEL});
+  if (u->pipe_ok) names.push_back(Named{base + u->blocks[2 * (n - 1)].b.o_pw, n - 1, -1, ADX_PLAN_CONV_RUN});
+  auto find = [&](const void* w, int* out3) {
+    out3[0] = -1; out3[1] = -1; out3[2] = -1;
+    for (const Named& k : names)
+      if (k.w == w) { out3[0] = k.group; out3[1] = k.block; out3[2] = k.conv; return true; }
+    return false;
+  };
+  const WsLayout wl = ws_layout(u, rows);
+  int group = 0;      // launches that carry no weights (embedding, ticket reset, attention LayerNorm / core) count with their neighbours
+  for (int i = 0; i < sink.n; ++i) {
+    const PlanLaunch& l = rec[i];
+    int a[3], b[3], layer[5] = {group, -1, -1, -1, -1};
+    if (l.w != nullptr) {
+      ADX_REQUIRE(find(l.w, a), "adx_unet_plan_describe: launch %d carries a weight image of no layer", i);
+      layer[0] = group = a[0]; layer[1] = a[1]; layer[2] = a[2];
+    }
+    if (l.w_b != nullptr) {
+      ADX_REQUIRE(find(l.w_b, b), "adx_unet_plan_describe: launch %d carries a second weight image of no layer", i);
+      layer[3] = b[1]; layer[4] = b[2];
+    }
+    const long long part_off = l.part != nullptr ? (long long)(static_cast<const float*>(l.part) - (ws + wl.scratch)) : -1;
+    plan_write(l, layer, part_off, ints + (size_t)i * ADX_PLAN_INTS);
+  }
+  *n_records = sink.n;
   return ADX_OK;
 }
 

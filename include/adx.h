@@ -207,6 +207,49 @@ int adx_unet_time_conditioning(adx_unet* u, const void* packed, void* workspace,
  * Refuses (ADX_ERR_*) a null handle or output and rows < 1. */
 int adx_unet_pipe_describe(const adx_unet* u, int32_t rows, int32_t* ints, int64_t* offs);
 
+/* For tests only: the launch plan of ONE eval forward of `rows` rows, one record per launch in launch order.  Needs no GPU,
+ * launches nothing and allocates nothing on a device: the call runs the forward's own host code -- the tile, split, chain
+ * and pipeline decisions of adx_unet_forward themselves, with the scratch and ticket words a forward owns -- on placeholder
+ * addresses, with every launch function recording its finished argument block instead of launching (csrc/plan.h).  The
+ * process-wide switches (ADX_UNET_CHAIN, ADX_UNET_PIPE, ADX_CHAIN_MASK, ADX_TCONV_EXACT) act as they do on a forward.
+ * The forward planned passes every per-row input (x_rows = t_rows = feat_rows = rows; `cond` under FREE_GUIDANCE), or,
+ * with ADX_PLAN_TIME_BIAS, a precomputed time_bias.  Whether the deepest level takes the pipeline launch also depends on
+ * the process (adx_unet_pipe_describe: runs); ADX_PLAN_ASSUME_PACKED plans as in a process whose device has seen an
+ * adx_unet_pack, which is how a CPU-only process learns what a GPU process launches.
+ * ints: ADX_PLAN_INTS words per record, at most max_records records (more launches: ADX_ERR_INVALID); *n_records: launches.
+ *   [0] group    layer group as the status words number them (adx_unet_status_name); a launch without weights counts with
+ *                the launch before it
+ *   [1] block    residual block within the group (0, 1), or -1
+ *   [2] conv     ADX_PLAN_CONV_*: which conv of the block / group (LEVEL: a whole chained level; RUN: the pipeline's seven
+ *                convs), or -1 for a launch without weights
+ *   [3] family   ADX_PLAN_*: the kernel
+ *   [4] bt, [5] row_tiles = ceil(rows / bt), [6] rows % bt: samples per row tile (the pipeline holds every row in one)
+ *   [7] ctiles   workgroups along the output channels (pipeline: 7 stages x P + the finisher)
+ *   [8] grid     = row_tiles x (ctiles x ksplit + ctiles_b)
+ *   [9] ksplit   workgroups sharing one (row tile, channel tile)'s reduction; [10] reduce: 0 no split, 1 ticket words, 2 a
+ *                reduce launch follows (its own record, family ADX_PLAN_REDUCE)
+ *   [11] chunks  staged input chunks one workgroup walks = ceil(min(channels of its share, cin_pad) / ck)
+ *   [12] vec_stage, [13] fast_epi, [14] live taps
+ *   [15] block_b, [16] conv_b, [17] ctiles_b: the second conv of a pair / mixed launch (-1, -1, 0 otherwise)
+ *   [18] ck, [19] cin_pad: channels per staged chunk, padded input channels
+ *   [20] part_floats, [21] part_off: ksplit > 1: the partial tiles' footprint and where it starts, in floats from the start of
+ *                the forward's split scratch (adx_unet_pipe_describe: offs[1]); -1: none
+ *   [22] dynamic LDS bytes, [23] lout, [24] cout (of the launch's last conv), [25] which launch without weights (1 time / condition
+ *                embedding, 2 ticket reset, 3 attention LayerNorm, 4 attention core), [26], [27] 0 */
+#define ADX_PLAN_INTS 28
+#define ADX_PLAN_ASSUME_PACKED 1
+#define ADX_PLAN_TIME_BIAS 2
+enum { ADX_PLAN_AUX = 0, ADX_PLAN_PIPE = 1, ADX_PLAN_CHAIN = 2, ADX_PLAN_KSPLIT = 3, ADX_PLAN_SHORTK = 4, ADX_PLAN_SHORTK_PAIR = 5,
+       ADX_PLAN_MIXED = 6, ADX_PLAN_GENERIC = 7, ADX_PLAN_EXACT = 8, ADX_PLAN_REDUCE = 9 };
+enum { ADX_PLAN_CONV_A = 0, ADX_PLAN_CONV_B = 1, ADX_PLAN_CONV_R = 2, ADX_PLAN_CONV_DOWN = 3, ADX_PLAN_CONV_UP = 4,
+       ADX_PLAN_CONV_HEAD0 = 5, ADX_PLAN_CONV_HEAD1 = 6, ADX_PLAN_CONV_TLIN = 7, ADX_PLAN_CONV_QKV = 8, ADX_PLAN_CONV_ATTN_OUT = 9,
+       ADX_PLAN_CONV_LEVEL = 10, ADX_PLAN_CONV_RUN = 11 };
+int adx_unet_plan_describe(const adx_unet* u, int32_t rows, int32_t flags, int32_t* n_records, int32_t* ints, int32_t max_records);
+/* The same for one adx_tconv_forward call on dense 16-byte aligned tensors of `batch` samples with a scratch of
+ * scratch_floats floats (0: none) and, if has_tickets, ticket words: group 0, block -1, conv 0, part_off 0. */
+int adx_tconv_plan_describe(const adx_tconv_desc* d, int32_t batch, int64_t scratch_floats, int32_t has_tickets, int32_t* n_records,
+                            int32_t* ints, int32_t max_records);
+
 /* ------------------------------------------------------------------------------------
  * Training step T1 (train.py:242-251), temporal stack: forward that keeps a tape, and backward.
  * The reference gets these from torch autograd; the gradients are written in PyTorch layouts.
