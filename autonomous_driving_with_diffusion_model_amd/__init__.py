@@ -5,6 +5,7 @@ Public surface mirrors the reference's packages:
     modeling.build_model(cfg)                         (reference: modeling/__init__.py)
     scheduler.{GuidanceDDIM,GuidanceDDPM,InpaintingDDIM,InpaintingDDPM}Scheduler, DDPMScheduler
     control.GuidanceLoss
+    DeviceNoise                                       (no reference counterpart: in-kernel sampler noise, noise.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
 All compute runs in libadx.so (hand-written HIP for gfx950); there is no CPU fallback.
 """
@@ -19,5 +20,6 @@ import os as _os
 _os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
 from . import _lib  # noqa: F401,E402
+from .noise import DeviceNoise  # noqa: E402
 
-__all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling"]
+__all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise"]

@@ -158,6 +158,11 @@ _SIGS = {
     "adx_image_augment": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "adx_ddim_step": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "adx_ddpm_step": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "adx_ddim_step_rng": (i32, [C.POINTER(StepCoef), vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "adx_ddpm_step_rng": (i32, [C.POINTER(StepCoef), vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "adx_noise_normal": (i32, [vp, i32, i64, vp, i64, vp]),
+    "adx_noise_words": (i32, [vp, i32, i64, vp, i64, vp]),
+    "adx_noise_advance": (i32, [vp, vp]),
     "adx_add_noise": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
 }
 

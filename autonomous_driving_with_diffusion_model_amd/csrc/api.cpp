@@ -67,6 +67,13 @@ int ddim_step(const adx_step_coef* c, const float* mo, const float* x, const flo
               const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
 int ddpm_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
               const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
+int ddim_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
+                  const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
+int ddpm_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
+                  const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
+int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);
+int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s);
+int noise_advance(uint32_t* state, hipStream_t s);
 int add_noise(const float* x, const float* n, const int64_t* t, const float* sa, const float* sb, int n_train,
               float* out, int batch, int horizon, int dim, int zero_first, hipStream_t s);
 
@@ -146,6 +153,25 @@ int adx_ddpm_step(const adx_step_coef* c, const float* model_output, const float
                   int32_t dim, adx_stream s) {
   return adx::ddpm_step(c, model_output, sample, noise, target, mask, prev, x0, batch, horizon, dim, (hipStream_t)s);
 }
+int adx_ddim_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
+                      int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
+                      int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::ddim_step_rng(c, model_output, sample, noise_state, slot, row_offset, target, mask, prev, x0, batch, horizon, dim,
+                            (hipStream_t)s);
+}
+int adx_ddpm_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
+                      int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
+                      int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::ddpm_step_rng(c, model_output, sample, noise_state, slot, row_offset, target, mask, prev, x0, batch, horizon, dim,
+                            (hipStream_t)s);
+}
+int adx_noise_normal(const uint32_t* state, int32_t slot, int64_t first_elem, float* out, int64_t n, adx_stream s) {
+  return adx::noise_normal(state, slot, first_elem, out, n, (hipStream_t)s);
+}
+int adx_noise_words(const uint32_t* state, int32_t slot, int64_t first_elem, uint32_t* out, int64_t n, adx_stream s) {
+  return adx::noise_words(state, slot, first_elem, out, n, (hipStream_t)s);
+}
+int adx_noise_advance(uint32_t* state, adx_stream s) { return adx::noise_advance(state, (hipStream_t)s); }
 int adx_add_noise(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
                   int32_t n_train, float* out, int32_t batch, int32_t horizon, int32_t dim, int32_t zero_first,
                   adx_stream s) {

@@ -12,7 +12,13 @@
 // coefficients (a host sync per step).  Here the host passes the fp32-rounded scalars by value
 // and the kernel repeats the reference's elementwise operations in the same order with
 // contraction disabled, so results are bit-identical to the torch CPU path.
+//
+// The step's Gaussian term comes from one of two sources, chosen at compile time: a noise TENSOR the caller drew (the
+// reference's path: torch.randn, or an injected variance_noise), or the counter-based noise stream of csrc/noise.h, evaluated
+// in the kernel where the tensor element would be read (adx_*_step_rng: no launch, no allocation, no [B,H,D] round trip, and a
+// captured graph draws fresh noise on every replay because the stream's state is read through a pointer).
 #include "adx_common.h"
+#include "noise.h"
 
 namespace adx {
 
@@ -26,6 +32,10 @@ struct StepArgs {
   float* prev;
   float* x0;
   int total, horizon, dim;
+  // noise stream (RNG kernels only): state words, slot = the integer timestep, first logical element of this launch's rows
+  const uint32_t* ns;
+  uint32_t slot;
+  uint64_t base;
 };
 
 __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
@@ -33,7 +43,7 @@ __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
   return v < lo ? lo : (v > hi ? hi : v);
 }
 
-template <bool DDPM>
+template <bool DDPM, bool RNG>
 __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -66,7 +76,14 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
     eps = p2 + q2;
   }
   if (c.clip) x0 = clamp_nan(x0, -c.clip_range, c.clip_range);
-  const float zn = (a.z != nullptr) ? a.z[e] : 0.f;
+  float zn;
+  if (RNG) {
+    // the element's index in the LOGICAL tensor, not in this launch: a shard of rows draws what the full batch draws there
+    const bool need = c.add_noise || (c.inpaint && c.known_noise && a.tgt != nullptr && a.mask != nullptr);
+    zn = need ? noise_normal_at(a.ns, a.slot, a.base + (uint64_t)e) : 0.f;
+  } else {
+    zn = (a.z != nullptr) ? a.z[e] : 0.f;
+  }
   float prev;
   if (!DDPM) {
     if (c.use_clipped_model_output) {
@@ -116,31 +133,101 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
   if (a.x0 != nullptr) a.x0[e] = x0;
 }
 
-template <bool DDPM>
-static int step_launch(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
-                       const float* mask, float* prev, float* x0, int batch, int horizon, int dim, hipStream_t s) {
+// e >> 2 is the stream's 32-bit counter word: logical elements live in [0, 2^34)
+static const int64_t kNoiseElems = (int64_t)1 << 34;
+
+template <bool DDPM, bool RNG>
+static int step_launch(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
+                       int64_t row_offset, const float* tgt, const float* mask, float* prev, float* x0, int batch, int horizon,
+                       int dim, hipStream_t s) {
   ADX_REQUIRE(c && mo && x && prev, "scheduler step: null tensor");
   ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1, "scheduler step: empty shape");
   ADX_REQUIRE(c->prediction_type >= 0 && c->prediction_type <= 2,
               "prediction_type given as %d must be one of `epsilon`, `sample`, or `v_prediction`", c->prediction_type);
-  ADX_REQUIRE(!(c->add_noise || (c->inpaint && c->known_noise && tgt && mask)) || z != nullptr,
-              "scheduler step: noise tensor required");
   StepArgs a;
+  a.ns = nullptr; a.slot = 0; a.base = 0;
+  if (RNG) {
+    ADX_REQUIRE(ns != nullptr, "scheduler step: null noise state");
+    ADX_REQUIRE(row_offset >= 0, "scheduler step: negative row_offset %lld", (long long)row_offset);
+    const int64_t per = (int64_t)horizon * dim;        // < 2^62
+    ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + batch) <= kNoiseElems / per,
+                "scheduler step: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements",
+                (long long)row_offset, (long long)row_offset + batch, (long long)per);
+    a.ns = ns; a.slot = (uint32_t)slot; a.base = (uint64_t)row_offset * (uint64_t)per;
+  } else {
+    ADX_REQUIRE(!(c->add_noise || (c->inpaint && c->known_noise && tgt && mask)) || z != nullptr,
+                "scheduler step: noise tensor required");
+  }
   a.c = *c;
   a.mo = mo; a.x = x; a.z = z; a.tgt = tgt; a.mask = mask; a.prev = prev; a.x0 = x0;
   a.total = batch * horizon * dim; a.horizon = horizon; a.dim = dim;
-  step_kernel<DDPM><<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
+  step_kernel<DDPM, RNG><<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
 
 int ddim_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
               const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<false>(c, mo, x, z, tgt, mask, prev, x0, b, h, d, s);
+  return step_launch<false, false>(c, mo, x, z, nullptr, 0, 0, tgt, mask, prev, x0, b, h, d, s);
 }
 int ddpm_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
               const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<true>(c, mo, x, z, tgt, mask, prev, x0, b, h, d, s);
+  return step_launch<true, false>(c, mo, x, z, nullptr, 0, 0, tgt, mask, prev, x0, b, h, d, s);
+}
+int ddim_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
+                  const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
+  return step_launch<false, true>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, prev, x0, b, h, d, s);
+}
+int ddpm_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
+                  const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
+  return step_launch<true, true>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, prev, x0, b, h, d, s);
+}
+
+// Fill out[0, n) with the stream's values of the logical elements [first, first + n): what a step kernel draws at those
+// elements under the same (state, slot).  One thread per element through the same __device__ function as the step.
+template <bool NORMAL, typename T>
+__global__ void __launch_bounds__(256) noise_fill_kernel(const uint32_t* state, uint32_t slot, uint64_t first, T* out, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (NORMAL) out[i] = (T)noise_normal_at(state, slot, first + i);
+  else out[i] = (T)noise_word_at(state, slot, first + i);
+}
+
+template <bool NORMAL, typename T>
+static int noise_fill(const uint32_t* state, int32_t slot, int64_t first, T* out, int64_t n, hipStream_t s) {
+  ADX_REQUIRE(state != nullptr, "noise fill: null noise state");
+  ADX_REQUIRE(first >= 0 && n >= 0, "noise fill: negative first element %lld or count %lld", (long long)first, (long long)n);
+  ADX_REQUIRE(first <= kNoiseElems && n <= kNoiseElems - first,
+              "noise fill: elements [%lld, %lld + %lld) leave the noise stream's 2^34 elements", (long long)first, (long long)first,
+              (long long)n);
+  if (n == 0) return ADX_OK;
+  ADX_REQUIRE(out != nullptr, "noise fill: null output");
+  noise_fill_kernel<NORMAL, T><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(state, (uint32_t)slot, (uint64_t)first, out,
+                                                                                      (uint64_t)n);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
+}
+
+int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s) {
+  return noise_fill<true, float>(state, slot, first, out, n, s);
+}
+int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s) {
+  return noise_fill<false, uint32_t>(state, slot, first, out, n, s);
+}
+
+// tick += 1 (64-bit, two words), by one vector lane: the next launches on the stream draw under the new tick
+__global__ void noise_advance_kernel(uint32_t* state) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const uint32_t lo = state[2] + 1u;
+  state[2] = lo;
+  if (lo == 0u) state[3] = state[3] + 1u;
+}
+
+int noise_advance(uint32_t* state, hipStream_t s) {
+  ADX_REQUIRE(state != nullptr, "noise advance: null noise state");
+  noise_advance_kernel<<<dim3(1), dim3(1), 0, s>>>(state);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
 }
 
 __global__ void __launch_bounds__(256) add_noise_kernel(const float* __restrict__ x, const float* __restrict__ n,

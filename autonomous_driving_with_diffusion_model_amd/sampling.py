@@ -10,6 +10,9 @@ Differences from the callers, both optional and numerically identical:
   * `target` may be [B, 2] (one goal per scene) instead of one [2] goal repeated over the batch;
   * `fuse=True` folds the classifier-free combine and the `[:, 0, :3] = 0` write into the scheduler's
     step kernel instead of issuing them as separate torch ops.
+A third option changes WHICH noise a stochastic sampler sees, not the arithmetic: `noise=DeviceNoise(...)` draws the initial
+trajectory and every step's noise from the counter-based stream of noise.py inside the step kernel, where the callers draw
+`torch.randn` tensors -- the same loop then also runs as one HIP graph (`GraphedSampler(..., noise=...)`).
 """
 from __future__ import annotations
 
@@ -20,6 +23,7 @@ import torch
 
 from ._lib import AdxRangeError
 from .misc.constant import GuidanceType
+from .noise import DeviceNoise
 
 
 def _targets(target: Optional[torch.Tensor], batch: int) -> Optional[torch.Tensor]:
@@ -36,12 +40,20 @@ def _targets(target: Optional[torch.Tensor], batch: int) -> Optional[torch.Tenso
 def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                   init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, scale_xy: bool = True,
                   step_noise: Optional[Callable[[int, tuple], torch.Tensor]] = None,
-                  set_timesteps: bool = True) -> torch.Tensor:
+                  set_timesteps: bool = True, noise: Optional[DeviceNoise] = None) -> torch.Tensor:
+    """`noise`: a DeviceNoise.  The call is then one tick of the noise stream: `begin_tick()` first, the initial trajectory
+    (when `init_trajs` is not given) from `INIT_SLOT`, and every scheduler step draws inside its kernel at the slot of its
+    timestep -- no noise tensor, no torch generator."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     model.eval()
     device = image.device
+    if noise is not None:
+        if step_noise is not None:
+            raise ValueError("generate_traj: pass `noise` (the in-kernel stream) or `step_noise` (injected tensors), not both")
+        noise.begin_tick()
     if init_trajs is None:
-        init_trajs = torch.randn((image.shape[0], cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM), device=device)
+        shape = (image.shape[0], cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM)
+        init_trajs = torch.randn(shape, device=device) if noise is None else noise.normal(DeviceNoise.INIT_SLOT, shape)
     trajs = init_trajs.clone().detach()
     B = trajs.shape[0]
     tgt = _targets(target, B)
@@ -67,18 +79,19 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     # beside the previous step's temporal stack (modeling/perception.py:frozen_image; a no-op for holders without the method)
     frozen = getattr(getattr(model, "perception", None), "frozen_image", None)
     with (frozen(image) if frozen is not None else contextlib.nullcontext()):
-        trajs = _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device)
+        trajs = _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device,
+                           noise)
     trajs = trajs.to(torch.float32).clamp(-1, 1)
     if scale_xy:
         trajs[..., :2] *= model.magic_num
     return trajs
 
 
-def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device):
+def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device, noise=None):
     action = None
     for i, t in enumerate(scheduler.timesteps):
         tck = None if tc is None else (tc, i)
-        extra = {}
+        extra = {} if noise is None else {"generator": noise}
         if is_ddpm and step_noise is not None:
             extra["variance_noise"] = step_noise(i, tuple(trajs.shape)).to(device)
         if use == GuidanceType.FREE_GUIDANCE:
@@ -120,10 +133,20 @@ def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair,
 
 
 @torch.no_grad()
-def evaluate_sample(model, noise_scheduler, image: torch.Tensor, init_trajs: torch.Tensor, n_steps: int,
-                    step_noise: Optional[Callable[[int, tuple], torch.Tensor]] = None) -> torch.Tensor:
-    """train.evaluate's loop: stock DDPM scheduler, B copies of one image, fresh/injected noise."""
+def evaluate_sample(model, noise_scheduler, image: torch.Tensor, init_trajs: Optional[torch.Tensor], n_steps: int,
+                    step_noise: Optional[Callable[[int, tuple], torch.Tensor]] = None,
+                    noise: Optional[DeviceNoise] = None) -> torch.Tensor:
+    """train.evaluate's loop: stock DDPM scheduler, B copies of one image, fresh/injected noise.  `noise`: as in
+    `generate_traj` (one tick of the noise stream; `init_trajs` may then be None: one trajectory per image row)."""
     model.eval()
+    if noise is not None:
+        if step_noise is not None:
+            raise ValueError("evaluate_sample: pass `noise` (the in-kernel stream) or `step_noise` (injected tensors), not both")
+        noise.begin_tick()
+    if init_trajs is None:
+        if noise is None:
+            raise ValueError("evaluate_sample: init_trajs is required without `noise`")
+        init_trajs = noise.normal(DeviceNoise.INIT_SLOT, (image.shape[0], model.horizon, model.transition_dim))
     B = init_trajs.shape[0]
     trajs = init_trajs.clone()
     trajs[:, 0, :3] = 0
@@ -134,7 +157,7 @@ def evaluate_sample(model, noise_scheduler, image: torch.Tensor, init_trajs: tor
         tc = model.time_conditioning(image, (ts.tensor if hasattr(ts, "tensor") else torch.as_tensor(ts)).to(image.device), rows=B)
     for i, t in enumerate(noise_scheduler.timesteps):
         out = model(trajs, image, t.reshape(-1).repeat(B), time_cond=None if tc is None else (tc, i))
-        kw = {}
+        kw = {} if noise is None else {"generator": noise}
         if step_noise is not None:
             kw["variance_noise"] = step_noise(i, tuple(trajs.shape)).to(image.device)
         trajs = noise_scheduler.step(out, t, trajs, **kw).prev_sample
@@ -151,15 +174,19 @@ class GraphedSampler:
     B = 1 the 50-step DDIM loop takes 29.2 ms eagerly and 26.4 ms as one graph launch on an MI355X
     (tools/graph_probe.py; at B = 64 the GPU is the bound either way).  Results are bit-identical to the eager loop.
 
-    Deterministic samplers only (DDIM with eta = 0; a DDPM loop would replay its captured noise), eval mode, fused
-    step path.  Inputs are copied into static buffers; the camera frame's perception pass is part of the graph, so
-    every replay sees the new frame.
+    Without `noise`: deterministic samplers only (DDIM with eta = 0; a DDPM loop would replay its captured noise tensors).
+    With `noise=DeviceNoise(...)` the DDPM scheduler is accepted too: `begin_tick()`, the initial draw (when `init_trajs`
+    is not passed) and every step's in-kernel draw are nodes of the graph and read the stream's state from device memory,
+    so replay k of a fresh object samples under tick k -- bit for bit what the eager `generate_traj(noise=...)` gives there.
+    Eval mode, fused step path.  Inputs are copied into static buffers; the camera frame's perception pass is part of
+    the graph, so every replay sees the new frame.
     """
 
-    def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True):
-        if not getattr(scheduler, "_is_ddim", False) or float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0:
-            raise ValueError("GraphedSampler needs a deterministic sampler (DDIM, eta = 0)")
-        self.model, self.scheduler, self.cfg, self.scale_xy = model, scheduler, cfg, scale_xy
+    def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None):
+        if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not getattr(scheduler, "_is_ddim", False)):
+            raise ValueError("GraphedSampler needs a deterministic sampler (DDIM, eta = 0), or a DeviceNoise for the DDPM sampler "
+                             "(noise=...)")
+        self.model, self.scheduler, self.cfg, self.scale_xy, self.noise = model, scheduler, cfg, scale_xy, noise
         self._key = None
         self._graph = None
 
@@ -170,15 +197,18 @@ class GraphedSampler:
         # the graph reads these device tensors on every replay: keep them alive even if somebody calls
         # scheduler.set_timesteps() again (which replaces the scheduler's own references)
         self._timesteps = list(self.scheduler.timesteps)
-        self._img, self._init = image.clone(), init_trajs.clone()
+        self._img, self._init = image.clone(), None if init_trajs is None else init_trajs.clone()
         self._tgt = None if target is None else target.clone()
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, self._img, self._tgt, self._init,  # noqa: E731
-                                    fuse=True, scale_xy=self.scale_xy, set_timesteps=False)
+                                    fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise)
+        tick = None if self.noise is None else self.noise.tick()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):          # warm-up off the capture: lazy packs, workspaces, tile tables
             run()
         torch.cuda.current_stream(dev).wait_stream(side)
+        if tick is not None:
+            self.noise.seek(tick)              # the warm-up consumed a tick: give it back, so that the first replay is the next one
         self.model._feat_cache = None          # the perception pass must be IN the graph (new frame every tick)
         self._graph = torch.cuda.CUDAGraph()
         # thread-local capture mode: a process group's watchdog thread (multi-rank runs) may query events while this
@@ -207,17 +237,20 @@ class GraphedSampler:
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if init_trajs is None:
+        if init_trajs is None and self.noise is None:
             init_trajs = torch.randn((image.shape[0], self.cfg.MODEL.HORIZON, self.cfg.MODEL.TRANSITION_DIM),
                                      device=image.device)
-        key = (tuple(image.shape), None if target is None else tuple(target.shape), tuple(init_trajs.shape), image.device,
+        # init_trajs None (with a DeviceNoise): the initial trajectory is drawn inside the graph, from INIT_SLOT
+        key = (tuple(image.shape), None if target is None else tuple(target.shape),
+               None if init_trajs is None else tuple(init_trajs.shape), image.device,
                self.cfg.EVAL.SAMPLE_STEPS, self.cfg.GUIDANCE.USE_COND)
         if key != self._key or self._graph is None or self._pointers != self._model_pointers():
             self._capture(image, target, init_trajs)
             self._key = key
         else:
             self._img.copy_(image)
-            self._init.copy_(init_trajs)
+            if init_trajs is not None:
+                self._init.copy_(init_trajs)
             if target is not None:
                 self._tgt.copy_(target)
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the

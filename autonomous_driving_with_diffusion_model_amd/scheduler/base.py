@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..noise import DeviceNoise
 
 PRED = {"epsilon": 0, "sample": 1, "v_prediction": 2}
 
@@ -226,18 +227,32 @@ class SchedulerBase:
         c.sqrt_beta_t = float(b_t ** 0.5)
         return c
 
-    def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True):
+    def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True, slot: int = 0):
+        """`noise`: the step's noise tensor (or None), or a DeviceNoise -- then the kernel draws element by element from the
+        noise stream at `slot` (the integer timestep) and no tensor exists."""
         B, H, D = x.shape
         prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
-        fn = L.lib().adx_ddpm_step if ddpm else L.lib().adx_ddim_step
         import ctypes as C
+        if isinstance(noise, DeviceNoise):
+            if noise.device != x.device:
+                raise ValueError(f"the DeviceNoise lives on {noise.device}, the sample on {x.device}")
+            fn = L.lib().adx_ddpm_step_rng if ddpm else L.lib().adx_ddim_step_rng
+            L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), noise.state_ptr(), int(slot), noise.row_offset, L.ptr(target),
+                       L.ptr(mask), prev.data_ptr(), L.ptr(x0), B, H, D, L.stream_ptr(x.device)), "scheduler step")
+            return prev, x0
+        fn = L.lib().adx_ddpm_step if ddpm else L.lib().adx_ddim_step
         L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(noise), L.ptr(target), L.ptr(mask), prev.data_ptr(),
                    L.ptr(x0), B, H, D, L.stream_ptr(x.device)), "scheduler step")
         return prev, x0
 
     @staticmethod
     def _noise(shape, generator, device, dtype, variance_noise=None):
+        if isinstance(generator, DeviceNoise):      # no tensor: the step kernel draws from the stream
+            if variance_noise is not None:
+                raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either "
+                                 "`generator` or `variance_noise` stays `None`.")
+            return generator
         if variance_noise is not None:
             return L.require_gpu_f32(variance_noise, "variance_noise")
         return torch.randn(tuple(shape), generator=generator, device=device, dtype=dtype)
@@ -290,7 +305,7 @@ class DDPMScheduler(SchedulerBase):
         mo, x = self._check_step_inputs(model_output, sample)
         c = self._ddpm_coef(t)
         z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise) if t > 0 else None
-        prev, x0 = self._launch(True, c, mo, x, z, None, None)
+        prev, x0 = self._launch(True, c, mo, x, z, None, None, slot=t)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)

@@ -53,7 +53,7 @@ class GuidanceDDIMScheduler(DDIMScheduler):
                 raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either "
                                  "`generator` or `variance_noise` stays `None`.")
             z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)
-        prev, x0 = self._launch(False, c, mo, x, z, None, None)
+        prev, x0 = self._launch(False, c, mo, x, z, None, None, slot=t)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
@@ -84,7 +84,7 @@ class GuidanceDDPMScheduler(DDPMScheduler):
             c.cfg_combine, c.free_scale = 1, float(cfg_scale)
         c.zero_first = int(zero_first)
         z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise) if t > 0 else None
-        prev, x0 = self._launch(True, c, mo, x, z, None, None)
+        prev, x0 = self._launch(True, c, mo, x, z, None, None, slot=t)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)

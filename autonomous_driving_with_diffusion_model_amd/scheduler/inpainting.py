@@ -32,7 +32,7 @@ class InpaintingDDIMScheduler(DDIMScheduler):
             # the reference draws the RePaint noise first and, when eta > 0 and no variance_noise was
             # given, a second independent tensor for the eta term; with variance_noise both are that tensor
             z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)
-        prev, x0 = self._launch(False, c, mo, x, z, tt, tm)
+        prev, x0 = self._launch(False, c, mo, x, z, tt, tm, slot=t)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
@@ -47,7 +47,7 @@ class InpaintingDDPMScheduler(DDPMScheduler):
         mo, x = self._check_step_inputs(model_output, sample)
         tt, tm = _known(target_traj, target_mask, x)
         z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)  # drawn even at t == 0 (:100-109)
-        prev, x0 = self._launch(True, c, mo, x, z, tt, tm)
+        prev, x0 = self._launch(True, c, mo, x, z, tt, tm, slot=t)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)

@@ -543,6 +543,40 @@ int adx_ddim_step(const adx_step_coef* c, const float* model_output, const float
 int adx_ddpm_step(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                   const float* target, const float* mask, float* prev, float* x0,
                   int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+/* ------------------------------------------------------------------------------------
+ * Noise stream v1: standard normals as a pure function of (seed, tick, slot, element).  No reference counterpart (the
+ * reference draws torch.randn per step); the values differ from torch's for the same seed.  Fixtures and users depend on
+ * this definition -- a change is a new stream version, never an edit.
+ *
+ *   words    Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85),
+ *            key = (seed low 32, seed high 32), counter = (e >> 2, slot, tick low 32, tick high 32) -> w0..w3
+ *   e        the element's flat index in the LOGICAL tensor [rows][H][D]: e = ((row_offset + b) * H + h) * D + d; never a
+ *            thread or tile index, so the values do not move with the launch shape or with how rows are sharded.
+ *            e >> 2 must fit 32 bits: e < 2^34, refused otherwise.
+ *   slot     the integer timestep t the scheduler step is taken at; ADX_NOISE_INIT_SLOT for the initial trajectory
+ *   normals  u_i = ((w_i >> 8) + 0.5) * 2^-24 in (0, 1);  r = sqrt(-2 ln u0), z0 = r cos(2 pi u1), z1 = r sin(2 pi u1);
+ *            z2, z3 the same from (u2, u3).  Element e takes z[e & 3] (adx_noise_words: w[e & 3]).  Accurate fp32 maths.
+ *   state    four 32-bit words {seed_lo, seed_hi, tick_lo, tick_hi} in DEVICE memory.  Every kernel reads them through the
+ *            pointer when it runs, so a captured graph draws under the values current at each replay.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_NOISE_INIT_SLOT (-1)   /* slot 0xFFFFFFFF */
+#define ADX_NOISE_STATE_WORDS 4
+
+/* out[i] = the stream's normal / raw word of logical element first_elem + i, i in [0, n), under the state's current seed and
+ * tick; first_elem and n need not be multiples of 4.  Exactly what a *_step_rng kernel draws at those elements. */
+int adx_noise_normal(const uint32_t* state, int32_t slot, int64_t first_elem, float* out, int64_t n, adx_stream s);
+int adx_noise_words(const uint32_t* state, int32_t slot, int64_t first_elem, uint32_t* out, int64_t n, adx_stream s);
+/* tick += 1 (64-bit) by a one-thread kernel on the stream: capturable, ordered with the draws around it */
+int adx_noise_advance(uint32_t* state, adx_stream s);
+/* adx_ddim_step / adx_ddpm_step with the noise tensor replaced by the stream: element (b, h, d) of the launch draws logical
+ * element ((row_offset + b) * H + h) * D + d of `slot`, inside the step kernel, only where the step uses noise. */
+int adx_ddim_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
+                      int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
+                      int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+int adx_ddpm_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
+                      int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
+                      int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+
 /* add_noise (train.py:234) fused with the [...,0,:3] = 0 of train.py:235 when zero_first != 0.
  * sqrt_ab / sqrt_1mab are the host tables sqrt(abar), sqrt(1-abar) of length n_train. */
 int adx_add_noise(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
