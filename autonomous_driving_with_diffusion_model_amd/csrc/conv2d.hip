@@ -402,6 +402,20 @@ static int conv2d_launch(const ConvSpec& L, const float* base, const float* x, c
 static thread_local float* t_split_scratch = nullptr;
 static thread_local size_t t_split_floats = 0;
 void conv2d_set_split_scratch(float* p, size_t floats) { t_split_scratch = p; t_split_floats = p != nullptr ? floats : 0; }
+// compute units of the calling thread's current device, asked once per device (devices folded modulo 64, like DeviceOnce)
+static int device_cus(int* cus) {
+  static std::atomic<int> known[64];
+  int dev = 0;
+  ADX_CHECK_HIP(hipGetDevice(&dev));
+  std::atomic<int>& n = known[dev & 63];
+  if (n.load(std::memory_order_relaxed) == 0) {
+    hipDeviceProp_t prop;
+    ADX_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
+    n.store(prop.multiProcessorCount > 8 ? prop.multiProcessorCount : 8, std::memory_order_relaxed);
+  }
+  *cus = n.load(std::memory_order_relaxed);
+  return ADX_OK;
+}
 static thread_local uint32_t* t_status = nullptr;
 void conv2d_set_status(uint32_t* word) { t_status = word; }
 uint32_t* conv2d_status() { return t_status; }
@@ -420,7 +434,7 @@ int conv2d_launch_raw(const ConvSpec& L, const float* x, const float* w, const f
   a.x_u8 = nullptr;
   a.d2s_cin = 0; a.d2s_h = 0; a.d2s_w = 0; a.stem_seg_tiles = 0; a.stem_nseg = 1;
   a.status = t_status;
-  a.ksplit = 1; a.cper = 0; a.part = t_split_scratch; a.part_stride = t_split_floats;   // part_stride: capacity until the launch fixes it
+  a.ksplit = 1; a.cper = 0; a.part = t_split_scratch; a.part_stride = 0;
   a.stats_part = nullptr; a.stats_p = 0;
   a.bs_raw = a.bs_out = a.bs_mean = a.bs_rstd = a.bs_gamma = a.bs_beta = nullptr; a.bs_mask = 0; a.bs_bits = nullptr; a.res_bits = nullptr;
   if (bst != nullptr) {
@@ -430,28 +444,33 @@ int conv2d_launch_raw(const ConvSpec& L, const float* x, const float* w, const f
     a.bs_raw = bst->raw; a.bs_out = bst->out; a.bs_mean = bst->mean; a.bs_rstd = bst->rstd; a.bs_gamma = bst->gamma;
     a.bs_beta = bst->beta; a.bs_mask = bst->mask; a.bs_bits = bst->mask == 1 ? bst->bits : nullptr;
     a.res_bits = bst->res_bits;
-    ADX_REQUIRE(a.res_bits == nullptr || (res != nullptr && stats_part != nullptr &&
-                                          conv2d_hs3x3_dgrad_stats(L, N, H, W, (fmt & kFmtXCells) != 0, stats_floats)),
-                "conv2d: a masked residual belongs to a data-gradient launch with the statistics epilogue");
   }
   a.x_cells = (fmt & kFmtXCells) != 0; a.y_cells = (fmt & kFmtYCells) != 0; a.res_cells = (fmt & kFmtResCells) != 0 && res != nullptr;
-  // cells: plain launches of the pipelined 3x3 kernel (the inference executor), or the INPUT of a training-forward launch
-  const bool train_cells = fmt == kFmtXCells && stats_part != nullptr && stats_p != nullptr && bst == nullptr && x_amax == nullptr &&
-                           conv2d_hs3x3_train_cells(L, N, H, W, stats_floats);
-  // ... or the input of a data-gradient launch: a gradient written as cells under a known power-of-two scale
-  const bool dgrad_cells = fmt == (kFmtXCells | kFmtXScaled) && L.dgrad && x_amax != nullptr && x_amax_n < 0 &&
-                           conv2d_hs3x3_dgrad_cells(L, N, H, W);
-  if (dgrad_cells) fmt = kFmtXCells;
-  ADX_REQUIRE(fmt == 0 || train_cells || dgrad_cells || (stats_part == nullptr && conv2d_hs3x3_plain(L, N, H, W)),
-              "conv2d: the cell layout belongs to plain launches of the pipelined 3x3 kernel (%d -> %d, k%d s%d)", L.cin, L.cout, L.k, L.stride);
+  // everything the 3x3 stride-1 split-fp16 kernels decide about this launch (family none: another kernel's)
+  Hs3x3Query q;
+  q.N = N; q.H = H; q.W = W; q.fmt = fmt;
+  q.stats_floats = stats_part != nullptr && stats_p != nullptr ? stats_floats : 0;
+  q.bst_mask = a.bs_mask; q.bst_bits = a.bs_bits != nullptr;
+  q.x_scale = x_amax == nullptr ? kXScaleNone : (x_amax_n < 0 ? kXScalePre : kXScaleDynamic);
+  q.affine = scale != nullptr; q.relu = relu != 0; q.has_res = res != nullptr;
+  q.y_aligned = (reinterpret_cast<uintptr_t>(y) & 15) == 0; q.res_aligned = (reinterpret_cast<uintptr_t>(res) & 15) == 0;
+  q.split_floats = t_split_floats;
+  if (L.k == 3 && L.stride == 1) {      // (the persistent grid of the 16x16x32 kernel)
+    const int rc = device_cus(&q.cus);
+    if (rc != ADX_OK) return rc;
+  }
+  const Hs3x3Plan plan = conv2d_hs3x3_plan(L, q);
+  ADX_REQUIRE(a.res_bits == nullptr || (res != nullptr && L.dgrad && plan.stats == 2),
+              "conv2d: a masked residual belongs to a data-gradient launch with the statistics epilogue");
+  ADX_REQUIRE(plan.admitted, "conv2d: the cell layout belongs to plain launches of the pipelined 3x3 kernel (%d -> %d, k%d s%d)", L.cin, L.cout,
+              L.k, L.stride);
   if (conv2d_hs_eligible(L)) {
-    if (stats_part != nullptr && stats_p != nullptr && conv2d_hs_stats_tiles(L, a) > 0 &&
-        (size_t)conv2d_hs_stats_tiles(L, a) * (L.cout * 2 + L.cout / 64) <= stats_floats) {     // (+ the data gradient's max |dz| per slab)
+    if (plan.stats != 0) {
       a.stats_part = stats_part;
-      a.stats_p = conv2d_hs_stats_tiles(L, a);
-      *stats_p = a.stats_p;
+      a.stats_p = plan.stats_tiles;
+      *stats_p = plan.stats_tiles;
     }
-    return conv2d_hs_launch(L, a, s);
+    return conv2d_hs_launch(L, a, s, &plan);
   }
   const int rows = (L.stride == 1 && L.k == 3 && g_conv_rows == 2) ? 2 : 1;   // 8-row tiles for the 3x3 stride-1 convs
   const int th = 4 * rows;

@@ -1533,12 +1533,13 @@ int conv2d_hs_pack_many(const HsPackJob* jobs, int n, hipStream_t s) {
   return ADX_OK;
 }
 
-bool conv2d_hs_eligible(const ConvSpec& L) {
-  if (debug_switches().conv_exact) return false;     // ADX_CONV_EXACT=1: every conv on the exact-fp32 MFMA kernels
+static bool hs_eligible(const ConvSpec& L, const DebugSwitches& sw) {
+  if (sw.conv_exact) return false;     // ADX_CONV_EXACT=1: every conv on the exact-fp32 MFMA kernels
   if (hs_is_stem(L) && !L.dgrad) return true;
   if (L.cin % kHsCC != 0 || L.cin_pad != L.cin || L.cout % kHsCout != 0) return false;
   return L.k == 3 && (L.stride == 1 || L.stride == 2);
 }
+bool conv2d_hs_eligible(const ConvSpec& L) { return hs_eligible(L, debug_switches()); }
 
 size_t conv2d_packed_floats(const ConvSpec& L) {
   const size_t direct = (size_t)L.k * L.k * L.cin_pad * L.cout;
@@ -1672,7 +1673,6 @@ int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const floa
   a.x_cells = x_cells;
   a.y_cells = y_cells;
   a.status = conv2d_status();
-  (void)ds;
   return conv2d_hs_launch(c1, a, s);
 }
 
@@ -1708,242 +1708,166 @@ __global__ void __launch_bounds__(256) conv2d_split_reduce_kernel(const float* _
   range_flag(status, out_of_fp16(amax));
 }
 
-// fp32-layout launches of a whole batch tile the virtual row too (conv2d_hs3x3_kernel: VR) -- training forward / data gradient
-static bool hs_vrow_ok(const Conv2dArgs& a) {
-  return debug_switches().conv_vrow && a.N > 1 && (long)a.N * (a.OW + 1) < (1L << 21) &&
-         (size_t)a.N * a.Cout * a.OH * a.OW * sizeof(float) < 0xC0000000u && (size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u;
+// LDS bytes of conv2d_hs3x3_kernel<MODE, STATS>: the patch and weight buffers, the BN constants (STATS == 2: + the consumer BatchNorm's)
+static constexpr size_t hs3x3_lds(int mode, int stats) {
+  const int th = mode == 1 ? 16 : 8, ct = mode == 2 ? 2 : 1;
+  return (size_t)2 * 64 * (th + 2) * 34 + (size_t)2 * 3 * 256 * ct * 16 + (2 * 64 * ct + 8) * sizeof(float) + 48 +
+         (stats == 2 ? 4 * 64 * ct * sizeof(float) : 0);
 }
-static int hs_vrow_tiles_x(const Conv2dArgs& a) { return ceil_div(a.N * (a.OW + 1) - 1, kTileW); }
+static_assert(hs3x3_lds(0, 2) <= 80 * 1024 && hs3x3_lds(1, 2) <= 160 * 1024 && hs3x3_lds(2, 2) <= 160 * 1024, "LDS budget");
 
-template <int MODE>
-static int hs3x3_launch(Conv2dArgs a, hipStream_t s) {
-  constexpr int NT = MODE == 0 ? 256 : 512, TH = MODE == 1 ? 16 : 8, CT = MODE == 2 ? 2 : 1;
-  constexpr size_t lds = (size_t)2 * 64 * (TH + 2) * 34 + (size_t)2 * 3 * 256 * CT * 16 + (2 * 64 * CT + 8) * sizeof(float) + 48;
-  constexpr size_t lds_bs = lds + 4 * 64 * CT * sizeof(float);       // STATS == 2: + the consumer BatchNorm's constants
-  static_assert(lds_bs <= (MODE == 0 ? 80 : 160) * 1024, "LDS budget");
-  static std::atomic<uint64_t> attr{0};
-  if (DeviceOnce once{attr}; once) {
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 0>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 1>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bs));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 0, false, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 1, false, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 2, false, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bs));
-    once.commit();
-  }
-  a.tiles_x = ceil_div(a.OW, kTileW); a.tiles_y = ceil_div(a.OH, TH); a.cout_tiles = a.Cout / (kHsCout * CT);
-  const size_t grid = (size_t)a.cout_tiles * a.tiles_x * a.tiles_y * a.N;
-  ADX_REQUIRE(grid < (1u << 31), "conv2d_hs: grid too large");
-  ADX_REQUIRE((size_t)a.Cout * a.OH * a.OW * sizeof(float) < 0x7FFFFFFFu, "conv2d_hs: one image of the output exceeds the 32-bit byte offsets");
-  // Small batches (one camera frame per tick): a 512->512 layer on one 8x29 map is 8 workgroups, each walking 96 stages
-  // (83 us); with a scratch buffer the chunks are split over up to 16 workgroups per tile and a reduce launch finishes.
-  constexpr bool split_on = true;
-  const size_t out_floats = (size_t)a.N * a.Cout * a.OH * a.OW;
-  const size_t cap = a.part != nullptr ? a.part_stride : 0;      // conv2d_launch_raw parks the scratch capacity here
-  const int nchunks = a.cin_pad / kHsCC;
-  a.ksplit = 1; a.cper = nchunks; a.part_stride = 0;
-  const bool fp32_layout = !(a.x_cells || a.y_cells || a.res_cells);
-  // (a training forward may read cells, and so may a data gradient whose cells carry their scale)
-  const bool xscaled = a.x_amax != nullptr && a.x_amax_n < 0;
-  const bool vrow = (fp32_layout || ((a.stats_part != nullptr || xscaled) && !a.y_cells && !a.res_cells)) && hs_vrow_ok(a);
-  auto set_vrow = [&]() -> size_t {           // column tiles over the images side by side (one shared zero column between neighbours)
-    a.vw = a.OW + 1;
-    a.inv_vw = 1.f / (float)a.vw;
-    a.tiles_x = hs_vrow_tiles_x(a);
-    return (size_t)a.cout_tiles * a.tiles_x * a.tiles_y;
-  };
-  if (a.stats_part != nullptr && a.x_cells && (conv2d_hs3x3q_train_eligible(a) || conv2d_hs3x3q_dgrad_eligible(a))) {      // the 16x16x32 kernel where its tile rules hold
-    a.part = nullptr;
-    return conv2d_hs3x3q_launch(a, s);
-  }
-  if (a.stats_part != nullptr) {          // training forward: statistics in the epilogue (one workgroup per tile: no split)
-    const size_t sgrid = vrow ? set_vrow() : grid;
-    const int slots = vrow ? a.tiles_y * a.tiles_x : a.N * a.tiles_y * a.tiles_x;
-    ADX_REQUIRE(a.stats_p == slots, "conv2d_hs: statistics buffer laid out for %d tiles, launch has %d", a.stats_p, slots);
-    a.part = nullptr;
-    if (a.x_cells) {
-      // training forward on a cell-layout input (resnet_train.hip: the activation between a block's two convs): the staging copies
-      // cells instead of converting fp32 values, everything else -- fp32 conv output, statistics -- as below
-      // ... or a data gradient with the consumer BatchNorm's sums in its epilogue, reading a gradient that was written as cells
-      ADX_REQUIRE((a.x_amax == nullptr || xscaled) && (a.bs_raw == nullptr) == (a.x_amax == nullptr) && !a.y_cells && !a.res_cells,
-                  "conv2d_hs: a cell-layout input with statistics belongs to a training-forward launch or to a data gradient with its scale");
-      ADX_REQUIRE((size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u, "conv2d_hs: a cell-layout tensor exceeds the 32-bit byte offsets");
-      static std::atomic<uint64_t> xattr{0};
-      if (DeviceOnce once{xattr}; once) {
-        ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 1, true, false, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 1, true, false, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 2, true, false, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bs));
-        ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 2, true, false, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bs));
-        once.commit();
-      }
-      if (a.bs_raw != nullptr) {
-        if (vrow) conv2d_hs3x3_kernel<MODE, 2, true, false, true><<<dim3((unsigned)sgrid), dim3(NT), lds_bs, s>>>(a);
-        else conv2d_hs3x3_kernel<MODE, 2, true, false, false><<<dim3((unsigned)sgrid), dim3(NT), lds_bs, s>>>(a);
-      } else if (vrow) conv2d_hs3x3_kernel<MODE, 1, true, false, true><<<dim3((unsigned)sgrid), dim3(NT), lds, s>>>(a);
-      else conv2d_hs3x3_kernel<MODE, 1, true, false, false><<<dim3((unsigned)sgrid), dim3(NT), lds, s>>>(a);
-    } else if (vrow) {
-      if (a.bs_raw != nullptr) conv2d_hs3x3_kernel<MODE, 2, false, false, true><<<dim3((unsigned)sgrid), dim3(NT), lds_bs, s>>>(a);
-      else conv2d_hs3x3_kernel<MODE, 1, false, false, true><<<dim3((unsigned)sgrid), dim3(NT), lds, s>>>(a);
-    } else {
-      if (a.bs_raw != nullptr) conv2d_hs3x3_kernel<MODE, 2><<<dim3((unsigned)sgrid), dim3(NT), lds_bs, s>>>(a);
-      else conv2d_hs3x3_kernel<MODE, 1><<<dim3((unsigned)sgrid), dim3(NT), lds, s>>>(a);
-    }
-    ADX_LAUNCH_CHECK();
-    return ADX_OK;
-  }
-  if (MODE == 0 && split_on && cap > 0 && grid <= 64 && nchunks >= 8 && a.x_amax == nullptr && (a.OH * a.OW) % 4 == 0 &&
-      (reinterpret_cast<uintptr_t>(a.y) & 15) == 0 && (a.res == nullptr || (reinterpret_cast<uintptr_t>(a.res) & 15) == 0)) {
-    int S = 16;
-    while (S > 1 && (nchunks % S != 0 || (nchunks / S) % 2 != 0 || grid * S > 256 || out_floats * S > cap)) S >>= 1;
-    if (S > 1) {
-      Conv2dArgs c = a;
-      c.ksplit = S; c.cper = nchunks / S; c.part_stride = out_floats;
-      c.scale = nullptr; c.shift = nullptr; c.res = nullptr; c.relu = 0; c.status = nullptr;
-      conv2d_hs3x3_kernel<MODE><<<dim3((unsigned)(grid * S)), dim3(NT), lds, s>>>(c);
-      ADX_LAUNCH_CHECK();
-      const size_t total4 = out_floats / 4;
-      conv2d_split_reduce_kernel<<<dim3((unsigned)ceil_div((long)total4, 256L)), dim3(256), 0, s>>>(
-          a.part, out_floats, S, a.scale, a.shift, a.res, a.y, a.Cout, a.OH * a.OW / 4, total4, a.relu, a.status);
-      ADX_LAUNCH_CHECK();
-      return ADX_OK;
-    }
-  }
-  a.part = nullptr;
-  if (a.x_cells && xscaled && !a.y_cells && !a.res_cells) {
-    // a data gradient (no statistics wanted from it) on a gradient that was written as cells: fp32 output [+ fp32 residual]
-    static std::atomic<uint64_t> dattr{0};
-    if (DeviceOnce once{dattr}; once) {
-      ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 0, true, false, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 0, true, false, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      once.commit();
-    }
-    ADX_REQUIRE((size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u, "conv2d_hs: a cell-layout tensor exceeds the 32-bit byte offsets");
-    if (vrow) {
-      const size_t vgrid = set_vrow();
-      conv2d_hs3x3_kernel<MODE, 0, true, false, true><<<dim3((unsigned)vgrid), dim3(NT), lds, s>>>(a);
-    } else {
-      conv2d_hs3x3_kernel<MODE, 0, true, false, false><<<dim3((unsigned)grid), dim3(NT), lds, s>>>(a);
-    }
-    ADX_LAUNCH_CHECK();
-    return ADX_OK;
-  }
-  if (a.x_cells || a.y_cells || a.res_cells) {
-    // the executor keeps a layer's 3x3 convs in the cell layout from the first one's output to the last one's (the stride-2
-    // kernel and the average pool read cells too), so a cell operand always comes with a cell output
-    ADX_REQUIRE(a.y_cells && a.x_amax == nullptr, "conv2d_hs: cell-layout operands come with a cell-layout output (and no dynamic range)");
-    if (conv2d_hs3x3q_eligible(a)) return conv2d_hs3x3q_launch(a, s);      // the 16x16x32 kernel (conv2d_hs16.hip) where its tile rules hold
-    constexpr size_t clds = lds;
-    static std::atomic<uint64_t> cattr{0};
-    if (DeviceOnce once{cattr}; once) {
-      const void* fns[2] = {reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 0, true, true>),
-                            reinterpret_cast<const void*>(&conv2d_hs3x3_kernel<MODE, 0, false, true>)};
-      for (const void* f : fns) ADX_CHECK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));
-      once.commit();
-    }
-    // column tiles over the images side by side with one shared zero column between neighbours (conv2d_hs3x3_kernel: YCELLS):
-    // one padded MFMA column per image instead of the round-up to 32
-    a.vw = a.N > 1 ? a.OW + 1 : a.OW;
-    a.inv_vw = 1.f / (float)a.vw;
-    ADX_REQUIRE((long)a.N * a.vw < (1L << 21), "conv2d_hs: batch x width exceeds the virtual-row arithmetic");
-    a.tiles_x = ceil_div(a.N * a.vw - (a.N > 1 ? 1 : 0), kTileW);       // the last image's zero column needs no tile
-    const size_t cgrid = (size_t)a.cout_tiles * a.tiles_x * a.tiles_y;
-    ADX_REQUIRE((size_t)a.N * a.Cout * a.OH * a.OW * sizeof(float) < 0xC0000000u && (size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u,
-                "conv2d_hs: a cell-layout tensor exceeds the 32-bit byte offsets");
-    if (a.x_cells) conv2d_hs3x3_kernel<MODE, 0, true, true><<<dim3((unsigned)cgrid), dim3(NT), clds, s>>>(a);
-    else conv2d_hs3x3_kernel<MODE, 0, false, true><<<dim3((unsigned)cgrid), dim3(NT), clds, s>>>(a);
-    ADX_LAUNCH_CHECK();
-    return ADX_OK;
-  }
-  if (vrow) {
-    const size_t vgrid = set_vrow();
-    conv2d_hs3x3_kernel<MODE, 0, false, false, true><<<dim3((unsigned)vgrid), dim3(NT), lds, s>>>(a);
-  } else {
-    conv2d_hs3x3_kernel<MODE><<<dim3((unsigned)grid), dim3(NT), lds, s>>>(a);
-  }
-  ADX_LAUNCH_CHECK();
-  return ADX_OK;
-}
-
-// tile mode of the pipelined 3x3 stride-1 kernel for this launch, -1 when another kernel serves it
-static int hs3x3_mode(const ConvSpec& L, const Conv2dArgs& a) {
-  if (!(L.k == 3 && L.stride == 1 && a.w_ds == nullptr)) return -1;
-  if (!((L.cin_pad / kHsCC) % 2 == 0 && L.pad == 1)) return -1;
-  const int mode_env = debug_switches().hs_mode;       // ADX_HS_MODE=0|1|2 pins the tile mode (default: by shape)
+Hs3x3Plan conv2d_hs3x3_plan(const ConvSpec& L, const Hs3x3Query& q, const DebugSwitches& sw) {
+  Hs3x3Plan p;
+  p.admitted = q.fmt == 0;
+  if (!hs_eligible(L, sw) || !(L.k == 3 && L.stride == 1 && L.pad == 1) || (L.cin_pad / kHsCC) % 2 != 0) return p;
+  const int N = q.N, OH = q.H, OW = q.W, nchunks = L.cin_pad / kHsCC;      // (pad 1: the output has the input's size)
   // The three tiles time within 3 % of each other on every ResNet-34 shape (the MFMA rate the chip sustains on
   // random data paces all of them): short K loops take the small tile (better tail balance), long ones the
   // 8-wave tiles that move fewer operand bytes per MFMA.
-  int mode = a.Cin < 256 ? 0 : (a.OH > 8 ? 1 : (a.Cout % 128 == 0 ? 2 : 0));
+  int mode = L.cin < 256 ? 0 : (OH > 8 ? 1 : (L.cout % 128 == 0 ? 2 : 0));
   // small batches (the deployed case: one camera frame per tick): the 8-wave tiles leave most of the chip idle (512->512
   // @8x29 at B = 1: four workgroups); the 4-wave tile doubles the workgroup count
-  if ((long)a.N * ceil_div(a.OH, 8) * ceil_div(a.OW, kTileW) * (a.Cout / kHsCout) <= 256) mode = 0;
-  if (mode_env >= 0 && !(mode_env == 2 && a.Cout % 128 != 0)) mode = mode_env;
-  return mode;
+  const long grid0 = (long)N * ceil_div(OH, 8) * ceil_div(OW, kTileW) * (L.cout / kHsCout);      // mode 0's grid
+  if (grid0 <= 256) mode = 0;
+  if (sw.hs_mode >= 0 && !(sw.hs_mode == 2 && L.cout % 128 != 0)) mode = sw.hs_mode == 1 || sw.hs_mode == 2 ? sw.hs_mode : 0;   // ADX_HS_MODE pins it
+  const int th = mode == 1 ? 16 : 8, ct = mode == 2 ? 2 : 1;
+  const bool xc = (q.fmt & kFmtXCells) != 0, yc = (q.fmt & kFmtYCells) != 0, rc = (q.fmt & kFmtResCells) != 0 && q.has_res;
+  const bool xscaled = q.x_scale == kXScalePre;
+  // the cell kernels and the virtual row address whole tensors through one descriptor with 32-bit offsets (batches of ~870 frames
+  // at 256x900 and up stay on the fp32 layout with its per-image descriptors)
+  const bool in_ok = (size_t)N * L.cin * q.H * q.W * sizeof(float) < 0xC0000000u;
+  const bool bytes_ok = in_ok && (size_t)N * L.cout * OH * OW * sizeof(float) < 0xC0000000u;
+  // the virtual row: column tiles over the images side by side, one shared zero column between neighbours (the last one's needs no tile)
+  const bool vfits = (long)N * (OW + 1) < (1L << 21);
+  const int vw = N > 1 ? OW + 1 : OW;
+  const int vtiles_x = (int)(((long)N * vw - (N > 1 ? 1 : 0) + kTileW - 1) / kTileW);
+  const bool vrow_ok = sw.conv_vrow && N > 1 && vfits && bytes_ok;     // fp32-layout launches of a whole batch tile it too
+  // the 16x16x32 kernel where its tile rules hold: plain cell launches, the training forward on a cell input (TRAIN == 1), a data
+  // gradient with the consumer BatchNorm's sums on cells under their scale (TRAIN == 2)
+  const bool q_shape = sw.hs_mode < 0 && L.cout % 128 == 0 && L.cin_pad % 64 == 0;
+  const bool q_fp32out = q_shape && xc && !yc && !rc && !q.affine && vfits && bytes_ok;
+  const bool q_train = q_fp32out && sw.train_cells >= 3 && !q.has_res && q.x_scale == kXScaleNone && q.bst_mask == 0;
+  const bool q_dgrad = q_fp32out && sw.train_cells >= 5 && xscaled && !q.relu && (q.bst_mask == 2 || (q.bst_mask == 1 && q.bst_bits));
+  const bool q_plain = q_shape && xc && yc && (!q.has_res || rc) && q.x_scale == kXScaleNone;
+  // statistics: one slot per workgroup of the launch that would leave them, taken when the buffer on offer holds them
+  const int stats_tiles = q_train || q_dgrad ? ceil_div(OH, kQTH) * vtiles_x
+                                             : ceil_div(OH, th) * (!yc && !rc && vrow_ok ? vtiles_x : N * ceil_div(OW, kTileW));
+  p.stats_need = (size_t)stats_tiles * (L.cout * 2 + L.cout / 64);
+  const bool stats = q.stats_floats > 0 && p.stats_need <= q.stats_floats;
+  // cells belong to the INPUT of a training-forward launch, to the input of a data gradient written under a known power-of-two
+  // scale, or to plain launches (the inference executor: no statistics, no split reduction)
+  const bool split_shape = mode == 0 && grid0 <= 64 && nchunks >= 8;
+  if (q.fmt == kFmtXCells && q.stats_floats > 0 && q.bst_mask == 0 && q.x_scale == kXScaleNone && sw.train_cells != 0 && !L.dgrad)
+    p.admitted = in_ok && stats;
+  else if (q.fmt == (kFmtXCells | kFmtXScaled) && L.dgrad && xscaled && sw.train_cells >= 4)
+    p.admitted = in_ok;
+  else if (q.fmt != 0)
+    p.admitted = q.stats_floats == 0 && sw.conv_cells && !L.dgrad && bytes_ok && !split_shape;
+
+  p.family = kHs3x3; p.mode = mode; p.threads = mode == 0 ? 256 : 512;
+  p.tiles_x = ceil_div(OW, kTileW); p.tiles_y = ceil_div(OH, th); p.cout_tiles = L.cout / (kHsCout * ct);
+  p.vw = OW; p.cper = nchunks;
+  p.grid = (size_t)p.cout_tiles * p.tiles_x * p.tiles_y * N;
+  if (stats) { p.stats = q.bst_mask != 0 ? 2 : 1; p.stats_tiles = stats_tiles; }
+  // Small batches (one camera frame per tick): a 512->512 layer on one 8x29 map is 8 workgroups, each walking 96 stages
+  // (83 us); with a scratch buffer the chunks are split over up to 16 workgroups per tile and a reduce launch finishes.
+  if (!stats && split_shape && q.split_floats > 0 && q.x_scale == kXScaleNone && (OH * OW) % 4 == 0 && q.y_aligned && (!q.has_res || q.res_aligned)) {
+    const size_t out_floats = (size_t)N * L.cout * OH * OW;
+    int S = 16;
+    while (S > 1 && (nchunks % S != 0 || (nchunks / S) % 2 != 0 || p.grid * S > 256 || out_floats * S > q.split_floats)) S >>= 1;
+    if (S > 1) { p.ksplit = S; p.cper = nchunks / S; p.grid *= S; }
+  }
+  // a data gradient (no statistics wanted from it) on a gradient that was written as cells has an fp32 output [+ fp32 residual];
+  // any other cell operand comes with a cell output: the executor keeps a layer's 3x3 convs in the cell layout from the first
+  // one's output to the last one's (the stride-2 kernel and the average pool read cells too)
+  const bool cells_out = !stats && p.ksplit == 1 && (xc || yc || rc) && !(xc && xscaled && !yc && !rc);
+  if (stats ? q_train || q_dgrad : cells_out && q_plain) {
+    p.family = kHs3x3q; p.dma = sw.hs_dma; p.threads = kQNT;
+    p.lds = p.dma ? kQLdsD : kQLds;
+    p.vw = vw; p.tiles_x = vtiles_x; p.tiles_y = ceil_div(OH, kQTH); p.cout_tiles = L.cout / 128;
+    // workgroup = (XCD, cout tile, slot); slots per (XCD, cout tile): as many as the longest eighth of the spatial tiles (one tile
+    // per workgroup: ADX_HS_PERSIST=0 and the register-staged form), or -- the LDS-DMA form -- as many as fit one workgroup per CU,
+    // each walking its XCD's range in steps of that count (bit-identical results either way)
+    p.q_slots = ceil_div(p.tiles_x * p.tiles_y, 8);
+    if (sw.hs_dma && sw.hs_persist) p.q_slots = std::min(p.q_slots, std::max(1, q.cus / (8 * p.cout_tiles)));
+    p.grid = (size_t)8 * p.cout_tiles * p.q_slots;
+    return p;
+  }
+  p.lds = hs3x3_lds(mode, p.stats);
+  if (p.ksplit > 1) return p;
+  p.xcells = xc; p.ycells = cells_out;
+  p.vr = !cells_out && (!(xc || yc || rc) || ((stats || xscaled) && !yc && !rc)) && vrow_ok;
+  if (p.ycells || p.vr) {
+    p.vw = vw; p.tiles_x = vtiles_x;
+    p.grid = (size_t)p.cout_tiles * p.tiles_x * p.tiles_y;
+  }
+  return p;
 }
 
-bool conv2d_hs3x3_plain(const ConvSpec& L, int N, int H, int W) {
-  if (!debug_switches().conv_cells || !conv2d_hs_eligible(L) || L.dgrad) return false;   // ADX_CONV_CELLS=0: fp32 NCHW between all layers
-  Conv2dArgs a{};
-  a.N = N; a.Cin = L.cin; a.Cout = L.cout; a.H = H; a.W = W;
-  a.OH = conv_out_dim(H, L.k, L.stride, L.pad); a.OW = conv_out_dim(W, L.k, L.stride, L.pad);
-  const int mode = hs3x3_mode(L, a);
-  if (mode < 0 || L.cin % 16 != 0 || L.cout % 64 != 0) return false;
-  // the cell kernels address whole tensors through one descriptor with 32-bit offsets (batches of ~870 frames at 256x900 and up
-  // stay on the fp32 layout with its per-image descriptors)
-  if ((size_t)N * L.cin * H * W * sizeof(float) >= 0xC0000000u || (size_t)N * L.cout * a.OH * a.OW * sizeof(float) >= 0xC0000000u) return false;
-  const long grid0 = (long)a.N * ceil_div(a.OH, 8) * ceil_div(a.OW, kTileW) * (a.Cout / kHsCout);
-  return mode != 0 || grid0 > 64 || L.cin_pad / kHsCC < 8;       // hs3x3_launch<0> splits the reduction of smaller launches
+typedef void (*HsKernel)(const Conv2dArgs);
+
+// every instantiation of conv2d_hs3x3_kernel of one tile mode, at [((STATS * 2 + XCELLS) * 2 + YCELLS) * 2 + VR] (null: there is none)
+template <int MODE>
+static const HsKernel* hs3x3_kernels() {
+#define HS_K(S, X, Y, V) &conv2d_hs3x3_kernel<MODE, S, X, Y, V>
+  static const HsKernel table[3 * 8] = {
+      HS_K(0, false, false, false), HS_K(0, false, false, true), HS_K(0, false, true, false), nullptr,
+      HS_K(0, true, false, false),  HS_K(0, true, false, true),  HS_K(0, true, true, false),  nullptr,
+      HS_K(1, false, false, false), HS_K(1, false, false, true), nullptr, nullptr,
+      HS_K(1, true, false, false),  HS_K(1, true, false, true),  nullptr, nullptr,
+      HS_K(2, false, false, false), HS_K(2, false, false, true), nullptr, nullptr,
+      HS_K(2, true, false, false),  HS_K(2, true, false, true),  nullptr, nullptr};
+#undef HS_K
+  return table;
 }
 
-bool conv2d_hs3x3_dgrad_cells(const ConvSpec& L, int N, int H, int W) {
-  if (debug_switches().train_cells < 4 || !conv2d_hs_eligible(L) || !L.dgrad) return false;
-  Conv2dArgs a{};
-  a.N = N; a.Cin = L.cin; a.Cout = L.cout; a.H = H; a.W = W;
-  a.OH = conv_out_dim(H, L.k, L.stride, L.pad); a.OW = conv_out_dim(W, L.k, L.stride, L.pad);
-  return hs3x3_mode(L, a) >= 0 && L.cin % 16 == 0 && L.cin == L.cin_pad && L.cout % 64 == 0 &&
-         (size_t)N * L.cin * H * W * sizeof(float) < 0xC0000000u;
-}
-
-bool conv2d_hs3x3_dgrad_stats(const ConvSpec& L, int N, int H, int W, bool x_cells, size_t stats_floats) {
-  if (!conv2d_hs_eligible(L) || !L.dgrad) return false;
-  Conv2dArgs a{};
-  a.N = N; a.Cin = L.cin; a.Cout = L.cout; a.H = H; a.W = W;
-  a.OH = conv_out_dim(H, L.k, L.stride, L.pad); a.OW = conv_out_dim(W, L.k, L.stride, L.pad);
-  a.KH = L.k; a.KW = L.k; a.stride = L.stride; a.pad = L.pad; a.cin_pad = L.cin_pad;
-  a.x_cells = x_cells ? 1 : 0;
-  const int tiles = conv2d_hs_stats_tiles(L, a);
-  return L.k == 3 && L.stride == 1 && tiles > 0 && (size_t)tiles * (L.cout * 2 + L.cout / 64) <= stats_floats;
-}
-
-bool conv2d_hs3x3_train_cells(const ConvSpec& L, int N, int H, int W, size_t stats_floats) {
-  if (debug_switches().train_cells == 0 || !conv2d_hs_eligible(L) || L.dgrad) return false;     // ADX_TRAIN_CELLS=0: fp32 NCHW everywhere
-  Conv2dArgs a{};
-  a.N = N; a.Cin = L.cin; a.Cout = L.cout; a.H = H; a.W = W;
-  a.OH = conv_out_dim(H, L.k, L.stride, L.pad); a.OW = conv_out_dim(W, L.k, L.stride, L.pad);
-  a.x_cells = 1;
-  if (hs3x3_mode(L, a) < 0 || L.cin % 16 != 0 || L.cin != L.cin_pad || L.cout % 64 != 0) return false;
-  if ((size_t)N * L.cin * H * W * sizeof(float) >= 0xC0000000u) return false;
-  const int tiles = conv2d_hs_stats_tiles(L, a);
-  return tiles > 0 && (size_t)tiles * L.cout * 2 <= stats_floats;
-}
-
-int conv2d_hs_stats_tiles(const ConvSpec& L, const Conv2dArgs& a) {
-  const int mode = hs3x3_mode(L, a);
-  if (mode < 0) return 0;
-  if (a.x_cells && (conv2d_hs3x3q_train_eligible(a) || conv2d_hs3x3q_dgrad_eligible(a))) return conv2d_hs3x3q_train_tiles(a);
-  if (!(a.y_cells || a.res_cells) && hs_vrow_ok(a)) return ceil_div(a.OH, mode == 1 ? 16 : 8) * hs_vrow_tiles_x(a);
-  return a.N * ceil_div(a.OH, mode == 1 ? 16 : 8) * ceil_div(a.OW, kTileW);
+static int hs3x3_launch(const Hs3x3Plan& p, Conv2dArgs a, hipStream_t s) {
+  const HsKernel* const table = p.mode == 1 ? hs3x3_kernels<1>() : (p.mode == 2 ? hs3x3_kernels<2>() : hs3x3_kernels<0>());
+  static std::atomic<uint64_t> attr[3];
+  if (DeviceOnce once{attr[p.mode]}; once) {
+    for (int v = 0; v < 3 * 8; ++v)
+      if (table[v] != nullptr)
+        ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(table[v]), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)hs3x3_lds(p.mode, v / 8)));
+    once.commit();
+  }
+  ADX_REQUIRE(p.grid < (1u << 31), "conv2d_hs: grid too large");
+  ADX_REQUIRE((size_t)a.Cout * a.OH * a.OW * sizeof(float) < 0x7FFFFFFFu, "conv2d_hs: one image of the output exceeds the 32-bit byte offsets");
+  if (p.ycells) {
+    ADX_REQUIRE(a.y_cells && a.x_amax == nullptr, "conv2d_hs: cell-layout operands come with a cell-layout output (and no dynamic range)");
+    ADX_REQUIRE((long)a.N * p.vw < (1L << 21), "conv2d_hs: batch x width exceeds the virtual-row arithmetic");
+    ADX_REQUIRE((size_t)a.N * a.Cout * a.OH * a.OW * sizeof(float) < 0xC0000000u && (size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u,
+                "conv2d_hs: a cell-layout tensor exceeds the 32-bit byte offsets");
+  } else if (p.xcells) {
+    // training forward on a cell-layout input (resnet_train.hip: the activation between a block's two convs): the staging copies
+    // cells instead of converting fp32 values, everything else -- fp32 conv output, statistics -- as for an fp32 input
+    // ... or a data gradient reading a gradient that was written as cells, with or without the consumer BatchNorm's sums
+    ADX_REQUIRE(p.stats == 0 || ((a.x_amax == nullptr || a.x_amax_n < 0) && (a.bs_raw == nullptr) == (a.x_amax == nullptr) && !a.y_cells && !a.res_cells),
+                "conv2d_hs: a cell-layout input with statistics belongs to a training-forward launch or to a data gradient with its scale");
+    ADX_REQUIRE((size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u, "conv2d_hs: a cell-layout tensor exceeds the 32-bit byte offsets");
+  }
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.cout_tiles = p.cout_tiles;
+  a.vw = p.vw; a.inv_vw = 1.f / (float)p.vw;
+  a.ksplit = p.ksplit; a.cper = p.cper;
+  const HsKernel kernel = table[((p.stats * 2 + p.xcells) * 2 + p.ycells) * 2 + p.vr];
+  ADX_REQUIRE(kernel != nullptr, "conv2d_hs: no kernel variant for this plan (internal error)");
+  const dim3 grid((unsigned)p.grid), block(p.threads);
+  if (p.ksplit > 1) {       // the parts to the scratch, then a reduce launch with the epilogue
+    const size_t out_floats = (size_t)a.N * a.Cout * a.OH * a.OW, total4 = out_floats / 4;
+    Conv2dArgs c = a;
+    c.part_stride = out_floats;
+    c.scale = nullptr; c.shift = nullptr; c.res = nullptr; c.relu = 0; c.status = nullptr;
+    kernel<<<grid, block, p.lds, s>>>(c);
+    ADX_LAUNCH_CHECK();
+    conv2d_split_reduce_kernel<<<dim3((unsigned)ceil_div((long)total4, 256L)), dim3(256), 0, s>>>(
+        a.part, out_floats, p.ksplit, a.scale, a.shift, a.res, a.y, a.Cout, a.OH * a.OW / 4, total4, a.relu, a.status);
+    ADX_LAUNCH_CHECK();
+    return ADX_OK;
+  }
+  a.part = nullptr;
+  kernel<<<grid, block, p.lds, s>>>(a);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
 }
 
 // forward weight [cout][cin][3][3] -> weight [4 cin][cout][2][2] of the 2x2 conv that is the stride-2 data gradient:
@@ -1991,7 +1915,7 @@ int conv2d_hs_dgrad_s2(const float* w, const float* dy, float* dx, int accumulat
   return hs_launch_t<1, 2, 2, 2, false>(a, s);
 }
 
-int conv2d_hs_launch(const ConvSpec& L, Conv2dArgs a, hipStream_t s) {
+int conv2d_hs_launch(const ConvSpec& L, Conv2dArgs a, hipStream_t s, const Hs3x3Plan* plan) {
   ADX_REQUIRE((size_t)L.cin * a.H * a.W * sizeof(float) < 0xC0000000u, "conv2d_hs: one image of the input exceeds the 32-bit byte offsets");
   const bool ds = a.w_ds != nullptr;
   if (hs_is_stem(L) && !ds) {
@@ -1999,8 +1923,7 @@ int conv2d_hs_launch(const ConvSpec& L, Conv2dArgs a, hipStream_t s) {
     return hs_stem_launch(a, s);
   }
   if (L.k == 3 && L.stride == 1 && !ds) {
-    const int mode = hs3x3_mode(L, a);
-    if (mode >= 0) return mode == 1 ? hs3x3_launch<1>(a, s) : (mode == 2 ? hs3x3_launch<2>(a, s) : hs3x3_launch<0>(a, s));
+    if (plan != nullptr && plan->family != kHsNone) return plan->family == kHs3x3q ? conv2d_hs3x3q_launch(*plan, a, s) : hs3x3_launch(*plan, a, s);
     ADX_REQUIRE(a.stats_part == nullptr, "conv2d_hs: statistics requested from a launch the pipelined kernel does not serve");
     return hs_launch_t<1, 3, 2, 2, false>(a, s);
   }

@@ -29,23 +29,6 @@ namespace adx {
 
 namespace {
 
-constexpr int kQNT = 512;                  // threads
-constexpr int kQTH = 8;                    // output rows per workgroup
-constexpr int kQPW = 34;                   // patch columns
-constexpr int kQPlane = (kQTH + 2) * kQPW; // 340 staged pixels
-constexpr int kQPlaneP = 344;              // pitch of one [k-group][plane] image: 2 * pitch is a multiple of 16 cells, so the four
-                                           // k-groups of a fragment read start on the same bank phase (conflict-free ds_read_b128)
-constexpr int kQPairs = 4 * kQPlane;       // (k-group, pixel) cell pairs of a 32-channel chunk
-constexpr int kQPit = (kQPairs + kQNT - 1) / kQNT;   // 3 rounds
-constexpr int kQWst = 1024;                // weight cells of a stage: [slab][16-channel half][plane][k-half][64]
-constexpr size_t kQLds = (size_t)2 * 8 * kQPlaneP * 16 + (size_t)2 * kQWst * 16 + 256 * sizeof(float) + 2 * 16 + 512 * sizeof(float);
-// DMA variant (buffer_load / global_load ... lds: the staged cells go from memory to LDS without passing through registers): a wave's
-// 64 lanes write 64 CONSECUTIVE cells, so the patch image is [plane][k-group][pitch] with the cell pairs of a chunk numbered
-// linearly over (k-group, pixel); pitch 352 = 22 x 16 cells keeps the four k-groups of a fragment read on one bank phase
-constexpr int kQPlaneD = 352;
-constexpr int kQPairsD = 4 * kQPlaneD;     // 1408 = 22 waves of 64: whole waves only
-constexpr size_t kQLdsD = (size_t)2 * 8 * kQPlaneD * 16 + (size_t)2 * kQWst * 16 + 256 * sizeof(float) + 2 * 16 + 512 * sizeof(float) +
-                          (size_t)kQPit * kQNT * sizeof(uint32_t);      // + the next tile's gather offsets, parked per thread
 typedef __attribute__((address_space(3))) void lds_void;
 
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
@@ -571,88 +554,29 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   range_flag(a.status, bad);
 }
 
-// a training-forward launch (cells in, fp32 + statistics out) the TRAIN variant serves
-bool conv2d_hs3x3q_train_eligible(const Conv2dArgs& a) {
-  return debug_switches().hs_mode < 0 && debug_switches().train_cells >= 3 && a.x_cells && !a.y_cells && !a.res_cells && a.res == nullptr &&
-         a.x_amax == nullptr && a.bs_raw == nullptr && a.scale == nullptr && a.Cout % 128 == 0 && a.cin_pad % 64 == 0 && a.cin_pad == a.Cin &&
-         a.pad == 1 && a.stride == 1 && a.KH == 3 && a.KW == 3 && a.H == a.OH && a.W == a.OW && (long)a.N * (a.OW + 1) < (1L << 21) &&
-         (size_t)a.N * a.Cout * a.OH * a.OW * sizeof(float) < 0xC0000000u && (size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u;
-}
-// a data-gradient launch with the consumer BatchNorm's sums (cells in under their scale, fp32 out) the TRAIN == 2 variant serves
-bool conv2d_hs3x3q_dgrad_eligible(const Conv2dArgs& a) {
-  return debug_switches().hs_mode < 0 && debug_switches().train_cells >= 5 && a.x_cells && !a.y_cells && !a.res_cells &&
-         a.x_amax != nullptr && a.x_amax_n < 0 && a.bs_raw != nullptr && (a.bs_mask == 2 || (a.bs_mask == 1 && a.bs_bits != nullptr)) &&
-         a.scale == nullptr && a.relu == 0 && a.Cout % 128 == 0 && a.cin_pad % 64 == 0 && a.cin_pad == a.Cin &&
-         a.pad == 1 && a.stride == 1 && a.KH == 3 && a.KW == 3 && a.H == a.OH && a.W == a.OW && (long)a.N * (a.OW + 1) < (1L << 21) &&
-         (size_t)a.N * a.Cout * a.OH * a.OW * sizeof(float) < 0xC0000000u && (size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u;
-}
-int conv2d_hs3x3q_train_tiles(const Conv2dArgs& a) {
-  const int vw = a.N > 1 ? a.OW + 1 : a.OW;
-  return ceil_div(a.OH, kQTH) * ceil_div(a.N * vw - (a.N > 1 ? 1 : 0), 32);
-}
-
-bool conv2d_hs3x3q_eligible(const Conv2dArgs& a) {
-  const int pin = debug_switches().hs_mode;            // ADX_HS_MODE=0|1|2 pins a tile mode of the 32x32x16 kernel
-  return pin < 0 && a.x_cells && a.y_cells && (a.res == nullptr || a.res_cells) && a.x_amax == nullptr && a.stats_part == nullptr &&
-         a.Cout % 128 == 0 && a.cin_pad % 64 == 0 && a.cin_pad == a.Cin && a.pad == 1 && a.stride == 1 && a.KH == 3 && a.KW == 3 &&
-         a.H == a.OH && a.W == a.OW;
-}
-
-int conv2d_hs3x3q_launch(Conv2dArgs a, hipStream_t s) {
-  const bool train = a.stats_part != nullptr, dgrad = train && a.bs_raw != nullptr;
-  ADX_REQUIRE(dgrad ? conv2d_hs3x3q_dgrad_eligible(a) : (train ? conv2d_hs3x3q_train_eligible(a) : conv2d_hs3x3q_eligible(a)),
-              "conv2d_hs3x3q: launch outside the kernel's rules");
+// carries out a plan of the kHs3x3q family (conv2d_hs.hip: conv2d_hs3x3_plan)
+int conv2d_hs3x3q_launch(const Hs3x3Plan& p, Conv2dArgs a, hipStream_t s) {
+  typedef void (*QKernel)(const Conv2dArgs);
+  static const QKernel table[2][3] = {       // [DMA][TRAIN]
+      {&conv2d_hs3x3q_kernel<false, 0>, &conv2d_hs3x3q_kernel<false, 1>, &conv2d_hs3x3q_kernel<false, 2>},
+      {&conv2d_hs3x3q_kernel<true, 0>, &conv2d_hs3x3q_kernel<true, 1>, &conv2d_hs3x3q_kernel<true, 2>}};
   static std::atomic<uint64_t> attr{0};
   if (DeviceOnce once{attr}; once) {
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3q_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQLds));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3q_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQLdsD));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3q_kernel<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQLds));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3q_kernel<true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQLdsD));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3q_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQLds));
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3q_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQLdsD));
+    for (int dma = 0; dma < 2; ++dma)
+      for (const QKernel k : table[dma])
+        ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(dma ? kQLdsD : kQLds)));
     once.commit();
   }
-  a.vw = a.N > 1 ? a.OW + 1 : a.OW;
-  a.inv_vw = 1.f / (float)a.vw;
-  ADX_REQUIRE((long)a.N * a.vw < (1L << 21), "conv2d_hs: batch x width exceeds the virtual-row arithmetic");
-  a.tiles_x = ceil_div(a.N * a.vw - (a.N > 1 ? 1 : 0), 32);       // the last image's zero column needs no tile
-  a.tiles_y = ceil_div(a.OH, kQTH);
-  a.cout_tiles = a.Cout / 128;
-  const size_t tiles = (size_t)a.cout_tiles * a.tiles_x * a.tiles_y;
+  ADX_REQUIRE((long)a.N * p.vw < (1L << 21), "conv2d_hs: batch x width exceeds the virtual-row arithmetic");
+  const size_t tiles = (size_t)p.cout_tiles * p.tiles_x * p.tiles_y;
   ADX_REQUIRE(tiles < (1u << 31), "conv2d_hs: grid too large");
-  a.ntiles = (int)tiles;
-  // workgroup = (XCD, cout tile, slot); slots per (XCD, cout tile): as many as the longest eighth of the spatial tiles (one tile
-  // per workgroup: ADX_HS_PERSIST=0 and the register-staged form), or -- the LDS-DMA form -- as many as fit one workgroup per CU,
-  // each walking its XCD's range in steps of that count (bit-identical results either way)
-  const int nsp = a.tiles_x * a.tiles_y;
-  int slots = ceil_div(nsp, 8);
-  if (debug_switches().hs_dma && debug_switches().hs_persist) {
-    static std::atomic<int> n_cu{0};
-    int cus = n_cu.load(std::memory_order_relaxed);
-    if (cus == 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      ADX_CHECK_HIP(hipGetDevice(&dev));
-      ADX_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-      cus = prop.multiProcessorCount > 8 ? prop.multiProcessorCount : 8;
-      n_cu.store(cus, std::memory_order_relaxed);
-    }
-    slots = std::min(slots, std::max(1, cus / (8 * a.cout_tiles)));
-  }
-  a.q_slots = slots;
-  const size_t grid = (size_t)8 * a.cout_tiles * slots;
   ADX_REQUIRE((size_t)a.N * a.Cout * a.OH * a.OW * sizeof(float) < 0xC0000000u && (size_t)a.N * a.Cin * a.H * a.W * sizeof(float) < 0xC0000000u,
               "conv2d_hs: a cell-layout tensor exceeds the 32-bit byte offsets");
-  if (train) {
-    ADX_REQUIRE(a.stats_p == a.tiles_y * a.tiles_x, "conv2d_hs3x3q: statistics buffer laid out for %d tiles, launch has %d", a.stats_p,
-                a.tiles_y * a.tiles_x);
-    if (dgrad) {
-      if (debug_switches().hs_dma) conv2d_hs3x3q_kernel<true, 2><<<dim3((unsigned)grid), dim3(kQNT), kQLdsD, s>>>(a);
-      else conv2d_hs3x3q_kernel<false, 2><<<dim3((unsigned)grid), dim3(kQNT), kQLds, s>>>(a);
-    } else if (debug_switches().hs_dma) conv2d_hs3x3q_kernel<true, 1><<<dim3((unsigned)grid), dim3(kQNT), kQLdsD, s>>>(a);
-    else conv2d_hs3x3q_kernel<false, 1><<<dim3((unsigned)grid), dim3(kQNT), kQLds, s>>>(a);
-  } else if (debug_switches().hs_dma) conv2d_hs3x3q_kernel<true><<<dim3((unsigned)grid), dim3(kQNT), kQLdsD, s>>>(a);
-  else conv2d_hs3x3q_kernel<false><<<dim3((unsigned)grid), dim3(kQNT), kQLds, s>>>(a);
+  a.vw = p.vw; a.inv_vw = 1.f / (float)p.vw;
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.cout_tiles = p.cout_tiles; a.ntiles = (int)tiles;
+  a.q_slots = p.q_slots;
+  a.ksplit = p.ksplit; a.cper = p.cper; a.part = nullptr;
+  table[p.dma][p.stats]<<<dim3((unsigned)p.grid), dim3(p.threads), p.lds, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }

@@ -12,6 +12,26 @@ constexpr int kHsCout = 64;          // output channels per workgroup
 constexpr int kHsCC = 16;            // channels per chunk = K of one MFMA
 constexpr float kLoScale = 2048.f;   // 2^11
 
+// conv2d_hs3x3q_kernel (conv2d_hs16.hip): tile and LDS image; here because the launch plan (conv2d_hs.hip) sizes its launches
+constexpr int kQNT = 512;                  // threads
+constexpr int kQTH = 8;                    // output rows per workgroup
+constexpr int kQPW = 34;                   // patch columns
+constexpr int kQPlane = (kQTH + 2) * kQPW; // 340 staged pixels
+constexpr int kQPlaneP = 344;              // pitch of one [k-group][plane] image: 2 * pitch is a multiple of 16 cells, so the four
+                                           // k-groups of a fragment read start on the same bank phase (conflict-free ds_read_b128)
+constexpr int kQPairs = 4 * kQPlane;       // (k-group, pixel) cell pairs of a 32-channel chunk
+constexpr int kQPit = (kQPairs + kQNT - 1) / kQNT;   // 3 rounds
+constexpr int kQWst = 1024;                // weight cells of a stage: [slab][16-channel half][plane][k-half][64]
+constexpr size_t kQLds = (size_t)2 * 8 * kQPlaneP * 16 + (size_t)2 * kQWst * 16 + 256 * sizeof(float) + 2 * 16 + 512 * sizeof(float);
+// DMA variant (buffer_load / global_load ... lds: the staged cells go from memory to LDS without passing through registers): a wave's
+// 64 lanes write 64 CONSECUTIVE cells, so the patch image is [plane][k-group][pitch] with the cell pairs of a chunk numbered
+// linearly over (k-group, pixel); pitch 352 = 22 x 16 cells keeps the four k-groups of a fragment read on one bank phase
+constexpr int kQPlaneD = 352;
+constexpr int kQPairsD = 4 * kQPlaneD;     // 1408 = 22 waves of 64: whole waves only
+constexpr size_t kQLdsD = (size_t)2 * 8 * kQPlaneD * 16 + (size_t)2 * kQWst * 16 + 256 * sizeof(float) + 2 * 16 + 512 * sizeof(float) +
+                          (size_t)kQPit * kQNT * sizeof(uint32_t);      // + the next tile's gather offsets, parked per thread
+static_assert(kQLds <= 160 * 1024 && kQLdsD <= 160 * 1024, "LDS budget");
+
 #ifdef ADX_HS_M16_TIMING
 // TIMING-ONLY build (garbage results): every v_mfma_f32_32x32x16_f16 of the pipelined 3x3 kernel issued as two
 // v_mfma_f32_16x16x32_f16 on the same operand registers -- the same flops per instruction slot pair; what the smaller shape

@@ -113,30 +113,81 @@ namespace adx {
 // one conv2d launch: y = [relu](conv(x, w) [* scale + shift] [+ res]); w = packed [tap][cin_pad][cout]
 // x_amax (optional, device): x_amax_n bit patterns whose maximum is max|x| over the whole input; the split-fp16 kernels use it to move x
 // into fp16's normal range by an exact power of two (data gradients are far below 2^-14)
+// stats_part (optional, stats_floats floats): where the launch may leave per-workgroup partial sums of its output and of its
+// squares ([Cout][2][P] floats); *stats_p = P when it did (the pipelined 3x3 stride-1 kernel does), 0 when the caller has to
+// compute the statistics from the output itself
 struct BnBwdStats { const float* raw; const float* out; const float* mean; const float* rstd; const float* gamma; const float* beta; int mask;
                     const uint8_t* bits = nullptr; const uint8_t* res_bits = nullptr; };
 int conv2d_launch_raw(const ConvSpec& L, const float* x, const float* w, const float* scale, const float* shift,
                       const float* res, float* y, int N, int H, int W, int relu, hipStream_t s,
                       const uint32_t* x_amax = nullptr, int x_amax_n = 0, float* stats_part = nullptr, size_t stats_floats = 0,
                       int* stats_p = nullptr, int fmt = 0, const BnBwdStats* bst = nullptr);
+
+// ---- the plan of a 3x3 stride-1 split-fp16 launch ----
+// Which kernel serves such a launch, in which variant, on which grid and with how many statistics tiles is decided ONCE, by
+// conv2d_hs3x3_plan: a pure function (no HIP call, no state) of what is known before the launch.  conv2d_launch_raw computes
+// the plan and the launchers only carry it out; the executors ask the same function ahead of time which layouts a launch
+// will take (the predicates below), so an answer cannot differ from what the launch then does.
+enum { kHsNone = 0, kHs3x3 = 1, kHs3x3q = 2 };               // family: another kernel / conv2d_hs3x3_kernel / conv2d_hs3x3q_kernel
+enum { kXScaleNone = 0, kXScaleDynamic = 1, kXScalePre = 2 }; // x_amax: none / partial maxima of |x| / the scale x was written under
+struct Hs3x3Query {
+  int N = 0, H = 0, W = 0;
+  int fmt = 0;                    // kFmt* bits as the caller passes them
+  size_t stats_floats = 0;        // floats of the statistics buffer on offer (0: none)
+  int bst_mask = 0;               // BatchNorm-backward request (BnBwdStats::mask), 0: none
+  bool bst_bits = false;          // ... with the mask as bits
+  int x_scale = kXScaleNone;
+  bool affine = false, relu = false, has_res = false;
+  bool y_aligned = true, res_aligned = true;       // 16-byte alignment (the split reduction's vector accesses)
+  size_t split_floats = 0;        // capacity of the split-reduction scratch (0: none)
+  int cus = 0;                    // compute units of the device (sizes the persistent grid only)
+};
+struct Hs3x3Plan {
+  bool admitted = false;          // the operand formats of the query are ones the launch can take (fmt == 0 always is)
+  int family = kHsNone;
+  int mode = 0;                   // tile mode 0 / 1 / 2 of conv2d_hs3x3_kernel
+  int stats = 0;                  // STATS / TRAIN: 0 none, 1 output sums, 2 the consumer BatchNorm's backward sums
+  bool xcells = false, ycells = false, vr = false;
+  bool dma = false;               // conv2d_hs3x3q_kernel: LDS-DMA staging
+  int ksplit = 1, cper = 0;
+  int tiles_x = 0, tiles_y = 0, cout_tiles = 0, vw = 0, q_slots = 0;
+  size_t grid = 0;
+  int threads = 0;
+  size_t lds = 0;
+  int stats_tiles = 0;            // partial-sum slots per channel when stats != 0
+  size_t stats_need = 0;          // floats those take: the sums and (data gradient) max |dz| per 64-channel slab
+};
+Hs3x3Plan conv2d_hs3x3_plan(const ConvSpec& L, const Hs3x3Query& q, const DebugSwitches& sw = debug_switches());
 // true when this launch will run the pipelined 3x3 stride-1 kernel as ONE launch (no split reduction): the launches whose
 // input / output / residual may be in the cell layout (fmt: kFmt*)
-bool conv2d_hs3x3_plain(const ConvSpec& L, int N, int H, int W);
+inline bool conv2d_hs3x3_plain(const ConvSpec& L, int N, int H, int W) {
+  Hs3x3Query q;
+  q.N = N; q.H = H; q.W = W; q.fmt = kFmtXCells | kFmtYCells;
+  return conv2d_hs3x3_plan(L, q).admitted;
+}
 // true when a training-forward launch of this conv (statistics in the epilogue, fp32 output) can read its input as a cell tensor
-// (fmt = kFmtXCells together with stats_part): the pipelined 3x3 stride-1 kernel with room for its partial sums in stats_floats
-bool conv2d_hs3x3_train_cells(const ConvSpec& L, int N, int H, int W, size_t stats_floats);
+// (fmt = kFmtXCells together with stats_part): a 3x3 stride-1 split-fp16 launch with room for its partial sums in stats_floats
+inline bool conv2d_hs3x3_train_cells(const ConvSpec& L, int N, int H, int W, size_t stats_floats) {
+  Hs3x3Query q;
+  q.N = N; q.H = H; q.W = W; q.fmt = kFmtXCells; q.stats_floats = stats_floats;
+  return stats_floats > 0 && conv2d_hs3x3_plan(L, q).admitted;
+}
 // true when a data-gradient launch of this (dgrad) spec can read a cell-layout, pre-scaled gradient (fmt = kFmtXCells | kFmtXScaled)
-bool conv2d_hs3x3_dgrad_cells(const ConvSpec& L, int N, int H, int W);
-// true when a data-gradient launch of this spec with a BnBwdStats request will run the pipelined 3x3 kernel's statistics epilogue
-// (the launches that can take BnBwdStats::res_bits)
-bool conv2d_hs3x3_dgrad_stats(const ConvSpec& L, int N, int H, int W, bool x_cells, size_t stats_floats);
-// conv2d_hs16.hip: the 16x16x32 kernel's training-forward variant (cells in, fp32 + statistics out) and its tile count
-bool conv2d_hs3x3q_train_eligible(const Conv2dArgs& a);
-bool conv2d_hs3x3q_dgrad_eligible(const Conv2dArgs& a);
-int conv2d_hs3x3q_train_tiles(const Conv2dArgs& a);
-// stats_part (optional, stats_floats floats): where the launch may leave per-workgroup partial sums of its output and of its
-// squares ([Cout][2][P] floats); *stats_p = P when it did (the pipelined 3x3 stride-1 kernel does), 0 when the caller has to
-// compute the statistics from the output itself
+inline bool conv2d_hs3x3_dgrad_cells(const ConvSpec& L, int N, int H, int W) {
+  Hs3x3Query q;
+  q.N = N; q.H = H; q.W = W; q.fmt = kFmtXCells | kFmtXScaled; q.x_scale = kXScalePre;
+  return L.dgrad && conv2d_hs3x3_plan(L, q).admitted;
+}
+// true when a data-gradient launch of this spec (dx accumulated in place) with a BnBwdStats request of this mask form will run
+// the statistics epilogue (the launches that can take BnBwdStats::res_bits)
+inline bool conv2d_hs3x3_dgrad_stats(const ConvSpec& L, int N, int H, int W, bool x_cells, int bst_mask, bool bst_bits, size_t stats_floats) {
+  Hs3x3Query q;
+  q.N = N; q.H = H; q.W = W; q.stats_floats = stats_floats; q.bst_mask = bst_mask; q.bst_bits = bst_bits; q.has_res = true;
+  q.fmt = x_cells ? kFmtXCells | kFmtXScaled : 0;
+  q.x_scale = x_cells ? kXScalePre : kXScaleDynamic;
+  const Hs3x3Plan p = conv2d_hs3x3_plan(L, q);
+  return L.dgrad && p.admitted && p.stats == 2;
+}
 // [Cout][Cin][k][k] -> [tap][cin_pad][Cout]; dgrad = 1 packs the data-gradient view instead:
 // [tap'][cout_pad as K][Cin as N] with the taps flipped (conv of dy with this image gives dx)
 int conv2d_pack_raw(const float* w, float* packed, int cout, int cin, int k, int cin_pad, int dgrad, hipStream_t s);
@@ -154,14 +205,11 @@ int conv2d_hs_pack(const ConvSpec& consumer, const float* w, void* packed, int d
 struct HsPackJob { const float* w; void* packed; int cout, cin_pad, cin, taps, dgrad; };
 bool conv2d_hs_pack_batchable(const ConvSpec& consumer, int dgrad);
 int conv2d_hs_pack_many(const HsPackJob* jobs, int n, hipStream_t s);
-int conv2d_hs_launch(const ConvSpec& L, Conv2dArgs a, hipStream_t s);
-// conv2d_hs16.hip: the same convolution on v_mfma_f32_16x16x32_f16 for the inference executor's plain cell-layout launches with
-// Cout % 128 == 0 and Cin % 64 == 0 (same packed weights, same cell tensors; ADX_HS_MODE=0|1|2 keeps every launch on the 32x32x16 kernel)
-bool conv2d_hs3x3q_eligible(const Conv2dArgs& a);
-int conv2d_hs3x3q_launch(Conv2dArgs a, hipStream_t s);
-// partial-sum slots (workgroups per 64-channel slab) the pipelined 3x3 stride-1 kernel would fill for this launch, 0 if another
-// kernel serves it
-int conv2d_hs_stats_tiles(const ConvSpec& L, const Conv2dArgs& a);
+// plan: of a 3x3 stride-1 launch (conv2d_launch_raw), null for every other
+int conv2d_hs_launch(const ConvSpec& L, Conv2dArgs a, hipStream_t s, const Hs3x3Plan* plan = nullptr);
+// conv2d_hs16.hip: the same convolution on v_mfma_f32_16x16x32_f16 where the plan picks it (same packed weights, same cell tensors;
+// ADX_HS_MODE=0|1|2 keeps every launch on the 32x32x16 kernel)
+int conv2d_hs3x3q_launch(const Hs3x3Plan& p, Conv2dArgs a, hipStream_t s);
 // Data gradient of a 3x3 stride-2 pad-1 conv (forward weight w [cout][cin][3][3], forward input h x w, output oh x ow):
 // dx [n][cin][h][w] (+= when accumulate) from dy [n][cout][oh][ow].  An input pixel of parity class (py, px) receives from
 // 1 / 2 / 2 / 4 of the nine taps, and all of them lie in the 2x2 window [oy, oy+1] x [ox, ox+1] of dy with oy = iy >> 1,

@@ -1847,7 +1847,8 @@ int adx_resnet_backward_ex(adx_resnet* r, const float* const* T, float* const* G
     const bool masked_res = need_in && !ds && prev != nullptr && prev->relu && c2.bits != nullptr && tape->stats_part != nullptr &&
                             dgrad_img[c1.L - r->convs.data()] != nullptr &&
                             conv2d_hs3x3_dgrad_stats(dgrad_spec(*c1.L), batch, c1.OH, c1.OW,
-                                                     draw_cells_of(c1, true) && (reinterpret_cast<uintptr_t>(draw) & 15) == 0, kStatsPartFloats);
+                                                     draw_cells_of(c1, true) && (reinterpret_cast<uintptr_t>(draw) & 15) == 0,
+                                                     prev->identity != nullptr ? 1 : 2, prev->bits != nullptr, kStatsPartFloats);
     // dz2 (the masked d(block out)) feeds the identity path: the downsample's backward, or d(block in) directly
     const bool keep_dz2 = !masked_res && (ds ? ds_run : need_in);
     rc = conv_bn_bwd(c2, g_cur, keep_dz2 ? dz2 : nullptr, draw, do1, false, c1_run, &c1);   // -> do1 = d(o1) (c1's incoming gradient), dz2 = masked dout

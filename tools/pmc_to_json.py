@@ -48,7 +48,7 @@ def main():
     grids = {}
     for (cin, cout, k, s, p, h, w), cnt in shapes.items():
         cols = (bench.B * (w + 1) - 1 + 31) // 32          # column tiles over the images side by side, one shared zero column between neighbours
-        if cout % 128 == 0 and cin % 64 == 0:              # conv2d_hs3x3q_eligible: the 16x16x32 kernel, 8 rows x 32 columns x 128 channels, 512 threads
+        if cout % 128 == 0 and cin % 64 == 0:              # conv2d_hs3x3_plan's rule for the 16x16x32 kernel: 8 rows x 32 columns x 128 channels, 512 threads
             wgs, nt, label = ((h + 7) // 8) * cols * (cout // 128), 512, "16x16x32 kernel"
         else:
             mode = 0 if cin < 256 else (1 if h > 8 else 2)       # conv2d_hs_launch's tile-mode rule
