@@ -166,7 +166,13 @@ _SIGS = {
     "adx_add_noise": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
 }
 
-EXPORTED_SYMBOLS = tuple(_SIGS)
+# resolved on first use (lazy()), not at load: ADX_LIB may point at a library built before these entry points existed (A/B runs)
+_LAZY_SIGS = {
+    "adx_conv2d_pack_ds": (i32, [i32, i32, vp, vp, vp]),
+    "adx_conv2d_block_s2_cells": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+}
+
+EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)
 
 _lib: Optional[C.CDLL] = None
 
@@ -200,6 +206,19 @@ def lib() -> C.CDLL:
             fn.argtypes = args
         _lib = handle
     return _lib
+
+
+def lazy(name: str):
+    """An entry point of _LAZY_SIGS; raises AdxError when the loaded library does not export it."""
+    handle = lib()
+    res, args = _LAZY_SIGS[name]
+    try:
+        fn = getattr(handle, name)
+    except AttributeError:
+        raise AdxError(f"{LIB_PATH} does not export {name} (a library built from older sources?)") from None
+    fn.restype = res
+    fn.argtypes = args
+    return fn
 
 
 class NativeTape:

@@ -403,7 +403,7 @@ static thread_local float* t_split_scratch = nullptr;
 static thread_local size_t t_split_floats = 0;
 void conv2d_set_split_scratch(float* p, size_t floats) { t_split_scratch = p; t_split_floats = p != nullptr ? floats : 0; }
 // compute units of the calling thread's current device, asked once per device (devices folded modulo 64, like DeviceOnce)
-static int device_cus(int* cus) {
+int device_cus(int* cus) {
   static std::atomic<int> known[64];
   int dev = 0;
   ADX_CHECK_HIP(hipGetDevice(&dev));
@@ -575,6 +575,39 @@ int adx_conv2d_forward_cells(const adx_conv2d_desc* d, const void* x, const floa
               "(adx_conv2d_cells_supported)");
   return conv2d_launch_raw(L, (const float*)x, packed_w, scale, shift, (const float*)res, (float*)y, n, h, w, relu,
                            (hipStream_t)stream, nullptr, 0, nullptr, 0, nullptr, fmt);
+}
+
+static int block_s2_specs(int32_t cin, int32_t cout, ConvSpec* c1, ConvSpec* ds, const char* who) {
+  const adx_conv2d_desc d1{cin, cout, 3, 2, 1}, dd{cin, cout, 1, 2, 0};
+  int rc = spec_from_desc(&d1, c1);
+  if (rc == ADX_OK) rc = spec_from_desc(&dd, ds);
+  if (rc != ADX_OK) return rc;
+  ADX_REQUIRE(resnet_fuses_ds(*c1, *ds), "%s: %d -> %d is no block entry the split-fp16 kernels fuse (cin %% 16, cout %% 64, not ADX_CONV_EXACT=1)",
+              who, cin, cout);
+  return ADX_OK;
+}
+
+int adx_conv2d_pack_ds(int32_t cin, int32_t cout, const float* w, float* packed, adx_stream stream) {
+  ConvSpec c1, ds;
+  const int rc = block_s2_specs(cin, cout, &c1, &ds, "adx_conv2d_pack_ds");
+  if (rc != ADX_OK) return rc;
+  ADX_REQUIRE(w && packed, "adx_conv2d_pack_ds: null pointer");
+  return conv2d_hs_pack(ds, w, packed, 0, (hipStream_t)stream);
+}
+
+int adx_conv2d_block_s2_cells(int32_t cin, int32_t cout, const void* x, const float* packed_w1, const float* scale1, const float* shift1,
+                              void* y1, const float* packed_wd, const float* scaled, const float* shiftd, void* yd, int32_t n, int32_t h,
+                              int32_t w, int32_t flags, adx_stream stream) {
+  ConvSpec c1, ds;
+  const int rc = block_s2_specs(cin, cout, &c1, &ds, "adx_conv2d_block_s2_cells");
+  if (rc != ADX_OK) return rc;
+  ADX_REQUIRE(x && packed_w1 && y1 && packed_wd && yd, "adx_conv2d_block_s2_cells: null tensor");
+  ADX_REQUIRE((scale1 == nullptr) == (shift1 == nullptr) && (scaled == nullptr) == (shiftd == nullptr),
+              "adx_conv2d_block_s2_cells: scale and shift go together");
+  ADX_REQUIRE(n >= 1 && h >= 1 && w >= 1 && flags >= 0 && flags <= 1, "adx_conv2d_block_s2_cells: bad shape %d x %d x %d or flags %d", n, h, w, flags);
+  ADX_REQUIRE((size_t)n * cin * h * w * sizeof(float) < 0xC0000000u, "adx_conv2d_block_s2_cells: the input exceeds the 32-bit byte offsets");
+  return conv2d_hs_launch_block_s2(c1, ds, (const float*)x, packed_w1, scale1, shift1, (float*)y1, packed_wd, scaled, shiftd, (float*)yd, n, h, w,
+                                   (hipStream_t)stream, 1, 1, 1, (flags & 1) != 0);
 }
 
 int adx_conv2d_stem_pool(const void* x, int32_t x_u8, const float* packed_w, const float* scale, const float* shift,

@@ -1660,7 +1660,7 @@ int conv2d_hs_stem_pool(const ConvSpec& L, const float* x, const float* w, const
 
 int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const float* x, const float* w1, const float* scale1,
                               const float* shift1, float* y1, const float* wd, const float* scaled, const float* shiftd,
-                              float* yd, int N, int H, int W, hipStream_t s, int x_cells, int y_cells, int relu) {
+                              float* yd, int N, int H, int W, hipStream_t s, int x_cells, int y_cells, int relu, bool force_32) {
   ADX_REQUIRE(x && w1 && y1 && wd && yd && (scale1 != nullptr) == (shift1 != nullptr) && (scaled != nullptr) == (shiftd != nullptr),
               "conv2d_hs block launch: null pointer");
   Conv2dArgs a{};
@@ -1673,7 +1673,39 @@ int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const floa
   a.x_cells = x_cells;
   a.y_cells = y_cells;
   a.status = conv2d_status();
+  HsS2Query q;
+  q.N = N; q.H = H; q.W = W; q.x_cells = x_cells != 0; q.y_cells = y_cells != 0;
+  if (q.x_cells && q.y_cells && !force_32) {      // (the persistent grid of the 16x16x32 kernel)
+    const int rc = device_cus(&q.cus);
+    if (rc != ADX_OK) return rc;
+    const HsS2Plan plan = conv2d_hs_s2_plan(c1, ds, q);
+    if (plan.q) return conv2d_hs3x3q_s2_launch(plan, a, s);
+  }
   return conv2d_hs_launch(c1, a, s);
+}
+
+HsS2Plan conv2d_hs_s2_plan(const ConvSpec& c1, const ConvSpec& ds, const HsS2Query& q, const DebugSwitches& sw) {
+  HsS2Plan p;
+  const bool shape = hs_eligible(c1, sw) && c1.k == 3 && c1.stride == 2 && c1.pad == 1 && ds.k == 1 && ds.stride == 2 && ds.pad == 0 &&
+                     ds.cin == c1.cin && ds.cout == c1.cout && c1.cin_pad % 64 == 0 && c1.cout % 128 == 0;
+  if (!shape || !q.x_cells || !q.y_cells || !sw.hs_s2q || !sw.hs_dma || sw.hs_mode >= 0 || q.N < 1 || q.H < 1 || q.W < 1) return p;
+  const int N = q.N, OH = conv_out_dim(q.H, 3, 2, 1), OW = conv_out_dim(q.W, 3, 2, 1);
+  // one descriptor with 32-bit offsets per tensor, and the virtual row's division (conv2d_hs3x3_plan)
+  if ((size_t)N * c1.cin * q.H * q.W * sizeof(float) >= 0xC0000000u || (size_t)N * c1.cout * OH * OW * sizeof(float) >= 0xC0000000u ||
+      (long)N * (OW + 1) >= (1L << 21))
+    return p;
+  p.q = true;
+  p.vw = N > 1 ? OW + 1 : OW;
+  p.tiles_x = (int)(((long)N * p.vw - (N > 1 ? 1 : 0) + kTileW - 1) / kTileW);
+  p.tiles_y = ceil_div(OH, kQTH);
+  p.cout_tiles = c1.cout / 128;
+  // workgroup = (XCD, cout tile, slot), as for the stride-1 launches of the kernel: one workgroup per CU where the tiles allow
+  p.q_slots = ceil_div(p.tiles_x * p.tiles_y, 8);
+  if (sw.hs_persist) p.q_slots = std::min(p.q_slots, std::max(1, q.cus / (8 * p.cout_tiles)));
+  p.grid = (size_t)8 * p.cout_tiles * p.q_slots;
+  p.threads = kQNT;
+  p.lds = kQLdsS2;
+  return p;
 }
 
 // second half of a split 3x3 conv: y = [relu](sum_p part[p] * scale[c] + shift[c] [+ res]), four elements per thread

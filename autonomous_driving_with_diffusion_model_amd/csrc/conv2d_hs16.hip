@@ -21,6 +21,7 @@
 // the batch size that picks the kernel): a stage's 1024 cells are four contiguous 4 KB runs of it.
 // Scope: the inference executor's plain cell-layout launches (x, y and the residual as cell tensors, virtual-row column tiles)
 // with Cout % 128 == 0 and Cin % 64 == 0 -- 23 of the 29 stride-1 convs of ResNet-34; everything else stays on conv2d_hs3x3_kernel.
+// The same tile walk also serves the three stride-2 block entries (conv1 + downsample on cells: TRAIN == 3 below).
 #include "adx_common.h"
 #include "conv2d_internal.h"
 #include "conv2d_hs_common.h"
@@ -50,8 +51,18 @@ __device__ __forceinline__ void half4(uint32_t h0, uint32_t h1, uint32_t l0, uin
 // TRAIN == 2: a data gradient of the training backward on a cell-layout, pre-scaled gradient (x_amax_n < 0): dx = conv + residual
 // (fp32 NCHW, the residual optionally through mask bits) and, like conv2d_hs3x3_kernel's STATS == 2, the consumer BatchNorm's
 // backward sums (sum dz, sum dz xhat per channel) and max |dz| per workgroup.
+// TRAIN == 3 (S2) is no training launch: the block entry of a ResNet layer in the inference executor -- conv1 (3x3 stride 2 pad 1,
+// BN, ReLU) and the downsample (1x1 stride 2, BN) of one cell tensor, both outputs cells -- on the SAME tile, LDS images, fragment
+// reads and epilogue.  The input splits into four parity planes P[pr][pc][q][p] = x[2 q + pr][2 p + pc]; tap (kh, kw) reads plane
+// (kh != 1, kw != 1) at the stride-1 offset (kh > 0, kw > 0) - 1 of the OUTPUT geometry, so a 32-channel chunk is nine ordinary
+// stages over four patches (2 + 1 + 2 + 4 taps) that differ from a stride-1 patch only in the gather offsets of their cells: the
+// planes never exist in memory.  The downsample is the centre tap of plane (0, 0) under its own weights: a second loop of
+// Cin / 32 stages of the same tile visit, after conv1's epilogue, into the same accumulators.  a.H x a.W is the input there,
+// a.OH x a.OW the tiled geometry of both outputs.
 template <bool DMA, int TRAIN = 0>
 __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs a) {
+  constexpr bool S2 = TRAIN == 3;
+  static_assert(!S2 || DMA, "the stride-2 block entry stages with LDS-DMA only");
   constexpr int NT = kQNT, PW = kQPW, PLANE = DMA ? kQPlaneD : kQPlane, PP = DMA ? kQPlaneD : kQPlaneP, PIT = kQPit, WST = kQWst;
   constexpr int NPAIRS = DMA ? kQPairsD : kQPairs;
   // cell strides of the patch image: [k-group][plane][PP], or (DMA) [plane][k-group][PP]
@@ -63,6 +74,7 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   u32x4* dummy = reinterpret_cast<u32x4*>(ss + 256);          // where the idle threads of the last patch round write
   float* bsl = reinterpret_cast<float*>(dummy + 2);           // TRAIN == 2: [mean | rstd | mask scale | mask shift] x 128
   uint32_t* gnext = reinterpret_cast<uint32_t*>(bsl + 512);   // DMA: [round][thread] gather offsets of this workgroup's NEXT tile
+  uint32_t* gpl = gnext + PIT * NT;                           // S2: [plane][round][thread] gather offsets of the CURRENT tile's four parity planes
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rowpair = wave & 3, slab = wave >> 2;
@@ -102,13 +114,32 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
     const bool ok = e < NPAIRS && p < kQPlane && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W && ni < a.N;
     return !ok ? kOutside : (uint32_t)((size_t)ni * a.Cin * hw * sizeof(float) + (size_t)g * 8 * hw * sizeof(float) + ((size_t)iy * a.W + ix) * 16);
   };
+  // S2: the same for parity plane (pr, pc) of the input: staged pixel (py, px) is cell (q, pcl) of the plane, i.e. input pixel
+  // (2 q + pr, 2 pcl + pc).  A row 2 q + 1 == H or a column 2 pcl + 1 == W (the far edge of an odd-sized map) is padding, like
+  // row / column -1; the patch row and column no tap of the plane reads (the bottom row and the right column of every plane: the
+  // offsets are -1 and 0 only; the top row of the planes pr == 0, the left column of the planes pc == 0) cost no traffic
+  auto goff_s2 = [&](int t_, int k, int oy0_, int vx0_, int pr, int pc) -> uint32_t {
+    const int e = t_ + NT * k;
+    const int g = e / PLANE, p = e - g * PLANE;
+    const int py = p / PW, px = p - py * PW;
+    const int q = oy0_ - 1 + py;
+    const int v = vx0_ - 1 + px;
+    const int ni = vdiv(v < 0 ? 0 : v);
+    const int pcl = v - ni * a.vw;
+    const int iy = 2 * q + pr, ix = 2 * pcl + pc;
+    const bool ok = e < NPAIRS && py + pr > 0 && py <= kQTH && px + pc > 0 && px < PW - 1 && q >= 0 && iy < a.H && pcl >= 0 && pcl < a.OW &&
+                    ix < a.W && ni < a.N;
+    return !ok ? kOutside : (uint32_t)((size_t)ni * a.Cin * hw * sizeof(float) + (size_t)g * 8 * hw * sizeof(float) + ((size_t)iy * a.W + ix) * 16);
+  };
+  constexpr int kTap[9] = {1, 7, 4, 3, 5, 0, 2, 6, 8};     // S2: the taps in stage order (planes (1,0) (0,0) (0,1) (1,1), below)
   uint32_t goff[PIT];
   int pcell[PIT];
 #pragma unroll
   for (int k = 0; k < PIT; ++k) {
     const int e = tid + NT * k;
     const int g = e / PLANE, p = e - g * PLANE;
-    goff[k] = goff_of(tid, k, oy0, vx0);
+    if constexpr (S2) goff[k] = goff_s2(tid, k, oy0, vx0, 1, 0);       // (the prologue's patch: plane (1, 0) of chunk 0)
+    else goff[k] = goff_of(tid, k, oy0, vx0);
     pcell[k] = e < NPAIRS ? g * GST + p : -1;
   }
   // this thread's two weight cells of a stage: cell e of the LDS image is cell wsrc_off[k] + (18 chunk + tap) * 256 of the packed image
@@ -139,6 +170,26 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
       if constexpr (DMA) __builtin_amdgcn_global_load_lds(ws + wsrc_off[k], (lds_void*)(wl + set * WST + wcell + NT * k), 16, 0, 0);
       else wv[set][k] = ws[wsrc_off[k]];
     }
+  };
+  // S2: tap `tap` of 32-channel chunk `chunk` of conv1's image; chunk `chunk` of the downsample's image [cout/64][cin/16][256].
+  // Through buffer descriptors: thread t's cell of round k lies t cells past a wave-uniform start (waves 4-7 stage the second
+  // 16-channel half: 8 taps further in conv1's image), so ONE 32-bit offset per thread serves every stage of both images where
+  // global_load_lds keeps two 64-bit addresses alive
+  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(a.w), 0, (int)((size_t)a.Cout * a.cin_pad * 9 * sizeof(float)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wdrsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(S2 ? a.w_ds : a.w), 0, S2 ? (int)((size_t)a.Cout * a.cin_pad * sizeof(float)) : 0, 0x00020000);
+  auto load_w_tap = [&](int chunk, int tap, int set) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (lds_void*)(wl + set * WST + wcell + NT * k), 16, (uint32_t)(tid * 16),
+                                               (uint32_t)(((ct * 2 + k) * nch16 * 9 + chunk * 18 + tap + (wave >> 2) * 8) * 256 * 16), 0, 0);
+  };
+  auto load_w_ds = [&](int chunk, int set) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wdrsrc, (lds_void*)(wl + set * WST + wcell + NT * k), 16, (uint32_t)(tid * 16),
+                                               (uint32_t)(((ct * 2 + k) * nch16 + chunk * 2) * 256 * 16), 0, 0);
   };
   auto store_w = [&](int set, int buf) {
     if constexpr (!DMA) {
@@ -174,7 +225,8 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   // A (channels) of lane (j, kq): weight cell slab * 512 + (kq >> 1) * 256 + plane * 128 + (kq & 1) * 64 + 16 cb + j
 
   // prologue (a workgroup's FIRST tile only): stage 0 complete in LDS, the weights of stage 1 in flight
-  load_w(0, 0);
+  if constexpr (S2) load_w_tap(0, kTap[0], 0);
+  else load_w(0, 0);
   store_w(0, 0);
 #pragma unroll
   for (int k = 0; k < PIT; ++k) { load_p(0, k, 0); store_p(0, k, 0); }
@@ -185,6 +237,12 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
     const float mu = a.bs_mean[c], rs = a.bs_rstd[c];
     const float sc = a.bs_gamma[c] * rs;          // the mask's affine form exactly as the forward pass applied it (resnet_train.hip: bn_affine)
     bsl[tid] = which == 0 ? mu : (which == 1 ? rs : (which == 2 ? sc : __builtin_fmaf(-mu, sc, a.bs_beta[c])));
+  }
+  if constexpr (S2) {      // the downsample's constants, where TRAIN == 2 keeps the consumer BatchNorm's
+    if (tid < 256) {
+      const int c = ct * 128 + (tid & 127);
+      bsl[tid] = a.scale_ds == nullptr ? (tid < 128 ? 1.f : 0.f) : (tid < 128 ? a.scale_ds[c] : a.shift_ds[c]);
+    }
   }
   if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -198,8 +256,10 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   asm volatile("" : "+s"(zero_));
   const int tl = tid + zero_;
   if constexpr (DMA) {
+    if constexpr (!S2) {
 #pragma unroll
-    for (int k = 0; k < PIT; ++k) goff[k] = goff_of(tl, k, oy0, vx0);
+      for (int k = 0; k < PIT; ++k) goff[k] = goff_of(tl, k, oy0, vx0);
+    }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int e = tl + NT * k;
@@ -217,7 +277,19 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   const int n_oy0 = nty * kQTH, n_vx0 = ntx * 32;
   // the next tile's gather offsets: parked in LDS (a thread's own words) until the last chunk asks for them -- in registers they
   // pushed the stage loop over its budget, computed where they are used they kept a dozen scalars of the address arithmetic alive
-  if constexpr (DMA) {
+  if constexpr (S2) {
+    // the four planes' offsets of THIS tile go the same way: they differ by a wave-uniform constant except at the far edge of an
+    // odd-sized map, and a mask per plane would have to live in registers through the stage loop
+#pragma unroll
+    for (int k = 0; k < PIT; ++k) {
+      const uint32_t g10 = goff_s2(tl, k, oy0, vx0, 1, 0);
+      gpl[(0 * PIT + k) * NT + tid] = goff_s2(tl, k, oy0, vx0, 1, 1);
+      gpl[(1 * PIT + k) * NT + tid] = g10;
+      gpl[(2 * PIT + k) * NT + tid] = goff_s2(tl, k, oy0, vx0, 0, 1);
+      gpl[(3 * PIT + k) * NT + tid] = goff_s2(tl, k, oy0, vx0, 0, 0);
+      gnext[k * NT + tid] = has_next ? goff_s2(tl, k, n_oy0, n_vx0, 1, 0) : g10;       // (a tile's first patch: plane (1, 0))
+    }
+  } else if constexpr (DMA) {
 #pragma unroll
     for (int k = 0; k < PIT; ++k) gnext[k * NT + tid] = has_next ? goff_of(tl, k, n_oy0, n_vx0) : goff[k];
   }
@@ -228,9 +300,58 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
 #pragma unroll
       for (int i = 0; i < 4; ++i) { accm[cb][pb][i] = 0.f; accl[cb][pb][i] = 0.f; }
 
+  // S2: one stage once its transfers are issued -- the stride-1 stage below without the register-staged form's stores
+  auto s2_stage = [&](const u32x4* pb0, const u32x4* wa0) {
+    __builtin_amdgcn_sched_barrier(0);
+    f16x8 A[2][4], B[2][4];
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) A[pl][cb] = __builtin_bit_cast(f16x8, wa0[pl * 128 + cb * 16]);
+#pragma unroll
+      for (int pb = 0; pb < 4; ++pb) B[pl][pb] = __builtin_bit_cast(f16x8, pb0[pl * PLST + (pb >> 1) * PW + (pb & 1) * 16]);
+    }
+#pragma unroll
+    for (int pb = 0; pb < 4; ++pb) {
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        accm[cb][pb] = mfma16(A[0][cb], B[0][pb], accm[cb][pb]);
+        accl[cb][pb] = mfma16(A[0][cb], B[1][pb], accl[cb][pb]);
+      }
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) accl[cb][pb] = mfma16(A[1][cb], B[0][pb], accl[cb][pb]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this stage's transfers have landed
+    __syncthreads();
+  };
   // (The compiler places each stage's barrier in the MIDDLE of the stage's MFMAs -- legal: the fragments are in registers -- so a
   // wave reads the next stage's fragments while its SIMD partner still multiplies.  Pinning the barrier to the stage's end, or
   // staggering waves 4-7 by half a stage against waves 0-3, measured 1-3 % slower: profiles/README.md, round 5.)
+  if constexpr (S2) {
+    // conv1: per 32-channel chunk the planes (1,0) (0,0) (0,1) (1,1) in patch buffers 0 1 0 1, their taps in kTap's order; while a
+    // plane's stages multiply, the next plane's patch arrives in the other buffer -- three rounds over 2, 1, 2 and 4 stages.  The
+    // order puts the fetches that MISS the L2 under the long windows: planes of one row parity share their cache lines, so the
+    // second of a pair hits -- (0,0) [first of the even rows] arrives under (1,0)'s two stages, (0,1) [hit] under (0,0)'s one,
+    // (1,1) [hit] under (0,1)'s two, and the next chunk's (1,0) [new channels: miss] under (1,1)'s four
+    constexpr int kBuf[9] = {0, 0, 1, 0, 0, 1, 1, 1, 1};
+    constexpr int kPlaneNext[9] = {3, 3, 2, 0, 0, 1, 1, 1, 1};                                          // whose patch a stage's rounds belong to
+    constexpr int kRound0[9] = {0, 2, 0, 0, 2, 0, 1, 2, 3}, kRounds[9] = {2, 1, 3, 2, 1, 1, 1, 1, 0};   // patch rounds a stage issues
+    for (int cp = 0; cp < nch32; cp += 2) {
+#pragma unroll
+      for (int i = 0; i < 18; ++i) {
+        const int cpar = i / 9, t = i % 9, c = cp + cpar, kh = kTap[t] / 3, kw = kTap[t] % 3;
+        const bool last = cpar == 1 && c + 1 >= nch32;        // conv1's last chunk: the downsample's first stage comes next
+        if (t < 8) load_w_tap(c, kTap[t + 1], (i + 1) & 1);
+        else if (!last) load_w_tap(c + 1, kTap[0], (i + 1) & 1);
+        else load_w_ds(0, 0);
+        const int nplane = t >= 5 && last ? 3 : kPlaneNext[t];
+        const int nchunk = t < 5 ? c : (last ? 0 : c + 1);
+#pragma unroll
+        for (int k = kRound0[t]; k < kRound0[t] + kRounds[t]; ++k) load_p_at(nchunk, k, kBuf[t] ^ 1, gpl[(nplane * PIT + k) * NT + tid]);
+        s2_stage(patch + kBuf[t] * 8 * PP + pb_lane + (kh > 0) * PW + (kw > 0), wl + (i & 1) * WST + wa_lane);
+      }
+    }
+  } else
   for (int cp = 0; cp < nch32; cp += 2) {
 #pragma unroll
     for (int i = 0; i < 18; ++i) {
@@ -471,18 +592,52 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
         }
     }
   } else {
+  // (S2: twice per tile -- conv1 into y, then, after its stages, the downsample under its own constants, without ReLU, into y_ds)
+  int pass = 0;        // (a do-while whose condition is constant false without S2: the stride-1 instantiations keep their code)
+  do {
+  if constexpr (S2) {
+    if (pass == 1) {
+      // the downsample: chunk d's plane (0, 0) in patch buffer d & 1 (the first arrived under conv1's last stage), centre tap; its
+      // last stage fetches what a tile's last stage fetches: the next tile's first patch and first tap
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int pb = 0; pb < 4; ++pb)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { accm[cb][pb][i] = 0.f; accl[cb][pb][i] = 0.f; }
+      for (int d = 0; d < nch32; d += 2) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int c = d + i;
+          if (i == 0 || c + 1 < nch32) {
+            load_w_ds(c + 1, (i + 1) & 1);
+#pragma unroll
+            for (int k = 0; k < PIT; ++k) load_p_at(c + 1, k, (i + 1) & 1, gpl[(3 * PIT + k) * NT + tid]);
+          } else {
+            load_w_tap(0, kTap[0], 0);
+#pragma unroll
+            for (int k = 0; k < PIT; ++k) load_p_at(0, k, 0, gnext[k * NT + tid]);
+          }
+          s2_stage(patch + i * 8 * PP + pb_lane + PW + 1, wl + i * WST + wa_lane);
+        }
+      }
+    }
+  }
+  float* const yout = S2 && pass == 1 ? a.y_ds : a.y;
+  const float* const ssp = S2 && pass == 1 ? bsl : ss;
+  const int relu = S2 && pass == 1 ? 0 : a.relu;
   // ---- epilogue: one cell (8 channels of a pixel, hi + lo) per lane and (channel block, row) ----
   // Accumulator lane (j, kq) holds channels 16 cb + 4 kq + i of pixel (row pb >> 1, column 16 (pb & 1) + j).  After the swaps of
   // a row's two pixel blocks lane (j, rw = kq) holds the cell of channels 16 cb + 8 (rw >> 1) .. + 7 at column 16 (rw & 1) + j.
   const int rw = kq;
   const int vcol = vx0 + 16 * (rw & 1) + j;
   const int nl = vdiv(vcol), xl = vcol - nl * a.vw;
-  const bool col_valid = nl < a.N && xl < a.W;
+  const bool col_valid = nl < a.N && xl < (S2 ? a.OW : a.W);      // (stride 1: the output has the input's size)
   const uint32_t plane_ob = (uint32_t)(a.OH * a.OW) * (uint32_t)sizeof(float);
   const uint32_t cplane = (uint32_t)(a.OH * a.OW) * 16u;
   const uint32_t img_bytes = (uint32_t)a.N * (uint32_t)a.Cout * plane_ob;
   const uint32_t img_off = (uint32_t)nl * (uint32_t)a.Cout * plane_ob;
-  const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (int)img_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(yout, 0, (int)img_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(a.res != nullptr ? a.res : a.y), 0, a.res != nullptr ? (int)img_bytes : 0, 0x00020000);
   const int cout0 = ct * 128 + slab * 64;
@@ -500,11 +655,16 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
       const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
-      rh[cb][rr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vcell[rr], so, 0);
-      rl[cb][rr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vcell[rr], so + cplane, 0);
+      if constexpr (S2) {       // (a block entry has no residual)
+        rh[cb][rr] = u32x4{0u, 0u, 0u, 0u};
+        rl[cb][rr] = u32x4{0u, 0u, 0u, 0u};
+      } else {
+        rh[cb][rr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vcell[rr], so, 0);
+        rl[cb][rr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vcell[rr], so + cplane, 0);
+      }
     }
-  const float* sc = ss + slab * 64;
-  const float* sh = ss + 128 + slab * 64;
+  const float* sc = ssp + slab * 64;
+  const float* sh = ssp + 128 + slab * 64;
   float am[2] = {0.f, 0.f};        // per row of the lane: max |x| over its stored values (adx_common.h: fp16_amax)
 #pragma unroll
   for (int cb = 0; cb < 4; ++cb)
@@ -531,7 +691,7 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float tsum = o[i] + r8[i];
-        o[i] = a.relu ? __builtin_fmaxf(tsum, 0.f) : tsum;
+        o[i] = relu ? __builtin_fmaxf(tsum, 0.f) : tsum;
         am[rr] = fp16_amax(am[rr], o[i]);
       }
       u32x4 hi, lo;
@@ -545,10 +705,11 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
     }
   // only pixels of the map count: the shared zero column of the virtual row and the lanes past the last image store nothing
   bad |= ((vcell[0] != kOutside) & out_of_fp16(am[0])) | ((vcell[1] != kOutside) & out_of_fp16(am[1]));
+  } while (S2 && ++pass < 2);
   }
   // ---- on to this workgroup's next tile: its first chunk and first tap are in LDS already ----
   if (!has_next) break;
-  if constexpr (TRAIN != 0) __syncthreads();        // every wave is done with this tile's statistics area (patch buffer 1)
+  if constexpr (TRAIN == 1 || TRAIN == 2) __syncthreads();        // every wave is done with this tile's statistics area (patch buffer 1)
   sp = sp_next; tx = ntx; ty = nty; oy0 = n_oy0; vx0 = n_vx0;
   }
   range_flag(a.status, bad);
@@ -577,6 +738,24 @@ int conv2d_hs3x3q_launch(const Hs3x3Plan& p, Conv2dArgs a, hipStream_t s) {
   a.q_slots = p.q_slots;
   a.ksplit = p.ksplit; a.cper = p.cper; a.part = nullptr;
   table[p.dma][p.stats]<<<dim3((unsigned)p.grid), dim3(p.threads), p.lds, s>>>(a);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
+}
+
+// carries out a plan of conv2d_hs_s2_plan (conv2d_hs.hip) that picked this kernel
+int conv2d_hs3x3q_s2_launch(const HsS2Plan& p, Conv2dArgs a, hipStream_t s) {
+  static std::atomic<uint64_t> attr{0};
+  if (DeviceOnce once{attr}; once) {
+    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_hs3x3q_kernel<true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQLdsS2));
+    once.commit();
+  }
+  ADX_REQUIRE(p.q && a.x_cells && a.y_cells && a.w_ds != nullptr && a.y_ds != nullptr && a.res == nullptr && a.x_amax == nullptr,
+              "conv2d_hs: the 16x16x32 block entry takes a cell input, two cell outputs, no residual and no dynamic range");
+  a.vw = p.vw; a.inv_vw = 1.f / (float)p.vw;
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.cout_tiles = p.cout_tiles; a.ntiles = p.cout_tiles * p.tiles_x * p.tiles_y;
+  a.q_slots = p.q_slots;
+  a.ksplit = 1; a.cper = a.cin_pad / kHsCC; a.part = nullptr;
+  conv2d_hs3x3q_kernel<true, 3><<<dim3((unsigned)p.grid), dim3(p.threads), p.lds, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }

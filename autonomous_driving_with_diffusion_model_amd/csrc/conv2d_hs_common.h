@@ -30,7 +30,9 @@ constexpr int kQPlaneD = 352;
 constexpr int kQPairsD = 4 * kQPlaneD;     // 1408 = 22 waves of 64: whole waves only
 constexpr size_t kQLdsD = (size_t)2 * 8 * kQPlaneD * 16 + (size_t)2 * kQWst * 16 + 256 * sizeof(float) + 2 * 16 + 512 * sizeof(float) +
                           (size_t)kQPit * kQNT * sizeof(uint32_t);      // + the next tile's gather offsets, parked per thread
-static_assert(kQLds <= 160 * 1024 && kQLdsD <= 160 * 1024, "LDS budget");
+// the stride-2 block entry (conv2d_hs3x3q_s2_kernel): + the current tile's gather offsets of the four parity planes, parked the same way
+constexpr size_t kQLdsS2 = kQLdsD + (size_t)4 * kQPit * kQNT * sizeof(uint32_t);
+static_assert(kQLds <= 160 * 1024 && kQLdsD <= 160 * 1024 && kQLdsS2 <= 160 * 1024, "LDS budget");
 
 #ifdef ADX_HS_M16_TIMING
 // TIMING-ONLY build (garbage results): every v_mfma_f32_32x32x16_f16 of the pipelined 3x3 kernel issued as two

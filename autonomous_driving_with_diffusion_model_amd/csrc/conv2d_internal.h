@@ -235,7 +235,28 @@ int conv2d_hs_stem_pool(const ConvSpec& L, const float* x, const float* w, const
 // scale / shift pairs may be null (identity: the training forward wants both raw conv outputs); relu applies to conv1 only
 int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const float* x, const float* w1, const float* scale1,
                               const float* shift1, float* y1, const float* wd, const float* scaled, const float* shiftd,
-                              float* yd, int N, int H, int W, hipStream_t s, int x_cells = 0, int y_cells = 0, int relu = 1);   // x / both outputs in the cell layout
+                              float* yd, int N, int H, int W, hipStream_t s, int x_cells = 0, int y_cells = 0, int relu = 1,   // x / both outputs in the cell layout
+                              bool force_32 = false);     // keep the launch on conv2d_hs_kernel whatever the plan says (tests)
+// ---- the plan of a fused block-entry launch ----
+// conv2d_hs_launch_block_s2 runs conv2d_hs3x3q_s2_kernel (conv2d_hs16.hip: the 16x16x32 tile walk over parity planes) where this
+// pure function says so, and conv2d_hs_kernel (32x32x16, one tile per workgroup) everywhere else.  Like conv2d_hs3x3_plan it sees
+// only the layer's shape, the operand formats the caller chose and the switches -- never the stream or the call's history.
+struct HsS2Query {
+  int N = 0, H = 0, W = 0;        // the INPUT's size
+  bool x_cells = false, y_cells = false;
+  int cus = 0;                    // compute units of the device (sizes the persistent grid only)
+};
+struct HsS2Plan {
+  bool q = false;                 // conv2d_hs3x3q_s2_kernel serves the launch
+  int tiles_x = 0, tiles_y = 0, cout_tiles = 0, vw = 0, q_slots = 0;
+  size_t grid = 0;
+  int threads = 0;
+  size_t lds = 0;
+};
+HsS2Plan conv2d_hs_s2_plan(const ConvSpec& c1, const ConvSpec& ds, const HsS2Query& q, const DebugSwitches& sw = debug_switches());
+int conv2d_hs3x3q_s2_launch(const HsS2Plan& p, Conv2dArgs a, hipStream_t s);
+// compute units of the calling thread's current device (conv2d.hip)
+int device_cus(int* cus);
 // conv1 3x3 stride 2 on the split-fp16 kernel + a 1x1 stride-2 downsample of the same shape: one fused launch (conv2d.hip)
 inline bool resnet_fuses_ds(const ConvSpec& c1, const ConvSpec& ds) {
   return conv2d_hs_eligible(c1) && c1.k == 3 && c1.stride == 2 && c1.pad == 1 && ds.k == 1 && ds.stride == 2 && ds.pad == 0 &&

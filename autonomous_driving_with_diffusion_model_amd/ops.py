@@ -159,6 +159,30 @@ def conv2d_cells(x: torch.Tensor, packed: torch.Tensor, cin: int, cout: int, n: 
     return y
 
 
+def conv2d_block_s2_cells(x: torch.Tensor, w1: torch.Tensor, wd: torch.Tensor, n: int, h: int, w: int, *, scale1=None, shift1=None,
+                          scaled=None, shiftd=None, force_32: bool = False, packed=None):
+    """The entry of a ResNet layer as one launch on cell tensors (adx_conv2d_block_s2_cells): x = cells of [n, cin, h, w];
+    w1 [cout, cin, 3, 3] (stride 2, pad 1, then scale1 / shift1 and ReLU), wd [cout, cin, 1, 1] (stride 2, then scaled / shiftd).
+    Returns (y1 cells, yd cells, packed); `packed` = the two weight images, reusable.  force_32: the 32x32x16 kernel."""
+    cout, cin = w1.shape[0], w1.shape[1]
+    s = L.stream_ptr(x.device)
+    if packed is None:
+        d = L.Conv2dDesc(cin, cout, 3, 2, 1)
+        p1 = torch.empty(L.lib().adx_conv2d_packed_bytes(C.byref(d)) // 4, dtype=torch.float32, device=x.device)
+        pd = torch.empty(cout * cin, dtype=torch.float32, device=x.device)
+        w1c, wdc = w1.detach().contiguous(), wd.detach().contiguous()
+        L.check(L.lib().adx_conv2d_pack(C.byref(d), w1c.data_ptr(), p1.data_ptr(), s), "adx_conv2d_pack")
+        L.check(L.lazy("adx_conv2d_pack_ds")(cin, cout, wdc.data_ptr(), pd.data_ptr(), s), "adx_conv2d_pack_ds")
+        packed = (p1, pd)
+    oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    y1 = torch.empty(n * cout * oh * ow * 4, dtype=torch.uint8, device=x.device)
+    yd = torch.empty_like(y1)
+    L.check(L.lazy("adx_conv2d_block_s2_cells")(cin, cout, x.data_ptr(), packed[0].data_ptr(), L.ptr(scale1), L.ptr(shift1), y1.data_ptr(),
+                                               packed[1].data_ptr(), L.ptr(scaled), L.ptr(shiftd), yd.data_ptr(), n, h, w,
+                                               1 if force_32 else 0, s), "adx_conv2d_block_s2_cells")
+    return y1, yd, packed
+
+
 def conv2d_weight_grad(x: torch.Tensor, dy: torch.Tensor, k: int, *, stride: int = 1, pad: int = 0,
                        estimate_range: bool = True) -> torch.Tensor:
     """d(loss)/d(weight) of conv2d(x, weight, stride, pad) given dy = d(loss)/d(output): [cout, cin, k, k]."""

@@ -350,6 +350,17 @@ int adx_conv2d_cells_supported(const adx_conv2d_desc* d, int32_t n, int32_t h, i
 int adx_conv2d_forward_cells(const adx_conv2d_desc* d, const void* x, const float* packed_w, const float* scale,
                              const float* shift, const void* res, void* y, int32_t n, int32_t h, int32_t w, int32_t relu,
                              int32_t fmt, adx_stream s);
+/* The entry of a ResNet layer as the inference executor launches it, for tests: conv1 = Conv2d(cin, cout, 3, 2, 1) + BatchNorm
+ * (scale1, shift1) + ReLU into y1 and the downsample Conv2d(cin, cout, 1, 2, 0) + BatchNorm (scaled, shiftd) into yd, one launch
+ * over x (modeling/resnet.py:87-102, 230-231).  x [n][cin][h][w] and both outputs [n][cout][(h - 1) / 2 + 1][(w - 1) / 2 + 1] are
+ * cell tensors (adx_conv2d_forward_cells).  packed_w1: adx_conv2d_pack's image of conv1's weights; packed_wd: adx_conv2d_pack_ds's
+ * image of the downsample's [cout][cin][1][1] (cout * cin floats).  Scale / shift pairs may be NULL (identity).  Which kernel runs
+ * follows from the shape (cin % 64 == 0 and cout % 128 == 0: the 16x16x32 tile walk over the input's parity planes, else the
+ * 32x32x16 kernel); flags bit 0 keeps the launch on the 32x32x16 kernel, as ADX_HS_S2Q=0 does for every launch. */
+int adx_conv2d_pack_ds(int32_t cin, int32_t cout, const float* w, float* packed, adx_stream s);
+int adx_conv2d_block_s2_cells(int32_t cin, int32_t cout, const void* x, const float* packed_w1, const float* scale1,
+                              const float* shift1, void* y1, const float* packed_wd, const float* scaled, const float* shiftd,
+                              void* yd, int32_t n, int32_t h, int32_t w, int32_t flags, adx_stream s);
 /* The ResNet's stem as the inference executor runs it, for tests: Conv2d(3, 64, 7, 2, 3) + BatchNorm (scale, shift: [64])
  * + ReLU + MaxPool2d(3, 2, 1) in one launch; only the pooled map is written.  x: fp32 NCHW [n][3][h][w], or with x_u8 = 1
  * uint8 camera frames [n][h][w][3] normalised on the fly as (v / 255 - mean) / std (mean, std: three host floats).
