@@ -4,6 +4,7 @@ Justin900429/autonomous_driving_with_diffusion_model).
 Public surface mirrors the reference's packages:
     modeling.build_model(cfg)                         (reference: modeling/__init__.py)
     scheduler.{GuidanceDDIM,GuidanceDDPM,InpaintingDDIM,InpaintingDDPM}Scheduler, DDPMScheduler
+    scheduler.GuidanceDPMSolverMultistepScheduler     (no reference counterpart: what `EVAL.SCHEDULER: dpm` names, scheduler/dpm.py)
     control.GuidanceLoss
     DeviceNoise                                       (no reference counterpart: in-kernel sampler noise, noise.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -21,5 +22,6 @@ _os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
 from . import _lib  # noqa: F401,E402
 from .noise import DeviceNoise  # noqa: E402
+from .scheduler import GuidanceDPMSolverMultistepScheduler  # noqa: E402
 
-__all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise"]
+__all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler"]

@@ -63,6 +63,12 @@ class StepCoef(C.Structure):
                 ("free_scale", f32), ("zero_first", i32)]
 
 
+class DpmCoef(C.Structure):
+    _fields_ = [("prediction_type", i32), ("clip", i32), ("clip_range", f32), ("alpha_s", f32), ("sigma_s", f32),
+                ("r", f32), ("k", f32), ("second_order", i32), ("inv_r0", f32), ("half_k", f32), ("cfg_combine", i32),
+                ("free_scale", f32), ("zero_first", i32)]
+
+
 _SIGS = {
     "adx_version": (i32, []),
     "adx_last_error": (C.c_char_p, []),
@@ -160,6 +166,7 @@ _SIGS = {
     "adx_ddpm_step": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "adx_ddim_step_rng": (i32, [C.POINTER(StepCoef), vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp]),
     "adx_ddpm_step_rng": (i32, [C.POINTER(StepCoef), vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "adx_dpm_step": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "adx_noise_normal": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_words": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_advance": (i32, [vp, vp]),

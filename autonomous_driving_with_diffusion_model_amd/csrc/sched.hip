@@ -183,6 +183,83 @@ int ddpm_step_rng(const adx_step_coef* c, const float* mo, const float* x, const
   return step_launch<true, true>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, prev, x0, b, h, d, s);
 }
 
+// DPM-Solver++ multistep step (order 1 and the order-2 midpoint rule; diffusers 0.28.0 DPMSolverMultistepScheduler,
+// algorithm_type = "dpmsolver++", restated in scheduler/dpm.py).  The same shape as step_kernel: one thread per element, the
+// host's fp32 scalars by value, every product rounded on its own and evaluated left to right.  The one thing the DDIM step
+// does not have is HISTORY: the second-order term reads the x0 the previous step wrote, so x0 is always written.
+struct DpmArgs {
+  adx_dpm_coef c;
+  const float* mo;
+  const float* x;
+  const float* px0;     // x0 of the previous step; null on a first-order step
+  float* prev;
+  float* x0;
+  int total, horizon, dim;
+};
+
+__global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.total) return;
+  const adx_dpm_coef& c = a.c;
+  float m;
+  if (c.cfg_combine) {
+    const float cnd = a.mo[e], unc = a.mo[e + a.total];
+    const float d = cnd - unc;
+    const float sd = c.free_scale * d;
+    m = unc + sd;
+  } else {
+    m = a.mo[e];
+  }
+  const float xs = a.x[e];
+  float x0;
+  if (c.prediction_type == ADX_PRED_EPSILON) {
+    const float p = c.sigma_s * m;
+    x0 = (xs - p) / c.alpha_s;
+  } else if (c.prediction_type == ADX_PRED_SAMPLE) {
+    x0 = m;
+  } else {
+    const float p = c.alpha_s * xs, q = c.sigma_s * m;
+    x0 = p - q;
+  }
+  if (c.clip) x0 = clamp_nan(x0, -c.clip_range, c.clip_range);
+  const float p = c.r * xs, q = c.k * x0;
+  float prev = p - q;
+  if (c.second_order && a.px0 != nullptr) {
+    const float d0 = x0 - a.px0[e];
+    const float d1 = c.inv_r0 * d0;
+    const float u = c.half_k * d1;
+    prev = prev - u;
+  }
+  if (c.zero_first) {
+    const int d = e % a.dim;
+    const int h = (e / a.dim) % a.horizon;
+    if (h == 0 && d < 3) prev = 0.f;
+  }
+  a.prev[e] = prev;
+  a.x0[e] = x0;          // as computed (not zeroed): the next step's history
+}
+
+int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, float* prev, float* x0, int batch,
+             int horizon, int dim, hipStream_t s) {
+  ADX_REQUIRE(c && mo && x && prev && x0, "dpm step: null tensor");
+  ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1, "dpm step: empty shape");
+  ADX_REQUIRE((int64_t)batch * horizon * dim <= (int64_t)0x3fffffff, "dpm step: %lld elements do not fit the kernel's 32-bit index",
+              (long long)batch * horizon * dim);
+  ADX_REQUIRE(c->prediction_type >= 0 && c->prediction_type <= 2,
+              "prediction_type given as %d must be one of `epsilon`, `sample`, or `v_prediction`", c->prediction_type);
+  ADX_REQUIRE(!c->second_order || px0 != nullptr, "dpm step: a second-order step needs the previous step's x0");
+  ADX_REQUIRE(px0 != prev && px0 != x0 && x != prev && x != x0 && mo != prev && mo != x0 && prev != x0,
+              "dpm step: outputs alias an input or each other");
+  DpmArgs a;
+  a.c = *c;
+  a.mo = mo; a.x = x; a.px0 = px0; a.prev = prev; a.x0 = x0;
+  a.total = batch * horizon * dim; a.horizon = horizon; a.dim = dim;
+  dpm_step_kernel<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
+}
+
 // Fill out[0, n) with the stream's values of the logical elements [first, first + n): what a step kernel draws at those
 // elements under the same (state, slot).  One thread per element through the same __device__ function as the step.
 template <bool NORMAL, typename T>

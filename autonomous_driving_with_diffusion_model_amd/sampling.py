@@ -63,7 +63,8 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     trajs[:, 0, :3] = 0.0
     if set_timesteps:
         scheduler.set_timesteps(cfg.EVAL.SAMPLE_STEPS, device=device)
-    is_ddpm = not getattr(scheduler, "_is_ddim", False)
+    # whose step takes an injected `variance_noise`: the DDPM schedulers (a deterministic solver has no noise argument)
+    is_ddpm = not getattr(scheduler, "_is_ddim", False) and not getattr(scheduler, "deterministic", False)
     # What the UNet derives from (t, target, image feature) alone does not change inside the loop: with the perception
     # memo on (the product default) it is computed for all timesteps in one pass, and each step then starts at the first
     # convolution.  The reference-faithful mode (cache_perception = False) keeps the reference's per-step recomputation.
@@ -174,7 +175,9 @@ class GraphedSampler:
     B = 1 the 50-step DDIM loop takes 29.2 ms eagerly and 26.4 ms as one graph launch on an MI355X
     (tools/graph_probe.py; at B = 64 the GPU is the bound either way).  Results are bit-identical to the eager loop.
 
-    Without `noise`: deterministic samplers only (DDIM with eta = 0; a DDPM loop would replay its captured noise tensors).
+    Without `noise`: deterministic samplers only (DDIM with eta = 0, or a scheduler that says `deterministic = True` of itself:
+    the DPM-Solver++ multistep sampler, whose x0 history is allocated by its steps inside the capture and so lives in the graph's
+    pool; a DDPM loop would replay its captured noise tensors).
     With `noise=DeviceNoise(...)` the DDPM scheduler is accepted too: `begin_tick()`, the initial draw (when `init_trajs`
     is not passed) and every step's in-kernel draw are nodes of the graph and read the stream's state from device memory,
     so replay k of a fresh object samples under tick k -- bit for bit what the eager `generate_traj(noise=...)` gives there.
@@ -183,9 +186,10 @@ class GraphedSampler:
     """
 
     def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None):
-        if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not getattr(scheduler, "_is_ddim", False)):
-            raise ValueError("GraphedSampler needs a deterministic sampler (DDIM, eta = 0), or a DeviceNoise for the DDPM sampler "
-                             "(noise=...)")
+        deterministic = getattr(scheduler, "_is_ddim", False) or getattr(scheduler, "deterministic", False)
+        if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not deterministic):
+            raise ValueError("GraphedSampler needs a deterministic sampler (DDIM with eta = 0, DPM-Solver++), or a DeviceNoise for "
+                             "the DDPM sampler (noise=...)")
         self.model, self.scheduler, self.cfg, self.scale_xy, self.noise = model, scheduler, cfg, scale_xy, noise
         self._key = None
         self._graph = None

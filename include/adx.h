@@ -554,6 +554,37 @@ int adx_ddim_step(const adx_step_coef* c, const float* model_output, const float
 int adx_ddpm_step(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                   const float* target, const float* mask, float* prev, float* x0,
                   int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+/* DPM-Solver++ multistep step, orders 1 and 2 (midpoint).  No reference counterpart: the reference names a "dpm" scheduler
+ * (interact.py:92-93) but never constructs one; the arithmetic is diffusers 0.28.0 DPMSolverMultistepScheduler with
+ * algorithm_type = "dpmsolver++", restated on the host in scheduler/dpm.py.  With sigma_i the schedule's noise level at
+ * step i (sigma = 0 after the last step), alpha = 1 / sqrt(sigma^2 + 1), sigma_t = sigma * alpha, lambda = log(alpha) -
+ * log(sigma_t) and h = lambda_{i+1} - lambda_i, the host passes fp32 scalars by value; the kernel rounds every product on its
+ * own, left to right:
+ *   m     = cfg_combine ? uncond + free_scale * (cond - uncond) : model_output      (rows [0,B) cond, [B,2B) uncond)
+ *   x0    = epsilon: (x - sigma_s * m) / alpha_s;  sample: m;  v_prediction: alpha_s * x - sigma_s * m;  then the clamp
+ *   prev  = r * x - k * x0                                                           first order (== a DDIM step)
+ *   prev  = (r * x - k * x0) - half_k * (inv_r0 * (x0 - prev_x0))                    second_order, prev_x0 given
+ * The last step of a schedule has sigma_{i+1} = 0: h = inf, r = 0, k = -1, i.e. prev = x0. */
+typedef struct adx_dpm_coef {
+  int32_t prediction_type;     /* ADX_PRED_* */
+  int32_t clip;                /* 1: clamp x0 to [-clip_range, clip_range] (`thresholding=True`, sample_max_value = 1) */
+  float clip_range;
+  float alpha_s, sigma_s;      /* alpha and sigma * alpha at the CURRENT step i */
+  float r;                     /* sigma_t(i+1) / sigma_t(i) */
+  float k;                     /* alpha(i+1) * (exp(-h) - 1) */
+  int32_t second_order;        /* 1: add the multistep term; needs prev_x0 */
+  float inv_r0;                /* 1 / r0, r0 = (lambda_i - lambda_{i-1}) / h */
+  float half_k;                /* 0.5 * k */
+  int32_t cfg_combine; float free_scale;   /* as in adx_step_coef */
+  int32_t zero_first;          /* 1: prev[:, 0, :3] = 0 on prev_sample only; x0 is written as computed */
+} adx_dpm_coef;
+
+/* model_output: [batch][horizon][dim], or [2 * batch] rows when c->cfg_combine.  prev_x0: the x0 the previous step wrote, or
+ * NULL (then the step is first order; NULL with c->second_order set is refused).  prev_sample and x0 are both always
+ * written and may not alias an input: x0 is the next step's prev_x0. */
+int adx_dpm_step(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                 float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+
 /* ------------------------------------------------------------------------------------
  * Noise stream v1: standard normals as a pure function of (seed, tick, slot, element).  No reference counterpart (the
  * reference draws torch.randn per step); the values differ from torch's for the same seed.  Fixtures and users depend on
