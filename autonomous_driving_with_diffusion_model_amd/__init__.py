@@ -7,6 +7,7 @@ Public surface mirrors the reference's packages:
     scheduler.GuidanceDPMSolverMultistepScheduler     (no reference counterpart: what `EVAL.SCHEDULER: dpm` names, scheduler/dpm.py)
     control.GuidanceLoss
     DeviceNoise                                       (no reference counterpart: in-kernel sampler noise, noise.py)
+    TrajectorySelector, Selection                     (no reference counterpart: best-of-K sampling, control/select.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
 All compute runs in libadx.so (hand-written HIP for gfx950); there is no CPU fallback.
 """
@@ -23,5 +24,7 @@ _os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 from . import _lib  # noqa: F401,E402
 from .noise import DeviceNoise  # noqa: E402
 from .scheduler import GuidanceDPMSolverMultistepScheduler  # noqa: E402
+from .control.select import Selection, TrajectorySelector  # noqa: E402
 
-__all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler"]
+__all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
+           "TrajectorySelector", "Selection"]

@@ -69,6 +69,11 @@ class DpmCoef(C.Structure):
                 ("free_scale", f32), ("zero_first", i32)]
 
 
+class SelectCfg(C.Structure):
+    _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("w_goal", f32), ("w_smooth", f32),
+                ("w_consensus", f32)]
+
+
 _SIGS = {
     "adx_version": (i32, []),
     "adx_last_error": (C.c_char_p, []),
@@ -167,6 +172,7 @@ _SIGS = {
     "adx_ddim_step_rng": (i32, [C.POINTER(StepCoef), vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp]),
     "adx_ddpm_step_rng": (i32, [C.POINTER(StepCoef), vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp]),
     "adx_dpm_step": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "adx_traj_select": (i32, [C.POINTER(SelectCfg), vp, vp, vp, vp, vp, vp]),
     "adx_noise_normal": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_words": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_advance": (i32, [vp, vp]),

@@ -1,0 +1,62 @@
+"""Best-of-K sampling: score K candidate trajectories per scene on the device and keep the best one.
+
+`TrajectorySelector` is one launch of `adx_traj_select` (csrc/select.hip): the costs, the arg-min and the copy of the winning
+row run on the GPU with no host decision, so the call can be a node of a captured graph (`GraphedSampler(..., candidates=K)`).
+The cost is "selection cost v1" of include/adx.h -- goal distance, smoothness and consensus terms over the xy columns, in the
+model's own units (the clamped trajectory before xy scaling).  No reference counterpart: the reference's `train.evaluate`
+draws many trajectories for one image only to paint them (train.py:62-90).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import torch
+
+from .. import _lib as L
+
+MAX_CANDIDATES = 64
+
+
+class Selection(NamedTuple):
+    best: torch.Tensor                 # [S, H, D]: the chosen candidate of every scene, bit for bit
+    index: torch.Tensor                # [S] int32: which candidate that is
+    cost: torch.Tensor                 # [S, K]: every candidate's cost
+    candidates: Optional[torch.Tensor] = None   # [K, S, H, D] (generate_traj(..., return_selection=True) only)
+
+
+class TrajectorySelector:
+    """cost = w_goal * goal + w_smooth * smooth + w_consensus * consensus (include/adx.h, selection cost v1); the
+    candidate with the smallest cost wins, ties go to the lowest index, a non-finite cost loses to every finite one."""
+
+    def __init__(self, w_goal: float = 1.0, w_smooth: float = 0.0, w_consensus: float = 0.0):
+        self.w_goal, self.w_smooth, self.w_consensus = float(w_goal), float(w_smooth), float(w_consensus)
+
+    def __call__(self, trajs: torch.Tensor, scenes: int, target: Optional[torch.Tensor] = None) -> Selection:
+        """trajs [K * scenes, H, D] in candidate-major order (candidate k of scene s is row k * scenes + s), or
+        [K, scenes, H, D]; target None or [scenes, 2] in the units of trajs."""
+        scenes = int(scenes)
+        if trajs.dim() == 4:
+            if trajs.shape[1] != scenes:
+                raise ValueError(f"trajs {tuple(trajs.shape)} is not [K, {scenes}, H, D]")
+            trajs = trajs.reshape(-1, trajs.shape[2], trajs.shape[3])
+        if trajs.dim() != 3 or scenes < 1 or trajs.shape[0] % scenes != 0:
+            raise ValueError(f"trajs must be [K * {scenes}, H, D], got {tuple(trajs.shape)}")
+        trajs = L.require_gpu_f32(trajs, "trajs")
+        rows, H, D = trajs.shape
+        K = rows // scenes
+        if target is not None:
+            target = L.require_gpu_f32(target, "target")
+            if tuple(target.shape) != (scenes, 2):
+                raise ValueError(f"target must be [{scenes}, 2], got {tuple(target.shape)}")
+        dev = trajs.device
+        cost = torch.empty((scenes, K), dtype=torch.float32, device=dev)
+        index = torch.empty((scenes,), dtype=torch.int32, device=dev)
+        best = torch.empty((scenes, H, D), dtype=torch.float32, device=dev)
+        cfg = L.SelectCfg(scenes, K, H, D, self.w_goal, self.w_smooth, self.w_consensus)
+        L.check(L.lib().adx_traj_select(C.byref(cfg), trajs.data_ptr(), L.ptr(target), cost.data_ptr(), index.data_ptr(),
+                                        best.data_ptr(), L.stream_ptr(dev)), "adx_traj_select")
+        return Selection(best, index, cost)
+
+    def __repr__(self):
+        return f"TrajectorySelector(w_goal={self.w_goal}, w_smooth={self.w_smooth}, w_consensus={self.w_consensus})"

@@ -74,6 +74,8 @@ int ddpm_step_rng(const adx_step_coef* c, const float* mo, const float* x, const
                   const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
 int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, float* prev, float* x0, int b, int h,
              int d, hipStream_t s);
+int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
+                hipStream_t s);
 int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);
 int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s);
 int noise_advance(uint32_t* state, hipStream_t s);
@@ -171,6 +173,10 @@ int adx_ddpm_step_rng(const adx_step_coef* c, const float* model_output, const f
 int adx_dpm_step(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                  float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
   return adx::dpm_step(c, model_output, sample, prev_x0, prev_sample, x0, batch, horizon, dim, (hipStream_t)s);
+}
+int adx_traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index,
+                    float* best, adx_stream s) {
+  return adx::traj_select(c, trajs, target, cost, index, best, (hipStream_t)s);
 }
 int adx_noise_normal(const uint32_t* state, int32_t slot, int64_t first_elem, float* out, int64_t n, adx_stream s) {
   return adx::noise_normal(state, slot, first_elem, out, n, (hipStream_t)s);

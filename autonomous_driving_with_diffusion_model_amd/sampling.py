@@ -13,6 +13,8 @@ Differences from the callers, both optional and numerically identical:
 A third option changes WHICH noise a stochastic sampler sees, not the arithmetic: `noise=DeviceNoise(...)` draws the initial
 trajectory and every step's noise from the counter-based stream of noise.py inside the step kernel, where the callers draw
 `torch.randn` tensors -- the same loop then also runs as one HIP graph (`GraphedSampler(..., noise=...)`).
+A fourth has no counterpart in the callers: `candidates=K` draws K trajectories per scene in one loop of K * S rows (the encoder
+still runs once per scene) and keeps the one a device-side cost prefers (control/select.py, "selection cost v1" of include/adx.h).
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ from typing import Callable, Optional
 import torch
 
 from ._lib import AdxRangeError
+from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
 from .noise import DeviceNoise
 
@@ -37,26 +40,60 @@ def _targets(target: Optional[torch.Tensor], batch: int) -> Optional[torch.Tenso
     return t.contiguous()
 
 
+def _candidates(cfg, candidates: int, selector):
+    """The keyword arguments left at their defaults read EVAL.CANDIDATES / EVAL.SELECT (absent keys: 1, goal distance only)."""
+    K = int(candidates)
+    if K == 1:
+        K = int(getattr(cfg.EVAL, "CANDIDATES", 1))
+    if not 1 <= K <= MAX_CANDIDATES:
+        raise ValueError(f"candidates must be 1..{MAX_CANDIDATES}, got {K}")
+    if K > 1 and selector is None:
+        selector = TrajectorySelector(*getattr(cfg.EVAL, "SELECT", (1.0, 0.0, 0.0)))
+    return K, selector
+
+
 def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                   init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, scale_xy: bool = True,
                   step_noise: Optional[Callable[[int, tuple], torch.Tensor]] = None,
-                  set_timesteps: bool = True, noise: Optional[DeviceNoise] = None) -> torch.Tensor:
+                  set_timesteps: bool = True, noise: Optional[DeviceNoise] = None, candidates: int = 1,
+                  selector: Optional[TrajectorySelector] = None, return_selection: bool = False):
     """`noise`: a DeviceNoise.  The call is then one tick of the noise stream: `begin_tick()` first, the initial trajectory
     (when `init_trajs` is not given) from `INIT_SLOT`, and every scheduler step draws inside its kernel at the slot of its
-    timestep -- no noise tensor, no torch generator."""
+    timestep -- no noise tensor, no torch generator.
+
+    `candidates` = K > 1: best-of-K sampling.  With S = image.shape[0] scenes the loop runs on K * S rows in candidate-major
+    order (candidate k of scene s is row k * S + s, and draws logical row k * S + s of the noise stream); the targets are
+    tiled K times and the conditioning table keeps the image batch at S, so the encoder runs once per scene.  After the
+    final clamp `selector` (default: `TrajectorySelector(*cfg.EVAL.SELECT)`) scores the candidates against `target` on the
+    device and the call returns the [S, H, D] winners, xy-scaled as usual.  `init_trajs`, when given, is [K * S, H, D].
+    `return_selection=True` returns `(traj, Selection)`, whose `candidates` is the [K, S, H, D] tensor scaled like `traj`
+    (`(traj, None)` at K = 1, where no selector runs).  Needs the hoisted conditioning path (`fuse=True`, `model.cache_perception`
+    on) and an unsharded `noise`.  K = 1 (the default, or EVAL.CANDIDATES when the argument is left at 1) is the loop as it was."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     model.eval()
     device = image.device
+    K, selector = _candidates(cfg, candidates, selector)
+    S = image.shape[0]
+    if K > 1:
+        if not (fuse and getattr(model, "cache_perception", False) and hasattr(model, "time_conditioning")):
+            raise ValueError("generate_traj: candidates > 1 needs the hoisted conditioning path: fuse=True and "
+                             "model.cache_perception on (the per-step path would run the encoder on K * S rows)")
+        if noise is not None and noise.row_offset > 0:
+            raise ValueError("generate_traj: candidates > 1 does not take a sharded DeviceNoise (row_offset "
+                             f"{noise.row_offset}): scene sharding and candidate-major rows do not compose")
+        if init_trajs is not None and init_trajs.shape[0] != K * S:
+            raise ValueError(f"init_trajs must have candidates * scenes = {K * S} rows, got {tuple(init_trajs.shape)}")
     if noise is not None:
         if step_noise is not None:
             raise ValueError("generate_traj: pass `noise` (the in-kernel stream) or `step_noise` (injected tensors), not both")
         noise.begin_tick()
     if init_trajs is None:
-        shape = (image.shape[0], cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM)
+        shape = (K * S, cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM)
         init_trajs = torch.randn(shape, device=device) if noise is None else noise.normal(DeviceNoise.INIT_SLOT, shape)
     trajs = init_trajs.clone().detach()
     B = trajs.shape[0]
-    tgt = _targets(target, B)
+    scene_tgt = _targets(target, S) if K > 1 else None
+    tgt = _targets(target, B) if K == 1 else (None if scene_tgt is None else scene_tgt.repeat(K, 1))
     cond = None
     if tgt is not None and use == GuidanceType.FREE_GUIDANCE:
         cond = torch.cat([tgt, torch.zeros_like(tgt)], dim=0)   # interact.py:121-127
@@ -74,6 +111,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         ts = scheduler.timesteps
         ts = ts.tensor if hasattr(ts, "tensor") else torch.as_tensor(ts)
         with torch.no_grad():
+            # table row r reads image feature r % S: with candidate-major rows that is the row's own scene
             tc = model.time_conditioning(image, ts.to(device), cond=cond, rows=rows)
     pair = (lambda x: x) if B == 1 and tc is not None else (lambda x: torch.cat([x, x], dim=0))
     # nothing in this loop writes `image`: say so, so that the reference-faithful per-step encoder pass of a batched tick may run
@@ -83,9 +121,21 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         trajs = _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device,
                            noise)
     trajs = trajs.to(torch.float32).clamp(-1, 1)
+    if K == 1:
+        if scale_xy:
+            trajs[..., :2] *= model.magic_num
+        return (trajs, None) if return_selection else trajs
+    # the cost is taken in the model's own units (before xy scaling: the units of `target`)
+    sel = selector(trajs, S, scene_tgt)
+    best = sel.best
     if scale_xy:
-        trajs[..., :2] *= model.magic_num
-    return trajs
+        best[..., :2] *= model.magic_num
+    if not return_selection:
+        return best
+    cands = trajs.reshape(K, S, trajs.shape[1], trajs.shape[2])
+    if scale_xy:
+        cands[..., :2] *= model.magic_num
+    return best, Selection(best, sel.index, sel.cost, cands)
 
 
 def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device, noise=None):
@@ -183,16 +233,21 @@ class GraphedSampler:
     so replay k of a fresh object samples under tick k -- bit for bit what the eager `generate_traj(noise=...)` gives there.
     Eval mode, fused step path.  Inputs are copied into static buffers; the camera frame's perception pass is part of
     the graph, so every replay sees the new frame.
+    `candidates=K` > 1 (or EVAL.CANDIDATES when left at 1): best-of-K sampling as in `generate_traj`; the select kernel is a
+    node of the graph, the call returns the [S, H, D] winners and `last_selection` the last replay's index and cost.
     """
 
-    def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None):
+    def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None,
+                 candidates: int = 1, selector: Optional[TrajectorySelector] = None):
         deterministic = getattr(scheduler, "_is_ddim", False) or getattr(scheduler, "deterministic", False)
         if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not deterministic):
             raise ValueError("GraphedSampler needs a deterministic sampler (DDIM with eta = 0, DPM-Solver++), or a DeviceNoise for "
                              "the DDPM sampler (noise=...)")
         self.model, self.scheduler, self.cfg, self.scale_xy, self.noise = model, scheduler, cfg, scale_xy, noise
+        self.candidates, self.selector = int(candidates), selector
         self._key = None
         self._graph = None
+        self._sel = None
 
     def _capture(self, image, target, init_trajs):
         dev = image.device
@@ -204,7 +259,8 @@ class GraphedSampler:
         self._img, self._init = image.clone(), None if init_trajs is None else init_trajs.clone()
         self._tgt = None if target is None else target.clone()
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, self._img, self._tgt, self._init,  # noqa: E731
-                                    fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise)
+                                    fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
+                                    candidates=self.candidates, selector=self.selector, return_selection=True)
         tick = None if self.noise is None else self.noise.tick()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -218,7 +274,7 @@ class GraphedSampler:
         # thread-local capture mode: a process group's watchdog thread (multi-rank runs) may query events while this
         # thread captures; in the default global mode that would invalidate the capture
         with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
-            self._out = run()
+            self._out, self._sel = run()
         self.model._feat_cache = None          # the memo now points at the static frame buffer: drop it
         self._pointers = self._model_pointers()
 
@@ -236,18 +292,28 @@ class GraphedSampler:
     def reset(self) -> None:
         """Forget the captured graph (call after the model's weights changed: the weight images are packed outside
         the graph, during the warm-up pass of the next capture)."""
-        self._key, self._graph = None, None
+        self._key, self._graph, self._sel = None, None, None
+
+    @property
+    def last_selection(self) -> Optional[Selection]:
+        """Clones of the static `index` [S] and `cost` [S, K] buffers as the last replay left them (`best` and `candidates`
+        are not kept: the call returned the winners); None before the first call and at one candidate per scene."""
+        if self._sel is None:
+            return None
+        return Selection(None, self._sel.index.clone(), self._sel.cost.clone())
 
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        K, sel = _candidates(self.cfg, self.candidates, self.selector)
         if init_trajs is None and self.noise is None:
-            init_trajs = torch.randn((image.shape[0], self.cfg.MODEL.HORIZON, self.cfg.MODEL.TRANSITION_DIM),
+            init_trajs = torch.randn((K * image.shape[0], self.cfg.MODEL.HORIZON, self.cfg.MODEL.TRANSITION_DIM),
                                      device=image.device)
         # init_trajs None (with a DeviceNoise): the initial trajectory is drawn inside the graph, from INIT_SLOT
         key = (tuple(image.shape), None if target is None else tuple(target.shape),
                None if init_trajs is None else tuple(init_trajs.shape), image.device,
-               self.cfg.EVAL.SAMPLE_STEPS, self.cfg.GUIDANCE.USE_COND)
+               self.cfg.EVAL.SAMPLE_STEPS, self.cfg.GUIDANCE.USE_COND, K,
+               None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus))   # baked into the select node
         if key != self._key or self._graph is None or self._pointers != self._model_pointers():
             self._capture(image, target, init_trajs)
             self._key = key

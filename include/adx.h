@@ -619,6 +619,42 @@ int adx_ddpm_step_rng(const adx_step_coef* c, const float* model_output, const f
                       int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
 
+/* ------------------------------------------------------------------------------------
+ * Selection cost v1: best-of-K sampling.  K candidate trajectories per scene are scored and the best one is copied out, in
+ * one launch with no host decision (a node of a captured graph).  No reference counterpart: train.evaluate draws many
+ * trajectories for one image only to paint them (train.py:62-90).  Callers and fixtures depend on this definition -- a
+ * change is a new cost version, never an edit.
+ *
+ *   layout   trajs [candidates * scenes][H][D], CANDIDATE-MAJOR: candidate k of scene s is row k * scenes + s -- the row
+ *            order of a sampling loop whose image batch is `scenes` (adx_embed_forward: row r reads feature r % feat_rows).
+ *   points   p_h = (x, y) = the first min(D, 2) columns of waypoint h, h = 0..H-1; a missing y column (D = 1) counts as 0.
+ *            Units are the model's own: the clamped trajectory BEFORE any xy scaling, the units of `target`.
+ *   goal     min over h of |p_h - g_s|^2, g_s = target[s].  0 when target is NULL; w_goal is then ignored.
+ *   smooth   mean over h = 1..H-2 of |p_{h+1} - 2 p_h + p_{h-1}|^2; 0 when H < 3.
+ *   consensus  mean over h of |p_h - m_h|^2, m_h = the mean of p_h over the scene's K candidates.
+ *   cost     w_goal * goal + w_smooth * smooth + w_consensus * consensus, in this order.  A term whose weight is exactly 0
+ *            is not evaluated: it contributes 0 whatever its value would be (a NaN candidate then cannot reach the others'
+ *            costs through the mean path of a consensus term nobody asked for).  A NaN waypoint makes every term it enters NaN.
+ *   index    index[s] = the smallest k with the smallest cost.  A non-finite cost (NaN, +-inf) loses to every finite one;
+ *            if no cost of the scene is finite, index[s] = 0.
+ *   best     best[s] = row index[s] * scenes + s of trajs, all H * D values, copied bit for bit.
+ *   arithmetic  fp32, every product and sum rounded on its own, fixed reduction trees, no atomics: the same input gives the
+ *            same bits on every launch.  cost is defined up to fp32 rounding of the sums above (tests/select_ref.py restates
+ *            it in fp64 and derives the bound), index and best exactly wherever the two smallest costs differ by more than that.
+ *
+ * Limits: 1 <= candidates <= 64, 1 <= horizon <= 64 (the longest the UNet takes), 1 <= dim <= 16, 1 <= scenes <= 65535.
+ * ADX_ERR_INVALID before any GPU work for a value out of range, a NULL pointer other than target, or an output that
+ * overlaps trajs or another output.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_select_cfg {
+  int32_t scenes, candidates, horizon, dim;
+  float w_goal, w_smooth, w_consensus;
+} adx_select_cfg;
+/* trajs [candidates*scenes][H][D], row = k*scenes + s; target [scenes][2] or NULL; cost [scenes][candidates];
+ * index [scenes] (int32); best [scenes][H][D].  No output may alias trajs. */
+int adx_traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index,
+                    float* best, adx_stream s);
+
 /* add_noise (train.py:234) fused with the [...,0,:3] = 0 of train.py:235 when zero_first != 0.
  * sqrt_ab / sqrt_1mab are the host tables sqrt(abar), sqrt(1-abar) of length n_train. */
 int adx_add_noise(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,

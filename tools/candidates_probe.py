@@ -1,0 +1,193 @@
+"""What do K candidates per scene cost a driving tick?  One scene, H = 16, FREE guidance (scale 7.5), full-size camera frame,
+perception pass inside the tick, every arm a GraphedSampler(candidates=K, noise=DeviceNoise) -- one HIP graph launch per tick
+with the select kernel as its last compute node -- for K in {1, 2, 4, 8, 16, 32} under
+
+    ddim50   GuidanceDDIMScheduler (eta = 0), 50 steps: the deployed configuration
+    dpm10    GuidanceDPMSolverMultistepScheduler (2M), 10 steps
+
+The arms alternate in one process, `--rounds` times, each window timed with device events around >= `--ticks` ticks (at least
+`--seconds` of them); reported are the median over the rounds, the spread, and every K against K = 1 of the same sampler, same
+process.  K = 1 is the loop as it was (no select launch).  This measures time only: whether the chosen candidate drives
+better is not something the repository can measure (it has no trained weights).
+
+    python tools/candidates_probe.py --json profiles/candidates_tick.json
+
+The select kernel's own time comes from a trace, in a run of its own (tracing slows the host):
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/candidates_probe.py --select-launches 200
+    python tools/candidates_probe.py --fold-trace OUT --json profiles/candidates_tick.json
+
+`--select-launches N` launches the selector alone N times per K (K = 2 .. 32, in that order, on [K, 1, 16, 7] candidates);
+`--fold-trace` reads the per-dispatch kernel trace, cuts the select kernel's dispatches into those blocks of N and adds
+`select_kernel_us` to the record.
+"""
+import argparse
+import contextlib
+import csv
+import glob
+import json
+import os
+import statistics
+import sys
+
+KS = (1, 2, 4, 8, 16, 32)
+SAMPLERS = (("ddim", 50), ("dpm", 10))
+SCHED_KW = dict(num_train_timesteps=100, prediction_type="sample", beta_schedule="squaredcos_cap_v2", beta_start=1e-4, beta_end=0.02)
+IMG = (256, 900)
+WEIGHTS = (1.0, 0.5, 0.25)
+KERNEL = "traj_select_kernel"
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def make_cfg(steps):
+    from autonomous_driving_with_diffusion_model_amd.config import create_cfg
+    cfg = create_cfg()
+    cfg.MODEL.HORIZON = 16
+    cfg.TRAIN.USE_COND = cfg.GUIDANCE.USE_COND = "FREE_GUIDANCE"
+    cfg.GUIDANCE.FREE_SCALE, cfg.EVAL.SAMPLE_STEPS = 7.5, steps
+    return cfg
+
+
+def arms(dev):
+    import torch  # noqa: F401
+    from autonomous_driving_with_diffusion_model_amd import DeviceNoise, TrajectorySelector
+    from autonomous_driving_with_diffusion_model_amd import scheduler as S
+    from autonomous_driving_with_diffusion_model_amd.modeling import build_model
+    from autonomous_driving_with_diffusion_model_amd.sampling import GraphedSampler
+    from autonomous_driving_with_diffusion_model_amd.utils import procedural as P
+    with contextlib.redirect_stdout(sys.stderr):
+        model = build_model(make_cfg(10))
+    P.load_procedural(model, 0)
+    model = model.to(dev).eval()
+    d = {k: v.to(dev) for k, v in P.synthetic_batch(1, 16, image_hw=IMG, seed=3).items()}
+    img, tgt = d["imgs"], d["target"]
+    fns = {}
+    for K in reversed(KS):            # the largest K first: its warm-up sizes the model's workspace once, for every arm
+        for kind, steps in SAMPLERS:
+            cfg = make_cfg(steps)
+            if kind == "dpm":
+                sch = S.GuidanceDPMSolverMultistepScheduler(cfg=cfg, thresholding=True, lambda_min_clipped=-5.1, **SCHED_KW)
+            else:
+                sch = S.GuidanceDDIMScheduler(cfg=cfg, thresholding=True, **SCHED_KW)
+            gs = GraphedSampler(model, sch, cfg, noise=DeviceNoise(1000 + K, dev), candidates=K, selector=TrajectorySelector(*WEIGHTS))
+            fns[f"{kind}{steps}_k{K}"] = (lambda gs=gs: gs(img, tgt))
+    return fns
+
+
+def timed(fn, ticks):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(ticks):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / ticks
+
+
+def measure(a):
+    import torch
+    dev = torch.device("cuda:0")
+    with torch.no_grad():
+        fns = arms(dev)
+        ticks = {}
+        for fn in fns.values():                 # warm every arm (captures included) ...
+            for _ in range(3):
+                fn()
+        for k, fn in fns.items():               # ... then size the windows, once no arm's capture can move the model's buffers
+            fn()
+            torch.cuda.synchronize()
+            ticks[k] = max(a.ticks, int(a.seconds * 1e3 / timed(fn, 5)) + 1)
+        ms = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                ms[k].append(timed(fn, ticks[k]))
+    record = {"device": torch.cuda.get_device_name(0), "image": list(IMG), "horizon": 16, "scenes": 1, "guidance": "FREE_GUIDANCE",
+              "selector_weights": list(WEIGHTS), "rounds": a.rounds, "arms": {}, "over_k1": {}, "added_ms_over_k1": {}}
+    for kind, steps in SAMPLERS:
+        for K in KS:
+            k = f"{kind}{steps}_k{K}"
+            med = statistics.median(ms[k])
+            record["arms"][k] = {"sampler": kind, "steps": steps, "candidates": K, "rows_per_step": 2 * K,
+                                 "ticks_per_window": ticks[k], "ticks": ticks[k] * a.rounds,
+                                 "ms_per_tick": [round(v, 4) for v in ms[k]], "median_ms": round(med, 4),
+                                 "min_ms": round(min(ms[k]), 4), "max_ms": round(max(ms[k]), 4),
+                                 "spread_pct": round(100 * (max(ms[k]) - min(ms[k])) / med, 2)}
+        base = record["arms"][f"{kind}{steps}_k1"]["median_ms"]
+        record["over_k1"][f"{kind}{steps}"] = {str(K): round(record["arms"][f"{kind}{steps}_k{K}"]["median_ms"] / base, 4) for K in KS}
+        record["added_ms_over_k1"][f"{kind}{steps}"] = {str(K): round(record["arms"][f"{kind}{steps}_k{K}"]["median_ms"] - base, 4)
+                                                        for K in KS}
+    print(f"one scene, H = 16, FREE guidance, {IMG[0]}x{IMG[1]} frame, graph ticks ({a.rounds} alternating rounds)", file=sys.stderr)
+    print(f"{'arm':<14}{'median ms':>10}{'min':>9}{'max':>9}{'spread %':>10}{'x K=1':>9}{'ticks':>8}", file=sys.stderr)
+    for k, v in record["arms"].items():
+        r = record["over_k1"][f"{v['sampler']}{v['steps']}"][str(v["candidates"])]
+        print(f"{k:<14}{v['median_ms']:>10.3f}{v['min_ms']:>9.3f}{v['max_ms']:>9.3f}{v['spread_pct']:>10.2f}{r:>9.4f}{v['ticks']:>8}",
+              file=sys.stderr)
+    return record
+
+
+def select_launches(n):
+    """The workload of the trace run: the selector alone, n launches per K, K ascending."""
+    import torch
+    from autonomous_driving_with_diffusion_model_amd import TrajectorySelector
+    dev = torch.device("cuda:0")
+    sel = TrajectorySelector(*WEIGHTS)
+    g = torch.Generator().manual_seed(0)
+    tgt = (torch.rand((1, 2), generator=g) * 2 - 1).to(dev)
+    for K in KS[1:]:
+        t = (torch.rand((K, 16, 7), generator=g) * 2 - 1).to(dev)
+        for _ in range(n):
+            sel(t, 1, tgt)
+        torch.cuda.synchronize()
+    print(json.dumps({"select_launches_per_k": n, "ks": list(KS[1:])}))
+
+
+def fold_trace(out_dir):
+    """{K: median / min / max us} of the select kernel from rocprofv3's per-dispatch kernel trace under out_dir."""
+    rows = []
+    for path in glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path, newline="") as f:
+            for r in csv.DictReader(f):
+                if KERNEL in r["Kernel_Name"]:
+                    rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
+    rows.sort()
+    ks = KS[1:]
+    if not rows or len(rows) % len(ks) != 0:
+        raise SystemExit(f"{len(rows)} dispatches of {KERNEL} under {out_dir}: not a whole number of blocks for K in {ks}")
+    n = len(rows) // len(ks)
+    res = {"source": "rocprofv3 --kernel-trace --stats, the selector alone, one scene, H = 16, D = 7", "launches_per_k": n, "by_k": {}}
+    for i, K in enumerate(ks):
+        us = [(e - s) / 1e3 for s, e in rows[i * n:(i + 1) * n]][n // 10:]        # the first tenth: code load, clocks
+        res["by_k"][str(K)] = {"median_us": round(statistics.median(us), 3), "min_us": round(min(us), 3), "max_us": round(max(us), 3)}
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--ticks", type=int, default=50, help="least number of ticks per window (x rounds = ticks per arm)")
+    ap.add_argument("--seconds", type=float, default=0.5, help="least length of a window")
+    ap.add_argument("--json", default=None, help="write (or, with --fold-trace, update) the record here")
+    ap.add_argument("--select-launches", type=int, default=0, help="trace workload: the selector alone, this many launches per K")
+    ap.add_argument("--fold-trace", default=None, help="directory of a rocprofv3 run over --select-launches")
+    a = ap.parse_args()
+    if a.select_launches:
+        return select_launches(a.select_launches)
+    if a.fold_trace:
+        record = {}
+        if a.json and os.path.exists(a.json):
+            with open(a.json) as f:
+                record = json.load(f)
+        record["select_kernel_us"] = fold_trace(a.fold_trace)
+    else:
+        record = measure(a)
+    print(json.dumps(record))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(record, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
