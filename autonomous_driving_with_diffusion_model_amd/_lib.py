@@ -114,6 +114,7 @@ _SIGS = {
     "adx_resnet_packed_bytes": (C.c_size_t, [vp]),
     "adx_resnet_pack": (i32, [vp, C.POINTER(vp), i32, vp, vp]),
     "adx_resnet_workspace_bytes": (C.c_size_t, [vp, i32, i32, i32]),
+    "adx_resnet_plan_describe": (i32, [vp, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32]),
     "adx_resnet_forward": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "adx_resnet_forward_u8": (i32, [vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i32, vp, vp]),
     "adx_unet_status_words": (i32, [vp]),

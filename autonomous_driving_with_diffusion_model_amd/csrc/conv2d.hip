@@ -23,8 +23,6 @@ namespace adx {
 
 constexpr int kCoutT = 64;   // output channels per workgroup (2 MFMA row blocks)
 constexpr size_t kMaxLds = 96 * 1024;
-constexpr int g_conv_cc = 16;    // channels per LDS chunk of the 8-row kernel
-constexpr int g_conv_rows = 2;   // rows per wave of the 3x3 stride-1 kernel
 
 // Software pipeline (register double buffer): the global loads of chunk i+1 (input patch + weight
 // slab) are issued before the MFMAs of chunk i and written to LDS after them, so HBM/L2 latency
@@ -389,10 +387,6 @@ int avgpool_fc_launch(const float* x, const float* fw, const float* fb, float* o
 
 namespace adx {
 
-static size_t align64f(size_t v) { return (v + 63) / 64 * 64; }
-
-static int conv_out(int h, int k, int s, int p) { return conv_out_dim(h, k, s, p); }
-
 static int conv2d_launch(const ConvSpec& L, const float* base, const float* x, const float* res, float* y, int N, int H,
                          int W, int relu, hipStream_t s, int fmt = 0) {
   return conv2d_launch_raw(L, x, base + L.o_w, base + L.o_scale, base + L.o_shift, res, y, N, H, W, relu, s, nullptr, 0, nullptr, 0,
@@ -428,7 +422,7 @@ int conv2d_launch_raw(const ConvSpec& L, const float* x, const float* w, const f
   a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.y = y; a.x_amax = x_amax; a.x_amax_n = x_amax_n;
   a.w_ds = nullptr; a.scale_ds = nullptr; a.shift_ds = nullptr; a.y_ds = nullptr;
   a.N = N; a.Cin = L.cin; a.H = H; a.W = W; a.Cout = L.cout;
-  a.OH = conv_out(H, L.k, L.stride, L.pad); a.OW = conv_out(W, L.k, L.stride, L.pad);
+  a.OH = conv_out_dim(H, L.k, L.stride, L.pad); a.OW = conv_out_dim(W, L.k, L.stride, L.pad);
   a.KH = L.k; a.KW = L.k; a.stride = L.stride; a.pad = L.pad; a.relu = relu;
   a.cin_pad = L.cin_pad; a.cc = L.cc;
   a.x_u8 = nullptr;
@@ -472,33 +466,28 @@ int conv2d_launch_raw(const ConvSpec& L, const float* x, const float* w, const f
     }
     return conv2d_hs_launch(L, a, s, &plan);
   }
-  const int rows = (L.stride == 1 && L.k == 3 && g_conv_rows == 2) ? 2 : 1;   // 8-row tiles for the 3x3 stride-1 convs
+  const int rows = (L.stride == 1 && L.k == 3) ? 2 : 1;   // 8-row tiles for the 3x3 stride-1 convs
   const int th = 4 * rows;
   a.tiles_x = ceil_div(a.OW, kTileW); a.tiles_y = ceil_div(a.OH, th); a.cout_tiles = L.cout / kCoutT;
   a.PH = (th - 1) * L.stride + L.k; a.PW = (kTileW - 1) * L.stride + L.k;
   a.PWp = a.PW;
   ADX_REQUIRE(L.cin % L.cc == 0 || L.cin < L.cc, "conv2d: cin %d must be < %d or a multiple of it", L.cin, L.cc);
   ADX_REQUIRE((size_t)L.cin * H * W < (1u << 31), "conv2d: image plane too large for 32-bit gather offsets");
-  const int cch = (rows == 2 && g_conv_cc == 8) ? 8 : a.cc;   // channels staged per chunk
-  const size_t np = (size_t)cch * a.PH * a.PW;
-  const size_t lds = sizeof(float) * ((np + 255) / 256 * 256 + (size_t)L.k * L.k * cch * kCoutT + 2 * kCoutT);
+  const size_t np = (size_t)a.cc * a.PH * a.PW;
+  const size_t lds = sizeof(float) * ((np + 255) / 256 * 256 + (size_t)L.k * L.k * a.cc * kCoutT + 2 * kCoutT);
   ADX_REQUIRE(lds <= kMaxLds, "conv2d: LDS %zu bytes too large", lds);
   const size_t grid = (size_t)a.cout_tiles * a.tiles_x * a.tiles_y * N;
   ADX_REQUIRE(grid < (1u << 31), "conv2d: grid too large");
   static std::atomic<uint64_t> attr_set{0};  // dynamic LDS above 64 KB must be opted into once per kernel
   if (DeviceOnce once{attr_set}; once) {
-    const void* fns[6] = {reinterpret_cast<const void*>(&conv2d_kernel<1, 3, 1>), reinterpret_cast<const void*>(&conv2d_kernel<2, 3, 1>),
+    const void* fns[5] = {reinterpret_cast<const void*>(&conv2d_kernel<1, 3, 2>), reinterpret_cast<const void*>(&conv2d_kernel<2, 3, 1>),
                           reinterpret_cast<const void*>(&conv2d_kernel<2, 1, 1>), reinterpret_cast<const void*>(&conv2d_kernel<2, 7, 1>),
-                          reinterpret_cast<const void*>(&conv2d_kernel<1, 1, 1>), reinterpret_cast<const void*>(&conv2d_kernel<1, 3, 2>)};
-    ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_kernel<1, 3, 2, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
+                          reinterpret_cast<const void*>(&conv2d_kernel<1, 1, 1>)};
     for (const void* f : fns) ADX_CHECK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
     once.commit();
   }
   const dim3 g((unsigned)grid), blk(256);
-  if (L.stride == 1 && L.k == 3 && rows == 2 && cch == 8) conv2d_kernel<1, 3, 2, 8><<<g, blk, lds, s>>>(a);
-  else if (L.stride == 1 && L.k == 3 && rows == 2) conv2d_kernel<1, 3, 2><<<g, blk, lds, s>>>(a);
-  else if (L.stride == 1 && L.k == 3) conv2d_kernel<1, 3, 1><<<g, blk, lds, s>>>(a);
+  if (L.stride == 1 && L.k == 3) conv2d_kernel<1, 3, 2><<<g, blk, lds, s>>>(a);
   else if (L.stride == 2 && L.k == 3) conv2d_kernel<2, 3, 1><<<g, blk, lds, s>>>(a);
   else if (L.stride == 2 && L.k == 1) conv2d_kernel<2, 1, 1><<<g, blk, lds, s>>>(a);
   else if (L.stride == 2 && L.k == 7) conv2d_kernel<2, 7, 1><<<g, blk, lds, s>>>(a);
@@ -636,9 +625,9 @@ int adx_resnet_create(int32_t out_dim, adx_resnet** out) {
     L.cc = cin >= 16 ? 16 : 4;
     L.cin_pad = round_up(cin, L.cc);
     L.fuse_with = -1;
-    L.o_w = off; off = align64f(off + (conv2d_hs_eligible(L) ? conv2d_packed_floats(L) : (size_t)k * k * L.cin_pad * cout));
-    L.o_scale = off; off = align64f(off + cout);
-    L.o_shift = off; off = align64f(off + cout);
+    L.o_w = off; off = al64(off + (conv2d_hs_eligible(L) ? conv2d_packed_floats(L) : (size_t)k * k * L.cin_pad * cout));
+    L.o_scale = off; off = al64(off + cout);
+    L.o_shift = off; off = al64(off + cout);
     r->convs.push_back(L);
   };
   add(3, 64, 7, 2, 3);
@@ -659,8 +648,8 @@ int adx_resnet_create(int32_t out_dim, adx_resnet** out) {
     }
   r->t_fcw = t++; r->t_fcb = t++;
   r->n_tensors = t;
-  r->o_fcw = off; off = align64f(off + (size_t)out_dim * 512);
-  r->o_fcb = off; off = align64f(off + out_dim);
+  r->o_fcw = off; off = al64(off + (size_t)out_dim * 512);
+  r->o_fcb = off; off = al64(off + out_dim);
   r->packed_floats = off;
   *out = r;
   return ADX_OK;
@@ -728,18 +717,202 @@ int adx_resnet_pack(adx_resnet* r, const float* const* T, int32_t n, void* packe
 }
 
 // workspace: the stem output, then three rotating buffers sized for the post-maxpool map
-static void resnet_dims(int h, int w, int* h1, int* w1, int* h2, int* w2) {
-  *h1 = conv_out(h, 7, 2, 3); *w1 = conv_out(w, 7, 2, 3);
-  *h2 = conv_out(*h1, 3, 2, 1); *w2 = conv_out(*w1, 3, 2, 1);
+extern "C++" ResnetLayout adx::resnet_layout(int batch, int h, int w) {
+  ResnetLayout l;
+  l.h1 = conv_out_dim(h, 7, 2, 3); l.w1 = conv_out_dim(w, 7, 2, 3);
+  l.h2 = conv_out_dim(l.h1, 3, 2, 1); l.w2 = conv_out_dim(l.w1, 3, 2, 1);
+  l.stem = al64((size_t)batch * 64 * l.h1 * l.w1);
+  l.act = al64((size_t)batch * 64 * l.h2 * l.w2);
+  return l;
 }
 
 size_t adx_resnet_workspace_bytes(const adx_resnet* r, int32_t batch, int32_t h, int32_t w) {
   if (!r || batch < 1 || h < 32 || w < 32) return 0;
-  int h1, w1, h2, w2;
-  resnet_dims(h, w, &h1, &w1, &h2, &w2);
-  const size_t stem = align64f((size_t)batch * 64 * h1 * w1);
-  const size_t act = align64f((size_t)batch * 64 * h2 * w2);
-  return (stem + 3 * act) * sizeof(float);
+  return resnet_layout(batch, h, w).floats() * sizeof(float);
+}
+
+// The plan of one eval forward (conv2d_internal.h states the format rule).
+// Sub-batches on streams of their own (round 5).  A launch of the pipelined 3x3 kernels is one workgroup per CU and tile, and at
+// B = 64 the tile counts are 1.8 (256 channels) / 3.6 (128) / 0.94 (512) times the 256 CUs: the last round of every launch leaves
+// 6-10 % of the chip idle and the next launch cannot start before it ends.  Two half batches are two independent chains of
+// launches: while one's last workgroups run, the other's fill the idle CUs (a second workgroup of these kernels does not fit
+// a CU, so the co-scheduled kernel gets exactly the idle ones).  Same kernels, same per-image arithmetic: the features are bit
+// for bit those of the single-stream pass wherever the tile modes agree.  Weights are read once per sub-batch instead of once.
+// (Running stem, layer1 and layer2's first block in batch chunks of 16, so that a 59 MB activation is still in the 256 MB
+// Infinity Cache when the next launch reads it, was measured: layer1's convs already find most of their input there at
+// B = 64 -- inside a pass they take 0.20 ms where the same launch repeated on fixed buffers takes 0.25 -- and the chunked
+// stem launch has too few workgroups: +-1 % end to end for 2..4 chunks, -13 % for 8.  Not kept.)
+extern "C++" int adx::resnet_eval_plan(const adx_resnet& r, const ResnetEvalQuery& q, ResnetEvalPlan* plan, const DebugSwitches& sw) {
+  const int nblocks = (int)r.block_has_ds.size();
+  ADX_REQUIRE(q.batch >= 1 && q.h >= 32 && q.w >= 32, "adx_resnet_forward: image %dx%d (batch %d) too small", q.h, q.w, q.batch);
+  ADX_REQUIRE(!r.convs.empty() && nblocks <= kResnetMaxBlocks, "adx_resnet_forward: %d BasicBlocks, the plan holds %d", nblocks, kResnetMaxBlocks);
+  // the stem + max-pool run as one launch wherever the split-fp16 stem kernel exists; the unpooled stem map is never written then
+  // and its region is the split-reduction scratch of the convs, one slice per sub-batch
+  const bool stem_fused = conv2d_hs_eligible(r.convs[0], sw);
+  ADX_REQUIRE(stem_fused || !q.u8,
+              "adx_resnet_forward_u8: the uint8 front-end lives in the split-fp16 stem kernel (unavailable with ADX_CONV_EXACT=1)");
+  ResnetEvalPlan& p = *plan;
+  p = ResnetEvalPlan{};
+  p.lay = resnet_layout(q.batch, q.h, q.w);
+  // not inside a stream capture: a replayed graph with the forked branches measured 2 % SLOWER per tick than the single chain
+  // (profiles/README.md, round 5), and streams are not created while capturing
+  if (q.batch >= 32 && !sw.check_range && stem_fused && !q.capturing) {
+    p.nsub = std::min(sw.resnet_streams, adx_resnet::kMaxSub);
+    while (p.nsub > 1 && q.batch / p.nsub < 16) --p.nsub;
+  }
+  // The stem and the first layer (the blocks in front of the first downsample block) run as ONE chain on the whole batch, the fork
+  // comes behind them: their launches are thousands of two-per-CU workgroups whose last round hardly matters, and split they
+  // only stream their operands twice (-1.6 % per faithful step, profiles/README.md).  Only blocks of the FIRST layer: their maps
+  // have the pooled map's per-image size, so the whole-batch tensors they leave are laid out exactly like the sub-batches'
+  // regions.  ADX_RESNET_SPLIT_FROM=<block> can only shorten the prefix.
+  if (p.nsub > 1) {
+    while (p.first_split < nblocks && !r.block_has_ds[p.first_split]) ++p.first_split;
+    if (sw.resnet_split_from >= 0) p.first_split = std::min(sw.resnet_split_from, p.first_split);
+  }
+  int c1_of[kResnetMaxBlocks + 1];          // index of block b's conv1 in r.convs (conv2 and the downsample follow it)
+  c1_of[0] = 1;
+  for (int b = 0; b < nblocks; ++b) c1_of[b + 1] = c1_of[b] + 2 + (r.block_has_ds[b] ? 1 : 0);
+
+  auto plain = [&](const ConvSpec& c, int nf, int H, int W) {
+    Hs3x3Query hq;
+    hq.N = nf; hq.H = H; hq.W = W; hq.fmt = kFmtXCells | kFmtYCells;
+    return conv2d_hs3x3_plan(c, hq, sw).admitted;
+  };
+  auto fuses = [&](int b) { return r.block_has_ds[b] && resnet_fuses_ds(r.convs[c1_of[b]], r.convs[c1_of[b] + 2], sw); };
+  auto reads_cells = [&](int b, int nf, int H, int W) {       // block b on an input map of H x W
+    const ConvSpec& c1 = r.convs[c1_of[b]];
+    if (r.block_has_ds[b]) return fuses(b);
+    return c1.stride == 1 && plain(c1, nf, H, W) && plain(r.convs[c1_of[b] + 1], nf, H, W);
+  };
+  struct Edge { int buf, H, W; bool cells; };
+  // the stem (g.stem) and blocks [b0, b1) of one segment, from the edge `at` on; leaves the edge it ends with
+  auto chain = [&](ResnetSegment& g, int b0, int b1, Edge& at) -> int {
+    if (g.stem) at = Edge{0, p.lay.h2, p.lay.w2, false};
+    bool reads = b0 < nblocks && reads_cells(b0, g.nf, at.H, at.W);     // of the block at hand, asked once: as its producer's reader
+    if (g.stem) {
+      g.stem_fused = stem_fused;
+      at.cells = g.pooled_cells = stem_fused && reads;
+    }
+    for (int b = b0; b < b1; ++b) {
+      ResnetBlockStep& t = g.steps[g.nsteps++];
+      const ConvSpec& c1 = r.convs[c1_of[b]];
+      const ConvSpec& c2 = r.convs[c1_of[b] + 1];
+      const bool has_ds = r.block_has_ds[b] != 0;
+      t.block = b; t.c1 = c1_of[b]; t.status = 1 + b;
+      t.H = at.H; t.W = at.W;
+      t.OH = conv_out_dim(t.H, 3, c1.stride, 1); t.OW = conv_out_dim(t.W, 3, c1.stride, 1);
+      t.fused_ds = fuses(b);
+      // With a downsample the identity lives in the third buffer and the result overwrites the block's input (dead by then)
+      t.in = at.buf; t.mid = (at.buf + 1) % 3;
+      t.id = has_ds ? (at.buf + 2) % 3 : at.buf;
+      t.out = has_ds ? at.buf : (at.buf + 2) % 3;
+      const bool c2_plain = plain(c2, g.nf, t.OH, t.OW), next_reads = b + 1 < nblocks && reads_cells(b + 1, g.nf, t.OH, t.OW);
+      t.in_cells = at.cells;              // the producer's decision
+      t.mid_cells = t.fused_ds ? c2_plain : (!has_ds && reads);
+      t.id_cells = has_ds ? (t.fused_ds && t.mid_cells) : t.in_cells;
+      t.out_cells = c2_plain && (b + 1 == nblocks || next_reads);
+      // every cell operand has a reader of cells: the block itself (its input), and whoever reads conv2's output when conv2 reads any
+      ADX_REQUIRE((!t.in_cells || reads) && (t.out_cells || !(t.mid_cells || t.id_cells)),
+                  "adx_resnet_forward: internal error (cell-layout input of a launch that cannot read it): BasicBlock %d at batch %d of %d", b,
+                  g.nf, q.batch);
+      at = Edge{t.out, t.OH, t.OW, t.out_cells};
+      reads = next_reads;
+    }
+    g.final_buf = at.buf; g.final_h = at.H; g.final_w = at.W; g.final_cells = at.cells;
+    return ADX_OK;
+  };
+
+  const size_t scratch_per = stem_fused ? ((size_t)q.batch * 64 * p.lay.h1 * p.lay.w1 / p.nsub) & ~(size_t)63 : 0;
+  Edge whole{};
+  if (p.first_split > 0) {
+    ResnetSegment& g = p.seg[p.nseg++];
+    g.id = 0; g.n0 = 0; g.n = g.nf = q.batch; g.stream = 0;
+    g.scratch_off = 0; g.scratch_floats = scratch_per;       // (sub-batch 0's slice: it starts behind the prefix on the same stream)
+    g.stem = true;
+    const int rc = chain(g, 0, p.first_split, whole);
+    if (rc != ADX_OK) return rc;
+  }
+  // a sub-batch owns the SAME region of every rotating buffer at every layer (its first image's slot of the largest map, the
+  // pooled one; the images of a layer are packed from there): sub-batches run on streams of their own and are at different
+  // layers at the same time, so a region that moved with the layer's per-image size would overlap another sub-batch's
+  for (int k = 0, n0 = 0; k < p.nsub; ++k) {
+    ResnetSegment& g = p.seg[p.nseg++];
+    g.id = 1 + k; g.n0 = n0; g.n = g.nf = q.batch / p.nsub + (k < q.batch % p.nsub ? 1 : 0); g.stream = k;
+    n0 += g.n;
+    g.scratch_off = (size_t)k * scratch_per; g.scratch_floats = scratch_per;
+    g.stem = p.first_split == 0;
+    Edge at = whole;
+    const int rc = chain(g, p.first_split, nblocks, at);
+    if (rc != ADX_OK) return rc;
+  }
+  return ADX_OK;
+}
+
+// Calls f(segment, i) for every step of segments seg[0 .. n) in issue order -- i = -1: the stem, 0 .. nsteps - 1: a block step,
+// nsteps: the average pool + fc (sub-batches only) -- until one fails: layer by layer, alternating between the segments, so
+// that every stream's queue has work early.  A forward is the prefix (if any) on its own, the fork, then the sub-batches together.
+extern "C++" template <class F>
+static int resnet_plan_each(const ResnetSegment* seg, int n, F&& f) {
+  int rc = ADX_OK;
+  for (int k = 0; k < n && rc == ADX_OK && seg[k].stem; ++k) rc = f(seg[k], -1);
+  for (int i = 0; n > 0 && i < seg[0].nsteps + (seg[0].id > 0 ? 1 : 0); ++i)
+    for (int k = 0; k < n && rc == ADX_OK; ++k) rc = f(seg[k], i);
+  return rc;
+}
+
+int adx_resnet_plan_describe(const adx_resnet* r, int32_t batch, int32_t h, int32_t w, int32_t flags, int32_t* n_records, int32_t* ints,
+                             int32_t max_records) {
+  ADX_REQUIRE(r && n_records && ints, "adx_resnet_plan_describe: null argument");
+  ADX_REQUIRE((flags & ~ADX_RESNET_PLAN_CAPTURING) == 0 && max_records >= 1, "adx_resnet_plan_describe: flags 0x%x, max_records %d",
+              (unsigned)flags, max_records);
+  ResnetEvalQuery q;
+  q.batch = batch; q.h = h; q.w = w; q.capturing = (flags & ADX_RESNET_PLAN_CAPTURING) != 0;
+  ResnetEvalPlan p;
+  int rc = resnet_eval_plan(*r, q, &p);
+  if (rc != ADX_OK) return rc;
+  const ResnetLayout& lay = p.lay;
+  int n = 0;
+  // one launch: kind, block, conv, input map, output map, channels, kFmt* bits, buffers of x / residual / y / second output
+  auto put = [&](const ResnetSegment& g, int kind, int block, int conv, int H, int W, int OH, int OW, int cin, int cout, int fmt, int x, int res,
+                 int y, int y2, int status) {
+    if (n < max_records) {
+      const int32_t rec[ADX_RESNET_PLAN_INTS] = {g.id, g.stream, g.n0, g.n, g.nf, kind, block, conv, H, W, OH, OW, cin, cout, fmt, x, res, y, y2,
+                                                 (int32_t)(g.scratch_off / 64), (int32_t)(g.scratch_floats / 64), status, p.nsub, p.first_split};
+      memcpy(ints + (size_t)n * ADX_RESNET_PLAN_INTS, rec, sizeof(rec));
+    }
+    ++n;
+  };
+  auto record = [&](const ResnetSegment& g, int i) -> int {
+    if (i < 0) {
+      if (g.stem_fused) {
+        put(g, ADX_RESNET_PLAN_STEM_POOL, -1, -1, h, w, lay.h2, lay.w2, 3, 64, g.pooled_cells ? kFmtYCells : 0, -1, -1, 0, -1, 0);
+      } else {
+        put(g, ADX_RESNET_PLAN_STEM, -1, -1, h, w, lay.h1, lay.w1, 3, 64, 0, -1, -1, kResnetBufStem, -1, 0);
+        put(g, ADX_RESNET_PLAN_MAXPOOL, -1, -1, lay.h1, lay.w1, lay.h2, lay.w2, 64, 64, 0, kResnetBufStem, -1, 0, -1, 0);
+      }
+    } else if (i == g.nsteps) {
+      put(g, ADX_RESNET_PLAN_AVGPOOL_FC, -1, -1, g.final_h, g.final_w, 1, 1, 512, r->out_dim, g.final_cells ? kFmtXCells : 0, g.final_buf, -1, -1,
+          -1, 1 + (int)r->block_has_ds.size());
+    } else {
+      const ResnetBlockStep& t = g.steps[i];
+      const ConvSpec& c1 = r->convs[t.c1];
+      const int fmt1 = (t.in_cells ? kFmtXCells : 0) | (t.mid_cells ? kFmtYCells : 0);
+      if (t.fused_ds) {
+        put(g, ADX_RESNET_PLAN_ENTRY, t.block, 0, t.H, t.W, t.OH, t.OW, c1.cin, c1.cout, fmt1, t.in, -1, t.mid, t.id, t.status);
+      } else {
+        put(g, ADX_RESNET_PLAN_CONV, t.block, 0, t.H, t.W, t.OH, t.OW, c1.cin, c1.cout, fmt1, t.in, -1, t.mid, -1, t.status);
+        if (r->block_has_ds[t.block]) put(g, ADX_RESNET_PLAN_CONV, t.block, 2, t.H, t.W, t.OH, t.OW, c1.cin, c1.cout, 0, t.in, -1, t.id, -1, t.status);
+      }
+      put(g, ADX_RESNET_PLAN_CONV, t.block, 1, t.OH, t.OW, t.OH, t.OW, c1.cout, c1.cout,
+          (t.mid_cells ? kFmtXCells : 0) | (t.out_cells ? kFmtYCells : 0) | (t.id_cells ? kFmtResCells : 0), t.mid, t.id, t.out, -1, t.status);
+    }
+    return ADX_OK;
+  };
+  (void)resnet_plan_each(p.seg, p.nseg - p.nsub, record);
+  (void)resnet_plan_each(p.seg + p.nseg - p.nsub, p.nsub, record);
+  *n_records = n;
+  ADX_REQUIRE(n <= max_records, "adx_resnet_plan_describe: %d launches, room for %d", n, max_records);
+  return ADX_OK;
 }
 
 static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspace, const float* img,
@@ -755,8 +928,6 @@ int adx_resnet_forward(adx_resnet* r, const void* packed, void* workspace, const
 int adx_resnet_forward_u8(adx_resnet* r, const void* packed, void* workspace, const uint8_t* frames_hwc, const float* mean,
                           const float* stdv, int32_t batch, int32_t h, int32_t w, float* feature, adx_stream stream) {
   ADX_REQUIRE(frames_hwc && mean && stdv, "adx_resnet_forward_u8: null frames / mean / std");
-  ADX_REQUIRE(r != nullptr && !r->convs.empty() && conv2d_hs_eligible(r->convs[0]),
-              "adx_resnet_forward_u8: the uint8 front-end lives in the split-fp16 stem kernel (unavailable with ADX_CONV_EXACT=1)");
   return resnet_forward_impl(r, packed, workspace, nullptr, frames_hwc, mean, stdv, batch, h, w, feature, stream);
 }
 
@@ -793,6 +964,7 @@ extern "C++" int adx::conv2d_range_check(const char* what, int index, const floa
   return ADX_OK;
 }
 
+// Carries out resnet_eval_plan: every decision between the fork and the join is the plan's.
 static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspace, const float* img,
                                const uint8_t* frames_u8, const float* mean, const float* stdv, int32_t batch, int32_t h,
                                int32_t w, float* feature, adx_stream stream) {
@@ -801,227 +973,121 @@ static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspac
     set_error("adx_resnet_forward: weights were never packed (call adx_resnet_pack first)");
     return ADX_ERR_STATE;
   }
-  ADX_REQUIRE(batch >= 1 && h >= 32 && w >= 32, "adx_resnet_forward: image %dx%d (batch %d) too small", h, w, batch);
   hipStream_t s = (hipStream_t)stream;
-  const float* base = (const float*)packed;
-  int h1, w1, h2, w2;
-  resnet_dims(h, w, &h1, &w1, &h2, &w2);
-  float* ws = (float*)workspace;
-  float* stem = ws;
-  const size_t act = align64f((size_t)batch * 64 * h2 * w2);
-  float* buf[3];
-  buf[0] = ws + align64f((size_t)batch * 64 * h1 * w1);
-  buf[1] = buf[0] + act;
-  buf[2] = buf[1] + act;
-
-  struct ScratchScope {     // split-reduction scratch of the 3x3 convs of THIS call
-    void set(float* p, size_t n) { conv2d_set_split_scratch(p, n); }
-    ~ScratchScope() { conv2d_set_split_scratch(nullptr, 0); }
-  } scratch_scope;
-  const size_t nblocks = r->block_has_ds.size();
-  uint32_t* const words = r->status;       // range status (adx_resnet_set_status): [0] stem, [1 + b] block b, [1 + nblocks] fc
-  StatusScope status_scope(words);
-
-  struct Cursor { size_t ci; int cur, H, W; bool cells; };
-  constexpr int fuse = 1;         // stem + max-pool as one launch (0: two launches, the round-1 form)
-
-  // stem (+ pool) of images [n0, n0 + n)
-  auto run_stem = [&](Cursor& st, int n0, int n, int nf, hipStream_t s) -> int {
-    const ConvSpec& c0 = r->convs[0];
-    const float* im = img != nullptr ? img + (size_t)n0 * 3 * h * w : nullptr;
-    const uint8_t* fr = frames_u8 != nullptr ? frames_u8 + (size_t)n0 * 3 * h * w : nullptr;
-    status_scope.set(words);
-    float* pooled = buf[0] + (size_t)n0 * 64 * h2 * w2;
-    bool pooled_cells = false;
-    int rc;
-    if ((fuse || frames_u8 != nullptr) && conv2d_hs_eligible(c0)) {
-      // (the unpooled stem map is never written on this path: its region is the split-reduction scratch of this sub-batch's convs)
-      // the pooled map's readers are layer1's first block: conv1 (input) and conv2 (residual); cells if both read cells
-      pooled_cells = nblocks > 0 && !r->block_has_ds[0] && r->convs[1].stride == 1 && conv2d_hs3x3_plain(r->convs[1], nf, h2, w2) &&
-                     conv2d_hs3x3_plain(r->convs[2], nf, h2, w2);
-      rc = conv2d_hs_stem_pool(c0, im, base + c0.o_w, base + c0.o_scale, base + c0.o_shift, pooled, n, h, w, s, fr, mean, stdv,
-                               pooled_cells);
-      if (rc != ADX_OK) return rc;
-    } else {
-      float* sm = stem + (size_t)n0 * 64 * h1 * w1;
-      rc = conv2d_launch(c0, base, im, nullptr, sm, n, h, w, 1, s);
-      if (rc != ADX_OK) return rc;
-      rc = maxpool_launch(sm, pooled, n * 64, h1, w1, h2, w2, s);
-      if (rc != ADX_OK) return rc;
-    }
-    st = Cursor{1, 0, h2, w2, pooled_cells};
-    return conv2d_range_check("the stem (conv1 + bn1 + relu + maxpool), tensor", 0, pooled, (size_t)n * 64 * h2 * w2, pooled_cells, s);
-  };
-
-  // Activation formats (conv2d_hs.hip: XCELLS).  Where a layer's 3x3 stride-1 convs run as plain launches of the pipelined
-  // kernel, everything from the first one's output to the last one's is a CELL tensor (same bytes, same buffers): the next
-  // layer's fused stride-2 launch reads AND writes cells (both of its outputs), the fused stem + pool launch writes them and
-  // the average pool reads them.  What stays fp32 NCHW: all of a layer whose launches split their reduction (small batches)
-  // -- and the pooled stem map then.
-  // One BasicBlock for images [n0, n0 + n); nf = the batch the format decisions are made for.
-  auto run_block = [&](size_t b, Cursor& st, int n0, int n, int nf, hipStream_t s) -> int {
-    size_t ci = st.ci;
-    const int cur = st.cur, H = st.H, W = st.W;
-    const bool cur_cells = st.cells;
-    status_scope.set(words != nullptr ? words + 1 + b : nullptr);
-    const ConvSpec& c1 = r->convs[ci++];
-    const ConvSpec& c2 = r->convs[ci++];
-    const int mid = (cur + 1) % 3, outb = (cur + 2) % 3;
-    const int OH = conv_out(H, 3, c1.stride, 1), OW = conv_out(W, 3, c1.stride, 1);
-    // a sub-batch owns the SAME region of every rotating buffer at every layer (its first image's slot of the largest map, the
-    // pooled one; the images of a layer are packed from there): sub-batches run on streams of their own and are at different
-    // layers at the same time, so a region that moved with the layer's per-image size would overlap another sub-batch's
-    const size_t off_in = (size_t)n0 * 64 * h2 * w2, off_out = off_in;
-    const float* xin = buf[cur] + off_in;
-    const float* identity = xin;
-    bool id_cells = cur_cells, mid_cells = false;
-    const bool c2_plain = conv2d_hs3x3_plain(c2, nf, OH, OW);
-    int rc;
-    if (r->block_has_ds[b] && resnet_fuses_ds(c1, r->convs[ci + 0])) {
-      const ConvSpec& ds = r->convs[ci++];
-      mid_cells = c2_plain;            // conv2 reads conv1's output and the downsample's (its residual): cells if it can
-      rc = conv2d_hs_launch_block_s2(c1, ds, xin, base + c1.o_w, base + c1.o_scale, base + c1.o_shift, buf[mid] + off_out,
-                                     base + ds.o_w, base + ds.o_scale, base + ds.o_shift, buf[outb] + off_out, n, H, W, s, cur_cells,
-                                     mid_cells);
-      if (rc != ADX_OK) return rc;
-      identity = buf[outb] + off_out;
-      id_cells = mid_cells;
-    } else {
-      const bool c1_plain = c1.stride == 1 && conv2d_hs3x3_plain(c1, nf, H, W);
-      ADX_REQUIRE(!cur_cells || c1_plain, "adx_resnet_forward: internal error (cell-layout input of a launch that cannot read it)");
-      mid_cells = c1_plain && c2_plain && !r->block_has_ds[b];
-      rc = conv2d_launch(c1, base, xin, nullptr, buf[mid] + off_out, n, H, W, 1, s,            // conv1 + bn1 + relu
-                         (cur_cells ? kFmtXCells : 0) | (mid_cells ? kFmtYCells : 0));
-      if (rc != ADX_OK) return rc;
-      if (r->block_has_ds[b]) {
-        const ConvSpec& ds = r->convs[ci++];
-        ADX_REQUIRE(!cur_cells, "adx_resnet_forward: internal error (cell-layout input of the downsample conv)");
-        rc = conv2d_launch(ds, base, xin, nullptr, buf[outb] + off_out, n, H, W, 0, s);  // downsample conv + bn
-        if (rc != ADX_OK) return rc;
-        identity = buf[outb] + off_out;
-        id_cells = false;
-      }
-    }
-    // conv2 + bn2 + identity + relu.  With a downsample the identity lives in buf[outb] and the result
-    // overwrites buf[cur] (the block input is dead by then); otherwise the result goes to buf[outb].
-    float* dst = (r->block_has_ds[b] ? buf[cur] : buf[outb]) + off_out;
-    // the block output is a cell tensor when conv2 is a plain launch and whoever reads it reads cells: the next block's plain
-    // conv1 + conv2 (as input and as residual), the next layer's fused stride-2 launch, or the average pool
-    bool out_cells = false;
-    if (c2_plain) {
-      if (b + 1 == nblocks) {
-        out_cells = true;
-      } else if (r->block_has_ds[b + 1]) {
-        out_cells = resnet_fuses_ds(r->convs[ci], r->convs[ci + 2]);
-      } else {
-        out_cells = r->convs[ci].stride == 1 && conv2d_hs3x3_plain(r->convs[ci], nf, OH, OW) &&
-                    conv2d_hs3x3_plain(r->convs[ci + 1], nf, OH, OW);
-      }
-    }
-    ADX_REQUIRE(out_cells || !(mid_cells || id_cells),
-                "adx_resnet_forward: internal error (a conv with cell-layout operands whose reader wants fp32)");
-    rc = conv2d_range_check("conv1 + bn1 + relu of BasicBlock", (int)b, buf[mid] + off_out, (size_t)n * c1.cout * OH * OW, mid_cells, s);
-    if (rc != ADX_OK) return rc;
-    rc = conv2d_launch(c2, base, buf[mid] + off_out, identity, dst, n, OH, OW, 1, s,
-                       (mid_cells ? kFmtXCells : 0) | (out_cells ? kFmtYCells : 0) | (id_cells ? kFmtResCells : 0));
-    if (rc != ADX_OK) return rc;
-    rc = conv2d_range_check("the output of BasicBlock", (int)b, dst, (size_t)n * c2.cout * OH * OW, out_cells, s);
-    if (rc != ADX_OK) return rc;
-    st = Cursor{ci, r->block_has_ds[b] ? cur : outb, OH, OW, out_cells};
-    return ADX_OK;
-  };
-
-  // (Running stem, layer1 and layer2's first block in batch chunks of 16, so that a 59 MB activation is still in the 256 MB
-  // Infinity Cache when the next launch reads it, was measured: layer1's convs already find most of their input there at
-  // B = 64 -- inside a pass they take 0.20 ms where the same launch repeated on fixed buffers takes 0.25 -- and the chunked
-  // stem launch has too few workgroups: +-1 % end to end for 2..4 chunks, -13 % for 8.  Not kept.)
-  // Sub-batches on streams of their own (round 5).  A launch of the pipelined 3x3 kernels is one workgroup per CU and tile, and at
-  // B = 64 the tile counts are 1.8 (256 channels) / 3.6 (128) / 0.94 (512) times the 256 CUs: the last round of every launch leaves
-  // 6-10 % of the chip idle and the next launch cannot start before it ends.  Two half batches are two independent chains of
-  // launches: while one's last workgroups run, the other's fill the idle CUs (a second workgroup of these kernels does not fit
-  // a CU, so the co-scheduled kernel gets exactly the idle ones).  Same kernels, same per-image arithmetic: the features are bit
-  // for bit those of the single-stream pass wherever the tile modes agree.  Weights are read once per sub-batch instead of once.
-  constexpr int kMaxSub = adx_resnet::kMaxSub;
-  int nsub = 1;
-  if (batch >= 32 && !debug_switches().check_range && fuse && conv2d_hs_eligible(r->convs[0])) {
-    nsub = std::min(debug_switches().resnet_streams, kMaxSub);
-    while (nsub > 1 && batch / nsub < 16) --nsub;
-  }
-  if (nsub > 1) {
-    // not inside a stream capture: a replayed graph with the forked branches measured 2 % SLOWER per tick than the single chain
-    // (profiles/README.md, round 5), and streams are not created while capturing
+  ResnetEvalQuery q;
+  q.batch = batch; q.h = h; q.w = w; q.u8 = frames_u8 != nullptr;
+  ResnetEvalPlan plan;
+  int rc = resnet_eval_plan(*r, q, &plan);
+  if (rc == ADX_OK && plan.nsub > 1) {      // (only a pass that would fork asks the runtime)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) nsub = 1;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+      q.capturing = true;
+      rc = resnet_eval_plan(*r, q, &plan);
+    }
   }
+  if (rc != ADX_OK) return rc;
+  const int nsub = plan.nsub;
   if (nsub > 1) {
     int dev = 0;
     ADX_CHECK_HIP(hipGetDevice(&dev));
     if (r->side_device != dev || r->side[nsub - 2] == nullptr) {
-      {
-        if (r->side_device != dev) {
-          // the handle moved to another device (module.to(other_gpu)): streams AND events belong to the device they were
-          // created on -- recording an old event on a new stream fails -- so all of them are recreated here
-          for (auto& st : r->side) if (st != nullptr) { (void)hipStreamDestroy(st); st = nullptr; }
-          if (r->ev_fork != nullptr) { (void)hipEventDestroy(r->ev_fork); r->ev_fork = nullptr; }
-          for (auto& ev : r->ev_join) if (ev != nullptr) { (void)hipEventDestroy(ev); ev = nullptr; }
-          r->side_device = dev;
-        }
-        if (r->ev_fork == nullptr) ADX_CHECK_HIP(hipEventCreateWithFlags(&r->ev_fork, hipEventDisableTiming));
-        for (int k = 0; k < nsub - 1; ++k) {
-          if (r->side[k] == nullptr) ADX_CHECK_HIP(hipStreamCreateWithFlags(&r->side[k], hipStreamNonBlocking));
-          if (r->ev_join[k] == nullptr) ADX_CHECK_HIP(hipEventCreateWithFlags(&r->ev_join[k], hipEventDisableTiming));
-        }
+      if (r->side_device != dev) {
+        // the handle moved to another device (module.to(other_gpu)): streams AND events belong to the device they were
+        // created on -- recording an old event on a new stream fails -- so all of them are recreated here
+        for (auto& st : r->side) if (st != nullptr) { (void)hipStreamDestroy(st); st = nullptr; }
+        if (r->ev_fork != nullptr) { (void)hipEventDestroy(r->ev_fork); r->ev_fork = nullptr; }
+        for (auto& ev : r->ev_join) if (ev != nullptr) { (void)hipEventDestroy(ev); ev = nullptr; }
+        r->side_device = dev;
+      }
+      if (r->ev_fork == nullptr) ADX_CHECK_HIP(hipEventCreateWithFlags(&r->ev_fork, hipEventDisableTiming));
+      for (int k = 0; k < nsub - 1; ++k) {
+        if (r->side[k] == nullptr) ADX_CHECK_HIP(hipStreamCreateWithFlags(&r->side[k], hipStreamNonBlocking));
+        if (r->ev_join[k] == nullptr) ADX_CHECK_HIP(hipEventCreateWithFlags(&r->ev_join[k], hipEventDisableTiming));
       }
     }
   }
-  hipStream_t streams[kMaxSub];
-  int n0s[kMaxSub], ns[kMaxSub];
-  Cursor st[kMaxSub]{};
-  for (int k = 0, at = 0; k < nsub; ++k) {
-    streams[k] = k == 0 ? s : r->side[k - 1];
-    n0s[k] = at;
-    ns[k] = batch / nsub + (k < batch % nsub ? 1 : 0);
-    at += ns[k];
-  }
-  const size_t scratch_per = ((size_t)batch * 64 * h1 * w1 / nsub) & ~(size_t)63;
-  // (only where the fused stem + pool launch leaves the stem map's region unwritten; each sub-batch gets its own slice)
-  const bool stem_free = (fuse || frames_u8 != nullptr) && conv2d_hs_eligible(r->convs[0]);
-  auto lend = [&](int k) { if (stem_free) scratch_scope.set(stem + (size_t)k * scratch_per, scratch_per); };
-  int rc = ADX_OK;
-  // The stem and the first layer (the blocks in front of the first downsample block) run as ONE chain on the whole batch, the fork
-  // comes behind them: their launches are thousands of two-per-CU workgroups whose last round hardly matters, and split they
-  // only stream their operands twice (-1.6 % per faithful step, profiles/README.md).  The hand-off format does not depend on the
-  // batch: a downsample block's fused stride-2 launch reads cells or fp32 as it finds them.  ADX_RESNET_SPLIT_FROM=<block> shortens it.
-  size_t first_split = 0;
-  if (nsub > 1) {
-    while (first_split < nblocks && !r->block_has_ds[first_split]) ++first_split;
-    // (only blocks of the FIRST layer: their maps have the pooled map's per-image size, so the whole-batch tensors they leave are
-    // laid out exactly like the sub-batches' regions; the override can only shorten the prefix)
-    if (debug_switches().resnet_split_from >= 0) first_split = std::min((size_t)debug_switches().resnet_split_from, first_split);
-  }
-  if (first_split > 0) {
-    Cursor whole{};
-    lend(0);
-    rc = run_stem(whole, 0, batch, batch, s);
-    for (size_t b = 0; b < first_split && rc == ADX_OK; ++b) rc = run_block(b, whole, 0, batch, batch, s);
-    for (int k = 0; k < nsub; ++k) st[k] = whole;
-  }
+
+  const float* base = (const float*)packed;
+  const ResnetLayout& lay = plan.lay;
+  const int h1 = lay.h1, w1 = lay.w1, h2 = lay.h2, w2 = lay.w2;
+  float* const ws = (float*)workspace;
+  float* const region[4] = {ws + lay.stem, ws + lay.stem + lay.act, ws + lay.stem + 2 * lay.act, ws};
+  // a segment's part of a buffer: from its first image's slot of the buffer's largest map
+  auto at = [&](const ResnetSegment& g, int buf) { return region[buf] + (size_t)g.n0 * 64 * (buf == kResnetBufStem ? h1 * w1 : h2 * w2); };
+  struct ScratchScope {     // split-reduction scratch of the 3x3 convs of THIS call
+    void set(float* p, size_t n) { conv2d_set_split_scratch(p, n); }
+    ~ScratchScope() { conv2d_set_split_scratch(nullptr, 0); }
+  } scratch_scope;
+  uint32_t* const words = r->status;       // range status (adx_resnet_set_status): [0] stem, [1 + b] block b, [1 + nblocks] fc
+  StatusScope status_scope(words);
+
+  auto issue = [&](const ResnetSegment& g, int i) -> int {
+    hipStream_t st = g.stream == 0 ? s : r->side[g.stream - 1];
+    const int n = g.n;
+    scratch_scope.set(g.scratch_floats != 0 ? ws + g.scratch_off : nullptr, g.scratch_floats);
+    int rc;
+    if (i < 0) {                    // stem (+ pool)
+      const ConvSpec& c0 = r->convs[0];
+      const float* im = img != nullptr ? img + (size_t)g.n0 * 3 * h * w : nullptr;
+      const uint8_t* fr = frames_u8 != nullptr ? frames_u8 + (size_t)g.n0 * 3 * h * w : nullptr;
+      status_scope.set(words);
+      float* pooled = at(g, 0);
+      if (g.stem_fused) {
+        rc = conv2d_hs_stem_pool(c0, im, base + c0.o_w, base + c0.o_scale, base + c0.o_shift, pooled, n, h, w, st, fr, mean, stdv,
+                                 g.pooled_cells);
+      } else {
+        float* sm = at(g, kResnetBufStem);
+        rc = conv2d_launch(c0, base, im, nullptr, sm, n, h, w, 1, st);
+        if (rc != ADX_OK) return rc;
+        rc = maxpool_launch(sm, pooled, n * 64, h1, w1, h2, w2, st);
+      }
+      if (rc != ADX_OK) return rc;
+      return conv2d_range_check("the stem (conv1 + bn1 + relu + maxpool), tensor", 0, pooled, (size_t)n * 64 * h2 * w2, g.pooled_cells, st);
+    }
+    if (i == g.nsteps) {            // average pool + fc
+      const int fc = 1 + (int)r->block_has_ds.size();
+      return avgpool_fc_launch(at(g, g.final_buf), base + r->o_fcw, base + r->o_fcb, feature + (size_t)g.n0 * r->out_dim, n, 512,
+                               g.final_h * g.final_w, r->out_dim, st, g.final_cells, words != nullptr ? words + fc : nullptr);
+    }
+    const ResnetBlockStep& t = g.steps[i];      // one BasicBlock
+    const ConvSpec& c1 = r->convs[t.c1];
+    const ConvSpec& c2 = r->convs[t.c1 + 1];
+    status_scope.set(words != nullptr ? words + t.status : nullptr);
+    const float* xin = at(g, t.in);
+    float* mid = at(g, t.mid);
+    float* identity = at(g, t.id);
+    float* dst = at(g, t.out);
+    if (t.fused_ds) {
+      const ConvSpec& ds = r->convs[t.c1 + 2];
+      rc = conv2d_hs_launch_block_s2(c1, ds, xin, base + c1.o_w, base + c1.o_scale, base + c1.o_shift, mid, base + ds.o_w, base + ds.o_scale,
+                                     base + ds.o_shift, identity, n, t.H, t.W, st, t.in_cells, t.mid_cells);
+      if (rc != ADX_OK) return rc;
+    } else {
+      rc = conv2d_launch(c1, base, xin, nullptr, mid, n, t.H, t.W, 1, st,            // conv1 + bn1 + relu
+                         (t.in_cells ? kFmtXCells : 0) | (t.mid_cells ? kFmtYCells : 0));
+      if (rc != ADX_OK) return rc;
+      if (r->block_has_ds[t.block]) {
+        rc = conv2d_launch(r->convs[t.c1 + 2], base, xin, nullptr, identity, n, t.H, t.W, 0, st);  // downsample conv + bn
+        if (rc != ADX_OK) return rc;
+      }
+    }
+    rc = conv2d_range_check("conv1 + bn1 + relu of BasicBlock", t.block, mid, (size_t)n * c1.cout * t.OH * t.OW, t.mid_cells, st);
+    if (rc != ADX_OK) return rc;
+    rc = conv2d_launch(c2, base, mid, identity, dst, n, t.OH, t.OW, 1, st,           // conv2 + bn2 + identity + relu
+                       (t.mid_cells ? kFmtXCells : 0) | (t.out_cells ? kFmtYCells : 0) | (t.id_cells ? kFmtResCells : 0));
+    if (rc != ADX_OK) return rc;
+    return conv2d_range_check("the output of BasicBlock", t.block, dst, (size_t)n * c2.cout * t.OH * t.OW, t.out_cells, st);
+  };
+
+  rc = resnet_plan_each(plan.seg, plan.nseg - nsub, issue);
   if (nsub > 1) {
     ADX_CHECK_HIP(hipEventRecord(r->ev_fork, s));
-    for (int k = 1; k < nsub; ++k) ADX_CHECK_HIP(hipStreamWaitEvent(streams[k], r->ev_fork, 0));
+    for (int k = 1; k < nsub; ++k) ADX_CHECK_HIP(hipStreamWaitEvent(r->side[k - 1], r->ev_fork, 0));
   }
-  // launches are issued layer by layer, alternating between the sub-batches, so that every stream's queue has work early
-  for (int k = 0; k < nsub && rc == ADX_OK && first_split == 0; ++k) { lend(k); rc = run_stem(st[k], n0s[k], ns[k], ns[k], streams[k]); }
-  for (size_t b = first_split; b < nblocks && rc == ADX_OK; ++b)
-    for (int k = 0; k < nsub && rc == ADX_OK; ++k) { lend(k); rc = run_block(b, st[k], n0s[k], ns[k], ns[k], streams[k]); }
-  for (int k = 0; k < nsub && rc == ADX_OK; ++k) {
-    const size_t off = (size_t)n0s[k] * 64 * h2 * w2;          // the sub-batch's region (run_block)
-    rc = avgpool_fc_launch(buf[st[k].cur] + off, base + r->o_fcw, base + r->o_fcb, feature + (size_t)n0s[k] * r->out_dim, ns[k], 512,
-                           st[k].H * st[k].W, r->out_dim, streams[k], st[k].cells, words != nullptr ? words + 1 + nblocks : nullptr);
-  }
+  if (rc == ADX_OK) rc = resnet_plan_each(plan.seg + plan.nseg - nsub, nsub, issue);
   // join even after an error: a side stream must not be left forked from a capturing stream
   for (int k = 1; k < nsub; ++k) {
-    if (hipEventRecord(r->ev_join[k - 1], streams[k]) == hipSuccess) (void)hipStreamWaitEvent(s, r->ev_join[k - 1], 0);
+    if (hipEventRecord(r->ev_join[k - 1], r->side[k - 1]) == hipSuccess) (void)hipStreamWaitEvent(s, r->ev_join[k - 1], 0);
   }
   return rc;
 }

@@ -1539,7 +1539,7 @@ static bool hs_eligible(const ConvSpec& L, const DebugSwitches& sw) {
   if (L.cin % kHsCC != 0 || L.cin_pad != L.cin || L.cout % kHsCout != 0) return false;
   return L.k == 3 && (L.stride == 1 || L.stride == 2);
 }
-bool conv2d_hs_eligible(const ConvSpec& L) { return hs_eligible(L, debug_switches()); }
+bool conv2d_hs_eligible(const ConvSpec& L, const DebugSwitches& sw) { return hs_eligible(L, sw); }
 
 size_t conv2d_packed_floats(const ConvSpec& L) {
   const size_t direct = (size_t)L.k * L.k * L.cin_pad * L.cout;

@@ -196,7 +196,7 @@ int conv2d_pack_raw(const float* w, float* packed, int cout, int cin, int k, int
 // image is its data-gradient view (roles swapped, taps flipped).
 int conv2d_pack_spec(const ConvSpec& consumer, const float* w, float* packed, int dgrad, hipStream_t s);
 // conv2d_hs.hip: fp32-equivalent convolution on the fp16 matrix cores (hi/lo split operands, 3 MFMAs per product)
-bool conv2d_hs_eligible(const ConvSpec& L);
+bool conv2d_hs_eligible(const ConvSpec& L, const DebugSwitches& sw = debug_switches());
 // floats a layer's packed weight image takes (direct image, plus the Winograd F(2,3) image where that path applies)
 size_t conv2d_packed_floats(const ConvSpec& L);
 int conv2d_hs_pack(const ConvSpec& consumer, const float* w, void* packed, int dgrad, hipStream_t s);
@@ -258,8 +258,8 @@ int conv2d_hs3x3q_s2_launch(const HsS2Plan& p, Conv2dArgs a, hipStream_t s);
 // compute units of the calling thread's current device (conv2d.hip)
 int device_cus(int* cus);
 // conv1 3x3 stride 2 on the split-fp16 kernel + a 1x1 stride-2 downsample of the same shape: one fused launch (conv2d.hip)
-inline bool resnet_fuses_ds(const ConvSpec& c1, const ConvSpec& ds) {
-  return conv2d_hs_eligible(c1) && c1.k == 3 && c1.stride == 2 && c1.pad == 1 && ds.k == 1 && ds.stride == 2 && ds.pad == 0 &&
+inline bool resnet_fuses_ds(const ConvSpec& c1, const ConvSpec& ds, const DebugSwitches& sw = debug_switches()) {
+  return conv2d_hs_eligible(c1, sw) && c1.k == 3 && c1.stride == 2 && c1.pad == 1 && ds.k == 1 && ds.stride == 2 && ds.pad == 0 &&
          ds.cin == c1.cin && ds.cout == c1.cout;
 }
 // conv2d_wgrad_hs.hip: weight gradient of the 3x3 convs on the fp16 matrix cores; dw must be zero on entry
@@ -277,6 +277,65 @@ bool conv2d_wgrad_stem_hs_eligible(int Cin, int Cout, int k, int stride, int pad
 int conv2d_wgrad_stem_hs(const float* x, const float* dy, float* dw, int N, int H, int W, const uint32_t* dy_amax, int dy_amax_n,
                          hipStream_t s);
 inline int conv_out_dim(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
+inline size_t al64(size_t v) { return (v + 63) / 64 * 64; }
+
+// ---- the plan of one eval forward (conv2d.hip) ----
+// Everything adx_resnet_forward decides above the single launch -- sub-batches and the whole-batch prefix, the activation
+// format of every edge, the buffer of every tensor, the scratch slice and the status group of every launch -- is decided ONCE, by
+// resnet_eval_plan: a pure function (no HIP call, no state, no heap) of the network, the call's shape and the switches.  The
+// executor only carries the plan out; adx_resnet_plan_describe (include/adx.h) exports it, one record per launch.
+//
+// The format rule.  An edge is a CELL tensor iff its producer can write cells and every reader reads cells.  With plain(c) =
+// conv2d_hs3x3_plain(c, nf, H, W) at the conv's own map size and nf the segment's batch:
+//   * a block READS cells iff it is a fused entry (resnet_fuses_ds(c1, ds)), or has no downsample and c1.stride == 1 &&
+//     plain(c1) && plain(c2): conv1 reads the input, conv2 reads it again as the residual;
+//   * the map between a block's convs is cells iff plain(c2) (fused entry; the downsample's output goes with it) or the block
+//     has no downsample and reads cells;
+//   * a block's output is cells iff plain(c2) && (it is the last block -- the average pool reads both -- || the next block reads cells);
+//   * the pooled map is cells iff the fused stem + pool launch writes it and block 0 reads cells.
+// At the hand-off from the whole-batch prefix (nf = batch) to a sub-batch (nf = its own size) the producer's decision stands.
+struct ResnetEvalQuery {
+  int batch = 0, h = 0, w = 0;
+  bool capturing = false;         // the caller's stream is being captured: one chain (no side streams)
+  bool u8 = false;                // uint8 frames: the front-end lives in the fused stem + pool launch alone
+};
+// the workspace in floats: the stem region (the unpooled stem map, or split-reduction scratch where it is never written), then
+// three rotating activation regions sized for the pooled map
+struct ResnetLayout {
+  int h1 = 0, w1 = 0, h2 = 0, w2 = 0;       // stem map, pooled map
+  size_t stem = 0, act = 0;
+  size_t floats() const { return stem + 3 * act; }
+};
+ResnetLayout resnet_layout(int batch, int h, int w);
+constexpr int kResnetMaxBlocks = 16;        // ResNet-34
+constexpr int kResnetBufStem = 3;           // buffer indices: 0..2 the rotating regions, 3 the stem region, -1 none
+struct ResnetBlockStep {
+  int block = 0, c1 = 0;                    // the block, and its conv1 in adx_resnet::convs (conv2 and the downsample follow it)
+  int H = 0, W = 0, OH = 0, OW = 0;         // the input map and the block's own
+  bool fused_ds = false;                    // conv1 + downsample as one block-entry launch
+  int in = 0, mid = 0, id = 0, out = 0;     // buffers of the input, conv1's output, the identity (= in without a downsample), the output
+  bool in_cells = false, mid_cells = false, id_cells = false, out_cells = false;
+  int status = 0;                           // status group (adx_resnet_status_name)
+};
+struct ResnetSegment {                      // the whole-batch prefix, or one sub-batch
+  int id = 0;                               // 0: the prefix, 1 + k: sub-batch k
+  int n0 = 0, n = 0, nf = 0;                // images [n0, n0 + n); nf: the batch its format decisions are made for
+  int stream = 0;                           // 0: the caller's, k: side stream k - 1
+  size_t scratch_off = 0, scratch_floats = 0;   // its slice of the stem region as split-reduction scratch (0, 0 where the region is written)
+  bool stem = false, stem_fused = false, pooled_cells = false;
+  int nsteps = 0;
+  ResnetBlockStep steps[kResnetMaxBlocks];
+  int final_buf = 0, final_h = 0, final_w = 0;  // what the average pool reads (sub-batches only)
+  bool final_cells = false;
+};
+struct ResnetEvalPlan {
+  int nsub = 1, first_split = 0;            // blocks [0, first_split) run once, on the whole batch (with the stem when first_split > 0)
+  ResnetLayout lay;
+  int nseg = 0;                             // (first_split > 0) + nsub: the prefix first
+  ResnetSegment seg[1 + adx_resnet::kMaxSub];
+};
+// ADX_ERR_INVALID (with the message set) for a shape or format hand-off the executor cannot run
+int resnet_eval_plan(const adx_resnet& r, const ResnetEvalQuery& q, ResnetEvalPlan* plan, const DebugSwitches& sw = debug_switches());
 // ADX_CHECK_RANGE=1 (no-op otherwise): fails with ADX_ERR_RANGE naming (what, index) when the tensor holds |x| >= 65504 or a
 // non-finite value (cells: an fp16 hi half that is inf / NaN); synchronises the stream
 int conv2d_range_check(const char* what, int index, const float* t, size_t floats, bool cells, hipStream_t s);

@@ -1221,8 +1221,6 @@ int adx_conv2d_wgrad_cells(const adx_conv2d_desc* d, const void* x_cells, const 
 
 namespace adx {
 
-static size_t al64(size_t v) { return (v + 63) / 64 * 64; }
-
 struct Bump2 {
   float* base; size_t off, cap; bool ok = true;
   float* take(size_t n) {

@@ -327,6 +327,37 @@ int adx_resnet_forward_u8(adx_resnet* r, const void* packed, void* workspace, co
  * adx_resnet_status_words(r) = the number of words (<0 on a null handle); adx_resnet_set_status(r, words) attaches a
  * device buffer of that many words (NULL detaches); adx_resnet_status_name(r, g) = group g's name (NULL on a bad index).
  * The training forward (adx_resnet_forward_train) never writes the words; ADX_CHECK_RANGE=1 is unchanged. */
+/* For tests only: the plan of ONE eval forward of `batch` images of h x w, one record per launch in issue order.  Needs no
+ * GPU and launches nothing: the call runs the pure function the executor itself carries out (csrc/conv2d_internal.h:
+ * resnet_eval_plan), which decides the sub-batches, the activation format and buffer of every tensor, the scratch slice and
+ * the status group of every launch.  Which kernel serves a launch, its tiles and its reduction split are decided below that,
+ * per launch, and are not part of this export.  The process-wide switches (ADX_RESNET_STREAMS, ADX_RESNET_SPLIT_FROM,
+ * ADX_CHECK_RANGE, ADX_CONV_EXACT, ADX_CONV_CELLS, ...) act as they do on a forward.
+ * flags: ADX_RESNET_PLAN_CAPTURING plans the forward as inside a stream capture (one chain, no side streams).
+ * ints: ADX_RESNET_PLAN_INTS words per record, at most max_records records (more launches: ADX_ERR_INVALID); *n_records: launches.
+ *   [0] segment  0: the whole-batch prefix in front of the fork (the stem and blocks [0, first_split)), 1 + k: sub-batch k
+ *   [1] stream   0: the caller's, k: side stream k - 1
+ *   [2] n0, [3] n: the segment's images [n0, n0 + n); [4] nf: the batch its format decisions are made for
+ *   [5] kind     ADX_RESNET_PLAN_*: stem + pool in one launch, stem conv, max pool, conv, block entry (conv1 + downsample in one
+ *                launch), average pool + fc
+ *   [6] block    BasicBlock 0..15, or -1; [7] conv: 0 conv1 (the block entry too), 1 conv2, 2 the downsample conv, or -1
+ *   [8] H, [9] W: the launch's input map; [10] OH, [11] OW: its output map; [12] cin, [13] cout
+ *   [14] fmt     bit 0: x is a cell tensor, bit 1: y (both outputs of a block entry), bit 2: the residual; fp32 NCHW otherwise
+ *   [15] x, [16] res, [17] y, [18] y2: buffers -- 0..2 the rotating activation regions, 3 the stem region, -1 none (the image, the
+ *                feature, no residual); y2: the downsample's output of a block entry.  A segment's tensors start at its first
+ *                image's slot of the region's largest map: n0 * 64 * h2 * w2 floats into a rotating region (h2 x w2: the pooled
+ *                map), n0 * 64 * h1 * w1 into the stem region (h1 x w1: the stem map).  Workspace, in floats: the stem region,
+ *                align64(batch * 64 * h1 * w1), then the three rotating regions of align64(batch * 64 * h2 * w2) each.
+ *   [19] scratch_off, [20] scratch_floats: the slice of the stem region lent to the launch as split-reduction scratch, both in
+ *                units of 64 floats (0, 0: none -- the region holds the stem map)
+ *   [21] status  the launch's status group (adx_resnet_status_name)
+ *   [22] nsub, [23] first_split: the forward's sub-batches and the first block that runs per sub-batch (the same in every record) */
+#define ADX_RESNET_PLAN_INTS 24
+#define ADX_RESNET_PLAN_CAPTURING 1
+enum { ADX_RESNET_PLAN_STEM_POOL = 0, ADX_RESNET_PLAN_STEM = 1, ADX_RESNET_PLAN_MAXPOOL = 2, ADX_RESNET_PLAN_CONV = 3,
+       ADX_RESNET_PLAN_ENTRY = 4, ADX_RESNET_PLAN_AVGPOOL_FC = 5 };
+int adx_resnet_plan_describe(const adx_resnet* r, int32_t batch, int32_t h, int32_t w, int32_t flags, int32_t* n_records, int32_t* ints,
+                             int32_t max_records);
 int32_t adx_resnet_status_words(const adx_resnet* r);
 int adx_resnet_set_status(adx_resnet* r, uint32_t* words /* device, adx_resnet_status_words(r) words, or NULL */);
 const char* adx_resnet_status_name(const adx_resnet* r, int32_t group);

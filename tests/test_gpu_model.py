@@ -62,7 +62,10 @@ def test_resnet_ragged_sizes_and_batch():
     m, _ = make_model("NO_GUIDANCE", 16)
     # the larger cases change layout decisions layer by layer (cell tensors and batch-wide column tiles where a layer's convs are
     # plain launches, fp32 NCHW where they split their reduction; maps narrower than 16 columns tile per image)
-    for hw, b in (((70, 101), 3), ((33, 47), 1), ((128, 131), 2), ((200, 333), 3), ((129, 515), 9), ((97, 131), 33), ((64, 2048), 2)):
+    for hw, b in (((70, 101), 3), ((33, 47), 1), ((128, 131), 2), ((200, 333), 3), ((129, 515), 9), ((97, 131), 33), ((64, 2048), 2),
+                  # the smallest image, on each side of every format change there (tests/test_resnet_plan_cpu.py: PINNED) and on an
+                  # uneven and an even pair of sub-batches
+                  ((32, 32), 9), ((32, 32), 17), ((32, 32), 33), ((32, 32), 40)):
         img = P.synthetic_batch(b, 16, image_hw=hw, seed=5)["imgs"]
         with torch.no_grad():
             f = m.perception(img.to(DEV)).cpu()
