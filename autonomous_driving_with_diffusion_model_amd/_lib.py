@@ -177,6 +177,7 @@ _SIGS = {
     "adx_noise_normal": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_words": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_advance": (i32, [vp, vp]),
+    "adx_warm_init": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, f32, f32, vp, i64, i32, vp]),
     "adx_add_noise": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp]),
 }
 

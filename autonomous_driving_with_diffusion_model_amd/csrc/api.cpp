@@ -79,6 +79,8 @@ int traj_select(const adx_select_cfg* c, const float* trajs, const float* target
 int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);
 int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s);
 int noise_advance(uint32_t* state, hipStream_t s);
+int warm_init(const float* prev, int prev_rows, const float* motion, float* out, int rows, int horizon, int dim, int shift,
+              float sqrt_ab, float sqrt_1mab, const uint32_t* ns, int64_t row_offset, int zero_first, hipStream_t s);
 int add_noise(const float* x, const float* n, const int64_t* t, const float* sa, const float* sb, int n_train,
               float* out, int batch, int horizon, int dim, int zero_first, hipStream_t s);
 
@@ -185,6 +187,12 @@ int adx_noise_words(const uint32_t* state, int32_t slot, int64_t first_elem, uin
   return adx::noise_words(state, slot, first_elem, out, n, (hipStream_t)s);
 }
 int adx_noise_advance(uint32_t* state, adx_stream s) { return adx::noise_advance(state, (hipStream_t)s); }
+int adx_warm_init(const float* prev, int32_t prev_rows, const float* motion, float* out, int32_t rows, int32_t horizon,
+                  int32_t dim, int32_t shift, float sqrt_ab, float sqrt_1mab, const uint32_t* noise_state, int64_t row_offset,
+                  int32_t zero_first, adx_stream s) {
+  return adx::warm_init(prev, prev_rows, motion, out, rows, horizon, dim, shift, sqrt_ab, sqrt_1mab, noise_state, row_offset,
+                        zero_first, (hipStream_t)s);
+}
 int adx_add_noise(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
                   int32_t n_train, float* out, int32_t batch, int32_t horizon, int32_t dim, int32_t zero_first,
                   adx_stream s) {

@@ -307,6 +307,97 @@ int noise_advance(uint32_t* state, hipStream_t s) {
   return ADX_OK;
 }
 
+// Warm start v1 (include/adx.h): this tick's initial trajectory from the last tick's result -- advance by `shift` waypoints,
+// re-base onto the new first waypoint (or the caller's odometry), clamp, re-noise to the level the schedule's suffix starts at.
+// One thread per OUTPUT element; the noise is the stream's INIT_SLOT draw of the element's logical index, as in step_kernel.
+struct WarmArgs {
+  const float* prev;      // [prev_rows][H][D]
+  const float* motion;    // [prev_rows][3] = (tx, ty, phi), or null
+  float* out;             // [rows][H][D]
+  const uint32_t* ns;
+  uint64_t base;          // first logical element of this launch's rows
+  float sqrt_ab, sqrt_1mab;
+  int total, prev_rows, horizon, dim, shift, zero_first;
+};
+
+// u[h][d] of the contract: the waypoint `shift` steps on; past the end xy go on in a straight line, the rest is held
+__device__ __forceinline__ float warm_advance(const float* p, int h, int d, int H, int D, int shift) {
+#pragma clang fp contract(off)
+  const int j = h + shift;
+  if (j <= H - 1) return p[j * D + d];
+  const float last = p[(H - 1) * D + d];
+  if (d >= 2) return last;
+  const float step = last - p[(H - 2) * D + d];
+  const float run = (float)(j - (H - 1)) * step;
+  return last + run;
+}
+
+__global__ void __launch_bounds__(256) warm_init_kernel(const WarmArgs a) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.total) return;
+  const int H = a.horizon, D = a.dim;
+  const int d = e % D, h = (e / D) % H, r = e / (H * D);
+  const int pr = r % a.prev_rows;
+  const float* p = a.prev + (size_t)pr * H * D;
+  float w;
+  if (a.motion != nullptr && d < 2) {
+    const float tx = a.motion[pr * 3 + 0], ty = a.motion[pr * 3 + 1], phi = a.motion[pr * 3 + 2];
+    const float c = cosf(phi), s = sinf(phi);
+    const float qx = warm_advance(p, h, 0, H, D, a.shift) - tx;
+    const float qy = (D > 1 ? warm_advance(p, h, 1, H, D, a.shift) : 0.f) - ty;
+    if (d == 0) {
+      const float m0 = c * qx, m1 = s * qy;
+      w = m0 + m1;
+    } else {
+      const float m0 = s * qx, m1 = c * qy;
+      w = -m0 + m1;
+    }
+  } else {
+    w = warm_advance(p, h, d, H, D, a.shift);
+    if (d < 3) w = w - p[a.shift * D + d];
+  }
+  w = clamp_nan(w, -1.0f, 1.0f);
+  const float z = noise_normal_at(a.ns, 0xFFFFFFFFu, a.base + (uint64_t)e);
+  const float m0 = a.sqrt_ab * w, m1 = a.sqrt_1mab * z;
+  float v = m0 + m1;
+  if (a.zero_first && h == 0 && d < 3) v = 0.f;
+  a.out[e] = v;
+}
+
+static bool byte_ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + qn && b < a + pn;
+}
+
+int warm_init(const float* prev, int prev_rows, const float* motion, float* out, int rows, int horizon, int dim, int shift,
+              float sqrt_ab, float sqrt_1mab, const uint32_t* ns, int64_t row_offset, int zero_first, hipStream_t s) {
+  ADX_REQUIRE(prev != nullptr && out != nullptr && ns != nullptr, "warm init: null prev, out or noise state");
+  ADX_REQUIRE(horizon >= 2 && horizon <= 64, "warm init: horizon %d outside 2..64", horizon);
+  ADX_REQUIRE(dim >= 1 && dim <= 16, "warm init: dim %d outside 1..16", dim);
+  ADX_REQUIRE(shift >= 0 && shift <= horizon - 1, "warm init: shift %d outside 0..%d (horizon - 1)", shift, horizon - 1);
+  ADX_REQUIRE(prev_rows >= 1 && rows >= 1 && rows % prev_rows == 0, "warm init: rows %d must be a positive multiple of prev_rows %d",
+              rows, prev_rows);
+  ADX_REQUIRE(row_offset >= 0, "warm init: negative row_offset %lld", (long long)row_offset);
+  const int64_t per = (int64_t)horizon * dim;
+  ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + rows) <= kNoiseElems / per,
+              "warm init: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements", (long long)row_offset,
+              (long long)row_offset + rows, (long long)per);
+  ADX_REQUIRE((int64_t)rows * per <= (int64_t)0x3fffffff, "warm init: %lld elements do not fit the kernel's 32-bit index",
+              (long long)rows * per);
+  ADX_REQUIRE(!byte_ranges_overlap(out,(size_t)rows * per * sizeof(float), prev, (size_t)prev_rows * per * sizeof(float)),
+              "warm init: the output overlaps prev");
+  WarmArgs a;
+  a.prev = prev; a.motion = motion; a.out = out; a.ns = ns;
+  a.base = (uint64_t)row_offset * (uint64_t)per;
+  a.sqrt_ab = sqrt_ab; a.sqrt_1mab = sqrt_1mab;
+  a.total = (int)(rows * per); a.prev_rows = prev_rows; a.horizon = horizon; a.dim = dim; a.shift = shift;
+  a.zero_first = zero_first != 0;
+  warm_init_kernel<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
+}
+
 __global__ void __launch_bounds__(256) add_noise_kernel(const float* __restrict__ x, const float* __restrict__ n,
                                                          const int64_t* __restrict__ t, const float* __restrict__ sa,
                                                          const float* __restrict__ sb, float* __restrict__ out,

@@ -15,14 +15,18 @@ trajectory and every step's noise from the counter-based stream of noise.py insi
 `torch.randn` tensors -- the same loop then also runs as one HIP graph (`GraphedSampler(..., noise=...)`).
 A fourth has no counterpart in the callers: `candidates=K` draws K trajectories per scene in one loop of K * S rows (the encoder
 still runs once per scene) and keeps the one a device-side cost prefers (control/select.py, "selection cost v1" of include/adx.h).
+A fifth has none either: `warm=WarmStart(steps=m)` starts a tick from the previous tick's result -- advanced, re-based, clamped
+and re-noised on the device ("warm start v1" of include/adx.h) -- and runs only the last m steps of the schedule.
 """
 from __future__ import annotations
 
 import contextlib
-from typing import Callable, Optional
+from types import SimpleNamespace
+from typing import Callable, Optional, Tuple
 
 import torch
 
+from . import _lib as L
 from ._lib import AdxRangeError
 from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
@@ -52,11 +56,106 @@ def _candidates(cfg, candidates: int, selector):
     return K, selector
 
 
+class WarmStart:
+    """Receding-horizon warm starting: the state one agent carries from tick to tick.
+
+    `steps` = m: a warm tick runs the last m of the EVAL.SAMPLE_STEPS = n steps, from the previous result noised to the level
+    of `timesteps[n - m]`; `shift`: the waypoints the vehicle passed between two ticks.  Left at None they read EVAL.WARM_STEPS
+    (0 = off: every tick is cold and this object is never touched) and EVAL.WARM_SHIFT (1).  `prev` is the static [S, H, D]
+    buffer of the last result in the model's own units (clamped, before xy scaling; the winners at K > 1), allocated on first
+    use and never re-allocated -- captured graphs read and write it; `valid` says on the host whether it holds one.  `reset()`
+    makes the next tick cold: call it after a scene cut or a teleport.  How good a plan m steps give is a property of the
+    trained weights and is not measured in this repository."""
+
+    def __init__(self, steps: Optional[int] = None, shift: Optional[int] = None):
+        self.steps, self.shift = steps, shift
+        self.prev: Optional[torch.Tensor] = None
+        self.valid = False
+
+    def reset(self) -> None:
+        self.valid = False
+
+    def resolve(self, cfg) -> Tuple[int, int]:
+        m = int(getattr(cfg.EVAL, "WARM_STEPS", 0) if self.steps is None else self.steps)
+        shift = int(getattr(cfg.EVAL, "WARM_SHIFT", 1) if self.shift is None else self.shift)
+        if m < 0:
+            raise ValueError(f"WarmStart: steps must be >= 0, got {m}")
+        return m, shift
+
+    def _store(self, result: torch.Tensor) -> None:
+        if self.prev is None:
+            self.prev = torch.empty_like(result)
+        self.prev.copy_(result)
+        self.valid = True
+
+    def __repr__(self):
+        shape = None if self.prev is None else tuple(self.prev.shape)
+        return f"WarmStart(steps={self.steps}, shift={self.shift}, valid={self.valid}, prev={shape})"
+
+
+def _warm_plan(cfg, warm: Optional[WarmStart], noise, init_trajs, image, K: int, motion, scheduler=None):
+    """(m, shift, is_warm, motion) of this tick, every refusal raised here: before any launch, before a tick of the noise stream
+    is consumed, before a capture opens.  m == 0 (no `warm`, or one that is off) is the loop as it was.  `scheduler`: one whose
+    timesteps the caller has set itself and the warm tick will index."""
+    S = int(image.shape[0])
+    if motion is not None:
+        if warm is None:
+            raise ValueError("generate_traj: `motion` is the odometry of a warm start; pass warm=WarmStart(...) with it")
+        # checked on every tick it is given, cold ones included (which do not read it): a wrong shape shows on the first call
+        motion = L.require_gpu_f32(motion, "motion")
+        if tuple(motion.shape) != (S, 3) or motion.device != image.device:
+            raise ValueError(f"motion must be [{S}, 3] = (tx, ty, phi) per scene on {image.device}, got {tuple(motion.shape)} "
+                             f"on {motion.device}")
+    if warm is None or warm.resolve(cfg)[0] == 0:
+        return 0, 0, False, None
+    m, shift = warm.resolve(cfg)
+    n, H, D = int(cfg.EVAL.SAMPLE_STEPS), int(cfg.MODEL.HORIZON), int(cfg.MODEL.TRANSITION_DIM)
+    if m > n:
+        raise ValueError(f"WarmStart: steps = {m} is more than EVAL.SAMPLE_STEPS = {n}")
+    if not 0 <= shift < H:
+        raise ValueError(f"WarmStart: shift = {shift} must be in 0..{H - 1} (MODEL.HORIZON = {H})")
+    if not isinstance(noise, DeviceNoise):
+        raise ValueError("WarmStart needs noise=DeviceNoise(...): the re-noise is drawn inside the warm-start kernel")
+    if noise.device != image.device:
+        raise ValueError(f"the DeviceNoise lives on {noise.device}, the image on {image.device}")
+    if warm.prev is not None and (tuple(warm.prev.shape) != (S, H, D) or warm.prev.device != image.device):
+        raise ValueError(f"WarmStart: the state holds {tuple(warm.prev.shape)} on {warm.prev.device}, this tick is "
+                         f"{(S, H, D)} on {image.device}; use a new WarmStart for another batch shape or device")
+    if not warm.valid:
+        return m, shift, False, None
+    if init_trajs is not None:
+        raise ValueError("generate_traj: `init_trajs` and a valid warm state both name the tick's start; warm.reset() first "
+                         "for a cold tick from init_trajs")
+    if scheduler is not None and len(scheduler.timesteps) != n:       # a caller that keeps its own timesteps (set_timesteps=False)
+        raise ValueError(f"the scheduler holds {len(scheduler.timesteps)} timesteps, EVAL.SAMPLE_STEPS is {n}")
+    return m, shift, True, motion
+
+
+def warm_init(prev: torch.Tensor, rows: int, shift: int, level: Tuple[float, float], noise: DeviceNoise,
+              motion: Optional[torch.Tensor] = None, zero_first: bool = True) -> torch.Tensor:
+    """One launch of `adx_warm_init` ("warm start v1", include/adx.h): [rows, H, D] from prev [prev_rows, H, D] under the
+    stream's current tick; `level` = `scheduler.noise_level(tau)`; row r draws logical row `noise.row_offset + r`."""
+    prev = L.require_gpu_f32(prev, "prev")
+    if prev.dim() != 3:
+        raise ValueError(f"prev must be [rows, H, D], got {tuple(prev.shape)}")
+    if motion is not None:
+        motion = L.require_gpu_f32(motion, "motion")
+        if tuple(motion.shape) != (prev.shape[0], 3):
+            raise ValueError(f"motion must be [{prev.shape[0]}, 3], got {tuple(motion.shape)}")
+    P, H, D = prev.shape
+    out = torch.empty((int(rows), H, D), dtype=torch.float32, device=prev.device)
+    L.check(L.lib().adx_warm_init(prev.data_ptr(), P, L.ptr(motion), out.data_ptr(), int(rows), H, D, int(shift), float(level[0]),
+                                  float(level[1]), noise.state_ptr(), noise.row_offset, int(bool(zero_first)),
+                                  L.stream_ptr(prev.device)), "adx_warm_init")
+    return out
+
+
 def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                   init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, scale_xy: bool = True,
                   step_noise: Optional[Callable[[int, tuple], torch.Tensor]] = None,
                   set_timesteps: bool = True, noise: Optional[DeviceNoise] = None, candidates: int = 1,
-                  selector: Optional[TrajectorySelector] = None, return_selection: bool = False):
+                  selector: Optional[TrajectorySelector] = None, return_selection: bool = False,
+                  warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None):
     """`noise`: a DeviceNoise.  The call is then one tick of the noise stream: `begin_tick()` first, the initial trajectory
     (when `init_trajs` is not given) from `INIT_SLOT`, and every scheduler step draws inside its kernel at the slot of its
     timestep -- no noise tensor, no torch generator.
@@ -68,7 +167,14 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     device and the call returns the [S, H, D] winners, xy-scaled as usual.  `init_trajs`, when given, is [K * S, H, D].
     `return_selection=True` returns `(traj, Selection)`, whose `candidates` is the [K, S, H, D] tensor scaled like `traj`
     (`(traj, None)` at K = 1, where no selector runs).  Needs the hoisted conditioning path (`fuse=True`, `model.cache_perception`
-    on) and an unsharded `noise`.  K = 1 (the default, or EVAL.CANDIDATES when the argument is left at 1) is the loop as it was."""
+    on) and an unsharded `noise`.  K = 1 (the default, or EVAL.CANDIDATES when the argument is left at 1) is the loop as it was.
+
+    `warm` = a WarmStart with steps = m > 0: while `warm.valid` is False the tick is cold -- the loop as it was -- and ends by
+    copying the clamped, unscaled [S, H, D] result (the winners at K > 1) into `warm.prev`.  After that a tick is warm: with
+    n = EVAL.SAMPLE_STEPS and i0 = n - m, `adx_warm_init` builds the K * S start rows from `warm.prev` (row r from scene r % S)
+    and the optional `motion` [S, 3] = (tx, ty, phi) at the noise level of `timesteps[i0]`, `scheduler.set_begin_index(i0)`,
+    and the loop runs `timesteps[i0:]` only; clamp, selection, scaling and the copy into `warm.prev` follow as on a cold tick.
+    Needs `noise` (the re-noise is the stream's INIT_SLOT draw of the tick).  m = 0 is `warm=None`."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     model.eval()
     device = image.device
@@ -83,23 +189,34 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
                              f"{noise.row_offset}): scene sharding and candidate-major rows do not compose")
         if init_trajs is not None and init_trajs.shape[0] != K * S:
             raise ValueError(f"init_trajs must have candidates * scenes = {K * S} rows, got {tuple(init_trajs.shape)}")
+    if noise is not None and step_noise is not None:
+        raise ValueError("generate_traj: pass `noise` (the in-kernel stream) or `step_noise` (injected tensors), not both")
+    m_warm, shift, is_warm, motion = _warm_plan(cfg, warm, noise, init_trajs, image, K, motion,
+                                                None if set_timesteps else scheduler)
     if noise is not None:
-        if step_noise is not None:
-            raise ValueError("generate_traj: pass `noise` (the in-kernel stream) or `step_noise` (injected tensors), not both")
         noise.begin_tick()
-    if init_trajs is None:
-        shape = (K * S, cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM)
-        init_trajs = torch.randn(shape, device=device) if noise is None else noise.normal(DeviceNoise.INIT_SLOT, shape)
-    trajs = init_trajs.clone().detach()
+    i0 = 0
+    if is_warm:
+        if set_timesteps:
+            scheduler.set_timesteps(cfg.EVAL.SAMPLE_STEPS, device=device)
+        i0 = len(scheduler.timesteps) - m_warm
+        # zero_first: the kernel writes the `[:, 0, :3] = 0` of the loop's entry itself
+        trajs = warm_init(warm.prev, K * S, shift, scheduler.noise_level(scheduler.timesteps[i0]), noise, motion)
+    else:
+        if init_trajs is None:
+            shape = (K * S, cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM)
+            init_trajs = torch.randn(shape, device=device) if noise is None else noise.normal(DeviceNoise.INIT_SLOT, shape)
+        trajs = init_trajs.clone().detach()
     B = trajs.shape[0]
     scene_tgt = _targets(target, S) if K > 1 else None
     tgt = _targets(target, B) if K == 1 else (None if scene_tgt is None else scene_tgt.repeat(K, 1))
     cond = None
     if tgt is not None and use == GuidanceType.FREE_GUIDANCE:
         cond = torch.cat([tgt, torch.zeros_like(tgt)], dim=0)   # interact.py:121-127
-    trajs[:, 0, :3] = 0.0
-    if set_timesteps:
-        scheduler.set_timesteps(cfg.EVAL.SAMPLE_STEPS, device=device)
+    if not is_warm:
+        trajs[:, 0, :3] = 0.0
+        if set_timesteps:
+            scheduler.set_timesteps(cfg.EVAL.SAMPLE_STEPS, device=device)
     # whose step takes an injected `variance_noise`: the DDPM schedulers (a deterministic solver has no noise argument)
     is_ddpm = not getattr(scheduler, "_is_ddim", False) and not getattr(scheduler, "deterministic", False)
     # What the UNet derives from (t, target, image feature) alone does not change inside the loop: with the perception
@@ -110,6 +227,8 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         rows = 2 * B if use == GuidanceType.FREE_GUIDANCE else B
         ts = scheduler.timesteps
         ts = ts.tensor if hasattr(ts, "tensor") else torch.as_tensor(ts)
+        if i0 > 0:
+            ts = ts[i0:]        # a warm tick's table holds the suffix only; the loop indexes it relative to i0
         with torch.no_grad():
             # table row r reads image feature r % S: with candidate-major rows that is the row's own scene
             tc = model.time_conditioning(image, ts.to(device), cond=cond, rows=rows)
@@ -117,17 +236,27 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     # nothing in this loop writes `image`: say so, so that the reference-faithful per-step encoder pass of a batched tick may run
     # beside the previous step's temporal stack (modeling/perception.py:frozen_image; a no-op for holders without the method)
     frozen = getattr(getattr(model, "perception", None), "frozen_image", None)
-    with (frozen(image) if frozen is not None else contextlib.nullcontext()):
-        trajs = _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device,
-                           noise)
+    if is_warm:
+        scheduler.set_begin_index(i0)
+    try:
+        with (frozen(image) if frozen is not None else contextlib.nullcontext()):
+            trajs = _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device,
+                               noise, i0)
+    finally:
+        if is_warm:
+            scheduler.set_begin_index(0)       # the begin index belongs to this tick: a later loop on the scheduler starts at 0
     trajs = trajs.to(torch.float32).clamp(-1, 1)
     if K == 1:
+        if m_warm > 0:
+            warm._store(trajs)
         if scale_xy:
             trajs[..., :2] *= model.magic_num
         return (trajs, None) if return_selection else trajs
     # the cost is taken in the model's own units (before xy scaling: the units of `target`)
     sel = selector(trajs, S, scene_tgt)
     best = sel.best
+    if m_warm > 0:
+        warm._store(best)
     if scale_xy:
         best[..., :2] *= model.magic_num
     if not return_selection:
@@ -138,9 +267,11 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     return best, Selection(best, sel.index, sel.cost, cands)
 
 
-def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device, noise=None):
+def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device, noise=None,
+               begin=0):
+    """`begin` > 0: the schedule's suffix `timesteps[begin:]`; `i` (the row of the conditioning table) counts from there."""
     action = None
-    for i, t in enumerate(scheduler.timesteps):
+    for i, t in enumerate(scheduler.timesteps if begin == 0 else list(scheduler.timesteps)[begin:]):
         tck = None if tc is None else (tc, i)
         extra = {} if noise is None else {"generator": noise}
         if is_ddpm and step_noise is not None:
@@ -235,48 +366,73 @@ class GraphedSampler:
     the graph, so every replay sees the new frame.
     `candidates=K` > 1 (or EVAL.CANDIDATES when left at 1): best-of-K sampling as in `generate_traj`; the select kernel is a
     node of the graph, the call returns the [S, H, D] winners and `last_selection` the last replay's index and cost.
+    `warm=WarmStart(...)` (or EVAL.WARM_STEPS > 0 when left at None): warm starting as in `generate_traj`.  The sampler then holds
+    two graphs, a cold and a warm one, and picks by the host flag `warm.valid`; both end with the copy into the static
+    `warm.prev`, so replay k + 1 starts from replay k's result without leaving the device.  `motion` travels through a static
+    buffer like `target`.  Up to `MAX_GRAPHS` captured graphs stay alive (keyed by shapes, K, warm state ...): alternating
+    between them replays, it does not capture again.
     """
 
+    MAX_GRAPHS = 4
+
     def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None,
-                 candidates: int = 1, selector: Optional[TrajectorySelector] = None):
+                 candidates: int = 1, selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None):
         deterministic = getattr(scheduler, "_is_ddim", False) or getattr(scheduler, "deterministic", False)
         if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not deterministic):
             raise ValueError("GraphedSampler needs a deterministic sampler (DDIM with eta = 0, DPM-Solver++), or a DeviceNoise for "
                              "the DDPM sampler (noise=...)")
+        if warm is None and int(getattr(cfg.EVAL, "WARM_STEPS", 0)) > 0:
+            warm = WarmStart()                 # a sampler carries state from tick to tick: the config keys are enough
+        if warm is not None and warm.resolve(cfg)[0] > 0 and noise is None:
+            raise ValueError("GraphedSampler: WarmStart needs noise=DeviceNoise(...): the re-noise is drawn inside the warm-start kernel")
         self.model, self.scheduler, self.cfg, self.scale_xy, self.noise = model, scheduler, cfg, scale_xy, noise
-        self.candidates, self.selector = int(candidates), selector
+        self.candidates, self.selector, self.warm = int(candidates), selector, warm
+        self._graphs = {}                      # key -> the captured graph and its static buffers
         self._key = None
-        self._graph = None
+        self._graph = None                     # the graph of the last call
         self._sel = None
 
-    def _capture(self, image, target, init_trajs):
+    def _capture(self, image, target, init_trajs, motion):
         dev = image.device
+        warm = self.warm
         self.model.eval()
         self.scheduler.set_timesteps(self.cfg.EVAL.SAMPLE_STEPS, device=dev)   # host tables + device timesteps, once
+        g = SimpleNamespace()
         # the graph reads these device tensors on every replay: keep them alive even if somebody calls
         # scheduler.set_timesteps() again (which replaces the scheduler's own references)
-        self._timesteps = list(self.scheduler.timesteps)
-        self._img, self._init = image.clone(), None if init_trajs is None else init_trajs.clone()
-        self._tgt = None if target is None else target.clone()
-        run = lambda: generate_traj(self.model, self.scheduler, self.cfg, self._img, self._tgt, self._init,  # noqa: E731
+        g.timesteps = list(self.scheduler.timesteps)
+        g.img, g.init = image.clone(), None if init_trajs is None else init_trajs.clone()
+        g.tgt = None if target is None else target.clone()
+        g.motion = None if motion is None else motion.clone()
+        run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
-                                    candidates=self.candidates, selector=self.selector, return_selection=True)
+                                    candidates=self.candidates, selector=self.selector, return_selection=True,
+                                    warm=warm, motion=g.motion)
         tick = None if self.noise is None else self.noise.tick()
+        # the warm-up pass below is a real tick: it moves the noise stream on and overwrites the warm state.  Both are given
+        # back, so that the first replay is the next tick and starts from the result of the tick before it
+        valid = warm is not None and warm.valid
+        prev = warm.prev.clone() if valid else None
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):          # warm-up off the capture: lazy packs, workspaces, tile tables
+        with torch.cuda.stream(side):          # warm-up off the capture: lazy packs, workspaces, tile tables (and warm.prev)
             run()
         torch.cuda.current_stream(dev).wait_stream(side)
         if tick is not None:
             self.noise.seek(tick)              # the warm-up consumed a tick: give it back, so that the first replay is the next one
+        if warm is not None:
+            warm.valid = valid
+            if prev is not None:
+                warm.prev.copy_(prev)
         self.model._feat_cache = None          # the perception pass must be IN the graph (new frame every tick)
-        self._graph = torch.cuda.CUDAGraph()
+        g.graph = torch.cuda.CUDAGraph()
         # thread-local capture mode: a process group's watchdog thread (multi-rank runs) may query events while this
         # thread captures; in the default global mode that would invalidate the capture
-        with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
-            self._out, self._sel = run()
+        with torch.cuda.graph(g.graph, capture_error_mode="thread_local"):
+            g.out, g.sel = run()
         self.model._feat_cache = None          # the memo now points at the static frame buffer: drop it
-        self._pointers = self._model_pointers()
+        g.pointers = self._model_pointers()
+        return g
 
     def _model_pointers(self):
         """Addresses of the model-owned buffers the captured launches read and write (workspaces, packed weight images and
@@ -290,9 +446,15 @@ class GraphedSampler:
                      for t in (getattr(o, "_ws", None), getattr(o, "_packed", None), getattr(o, "_range_words", None)))
 
     def reset(self) -> None:
-        """Forget the captured graph (call after the model's weights changed: the weight images are packed outside
-        the graph, during the warm-up pass of the next capture)."""
+        """Forget the captured graphs (call after the model's weights changed: the weight images are packed outside
+        the graph, during the warm-up pass of the next capture).  The warm state is the WarmStart's: `warm.reset()`."""
+        self._graphs = {}
         self._key, self._graph, self._sel = None, None, None
+
+    @property
+    def captured(self) -> int:
+        """How many graphs are alive."""
+        return len(self._graphs)
 
     @property
     def last_selection(self) -> Optional[Selection]:
@@ -304,8 +466,10 @@ class GraphedSampler:
 
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
-                 init_trajs: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None) -> torch.Tensor:
         K, sel = _candidates(self.cfg, self.candidates, self.selector)
+        warm = self.warm
+        m_warm, shift, is_warm, motion = _warm_plan(self.cfg, warm, self.noise, init_trajs, image, K, motion)
         if init_trajs is None and self.noise is None:
             init_trajs = torch.randn((K * image.shape[0], self.cfg.MODEL.HORIZON, self.cfg.MODEL.TRANSITION_DIM),
                                      device=image.device)
@@ -313,24 +477,34 @@ class GraphedSampler:
         key = (tuple(image.shape), None if target is None else tuple(target.shape),
                None if init_trajs is None else tuple(init_trajs.shape), image.device,
                self.cfg.EVAL.SAMPLE_STEPS, self.cfg.GUIDANCE.USE_COND, K,
-               None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus))   # baked into the select node
-        if key != self._key or self._graph is None or self._pointers != self._model_pointers():
-            self._capture(image, target, init_trajs)
-            self._key = key
+               None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus),   # baked into the select node
+               # a cold and a warm graph (m_warm == 0: the loop as it was); baked into the warm-start node
+               None if m_warm == 0 else (m_warm, shift, is_warm, motion is None, id(warm)))
+        g = self._graphs.get(key)
+        if g is None or g.pointers != self._model_pointers():
+            self._graphs.pop(key, None)
+            while len(self._graphs) >= self.MAX_GRAPHS:
+                self._graphs.pop(next(iter(self._graphs)))        # the oldest capture
+            g = self._graphs[key] = self._capture(image, target, init_trajs, motion)
         else:
-            self._img.copy_(image)
+            g.img.copy_(image)
             if init_trajs is not None:
-                self._init.copy_(init_trajs)
+                g.init.copy_(init_trajs)
             if target is not None:
-                self._tgt.copy_(target)
+                g.tgt.copy_(target)
+            if motion is not None:
+                g.motion.copy_(motion)
+        self._key, self._graph, self._sel = key, g.graph, g.sel
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured
         guard = getattr(self.model, "range_guard", "off") == "raise"
         if guard:
             self.model.clear_range_status()
-        self._graph.replay()
+        g.graph.replay()
+        if m_warm > 0:
+            warm.valid = True                  # the replay ended with the copy into warm.prev
         if guard:
             bad = self.model.range_status()
             if bad:
                 raise AdxRangeError(bad)
-        return self._out.clone()
+        return g.out.clone()

@@ -148,6 +148,7 @@ class SchedulerBase:
         self.num_inference_steps = None
         self.custom_timesteps = False
         self._dev_tables = {}
+        self.begin_index = 0
         self.timesteps = TimestepSequence(list(range(num_train_timesteps))[::-1])
 
     # -- diffusers API ---------------------------------------------------------------------------
@@ -169,6 +170,25 @@ class SchedulerBase:
         ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
         ts += self.config.steps_offset
         self.timesteps = TimestepSequence(ts.tolist(), device=device)
+        self.begin_index = 0
+
+    def set_begin_index(self, begin_index: int = 0):
+        """The schedule begins in the middle (the name diffusers gives it): the caller's loop runs `timesteps[begin_index:]`
+        on a sample noised to `timesteps[begin_index]` (`noise_level`).  The DDIM / DDPM steps depend on `t` alone, so they
+        only record the index; a multistep solver takes step `begin_index` without history.  `set_timesteps` resets it to 0."""
+        i0 = int(begin_index)
+        if not 0 <= i0 < len(self.timesteps):
+            raise ValueError(f"begin_index {begin_index} is outside the schedule's {len(self.timesteps)} timesteps")
+        self.begin_index = i0
+
+    def noise_level(self, timestep):
+        """(sqrt(abar_t), sqrt(1 - abar_t)) as Python floats holding the fp32 values of the tables `add_noise` gathers from:
+        the pair `adx_warm_init` takes by value."""
+        t = timestep_to_int(timestep)
+        if not 0 <= t < self.config.num_train_timesteps:
+            raise ValueError(f"timestep {t} is outside the {self.config.num_train_timesteps} train timesteps")
+        sa, sb = self._tables("cpu")
+        return float(sa[t]), float(sb[t])
 
     def previous_timestep(self, timestep):
         n = self.num_inference_steps if self.num_inference_steps else self.config.num_train_timesteps
@@ -194,10 +214,14 @@ class SchedulerBase:
 
     # -- helpers -----------------------------------------------------------------------------------
     def _tables(self, device):
+        """(sqrt(abar), sqrt(1 - abar)) [num_train_timesteps] on `device`: built once on the host, every device's pair a copy of
+        that one (`add_noise` gathers from it on the device, `noise_level` reads one entry of it on the host)."""
         key = str(device)
         if key not in self._dev_tables:
-            ac = self.alphas_cumprod
-            self._dev_tables[key] = ((ac ** 0.5).to(device), ((1 - ac) ** 0.5).to(device))
+            if "cpu" not in self._dev_tables:
+                ac = self.alphas_cumprod
+                self._dev_tables["cpu"] = (ac ** 0.5, (1 - ac) ** 0.5)
+            self._dev_tables[key] = tuple(t.to(device) for t in self._dev_tables["cpu"])
         return self._dev_tables[key]
 
     def _check_step_inputs(self, model_output, sample, cfg_combine=False):

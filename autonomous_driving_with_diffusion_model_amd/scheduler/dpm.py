@@ -12,7 +12,8 @@ reference has no vectors for this sampler.
 The solver has one step of memory: a second-order step reads the x0 the previous step produced.  The scheduler keeps a
 reference to that tensor and to the index of the call that wrote it; the index of a call is found from the timestep's VALUE
 (not counted), index 0 never reads history, so loops may be run any number of times -- and captured into a graph -- without
-a reset between them.
+a reset between them.  `set_begin_index(i0)` moves that first, history-free step to index i0: step i0 is then first order,
+the steps after it are what they are in the full schedule.
 """
 from __future__ import annotations
 
@@ -100,6 +101,7 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
         self.timesteps = TimestepSequence(ts.tolist(), device=device)
         self._index = {t: i for i, t in enumerate(ts.tolist())}
         self._last = None
+        self.begin_index = 0
 
     def previous_timestep(self, timestep):
         raise NotImplementedError("the multistep solver steps along `timesteps`, not by a fixed stride")
@@ -140,7 +142,8 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
         c.r = float(sigma_t / sigma_s0)
         c.k = float(k)
         c.half_k = float(0.5 * k)
-        second = self.config.solver_order == 2 and 0 < i < n - 1
+        # the first executed step (set_begin_index; 0 unless the schedule begins in the middle) has no history: first order
+        second = self.config.solver_order == 2 and self.begin_index < i < n - 1
         c.second_order = int(second)
         if second:
             alpha_s1, sigma_s1 = self._sigma_to_alpha_sigma_t(self.sigmas[i - 1])

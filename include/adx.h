@@ -686,6 +686,40 @@ typedef struct adx_select_cfg {
 int adx_traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index,
                     float* best, adx_stream s);
 
+/* ------------------------------------------------------------------------------------
+ * Warm start v1: a sampling tick's initial trajectory from the previous tick's result (receding-horizon warm starting).
+ * One launch, one thread per output element, no host decision; the stream's state is read through the pointer, so the call
+ * can be a node of a captured graph.  No reference counterpart: the reference's agents start every tick from noise
+ * (e2e_driving/diffusion_agent.py:94,181).  Callers and fixtures depend on this definition -- a change is a new version,
+ * never an edit.
+ *
+ *   prev     [prev_rows][H][D]: the last tick's result in the model's own units -- the clamped trajectory BEFORE xy scaling,
+ *            the units of selection cost v1.  Columns: 0, 1 = x, y; 2 = yaw relative to the first waypoint; 3.. = speed, controls.
+ *   rows     a multiple of prev_rows; output row r reads prev[r % prev_rows] (candidate-major: every candidate of a scene
+ *            starts from that scene's last winner).
+ *   shift    0 <= shift <= H - 1: the waypoints passed since the last tick.
+ *   motion   [prev_rows][3] = (tx, ty, phi), the caller's odometry in model units and radians, or NULL.
+ *   arithmetic  fp32, no contraction, every product and sum rounded on its own, in this order:
+ *     advance  j = h + shift.  j <= H-1: u[h][d] = prev[j][d].  Otherwise d < 2: u[h][d] = prev[H-1][d] +
+ *              (float)(j - (H-1)) * (prev[H-1][d] - prev[H-2][d]);  d >= 2: u[h][d] = prev[H-1][d] (the tail is held).
+ *     re-base  with o = prev[shift].  motion NULL: w = u[h][d] - o[d] for d < min(D, 3); columns d >= 3 are u unchanged (no
+ *              rotation is evaluated, nothing is multiplied by 1).  With motion: qx = u[h][0] - tx, qy = u[h][1] - ty (a
+ *              missing y column counts as 0), c = cosf(phi), s = sinf(phi), x' = c * qx + s * qy, y' = -(s * qx) + c * qy;
+ *              column 2 is still u - o[2].
+ *     clamp    to [-1, 1]; NaN propagates.
+ *     noise    v = sqrt_ab * w + sqrt_1mab * z, z = the stream's normal at slot ADX_NOISE_INIT_SLOT and logical element
+ *              ((row_offset + r) * H + h) * D + d (a warm tick makes no cold initial draw: the slot is free in that tick).
+ *     zero_first != 0: v = 0 where h == 0 && d < 3.
+ *   sqrt_ab, sqrt_1mab: sqrt(abar_tau), sqrt(1 - abar_tau) of the level tau the schedule's suffix starts at, by value.
+ *
+ * ADX_ERR_INVALID before any GPU work: H outside 2..64, D outside 1..16, shift outside 0..H-1, rows not a positive multiple of
+ * prev_rows, rows that leave the stream's 2^34 elements, more elements than the kernel's 32-bit index holds, a NULL pointer
+ * other than motion, an output that overlaps prev.
+ * -----------------------------------------------------------------------------------*/
+int adx_warm_init(const float* prev, int32_t prev_rows, const float* motion, float* out, int32_t rows, int32_t horizon,
+                  int32_t dim, int32_t shift, float sqrt_ab, float sqrt_1mab, const uint32_t* noise_state, int64_t row_offset,
+                  int32_t zero_first, adx_stream s);
+
 /* add_noise (train.py:234) fused with the [...,0,:3] = 0 of train.py:235 when zero_first != 0.
  * sqrt_ab / sqrt_1mab are the host tables sqrt(abar), sqrt(1-abar) of length n_train. */
 int adx_add_noise(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
