@@ -9,6 +9,8 @@ Public surface mirrors the reference's packages:
     DeviceNoise                                       (no reference counterpart: in-kernel sampler noise, noise.py)
     TrajectorySelector, Selection                     (no reference counterpart: best-of-K sampling, control/select.py)
     WarmStart                                         (no reference counterpart: receding-horizon warm starting, sampling.py)
+    DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
+                                                       control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
 All compute runs in libadx.so (hand-written HIP for gfx950); there is no CPU fallback.
 """
@@ -26,7 +28,8 @@ from . import _lib  # noqa: F401,E402
 from .noise import DeviceNoise  # noqa: E402
 from .scheduler import GuidanceDPMSolverMultistepScheduler  # noqa: E402
 from .control.select import Selection, TrajectorySelector  # noqa: E402
+from .control.device import DeviceController  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
-           "TrajectorySelector", "Selection", "WarmStart"]
+           "TrajectorySelector", "Selection", "WarmStart", "DeviceController"]

@@ -74,6 +74,13 @@ class SelectCfg(C.Structure):
                 ("w_consensus", f32)]
 
 
+class ControlCfg(C.Structure):
+    _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
+                [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
+                                    "speed_kd", "aim_dist", "angle_thresh", "dist_thresh", "brake_speed", "brake_ratio", "clip_delta",
+                                    "max_throttle")])
+
+
 _SIGS = {
     "adx_version": (i32, []),
     "adx_last_error": (C.c_char_p, []),
@@ -174,6 +181,9 @@ _SIGS = {
     "adx_ddpm_step_rng": (i32, [C.POINTER(StepCoef), vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, i32, vp]),
     "adx_dpm_step": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "adx_traj_select": (i32, [C.POINTER(SelectCfg), vp, vp, vp, vp, vp, vp]),
+    "adx_control_state_bytes": (C.c_size_t, [i32, i32, i32]),
+    "adx_control_step": (i32, [C.POINTER(ControlCfg), vp, vp, vp, vp, vp, vp]),
+    "adx_control_reset": (i32, [vp, i32, i32, i32, vp, vp]),
     "adx_noise_normal": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_words": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_advance": (i32, [vp, vp]),

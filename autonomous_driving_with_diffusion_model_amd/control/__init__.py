@@ -1,8 +1,9 @@
 from .controller import Controller, post_process_control
+from .device import DeviceController
 from .guidance import GuidanceLoss
 from .guidance_loss import TargetGuidance
 from .pid import PIDController
 from .select import Selection, TrajectorySelector
 
 __all__ = ["GuidanceLoss", "TargetGuidance", "Controller", "PIDController", "post_process_control", "Selection",
-           "TrajectorySelector"]
+           "TrajectorySelector", "DeviceController"]

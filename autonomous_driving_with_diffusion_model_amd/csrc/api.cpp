@@ -76,6 +76,10 @@ int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float
              int d, hipStream_t s);
 int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
                 hipStream_t s);
+size_t control_state_bytes(int scenes, int n_turn, int n_speed);
+int control_step(const adx_control_cfg* c, const float* traj, const float* velocity, const float* target, void* state,
+                 float* control, hipStream_t s);
+int control_reset(void* state, int scenes, int n_turn, int n_speed, const uint8_t* mask, hipStream_t s);
 int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);
 int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s);
 int noise_advance(uint32_t* state, hipStream_t s);
@@ -179,6 +183,16 @@ int adx_dpm_step(const adx_dpm_coef* c, const float* model_output, const float* 
 int adx_traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index,
                     float* best, adx_stream s) {
   return adx::traj_select(c, trajs, target, cost, index, best, (hipStream_t)s);
+}
+size_t adx_control_state_bytes(int32_t scenes, int32_t n_turn, int32_t n_speed) {
+  return adx::control_state_bytes(scenes, n_turn, n_speed);
+}
+int adx_control_step(const adx_control_cfg* c, const float* traj, const float* velocity, const float* target, void* state,
+                     float* control, adx_stream s) {
+  return adx::control_step(c, traj, velocity, target, state, control, (hipStream_t)s);
+}
+int adx_control_reset(void* state, int32_t scenes, int32_t n_turn, int32_t n_speed, const uint8_t* mask, adx_stream s) {
+  return adx::control_reset(state, scenes, n_turn, n_speed, mask, (hipStream_t)s);
 }
 int adx_noise_normal(const uint32_t* state, int32_t slot, int64_t first_elem, float* out, int64_t n, adx_stream s) {
   return adx::noise_normal(state, slot, first_elem, out, n, (hipStream_t)s);

@@ -17,6 +17,8 @@ A fourth has no counterpart in the callers: `candidates=K` draws K trajectories 
 still runs once per scene) and keeps the one a device-side cost prefers (control/select.py, "selection cost v1" of include/adx.h).
 A fifth has none either: `warm=WarmStart(steps=m)` starts a tick from the previous tick's result -- advanced, re-based, clamped
 and re-noised on the device ("warm start v1" of include/adx.h) -- and runs only the last m steps of the schedule.
+A sixth closes the tick: `controller=DeviceController(...)` turns the result into (throttle, steer, brake) per scene on the device
+("control v1" of include/adx.h, control/device.py), where the callers hand `traj[0, :4, :2]` to a host `Controller`.
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ import torch
 
 from . import _lib as L
 from ._lib import AdxRangeError
+from .control.device import DeviceController
 from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
 from .noise import DeviceNoise
@@ -131,6 +134,29 @@ def _warm_plan(cfg, warm: Optional[WarmStart], noise, init_trajs, image, K: int,
     return m, shift, True, motion
 
 
+def _control_plan(cfg, controller: Optional[DeviceController], velocity, image, has_target: bool):
+    """The velocity a controlled tick hands to its controller (None without one), every refusal raised here: beside `_warm_plan`'s,
+    before any launch, before a tick of the noise stream is consumed, before a capture opens."""
+    if controller is None:
+        if velocity is not None:
+            raise ValueError("generate_traj: `velocity` is the speed a controller reads; pass controller=DeviceController(...) with it")
+        return None
+    S = int(image.shape[0])
+    if controller.scenes != S or controller.device != image.device:
+        raise ValueError(f"the DeviceController holds the windows of {controller.scenes} scenes on {controller.device}, this tick is "
+                         f"{S} scenes on {image.device}; use a controller of its own for another batch or device")
+    controller.check(cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM, has_target)
+    if velocity is None:
+        if controller.source != "action":
+            raise ValueError("generate_traj: a controller with source='pid' needs `velocity` [S], the scenes' current speeds")
+        return None
+    if not torch.is_tensor(velocity) or tuple(velocity.shape) != (S,) or velocity.device != image.device or \
+            velocity.dtype != torch.float32:
+        what = (tuple(velocity.shape), velocity.dtype, velocity.device) if torch.is_tensor(velocity) else type(velocity).__name__
+        raise ValueError(f"velocity must be a float32 tensor [{S}] on {image.device}, got {what}")
+    return velocity
+
+
 def warm_init(prev: torch.Tensor, rows: int, shift: int, level: Tuple[float, float], noise: DeviceNoise,
               motion: Optional[torch.Tensor] = None, zero_first: bool = True) -> torch.Tensor:
     """One launch of `adx_warm_init` ("warm start v1", include/adx.h): [rows, H, D] from prev [prev_rows, H, D] under the
@@ -155,7 +181,8 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
                   step_noise: Optional[Callable[[int, tuple], torch.Tensor]] = None,
                   set_timesteps: bool = True, noise: Optional[DeviceNoise] = None, candidates: int = 1,
                   selector: Optional[TrajectorySelector] = None, return_selection: bool = False,
-                  warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None):
+                  warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
+                  controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None):
     """`noise`: a DeviceNoise.  The call is then one tick of the noise stream: `begin_tick()` first, the initial trajectory
     (when `init_trajs` is not given) from `INIT_SLOT`, and every scheduler step draws inside its kernel at the slot of its
     timestep -- no noise tensor, no torch generator.
@@ -174,7 +201,15 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     n = EVAL.SAMPLE_STEPS and i0 = n - m, `adx_warm_init` builds the K * S start rows from `warm.prev` (row r from scene r % S)
     and the optional `motion` [S, 3] = (tx, ty, phi) at the noise level of `timesteps[i0]`, `scheduler.set_begin_index(i0)`,
     and the loop runs `timesteps[i0:]` only; clamp, selection, scaling and the copy into `warm.prev` follow as on a cold tick.
-    Needs `noise` (the re-noise is the stream's INIT_SLOT draw of the tick).  m = 0 is `warm=None`."""
+    Needs `noise` (the re-noise is the stream's INIT_SLOT draw of the tick).  m = 0 is `warm=None`.
+
+    `controller` = a DeviceController built for S scenes on the image's device, `velocity` [S] = their current speeds (may be
+    left out with source='action'): the tick ends with one launch of `controller.step` on the clamped, unscaled [S, H, D] result
+    (the winners at K > 1) with `xy_scale = model.magic_num` and the scenes' targets ([S, 2] in the model's units; None: the
+    waypoint after the controller's last stands in).  The order at the end of a tick is fixed: clamp, selection, the copy
+    into `warm.prev`, the control launch, xy scaling.  The call then returns `(traj, control)` -- `(traj, selection, control)`
+    with `return_selection=True` -- with control [S, 3] = (throttle, steer, brake); `traj` is bit for bit what the call
+    without a controller returns.  Without a controller nothing changes."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     model.eval()
     device = image.device
@@ -193,6 +228,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         raise ValueError("generate_traj: pass `noise` (the in-kernel stream) or `step_noise` (injected tensors), not both")
     m_warm, shift, is_warm, motion = _warm_plan(cfg, warm, noise, init_trajs, image, K, motion,
                                                 None if set_timesteps else scheduler)
+    velocity = _control_plan(cfg, controller, velocity, image, target is not None)
     if noise is not None:
         noise.begin_tick()
     i0 = 0
@@ -249,22 +285,29 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     if K == 1:
         if m_warm > 0:
             warm._store(trajs)
+        if controller is not None:
+            control = controller.step(trajs, velocity, tgt, xy_scale=model.magic_num)
         if scale_xy:
             trajs[..., :2] *= model.magic_num
+        if controller is not None:
+            return (trajs, None, control) if return_selection else (trajs, control)
         return (trajs, None) if return_selection else trajs
     # the cost is taken in the model's own units (before xy scaling: the units of `target`)
     sel = selector(trajs, S, scene_tgt)
     best = sel.best
     if m_warm > 0:
         warm._store(best)
+    if controller is not None:
+        control = controller.step(best, velocity, scene_tgt, xy_scale=model.magic_num)
     if scale_xy:
         best[..., :2] *= model.magic_num
     if not return_selection:
-        return best
+        return best if controller is None else (best, control)
     cands = trajs.reshape(K, S, trajs.shape[1], trajs.shape[2])
     if scale_xy:
         cands[..., :2] *= model.magic_num
-    return best, Selection(best, sel.index, sel.cost, cands)
+    sel = Selection(best, sel.index, sel.cost, cands)
+    return (best, sel) if controller is None else (best, sel, control)
 
 
 def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device, noise=None,
@@ -371,12 +414,18 @@ class GraphedSampler:
     `warm.prev`, so replay k + 1 starts from replay k's result without leaving the device.  `motion` travels through a static
     buffer like `target`.  Up to `MAX_GRAPHS` captured graphs stay alive (keyed by shapes, K, warm state ...): alternating
     between them replays, it does not capture again.
+    `controller=DeviceController(...)`: the control launch is the graph's last kernel node (`generate_traj(controller=...)`);
+    `velocity` travels through a static buffer like `target` and `motion`, the call still returns the trajectory and
+    `last_control` the [S, 3] controls of the last replay.  The controller's windows live in its own device buffer, which the
+    graph reads and advances through its address: replay k of a fresh sampler sees the windows k eager ticks leave (the
+    capture's warm-up pass, a real tick, gives its sample back).
     """
 
     MAX_GRAPHS = 4
 
     def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None,
-                 candidates: int = 1, selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None):
+                 candidates: int = 1, selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
+                 controller: Optional[DeviceController] = None):
         deterministic = getattr(scheduler, "_is_ddim", False) or getattr(scheduler, "deterministic", False)
         if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not deterministic):
             raise ValueError("GraphedSampler needs a deterministic sampler (DDIM with eta = 0, DPM-Solver++), or a DeviceNoise for "
@@ -387,12 +436,14 @@ class GraphedSampler:
             raise ValueError("GraphedSampler: WarmStart needs noise=DeviceNoise(...): the re-noise is drawn inside the warm-start kernel")
         self.model, self.scheduler, self.cfg, self.scale_xy, self.noise = model, scheduler, cfg, scale_xy, noise
         self.candidates, self.selector, self.warm = int(candidates), selector, warm
+        self.controller = controller
         self._graphs = {}                      # key -> the captured graph and its static buffers
         self._key = None
         self._graph = None                     # the graph of the last call
         self._sel = None
+        self._ctl = None
 
-    def _capture(self, image, target, init_trajs, motion):
+    def _capture(self, image, target, init_trajs, motion, velocity=None):
         dev = image.device
         warm = self.warm
         self.model.eval()
@@ -404,15 +455,18 @@ class GraphedSampler:
         g.img, g.init = image.clone(), None if init_trajs is None else init_trajs.clone()
         g.tgt = None if target is None else target.clone()
         g.motion = None if motion is None else motion.clone()
+        g.vel = None if velocity is None else velocity.clone()
+        ctl = self.controller
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
                                     candidates=self.candidates, selector=self.selector, return_selection=True,
-                                    warm=warm, motion=g.motion)
+                                    warm=warm, motion=g.motion, controller=ctl, velocity=g.vel)
         tick = None if self.noise is None else self.noise.tick()
         # the warm-up pass below is a real tick: it moves the noise stream on and overwrites the warm state.  Both are given
         # back, so that the first replay is the next tick and starts from the result of the tick before it
         valid = warm is not None and warm.valid
         prev = warm.prev.clone() if valid else None
+        windows = None if ctl is None else ctl.state_snapshot()       # ... and pushes a sample into every PID window
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):          # warm-up off the capture: lazy packs, workspaces, tile tables (and warm.prev)
@@ -424,12 +478,14 @@ class GraphedSampler:
             warm.valid = valid
             if prev is not None:
                 warm.prev.copy_(prev)
+        if windows is not None:
+            ctl.state_restore(windows)
         self.model._feat_cache = None          # the perception pass must be IN the graph (new frame every tick)
         g.graph = torch.cuda.CUDAGraph()
         # thread-local capture mode: a process group's watchdog thread (multi-rank runs) may query events while this
         # thread captures; in the default global mode that would invalidate the capture
         with torch.cuda.graph(g.graph, capture_error_mode="thread_local"):
-            g.out, g.sel = run()
+            g.out, g.sel, g.ctl = run() if ctl is not None else (*run(), None)
         self.model._feat_cache = None          # the memo now points at the static frame buffer: drop it
         g.pointers = self._model_pointers()
         return g
@@ -449,7 +505,7 @@ class GraphedSampler:
         """Forget the captured graphs (call after the model's weights changed: the weight images are packed outside
         the graph, during the warm-up pass of the next capture).  The warm state is the WarmStart's: `warm.reset()`."""
         self._graphs = {}
-        self._key, self._graph, self._sel = None, None, None
+        self._key, self._graph, self._sel, self._ctl = None, None, None, None
 
     @property
     def captured(self) -> int:
@@ -464,12 +520,21 @@ class GraphedSampler:
             return None
         return Selection(None, self._sel.index.clone(), self._sel.cost.clone())
 
+    @property
+    def last_control(self) -> Optional[torch.Tensor]:
+        """A clone of the static control [S, 3] = (throttle, steer, brake) as the last replay left it; None before the first
+        call and without a controller."""
+        return None if self._ctl is None else self._ctl.clone()
+
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
-                 init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None,
+                 velocity: Optional[torch.Tensor] = None) -> torch.Tensor:
         K, sel = _candidates(self.cfg, self.candidates, self.selector)
         warm = self.warm
         m_warm, shift, is_warm, motion = _warm_plan(self.cfg, warm, self.noise, init_trajs, image, K, motion)
+        ctl = self.controller
+        velocity = _control_plan(self.cfg, ctl, velocity, image, target is not None)
         if init_trajs is None and self.noise is None:
             init_trajs = torch.randn((K * image.shape[0], self.cfg.MODEL.HORIZON, self.cfg.MODEL.TRANSITION_DIM),
                                      device=image.device)
@@ -479,13 +544,15 @@ class GraphedSampler:
                self.cfg.EVAL.SAMPLE_STEPS, self.cfg.GUIDANCE.USE_COND, K,
                None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus),   # baked into the select node
                # a cold and a warm graph (m_warm == 0: the loop as it was); baked into the warm-start node
-               None if m_warm == 0 else (m_warm, shift, is_warm, motion is None, id(warm)))
+               None if m_warm == 0 else (m_warm, shift, is_warm, motion is None, id(warm)),
+               # the controller's state address and every setting are baked into the control node
+               None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), velocity is None))
         g = self._graphs.get(key)
         if g is None or g.pointers != self._model_pointers():
             self._graphs.pop(key, None)
             while len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.pop(next(iter(self._graphs)))        # the oldest capture
-            g = self._graphs[key] = self._capture(image, target, init_trajs, motion)
+            g = self._graphs[key] = self._capture(image, target, init_trajs, motion, velocity)
         else:
             g.img.copy_(image)
             if init_trajs is not None:
@@ -494,7 +561,9 @@ class GraphedSampler:
                 g.tgt.copy_(target)
             if motion is not None:
                 g.motion.copy_(motion)
-        self._key, self._graph, self._sel = key, g.graph, g.sel
+            if velocity is not None:
+                g.vel.copy_(velocity)
+        self._key, self._graph, self._sel, self._ctl = key, g.graph, g.sel, g.ctl
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured
         guard = getattr(self.model, "range_guard", "off") == "raise"

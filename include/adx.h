@@ -720,6 +720,75 @@ int adx_warm_init(const float* prev, int32_t prev_rows, const float* motion, flo
                   int32_t dim, int32_t shift, float sqrt_ab, float sqrt_1mab, const uint32_t* noise_state, int64_t row_offset,
                   int32_t zero_first, adx_stream s);
 
+/* ------------------------------------------------------------------------------------
+ * Control v1: waypoints -> (throttle, steer, brake) on the device, the step after the sampling loop in the reference's agents
+ * (control/controller.py:29-76 `control_pid`, control/pid.py, `post_process_control` of interact.py:218-229 and
+ * e2e_driving/diffusion_agent.py:268-277).  One launch per tick for all scenes, no host decision; the PID windows live in
+ * device memory and are read and advanced through a pointer, so the call can be a node of a captured graph and a replay
+ * carries the windows on.  Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ * Per scene s, all arithmetic in fp32, no contraction, every product, sum, division and square root rounded on its own, in the
+ * order written; fixed evaluation order, no atomics.  clip(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x): a NaN goes through.
+ * |v| = sqrtf(v.x * v.x + v.y * v.y).
+ *
+ *   traj      [S][H][D], the model's own units: the clamped result BEFORE xy scaling, the units of selection cost v1.
+ *   waypoints wp[i] = (sign_x * (xy_scale * traj[s][i][0]), xy_scale * traj[s][i][1]), i = 0..W-1, 2 <= W <= H; a missing
+ *             y column (D = 1) counts as 0.  sign_x = -1 is the callers' `renew_traj`, xy_scale their `model.magic_num`.
+ *   target    tgt = (sign_x * (target_scale * target[s][0]), target_scale * target[s][1]); target NULL: waypoint W of the same
+ *             trajectory under the waypoint scaling (interact.py's `traj[0, 4, :2]`; needs W < H).
+ *   desired   the sum over i = 0..W-2, in index order, of (|wp[i+1] - wp[i]| * 2) / (float)(W - 1).
+ *   aim       wp[i*], i* = the smallest i in 0..W-2 that minimises key_i = |aim_dist - |(wp[i+1] + wp[i]) / 2||, among the i
+ *             with key_i < |aim_dist - 1e5| (strictly); i* = 0 when none qualifies.  A NaN key never qualifies.  (The
+ *             reference's sequential rule -- start from best = 1e5, take i whenever it is strictly closer -- restated.)
+ *   heading   heading(v) = (((float)(pi/2) - atan2f(v.y, v.x)) * (float)(180/pi)) / 90:  a = heading(aim),
+ *             a_last = heading(wp[W-1] - wp[W-2]), a_t = heading(tgt).
+ *   to_target |a_t| < |a|  or  (|a_t - a_last| > angle_thresh and tgt.y < dist_thresh).
+ *   steer     clip(PID_turn(to_target ? a_t : a), -1, 1).
+ *   brake     desired < brake_speed  or  speed / desired > brake_ratio, speed = velocity[s].
+ *   throttle  delta = clip(desired - speed, 0, clip_delta); r = PID_speed(delta) (stepped on every tick, braking or not);
+ *             throttle = brake ? 0 : clip(r, 0, max_throttle).
+ *   PID(e)    the window holds the last n samples, oldest first c_0 .. c_{n-1} with c_{n-1} = e, and starts as n zeros;
+ *             previous = c_{n-2}.  n >= 2: (k_p * e + k_i * mean) + k_d * (e - previous).  n = 1: k_p * e (control/pid.py: a
+ *             window of one sample has zero I and D terms).
+ *   mean      p_l = c_l + c_{l+64} + c_{l+128} + c_{l+192} (left to right, the j < n only; no such j: +0) for l = 0..63, then six
+ *             rounds p_l = p_l + p_{l ^ off}, off = 32, 16, 8, 4, 2, 1, and mean = p_0 / (float)n.
+ *   post      0: none.  1 (e2e agent): brake < 0.05f -> brake = 0; throttle > brake -> brake = 0; brake > 0.5f -> throttle = 0.
+ *             2 (interact.py): the same two first rules; brake > 0.5f -> brake = 1, steer = 0, throttle = 0.
+ *   source    0: the PID path above.  1: the callers' D > 2 path, (throttle, steer, brake) = post(traj[s][0][D-3..D-1]) bit for
+ *             bit; it touches no PID state and needs D >= 3.
+ *   control   [S][3] = (throttle, steer, brake); brake is 0.0 or 1.0 on the PID path.
+ *   state     one device buffer of adx_control_state_bytes(scenes, n_turn, n_speed) bytes, opaque to callers, all zero bytes =
+ *             fresh windows.  It holds both windows and their ring positions per scene; every launch reads and advances it
+ *             through the pointer -- nothing about it is a by-value argument.  (Today: per scene 2 + n_turn + n_speed 32-bit
+ *             words = the two next-slot indices, the turn ring, the speed ring; an index is taken modulo its ring's length.)
+ *   rounding  the controls are defined up to fp32 rounding of the operations above and the accuracy of atan2f
+ *             (tests/control_ref.py restates them in fp64 and derives the bound); the three decisions -- i*, to_target, brake --
+ *             exactly wherever their margins exceed that rounding.  A scene's result does not depend on the other scenes of
+ *             the launch, and the same input and state give the same bits on every launch.
+ *
+ * ADX_ERR_INVALID before any GPU work: W outside 2..H, H outside 2..64, D outside 1..16, source = 1 with D < 3, source or post
+ * not one of the above, a NULL target with W = H, a window length outside 1..256, scenes outside 1..65535, a NULL pointer
+ * other than target (step) or mask (reset), control or the state overlapping an input or each other.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_CONTROL_SOURCE_PID 0
+#define ADX_CONTROL_SOURCE_ACTION 1
+#define ADX_CONTROL_POST_NONE 0
+#define ADX_CONTROL_POST_AGENT 1
+#define ADX_CONTROL_POST_INTERACT 2
+#define ADX_CONTROL_MAX_WINDOW 256
+typedef struct adx_control_cfg {
+  int32_t scenes, horizon, dim, waypoints, n_turn, n_speed, source, post;
+  float sign_x, xy_scale, target_scale;
+  float turn_kp, turn_ki, turn_kd, speed_kp, speed_ki, speed_kd;
+  float aim_dist, angle_thresh, dist_thresh, brake_speed, brake_ratio, clip_delta, max_throttle;
+} adx_control_cfg;
+size_t adx_control_state_bytes(int32_t scenes, int32_t n_turn, int32_t n_speed);   /* 0 for a value out of range */
+/* traj [scenes][H][D]; velocity [scenes]; target [scenes][2] or NULL; state as above; control [scenes][3]. */
+int adx_control_step(const adx_control_cfg* c, const float* traj, const float* velocity, const float* target, void* state,
+                     float* control, adx_stream s);
+/* Fresh windows for the scenes with mask[s] != 0 (mask: [scenes] bytes on the device, NULL = every scene); a capturable launch. */
+int adx_control_reset(void* state, int32_t scenes, int32_t n_turn, int32_t n_speed, const uint8_t* mask, adx_stream s);
+
 /* add_noise (train.py:234) fused with the [...,0,:3] = 0 of train.py:235 when zero_first != 0.
  * sqrt_ab / sqrt_1mab are the host tables sqrt(abar), sqrt(1-abar) of length n_train. */
 int adx_add_noise(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
