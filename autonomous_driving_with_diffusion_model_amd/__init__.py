@@ -9,6 +9,7 @@ Public surface mirrors the reference's packages:
     DeviceNoise                                       (no reference counterpart: in-kernel sampler noise, noise.py)
     TrajectorySelector, Selection                     (no reference counterpart: best-of-K sampling, control/select.py)
     WarmStart                                         (no reference counterpart: receding-horizon warm starting, sampling.py)
+    Pin                                               (no reference counterpart: waypoints held through a tick, pin.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -29,7 +30,8 @@ from .noise import DeviceNoise  # noqa: E402
 from .scheduler import GuidanceDPMSolverMultistepScheduler  # noqa: E402
 from .control.select import Selection, TrajectorySelector  # noqa: E402
 from .control.device import DeviceController  # noqa: E402
+from .pin import Pin  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
-           "TrajectorySelector", "Selection", "WarmStart", "DeviceController"]
+           "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin"]

@@ -69,6 +69,11 @@ class DpmCoef(C.Structure):
                 ("free_scale", f32), ("zero_first", i32)]
 
 
+class PinDesc(C.Structure):
+    """adx_pin ("pinned waypoints v1", include/adx.h)."""
+    _fields_ = [("known", vp), ("mask", vp), ("known_rows", i32), ("c_known", f32), ("c_known_noise", f32), ("known_noise", i32)]
+
+
 class SelectCfg(C.Structure):
     _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("w_goal", f32), ("w_smooth", f32),
                 ("w_consensus", f32)]
@@ -195,6 +200,10 @@ _SIGS = {
 _LAZY_SIGS = {
     "adx_conv2d_pack_ds": (i32, [i32, i32, vp, vp, vp]),
     "adx_conv2d_block_s2_cells": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "adx_ddim_step_pin": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_ddpm_step_pin": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_dpm_step_pin": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_pin_apply": (i32, [vp, C.POINTER(PinDesc), vp, i64, i32, i32, i32, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)

@@ -57,8 +57,9 @@ def create_cfg() -> CfgNode:
     # candidates per scene and the selector's (w_goal, w_smooth, w_consensus); 1 = one sample per scene, as the reference
     # WARM_STEPS / WARM_SHIFT: warm starting (no reference counterpart; sampling.WarmStart) -- the steps a warm tick runs
     # (0 = off: every tick starts from noise, as the reference) and the waypoints passed between two ticks
+    # PIN_MODE: what a Pin whose mode is None does (no reference counterpart; pin.py) -- "clean" or "repaint"
     c.EVAL = CfgNode(BATCH_SIZE=4, ETA=0, CHECKPOINT=None, SCHEDULER="ddim", SAMPLE_STEPS=100, CANDIDATES=1,
-                     SELECT=(1.0, 0.0, 0.0), WARM_STEPS=0, WARM_SHIFT=1)
+                     SELECT=(1.0, 0.0, 0.0), WARM_STEPS=0, WARM_SHIFT=1, PIN_MODE="clean")
     # post-sampling control (reference config.py:67-86)
     c.PID = CfgNode(TURN_KP=1, TURN_KI=0.5, TURN_KD=1.0, TURN_N=40, SPEED_KP=5, SPEED_KI=0.5, SPEED_KD=1.0, SPEED_N=40)
     c.CONTROL = CfgNode(AIM_DIST=4.0, ANGLE_THRESH=0.3, DIST_THRESH=10, BRAKE_SPEED=0.4, BRAKE_RATIO=1.1, CLIP_DELTA=0.25,

@@ -74,6 +74,13 @@ int ddpm_step_rng(const adx_step_coef* c, const float* mo, const float* x, const
                   const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
 int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, float* prev, float* x0, int b, int h,
              int d, hipStream_t s);
+int ddim_step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
+                  int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s);
+int ddpm_step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
+                  int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s);
+int dpm_step_pin(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, const uint32_t* ns, int32_t slot,
+                 int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s);
+int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int b, int h, int d, hipStream_t s);
 int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
                 hipStream_t s);
 size_t control_state_bytes(int scenes, int n_turn, int n_speed);
@@ -179,6 +186,28 @@ int adx_ddpm_step_rng(const adx_step_coef* c, const float* model_output, const f
 int adx_dpm_step(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                  float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
   return adx::dpm_step(c, model_output, sample, prev_x0, prev_sample, x0, batch, horizon, dim, (hipStream_t)s);
+}
+int adx_ddim_step_pin(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                      const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev, float* x0,
+                      int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::ddim_step_pin(c, model_output, sample, noise, noise_state, slot, row_offset, pin, prev, x0, batch, horizon, dim,
+                            (hipStream_t)s);
+}
+int adx_ddpm_step_pin(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                      const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev, float* x0,
+                      int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::ddpm_step_pin(c, model_output, sample, noise, noise_state, slot, row_offset, pin, prev, x0, batch, horizon, dim,
+                            (hipStream_t)s);
+}
+int adx_dpm_step_pin(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                     const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev_sample,
+                     float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::dpm_step_pin(c, model_output, sample, prev_x0, noise_state, slot, row_offset, pin, prev_sample, x0, batch, horizon,
+                           dim, (hipStream_t)s);
+}
+int adx_pin_apply(float* x, const adx_pin* pin, const uint32_t* noise_state, int64_t row_offset, int32_t batch, int32_t horizon,
+                  int32_t dim, adx_stream s) {
+  return adx::pin_apply(x, pin, noise_state, row_offset, batch, horizon, dim, (hipStream_t)s);
 }
 int adx_traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index,
                     float* best, adx_stream s) {

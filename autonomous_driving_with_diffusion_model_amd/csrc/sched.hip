@@ -17,10 +17,37 @@
 // reference's path: torch.randn, or an injected variance_noise), or the counter-based noise stream of csrc/noise.h, evaluated
 // in the kernel where the tensor element would be read (adx_*_step_rng: no launch, no allocation, no [B,H,D] round trip, and a
 // captured graph draws fresh noise on every replay because the stream's state is read through a pointer).
+//
+// "Pinned waypoints v1" (include/adx.h) is a compile-time variant of both step kernels (PIN): the finished prev_sample is blended
+// with the caller's known trajectory under a mask before zero_first has the last word.  The unpinned instantiations do not read
+// the pin fields, which sit behind every field they do read: their code is what it was.
 #include "adx_common.h"
 #include "noise.h"
 
 namespace adx {
+
+// Pinned waypoints v1: known / mask [known_rows][H][D], `span` = known_rows * H * D: element e of a launch reads e % span, i.e. row
+// r reads known row r % known_rows
+struct PinArgs {
+  const float* known;
+  const float* mask;
+  int span;
+  float c_known, c_known_noise;
+  int known_noise;
+};
+
+// prev = mask * kp + (1 - mask) * prev, kp = c_known * known + (known_noise ? c_known_noise * z : 0): the RePaint blend of the
+// inpainting steps below, every product and sum rounded on its own
+__device__ __forceinline__ float pin_blend(const PinArgs& p, int e, float z, float prev) {
+#pragma clang fp contract(off)
+  const int ke = e % p.span;
+  const float k0 = p.c_known * p.known[ke];
+  const float k1 = p.known_noise ? p.c_known_noise * z : 0.f;
+  const float kp = k0 + k1;
+  const float mk = p.mask[ke];
+  const float u = mk * kp, v = (1.0f - mk) * prev;
+  return u + v;
+}
 
 struct StepArgs {
   adx_step_coef c;
@@ -36,6 +63,8 @@ struct StepArgs {
   const uint32_t* ns;
   uint32_t slot;
   uint64_t base;
+  // pinned waypoints v1 (PIN kernels only)
+  PinArgs pin;
 };
 
 __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
@@ -43,7 +72,7 @@ __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
   return v < lo ? lo : (v > hi ? hi : v);
 }
 
-template <bool DDPM, bool RNG>
+template <bool DDPM, bool RNG, bool PIN>
 __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -79,7 +108,8 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
   float zn;
   if (RNG) {
     // the element's index in the LOGICAL tensor, not in this launch: a shard of rows draws what the full batch draws there
-    const bool need = c.add_noise || (c.inpaint && c.known_noise && a.tgt != nullptr && a.mask != nullptr);
+    const bool need = c.add_noise || (c.inpaint && c.known_noise && a.tgt != nullptr && a.mask != nullptr) ||
+                      (PIN && a.pin.known_noise);
     zn = need ? noise_normal_at(a.ns, a.slot, a.base + (uint64_t)e) : 0.f;
   } else {
     zn = (a.z != nullptr) ? a.z[e] : 0.f;
@@ -124,28 +154,59 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
       prev = u + v;
     }
   }
+  if (PIN) prev = pin_blend(a.pin, e, zn, prev);      // the step's own z: no second draw
   if (c.zero_first) {
     const int d = e % a.dim;
     const int h = (e / a.dim) % a.horizon;
     if (h == 0 && d < 3) prev = 0.f;
   }
   a.prev[e] = prev;
-  if (a.x0 != nullptr) a.x0[e] = x0;
+  if (a.x0 != nullptr) a.x0[e] = x0;          // as computed: never pinned
 }
 
 // e >> 2 is the stream's 32-bit counter word: logical elements live in [0, 2^34)
 static const int64_t kNoiseElems = (int64_t)1 << 34;
 
-template <bool DDPM, bool RNG>
+static bool byte_ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + qn && b < a + pn;
+}
+
+// the refusals of "pinned waypoints v1" that every pinned launch shares; `out2` may be null
+static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const float* out, const float* out2, int batch, int horizon,
+                     int dim, PinArgs* p) {
+  ADX_REQUIRE(pin->known != nullptr && pin->mask != nullptr, "%s: null known or mask", what);
+  ADX_REQUIRE(pin->known_rows >= 1 && batch % pin->known_rows == 0, "%s: batch %d must be a positive multiple of known_rows %d", what,
+              batch, pin->known_rows);
+  ADX_REQUIRE(!pin->known_noise || has_noise, "%s: known_noise is set and there is no noise tensor and no noise state", what);
+  const int64_t per = (int64_t)horizon * dim;
+  ADX_REQUIRE((int64_t)batch * per <= (int64_t)0x3fffffff, "%s: %lld elements do not fit the kernel's 32-bit index", what,
+              (long long)batch * per);
+  const size_t kn = (size_t)pin->known_rows * per * sizeof(float), on = (size_t)batch * per * sizeof(float);
+  ADX_REQUIRE(!byte_ranges_overlap(out, on, pin->known, kn) && !byte_ranges_overlap(out, on, pin->mask, kn) &&
+              (out2 == nullptr || (!byte_ranges_overlap(out2, on, pin->known, kn) && !byte_ranges_overlap(out2, on, pin->mask, kn))),
+              "%s: an output overlaps known or mask", what);
+  p->known = pin->known; p->mask = pin->mask; p->span = (int)(pin->known_rows * per);
+  p->c_known = pin->c_known; p->c_known_noise = pin->c_known_noise; p->known_noise = pin->known_noise != 0;
+  return ADX_OK;
+}
+
+template <bool DDPM, bool RNG, bool PIN>
 static int step_launch(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
-                       int64_t row_offset, const float* tgt, const float* mask, float* prev, float* x0, int batch, int horizon,
-                       int dim, hipStream_t s) {
+                       int64_t row_offset, const float* tgt, const float* mask, const adx_pin* pin, float* prev, float* x0, int batch,
+                       int horizon, int dim, hipStream_t s) {
   ADX_REQUIRE(c && mo && x && prev, "scheduler step: null tensor");
   ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1, "scheduler step: empty shape");
   ADX_REQUIRE(c->prediction_type >= 0 && c->prediction_type <= 2,
               "prediction_type given as %d must be one of `epsilon`, `sample`, or `v_prediction`", c->prediction_type);
   StepArgs a;
   a.ns = nullptr; a.slot = 0; a.base = 0;
+  a.pin = PinArgs{nullptr, nullptr, 1, 0.f, 0.f, 0};
+  if (PIN) {
+    ADX_REQUIRE(!c->inpaint, "scheduler step: c->inpaint (the inpainting schedulers' blend) and a pin are two blends of one step");
+    const int rc = pin_check(pin, "scheduler step", RNG || z != nullptr, prev, x0, batch, horizon, dim, &a.pin);
+    if (rc != ADX_OK) return rc;
+  }
   if (RNG) {
     ADX_REQUIRE(ns != nullptr, "scheduler step: null noise state");
     ADX_REQUIRE(row_offset >= 0, "scheduler step: negative row_offset %lld", (long long)row_offset);
@@ -161,26 +222,47 @@ static int step_launch(const adx_step_coef* c, const float* mo, const float* x, 
   a.c = *c;
   a.mo = mo; a.x = x; a.z = z; a.tgt = tgt; a.mask = mask; a.prev = prev; a.x0 = x0;
   a.total = batch * horizon * dim; a.horizon = horizon; a.dim = dim;
-  step_kernel<DDPM, RNG><<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
+  step_kernel<DDPM, RNG, PIN><<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
 
 int ddim_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
               const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<false, false>(c, mo, x, z, nullptr, 0, 0, tgt, mask, prev, x0, b, h, d, s);
+  return step_launch<false, false, false>(c, mo, x, z, nullptr, 0, 0, tgt, mask, nullptr, prev, x0, b, h, d, s);
 }
 int ddpm_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
               const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<true, false>(c, mo, x, z, nullptr, 0, 0, tgt, mask, prev, x0, b, h, d, s);
+  return step_launch<true, false, false>(c, mo, x, z, nullptr, 0, 0, tgt, mask, nullptr, prev, x0, b, h, d, s);
 }
 int ddim_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
                   const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<false, true>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, prev, x0, b, h, d, s);
+  return step_launch<false, true, false>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, nullptr, prev, x0, b, h, d, s);
 }
 int ddpm_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
                   const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<true, true>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, prev, x0, b, h, d, s);
+  return step_launch<true, true, false>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, nullptr, prev, x0, b, h, d, s);
+}
+
+// adx_ddim_step_pin / adx_ddpm_step_pin: a NULL pin is the unpinned export (tensor or stream, whichever noise source is given)
+template <bool DDPM>
+static int step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
+                    int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
+  ADX_REQUIRE(z == nullptr || ns == nullptr, "scheduler step: a noise tensor and a noise state are both given");
+  if (pin == nullptr) {
+    if (ns != nullptr) return step_launch<DDPM, true, false>(c, mo, x, nullptr, ns, slot, row_offset, nullptr, nullptr, nullptr, prev, x0, b, h, d, s);
+    return step_launch<DDPM, false, false>(c, mo, x, z, nullptr, 0, 0, nullptr, nullptr, nullptr, prev, x0, b, h, d, s);
+  }
+  if (ns != nullptr) return step_launch<DDPM, true, true>(c, mo, x, nullptr, ns, slot, row_offset, nullptr, nullptr, pin, prev, x0, b, h, d, s);
+  return step_launch<DDPM, false, true>(c, mo, x, z, nullptr, 0, 0, nullptr, nullptr, pin, prev, x0, b, h, d, s);
+}
+int ddim_step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
+                  int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
+  return step_pin<false>(c, mo, x, z, ns, slot, row_offset, pin, prev, x0, b, h, d, s);
+}
+int ddpm_step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
+                  int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
+  return step_pin<true>(c, mo, x, z, ns, slot, row_offset, pin, prev, x0, b, h, d, s);
 }
 
 // DPM-Solver++ multistep step (order 1 and the order-2 midpoint rule; diffusers 0.28.0 DPMSolverMultistepScheduler,
@@ -195,8 +277,14 @@ struct DpmArgs {
   float* prev;
   float* x0;
   int total, horizon, dim;
+  // pinned waypoints v1 (the PIN kernel only): the blend and, for its noise, the stream as in StepArgs
+  PinArgs pin;
+  const uint32_t* ns;
+  uint32_t slot;
+  uint64_t base;
 };
 
+template <bool PIN>
 __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -231,6 +319,11 @@ __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
     const float u = c.half_k * d1;
     prev = prev - u;
   }
+  if (PIN) {
+    // the solver has no noise of its own: the draw exists for the blend alone, at the element's LOGICAL index as in step_kernel
+    const float zn = a.pin.known_noise ? noise_normal_at(a.ns, a.slot, a.base + (uint64_t)e) : 0.f;
+    prev = pin_blend(a.pin, e, zn, prev);
+  }
   if (c.zero_first) {
     const int d = e % a.dim;
     const int h = (e / a.dim) % a.horizon;
@@ -240,8 +333,9 @@ __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
   a.x0[e] = x0;          // as computed (not zeroed): the next step's history
 }
 
-int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, float* prev, float* x0, int batch,
-             int horizon, int dim, hipStream_t s) {
+template <bool PIN>
+static int dpm_launch(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, const uint32_t* ns, int32_t slot,
+                      int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int batch, int horizon, int dim, hipStream_t s) {
   ADX_REQUIRE(c && mo && x && prev && x0, "dpm step: null tensor");
   ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1, "dpm step: empty shape");
   ADX_REQUIRE((int64_t)batch * horizon * dim <= (int64_t)0x3fffffff, "dpm step: %lld elements do not fit the kernel's 32-bit index",
@@ -252,10 +346,74 @@ int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float
   ADX_REQUIRE(px0 != prev && px0 != x0 && x != prev && x != x0 && mo != prev && mo != x0 && prev != x0,
               "dpm step: outputs alias an input or each other");
   DpmArgs a;
+  a.pin = PinArgs{nullptr, nullptr, 1, 0.f, 0.f, 0};
+  a.ns = nullptr; a.slot = 0; a.base = 0;
+  if (PIN) {
+    const int rc = pin_check(pin, "dpm step", ns != nullptr, prev, x0, batch, horizon, dim, &a.pin);
+    if (rc != ADX_OK) return rc;
+    if (ns != nullptr) {
+      ADX_REQUIRE(row_offset >= 0, "dpm step: negative row_offset %lld", (long long)row_offset);
+      const int64_t per = (int64_t)horizon * dim;
+      ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + batch) <= kNoiseElems / per,
+                  "dpm step: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements", (long long)row_offset,
+                  (long long)row_offset + batch, (long long)per);
+      a.ns = ns; a.slot = (uint32_t)slot; a.base = (uint64_t)row_offset * (uint64_t)per;
+    }
+  }
   a.c = *c;
   a.mo = mo; a.x = x; a.px0 = px0; a.prev = prev; a.x0 = x0;
   a.total = batch * horizon * dim; a.horizon = horizon; a.dim = dim;
-  dpm_step_kernel<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
+  dpm_step_kernel<PIN><<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
+}
+
+int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, float* prev, float* x0, int batch,
+             int horizon, int dim, hipStream_t s) {
+  return dpm_launch<false>(c, mo, x, px0, nullptr, 0, 0, nullptr, prev, x0, batch, horizon, dim, s);
+}
+// a NULL pin is adx_dpm_step: the solver itself draws nothing, the noise arguments are then not looked at
+int dpm_step_pin(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, const uint32_t* ns, int32_t slot,
+                 int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int batch, int horizon, int dim, hipStream_t s) {
+  if (pin == nullptr) return dpm_launch<false>(c, mo, x, px0, nullptr, 0, 0, nullptr, prev, x0, batch, horizon, dim, s);
+  return dpm_launch<true>(c, mo, x, px0, ns, slot, row_offset, pin, prev, x0, batch, horizon, dim, s);
+}
+
+// The blend by itself, in place on a sample [batch][H][D]: the entry of a `clean` tick, where the reference writes
+// trajs[:, 0, :3] = 0 before its loop.  z, when asked for, is the stream's INIT_SLOT draw of the element's logical index.
+struct PinApplyArgs {
+  float* x;
+  PinArgs pin;
+  const uint32_t* ns;
+  uint64_t base;
+  int total;
+};
+
+__global__ void __launch_bounds__(256) pin_apply_kernel(const PinApplyArgs a) {
+#pragma clang fp contract(off)
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= a.total) return;
+  const float zn = a.pin.known_noise ? noise_normal_at(a.ns, 0xFFFFFFFFu, a.base + (uint64_t)e) : 0.f;
+  a.x[e] = pin_blend(a.pin, e, zn, a.x[e]);
+}
+
+int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int batch, int horizon, int dim, hipStream_t s) {
+  ADX_REQUIRE(x != nullptr && pin != nullptr, "pin apply: null sample or pin");
+  ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1, "pin apply: empty shape");
+  PinApplyArgs a;
+  const int rc = pin_check(pin, "pin apply", ns != nullptr, x, nullptr, batch, horizon, dim, &a.pin);
+  if (rc != ADX_OK) return rc;
+  a.ns = nullptr; a.base = 0;
+  if (ns != nullptr) {
+    ADX_REQUIRE(row_offset >= 0, "pin apply: negative row_offset %lld", (long long)row_offset);
+    const int64_t per = (int64_t)horizon * dim;
+    ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + batch) <= kNoiseElems / per,
+                "pin apply: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements", (long long)row_offset,
+                (long long)row_offset + batch, (long long)per);
+    a.ns = ns; a.base = (uint64_t)row_offset * (uint64_t)per;
+  }
+  a.x = x; a.total = batch * horizon * dim;
+  pin_apply_kernel<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
@@ -363,11 +521,6 @@ __global__ void __launch_bounds__(256) warm_init_kernel(const WarmArgs a) {
   float v = m0 + m1;
   if (a.zero_first && h == 0 && d < 3) v = 0.f;
   a.out[e] = v;
-}
-
-static bool byte_ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qn && b < a + pn;
 }
 
 int warm_init(const float* prev, int prev_rows, const float* motion, float* out, int rows, int horizon, int dim, int shift,

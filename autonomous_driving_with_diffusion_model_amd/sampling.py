@@ -19,6 +19,9 @@ A fifth has none either: `warm=WarmStart(steps=m)` starts a tick from the previo
 and re-noised on the device ("warm start v1" of include/adx.h) -- and runs only the last m steps of the schedule.
 A sixth closes the tick: `controller=DeviceController(...)` turns the result into (throttle, steer, brake) per scene on the device
 ("control v1" of include/adx.h, control/device.py), where the callers hand `traj[0, :4, :2]` to a host `Controller`.
+A seventh makes the loop's one hard-coded constraint general: `pin=Pin(known, mask)` holds waypoints the caller has already
+decided through the tick, inside the step kernels ("pinned waypoints v1" of include/adx.h, pin.py), where the callers can only
+say `trajs[:, 0, :3] = 0`.
 """
 from __future__ import annotations
 
@@ -34,6 +37,7 @@ from .control.device import DeviceController
 from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
 from .noise import DeviceNoise
+from .pin import Pin, pin_apply
 
 
 def _targets(target: Optional[torch.Tensor], batch: int) -> Optional[torch.Tensor]:
@@ -157,6 +161,32 @@ def _control_plan(cfg, controller: Optional[DeviceController], velocity, image, 
     return velocity
 
 
+def _pin_plan(cfg, pin: Optional[Pin], image, scheduler, noise, step_noise=None) -> Optional[Pin]:
+    """The pin of this tick with its mode resolved (None without one), every refusal raised here: beside `_warm_plan`'s and
+    `_control_plan`'s, before any launch, before a tick of the noise stream is consumed, before a capture opens."""
+    if pin is None:
+        return None
+    if not isinstance(pin, Pin):
+        raise TypeError(f"generate_traj: `pin` must be a Pin, got {type(pin).__name__}")
+    want = (int(image.shape[0]), int(cfg.MODEL.HORIZON), int(cfg.MODEL.TRANSITION_DIM))
+    for name, t in (("known", pin.known), ("mask", pin.mask)):
+        if tuple(t.shape) != want or t.device != image.device or t.dtype != torch.float32:
+            raise ValueError(f"pin.{name} must be a float32 tensor {want} = (scenes, MODEL.HORIZON, MODEL.TRANSITION_DIM) on "
+                             f"{image.device}, got {tuple(t.shape)}, {t.dtype} on {t.device}")
+    mode = pin.resolve(cfg)            # refuses an unknown EVAL.PIN_MODE
+    if not getattr(scheduler, "supports_pin", False):
+        raise ValueError(f"{type(scheduler).__name__}.step takes no pin: use GuidanceDDIMScheduler, GuidanceDDPMScheduler or "
+                         "GuidanceDPMSolverMultistepScheduler")
+    if mode == "repaint":
+        if step_noise is not None:
+            raise ValueError("generate_traj: a `repaint` pin shares each step's own noise; `step_noise` injects tensors for the "
+                             "DDPM steps alone -- use noise=DeviceNoise(...) or a `clean` pin")
+        if getattr(scheduler, "deterministic", False) and not isinstance(noise, DeviceNoise):
+            raise ValueError("generate_traj: a `repaint` pin on the DPM-Solver++ sampler needs noise=DeviceNoise(...): the solver "
+                             "has no noise of its own, the pin's is drawn inside the step kernel")
+    return pin.with_mode(mode)
+
+
 def warm_init(prev: torch.Tensor, rows: int, shift: int, level: Tuple[float, float], noise: DeviceNoise,
               motion: Optional[torch.Tensor] = None, zero_first: bool = True) -> torch.Tensor:
     """One launch of `adx_warm_init` ("warm start v1", include/adx.h): [rows, H, D] from prev [prev_rows, H, D] under the
@@ -182,7 +212,8 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
                   set_timesteps: bool = True, noise: Optional[DeviceNoise] = None, candidates: int = 1,
                   selector: Optional[TrajectorySelector] = None, return_selection: bool = False,
                   warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
-                  controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None):
+                  controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None,
+                  pin: Optional[Pin] = None):
     """`noise`: a DeviceNoise.  The call is then one tick of the noise stream: `begin_tick()` first, the initial trajectory
     (when `init_trajs` is not given) from `INIT_SLOT`, and every scheduler step draws inside its kernel at the slot of its
     timestep -- no noise tensor, no torch generator.
@@ -209,7 +240,17 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     waypoint after the controller's last stands in).  The order at the end of a tick is fixed: clamp, selection, the copy
     into `warm.prev`, the control launch, xy scaling.  The call then returns `(traj, control)` -- `(traj, selection, control)`
     with `return_selection=True` -- with control [S, 3] = (throttle, steer, brake); `traj` is bit for bit what the call
-    without a controller returns.  Without a controller nothing changes."""
+    without a controller returns.  Without a controller nothing changes.
+
+    `pin` = a Pin whose known / mask are [S, H, D] on the image's device, in the model's own units and this tick's ego frame:
+    "pinned waypoints v1".  Every `scheduler.step` of the loop gets it (fused or not, all three guidance branches) and blends
+    inside its kernel; with `candidates` = K the K * S rows read the [S, H, D] pin directly (row r reads scene r % S), nothing is
+    tiled.  `clean` mode also blends the start rows once at loop entry (`adx_pin_apply` -- on the cold draw, `init_trajs` or a
+    warm start's output -- between two writes of `[:, 0, :3] = 0`); `repaint` mode has no entry blend, its first step is the
+    entry.  Clamp, selection, the copy into `warm.prev`, the control launch and xy scaling follow untouched, so the warm state
+    and the controller see the pinned result: cells with mask 1 equal `known` there wherever |known| <= 1, outside
+    `[:, 0, :3]`.  A `repaint` pin needs `noise` with the DPM-Solver++ sampler and does not take `step_noise`.  None is the loop
+    as it was.  What a pin does to driving quality depends on trained weights and is not measured in this repository."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     model.eval()
     device = image.device
@@ -229,6 +270,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     m_warm, shift, is_warm, motion = _warm_plan(cfg, warm, noise, init_trajs, image, K, motion,
                                                 None if set_timesteps else scheduler)
     velocity = _control_plan(cfg, controller, velocity, image, target is not None)
+    pin = _pin_plan(cfg, pin, image, scheduler, noise, step_noise)
     if noise is not None:
         noise.begin_tick()
     i0 = 0
@@ -253,6 +295,10 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         trajs[:, 0, :3] = 0.0
         if set_timesteps:
             scheduler.set_timesteps(cfg.EVAL.SAMPLE_STEPS, device=device)
+    if pin is not None and pin.mode == "clean":
+        # the entry blend, where the callers write their one pinned cell group before the loop; waypoint 0 keeps the last word
+        trajs = pin_apply(trajs if trajs.is_contiguous() else trajs.contiguous(), pin)
+        trajs[:, 0, :3] = 0.0
     # whose step takes an injected `variance_noise`: the DDPM schedulers (a deterministic solver has no noise argument)
     is_ddpm = not getattr(scheduler, "_is_ddim", False) and not getattr(scheduler, "deterministic", False)
     # What the UNet derives from (t, target, image feature) alone does not change inside the loop: with the perception
@@ -277,7 +323,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     try:
         with (frozen(image) if frozen is not None else contextlib.nullcontext()):
             trajs = _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device,
-                               noise, i0)
+                               noise, i0, pin)
     finally:
         if is_warm:
             scheduler.set_begin_index(0)       # the begin index belongs to this tick: a later loop on the scheduler starts at 0
@@ -311,12 +357,15 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
 
 
 def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device, noise=None,
-               begin=0):
-    """`begin` > 0: the schedule's suffix `timesteps[begin:]`; `i` (the row of the conditioning table) counts from there."""
+               begin=0, pin=None):
+    """`begin` > 0: the schedule's suffix `timesteps[begin:]`; `i` (the row of the conditioning table) counts from there.
+    `pin`: handed to every `scheduler.step`."""
     action = None
     for i, t in enumerate(scheduler.timesteps if begin == 0 else list(scheduler.timesteps)[begin:]):
         tck = None if tc is None else (tc, i)
         extra = {} if noise is None else {"generator": noise}
+        if pin is not None:
+            extra["pin"] = pin
         if is_ddpm and step_noise is not None:
             extra["variance_noise"] = step_noise(i, tuple(trajs.shape)).to(device)
         if use == GuidanceType.FREE_GUIDANCE:
@@ -419,6 +468,9 @@ class GraphedSampler:
     `last_control` the [S, 3] controls of the last replay.  The controller's windows live in its own device buffer, which the
     graph reads and advances through its address: replay k of a fresh sampler sees the windows k eager ticks leave (the
     capture's warm-up pass, a real tick, gives its sample back).
+    `pin=Pin(...)` per call: pinned waypoints as in `generate_traj`.  `known` and `mask` travel through static buffers like
+    `target`, `motion` and `velocity`; presence, mode and shape are part of the graph key, new values never capture again.  A
+    `repaint` pin needs `noise=DeviceNoise(...)` at construction (a captured noise tensor would replay) and is refused without.
     """
 
     MAX_GRAPHS = 4
@@ -443,7 +495,7 @@ class GraphedSampler:
         self._sel = None
         self._ctl = None
 
-    def _capture(self, image, target, init_trajs, motion, velocity=None):
+    def _capture(self, image, target, init_trajs, motion, velocity=None, pin=None):
         dev = image.device
         warm = self.warm
         self.model.eval()
@@ -456,11 +508,12 @@ class GraphedSampler:
         g.tgt = None if target is None else target.clone()
         g.motion = None if motion is None else motion.clone()
         g.vel = None if velocity is None else velocity.clone()
+        g.pin = None if pin is None else Pin(pin.known.clone(), pin.mask.clone(), pin.mode)
         ctl = self.controller
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
                                     candidates=self.candidates, selector=self.selector, return_selection=True,
-                                    warm=warm, motion=g.motion, controller=ctl, velocity=g.vel)
+                                    warm=warm, motion=g.motion, controller=ctl, velocity=g.vel, pin=g.pin)
         tick = None if self.noise is None else self.noise.tick()
         # the warm-up pass below is a real tick: it moves the noise stream on and overwrites the warm state.  Both are given
         # back, so that the first replay is the next tick and starts from the result of the tick before it
@@ -529,12 +582,16 @@ class GraphedSampler:
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None,
-                 velocity: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None) -> torch.Tensor:
         K, sel = _candidates(self.cfg, self.candidates, self.selector)
         warm = self.warm
         m_warm, shift, is_warm, motion = _warm_plan(self.cfg, warm, self.noise, init_trajs, image, K, motion)
         ctl = self.controller
         velocity = _control_plan(self.cfg, ctl, velocity, image, target is not None)
+        pin = _pin_plan(self.cfg, pin, image, self.scheduler, self.noise)
+        if pin is not None and pin.mode == "repaint" and self.noise is None:
+            raise ValueError("GraphedSampler: a `repaint` pin needs noise=DeviceNoise(...) at construction: a noise tensor drawn "
+                             "during the capture would replay on every tick")
         if init_trajs is None and self.noise is None:
             init_trajs = torch.randn((K * image.shape[0], self.cfg.MODEL.HORIZON, self.cfg.MODEL.TRANSITION_DIM),
                                      device=image.device)
@@ -546,13 +603,15 @@ class GraphedSampler:
                # a cold and a warm graph (m_warm == 0: the loop as it was); baked into the warm-start node
                None if m_warm == 0 else (m_warm, shift, is_warm, motion is None, id(warm)),
                # the controller's state address and every setting are baked into the control node
-               None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), velocity is None))
+               None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), velocity is None),
+               # whether a pin is there, its mode (host scalars baked into the step nodes) and its shape
+               None if pin is None else (pin.mode, tuple(pin.known.shape)))
         g = self._graphs.get(key)
         if g is None or g.pointers != self._model_pointers():
             self._graphs.pop(key, None)
             while len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.pop(next(iter(self._graphs)))        # the oldest capture
-            g = self._graphs[key] = self._capture(image, target, init_trajs, motion, velocity)
+            g = self._graphs[key] = self._capture(image, target, init_trajs, motion, velocity, pin)
         else:
             g.img.copy_(image)
             if init_trajs is not None:
@@ -563,6 +622,9 @@ class GraphedSampler:
                 g.motion.copy_(motion)
             if velocity is not None:
                 g.vel.copy_(velocity)
+            if pin is not None:
+                g.pin.known.copy_(pin.known)
+                g.pin.mask.copy_(pin.mask)
         self._key, self._graph, self._sel, self._ctl = key, g.graph, g.sel, g.ctl
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured

@@ -251,16 +251,24 @@ class SchedulerBase:
         c.sqrt_beta_t = float(b_t ** 0.5)
         return c
 
-    def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True, slot: int = 0):
+    def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True, slot: int = 0, pin=None):
         """`noise`: the step's noise tensor (or None), or a DeviceNoise -- then the kernel draws element by element from the
-        noise stream at `slot` (the integer timestep) and no tensor exists."""
+        noise stream at `slot` (the integer timestep) and no tensor exists.  `pin`: the `adx_pin` of a pinned step (the PIN
+        variant of the kernel, "pinned waypoints v1"); None is the call as it was."""
         B, H, D = x.shape
         prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
         import ctypes as C
+        if isinstance(noise, DeviceNoise) and noise.device != x.device:
+            raise ValueError(f"the DeviceNoise lives on {noise.device}, the sample on {x.device}")
+        if pin is not None:
+            stream = isinstance(noise, DeviceNoise)
+            fn = L.lazy("adx_ddpm_step_pin" if ddpm else "adx_ddim_step_pin")
+            L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), None if stream else L.ptr(noise),
+                       noise.state_ptr() if stream else None, int(slot), noise.row_offset if stream else 0, C.byref(pin),
+                       prev.data_ptr(), L.ptr(x0), B, H, D, L.stream_ptr(x.device)), "scheduler step")
+            return prev, x0
         if isinstance(noise, DeviceNoise):
-            if noise.device != x.device:
-                raise ValueError(f"the DeviceNoise lives on {noise.device}, the sample on {x.device}")
             fn = L.lib().adx_ddpm_step_rng if ddpm else L.lib().adx_ddim_step_rng
             L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), noise.state_ptr(), int(slot), noise.row_offset, L.ptr(target),
                        L.ptr(mask), prev.data_ptr(), L.ptr(x0), B, H, D, L.stream_ptr(x.device)), "scheduler step")
@@ -269,6 +277,29 @@ class SchedulerBase:
         L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(noise), L.ptr(target), L.ptr(mask), prev.data_ptr(),
                    L.ptr(x0), B, H, D, L.stream_ptr(x.device)), "scheduler step")
         return prev, x0
+
+    # -- pinned waypoints v1 ------------------------------------------------------------------------
+    supports_pin = False        # the guidance schedulers' `step` takes `pin=`
+
+    def _repaint_level(self, timestep):
+        raise NotImplementedError(f"{type(self).__name__} has no pinned step")
+
+    def pin_level(self, timestep, mode: str = "clean"):
+        """(c_known, c_known_noise, known_noise) of the pinned step at `timestep`: (1, 0, False) in `clean` mode, the level the
+        step lands on in `repaint` mode, as Python floats holding fp32 values -- the host scalars of `adx_pin`."""
+        if mode == "clean":
+            return 1.0, 0.0, False
+        if mode != "repaint":
+            raise ValueError(f"pin mode must be 'clean' or 'repaint', got {mode!r}")
+        return self._repaint_level(timestep)
+
+    def _pin_desc(self, pin, timestep, x):
+        """(adx_pin, needs_noise) of this step, or (None, False) without a pin.  A Pin whose mode is None is `clean` here: a
+        step has no config to read EVAL.PIN_MODE from (`generate_traj` resolves it before its loop)."""
+        if pin is None:
+            return None, False
+        level = self.pin_level(timestep, pin.resolve())
+        return pin.desc(x, level), bool(level[2])
 
     @staticmethod
     def _noise(shape, generator, device, dtype, variance_noise=None):
@@ -324,6 +355,10 @@ class DDPMScheduler(SchedulerBase):
         c.known_noise = int(t > 0)
         return c
 
+    def _repaint_level(self, timestep):
+        c = self._ddpm_coef(timestep_to_int(timestep))
+        return c.c_known, c.c_known_noise, bool(c.known_noise)
+
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, variance_noise=None):
         t = timestep_to_int(timestep)
         mo, x = self._check_step_inputs(model_output, sample)
@@ -377,3 +412,7 @@ class DDIMScheduler(SchedulerBase):
         c.c_known_noise = float((1.0 - a_prev) ** 0.5)
         c.known_noise = int(t > 0)
         return c
+
+    def _repaint_level(self, timestep):
+        c = self._ddim_coef(timestep_to_int(timestep), 0.0, False)
+        return c.c_known, c.c_known_noise, bool(c.known_noise)

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..noise import DeviceNoise
 from .base import PRED, SchedulerBase, SchedulerOutput, TimestepSequence, timestep_to_int
 from .guidance import _wants_classifier_guidance
 
@@ -31,6 +32,7 @@ from .guidance import _wants_classifier_guidance
 class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
     _is_ddim = False
     deterministic = True        # no step draws noise: a captured loop replays exactly (sampling.GraphedSampler)
+    supports_pin = True
 
     def __init__(self, cfg=None, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
@@ -153,13 +155,28 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
             c.inv_r0 = float(1.0 / r0)
         return c
 
+    def _repaint_level(self, timestep):
+        """alpha and sigma * alpha of sigmas[i + 1], as `_dpm_coef` forms alpha_t and sigma_t; no noise on the last step."""
+        i = self.step_index(timestep)
+        alpha_t, sigma_t = self._sigma_to_alpha_sigma_t(self.sigmas[i + 1])
+        return float(alpha_t), float(sigma_t), i < len(self.timesteps) - 1
+
     # -- step --------------------------------------------------------------------------------------
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, target=None, action=None,
-             cfg_scale=None, zero_first: bool = False):
-        """One solver step.  `generator`, `target` and `action` are accepted for the callers' common signature and unused: no
-        step draws noise, and classifier guidance is refused at construction.  `cfg_scale` / `zero_first`: the fusions of
-        GuidanceDDIMScheduler.step; `pred_original_sample` is never zeroed (it is the next step's history)."""
+             cfg_scale=None, zero_first: bool = False, pin=None):
+        """One solver step.  `target` and `action` are accepted for the callers' common signature and unused (classifier
+        guidance is refused at construction); so is `generator` without a pin: no step draws noise.  `cfg_scale` /
+        `zero_first`: the fusions of GuidanceDDIMScheduler.step; `pred_original_sample` is never zeroed (it is the next step's
+        history).
+
+        `pin`: a Pin ("pinned waypoints v1", include/adx.h), blended into prev_sample before `zero_first`;
+        `pred_original_sample` is never pinned.  A `repaint` pin is the one thing that makes this step draw: it needs
+        `generator=DeviceNoise(...)` (the draw happens in the kernel, at the slot of the timestep) and raises ValueError without."""
         i = self.step_index(timestep)
+        stream = isinstance(generator, DeviceNoise)
+        if pin is not None and pin.resolve() == "repaint" and not stream:
+            raise ValueError("a `repaint` pin needs generator=DeviceNoise(...) on the DPM-Solver++ sampler: the solver has no noise "
+                             "of its own, the pin's is drawn inside the step kernel")
         c = self._dpm_coef(i)
         history = None
         if c.second_order:
@@ -175,9 +192,18 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
             c.cfg_combine, c.free_scale = 1, float(cfg_scale)
         c.zero_first = int(zero_first)
         B, H, D = x.shape
+        p, _ = self._pin_desc(pin, timestep, x)
         prev, x0 = torch.empty_like(x), torch.empty_like(x)
-        L.check(L.lib().adx_dpm_step(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history), prev.data_ptr(), x0.data_ptr(),
-                                     B, H, D, L.stream_ptr(x.device)), "scheduler step")
+        if p is None:
+            L.check(L.lib().adx_dpm_step(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history), prev.data_ptr(), x0.data_ptr(),
+                                         B, H, D, L.stream_ptr(x.device)), "scheduler step")
+        else:
+            if stream and generator.device != x.device:
+                raise ValueError(f"the DeviceNoise lives on {generator.device}, the sample on {x.device}")
+            L.check(L.lazy("adx_dpm_step_pin")(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history),
+                                               generator.state_ptr() if stream else None, timestep_to_int(timestep),
+                                               generator.row_offset if stream else 0, C.byref(p), prev.data_ptr(), x0.data_ptr(),
+                                               B, H, D, L.stream_ptr(x.device)), "scheduler step")
         self._last = (i, x0)
         if not return_dict:
             return (prev,)

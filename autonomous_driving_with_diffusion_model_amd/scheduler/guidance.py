@@ -17,6 +17,8 @@ def _wants_classifier_guidance(cfg) -> bool:
 
 
 class GuidanceDDIMScheduler(DDIMScheduler):
+    supports_pin = True
+
     def __init__(self, cfg, **kwargs):
         super().__init__(**kwargs)
         self.use_classifier_guidance = _wants_classifier_guidance(cfg)
@@ -32,10 +34,15 @@ class GuidanceDDIMScheduler(DDIMScheduler):
 
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False,
              generator=None, variance_noise=None, return_dict: bool = True, target=None, action=None,
-             cfg_scale=None, zero_first: bool = False):
+             cfg_scale=None, zero_first: bool = False, pin=None):
         """`cfg_scale` / `zero_first` are optional fusions (classifier-free combine of a [2B] model
         output, interact.py:142-144, and `prev[:, 0, :3] = 0`, interact.py:164); leaving them at their
-        defaults gives exactly the reference signature and behaviour."""
+        defaults gives exactly the reference signature and behaviour.
+
+        `pin`: a Pin ("pinned waypoints v1", include/adx.h): the finished prev_sample is blended with the pin's known values
+        under its mask in the same kernel, before `zero_first`.  A `repaint` pin shares the step's own noise (eta > 0); with
+        eta = 0 it draws from `generator` when that is a DeviceNoise, else a tensor as the step's noise would be drawn
+        (`variance_noise`, or torch.randn from `generator`).  None is the call as it was."""
         t = timestep_to_int(timestep)
         c = self._ddim_coef(t, eta, use_clipped_model_output)
         if self.use_classifier_guidance and target is not None:
@@ -53,13 +60,18 @@ class GuidanceDDIMScheduler(DDIMScheduler):
                 raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either "
                                  "`generator` or `variance_noise` stays `None`.")
             z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)
-        prev, x0 = self._launch(False, c, mo, x, z, None, None, slot=t)
+        p, p_noise = self._pin_desc(pin, t, x)
+        if p_noise and z is None:
+            z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)
+        prev, x0 = self._launch(False, c, mo, x, z, None, None, slot=t, pin=p)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
 
 
 class GuidanceDDPMScheduler(DDPMScheduler):
+    supports_pin = True
+
     def __init__(self, cfg, **kwargs):
         super().__init__(**kwargs)
         self.use_classifier_guidance = _wants_classifier_guidance(cfg)
@@ -72,7 +84,8 @@ class GuidanceDDPMScheduler(DDPMScheduler):
         return float(torch.exp(0.5 * self._get_variance(timestep_to_int(timestep))))
 
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, target=None,
-             action=None, variance_noise=None, cfg_scale=None, zero_first: bool = False):
+             action=None, variance_noise=None, cfg_scale=None, zero_first: bool = False, pin=None):
+        """`pin`: as in GuidanceDDIMScheduler.step; a `repaint` pin shares the step's noise (both exist exactly when t > 0)."""
         t = timestep_to_int(timestep)
         c = self._ddpm_coef(t)
         if self.use_classifier_guidance and target is not None:
@@ -84,7 +97,8 @@ class GuidanceDDPMScheduler(DDPMScheduler):
             c.cfg_combine, c.free_scale = 1, float(cfg_scale)
         c.zero_first = int(zero_first)
         z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise) if t > 0 else None
-        prev, x0 = self._launch(True, c, mo, x, z, None, None, slot=t)
+        p, _ = self._pin_desc(pin, t, x)
+        prev, x0 = self._launch(True, c, mo, x, z, None, None, slot=t, pin=p)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)

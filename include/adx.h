@@ -721,6 +721,66 @@ int adx_warm_init(const float* prev, int32_t prev_rows, const float* motion, flo
                   int32_t zero_first, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Pinned waypoints v1: waypoints the caller has already decided, held through a sampling tick while the sampler plans the rest
+ * around them (a commit horizon, a stop point, a fixed hand-over).  The reference's loops pin one cell group this way -- after
+ * every step they overwrite [:, 0, :3] with its clean value (interact.py:164, train.py:88; Diffuser's apply_conditioning) --
+ * and its Inpainting*Scheduler classes hold the RePaint blend, which no caller constructs; this is the first made general, with
+ * the second as a mode of the same arithmetic.  A compile-time variant of the step kernels, no host decision: a node of a
+ * captured graph.  Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ *   known    [known_rows][H][D] in the model's own units: the units of `target` and of the clamped result BEFORE xy scaling.
+ *   mask     [known_rows][H][D], float: 1 = pinned, 0 = free, values between blend linearly; values outside [0, 1] are the
+ *            caller's business.
+ *   rows     row r of a launch of `batch` rows reads known row r % known_rows (candidate-major, as the conditioning table reads
+ *            features: every candidate of a scene carries that scene's pins); batch % known_rows == 0.
+ *   per step on the finished prev_sample -- after the sampler's update and after the step's own noise term where it has one,
+ *            before zero_first, which keeps the last word on waypoint 0:
+ *              kp   = c_known * known + (known_noise ? c_known_noise * z : 0)
+ *              prev = mask * kp + (1 - mask) * prev              u = mask * kp;  v = (1 - mask) * prev;  prev = u + v
+ *            fp32, no contraction, every product and sum rounded on its own, as written.
+ *   z        the step's noise at that element, the very value the step's own noise term uses; no second draw is made.  Tensor
+ *            path: element e of the noise tensor.  Stream path: the stream's normal at slot = the step's integer timestep and
+ *            logical element e = ((row_offset + b) * H + h) * D + d (adx_pin_apply: slot ADX_NOISE_INIT_SLOT).
+ *   x0       pred_original_sample is written as computed and is never pinned: it is the DPM solver's history.
+ *   modes    host scalars only; the kernel knows none.
+ *     clean    c_known = 1, known_noise = 0: the reference loop's idiom.  Needs no noise; the step stays deterministic.
+ *     repaint  (c_known, c_known_noise, known_noise) = the level the step lands on.  DDIM / DDPM: sqrt(abar_prev),
+ *              sqrt(1 - abar_prev), t > 0 (the c_known, c_known_noise, known_noise of adx_step_coef, which the pinned step
+ *              does not read).  DPM: alpha and sigma * alpha of sigma_{i+1}, known_noise = (i < n - 1).
+ *   consequences  with finite operands mask == 1 gives prev == kp and mask == 0 leaves prev as it was, bit for bit (up to the
+ *            sign of a zero: x + 0 is +0 for x = -0).  The last step of every schedule lands on the clean level in both modes
+ *            (abar_prev = 1 with set_alpha_to_one, sigma = 0), so after the loop's clamp(-1, 1) a pinned cell equals `known`
+ *            exactly when |known| <= 1 and the cell is not one zero_first writes.
+ *
+ * ADX_ERR_INVALID before any GPU work: NULL known or mask, known_rows < 1 or not dividing batch, both a noise tensor and a noise
+ * state, known_noise set with neither, c->inpaint together with a pin, an output that overlaps known or mask, more elements than
+ * the kernel's 32-bit index holds, rows that leave the stream's 2^34 elements, and whatever the unpinned step refuses.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_pin {
+  const float* known;          /* [known_rows][H][D] */
+  const float* mask;           /* [known_rows][H][D] */
+  int32_t known_rows;
+  float c_known, c_known_noise;
+  int32_t known_noise;
+} adx_pin;
+/* adx_ddim_step(_rng) / adx_ddpm_step(_rng) with the blend above.  `noise`: the step's noise tensor or NULL; `noise_state`: the
+ * stream's state or NULL (then slot and row_offset are not read); at most one of the two.  A NULL pin is exactly the unpinned
+ * export of the noise source given (target = mask = NULL). */
+int adx_ddim_step_pin(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                      const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev, float* x0,
+                      int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+int adx_ddpm_step_pin(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                      const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev, float* x0,
+                      int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+/* adx_dpm_step with the blend: the one DPM path that can draw (known_noise), from the stream only.  A NULL pin is adx_dpm_step. */
+int adx_dpm_step_pin(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                     const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev_sample,
+                     float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+/* The blend alone, in place on x [batch][H][D]; z, if pin->known_noise, from the stream at ADX_NOISE_INIT_SLOT. */
+int adx_pin_apply(float* x, const adx_pin* pin, const uint32_t* noise_state, int64_t row_offset, int32_t batch, int32_t horizon,
+                  int32_t dim, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Control v1: waypoints -> (throttle, steer, brake) on the device, the step after the sampling loop in the reference's agents
  * (control/controller.py:29-76 `control_pid`, control/pid.py, `post_process_control` of interact.py:218-229 and
  * e2e_driving/diffusion_agent.py:268-277).  One launch per tick for all scenes, no host decision; the PID windows live in
