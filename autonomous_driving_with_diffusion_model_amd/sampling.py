@@ -26,6 +26,7 @@ say `trajs[:, 0, :3] = 0`.
 from __future__ import annotations
 
 import contextlib
+from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Callable, Optional, Tuple
 
@@ -49,18 +50,6 @@ def _targets(target: Optional[torch.Tensor], batch: int) -> Optional[torch.Tenso
     if t.shape[0] != batch:
         raise ValueError(f"target must be [2] or [{batch}, 2], got {tuple(target.shape)}")
     return t.contiguous()
-
-
-def _candidates(cfg, candidates: int, selector):
-    """The keyword arguments left at their defaults read EVAL.CANDIDATES / EVAL.SELECT (absent keys: 1, goal distance only)."""
-    K = int(candidates)
-    if K == 1:
-        K = int(getattr(cfg.EVAL, "CANDIDATES", 1))
-    if not 1 <= K <= MAX_CANDIDATES:
-        raise ValueError(f"candidates must be 1..{MAX_CANDIDATES}, got {K}")
-    if K > 1 and selector is None:
-        selector = TrajectorySelector(*getattr(cfg.EVAL, "SELECT", (1.0, 0.0, 0.0)))
-    return K, selector
 
 
 class WarmStart:
@@ -100,93 +89,6 @@ class WarmStart:
         return f"WarmStart(steps={self.steps}, shift={self.shift}, valid={self.valid}, prev={shape})"
 
 
-def _warm_plan(cfg, warm: Optional[WarmStart], noise, init_trajs, image, K: int, motion, scheduler=None):
-    """(m, shift, is_warm, motion) of this tick, every refusal raised here: before any launch, before a tick of the noise stream
-    is consumed, before a capture opens.  m == 0 (no `warm`, or one that is off) is the loop as it was.  `scheduler`: one whose
-    timesteps the caller has set itself and the warm tick will index."""
-    S = int(image.shape[0])
-    if motion is not None:
-        if warm is None:
-            raise ValueError("generate_traj: `motion` is the odometry of a warm start; pass warm=WarmStart(...) with it")
-        # checked on every tick it is given, cold ones included (which do not read it): a wrong shape shows on the first call
-        motion = L.require_gpu_f32(motion, "motion")
-        if tuple(motion.shape) != (S, 3) or motion.device != image.device:
-            raise ValueError(f"motion must be [{S}, 3] = (tx, ty, phi) per scene on {image.device}, got {tuple(motion.shape)} "
-                             f"on {motion.device}")
-    if warm is None or warm.resolve(cfg)[0] == 0:
-        return 0, 0, False, None
-    m, shift = warm.resolve(cfg)
-    n, H, D = int(cfg.EVAL.SAMPLE_STEPS), int(cfg.MODEL.HORIZON), int(cfg.MODEL.TRANSITION_DIM)
-    if m > n:
-        raise ValueError(f"WarmStart: steps = {m} is more than EVAL.SAMPLE_STEPS = {n}")
-    if not 0 <= shift < H:
-        raise ValueError(f"WarmStart: shift = {shift} must be in 0..{H - 1} (MODEL.HORIZON = {H})")
-    if not isinstance(noise, DeviceNoise):
-        raise ValueError("WarmStart needs noise=DeviceNoise(...): the re-noise is drawn inside the warm-start kernel")
-    if noise.device != image.device:
-        raise ValueError(f"the DeviceNoise lives on {noise.device}, the image on {image.device}")
-    if warm.prev is not None and (tuple(warm.prev.shape) != (S, H, D) or warm.prev.device != image.device):
-        raise ValueError(f"WarmStart: the state holds {tuple(warm.prev.shape)} on {warm.prev.device}, this tick is "
-                         f"{(S, H, D)} on {image.device}; use a new WarmStart for another batch shape or device")
-    if not warm.valid:
-        return m, shift, False, None
-    if init_trajs is not None:
-        raise ValueError("generate_traj: `init_trajs` and a valid warm state both name the tick's start; warm.reset() first "
-                         "for a cold tick from init_trajs")
-    if scheduler is not None and len(scheduler.timesteps) != n:       # a caller that keeps its own timesteps (set_timesteps=False)
-        raise ValueError(f"the scheduler holds {len(scheduler.timesteps)} timesteps, EVAL.SAMPLE_STEPS is {n}")
-    return m, shift, True, motion
-
-
-def _control_plan(cfg, controller: Optional[DeviceController], velocity, image, has_target: bool):
-    """The velocity a controlled tick hands to its controller (None without one), every refusal raised here: beside `_warm_plan`'s,
-    before any launch, before a tick of the noise stream is consumed, before a capture opens."""
-    if controller is None:
-        if velocity is not None:
-            raise ValueError("generate_traj: `velocity` is the speed a controller reads; pass controller=DeviceController(...) with it")
-        return None
-    S = int(image.shape[0])
-    if controller.scenes != S or controller.device != image.device:
-        raise ValueError(f"the DeviceController holds the windows of {controller.scenes} scenes on {controller.device}, this tick is "
-                         f"{S} scenes on {image.device}; use a controller of its own for another batch or device")
-    controller.check(cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM, has_target)
-    if velocity is None:
-        if controller.source != "action":
-            raise ValueError("generate_traj: a controller with source='pid' needs `velocity` [S], the scenes' current speeds")
-        return None
-    if not torch.is_tensor(velocity) or tuple(velocity.shape) != (S,) or velocity.device != image.device or \
-            velocity.dtype != torch.float32:
-        what = (tuple(velocity.shape), velocity.dtype, velocity.device) if torch.is_tensor(velocity) else type(velocity).__name__
-        raise ValueError(f"velocity must be a float32 tensor [{S}] on {image.device}, got {what}")
-    return velocity
-
-
-def _pin_plan(cfg, pin: Optional[Pin], image, scheduler, noise, step_noise=None) -> Optional[Pin]:
-    """The pin of this tick with its mode resolved (None without one), every refusal raised here: beside `_warm_plan`'s and
-    `_control_plan`'s, before any launch, before a tick of the noise stream is consumed, before a capture opens."""
-    if pin is None:
-        return None
-    if not isinstance(pin, Pin):
-        raise TypeError(f"generate_traj: `pin` must be a Pin, got {type(pin).__name__}")
-    want = (int(image.shape[0]), int(cfg.MODEL.HORIZON), int(cfg.MODEL.TRANSITION_DIM))
-    for name, t in (("known", pin.known), ("mask", pin.mask)):
-        if tuple(t.shape) != want or t.device != image.device or t.dtype != torch.float32:
-            raise ValueError(f"pin.{name} must be a float32 tensor {want} = (scenes, MODEL.HORIZON, MODEL.TRANSITION_DIM) on "
-                             f"{image.device}, got {tuple(t.shape)}, {t.dtype} on {t.device}")
-    mode = pin.resolve(cfg)            # refuses an unknown EVAL.PIN_MODE
-    if not getattr(scheduler, "supports_pin", False):
-        raise ValueError(f"{type(scheduler).__name__}.step takes no pin: use GuidanceDDIMScheduler, GuidanceDDPMScheduler or "
-                         "GuidanceDPMSolverMultistepScheduler")
-    if mode == "repaint":
-        if step_noise is not None:
-            raise ValueError("generate_traj: a `repaint` pin shares each step's own noise; `step_noise` injects tensors for the "
-                             "DDPM steps alone -- use noise=DeviceNoise(...) or a `clean` pin")
-        if getattr(scheduler, "deterministic", False) and not isinstance(noise, DeviceNoise):
-            raise ValueError("generate_traj: a `repaint` pin on the DPM-Solver++ sampler needs noise=DeviceNoise(...): the solver "
-                             "has no noise of its own, the pin's is drawn inside the step kernel")
-    return pin.with_mode(mode)
-
-
 def warm_init(prev: torch.Tensor, rows: int, shift: int, level: Tuple[float, float], noise: DeviceNoise,
               motion: Optional[torch.Tensor] = None, zero_first: bool = True) -> torch.Tensor:
     """One launch of `adx_warm_init` ("warm start v1", include/adx.h): [rows, H, D] from prev [prev_rows, H, D] under the
@@ -206,58 +108,136 @@ def warm_init(prev: torch.Tensor, rows: int, shift: int, level: Tuple[float, flo
     return out
 
 
-def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
-                  init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, scale_xy: bool = True,
-                  step_noise: Optional[Callable[[int, tuple], torch.Tensor]] = None,
-                  set_timesteps: bool = True, noise: Optional[DeviceNoise] = None, candidates: int = 1,
-                  selector: Optional[TrajectorySelector] = None, return_selection: bool = False,
-                  warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
-                  controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None,
-                  pin: Optional[Pin] = None):
-    """`noise`: a DeviceNoise.  The call is then one tick of the noise stream: `begin_tick()` first, the initial trajectory
-    (when `init_trajs` is not given) from `INIT_SLOT`, and every scheduler step draws inside its kernel at the slot of its
-    timestep -- no noise tensor, no torch generator.
+@dataclass(frozen=True, eq=False)
+class TickPlan:
+    """Every decision of one sampling tick, made once by `plan_tick` and only read afterwards: by `generate_traj`, which runs it,
+    and by `GraphedSampler`, which keys its captured graphs on `key()`.  Each field says how a captured graph sees it: "baked"
+    (a host value that becomes part of a graph node: it belongs in `key()`), "buffer" (a tensor whose values travel through a
+    static buffer: new values replay, they never capture again) or "derived" (a function of baked fields alone)."""
+    # ---- shapes ----
+    S: int                  # baked.  Scenes = image.shape[0]
+    # baked.  Candidates per scene: the argument, or EVAL.CANDIDATES when it is left at 1 (absent key: 1).  K > 1 is best-of-K
+    # sampling: the loop runs on K * S rows in candidate-major order (candidate k of scene s is row k * S + s and draws logical row
+    # k * S + s of the noise stream), the targets are tiled K times, the conditioning table keeps the image batch at S (the encoder
+    # runs once per scene) and after the final clamp `selector` picks the [S, H, D] winners.  Needs `hoisted` and an unsharded noise
+    K: int
+    selector: Optional[TrajectorySelector]   # baked (its three weights).  At K > 1: the argument, or TrajectorySelector(*EVAL.SELECT)
+    rows: int               # baked.  Rows of the loop: init_trajs.shape[0] when init_trajs is given, else K * S
+    H: int                  # baked.  MODEL.HORIZON
+    D: int                  # baked.  MODEL.TRANSITION_DIM
+    # ---- guidance and loop switches ----
+    n: int                  # baked.  EVAL.SAMPLE_STEPS
+    use: GuidanceType       # baked.  GUIDANCE.USE_COND
+    free_scale: Optional[float]    # baked.  GUIDANCE.FREE_SCALE under FREE_GUIDANCE, else None
+    fuse: bool              # baked.  The classifier-free combine and `[:, 0, :3] = 0` run inside the step kernel
+    # baked.  What the UNet derives from (t, target, image feature) alone does not change inside the loop: with the perception memo
+    # on (the product default) it is computed for all timesteps in one pass, and each step then starts at the first convolution.
+    # The reference-faithful mode (cache_perception = False) keeps the reference's per-step recomputation
+    hoisted: bool
+    table_rows: int         # derived.  Rows of the conditioning table: `rows`, twice that under FREE_GUIDANCE
+    is_ddpm: bool           # baked.  The step takes an injected `variance_noise`: the DDPM schedulers (a deterministic solver has none)
+    pair_identity: bool     # derived.  One row and a table: the table's rows make the classifier-free pair, not a cat
+    # ---- the noise of the tick ----
+    # by address.  The call is one tick of the stream: every step draws inside its kernel at the slot of its timestep -- no noise
+    # tensor, no torch generator -- and a graph node reads the stream's state through its pointer
+    noise: Optional[DeviceNoise]
+    step_noise: Optional[Callable[[int, tuple], torch.Tensor]]     # eager only.  Injected tensors for the DDPM steps
+    # ---- how the tick starts ----
+    # baked.  "warm": `adx_warm_init` from warm.prev; "init": a clone of init_trajs; "stream": the noise stream's INIT_SLOT draw;
+    # "randn": torch.randn (a GraphedSampler draws it outside the graph and hands it in as init_trajs: "init" to a graph)
+    start: str
+    # ---- warm start ----
+    # baked.  m > 0: the tick ends by copying the clamped, unscaled [S, H, D] result (the winners at K > 1) into warm.prev.
+    # 0: no `warm`, or one that is off -- the loop as it was
+    m_warm: int
+    shift: int              # baked.  Waypoints the vehicle passed between two ticks
+    # baked.  warm.valid, as the plan found it.  A warm tick builds its `rows` start rows from warm.prev (row r from scene r % S) and
+    # `motion` at the noise level of timesteps[i0], sets the scheduler's begin index to i0 and runs timesteps[i0:] only; clamp,
+    # selection, scaling and the copy into warm.prev follow as on a cold tick
+    is_warm: bool
+    motion: Optional[torch.Tensor]    # buffer; whether it is there is baked.  [S, 3] = (tx, ty, phi) per scene, on a warm tick only
+    i0: int                 # derived.  n - m_warm on a warm tick, else 0
+    # ---- controller ----
+    # baked (identity, state address, every setting).  The tick ends with one launch of `controller.step` on the clamped, unscaled
+    # [S, H, D] result (the winners at K > 1) with xy_scale = model.magic_num and the scenes' targets ([S, 2] in the model's units;
+    # None: the waypoint after the controller's last stands in)
+    controller: Optional[DeviceController]
+    velocity: Optional[torch.Tensor]  # buffer; whether it is there is baked.  [S], the scenes' current speeds
+    # ---- pin ----
+    # known and mask: buffers; presence, mode and shape: baked.  The pin with its mode resolved.  Every `scheduler.step` of the loop
+    # gets it (fused or not, all three guidance branches) and blends inside its kernel; the K * S rows read the [S, H, D] pin
+    # directly (row r reads scene r % S), nothing is tiled.  Cells with mask 1 equal `known` in the result wherever |known| <= 1,
+    # outside `[:, 0, :3]`
+    pin: Optional[Pin]
+    # derived.  `clean` mode also blends the start rows once at loop entry (`adx_pin_apply` -- on the cold draw, init_trajs or a warm
+    # start's output -- between two writes of `[:, 0, :3] = 0`); `repaint` mode has no entry blend, its first step is the entry
+    entry_blend: bool
 
-    `candidates` = K > 1: best-of-K sampling.  With S = image.shape[0] scenes the loop runs on K * S rows in candidate-major
-    order (candidate k of scene s is row k * S + s, and draws logical row k * S + s of the noise stream); the targets are
-    tiled K times and the conditioning table keeps the image batch at S, so the encoder runs once per scene.  After the
-    final clamp `selector` (default: `TrajectorySelector(*cfg.EVAL.SELECT)`) scores the candidates against `target` on the
-    device and the call returns the [S, H, D] winners, xy-scaled as usual.  `init_trajs`, when given, is [K * S, H, D].
-    `return_selection=True` returns `(traj, Selection)`, whose `candidates` is the [K, S, H, D] tensor scaled like `traj`
-    (`(traj, None)` at K = 1, where no selector runs).  Needs the hoisted conditioning path (`fuse=True`, `model.cache_perception`
-    on) and an unsharded `noise`.  K = 1 (the default, or EVAL.CANDIDATES when the argument is left at 1) is the loop as it was.
+    def key(self) -> tuple:
+        """Everything baked, as a hashable: two plans with equal keys capture the same graph over the same shapes."""
+        sel, ctl, pin = self.selector, self.controller, self.pin
+        return (self.S, self.K, None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus), self.rows, self.H, self.D,
+                self.n, self.use, self.free_scale, self.fuse, self.hoisted, self.is_ddpm,
+                "init" if self.start == "randn" else self.start,
+                self.m_warm, self.shift, self.is_warm, self.motion is None,
+                None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), self.velocity is None),
+                None if pin is None else (pin.mode, tuple(pin.known.shape)))
 
-    `warm` = a WarmStart with steps = m > 0: while `warm.valid` is False the tick is cold -- the loop as it was -- and ends by
-    copying the clamped, unscaled [S, H, D] result (the winners at K > 1) into `warm.prev`.  After that a tick is warm: with
-    n = EVAL.SAMPLE_STEPS and i0 = n - m, `adx_warm_init` builds the K * S start rows from `warm.prev` (row r from scene r % S)
-    and the optional `motion` [S, 3] = (tx, ty, phi) at the noise level of `timesteps[i0]`, `scheduler.set_begin_index(i0)`,
-    and the loop runs `timesteps[i0:]` only; clamp, selection, scaling and the copy into `warm.prev` follow as on a cold tick.
-    Needs `noise` (the re-noise is the stream's INIT_SLOT draw of the tick).  m = 0 is `warm=None`.
 
-    `controller` = a DeviceController built for S scenes on the image's device, `velocity` [S] = their current speeds (may be
-    left out with source='action'): the tick ends with one launch of `controller.step` on the clamped, unscaled [S, H, D] result
-    (the winners at K > 1) with `xy_scale = model.magic_num` and the scenes' targets ([S, 2] in the model's units; None: the
-    waypoint after the controller's last stands in).  The order at the end of a tick is fixed: clamp, selection, the copy
-    into `warm.prev`, the control launch, xy scaling.  The call then returns `(traj, control)` -- `(traj, selection, control)`
-    with `return_selection=True` -- with control [S, 3] = (throttle, steer, brake); `traj` is bit for bit what the call
-    without a controller returns.  Without a controller nothing changes.
+def _hoists(model) -> bool:
+    return bool(getattr(model, "cache_perception", False)) and hasattr(model, "time_conditioning")
 
-    `pin` = a Pin whose known / mask are [S, H, D] on the image's device, in the model's own units and this tick's ego frame:
-    "pinned waypoints v1".  Every `scheduler.step` of the loop gets it (fused or not, all three guidance branches) and blends
-    inside its kernel; with `candidates` = K the K * S rows read the [S, H, D] pin directly (row r reads scene r % S), nothing is
-    tiled.  `clean` mode also blends the start rows once at loop entry (`adx_pin_apply` -- on the cold draw, `init_trajs` or a
-    warm start's output -- between two writes of `[:, 0, :3] = 0`); `repaint` mode has no entry blend, its first step is the
-    entry.  Clamp, selection, the copy into `warm.prev`, the control launch and xy scaling follow untouched, so the warm state
-    and the controller see the pinned result: cells with mask 1 equal `known` there wherever |known| <= 1, outside
-    `[:, 0, :3]`.  A `repaint` pin needs `noise` with the DPM-Solver++ sampler and does not take `step_noise`.  None is the loop
-    as it was.  What a pin does to driving quality depends on trained weights and is not measured in this repository."""
+
+def _pin_plan(cfg, pin: Optional[Pin], image, scheduler, noise, step_noise=None, graphed: bool = False) -> Optional[Pin]:
+    """The pin section of `plan_tick`: the pin with its mode resolved (None without one), or a refusal."""
+    if pin is None:
+        return None
+    want = (int(image.shape[0]), int(cfg.MODEL.HORIZON), int(cfg.MODEL.TRANSITION_DIM))
+    if not isinstance(pin, Pin):
+        raise TypeError(f"generate_traj: `pin` must be a Pin, got {type(pin).__name__}")
+    for name, t in (("known", pin.known), ("mask", pin.mask)):
+        if tuple(t.shape) != want or t.device != image.device or t.dtype != torch.float32:
+            raise ValueError(f"pin.{name} must be a float32 tensor {want} = (scenes, MODEL.HORIZON, MODEL.TRANSITION_DIM) on "
+                             f"{image.device}, got {tuple(t.shape)}, {t.dtype} on {t.device}")
+    pin = pin.with_mode(pin.resolve(cfg))          # refuses an unknown EVAL.PIN_MODE
+    if not getattr(scheduler, "supports_pin", False):
+        raise ValueError(f"{type(scheduler).__name__}.step takes no pin: use GuidanceDDIMScheduler, GuidanceDDPMScheduler or "
+                         "GuidanceDPMSolverMultistepScheduler")
+    if pin.mode == "repaint":
+        if step_noise is not None:
+            raise ValueError("generate_traj: a `repaint` pin shares each step's own noise; `step_noise` injects tensors for the "
+                             "DDPM steps alone -- use noise=DeviceNoise(...) or a `clean` pin")
+        if getattr(scheduler, "deterministic", False) and not isinstance(noise, DeviceNoise):
+            raise ValueError("generate_traj: a `repaint` pin on the DPM-Solver++ sampler needs noise=DeviceNoise(...): the solver "
+                             "has no noise of its own, the pin's is drawn inside the step kernel")
+        if graphed and noise is None:
+            raise ValueError("GraphedSampler: a `repaint` pin needs noise=DeviceNoise(...) at construction: a noise tensor drawn "
+                             "during the capture would replay on every tick")
+    return pin
+
+
+def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
+              init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, set_timesteps: bool = True,
+              noise: Optional[DeviceNoise] = None, step_noise=None, candidates: int = 1,
+              selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
+              motion: Optional[torch.Tensor] = None, controller: Optional[DeviceController] = None,
+              velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, graphed: bool = False) -> TickPlan:
+    """The TickPlan of a `generate_traj` call with these arguments (`graphed`: of a GraphedSampler call).  Pure: no launch, no device
+    allocation (but one: a strided `motion` is packed, as it always was), no tick of the noise stream, nothing written to the
+    scheduler, `warm` or the controller -- so every refusal comes before any of those and before a capture opens, in the order
+    candidates, `noise` / `step_noise`, warm, control, pin.  `scheduler` is read for a warm tick on the caller's own timesteps
+    (`set_timesteps=False`) and for a pin; `is_ddpm` asks it with defaults."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
-    model.eval()
-    device = image.device
-    K, selector = _candidates(cfg, candidates, selector)
-    S = image.shape[0]
+    S, device = int(image.shape[0]), image.device
+    hoisted = bool(fuse) and _hoists(model)
+    # ---- candidates: the keyword arguments left at their defaults read EVAL.CANDIDATES / EVAL.SELECT ----
+    K = int(candidates) if int(candidates) != 1 else int(getattr(cfg.EVAL, "CANDIDATES", 1))
+    if not 1 <= K <= MAX_CANDIDATES:
+        raise ValueError(f"candidates must be 1..{MAX_CANDIDATES}, got {K}")
     if K > 1:
-        if not (fuse and getattr(model, "cache_perception", False) and hasattr(model, "time_conditioning")):
+        if selector is None:
+            selector = TrajectorySelector(*getattr(cfg.EVAL, "SELECT", (1.0, 0.0, 0.0)))
+        if not hoisted:
             raise ValueError("generate_traj: candidates > 1 needs the hoisted conditioning path: fuse=True and "
                              "model.cache_perception on (the per-step path would run the encoder on K * S rows)")
         if noise is not None and noise.row_offset > 0:
@@ -267,116 +247,190 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
             raise ValueError(f"init_trajs must have candidates * scenes = {K * S} rows, got {tuple(init_trajs.shape)}")
     if noise is not None and step_noise is not None:
         raise ValueError("generate_traj: pass `noise` (the in-kernel stream) or `step_noise` (injected tensors), not both")
-    m_warm, shift, is_warm, motion = _warm_plan(cfg, warm, noise, init_trajs, image, K, motion,
-                                                None if set_timesteps else scheduler)
-    velocity = _control_plan(cfg, controller, velocity, image, target is not None)
-    pin = _pin_plan(cfg, pin, image, scheduler, noise, step_noise)
+    n, H, D = int(cfg.EVAL.SAMPLE_STEPS), int(cfg.MODEL.HORIZON), int(cfg.MODEL.TRANSITION_DIM)
+    # ---- warm ----
+    if motion is not None:
+        if warm is None:
+            raise ValueError("generate_traj: `motion` is the odometry of a warm start; pass warm=WarmStart(...) with it")
+        # checked on every tick it is given, cold ones included (which do not read it): a wrong shape shows on the first call
+        motion = L.require_gpu_f32(motion, "motion")
+        if tuple(motion.shape) != (S, 3) or motion.device != device:
+            raise ValueError(f"motion must be [{S}, 3] = (tx, ty, phi) per scene on {device}, got {tuple(motion.shape)} "
+                             f"on {motion.device}")
+    m_warm, shift = (0, 0) if warm is None else warm.resolve(cfg)
+    is_warm = False
+    if m_warm == 0:
+        shift = 0
+    else:
+        if m_warm > n:
+            raise ValueError(f"WarmStart: steps = {m_warm} is more than EVAL.SAMPLE_STEPS = {n}")
+        if not 0 <= shift < H:
+            raise ValueError(f"WarmStart: shift = {shift} must be in 0..{H - 1} (MODEL.HORIZON = {H})")
+        if not isinstance(noise, DeviceNoise):
+            raise ValueError("WarmStart needs noise=DeviceNoise(...): the re-noise is drawn inside the warm-start kernel")
+        if noise.device != device:
+            raise ValueError(f"the DeviceNoise lives on {noise.device}, the image on {device}")
+        if warm.prev is not None and (tuple(warm.prev.shape) != (S, H, D) or warm.prev.device != device):
+            raise ValueError(f"WarmStart: the state holds {tuple(warm.prev.shape)} on {warm.prev.device}, this tick is "
+                             f"{(S, H, D)} on {device}; use a new WarmStart for another batch shape or device")
+        is_warm = bool(warm.valid)
+    if is_warm:
+        if init_trajs is not None:
+            raise ValueError("generate_traj: `init_trajs` and a valid warm state both name the tick's start; warm.reset() first "
+                             "for a cold tick from init_trajs")
+        if not set_timesteps and len(scheduler.timesteps) != n:    # a caller that keeps its own timesteps
+            raise ValueError(f"the scheduler holds {len(scheduler.timesteps)} timesteps, EVAL.SAMPLE_STEPS is {n}")
+    else:
+        motion = None
+    # ---- control ----
+    if controller is None:
+        if velocity is not None:
+            raise ValueError("generate_traj: `velocity` is the speed a controller reads; pass controller=DeviceController(...) with it")
+    else:
+        if controller.scenes != S or controller.device != device:
+            raise ValueError(f"the DeviceController holds the windows of {controller.scenes} scenes on {controller.device}, this tick "
+                             f"is {S} scenes on {device}; use a controller of its own for another batch or device")
+        controller.check(H, D, target is not None)
+        if velocity is None:
+            if controller.source != "action":
+                raise ValueError("generate_traj: a controller with source='pid' needs `velocity` [S], the scenes' current speeds")
+        elif not torch.is_tensor(velocity) or tuple(velocity.shape) != (S,) or velocity.device != device or \
+                velocity.dtype != torch.float32:
+            what = (tuple(velocity.shape), velocity.dtype, velocity.device) if torch.is_tensor(velocity) else type(velocity).__name__
+            raise ValueError(f"velocity must be a float32 tensor [{S}] on {device}, got {what}")
+    pin = _pin_plan(cfg, pin, image, scheduler, noise, step_noise, graphed)
+    rows = K * S if init_trajs is None else int(init_trajs.shape[0])
+    free = use == GuidanceType.FREE_GUIDANCE
+    return TickPlan(S=S, K=K, selector=selector if K > 1 else None, rows=rows, H=H, D=D, n=n, use=use,
+                    free_scale=float(cfg.GUIDANCE.FREE_SCALE) if free else None, fuse=bool(fuse), hoisted=hoisted,
+                    table_rows=2 * rows if free else rows, pair_identity=rows == 1 and hoisted, noise=noise, step_noise=step_noise,
+                    is_ddpm=not getattr(scheduler, "_is_ddim", False) and not getattr(scheduler, "deterministic", False),
+                    start="warm" if is_warm else "init" if init_trajs is not None else "randn" if noise is None else "stream",
+                    m_warm=m_warm, shift=shift, is_warm=is_warm, motion=motion, i0=n - m_warm if is_warm else 0,
+                    controller=controller, velocity=velocity, pin=pin, entry_blend=pin is not None and pin.mode == "clean")
+
+
+def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
+                  init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, scale_xy: bool = True,
+                  step_noise: Optional[Callable[[int, tuple], torch.Tensor]] = None,
+                  set_timesteps: bool = True, noise: Optional[DeviceNoise] = None, candidates: int = 1,
+                  selector: Optional[TrajectorySelector] = None, return_selection: bool = False,
+                  warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
+                  controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None,
+                  pin: Optional[Pin] = None):
+    """One sampling tick: `plan_tick` decides (what each argument means is written on the TickPlan field it becomes), this
+    function runs the plan.  With S = image.shape[0] scenes:
+
+    `target` [2] or [S, 2]; `init_trajs` [K * S, H, D] or None (a draw); `noise`: a DeviceNoise, of which the call is one tick
+    (`begin_tick()` first); `step_noise`: injected DDPM noise tensors instead; `candidates` = K and `selector`: best-of-K;
+    `warm` and `motion`: warm start; `controller` and `velocity`: the device controller; `pin`: pinned waypoints; `fuse`,
+    `set_timesteps`, `scale_xy`: as the module docstring says.
+
+    The order at the end of a tick is fixed: clamp, selection (K > 1), the copy into `warm.prev`, the control launch, xy scaling
+    -- so the warm state and the controller see the clamped, unscaled, pinned result.
+
+    Returns `traj` [S, H, D] (the winners at K > 1); `(traj, selection)` with `return_selection=True` (a Selection whose
+    `candidates` is the [K, S, H, D] tensor scaled like `traj`; None at K = 1, where no selector runs); with a controller
+    `control` [S, 3] = (throttle, steer, brake) comes last: `(traj, control)` or `(traj, selection, control)`.  `traj` is bit for
+    bit what the call without a controller returns."""
+    plan = plan_tick(model, scheduler, cfg, image, target, init_trajs, fuse=fuse, set_timesteps=set_timesteps, noise=noise,
+                     step_noise=step_noise, candidates=candidates, selector=selector, warm=warm, motion=motion,
+                     controller=controller, velocity=velocity, pin=pin)
+    model.eval()
+    device, K, S = image.device, plan.K, plan.S
+    noise, controller = plan.noise, plan.controller    # from here on the plan is the one source
     if noise is not None:
         noise.begin_tick()
-    i0 = 0
-    if is_warm:
+    if plan.start == "warm":
         if set_timesteps:
-            scheduler.set_timesteps(cfg.EVAL.SAMPLE_STEPS, device=device)
-        i0 = len(scheduler.timesteps) - m_warm
+            scheduler.set_timesteps(plan.n, device=device)
         # zero_first: the kernel writes the `[:, 0, :3] = 0` of the loop's entry itself
-        trajs = warm_init(warm.prev, K * S, shift, scheduler.noise_level(scheduler.timesteps[i0]), noise, motion)
+        trajs = warm_init(warm.prev, plan.rows, plan.shift, scheduler.noise_level(scheduler.timesteps[plan.i0]), noise, plan.motion)
     else:
-        if init_trajs is None:
-            shape = (K * S, cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM)
-            init_trajs = torch.randn(shape, device=device) if noise is None else noise.normal(DeviceNoise.INIT_SLOT, shape)
+        if plan.start != "init":
+            shape = (plan.rows, plan.H, plan.D)
+            init_trajs = torch.randn(shape, device=device) if plan.start == "randn" else noise.normal(DeviceNoise.INIT_SLOT, shape)
         trajs = init_trajs.clone().detach()
-    B = trajs.shape[0]
-    scene_tgt = _targets(target, S) if K > 1 else None
-    tgt = _targets(target, B) if K == 1 else (None if scene_tgt is None else scene_tgt.repeat(K, 1))
-    cond = None
-    if tgt is not None and use == GuidanceType.FREE_GUIDANCE:
-        cond = torch.cat([tgt, torch.zeros_like(tgt)], dim=0)   # interact.py:121-127
-    if not is_warm:
+    # the scenes' targets, and the rows': at K = 1 a row is its own scene
+    scene_tgt = _targets(target, plan.rows if K == 1 else S)
+    tgt = scene_tgt if K == 1 or scene_tgt is None else scene_tgt.repeat(K, 1)
+    free = tgt is not None and plan.use == GuidanceType.FREE_GUIDANCE
+    cond = torch.cat([tgt, torch.zeros_like(tgt)], dim=0) if free else None   # interact.py:121-127
+    if plan.start != "warm":
         trajs[:, 0, :3] = 0.0
         if set_timesteps:
-            scheduler.set_timesteps(cfg.EVAL.SAMPLE_STEPS, device=device)
-    if pin is not None and pin.mode == "clean":
-        # the entry blend, where the callers write their one pinned cell group before the loop; waypoint 0 keeps the last word
-        trajs = pin_apply(trajs if trajs.is_contiguous() else trajs.contiguous(), pin)
+            scheduler.set_timesteps(plan.n, device=device)
+    if plan.entry_blend:
+        # where the callers write their one pinned cell group before the loop; waypoint 0 keeps the last word
+        trajs = pin_apply(trajs if trajs.is_contiguous() else trajs.contiguous(), plan.pin)
         trajs[:, 0, :3] = 0.0
-    # whose step takes an injected `variance_noise`: the DDPM schedulers (a deterministic solver has no noise argument)
-    is_ddpm = not getattr(scheduler, "_is_ddim", False) and not getattr(scheduler, "deterministic", False)
-    # What the UNet derives from (t, target, image feature) alone does not change inside the loop: with the perception
-    # memo on (the product default) it is computed for all timesteps in one pass, and each step then starts at the first
-    # convolution.  The reference-faithful mode (cache_perception = False) keeps the reference's per-step recomputation.
-    tc = None
-    if fuse and getattr(model, "cache_perception", False) and hasattr(model, "time_conditioning"):
-        rows = 2 * B if use == GuidanceType.FREE_GUIDANCE else B
-        ts = scheduler.timesteps
-        ts = ts.tensor if hasattr(ts, "tensor") else torch.as_tensor(ts)
-        if i0 > 0:
-            ts = ts[i0:]        # a warm tick's table holds the suffix only; the loop indexes it relative to i0
-        with torch.no_grad():
-            # table row r reads image feature r % S: with candidate-major rows that is the row's own scene
-            tc = model.time_conditioning(image, ts.to(device), cond=cond, rows=rows)
-    pair = (lambda x: x) if B == 1 and tc is not None else (lambda x: torch.cat([x, x], dim=0))
+    # a warm tick's table holds the suffix only; table row r reads image feature r % S: with candidate-major rows its own scene
+    tc = _conditioning_table(model, scheduler, image, plan.table_rows, cond, plan.i0) if plan.hoisted else None
     # nothing in this loop writes `image`: say so, so that the reference-faithful per-step encoder pass of a batched tick may run
     # beside the previous step's temporal stack (modeling/perception.py:frozen_image; a no-op for holders without the method)
     frozen = getattr(getattr(model, "perception", None), "frozen_image", None)
-    if is_warm:
-        scheduler.set_begin_index(i0)
+    if plan.is_warm:
+        scheduler.set_begin_index(plan.i0)
     try:
         with (frozen(image) if frozen is not None else contextlib.nullcontext()):
-            trajs = _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device,
-                               noise, i0, pin)
+            trajs = _tick_loop(model, scheduler, plan, image, trajs, tgt, cond, tc)
     finally:
-        if is_warm:
+        if plan.is_warm:
             scheduler.set_begin_index(0)       # the begin index belongs to this tick: a later loop on the scheduler starts at 0
     trajs = trajs.to(torch.float32).clamp(-1, 1)
-    if K == 1:
-        if m_warm > 0:
-            warm._store(trajs)
-        if controller is not None:
-            control = controller.step(trajs, velocity, tgt, xy_scale=model.magic_num)
-        if scale_xy:
-            trajs[..., :2] *= model.magic_num
-        if controller is not None:
-            return (trajs, None, control) if return_selection else (trajs, control)
-        return (trajs, None) if return_selection else trajs
-    # the cost is taken in the model's own units (before xy scaling: the units of `target`)
-    sel = selector(trajs, S, scene_tgt)
-    best = sel.best
-    if m_warm > 0:
+    best, sel = trajs, None                            # at K = 1 the trajectory is its own winner
+    if K > 1:
+        sel = plan.selector(trajs, S, scene_tgt)       # the cost is taken in the model's own units (the units of `target`)
+        best = sel.best
+    if plan.m_warm > 0:
         warm._store(best)
-    if controller is not None:
-        control = controller.step(best, velocity, scene_tgt, xy_scale=model.magic_num)
+    control = None if controller is None else controller.step(best, plan.velocity, scene_tgt, xy_scale=model.magic_num)
     if scale_xy:
         best[..., :2] *= model.magic_num
-    if not return_selection:
-        return best if controller is None else (best, control)
-    cands = trajs.reshape(K, S, trajs.shape[1], trajs.shape[2])
-    if scale_xy:
-        cands[..., :2] *= model.magic_num
-    sel = Selection(best, sel.index, sel.cost, cands)
-    return (best, sel) if controller is None else (best, sel, control)
+    if K > 1 and return_selection:
+        cands = trajs.reshape(K, S, trajs.shape[1], trajs.shape[2])
+        if scale_xy:
+            cands[..., :2] *= model.magic_num
+        sel = Selection(best, sel.index, sel.cost, cands)
+    return _tick_result(best, sel, control, return_selection, controller is not None)
 
 
-def _tick_loop(model, scheduler, cfg, use, image, trajs, B, tgt, cond, tc, pair, fuse, is_ddpm, step_noise, device, noise=None,
-               begin=0, pin=None):
-    """`begin` > 0: the schedule's suffix `timesteps[begin:]`; `i` (the row of the conditioning table) counts from there.
-    `pin`: handed to every `scheduler.step`."""
+def _tick_result(traj, selection, control, return_selection: bool, controlled: bool):
+    """traj | (traj, selection) | (traj, control) | (traj, selection, control)"""
+    out = (traj,) + ((selection,) if return_selection else ()) + ((control,) if controlled else ())
+    return traj if len(out) == 1 else out
+
+
+def _conditioning_table(model, scheduler, image, rows: int, cond=None, begin: int = 0):
+    """What `model.time_conditioning` gives for `scheduler.timesteps[begin:]`: one pass for all the steps of a loop (`_hoists`)."""
+    ts = scheduler.timesteps
+    ts = ts.tensor if hasattr(ts, "tensor") else torch.as_tensor(ts)
+    if begin > 0:
+        ts = ts[begin:]         # the loop indexes the table relative to `begin`
+    with torch.no_grad():
+        return model.time_conditioning(image, ts.to(image.device), cond=cond, rows=rows)
+
+
+def _tick_loop(model, scheduler, plan: TickPlan, image, trajs, tgt, cond, tc):
+    """The steps `timesteps[plan.i0:]`; `i` (the row of the conditioning table) counts from there."""
+    use, fuse, B = plan.use, plan.fuse, plan.rows
+    extra = {} if plan.noise is None else {"generator": plan.noise}
+    if plan.pin is not None:
+        extra["pin"] = plan.pin
     action = None
-    for i, t in enumerate(scheduler.timesteps if begin == 0 else list(scheduler.timesteps)[begin:]):
+    for i, t in enumerate(scheduler.timesteps if plan.i0 == 0 else list(scheduler.timesteps)[plan.i0:]):
         tck = None if tc is None else (tc, i)
-        extra = {} if noise is None else {"generator": noise}
-        if pin is not None:
-            extra["pin"] = pin
-        if is_ddpm and step_noise is not None:
-            extra["variance_noise"] = step_noise(i, tuple(trajs.shape)).to(device)
+        if plan.is_ddpm and plan.step_noise is not None:
+            extra["variance_noise"] = plan.step_noise(i, tuple(trajs.shape)).to(image.device)
         if use == GuidanceType.FREE_GUIDANCE:
             with torch.no_grad():
-                out = model(pair(trajs), image, t.reshape(-1), cond=cond, time_cond=tck)
+                out = model(trajs if plan.pair_identity else torch.cat([trajs, trajs], dim=0), image, t.reshape(-1), cond=cond,
+                            time_cond=tck)
             if fuse:
-                trajs = scheduler.step(out, t, trajs, cfg_scale=cfg.GUIDANCE.FREE_SCALE, zero_first=True,
-                                       **extra).prev_sample
+                trajs = scheduler.step(out, t, trajs, cfg_scale=plan.free_scale, zero_first=True, **extra).prev_sample
                 continue
             c, u = out.chunk(2, dim=0)
-            model_output = u + cfg.GUIDANCE.FREE_SCALE * (c - u)
+            model_output = u + plan.free_scale * (c - u)
             trajs = scheduler.step(model_output, t, trajs, **extra).prev_sample
         elif use == GuidanceType.CLASSIFIER_GUIDANCE:
             with torch.no_grad():
@@ -425,10 +479,7 @@ def evaluate_sample(model, noise_scheduler, image: torch.Tensor, init_trajs: Opt
     trajs = init_trajs.clone()
     trajs[:, 0, :3] = 0
     noise_scheduler.set_timesteps(n_steps, device=image.device)
-    tc = None
-    if getattr(model, "cache_perception", False) and hasattr(model, "time_conditioning"):     # as in generate_traj
-        ts = noise_scheduler.timesteps
-        tc = model.time_conditioning(image, (ts.tensor if hasattr(ts, "tensor") else torch.as_tensor(ts)).to(image.device), rows=B)
+    tc = _conditioning_table(model, noise_scheduler, image, B) if _hoists(model) else None
     for i, t in enumerate(noise_scheduler.timesteps):
         out = model(trajs, image, t.reshape(-1).repeat(B), time_cond=None if tc is None else (tc, i))
         kw = {} if noise is None else {"generator": noise}
@@ -583,29 +634,17 @@ class GraphedSampler:
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None,
                  velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None) -> torch.Tensor:
-        K, sel = _candidates(self.cfg, self.candidates, self.selector)
         warm = self.warm
-        m_warm, shift, is_warm, motion = _warm_plan(self.cfg, warm, self.noise, init_trajs, image, K, motion)
-        ctl = self.controller
-        velocity = _control_plan(self.cfg, ctl, velocity, image, target is not None)
-        pin = _pin_plan(self.cfg, pin, image, self.scheduler, self.noise)
-        if pin is not None and pin.mode == "repaint" and self.noise is None:
-            raise ValueError("GraphedSampler: a `repaint` pin needs noise=DeviceNoise(...) at construction: a noise tensor drawn "
-                             "during the capture would replay on every tick")
-        if init_trajs is None and self.noise is None:
-            init_trajs = torch.randn((K * image.shape[0], self.cfg.MODEL.HORIZON, self.cfg.MODEL.TRANSITION_DIM),
-                                     device=image.device)
+        plan = plan_tick(self.model, self.scheduler, self.cfg, image, target, init_trajs, noise=self.noise,
+                         candidates=self.candidates, selector=self.selector, warm=warm, motion=motion,
+                         controller=self.controller, velocity=velocity, pin=pin, graphed=True)
+        motion, pin = plan.motion, plan.pin
+        if plan.start == "randn":
+            init_trajs = torch.randn((plan.rows, plan.H, plan.D), device=image.device)
         # init_trajs None (with a DeviceNoise): the initial trajectory is drawn inside the graph, from INIT_SLOT
+        # the sampler's own part (the shapes of the static buffers, the device, whose warm state the graph writes), then the plan's
         key = (tuple(image.shape), None if target is None else tuple(target.shape),
-               None if init_trajs is None else tuple(init_trajs.shape), image.device,
-               self.cfg.EVAL.SAMPLE_STEPS, self.cfg.GUIDANCE.USE_COND, K,
-               None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus),   # baked into the select node
-               # a cold and a warm graph (m_warm == 0: the loop as it was); baked into the warm-start node
-               None if m_warm == 0 else (m_warm, shift, is_warm, motion is None, id(warm)),
-               # the controller's state address and every setting are baked into the control node
-               None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), velocity is None),
-               # whether a pin is there, its mode (host scalars baked into the step nodes) and its shape
-               None if pin is None else (pin.mode, tuple(pin.known.shape)))
+               None if init_trajs is None else tuple(init_trajs.shape), image.device, id(warm), plan.key())
         g = self._graphs.get(key)
         if g is None or g.pointers != self._model_pointers():
             self._graphs.pop(key, None)
@@ -632,7 +671,7 @@ class GraphedSampler:
         if guard:
             self.model.clear_range_status()
         g.graph.replay()
-        if m_warm > 0:
+        if plan.m_warm > 0:
             warm.valid = True                  # the replay ended with the copy into warm.prev
         if guard:
             bad = self.model.range_status()

@@ -14,6 +14,7 @@ the reference's operation order, then handed BY VALUE to the fused HIP step kern
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -258,7 +259,6 @@ class SchedulerBase:
         B, H, D = x.shape
         prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
-        import ctypes as C
         if isinstance(noise, DeviceNoise) and noise.device != x.device:
             raise ValueError(f"the DeviceNoise lives on {noise.device}, the sample on {x.device}")
         if pin is not None:

@@ -432,6 +432,22 @@ def test_presence_and_mode_are_in_the_graph_key():
     assert graphs[0] is graphs[3] and graphs[1] is graphs[4] and graphs[2] is graphs[5] and len({id(g) for g in graphs}) == 3
 
 
+def test_the_graph_key_follows_the_plan_on_a_ddpm_sampler():
+    """DDPM with a DeviceNoise: cold unpinned, cold clean pin, cold repaint pin, then the first again.  `captured` goes 1, 2, 3, 3
+    and every result equals the eager tick bit for bit: the key holds what the plan bakes, and nothing that moves per tick."""
+    m, cfg, q = _setup("FREE_GUIDANCE", "ddpm")
+    z, z2 = DeviceNoise(97, DEV), DeviceNoise(97, DEV)
+    gs = GraphedSampler(m, q, cfg, noise=z, scale_xy=False)
+    for k, (mode, want_captured) in enumerate(((None, 1), ("clean", 2), ("repaint", 3), (None, 3))):
+        img, tgt = _frame(2, 98 + k, "FREE_GUIDANCE")
+        pin = None if mode is None else _pin(2, 8, 7, 102 + k, mode)
+        got = gs(img, tgt, pin=pin)
+        want = generate_traj(m, q, cfg, img, tgt, noise=z2, pin=pin, scale_xy=False)
+        assert gs.captured == want_captured, (k, mode, gs.captured)
+        assert torch.equal(_bits(got), _bits(want)), (k, mode, (got - want).abs().max().item())
+        assert z.tick() == z2.tick() == k + 1, k
+
+
 def test_refusals_come_before_any_launch_or_capture():
     m, cfg, q = _setup("FREE_GUIDANCE", "ddim")
     img, tgt = _frame(2, 95, "FREE_GUIDANCE")

@@ -1,4 +1,4 @@
-"""CPU: "pinned waypoints v1" -- the Pin object and Pin.points, every `_pin_plan` refusal that needs no device, the per-step levels
+"""CPU: "pinned waypoints v1" -- the Pin object and Pin.points, every pin refusal of `plan_tick` that needs no device, the per-step levels
 (c_known, c_known_noise, known_noise) of the three guidance schedulers against the fp32 restatement (tests/pin_ref.py), and the
 binding: the four exports declared, exported, prototyped, and refusing bad arguments on the host before any GPU work."""
 import ctypes
@@ -82,18 +82,22 @@ def test_points_pins_xy_of_the_chosen_waypoints(built):
 
 # ---- the plan ---------------------------------------------------------------------------------------------------------------
 def test_pin_plan_refuses_before_anything_runs(built):
-    """`_pin_plan` only looks: shapes, devices, dtypes, the mode, the scheduler, the noise source.  None of it needs a device, so
-    the image here is a CPU tensor (generate_traj would refuse that later, on its own)."""
+    """`plan_tick` only looks: shapes, devices, dtypes, the mode, the scheduler, the noise source.  None of it needs a device or a
+    model, so the image here is a CPU tensor (generate_traj would refuse that later, on its own)."""
     from autonomous_driving_with_diffusion_model_amd import scheduler as S
     from autonomous_driving_with_diffusion_model_amd.config import create_cfg
     from autonomous_driving_with_diffusion_model_amd.pin import Pin
-    from autonomous_driving_with_diffusion_model_amd.sampling import _pin_plan
+    from autonomous_driving_with_diffusion_model_amd.sampling import plan_tick
     cfg = create_cfg()
     cfg.MODEL.HORIZON, cfg.MODEL.TRANSITION_DIM = 8, 7
     img = torch.zeros(2, 3, 16, 16)
     ddim, ddpm = S.GuidanceDDIMScheduler(cfg=cfg, **SCHED_KW), S.GuidanceDDPMScheduler(cfg=cfg, **SCHED_KW)
     dpm = S.GuidanceDPMSolverMultistepScheduler(cfg=cfg, **SCHED_KW)
     k, m = torch.zeros(2, 8, 7), torch.ones(2, 8, 7)
+
+    def _pin_plan(cfg, pin, img, sch, noise, step_noise=None):
+        return plan_tick(None, sch, cfg, img, pin=pin, noise=noise, step_noise=step_noise).pin
+
     assert _pin_plan(cfg, None, img, ddim, None) is None
     for sch in (ddim, ddpm, dpm):
         got = _pin_plan(cfg, Pin(k, m), img, sch, None)
