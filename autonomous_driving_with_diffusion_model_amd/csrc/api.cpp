@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include "sched.h"
 #include "tconv.h"
 
 namespace adx {
@@ -64,40 +65,12 @@ const DebugSwitches& debug_switches() {
 
 int embed_forward(const adx_embed_weights* w, int dim, const int64_t* t, int t_rows, const float* cond,
                   const float* feat, int feat_rows, int rows, float* time_embed, float* mish_cond, hipStream_t s);
-int ddim_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
-              const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
-int ddpm_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
-              const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
-int ddim_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
-                  const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
-int ddpm_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
-                  const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s);
-int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, float* prev, float* x0, int b, int h,
-             int d, hipStream_t s);
-int ddim_step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
-                  int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s);
-int ddpm_step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
-                  int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s);
-int dpm_step_pin(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, const uint32_t* ns, int32_t slot,
-                 int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s);
-int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int b, int h, int d, hipStream_t s);
 int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
                 hipStream_t s);
 size_t control_state_bytes(int scenes, int n_turn, int n_speed);
 int control_step(const adx_control_cfg* c, const float* traj, const float* velocity, const float* target, void* state,
                  float* control, hipStream_t s);
 int control_reset(void* state, int scenes, int n_turn, int n_speed, const uint8_t* mask, hipStream_t s);
-int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);
-int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s);
-int noise_advance(uint32_t* state, hipStream_t s);
-int warm_init(const float* prev, int prev_rows, const float* motion, float* out, int rows, int horizon, int dim, int shift,
-              float sqrt_ab, float sqrt_1mab, const uint32_t* ns, int64_t row_offset, int zero_first, hipStream_t s);
-int add_noise(const float* x, const float* n, const int64_t* t, const float* sa, const float* sb, int n_train,
-              float* out, int batch, int horizon, int dim, int zero_first, hipStream_t s);
-
-int image_normalize(const uint8_t* src, float* dst, int n, int h, int w, const float* mean, const float* stdv,
-                    hipStream_t s);
-
 }  // namespace adx
 
 extern "C" {
@@ -161,49 +134,76 @@ int adx_embed_forward(const adx_embed_weights* w, int32_t dim, const int64_t* t,
   return adx::embed_forward(w, dim, t, t_rows, cond, img_feature, feat_rows, rows, time_embed, mish_cond,
                             (hipStream_t)s);
 }
+// The step exports: each fills the one record of sched.h; step_run / dpm_run check it and pick the kernel instantiation.
 int adx_ddim_step(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                   const float* target, const float* mask, float* prev, float* x0, int32_t batch, int32_t horizon,
                   int32_t dim, adx_stream s) {
-  return adx::ddim_step(c, model_output, sample, noise, target, mask, prev, x0, batch, horizon, dim, (hipStream_t)s);
+  adx::StepCall k;
+  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.tgt = target; k.mask = mask; k.prev = prev; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
 }
 int adx_ddpm_step(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                   const float* target, const float* mask, float* prev, float* x0, int32_t batch, int32_t horizon,
                   int32_t dim, adx_stream s) {
-  return adx::ddpm_step(c, model_output, sample, noise, target, mask, prev, x0, batch, horizon, dim, (hipStream_t)s);
+  adx::StepCall k;
+  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.tgt = target; k.mask = mask; k.prev = prev; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
 }
 int adx_ddim_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
                       int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::ddim_step_rng(c, model_output, sample, noise_state, slot, row_offset, target, mask, prev, x0, batch, horizon, dim,
-                            (hipStream_t)s);
+  ADX_REQUIRE(noise_state != nullptr, "scheduler step: null noise state");      // to step_run, no state is the tensor path
+  adx::StepCall k;
+  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
+  k.tgt = target; k.mask = mask; k.prev = prev; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
 }
 int adx_ddpm_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
                       int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::ddpm_step_rng(c, model_output, sample, noise_state, slot, row_offset, target, mask, prev, x0, batch, horizon, dim,
-                            (hipStream_t)s);
+  ADX_REQUIRE(noise_state != nullptr, "scheduler step: null noise state");      // to step_run, no state is the tensor path
+  adx::StepCall k;
+  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
+  k.tgt = target; k.mask = mask; k.prev = prev; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
 }
 int adx_dpm_step(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                  float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::dpm_step(c, model_output, sample, prev_x0, prev_sample, x0, batch, horizon, dim, (hipStream_t)s);
+  adx::DpmCall k;
+  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.prev = prev_sample; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::dpm_run(k);
 }
 int adx_ddim_step_pin(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::ddim_step_pin(c, model_output, sample, noise, noise_state, slot, row_offset, pin, prev, x0, batch, horizon, dim,
-                            (hipStream_t)s);
+  adx::StepCall k;
+  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
+  k.row_offset = row_offset; k.pin = pin; k.prev = prev; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
 }
 int adx_ddpm_step_pin(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::ddpm_step_pin(c, model_output, sample, noise, noise_state, slot, row_offset, pin, prev, x0, batch, horizon, dim,
-                            (hipStream_t)s);
+  adx::StepCall k;
+  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
+  k.row_offset = row_offset; k.pin = pin; k.prev = prev; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
 }
 int adx_dpm_step_pin(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                      const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev_sample,
                      float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::dpm_step_pin(c, model_output, sample, prev_x0, noise_state, slot, row_offset, pin, prev_sample, x0, batch, horizon,
-                           dim, (hipStream_t)s);
+  adx::DpmCall k;
+  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
+  k.pin = pin; k.prev = prev_sample; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::dpm_run(k);
 }
 int adx_pin_apply(float* x, const adx_pin* pin, const uint32_t* noise_state, int64_t row_offset, int32_t batch, int32_t horizon,
                   int32_t dim, adx_stream s) {

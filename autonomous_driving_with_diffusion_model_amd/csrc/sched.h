@@ -1,0 +1,55 @@
+// Entries of sched.hip.  A scheduler step is described by ONE record with named fields and run by ONE function: the exports of
+// api.cpp fill a StepCall / DpmCall and step_run / dpm_run validate it, pick the kernel instantiation and launch.
+#pragma once
+#include "adx_common.h"
+
+namespace adx {
+
+// One DDIM / DDPM step.  The kernel is step_kernel<ddpm, ns != null, pin != null>; z and ns may not both be given.
+struct StepCall {
+  bool ddpm = false;                  // which schedule: false DDIM, true DDPM
+  const adx_step_coef* c = nullptr;
+  const float* mo = nullptr;          // model output [batch][H][D], [2 * batch] rows when c->cfg_combine
+  const float* x = nullptr;           // sample
+  const float* z = nullptr;           // noise tensor, or
+  const uint32_t* ns = nullptr;       // the noise stream's state: the kernel draws at (slot, row_offset)
+  int32_t slot = 0;
+  int64_t row_offset = 0;
+  const float* tgt = nullptr;         // inpainting schedulers: known trajectory and
+  const float* mask = nullptr;        // its mask
+  const adx_pin* pin = nullptr;       // pinned waypoints v1
+  float* prev = nullptr;
+  float* x0 = nullptr;                // optional
+  int batch = 0, horizon = 0, dim = 0;
+  hipStream_t stream = nullptr;
+};
+
+// One DPM-Solver++ step.  The kernel is dpm_step_kernel<pin != null>; without a pin the noise fields are not looked at.
+struct DpmCall {
+  const adx_dpm_coef* c = nullptr;
+  const float* mo = nullptr;
+  const float* x = nullptr;
+  const float* px0 = nullptr;         // x0 of the previous step; null on a first-order step
+  const uint32_t* ns = nullptr;       // the pin's noise (known_noise): the stream only
+  int32_t slot = 0;
+  int64_t row_offset = 0;
+  const adx_pin* pin = nullptr;
+  float* prev = nullptr;
+  float* x0 = nullptr;                // always written
+  int batch = 0, horizon = 0, dim = 0;
+  hipStream_t stream = nullptr;
+};
+
+int step_run(const StepCall& k);
+int dpm_run(const DpmCall& k);
+int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int batch, int horizon, int dim, hipStream_t s);
+int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);
+int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s);
+int noise_advance(uint32_t* state, hipStream_t s);
+int warm_init(const float* prev, int prev_rows, const float* motion, float* out, int rows, int horizon, int dim, int shift,
+              float sqrt_ab, float sqrt_1mab, const uint32_t* ns, int64_t row_offset, int zero_first, hipStream_t s);
+int add_noise(const float* x, const float* n, const int64_t* t, const float* sa, const float* sb, int n_train, float* out,
+              int batch, int horizon, int dim, int zero_first, hipStream_t s);
+int image_normalize(const uint8_t* src, float* dst, int n, int h, int w, const float* mean, const float* stdv, hipStream_t s);
+
+}  // namespace adx

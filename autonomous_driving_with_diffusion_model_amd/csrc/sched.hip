@@ -13,6 +13,7 @@
 // and the kernel repeats the reference's elementwise operations in the same order with
 // contraction disabled, so results are bit-identical to the torch CPU path.
 //
+//
 // The step's Gaussian term comes from one of two sources, chosen at compile time: a noise TENSOR the caller drew (the
 // reference's path: torch.randn, or an injected variance_noise), or the counter-based noise stream of csrc/noise.h, evaluated
 // in the kernel where the tensor element would be read (adx_*_step_rng: no launch, no allocation, no [B,H,D] round trip, and a
@@ -21,7 +22,13 @@
 // "Pinned waypoints v1" (include/adx.h) is a compile-time variant of both step kernels (PIN): the finished prev_sample is blended
 // with the caller's known trajectory under a mask before zero_first has the last word.  The unpinned instantiations do not read
 // the pin fields, which sit behind every field they do read: their code is what it was.
-#include "adx_common.h"
+//
+// Host side (sched.h): every step export fills one record, StepCall or DpmCall, and one function, step_run or dpm_run, checks it
+// and picks the kernel instantiation from what the record holds (schedule, noise state or not, pin or not).  Every refusal of a
+// step lives in those two functions and the helpers they share with pin_apply, warm_init and add_noise: shape_check (non-empty,
+// fits the kernels' 32-bit index), noise_rows (the launch's rows inside the stream) and pin_check (what is pin-specific).
+// Device side: the arithmetic two kernels share is written once, in __device__ helpers that keep the reference's operation order.
+#include "sched.h"
 #include "noise.h"
 
 namespace adx {
@@ -36,17 +43,52 @@ struct PinArgs {
   int known_noise;
 };
 
-// prev = mask * kp + (1 - mask) * prev, kp = c_known * known + (known_noise ? c_known_noise * z : 0): the RePaint blend of the
-// inpainting steps below, every product and sum rounded on its own
-__device__ __forceinline__ float pin_blend(const PinArgs& p, int e, float z, float prev) {
+// prev = mask * kp + (1 - mask) * prev at element i of known / mask, kp = c_known * known + (known_noise ? c_known_noise * z : 0):
+// the RePaint blend of the inpainting steps and of a pin, every product and sum rounded on its own
+__device__ __forceinline__ float repaint_blend(const float* known, const float* mask, int i, float c_known, float c_known_noise,
+                                               int known_noise, float z, float prev) {
 #pragma clang fp contract(off)
-  const int ke = e % p.span;
-  const float k0 = p.c_known * p.known[ke];
-  const float k1 = p.known_noise ? p.c_known_noise * z : 0.f;
+  const float k0 = c_known * known[i];
+  const float k1 = known_noise ? c_known_noise * z : 0.f;
   const float kp = k0 + k1;
-  const float mk = p.mask[ke];
+  const float mk = mask[i];
   const float u = mk * kp, v = (1.0f - mk) * prev;
   return u + v;
+}
+
+__device__ __forceinline__ float pin_blend(const PinArgs& p, int e, float z, float prev) {
+  return repaint_blend(p.known, p.mask, e % p.span, p.c_known, p.c_known_noise, p.known_noise, z, prev);
+}
+
+// C1: uncond + free_scale * (cond - uncond) of a [2 * rows] model output, rows [0, rows) cond; else the model output itself
+__device__ __forceinline__ float cfg_model_output(const float* mo, int e, int total, int cfg_combine, float free_scale) {
+#pragma clang fp contract(off)
+  if (cfg_combine) {
+    const float cnd = mo[e], unc = mo[e + total];
+    const float d = cnd - unc;
+    const float sd = free_scale * d;
+    return unc + sd;
+  }
+  return mo[e];
+}
+
+// pred_original_sample before the clamp, from the model output m at signal level sa and noise level sb
+__device__ __forceinline__ float x0_from(int prediction_type, float sa, float sb, float xs, float m) {
+#pragma clang fp contract(off)
+  if (prediction_type == ADX_PRED_EPSILON) {
+    const float p = sb * m;
+    return (xs - p) / sa;
+  }
+  if (prediction_type == ADX_PRED_SAMPLE) return m;
+  const float p = sa * xs, q = sb * m;
+  return p - q;
+}
+
+// C2: element e of a [rows][horizon][dim] tensor lies in [:, 0, :3]
+__device__ __forceinline__ bool first_pose(int e, int horizon, int dim) {
+  const int d = e % dim;
+  const int h = (e / dim) % horizon;
+  return h == 0 && d < 3;
 }
 
 struct StepArgs {
@@ -78,38 +120,26 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= a.total) return;
   const adx_step_coef& c = a.c;
-  float m;
-  if (c.cfg_combine) {
-    const float cnd = a.mo[e], unc = a.mo[e + a.total];
-    const float d = cnd - unc;
-    const float sd = c.free_scale * d;
-    m = unc + sd;
-  } else {
-    m = a.mo[e];
-  }
+  const float m = cfg_model_output(a.mo, e, a.total, c.cfg_combine, c.free_scale);
   const float xs = a.x[e];
   const float sa = c.sqrt_alpha_t, sb = c.sqrt_beta_t;
-  float x0, eps;
+  float x0 = x0_from(c.prediction_type, sa, sb, xs, m);
+  float eps;
   if (c.prediction_type == ADX_PRED_EPSILON) {
-    const float p = sb * m;
-    x0 = (xs - p) / sa;
     eps = m;
   } else if (c.prediction_type == ADX_PRED_SAMPLE) {
-    x0 = m;
     const float p = sa * x0;
     eps = (xs - p) / sb;
   } else {
-    const float p = sa * xs, q = sb * m;
-    x0 = p - q;
     const float p2 = sa * m, q2 = sb * xs;
     eps = p2 + q2;
   }
   if (c.clip) x0 = clamp_nan(x0, -c.clip_range, c.clip_range);
+  const bool known = c.inpaint && a.tgt != nullptr && a.mask != nullptr;
   float zn;
   if (RNG) {
     // the element's index in the LOGICAL tensor, not in this launch: a shard of rows draws what the full batch draws there
-    const bool need = c.add_noise || (c.inpaint && c.known_noise && a.tgt != nullptr && a.mask != nullptr) ||
-                      (PIN && a.pin.known_noise);
+    const bool need = c.add_noise || (known && c.known_noise) || (PIN && a.pin.known_noise);
     zn = need ? noise_normal_at(a.ns, a.slot, a.base + (uint64_t)e) : 0.f;
   } else {
     zn = (a.z != nullptr) ? a.z[e] : 0.f;
@@ -125,14 +155,7 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
     prev = p + dir;
     if (c.inpaint) {
       prev = prev + c.c_const;
-      if (a.tgt != nullptr && a.mask != nullptr) {
-        const float k0 = c.c_known * a.tgt[e];
-        const float k1 = c.known_noise ? c.c_known_noise * zn : 0.f;
-        const float known = k0 + k1;
-        const float mk = a.mask[e];
-        const float u = mk * known, v = (1.0f - mk) * prev;
-        prev = u + v;
-      }
+      if (known) prev = repaint_blend(a.tgt, a.mask, e, c.c_known, c.c_known_noise, c.known_noise, zn, prev);
     }
     if (c.add_noise) {
       const float nz = c.c_noise * zn;
@@ -145,21 +168,10 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
       const float nz = c.c_noise * zn;
       prev = prev + nz;
     }
-    if (c.inpaint && a.tgt != nullptr && a.mask != nullptr) {
-      const float k0 = c.c_known * a.tgt[e];
-      const float k1 = c.known_noise ? c.c_known_noise * zn : 0.f;
-      const float known = k0 + k1;
-      const float mk = a.mask[e];
-      const float u = mk * known, v = (1.0f - mk) * prev;
-      prev = u + v;
-    }
+    if (known) prev = repaint_blend(a.tgt, a.mask, e, c.c_known, c.c_known_noise, c.known_noise, zn, prev);
   }
   if (PIN) prev = pin_blend(a.pin, e, zn, prev);      // the step's own z: no second draw
-  if (c.zero_first) {
-    const int d = e % a.dim;
-    const int h = (e / a.dim) % a.horizon;
-    if (h == 0 && d < 3) prev = 0.f;
-  }
+  if (c.zero_first && first_pose(e, a.horizon, a.dim)) prev = 0.f;
   a.prev[e] = prev;
   if (a.x0 != nullptr) a.x0[e] = x0;          // as computed: never pinned
 }
@@ -167,12 +179,33 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
 // e >> 2 is the stream's 32-bit counter word: logical elements live in [0, 2^34)
 static const int64_t kNoiseElems = (int64_t)1 << 34;
 
+// A [rows][horizon][dim] launch: not empty, and small enough for the kernels' int element index (and the e + total of the
+// classifier-free combine)
+static int shape_check(const char* what, int rows, int horizon, int dim) {
+  ADX_REQUIRE(rows >= 1 && horizon >= 1 && dim >= 1, "%s: empty shape", what);
+  const int64_t per = (int64_t)horizon * dim;        // < 2^62
+  const int64_t max = 0x3fffffff;
+  ADX_REQUIRE(per <= max && rows * per <= max, "%s: %lld elements do not fit the kernel's 32-bit index", what,
+              (long long)((uint64_t)rows * (uint64_t)per));
+  return ADX_OK;
+}
+
+// Rows [row_offset, row_offset + rows) of `per` >= 1 elements each lie inside the noise stream; *base = their first logical element
+static int noise_rows(const char* what, int64_t row_offset, int rows, int64_t per, uint64_t* base) {
+  ADX_REQUIRE(row_offset >= 0, "%s: negative row_offset %lld", what, (long long)row_offset);
+  ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + rows) <= kNoiseElems / per,
+              "%s: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements", what, (long long)row_offset,
+              (long long)row_offset + rows, (long long)per);
+  *base = (uint64_t)row_offset * (uint64_t)per;
+  return ADX_OK;
+}
+
 static bool byte_ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
   return a < b + qn && b < a + pn;
 }
 
-// the refusals of "pinned waypoints v1" that every pinned launch shares; `out2` may be null
+// the refusals of "pinned waypoints v1" that every pinned launch shares, after shape_check; `out2` may be null
 static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const float* out, const float* out2, int batch, int horizon,
                      int dim, PinArgs* p) {
   ADX_REQUIRE(pin->known != nullptr && pin->mask != nullptr, "%s: null known or mask", what);
@@ -180,8 +213,6 @@ static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const
               batch, pin->known_rows);
   ADX_REQUIRE(!pin->known_noise || has_noise, "%s: known_noise is set and there is no noise tensor and no noise state", what);
   const int64_t per = (int64_t)horizon * dim;
-  ADX_REQUIRE((int64_t)batch * per <= (int64_t)0x3fffffff, "%s: %lld elements do not fit the kernel's 32-bit index", what,
-              (long long)batch * per);
   const size_t kn = (size_t)pin->known_rows * per * sizeof(float), on = (size_t)batch * per * sizeof(float);
   ADX_REQUIRE(!byte_ranges_overlap(out, on, pin->known, kn) && !byte_ranges_overlap(out, on, pin->mask, kn) &&
               (out2 == nullptr || (!byte_ranges_overlap(out2, on, pin->known, kn) && !byte_ranges_overlap(out2, on, pin->mask, kn))),
@@ -191,78 +222,42 @@ static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const
   return ADX_OK;
 }
 
-template <bool DDPM, bool RNG, bool PIN>
-static int step_launch(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
-                       int64_t row_offset, const float* tgt, const float* mask, const adx_pin* pin, float* prev, float* x0, int batch,
-                       int horizon, int dim, hipStream_t s) {
-  ADX_REQUIRE(c && mo && x && prev, "scheduler step: null tensor");
-  ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1, "scheduler step: empty shape");
+int step_run(const StepCall& k) {
+  using Kernel = void (*)(const StepArgs);
+  static const Kernel kernels[2][2][2] = {      // [ddpm][noise stream][pin]
+      {{step_kernel<false, false, false>, step_kernel<false, false, true>}, {step_kernel<false, true, false>, step_kernel<false, true, true>}},
+      {{step_kernel<true, false, false>, step_kernel<true, false, true>}, {step_kernel<true, true, false>, step_kernel<true, true, true>}}};
+  const char* const what = "scheduler step";
+  const adx_step_coef* c = k.c;
+  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr;
+  ADX_REQUIRE(k.z == nullptr || !rng, "scheduler step: a noise tensor and a noise state are both given");
+  ADX_REQUIRE(c && k.mo && k.x && k.prev, "scheduler step: null tensor");
+  int rc = shape_check(what, k.batch, k.horizon, k.dim);
+  if (rc != ADX_OK) return rc;
   ADX_REQUIRE(c->prediction_type >= 0 && c->prediction_type <= 2,
               "prediction_type given as %d must be one of `epsilon`, `sample`, or `v_prediction`", c->prediction_type);
   StepArgs a;
   a.ns = nullptr; a.slot = 0; a.base = 0;
   a.pin = PinArgs{nullptr, nullptr, 1, 0.f, 0.f, 0};
-  if (PIN) {
+  if (pinned) {
     ADX_REQUIRE(!c->inpaint, "scheduler step: c->inpaint (the inpainting schedulers' blend) and a pin are two blends of one step");
-    const int rc = pin_check(pin, "scheduler step", RNG || z != nullptr, prev, x0, batch, horizon, dim, &a.pin);
+    rc = pin_check(k.pin, what, rng || k.z != nullptr, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.pin);
     if (rc != ADX_OK) return rc;
   }
-  if (RNG) {
-    ADX_REQUIRE(ns != nullptr, "scheduler step: null noise state");
-    ADX_REQUIRE(row_offset >= 0, "scheduler step: negative row_offset %lld", (long long)row_offset);
-    const int64_t per = (int64_t)horizon * dim;        // < 2^62
-    ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + batch) <= kNoiseElems / per,
-                "scheduler step: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements",
-                (long long)row_offset, (long long)row_offset + batch, (long long)per);
-    a.ns = ns; a.slot = (uint32_t)slot; a.base = (uint64_t)row_offset * (uint64_t)per;
+  if (rng) {
+    rc = noise_rows(what, k.row_offset, k.batch, (int64_t)k.horizon * k.dim, &a.base);
+    if (rc != ADX_OK) return rc;
+    a.ns = k.ns; a.slot = (uint32_t)k.slot;
   } else {
-    ADX_REQUIRE(!(c->add_noise || (c->inpaint && c->known_noise && tgt && mask)) || z != nullptr,
+    ADX_REQUIRE(!(c->add_noise || (c->inpaint && c->known_noise && k.tgt && k.mask)) || k.z != nullptr,
                 "scheduler step: noise tensor required");
   }
   a.c = *c;
-  a.mo = mo; a.x = x; a.z = z; a.tgt = tgt; a.mask = mask; a.prev = prev; a.x0 = x0;
-  a.total = batch * horizon * dim; a.horizon = horizon; a.dim = dim;
-  step_kernel<DDPM, RNG, PIN><<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
+  a.mo = k.mo; a.x = k.x; a.z = k.z; a.tgt = k.tgt; a.mask = k.mask; a.prev = k.prev; a.x0 = k.x0;
+  a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
+  kernels[k.ddpm][rng][pinned]<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, k.stream>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
-}
-
-int ddim_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
-              const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<false, false, false>(c, mo, x, z, nullptr, 0, 0, tgt, mask, nullptr, prev, x0, b, h, d, s);
-}
-int ddpm_step(const adx_step_coef* c, const float* mo, const float* x, const float* z, const float* tgt,
-              const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<true, false, false>(c, mo, x, z, nullptr, 0, 0, tgt, mask, nullptr, prev, x0, b, h, d, s);
-}
-int ddim_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
-                  const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<false, true, false>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, nullptr, prev, x0, b, h, d, s);
-}
-int ddpm_step_rng(const adx_step_coef* c, const float* mo, const float* x, const uint32_t* ns, int32_t slot, int64_t row_offset,
-                  const float* tgt, const float* mask, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_launch<true, true, false>(c, mo, x, nullptr, ns, slot, row_offset, tgt, mask, nullptr, prev, x0, b, h, d, s);
-}
-
-// adx_ddim_step_pin / adx_ddpm_step_pin: a NULL pin is the unpinned export (tensor or stream, whichever noise source is given)
-template <bool DDPM>
-static int step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
-                    int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  ADX_REQUIRE(z == nullptr || ns == nullptr, "scheduler step: a noise tensor and a noise state are both given");
-  if (pin == nullptr) {
-    if (ns != nullptr) return step_launch<DDPM, true, false>(c, mo, x, nullptr, ns, slot, row_offset, nullptr, nullptr, nullptr, prev, x0, b, h, d, s);
-    return step_launch<DDPM, false, false>(c, mo, x, z, nullptr, 0, 0, nullptr, nullptr, nullptr, prev, x0, b, h, d, s);
-  }
-  if (ns != nullptr) return step_launch<DDPM, true, true>(c, mo, x, nullptr, ns, slot, row_offset, nullptr, nullptr, pin, prev, x0, b, h, d, s);
-  return step_launch<DDPM, false, true>(c, mo, x, z, nullptr, 0, 0, nullptr, nullptr, pin, prev, x0, b, h, d, s);
-}
-int ddim_step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
-                  int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_pin<false>(c, mo, x, z, ns, slot, row_offset, pin, prev, x0, b, h, d, s);
-}
-int ddpm_step_pin(const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
-                  int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int b, int h, int d, hipStream_t s) {
-  return step_pin<true>(c, mo, x, z, ns, slot, row_offset, pin, prev, x0, b, h, d, s);
 }
 
 // DPM-Solver++ multistep step (order 1 and the order-2 midpoint rule; diffusers 0.28.0 DPMSolverMultistepScheduler,
@@ -290,26 +285,9 @@ __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= a.total) return;
   const adx_dpm_coef& c = a.c;
-  float m;
-  if (c.cfg_combine) {
-    const float cnd = a.mo[e], unc = a.mo[e + a.total];
-    const float d = cnd - unc;
-    const float sd = c.free_scale * d;
-    m = unc + sd;
-  } else {
-    m = a.mo[e];
-  }
+  const float m = cfg_model_output(a.mo, e, a.total, c.cfg_combine, c.free_scale);
   const float xs = a.x[e];
-  float x0;
-  if (c.prediction_type == ADX_PRED_EPSILON) {
-    const float p = c.sigma_s * m;
-    x0 = (xs - p) / c.alpha_s;
-  } else if (c.prediction_type == ADX_PRED_SAMPLE) {
-    x0 = m;
-  } else {
-    const float p = c.alpha_s * xs, q = c.sigma_s * m;
-    x0 = p - q;
-  }
+  float x0 = x0_from(c.prediction_type, c.alpha_s, c.sigma_s, xs, m);
   if (c.clip) x0 = clamp_nan(x0, -c.clip_range, c.clip_range);
   const float p = c.r * xs, q = c.k * x0;
   float prev = p - q;
@@ -324,59 +302,43 @@ __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
     const float zn = a.pin.known_noise ? noise_normal_at(a.ns, a.slot, a.base + (uint64_t)e) : 0.f;
     prev = pin_blend(a.pin, e, zn, prev);
   }
-  if (c.zero_first) {
-    const int d = e % a.dim;
-    const int h = (e / a.dim) % a.horizon;
-    if (h == 0 && d < 3) prev = 0.f;
-  }
+  if (c.zero_first && first_pose(e, a.horizon, a.dim)) prev = 0.f;
   a.prev[e] = prev;
   a.x0[e] = x0;          // as computed (not zeroed): the next step's history
 }
 
-template <bool PIN>
-static int dpm_launch(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, const uint32_t* ns, int32_t slot,
-                      int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int batch, int horizon, int dim, hipStream_t s) {
-  ADX_REQUIRE(c && mo && x && prev && x0, "dpm step: null tensor");
-  ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1, "dpm step: empty shape");
-  ADX_REQUIRE((int64_t)batch * horizon * dim <= (int64_t)0x3fffffff, "dpm step: %lld elements do not fit the kernel's 32-bit index",
-              (long long)batch * horizon * dim);
+// a NULL pin is adx_dpm_step: the solver itself draws nothing, the noise fields are then not looked at
+int dpm_run(const DpmCall& k) {
+  const char* const what = "dpm step";
+  const adx_dpm_coef* c = k.c;
+  ADX_REQUIRE(c && k.mo && k.x && k.prev && k.x0, "dpm step: null tensor");
+  int rc = shape_check(what, k.batch, k.horizon, k.dim);
+  if (rc != ADX_OK) return rc;
   ADX_REQUIRE(c->prediction_type >= 0 && c->prediction_type <= 2,
               "prediction_type given as %d must be one of `epsilon`, `sample`, or `v_prediction`", c->prediction_type);
-  ADX_REQUIRE(!c->second_order || px0 != nullptr, "dpm step: a second-order step needs the previous step's x0");
-  ADX_REQUIRE(px0 != prev && px0 != x0 && x != prev && x != x0 && mo != prev && mo != x0 && prev != x0,
+  ADX_REQUIRE(!c->second_order || k.px0 != nullptr, "dpm step: a second-order step needs the previous step's x0");
+  ADX_REQUIRE(k.px0 != k.prev && k.px0 != k.x0 && k.x != k.prev && k.x != k.x0 && k.mo != k.prev && k.mo != k.x0 && k.prev != k.x0,
               "dpm step: outputs alias an input or each other");
   DpmArgs a;
   a.pin = PinArgs{nullptr, nullptr, 1, 0.f, 0.f, 0};
   a.ns = nullptr; a.slot = 0; a.base = 0;
-  if (PIN) {
-    const int rc = pin_check(pin, "dpm step", ns != nullptr, prev, x0, batch, horizon, dim, &a.pin);
+  if (k.pin != nullptr) {
+    rc = pin_check(k.pin, what, k.ns != nullptr, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.pin);
     if (rc != ADX_OK) return rc;
-    if (ns != nullptr) {
-      ADX_REQUIRE(row_offset >= 0, "dpm step: negative row_offset %lld", (long long)row_offset);
-      const int64_t per = (int64_t)horizon * dim;
-      ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + batch) <= kNoiseElems / per,
-                  "dpm step: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements", (long long)row_offset,
-                  (long long)row_offset + batch, (long long)per);
-      a.ns = ns; a.slot = (uint32_t)slot; a.base = (uint64_t)row_offset * (uint64_t)per;
+    if (k.ns != nullptr) {
+      rc = noise_rows(what, k.row_offset, k.batch, (int64_t)k.horizon * k.dim, &a.base);
+      if (rc != ADX_OK) return rc;
+      a.ns = k.ns; a.slot = (uint32_t)k.slot;
     }
   }
   a.c = *c;
-  a.mo = mo; a.x = x; a.px0 = px0; a.prev = prev; a.x0 = x0;
-  a.total = batch * horizon * dim; a.horizon = horizon; a.dim = dim;
-  dpm_step_kernel<PIN><<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
+  a.mo = k.mo; a.x = k.x; a.px0 = k.px0; a.prev = k.prev; a.x0 = k.x0;
+  a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
+  const dim3 grid(ceil_div(a.total, 256));
+  if (k.pin != nullptr) dpm_step_kernel<true><<<grid, dim3(256), 0, k.stream>>>(a);
+  else dpm_step_kernel<false><<<grid, dim3(256), 0, k.stream>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
-}
-
-int dpm_step(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, float* prev, float* x0, int batch,
-             int horizon, int dim, hipStream_t s) {
-  return dpm_launch<false>(c, mo, x, px0, nullptr, 0, 0, nullptr, prev, x0, batch, horizon, dim, s);
-}
-// a NULL pin is adx_dpm_step: the solver itself draws nothing, the noise arguments are then not looked at
-int dpm_step_pin(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, const uint32_t* ns, int32_t slot,
-                 int64_t row_offset, const adx_pin* pin, float* prev, float* x0, int batch, int horizon, int dim, hipStream_t s) {
-  if (pin == nullptr) return dpm_launch<false>(c, mo, x, px0, nullptr, 0, 0, nullptr, prev, x0, batch, horizon, dim, s);
-  return dpm_launch<true>(c, mo, x, px0, ns, slot, row_offset, pin, prev, x0, batch, horizon, dim, s);
 }
 
 // The blend by itself, in place on a sample [batch][H][D]: the entry of a `clean` tick, where the reference writes
@@ -398,19 +360,18 @@ __global__ void __launch_bounds__(256) pin_apply_kernel(const PinApplyArgs a) {
 }
 
 int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int batch, int horizon, int dim, hipStream_t s) {
+  const char* const what = "pin apply";
   ADX_REQUIRE(x != nullptr && pin != nullptr, "pin apply: null sample or pin");
-  ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1, "pin apply: empty shape");
+  int rc = shape_check(what, batch, horizon, dim);
+  if (rc != ADX_OK) return rc;
   PinApplyArgs a;
-  const int rc = pin_check(pin, "pin apply", ns != nullptr, x, nullptr, batch, horizon, dim, &a.pin);
+  rc = pin_check(pin, what, ns != nullptr, x, nullptr, batch, horizon, dim, &a.pin);
   if (rc != ADX_OK) return rc;
   a.ns = nullptr; a.base = 0;
   if (ns != nullptr) {
-    ADX_REQUIRE(row_offset >= 0, "pin apply: negative row_offset %lld", (long long)row_offset);
-    const int64_t per = (int64_t)horizon * dim;
-    ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + batch) <= kNoiseElems / per,
-                "pin apply: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements", (long long)row_offset,
-                (long long)row_offset + batch, (long long)per);
-    a.ns = ns; a.base = (uint64_t)row_offset * (uint64_t)per;
+    rc = noise_rows(what, row_offset, batch, (int64_t)horizon * dim, &a.base);
+    if (rc != ADX_OK) return rc;
+    a.ns = ns;
   }
   a.x = x; a.total = batch * horizon * dim;
   pin_apply_kernel<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, s>>>(a);
@@ -519,7 +480,7 @@ __global__ void __launch_bounds__(256) warm_init_kernel(const WarmArgs a) {
   const float z = noise_normal_at(a.ns, 0xFFFFFFFFu, a.base + (uint64_t)e);
   const float m0 = a.sqrt_ab * w, m1 = a.sqrt_1mab * z;
   float v = m0 + m1;
-  if (a.zero_first && h == 0 && d < 3) v = 0.f;
+  if (a.zero_first && first_pose(e, H, D)) v = 0.f;
   a.out[e] = v;
 }
 
@@ -531,18 +492,15 @@ int warm_init(const float* prev, int prev_rows, const float* motion, float* out,
   ADX_REQUIRE(shift >= 0 && shift <= horizon - 1, "warm init: shift %d outside 0..%d (horizon - 1)", shift, horizon - 1);
   ADX_REQUIRE(prev_rows >= 1 && rows >= 1 && rows % prev_rows == 0, "warm init: rows %d must be a positive multiple of prev_rows %d",
               rows, prev_rows);
-  ADX_REQUIRE(row_offset >= 0, "warm init: negative row_offset %lld", (long long)row_offset);
   const int64_t per = (int64_t)horizon * dim;
-  ADX_REQUIRE(row_offset <= kNoiseElems && (row_offset + rows) <= kNoiseElems / per,
-              "warm init: rows [%lld, %lld) of %lld elements leave the noise stream's 2^34 elements", (long long)row_offset,
-              (long long)row_offset + rows, (long long)per);
-  ADX_REQUIRE((int64_t)rows * per <= (int64_t)0x3fffffff, "warm init: %lld elements do not fit the kernel's 32-bit index",
-              (long long)rows * per);
+  WarmArgs a;
+  int rc = noise_rows("warm init", row_offset, rows, per, &a.base);
+  if (rc != ADX_OK) return rc;
+  rc = shape_check("warm init", rows, horizon, dim);
+  if (rc != ADX_OK) return rc;
   ADX_REQUIRE(!byte_ranges_overlap(out,(size_t)rows * per * sizeof(float), prev, (size_t)prev_rows * per * sizeof(float)),
               "warm init: the output overlaps prev");
-  WarmArgs a;
   a.prev = prev; a.motion = motion; a.out = out; a.ns = ns;
-  a.base = (uint64_t)row_offset * (uint64_t)per;
   a.sqrt_ab = sqrt_ab; a.sqrt_1mab = sqrt_1mab;
   a.total = (int)(rows * per); a.prev_rows = prev_rows; a.horizon = horizon; a.dim = dim; a.shift = shift;
   a.zero_first = zero_first != 0;
@@ -562,17 +520,16 @@ __global__ void __launch_bounds__(256) add_noise_kernel(const float* __restrict_
   const int64_t tb = t[b];
   const float p = sa[tb] * x[e], q = sb[tb] * n[e];
   float v = p + q;
-  if (zero_first) {
-    const int d = e % dim, h = (e / dim) % horizon;
-    if (h == 0 && d < 3) v = 0.f;
-  }
+  if (zero_first && first_pose(e, horizon, dim)) v = 0.f;
   out[e] = v;
 }
 
 int add_noise(const float* x, const float* n, const int64_t* t, const float* sa, const float* sb, int n_train,
               float* out, int batch, int horizon, int dim, int zero_first, hipStream_t s) {
   ADX_REQUIRE(x && n && t && sa && sb && out, "add_noise: null tensor");
-  ADX_REQUIRE(batch >= 1 && horizon >= 1 && dim >= 1 && n_train >= 1, "add_noise: empty shape");
+  ADX_REQUIRE(n_train >= 1, "add_noise: empty shape");
+  const int rc = shape_check("add_noise", batch, horizon, dim);
+  if (rc != ADX_OK) return rc;
   const int total = batch * horizon * dim;
   add_noise_kernel<<<dim3(ceil_div(total, 256)), dim3(256), 0, s>>>(x, n, t, sa, sb, out, total, horizon * dim,
                                                                   horizon, dim, zero_first);

@@ -252,30 +252,48 @@ class SchedulerBase:
         c.sqrt_beta_t = float(b_t ** 0.5)
         return c
 
+    @staticmethod
+    def _noise_args(noise, x):
+        """(noise tensor pointer, noise state pointer, row_offset) of a step's noise: a tensor (or None), or a DeviceNoise --
+        then the kernel draws element by element from the noise stream and no tensor exists."""
+        if isinstance(noise, DeviceNoise):
+            if noise.device != x.device:
+                raise ValueError(f"the DeviceNoise lives on {noise.device}, the sample on {x.device}")
+            return None, noise.state_ptr(), noise.row_offset
+        return L.ptr(noise), None, 0
+
+    @staticmethod
+    def _fuse(c, cfg_scale, zero_first):
+        """The optional fusions of a guidance step, on a StepCoef or a DpmCoef: the classifier-free combine of a [2B] model
+        output and `prev[:, 0, :3] = 0`."""
+        if cfg_scale is not None:
+            c.cfg_combine, c.free_scale = 1, float(cfg_scale)
+        c.zero_first = int(zero_first)
+
+    @staticmethod
+    def _result(prev, x0, return_dict):
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
     def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True, slot: int = 0, pin=None):
-        """`noise`: the step's noise tensor (or None), or a DeviceNoise -- then the kernel draws element by element from the
-        noise stream at `slot` (the integer timestep) and no tensor exists.  `pin`: the `adx_pin` of a pinned step (the PIN
-        variant of the kernel, "pinned waypoints v1"); None is the call as it was."""
+        """`noise`: as `_noise_args` takes it; the stream is drawn at `slot` (the integer timestep).  `pin`: the `adx_pin` of a
+        pinned step (the PIN variant of the kernel, "pinned waypoints v1"); None is the call as it was."""
         B, H, D = x.shape
         prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
-        if isinstance(noise, DeviceNoise) and noise.device != x.device:
-            raise ValueError(f"the DeviceNoise lives on {noise.device}, the sample on {x.device}")
+        z, state, row_offset = self._noise_args(noise, x)
         if pin is not None:
-            stream = isinstance(noise, DeviceNoise)
             fn = L.lazy("adx_ddpm_step_pin" if ddpm else "adx_ddim_step_pin")
-            L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), None if stream else L.ptr(noise),
-                       noise.state_ptr() if stream else None, int(slot), noise.row_offset if stream else 0, C.byref(pin),
-                       prev.data_ptr(), L.ptr(x0), B, H, D, L.stream_ptr(x.device)), "scheduler step")
-            return prev, x0
-        if isinstance(noise, DeviceNoise):
+            source = (z, state, int(slot), row_offset, C.byref(pin))
+        elif state is not None:
             fn = L.lib().adx_ddpm_step_rng if ddpm else L.lib().adx_ddim_step_rng
-            L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), noise.state_ptr(), int(slot), noise.row_offset, L.ptr(target),
-                       L.ptr(mask), prev.data_ptr(), L.ptr(x0), B, H, D, L.stream_ptr(x.device)), "scheduler step")
-            return prev, x0
-        fn = L.lib().adx_ddpm_step if ddpm else L.lib().adx_ddim_step
-        L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(noise), L.ptr(target), L.ptr(mask), prev.data_ptr(),
-                   L.ptr(x0), B, H, D, L.stream_ptr(x.device)), "scheduler step")
+            source = (state, int(slot), row_offset, L.ptr(target), L.ptr(mask))
+        else:
+            fn = L.lib().adx_ddpm_step if ddpm else L.lib().adx_ddim_step
+            source = (z, L.ptr(target), L.ptr(mask))
+        L.check(fn(C.byref(c), mo.data_ptr(), x.data_ptr(), *source, prev.data_ptr(), L.ptr(x0), B, H, D, L.stream_ptr(x.device)),
+                "scheduler step")
         return prev, x0
 
     # -- pinned waypoints v1 ------------------------------------------------------------------------
@@ -365,9 +383,7 @@ class DDPMScheduler(SchedulerBase):
         c = self._ddpm_coef(t)
         z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise) if t > 0 else None
         prev, x0 = self._launch(True, c, mo, x, z, None, None, slot=t)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return self._result(prev, x0, return_dict)
 
 
 class DDIMScheduler(SchedulerBase):

@@ -25,7 +25,7 @@ import torch
 
 from .. import _lib as L
 from ..noise import DeviceNoise
-from .base import PRED, SchedulerBase, SchedulerOutput, TimestepSequence, timestep_to_int
+from .base import PRED, SchedulerBase, TimestepSequence, timestep_to_int
 from .guidance import _wants_classifier_guidance
 
 
@@ -188,9 +188,7 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
                                  f"{i - 1} on a sample of the same shape and device; the previous call was {was}")
             history = self._last[1]
         mo, x = self._check_step_inputs(model_output, sample, cfg_scale is not None)
-        if cfg_scale is not None:
-            c.cfg_combine, c.free_scale = 1, float(cfg_scale)
-        c.zero_first = int(zero_first)
+        self._fuse(c, cfg_scale, zero_first)
         B, H, D = x.shape
         p, _ = self._pin_desc(pin, timestep, x)
         prev, x0 = torch.empty_like(x), torch.empty_like(x)
@@ -198,14 +196,10 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
             L.check(L.lib().adx_dpm_step(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history), prev.data_ptr(), x0.data_ptr(),
                                          B, H, D, L.stream_ptr(x.device)), "scheduler step")
         else:
-            if stream and generator.device != x.device:
-                raise ValueError(f"the DeviceNoise lives on {generator.device}, the sample on {x.device}")
-            L.check(L.lazy("adx_dpm_step_pin")(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history),
-                                               generator.state_ptr() if stream else None, timestep_to_int(timestep),
-                                               generator.row_offset if stream else 0, C.byref(p), prev.data_ptr(), x0.data_ptr(),
+            _, state, row_offset = self._noise_args(generator if stream else None, x)      # the stream or nothing
+            L.check(L.lazy("adx_dpm_step_pin")(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history), state,
+                                               timestep_to_int(timestep), row_offset, C.byref(p), prev.data_ptr(), x0.data_ptr(),
                                                B, H, D, L.stream_ptr(x.device)), "scheduler step")
         self._last = (i, x0)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return self._result(prev, x0, return_dict)
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 
 from ..misc.constant import GuidanceType
-from .base import DDIMScheduler, DDPMScheduler, SchedulerOutput, timestep_to_int
+from .base import DDIMScheduler, DDPMScheduler, timestep_to_int
 
 
 def _wants_classifier_guidance(cfg) -> bool:
@@ -51,9 +51,7 @@ class GuidanceDDIMScheduler(DDIMScheduler):
                 model_std = torch.exp(0.5 * self._get_variance(t, prev_t))
                 model_output = self.guidance_loss(model_output, action, target, model_std)
         mo, x = self._check_step_inputs(model_output, sample, cfg_scale is not None)
-        if cfg_scale is not None:
-            c.cfg_combine, c.free_scale = 1, float(cfg_scale)
-        c.zero_first = int(zero_first)
+        self._fuse(c, cfg_scale, zero_first)
         z = None
         if eta > 0:
             if variance_noise is not None and generator is not None:
@@ -64,9 +62,7 @@ class GuidanceDDIMScheduler(DDIMScheduler):
         if p_noise and z is None:
             z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)
         prev, x0 = self._launch(False, c, mo, x, z, None, None, slot=t, pin=p)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return self._result(prev, x0, return_dict)
 
 
 class GuidanceDDPMScheduler(DDPMScheduler):
@@ -93,12 +89,8 @@ class GuidanceDDPMScheduler(DDPMScheduler):
                 model_std = torch.exp(0.5 * self._get_variance(t))
                 model_output = self.guidance_loss(model_output, action, target, model_std)
         mo, x = self._check_step_inputs(model_output, sample, cfg_scale is not None)
-        if cfg_scale is not None:
-            c.cfg_combine, c.free_scale = 1, float(cfg_scale)
-        c.zero_first = int(zero_first)
+        self._fuse(c, cfg_scale, zero_first)
         z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise) if t > 0 else None
         p, _ = self._pin_desc(pin, t, x)
         prev, x0 = self._launch(True, c, mo, x, z, None, None, slot=t, pin=p)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return self._result(prev, x0, return_dict)

@@ -4,7 +4,7 @@ Exported by the reference but not instantiated by any caller; kept to the same s
 the reference's quirk of adding the *scalar* DDIM variance to every element (:108-112,124-128)."""
 from __future__ import annotations
 
-from .base import DDIMScheduler, DDPMScheduler, SchedulerOutput, timestep_to_int
+from .base import DDIMScheduler, DDPMScheduler, timestep_to_int
 from .. import _lib as L
 
 
@@ -33,9 +33,7 @@ class InpaintingDDIMScheduler(DDIMScheduler):
             # given, a second independent tensor for the eta term; with variance_noise both are that tensor
             z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)
         prev, x0 = self._launch(False, c, mo, x, z, tt, tm, slot=t)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return self._result(prev, x0, return_dict)
 
 
 class InpaintingDDPMScheduler(DDPMScheduler):
@@ -48,6 +46,4 @@ class InpaintingDDPMScheduler(DDPMScheduler):
         tt, tm = _known(target_traj, target_mask, x)
         z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)  # drawn even at t == 0 (:100-109)
         prev, x0 = self._launch(True, c, mo, x, z, tt, tm, slot=t)
-        if not return_dict:
-            return (prev,)
-        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return self._result(prev, x0, return_dict)

@@ -576,7 +576,9 @@ typedef struct adx_step_coef {
 } adx_step_coef;
 
 /* S1/S3: GuidanceDDIMScheduler.step / InpaintingDDIMScheduler.step
- *        scheduler/guidance_ddim_scheduler.py:60-173, inpainting_ddim_scheduler.py:10-153 */
+ *        scheduler/guidance_ddim_scheduler.py:60-173, inpainting_ddim_scheduler.py:10-153
+ * Refused, as by every step export below: batch * horizon * dim above 0x3fffffff, more elements than the kernel's 32-bit
+ * index holds. */
 int adx_ddim_step(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                   const float* target, const float* mask, float* prev, float* x0,
                   int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
@@ -642,7 +644,8 @@ int adx_noise_words(const uint32_t* state, int32_t slot, int64_t first_elem, uin
 /* tick += 1 (64-bit) by a one-thread kernel on the stream: capturable, ordered with the draws around it */
 int adx_noise_advance(uint32_t* state, adx_stream s);
 /* adx_ddim_step / adx_ddpm_step with the noise tensor replaced by the stream: element (b, h, d) of the launch draws logical
- * element ((row_offset + b) * H + h) * D + d of `slot`, inside the step kernel, only where the step uses noise. */
+ * element ((row_offset + b) * H + h) * D + d of `slot`, inside the step kernel, only where the step uses noise.  Refused: what
+ * adx_ddim_step refuses (the 32-bit element count included), a NULL noise_state, rows that leave the stream's 2^34 elements. */
 int adx_ddim_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
                       int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
@@ -850,7 +853,8 @@ int adx_control_step(const adx_control_cfg* c, const float* traj, const float* v
 int adx_control_reset(void* state, int32_t scenes, int32_t n_turn, int32_t n_speed, const uint8_t* mask, adx_stream s);
 
 /* add_noise (train.py:234) fused with the [...,0,:3] = 0 of train.py:235 when zero_first != 0.
- * sqrt_ab / sqrt_1mab are the host tables sqrt(abar), sqrt(1-abar) of length n_train. */
+ * sqrt_ab / sqrt_1mab are the host tables sqrt(abar), sqrt(1-abar) of length n_train.  Refused: batch * horizon * dim above
+ * 0x3fffffff, more elements than the kernel's 32-bit index holds. */
 int adx_add_noise(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
                   int32_t n_train, float* out, int32_t batch, int32_t horizon, int32_t dim, int32_t zero_first,
                   adx_stream s);
