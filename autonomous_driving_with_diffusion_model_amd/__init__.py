@@ -10,6 +10,7 @@ Public surface mirrors the reference's packages:
     TrajectorySelector, Selection                     (no reference counterpart: best-of-K sampling, control/select.py)
     WarmStart                                         (no reference counterpart: receding-horizon warm starting, sampling.py)
     Pin                                               (no reference counterpart: waypoints held through a tick, pin.py)
+    Guide                                             (no reference counterpart: obstacles a tick steers around, guide.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -31,7 +32,8 @@ from .scheduler import GuidanceDPMSolverMultistepScheduler  # noqa: E402
 from .control.select import Selection, TrajectorySelector  # noqa: E402
 from .control.device import DeviceController  # noqa: E402
 from .pin import Pin  # noqa: E402
+from .guide import Guide  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
-           "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin"]
+           "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide"]

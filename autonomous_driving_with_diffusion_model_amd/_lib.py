@@ -74,6 +74,12 @@ class PinDesc(C.Structure):
     _fields_ = [("known", vp), ("mask", vp), ("known_rows", i32), ("c_known", f32), ("c_known_noise", f32), ("known_noise", i32)]
 
 
+class GuideDesc(C.Structure):
+    """adx_guide ("cost guidance v1", include/adx.h)."""
+    _fields_ = [("discs", vp), ("planes", vp), ("scene_rows", i32), ("n_discs", i32), ("n_planes", i32), ("iters", i32),
+                ("lambda_", f32), ("cap", f32)]
+
+
 class SelectCfg(C.Structure):
     _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("w_goal", f32), ("w_smooth", f32),
                 ("w_consensus", f32)]
@@ -204,6 +210,13 @@ _LAZY_SIGS = {
     "adx_ddpm_step_pin": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), vp, vp, i32, i32, i32, vp]),
     "adx_dpm_step_pin": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), vp, vp, i32, i32, i32, vp]),
     "adx_pin_apply": (i32, [vp, C.POINTER(PinDesc), vp, i64, i32, i32, i32, vp]),
+    "adx_ddim_step_guide": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc), vp, vp,
+                                  i32, i32, i32, vp]),
+    "adx_ddpm_step_guide": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc), vp, vp,
+                                  i32, i32, i32, vp]),
+    "adx_dpm_step_guide": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc), vp, vp,
+                                 i32, i32, i32, vp]),
+    "adx_guide_cost": (i32, [vp, C.POINTER(GuideDesc), vp, vp, i32, i32, i32, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)

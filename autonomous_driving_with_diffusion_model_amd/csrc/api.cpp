@@ -205,6 +205,37 @@ int adx_dpm_step_pin(const adx_dpm_coef* c, const float* model_output, const flo
   k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
   return adx::dpm_run(k);
 }
+int adx_ddim_step_guide(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  adx::StepCall k;
+  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
+  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.prev = prev; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
+}
+int adx_ddpm_step_guide(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  adx::StepCall k;
+  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
+  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.prev = prev; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
+}
+int adx_dpm_step_guide(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                       float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  adx::DpmCall k;
+  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
+  k.pin = pin; k.guide = guide; k.prev = prev_sample; k.x0 = x0;
+  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::dpm_run(k);
+}
+int adx_guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int32_t rows, int32_t horizon,
+                   int32_t dim, adx_stream s) {
+  return adx::guide_cost(traj, guide, cost, active, rows, horizon, dim, (hipStream_t)s);
+}
 int adx_pin_apply(float* x, const adx_pin* pin, const uint32_t* noise_state, int64_t row_offset, int32_t batch, int32_t horizon,
                   int32_t dim, adx_stream s) {
   return adx::pin_apply(x, pin, noise_state, row_offset, batch, horizon, dim, (hipStream_t)s);

@@ -5,7 +5,7 @@
 
 namespace adx {
 
-// One DDIM / DDPM step.  The kernel is step_kernel<ddpm, ns != null, pin != null>; z and ns may not both be given.
+// One DDIM / DDPM step.  The kernel is step_kernel<ddpm, ns != null, pin != null, guide != null>; z and ns may not both be given.
 struct StepCall {
   bool ddpm = false;                  // which schedule: false DDIM, true DDPM
   const adx_step_coef* c = nullptr;
@@ -18,13 +18,15 @@ struct StepCall {
   const float* tgt = nullptr;         // inpainting schedulers: known trajectory and
   const float* mask = nullptr;        // its mask
   const adx_pin* pin = nullptr;       // pinned waypoints v1
+  const adx_guide* guide = nullptr;   // cost guidance v1
   float* prev = nullptr;
   float* x0 = nullptr;                // optional
   int batch = 0, horizon = 0, dim = 0;
   hipStream_t stream = nullptr;
 };
 
-// One DPM-Solver++ step.  The kernel is dpm_step_kernel<pin != null>; without a pin the noise fields are not looked at.
+// One DPM-Solver++ step.  The kernel is dpm_step_kernel<pin != null, guide != null>; without a pin the noise fields are not
+// looked at.
 struct DpmCall {
   const adx_dpm_coef* c = nullptr;
   const float* mo = nullptr;
@@ -34,6 +36,7 @@ struct DpmCall {
   int32_t slot = 0;
   int64_t row_offset = 0;
   const adx_pin* pin = nullptr;
+  const adx_guide* guide = nullptr;   // cost guidance v1
   float* prev = nullptr;
   float* x0 = nullptr;                // always written
   int batch = 0, horizon = 0, dim = 0;
@@ -42,6 +45,7 @@ struct DpmCall {
 
 int step_run(const StepCall& k);
 int dpm_run(const DpmCall& k);
+int guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s);
 int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int batch, int horizon, int dim, hipStream_t s);
 int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);
 int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s);

@@ -23,10 +23,16 @@
 // with the caller's known trajectory under a mask before zero_first has the last word.  The unpinned instantiations do not read
 // the pin fields, which sit behind every field they do read: their code is what it was.
 //
+// "Cost guidance v1" (include/adx.h) is one more compile-time variant (GUIDE): after the step's own clip, an xy thread recomputes
+// its partner element's x0, walks the waypoint down the gradient of the scene's disc and half-plane cost and, where its own element
+// moved, runs the rest of the step from the moved x0.  The gradient is one __device__ helper, shared with guide_cost_kernel.  The
+// unguided instantiations do not read the guide fields, which sit behind the pin's: their code is what it was.
+//
 // Host side (sched.h): every step export fills one record, StepCall or DpmCall, and one function, step_run or dpm_run, checks it
-// and picks the kernel instantiation from what the record holds (schedule, noise state or not, pin or not).  Every refusal of a
+// and picks the kernel instantiation from what the record holds (schedule, noise state or not, pin or not, guide or not).  Every refusal of a
 // step lives in those two functions and the helpers they share with pin_apply, warm_init and add_noise: shape_check (non-empty,
-// fits the kernels' 32-bit index), noise_rows (the launch's rows inside the stream) and pin_check (what is pin-specific).
+// fits the kernels' 32-bit index), noise_rows (the launch's rows inside the stream), pin_check (what is pin-specific) and guide_check
+// (what is guide-specific; guide_cost shares it).
 // Device side: the arithmetic two kernels share is written once, in __device__ helpers that keep the reference's operation order.
 #include "sched.h"
 #include "noise.h"
@@ -55,6 +61,14 @@ __device__ __forceinline__ float repaint_blend(const float* known, const float* 
   const float u = mk * kp, v = (1.0f - mk) * prev;
   return u + v;
 }
+
+// Cost guidance v1: discs [scene_rows][M][5], planes [scene_rows][P][3]; row r of a launch reads scene r % scene_rows
+struct GuideArgs {
+  const float* discs;
+  const float* planes;
+  int scene_rows, M, P, iters;
+  float lambda, cap;
+};
 
 __device__ __forceinline__ float pin_blend(const PinArgs& p, int e, float z, float prev) {
   return repaint_blend(p.known, p.mask, e % p.span, p.c_known, p.c_known_noise, p.known_noise, z, prev);
@@ -107,6 +121,8 @@ struct StepArgs {
   uint64_t base;
   // pinned waypoints v1 (PIN kernels only)
   PinArgs pin;
+  // cost guidance v1 (GUIDE kernels only)
+  GuideArgs guide;
 };
 
 __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
@@ -114,7 +130,90 @@ __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
   return v < lo ? lo : (v > hi ? hi : v);
 }
 
-template <bool DDPM, bool RNG, bool PIN>
+// Cost guidance v1: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs and P planes, its
+// gradient and the number of active terms; the contract's operations in the contract's order, each rounded on its own
+__device__ __forceinline__ void guide_grad(const float* discs, int M, const float* planes, int P, float hf, float x, float y,
+                                           float& J, float& gx, float& gy, int& active) {
+#pragma clang fp contract(off)
+  J = 0.f; gx = 0.f; gy = 0.f; active = 0;
+  for (int i = 0; i < M; ++i) {
+    const float* q = discs + i * 5;
+    const float r = q[4];
+    if (!(r > 0.f)) continue;                  // an empty slot (a NaN radius too)
+    const float hx = hf * q[2], hy = hf * q[3];
+    const float ox = q[0] + hx, oy = q[1] + hy;
+    const float dx = x - ox, dy = y - oy;
+    const float xx = dx * dx, yy = dy * dy;
+    const float d2 = xx + yy;
+    const float rr = r * r;
+    const float inv = 1.0f / rr;
+    const float sd = d2 * inv;
+    const float phi = 1.0f - sd;
+    if (phi > 0.f) {
+      const float pp = phi * phi;
+      J = J + pp / 2.0f;
+      const float k2 = 2.0f * phi;
+      const float k = k2 * inv;
+      const float kx = k * dx, ky = k * dy;
+      gx = gx - kx;
+      gy = gy - ky;
+      ++active;
+    }
+  }
+  for (int i = 0; i < P; ++i) {
+    const float* q = planes + i * 3;
+    const float nx = q[0], ny = q[1];
+    const float ax = nx * x, ay = ny * y;
+    const float psi = (ax + ay) - q[2];
+    if (psi > 0.f) {
+      const float pp = psi * psi;
+      J = J + pp / 2.0f;
+      const float px = psi * nx, py = psi * ny;
+      gx = gx + px;
+      gy = gy + py;
+      ++active;
+    }
+  }
+}
+
+// The guide of one step at element e, whose clipped pred_original_sample is x0.  An xy element (d < 2; the host checked dim >= 2)
+// recomputes its partner's x0 through the step's own helpers, repeats the waypoint's iterations and, if its own component moved,
+// leaves the guided value in x0 and returns true.  (pt, sa, sb): the operands of x0_from at this step.
+__device__ __forceinline__ bool guide_x0(const GuideArgs& g, const float* mo, const float* x, int e, int total, int horizon, int dim,
+                                         int pt, float sa, float sb, int clip, float clip_range, int cfg_combine, float free_scale,
+                                         float& x0) {
+#pragma clang fp contract(off)
+  const int d = e % dim;
+  if (d >= 2) return false;
+  const int w = e / dim;
+  const int h = w % horizon, scene = (w / horizon) % g.scene_rows;
+  const int ep = d == 0 ? e + 1 : e - 1;                 // the waypoint's other xy element
+  float xp = x0_from(pt, sa, sb, x[ep], cfg_model_output(mo, ep, total, cfg_combine, free_scale));
+  if (clip) xp = clamp_nan(xp, -clip_range, clip_range);
+  float px = d == 0 ? x0 : xp, py = d == 0 ? xp : x0;
+  const float* discs = g.discs + (size_t)scene * g.M * 5;
+  const float* planes = g.planes + (size_t)scene * g.P * 3;
+  const float hf = (float)h;
+  bool moved = false;
+  for (int it = 0; it < g.iters; ++it) {
+    float J, gx, gy;
+    int active;
+    guide_grad(discs, g.M, planes, g.P, hf, px, py, J, gx, gy, active);
+    const float lx = g.lambda * gx, ly = g.lambda * gy;
+    const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
+    moved = moved || (d == 0 ? sx : sy) != 0.f;
+    px = px - sx;
+    py = py - sy;
+    if (clip) {
+      px = clamp_nan(px, -clip_range, clip_range);
+      py = clamp_nan(py, -clip_range, clip_range);
+    }
+  }
+  if (moved) x0 = d == 0 ? px : py;
+  return moved;
+}
+
+template <bool DDPM, bool RNG, bool PIN, bool GUIDE>
 __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -135,6 +234,10 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
     eps = p2 + q2;
   }
   if (c.clip) x0 = clamp_nan(x0, -c.clip_range, c.clip_range);
+  bool moved = false;
+  if (GUIDE)
+    moved = guide_x0(a.guide, a.mo, a.x, e, a.total, a.horizon, a.dim, c.prediction_type, sa, sb, c.clip, c.clip_range, c.cfg_combine,
+                     c.free_scale, x0);
   const bool known = c.inpaint && a.tgt != nullptr && a.mask != nullptr;
   float zn;
   if (RNG) {
@@ -146,7 +249,7 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
   }
   float prev;
   if (!DDPM) {
-    if (c.use_clipped_model_output) {
+    if (c.use_clipped_model_output || (GUIDE && moved)) {      // a moved x0 re-derives its eps
       const float p = sa * x0;
       eps = (xs - p) / sb;
     }
@@ -173,7 +276,7 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
   if (PIN) prev = pin_blend(a.pin, e, zn, prev);      // the step's own z: no second draw
   if (c.zero_first && first_pose(e, a.horizon, a.dim)) prev = 0.f;
   a.prev[e] = prev;
-  if (a.x0 != nullptr) a.x0[e] = x0;          // as computed: never pinned
+  if (a.x0 != nullptr) a.x0[e] = x0;          // as computed (guided where it moved): never pinned
 }
 
 // e >> 2 is the stream's 32-bit counter word: logical elements live in [0, 2^34)
@@ -222,14 +325,47 @@ static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const
   return ADX_OK;
 }
 
+// the refusals of "cost guidance v1" that every guided launch and guide_cost share; `step`: a step, which also reads iters, cap
+// and lambda; `out2` may be null
+static int guide_check(const adx_guide* g, const char* what, bool step, bool inpaint, const void* out, size_t on, const void* out2,
+                       size_t on2, int batch, int dim, GuideArgs* a) {
+  ADX_REQUIRE(dim >= 2, "%s: cost guidance moves (x, y), dim is %d", what, dim);
+  ADX_REQUIRE(g->n_discs >= 0 && g->n_discs <= ADX_GUIDE_MAX_DISCS, "%s: n_discs %d outside 0..%d", what, g->n_discs,
+              ADX_GUIDE_MAX_DISCS);
+  ADX_REQUIRE(g->n_planes >= 0 && g->n_planes <= ADX_GUIDE_MAX_PLANES, "%s: n_planes %d outside 0..%d", what, g->n_planes,
+              ADX_GUIDE_MAX_PLANES);
+  ADX_REQUIRE(g->discs != nullptr || g->n_discs == 0, "%s: null discs with n_discs %d", what, g->n_discs);
+  ADX_REQUIRE(g->planes != nullptr || g->n_planes == 0, "%s: null planes with n_planes %d", what, g->n_planes);
+  ADX_REQUIRE(g->scene_rows >= 1 && batch % g->scene_rows == 0, "%s: batch %d must be a positive multiple of scene_rows %d", what,
+              batch, g->scene_rows);
+  if (step) {
+    ADX_REQUIRE(g->iters >= 1 && g->iters <= ADX_GUIDE_MAX_ITERS, "%s: guide iters %d outside 1..%d", what, g->iters,
+                ADX_GUIDE_MAX_ITERS);
+    ADX_REQUIRE(g->cap >= 0.f, "%s: guide cap %g is negative or NaN", what, (double)g->cap);
+    ADX_REQUIRE(g->lambda == g->lambda, "%s: guide lambda is NaN", what);
+    ADX_REQUIRE(!inpaint, "%s: c->inpaint (the inpainting schedulers' blend) and a guide do not compose", what);
+  }
+  const size_t dn = (size_t)g->scene_rows * g->n_discs * 5 * sizeof(float), pn = (size_t)g->scene_rows * g->n_planes * 3 * sizeof(float);
+  ADX_REQUIRE(!byte_ranges_overlap(out, on, g->discs, dn) && !byte_ranges_overlap(out, on, g->planes, pn) &&
+              (out2 == nullptr || (!byte_ranges_overlap(out2, on2, g->discs, dn) && !byte_ranges_overlap(out2, on2, g->planes, pn))),
+              "%s: an output overlaps discs or planes", what);
+  a->discs = g->discs; a->planes = g->planes; a->scene_rows = g->scene_rows; a->M = g->n_discs; a->P = g->n_planes;
+  a->iters = g->iters; a->lambda = g->lambda; a->cap = g->cap;
+  return ADX_OK;
+}
+
+static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f};
+
 int step_run(const StepCall& k) {
   using Kernel = void (*)(const StepArgs);
-  static const Kernel kernels[2][2][2] = {      // [ddpm][noise stream][pin]
-      {{step_kernel<false, false, false>, step_kernel<false, false, true>}, {step_kernel<false, true, false>, step_kernel<false, true, true>}},
-      {{step_kernel<true, false, false>, step_kernel<true, false, true>}, {step_kernel<true, true, false>, step_kernel<true, true, true>}}};
+#define ADX_STEP_KERNELS(ddpm, rng) {{step_kernel<ddpm, rng, false, false>, step_kernel<ddpm, rng, false, true>}, \
+                                     {step_kernel<ddpm, rng, true, false>, step_kernel<ddpm, rng, true, true>}}
+  static const Kernel kernels[2][2][2][2] = {      // [ddpm][noise stream][pin][guide]
+      {ADX_STEP_KERNELS(false, false), ADX_STEP_KERNELS(false, true)}, {ADX_STEP_KERNELS(true, false), ADX_STEP_KERNELS(true, true)}};
+#undef ADX_STEP_KERNELS
   const char* const what = "scheduler step";
   const adx_step_coef* c = k.c;
-  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr;
+  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr, guided = k.guide != nullptr;
   ADX_REQUIRE(k.z == nullptr || !rng, "scheduler step: a noise tensor and a noise state are both given");
   ADX_REQUIRE(c && k.mo && k.x && k.prev, "scheduler step: null tensor");
   int rc = shape_check(what, k.batch, k.horizon, k.dim);
@@ -244,6 +380,12 @@ int step_run(const StepCall& k) {
     rc = pin_check(k.pin, what, rng || k.z != nullptr, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.pin);
     if (rc != ADX_OK) return rc;
   }
+  a.guide = kNoGuide;
+  if (guided) {
+    const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
+    rc = guide_check(k.guide, what, true, c->inpaint != 0, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
+    if (rc != ADX_OK) return rc;
+  }
   if (rng) {
     rc = noise_rows(what, k.row_offset, k.batch, (int64_t)k.horizon * k.dim, &a.base);
     if (rc != ADX_OK) return rc;
@@ -255,7 +397,7 @@ int step_run(const StepCall& k) {
   a.c = *c;
   a.mo = k.mo; a.x = k.x; a.z = k.z; a.tgt = k.tgt; a.mask = k.mask; a.prev = k.prev; a.x0 = k.x0;
   a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
-  kernels[k.ddpm][rng][pinned]<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, k.stream>>>(a);
+  kernels[k.ddpm][rng][pinned][guided]<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, k.stream>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
@@ -277,9 +419,11 @@ struct DpmArgs {
   const uint32_t* ns;
   uint32_t slot;
   uint64_t base;
+  // cost guidance v1 (the GUIDE kernels only)
+  GuideArgs guide;
 };
 
-template <bool PIN>
+template <bool PIN, bool GUIDE>
 __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -289,6 +433,9 @@ __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
   const float xs = a.x[e];
   float x0 = x0_from(c.prediction_type, c.alpha_s, c.sigma_s, xs, m);
   if (c.clip) x0 = clamp_nan(x0, -c.clip_range, c.clip_range);
+  if (GUIDE)      // a moved x0 is the solver's x0 from here on, the history it writes included
+    guide_x0(a.guide, a.mo, a.x, e, a.total, a.horizon, a.dim, c.prediction_type, c.alpha_s, c.sigma_s, c.clip, c.clip_range,
+             c.cfg_combine, c.free_scale, x0);
   const float p = c.r * xs, q = c.k * x0;
   float prev = p - q;
   if (c.second_order && a.px0 != nullptr) {
@@ -304,11 +451,14 @@ __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
   }
   if (c.zero_first && first_pose(e, a.horizon, a.dim)) prev = 0.f;
   a.prev[e] = prev;
-  a.x0[e] = x0;          // as computed (not zeroed): the next step's history
+  a.x0[e] = x0;          // as computed (not zeroed; guided where it moved): the next step's history
 }
 
 // a NULL pin is adx_dpm_step: the solver itself draws nothing, the noise fields are then not looked at
 int dpm_run(const DpmCall& k) {
+  using Kernel = void (*)(const DpmArgs);
+  static const Kernel kernels[2][2] = {{dpm_step_kernel<false, false>, dpm_step_kernel<false, true>},      // [pin][guide]
+                                       {dpm_step_kernel<true, false>, dpm_step_kernel<true, true>}};
   const char* const what = "dpm step";
   const adx_dpm_coef* c = k.c;
   ADX_REQUIRE(c && k.mo && k.x && k.prev && k.x0, "dpm step: null tensor");
@@ -331,12 +481,71 @@ int dpm_run(const DpmCall& k) {
       a.ns = k.ns; a.slot = (uint32_t)k.slot;
     }
   }
+  a.guide = kNoGuide;
+  if (k.guide != nullptr) {
+    const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
+    rc = guide_check(k.guide, what, true, false, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
+    if (rc != ADX_OK) return rc;
+  }
   a.c = *c;
   a.mo = k.mo; a.x = k.x; a.px0 = k.px0; a.prev = k.prev; a.x0 = k.x0;
   a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
-  const dim3 grid(ceil_div(a.total, 256));
-  if (k.pin != nullptr) dpm_step_kernel<true><<<grid, dim3(256), 0, k.stream>>>(a);
-  else dpm_step_kernel<false><<<grid, dim3(256), 0, k.stream>>>(a);
+  kernels[k.pin != nullptr][k.guide != nullptr]<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, k.stream>>>(a);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
+}
+
+// What a plan still violates (adx_guide_cost): per row the cost of "cost guidance v1" summed over its waypoints and the number of
+// active (waypoint, constraint) pairs.  Shaped like the control kernel: one wave per row, four rows per workgroup, lane = waypoint;
+// the waves share nothing (no LDS, no atomics), the two sums are the fixed xor butterfly, lane 0 stores.
+constexpr int kCostWaves = 4;
+
+struct GuideCostArgs {
+  const float* traj;
+  GuideArgs g;
+  float* cost;
+  int32_t* active;
+  int rows, horizon, dim;
+};
+
+__global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const GuideCostArgs a) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & (kWave - 1);
+  const int r = blockIdx.x * kCostWaves + (threadIdx.x >> 6);
+  if (r >= a.rows) return;                       // whole waves leave: the shuffles below always see all 64 lanes
+  float J = 0.f;
+  int active = 0;
+  if (lane < a.horizon) {
+    const float* p = a.traj + ((size_t)r * a.horizon + lane) * a.dim;
+    const int scene = r % a.g.scene_rows;
+    float gx, gy;
+    guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, (float)lane, p[0], p[1],
+               J, gx, gy, active);
+  }
+  J = wave_sum(J);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) active += __shfl_xor(active, off, kWave);
+  if (lane == 0) {
+    a.cost[r] = J;
+    a.active[r] = active;
+  }
+}
+
+int guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s) {
+  const char* const what = "guide cost";
+  ADX_REQUIRE(traj != nullptr && guide != nullptr && cost != nullptr && active != nullptr, "guide cost: null traj, guide, cost or active");
+  ADX_REQUIRE(horizon >= 1 && horizon <= kWave, "guide cost: horizon %d outside 1..%d", horizon, kWave);
+  int rc = shape_check(what, rows, horizon, dim);
+  if (rc != ADX_OK) return rc;
+  GuideCostArgs a;
+  const size_t cn = (size_t)rows * sizeof(float);
+  rc = guide_check(guide, what, false, false, cost, cn, active, cn, rows, dim, &a.g);
+  if (rc != ADX_OK) return rc;
+  const size_t tn = (size_t)rows * horizon * dim * sizeof(float);
+  ADX_REQUIRE(!byte_ranges_overlap(cost, cn, traj, tn) && !byte_ranges_overlap(active, cn, traj, tn) &&
+              !byte_ranges_overlap(cost, cn, active, cn), "guide cost: an output overlaps traj or the other output");
+  a.traj = traj; a.cost = cost; a.active = active; a.rows = rows; a.horizon = horizon; a.dim = dim;
+  guide_cost_kernel<<<dim3(ceil_div(rows, kCostWaves)), dim3(kCostWaves * kWave), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }

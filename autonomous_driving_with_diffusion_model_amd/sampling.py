@@ -22,6 +22,8 @@ A sixth closes the tick: `controller=DeviceController(...)` turns the result int
 A seventh makes the loop's one hard-coded constraint general: `pin=Pin(known, mask)` holds waypoints the caller has already
 decided through the tick, inside the step kernels ("pinned waypoints v1" of include/adx.h, pin.py), where the callers can only
 say `trajs[:, 0, :3] = 0`.
+An eighth says where NOT to go: `guide=Guide(discs, planes, ...)` bends every step's predicted clean trajectory away from the
+caller's obstacles, inside the step kernels ("cost guidance v1" of include/adx.h, guide.py).
 """
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ from .control.device import DeviceController
 from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
 from .noise import DeviceNoise
+from .guide import Guide
 from .pin import Pin, pin_apply
 
 
@@ -172,16 +175,22 @@ class TickPlan:
     # derived.  `clean` mode also blends the start rows once at loop entry (`adx_pin_apply` -- on the cold draw, init_trajs or a warm
     # start's output -- between two writes of `[:, 0, :3] = 0`); `repaint` mode has no entry blend, its first step is the entry
     entry_blend: bool
+    # ---- guide ----
+    # discs and planes: buffers; presence, M, P, scale, schedule, cap and iters: baked (lambda, which scale and schedule give per
+    # timestep, is a by-value argument of every step node).  Every `scheduler.step` of the loop gets it (fused or not, all three
+    # guidance branches) and moves its x0 inside its kernel; the K * S rows read the [S, ..] obstacles directly (row r reads scene
+    # r % S), nothing is tiled
+    guide: Optional[Guide]
 
     def key(self) -> tuple:
         """Everything baked, as a hashable: two plans with equal keys capture the same graph over the same shapes."""
-        sel, ctl, pin = self.selector, self.controller, self.pin
+        sel, ctl, pin, guide = self.selector, self.controller, self.pin, self.guide
         return (self.S, self.K, None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus), self.rows, self.H, self.D,
                 self.n, self.use, self.free_scale, self.fuse, self.hoisted, self.is_ddpm,
                 "init" if self.start == "randn" else self.start,
                 self.m_warm, self.shift, self.is_warm, self.motion is None,
                 None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), self.velocity is None),
-                None if pin is None else (pin.mode, tuple(pin.known.shape)))
+                None if pin is None else (pin.mode, tuple(pin.known.shape)), None if guide is None else guide.key())
 
 
 def _hoists(model) -> bool:
@@ -216,17 +225,36 @@ def _pin_plan(cfg, pin: Optional[Pin], image, scheduler, noise, step_noise=None,
     return pin
 
 
+def _guide_plan(cfg, guide: Optional[Guide], image, scheduler) -> Optional[Guide]:
+    """The guide section of `plan_tick`: the guide (None without one), or a refusal."""
+    if guide is None:
+        return None
+    if not isinstance(guide, Guide):
+        raise TypeError(f"generate_traj: `guide` must be a Guide, got {type(guide).__name__}")
+    S = int(image.shape[0])
+    for name, t in (("discs", guide.discs), ("planes", guide.planes)):
+        if t is not None and (int(t.shape[0]) != S or t.device != image.device):
+            raise ValueError(f"guide.{name} must hold {S} scenes (image.shape[0]) on {image.device}, got {tuple(t.shape)} on {t.device}")
+    if int(cfg.MODEL.TRANSITION_DIM) < 2:
+        raise ValueError(f"generate_traj: a guide moves (x, y) and needs MODEL.TRANSITION_DIM >= 2, got {int(cfg.MODEL.TRANSITION_DIM)}")
+    if not getattr(scheduler, "supports_guide", False):
+        raise ValueError(f"{type(scheduler).__name__}.step takes no guide: use GuidanceDDIMScheduler, GuidanceDDPMScheduler or "
+                         "GuidanceDPMSolverMultistepScheduler")
+    return guide
+
+
 def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
               init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, set_timesteps: bool = True,
               noise: Optional[DeviceNoise] = None, step_noise=None, candidates: int = 1,
               selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
               motion: Optional[torch.Tensor] = None, controller: Optional[DeviceController] = None,
-              velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, graphed: bool = False) -> TickPlan:
+              velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, guide: Optional[Guide] = None,
+              graphed: bool = False) -> TickPlan:
     """The TickPlan of a `generate_traj` call with these arguments (`graphed`: of a GraphedSampler call).  Pure: no launch, no device
     allocation (but one: a strided `motion` is packed, as it always was), no tick of the noise stream, nothing written to the
     scheduler, `warm` or the controller -- so every refusal comes before any of those and before a capture opens, in the order
-    candidates, `noise` / `step_noise`, warm, control, pin.  `scheduler` is read for a warm tick on the caller's own timesteps
-    (`set_timesteps=False`) and for a pin; `is_ddpm` asks it with defaults."""
+    candidates, `noise` / `step_noise`, warm, control, pin, guide.  `scheduler` is read for a warm tick on the caller's own timesteps
+    (`set_timesteps=False`), for a pin and for a guide; `is_ddpm` asks it with defaults."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     S, device = int(image.shape[0]), image.device
     hoisted = bool(fuse) and _hoists(model)
@@ -299,6 +327,7 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
             what = (tuple(velocity.shape), velocity.dtype, velocity.device) if torch.is_tensor(velocity) else type(velocity).__name__
             raise ValueError(f"velocity must be a float32 tensor [{S}] on {device}, got {what}")
     pin = _pin_plan(cfg, pin, image, scheduler, noise, step_noise, graphed)
+    guide = _guide_plan(cfg, guide, image, scheduler)
     rows = K * S if init_trajs is None else int(init_trajs.shape[0])
     free = use == GuidanceType.FREE_GUIDANCE
     return TickPlan(S=S, K=K, selector=selector if K > 1 else None, rows=rows, H=H, D=D, n=n, use=use,
@@ -307,7 +336,8 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
                     is_ddpm=not getattr(scheduler, "_is_ddim", False) and not getattr(scheduler, "deterministic", False),
                     start="warm" if is_warm else "init" if init_trajs is not None else "randn" if noise is None else "stream",
                     m_warm=m_warm, shift=shift, is_warm=is_warm, motion=motion, i0=n - m_warm if is_warm else 0,
-                    controller=controller, velocity=velocity, pin=pin, entry_blend=pin is not None and pin.mode == "clean")
+                    controller=controller, velocity=velocity, pin=pin, entry_blend=pin is not None and pin.mode == "clean",
+                    guide=guide)
 
 
 def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
@@ -317,17 +347,17 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
                   selector: Optional[TrajectorySelector] = None, return_selection: bool = False,
                   warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
                   controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None,
-                  pin: Optional[Pin] = None):
+                  pin: Optional[Pin] = None, guide: Optional[Guide] = None):
     """One sampling tick: `plan_tick` decides (what each argument means is written on the TickPlan field it becomes), this
     function runs the plan.  With S = image.shape[0] scenes:
 
     `target` [2] or [S, 2]; `init_trajs` [K * S, H, D] or None (a draw); `noise`: a DeviceNoise, of which the call is one tick
     (`begin_tick()` first); `step_noise`: injected DDPM noise tensors instead; `candidates` = K and `selector`: best-of-K;
-    `warm` and `motion`: warm start; `controller` and `velocity`: the device controller; `pin`: pinned waypoints; `fuse`,
+    `warm` and `motion`: warm start; `controller` and `velocity`: the device controller; `pin`: pinned waypoints; `guide`: cost guidance; `fuse`,
     `set_timesteps`, `scale_xy`: as the module docstring says.
 
     The order at the end of a tick is fixed: clamp, selection (K > 1), the copy into `warm.prev`, the control launch, xy scaling
-    -- so the warm state and the controller see the clamped, unscaled, pinned result.
+    -- so the warm state and the controller see the clamped, unscaled, pinned, guided result.
 
     Returns `traj` [S, H, D] (the winners at K > 1); `(traj, selection)` with `return_selection=True` (a Selection whose
     `candidates` is the [K, S, H, D] tensor scaled like `traj`; None at K = 1, where no selector runs); with a controller
@@ -335,7 +365,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     bit what the call without a controller returns."""
     plan = plan_tick(model, scheduler, cfg, image, target, init_trajs, fuse=fuse, set_timesteps=set_timesteps, noise=noise,
                      step_noise=step_noise, candidates=candidates, selector=selector, warm=warm, motion=motion,
-                     controller=controller, velocity=velocity, pin=pin)
+                     controller=controller, velocity=velocity, pin=pin, guide=guide)
     model.eval()
     device, K, S = image.device, plan.K, plan.S
     noise, controller = plan.noise, plan.controller    # from here on the plan is the one source
@@ -417,6 +447,8 @@ def _tick_loop(model, scheduler, plan: TickPlan, image, trajs, tgt, cond, tc):
     extra = {} if plan.noise is None else {"generator": plan.noise}
     if plan.pin is not None:
         extra["pin"] = plan.pin
+    if plan.guide is not None:
+        extra["guide"] = plan.guide
     action = None
     for i, t in enumerate(scheduler.timesteps if plan.i0 == 0 else list(scheduler.timesteps)[plan.i0:]):
         tck = None if tc is None else (tc, i)
@@ -522,6 +554,9 @@ class GraphedSampler:
     `pin=Pin(...)` per call: pinned waypoints as in `generate_traj`.  `known` and `mask` travel through static buffers like
     `target`, `motion` and `velocity`; presence, mode and shape are part of the graph key, new values never capture again.  A
     `repaint` pin needs `noise=DeviceNoise(...)` at construction (a captured noise tensor would replay) and is refused without.
+    `guide=Guide(...)` per call: cost guidance as in `generate_traj`.  `discs` and `planes` travel through static buffers; presence,
+    M, P, scale, schedule, cap and iters are part of the graph key (every step node holds its lambda by value), new obstacle values
+    never capture again.
     """
 
     MAX_GRAPHS = 4
@@ -546,7 +581,7 @@ class GraphedSampler:
         self._sel = None
         self._ctl = None
 
-    def _capture(self, image, target, init_trajs, motion, velocity=None, pin=None):
+    def _capture(self, image, target, init_trajs, motion, velocity=None, pin=None, guide=None):
         dev = image.device
         warm = self.warm
         self.model.eval()
@@ -560,11 +595,13 @@ class GraphedSampler:
         g.motion = None if motion is None else motion.clone()
         g.vel = None if velocity is None else velocity.clone()
         g.pin = None if pin is None else Pin(pin.known.clone(), pin.mask.clone(), pin.mode)
+        g.guide = None if guide is None else guide.like(None if guide.discs is None else guide.discs.clone(),
+                                                        None if guide.planes is None else guide.planes.clone())
         ctl = self.controller
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
                                     candidates=self.candidates, selector=self.selector, return_selection=True,
-                                    warm=warm, motion=g.motion, controller=ctl, velocity=g.vel, pin=g.pin)
+                                    warm=warm, motion=g.motion, controller=ctl, velocity=g.vel, pin=g.pin, guide=g.guide)
         tick = None if self.noise is None else self.noise.tick()
         # the warm-up pass below is a real tick: it moves the noise stream on and overwrites the warm state.  Both are given
         # back, so that the first replay is the next tick and starts from the result of the tick before it
@@ -633,12 +670,12 @@ class GraphedSampler:
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None,
-                 velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None) -> torch.Tensor:
+                 velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, guide: Optional[Guide] = None) -> torch.Tensor:
         warm = self.warm
         plan = plan_tick(self.model, self.scheduler, self.cfg, image, target, init_trajs, noise=self.noise,
                          candidates=self.candidates, selector=self.selector, warm=warm, motion=motion,
-                         controller=self.controller, velocity=velocity, pin=pin, graphed=True)
-        motion, pin = plan.motion, plan.pin
+                         controller=self.controller, velocity=velocity, pin=pin, guide=guide, graphed=True)
+        motion, pin, guide = plan.motion, plan.pin, plan.guide
         if plan.start == "randn":
             init_trajs = torch.randn((plan.rows, plan.H, plan.D), device=image.device)
         # init_trajs None (with a DeviceNoise): the initial trajectory is drawn inside the graph, from INIT_SLOT
@@ -650,7 +687,7 @@ class GraphedSampler:
             self._graphs.pop(key, None)
             while len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.pop(next(iter(self._graphs)))        # the oldest capture
-            g = self._graphs[key] = self._capture(image, target, init_trajs, motion, velocity, pin)
+            g = self._graphs[key] = self._capture(image, target, init_trajs, motion, velocity, pin, guide)
         else:
             g.img.copy_(image)
             if init_trajs is not None:
@@ -664,6 +701,11 @@ class GraphedSampler:
             if pin is not None:
                 g.pin.known.copy_(pin.known)
                 g.pin.mask.copy_(pin.mask)
+            if guide is not None:
+                if guide.M > 0:
+                    g.guide.discs.copy_(guide.discs)
+                if guide.P > 0:
+                    g.guide.planes.copy_(guide.planes)
         self._key, self._graph, self._sel, self._ctl = key, g.graph, g.sel, g.ctl
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured

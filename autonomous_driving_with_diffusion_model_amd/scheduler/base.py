@@ -276,14 +276,18 @@ class SchedulerBase:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
 
-    def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True, slot: int = 0, pin=None):
+    def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True, slot: int = 0, pin=None, guide=None):
         """`noise`: as `_noise_args` takes it; the stream is drawn at `slot` (the integer timestep).  `pin`: the `adx_pin` of a
-        pinned step (the PIN variant of the kernel, "pinned waypoints v1"); None is the call as it was."""
+        pinned step (the PIN variant of the kernel, "pinned waypoints v1"); `guide`: the `adx_guide` of a guided step (the GUIDE
+        variant, "cost guidance v1"); None is the call as it was."""
         B, H, D = x.shape
         prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
         z, state, row_offset = self._noise_args(noise, x)
-        if pin is not None:
+        if guide is not None:
+            fn = L.lazy("adx_ddpm_step_guide" if ddpm else "adx_ddim_step_guide")
+            source = (z, state, int(slot), row_offset, None if pin is None else C.byref(pin), C.byref(guide))
+        elif pin is not None:
             fn = L.lazy("adx_ddpm_step_pin" if ddpm else "adx_ddim_step_pin")
             source = (z, state, int(slot), row_offset, C.byref(pin))
         elif state is not None:
@@ -318,6 +322,27 @@ class SchedulerBase:
             return None, False
         level = self.pin_level(timestep, pin.resolve())
         return pin.desc(x, level), bool(level[2])
+
+    # -- cost guidance v1 ---------------------------------------------------------------------------
+    supports_guide = False      # the guidance schedulers' `step` takes `guide=`
+
+    def _guide_sb(self, timestep) -> float:
+        """The step's noise level sb as the fp32 number its kernel receives: sqrt_beta_t here, sigma_s on the DPM solver."""
+        return self._base_coef(self.alphas_cumprod[timestep_to_int(timestep)]).sqrt_beta_t
+
+    def guide_level(self, timestep, guide) -> float:
+        """lambda of the guided step at `timestep`, a Python float holding the fp32 value -- the host scalar of `adx_guide`:
+        fp32(scale) under the `constant` schedule, fp32(scale) * (sb * sb) in fp32 under `variance`."""
+        scale = np.float32(guide.scale)
+        if guide.schedule == "constant":
+            return float(scale)
+        sb = np.float32(self._guide_sb(timestep))
+        with np.errstate(over="ignore", invalid="ignore"):
+            return float(scale * np.float32(sb * sb))
+
+    def _guide_desc(self, guide, timestep, x):
+        """The adx_guide of this step, or None without a guide."""
+        return None if guide is None else guide.desc(x, self.guide_level(timestep, guide))
 
     @staticmethod
     def _noise(shape, generator, device, dtype, variance_noise=None):

@@ -33,6 +33,7 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
     _is_ddim = False
     deterministic = True        # no step draws noise: a captured loop replays exactly (sampling.GraphedSampler)
     supports_pin = True
+    supports_guide = True
 
     def __init__(self, cfg=None, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
                  trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
@@ -155,6 +156,9 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
             c.inv_r0 = float(1.0 / r0)
         return c
 
+    def _guide_sb(self, timestep) -> float:
+        return self._dpm_coef(self.step_index(timestep)).sigma_s
+
     def _repaint_level(self, timestep):
         """alpha and sigma * alpha of sigmas[i + 1], as `_dpm_coef` forms alpha_t and sigma_t; no noise on the last step."""
         i = self.step_index(timestep)
@@ -163,7 +167,7 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
 
     # -- step --------------------------------------------------------------------------------------
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, target=None, action=None,
-             cfg_scale=None, zero_first: bool = False, pin=None):
+             cfg_scale=None, zero_first: bool = False, pin=None, guide=None):
         """One solver step.  `target` and `action` are accepted for the callers' common signature and unused (classifier
         guidance is refused at construction); so is `generator` without a pin: no step draws noise.  `cfg_scale` /
         `zero_first`: the fusions of GuidanceDDIMScheduler.step; `pred_original_sample` is never zeroed (it is the next step's
@@ -171,7 +175,10 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
 
         `pin`: a Pin ("pinned waypoints v1", include/adx.h), blended into prev_sample before `zero_first`;
         `pred_original_sample` is never pinned.  A `repaint` pin is the one thing that makes this step draw: it needs
-        `generator=DeviceNoise(...)` (the draw happens in the kernel, at the slot of the timestep) and raises ValueError without."""
+        `generator=DeviceNoise(...)` (the draw happens in the kernel, at the slot of the timestep) and raises ValueError without.
+
+        `guide`: a Guide ("cost guidance v1", include/adx.h): a moved x0 enters the first- and second-order terms and is the
+        `pred_original_sample` the next step reads as history."""
         i = self.step_index(timestep)
         stream = isinstance(generator, DeviceNoise)
         if pin is not None and pin.resolve() == "repaint" and not stream:
@@ -191,8 +198,14 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
         self._fuse(c, cfg_scale, zero_first)
         B, H, D = x.shape
         p, _ = self._pin_desc(pin, timestep, x)
+        g = self._guide_desc(guide, timestep, x)
         prev, x0 = torch.empty_like(x), torch.empty_like(x)
-        if p is None:
+        if g is not None:
+            _, state, row_offset = self._noise_args(generator if stream else None, x)      # the stream or nothing
+            L.check(L.lazy("adx_dpm_step_guide")(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history), state,
+                                                 timestep_to_int(timestep), row_offset, None if p is None else C.byref(p), C.byref(g),
+                                                 prev.data_ptr(), x0.data_ptr(), B, H, D, L.stream_ptr(x.device)), "scheduler step")
+        elif p is None:
             L.check(L.lib().adx_dpm_step(C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history), prev.data_ptr(), x0.data_ptr(),
                                          B, H, D, L.stream_ptr(x.device)), "scheduler step")
         else:

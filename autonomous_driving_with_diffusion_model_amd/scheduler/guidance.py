@@ -18,6 +18,7 @@ def _wants_classifier_guidance(cfg) -> bool:
 
 class GuidanceDDIMScheduler(DDIMScheduler):
     supports_pin = True
+    supports_guide = True
 
     def __init__(self, cfg, **kwargs):
         super().__init__(**kwargs)
@@ -34,7 +35,7 @@ class GuidanceDDIMScheduler(DDIMScheduler):
 
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False,
              generator=None, variance_noise=None, return_dict: bool = True, target=None, action=None,
-             cfg_scale=None, zero_first: bool = False, pin=None):
+             cfg_scale=None, zero_first: bool = False, pin=None, guide=None):
         """`cfg_scale` / `zero_first` are optional fusions (classifier-free combine of a [2B] model
         output, interact.py:142-144, and `prev[:, 0, :3] = 0`, interact.py:164); leaving them at their
         defaults gives exactly the reference signature and behaviour.
@@ -42,7 +43,11 @@ class GuidanceDDIMScheduler(DDIMScheduler):
         `pin`: a Pin ("pinned waypoints v1", include/adx.h): the finished prev_sample is blended with the pin's known values
         under its mask in the same kernel, before `zero_first`.  A `repaint` pin shares the step's own noise (eta > 0); with
         eta = 0 it draws from `generator` when that is a DeviceNoise, else a tensor as the step's noise would be drawn
-        (`variance_noise`, or torch.randn from `generator`).  None is the call as it was."""
+        (`variance_noise`, or torch.randn from `generator`).  None is the call as it was.
+
+        `guide`: a Guide ("cost guidance v1", include/adx.h, guide.py): the xy of the clipped pred_original_sample move down the
+        gradient of the guide's cost inside the same kernel, a moved element's eps is re-derived from its x0 (the
+        `use_clipped_model_output` arithmetic) and `pred_original_sample` returns the guided value.  None is the call as it was."""
         t = timestep_to_int(timestep)
         c = self._ddim_coef(t, eta, use_clipped_model_output)
         if self.use_classifier_guidance and target is not None:
@@ -61,12 +66,13 @@ class GuidanceDDIMScheduler(DDIMScheduler):
         p, p_noise = self._pin_desc(pin, t, x)
         if p_noise and z is None:
             z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise)
-        prev, x0 = self._launch(False, c, mo, x, z, None, None, slot=t, pin=p)
+        prev, x0 = self._launch(False, c, mo, x, z, None, None, slot=t, pin=p, guide=self._guide_desc(guide, t, x))
         return self._result(prev, x0, return_dict)
 
 
 class GuidanceDDPMScheduler(DDPMScheduler):
     supports_pin = True
+    supports_guide = True
 
     def __init__(self, cfg, **kwargs):
         super().__init__(**kwargs)
@@ -80,8 +86,9 @@ class GuidanceDDPMScheduler(DDPMScheduler):
         return float(torch.exp(0.5 * self._get_variance(timestep_to_int(timestep))))
 
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, target=None,
-             action=None, variance_noise=None, cfg_scale=None, zero_first: bool = False, pin=None):
-        """`pin`: as in GuidanceDDIMScheduler.step; a `repaint` pin shares the step's noise (both exist exactly when t > 0)."""
+             action=None, variance_noise=None, cfg_scale=None, zero_first: bool = False, pin=None, guide=None):
+        """`pin`: as in GuidanceDDIMScheduler.step; a `repaint` pin shares the step's noise (both exist exactly when t > 0).
+        `guide`: as in GuidanceDDIMScheduler.step; a moved x0 enters `c_x0 * x0 + c_x * x`."""
         t = timestep_to_int(timestep)
         c = self._ddpm_coef(t)
         if self.use_classifier_guidance and target is not None:
@@ -92,5 +99,5 @@ class GuidanceDDPMScheduler(DDPMScheduler):
         self._fuse(c, cfg_scale, zero_first)
         z = self._noise(x.shape, generator, x.device, x.dtype, variance_noise) if t > 0 else None
         p, _ = self._pin_desc(pin, t, x)
-        prev, x0 = self._launch(True, c, mo, x, z, None, None, slot=t, pin=p)
+        prev, x0 = self._launch(True, c, mo, x, z, None, None, slot=t, pin=p, guide=self._guide_desc(guide, t, x))
         return self._result(prev, x0, return_dict)

@@ -784,6 +784,91 @@ int adx_pin_apply(float* x, const adx_pin* pin, const uint32_t* noise_state, int
                   int32_t dim, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Cost guidance v1: where NOT to go.  Analytic cost guidance on the predicted clean trajectory (Diffuser-style test-time
+ * steering): every sampler step moves the xy of its pred_original_sample down the gradient of a cost of moving discs and
+ * half-planes, inside the step kernel, and derives the rest of the step from the moved x0 -- how the reference's classifier
+ * guidance acts for its own PRED_TYPE = "sample".  The reference names the idea (GUIDANCE.LOSS_LIST, one entry, under
+ * CLASSIFIER_GUIDANCE only); as a caller-facing object it has no counterpart.  A compile-time variant of the step kernels, no
+ * host decision: a node of a captured graph.  Callers and fixtures depend on this definition -- a change is a new version,
+ * never an edit.
+ *
+ * Everything is in the model's own units (the units of `target` and of the clamped result BEFORE xy scaling) and in this tick's
+ * ego frame.
+ *
+ *   discs    [scene_rows][M][5] = (cx, cy, vx, vy, r), 0 <= M <= 32.  At waypoint h the centre is (cx + h * vx, cy + h * vy), h
+ *            converted to float.  A slot is empty unless r > 0 (a NaN or negative radius is an empty slot).
+ *   planes   [scene_rows][P][3] = (nx, ny, b), 0 <= P <= 8: the half-plane nx * x + ny * y <= b.  The normal is not normalised by
+ *            the kernel; an all-zero normal contributes a zero gradient by itself.
+ *   rows     row r of a launch of `batch` rows reads scene r % scene_rows (candidate-major, as the pin and the conditioning
+ *            table); batch % scene_rows == 0.
+ *   cost     of one waypoint p = (x, y) at index h: fp32, no contraction, every operation rounded on its own, in this order,
+ *            from J = gx = gy = 0, discs in index order and then planes in index order:
+ *              disc:   ox = cx + h * vx;  oy = cy + h * vy;  dx = x - ox;  dy = y - oy;  d2 = dx * dx + dy * dy
+ *                      inv = 1 / (r * r);  phi = 1 - d2 * inv;  active iff phi > 0
+ *                      J = J + (phi * phi) / 2;  k = (2 * phi) * inv;  gx = gx - k * dx;  gy = gy - k * dy
+ *              plane:  psi = (nx * x + ny * y) - b;  active iff psi > 0
+ *                      J = J + (psi * psi) / 2;  gx = gx + psi * nx;  gy = gy + psi * ny
+ *            No square root and no singular point: on a disc's centre the term is active with a zero gradient.  Every comparison
+ *            with a NaN is false, so that term is inactive.
+ *   per step inside the step kernel, for columns d < 2 only (columns d >= 2 take the unguided path untouched).  From p = the
+ *            step's pred_original_sample of the waypoint's two xy elements, after the step's own clip; then for it = 0..iters-1,
+ *            1 <= iters <= 8:
+ *              g  = the gradient above at p
+ *              sh = clamp(lambda * g, -cap, +cap)      componentwise; clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v)
+ *              p  = p - sh
+ *              if c->clip: p = clamp(p, -clip_range, +clip_range)
+ *            cap may be +inf.  The cost couples nothing across waypoints, so the iterations are local to a thread; the x thread
+ *            and the y thread of a waypoint repeat the same sequence (each recomputes its partner's x0) and agree.
+ *   moved    an element moves iff its own component of sh compared unequal to 0 in some iteration (a NaN does).  A moved
+ *            element uses its component of the final p as its x0 everywhere after this point:
+ *              DDIM   c_x0 * x0 + c_dir * eps, eps re-derived as (x - sqrt_alpha_t * x0) / sqrt_beta_t: exactly the
+ *                     use_clipped_model_output arithmetic;
+ *              DDPM   c_x0 * x0 + c_x * x;
+ *              DPM    the first- and second-order terms;
+ *            and its x0 output is the guided value: the 2M solver's history.  An element that did not move runs the unguided
+ *            step, bit for bit (its x0 is the value before the iterations, whatever the sign of a zero became in them).
+ *   order    classifier-free combine (when fused; the partner element's model output is combined the same way), x0, clip, guide,
+ *            sampler update, noise, pin blend, zero_first.  Waypoint 0 is guided like any other; zero_first keeps the last word
+ *            on prev.
+ *   lambda   a host scalar by value; the kernel knows no schedule.  `constant`: lambda = fp32(scale).  `variance`: lambda =
+ *            fp32(scale) * (sb * sb) in fp32, sb = sqrt_beta_t for DDIM / DDPM and sigma_s for DPM: guidance fades as the sample
+ *            gets clean (Diffuser's Sigma-scaling).
+ *
+ * ADX_ERR_INVALID before any GPU work, each with its own text: dim < 2; M or P out of range; a NULL array with a nonzero count;
+ * scene_rows < 1 or not dividing batch; iters out of range; cap negative or NaN; lambda NaN; c->inpaint together with a guide;
+ * an output overlapping discs or planes; and whatever the unguided (pinned) step refuses.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_GUIDE_MAX_DISCS 32
+#define ADX_GUIDE_MAX_PLANES 8
+#define ADX_GUIDE_MAX_ITERS 8
+typedef struct adx_guide {
+  const float* discs;          /* [scene_rows][n_discs][5], or NULL with n_discs == 0 */
+  const float* planes;         /* [scene_rows][n_planes][3], or NULL with n_planes == 0 */
+  int32_t scene_rows, n_discs, n_planes;
+  int32_t iters;
+  float lambda, cap;
+} adx_guide;
+/* adx_ddim_step_pin / adx_ddpm_step_pin / adx_dpm_step_pin with the guidance above; pin and guide may each be NULL.  A NULL guide
+ * is exactly the _pin export. */
+int adx_ddim_step_guide(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+int adx_ddpm_step_guide(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+int adx_dpm_step_guide(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                       float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+/* What a plan still violates: cost[r] = the cost above summed over row r's waypoints, active[r] = the number of active
+ * (waypoint, constraint) pairs, of traj [rows][H][D] (2 <= D, H <= 64; row r reads scene r % scene_rows).  iters, lambda and cap
+ * are not read.  Per waypoint J is accumulated as written above; the H values are then summed by a fixed xor butterfly over a
+ * 64-lane wave (offsets 32, 16, .. 1; lanes h >= H hold 0): the same input gives the same bits, and cost is defined up to fp32
+ * rounding of that sum (tests/guide_ref.py restates it in fp64 and derives the bound).  Refused: a NULL pointer, H outside 1..64,
+ * D < 2, the guide's own shape refusals above, an output overlapping traj, discs, planes or the other output. */
+int adx_guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int32_t rows, int32_t horizon,
+                   int32_t dim, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Control v1: waypoints -> (throttle, steer, brake) on the device, the step after the sampling loop in the reference's agents
  * (control/controller.py:29-76 `control_pid`, control/pid.py, `post_process_control` of interact.py:218-229 and
  * e2e_driving/diffusion_agent.py:268-277).  One launch per tick for all scenes, no host decision; the PID windows live in

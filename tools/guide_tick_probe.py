@@ -1,0 +1,143 @@
+"""What does cost guidance cost a driving tick?  FREE guidance (scale 7.5), full-size camera frame, perception pass inside the
+tick, n = `--steps` (20) DDIM sampling steps; every arm a GraphedSampler with a DeviceNoise (one HIP graph launch per tick), at
+one scene (H = 16) and at 64 scenes (H = 32):
+
+    none         the tick as it was: no guide
+    m4p2i1       guide=Guide(discs [S, 4, 5], planes [S, 2, 3], iters=1): the GUIDE variant of every step, a light scene
+    m32p8i8      guide=Guide(discs [S, 32, 5], planes [S, 8, 3], iters=8): the contract's largest scene, 320 constraint
+                 evaluations per xy element and step
+
+The obstacles lie where a clamped trajectory meets them (centres in [-0.5, 0.5]^2, radii 0.2 .. 0.5, no empty slot), and their
+values travel through the sampler's static buffers on every tick.  The arms alternate in one process, `--rounds` times, each
+window timed with device events around >= `--ticks` ticks (at least `--seconds` of them).  Nobody has measured the guided step
+before, so there is no expectation to hold it against; the step stays one launch of a few hundred to a few tens of thousands of
+threads, two in seven of which loop over the constraints.  Prints a table and one JSON line; `--json PATH` also writes the
+record.  This measures time only: what a guide does to a trained model's driving quality is not something the repository can
+measure (it has no trained weights).
+
+    python tools/guide_tick_probe.py --json profiles/guide_tick_probe.json
+"""
+import argparse
+import contextlib
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from autonomous_driving_with_diffusion_model_amd import DeviceNoise, Guide  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd import scheduler as S  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd.config import create_cfg  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd.modeling import build_model  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd.sampling import GraphedSampler  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd.utils import procedural as P  # noqa: E402
+
+SCHED_KW = dict(num_train_timesteps=100, prediction_type="sample", beta_schedule="squaredcos_cap_v2", beta_start=1e-4, beta_end=0.02)
+IMG = (256, 900)
+SIZES = ((1, 16), (64, 32))            # (scenes, horizon)
+ARMS = (("none", None), ("m4p2i1", (4, 2, 1)), ("m32p8i8", (32, 8, 8)))      # (M, P, iters)
+
+
+def make_cfg(steps, horizon):
+    cfg = create_cfg()
+    cfg.MODEL.HORIZON = horizon
+    cfg.TRAIN.USE_COND = cfg.GUIDANCE.USE_COND = "FREE_GUIDANCE"
+    cfg.GUIDANCE.FREE_SCALE, cfg.EVAL.SAMPLE_STEPS = 7.5, steps
+    return cfg
+
+
+def obstacles(scenes, M, P, iters, dev):
+    g = torch.Generator().manual_seed(11)
+    discs = torch.zeros(scenes, M, 5)
+    discs[..., :2] = torch.rand(scenes, M, 2, generator=g) - 0.5
+    discs[..., 2:4] = (torch.rand(scenes, M, 2, generator=g) - 0.5) * 0.02
+    discs[..., 4] = 0.2 + 0.3 * torch.rand(scenes, M, generator=g)
+    planes = torch.zeros(scenes, P, 3)
+    planes[..., :2] = torch.rand(scenes, P, 2, generator=g) * 2 - 1
+    planes[..., 2] = torch.rand(scenes, P, generator=g) * 0.5
+    return Guide(discs.to(dev), planes.to(dev), scale=0.2, schedule="variance", cap=0.1, iters=iters)
+
+
+def arms(dev, n):
+    fns, meta = {}, {}
+    for scenes, horizon in SIZES:
+        cfg = make_cfg(n, horizon)
+        with contextlib.redirect_stdout(sys.stderr):
+            model = build_model(cfg)
+        P.load_procedural(model, 0)
+        model = model.to(dev).eval()
+        d = {k: v.to(dev) for k, v in P.synthetic_batch(scenes, horizon, image_hw=IMG, seed=3).items()}
+        img, tgt = d["imgs"], d["target"]
+        for arm, mpi in ARMS:
+            sch = S.GuidanceDDIMScheduler(cfg=cfg, thresholding=True, **SCHED_KW)
+            gs = GraphedSampler(model, sch, cfg, noise=DeviceNoise(7, dev))
+            guide = None if mpi is None else obstacles(scenes, *mpi, dev)
+            name = f"s{scenes}.{arm}"
+            fns[name] = (lambda gs=gs, img=img, tgt=tgt, guide=guide: gs(img, tgt, guide=guide))
+            meta[name] = (scenes, horizon, arm)
+    return fns, meta
+
+
+def timed(fn, ticks):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(ticks):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / ticks
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20, help="n = EVAL.SAMPLE_STEPS")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--ticks", type=int, default=50, help="least number of ticks per window (x rounds = ticks per arm)")
+    ap.add_argument("--seconds", type=float, default=0.5, help="least length of a window")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    n = a.steps
+    with torch.no_grad():
+        fns, meta = arms(dev, n)
+        ticks = {}
+        for fn in fns.values():                 # warm every arm: the capture, then replays ...
+            for _ in range(3):
+                fn()
+        for k, fn in fns.items():               # ... then size the windows, once no arm's capture can move the model's buffers
+            fn()                                # (a sampler re-captures by itself when a later arm's warm-up grew a workspace)
+            fn()
+            torch.cuda.synchronize()
+            ticks[k] = max(a.ticks, int(a.seconds * 1e3 / timed(fn, 5)) + 1)
+        ms = {k: [] for k in fns}
+        for _ in range(a.rounds):
+            for k, fn in fns.items():
+                ms[k].append(timed(fn, ticks[k]))
+    record = {"device": torch.cuda.get_device_name(0), "image": list(IMG), "guidance": "FREE_GUIDANCE", "sampler": "ddim",
+              "sample_steps": n, "rounds": a.rounds, "guide": "scale 0.2, variance schedule, cap 0.1", "arms": {}, "guided_over_none": {}}
+    for k in fns:
+        scenes, horizon, mode = meta[k]
+        med = statistics.median(ms[k])
+        record["arms"][k] = {"scenes": scenes, "horizon": horizon, "guide": mode, "ticks_per_window": ticks[k], "ticks": ticks[k] * a.rounds,
+                             "ms_per_tick": [round(v, 4) for v in ms[k]], "median_ms": round(med, 4), "min_ms": round(min(ms[k]), 4),
+                             "max_ms": round(max(ms[k]), 4), "spread_pct": round(100 * (max(ms[k]) - min(ms[k])) / med, 2)}
+    for k, v in record["arms"].items():
+        if v["guide"] != "none":
+            record["guided_over_none"][k] = round(v["median_ms"] / record["arms"][f"s{v['scenes']}.none"]["median_ms"], 4)
+    print(f"FREE guidance, DDIM, {IMG[0]}x{IMG[1]} frame, n = {n}, graph ticks ({a.rounds} alternating rounds)", file=sys.stderr)
+    print(f"{'arm':<14}{'scenes':>7}{'H':>4}{'median ms':>11}{'min':>9}{'max':>9}{'spread %':>10}{'/ none':>9}{'ticks':>8}", file=sys.stderr)
+    for k, v in record["arms"].items():
+        r = record["guided_over_none"].get(k)
+        print(f"{k:<14}{v['scenes']:>7}{v['horizon']:>4}{v['median_ms']:>11.3f}{v['min_ms']:>9.3f}{v['max_ms']:>9.3f}"
+              f"{v['spread_pct']:>10.2f}{('' if r is None else format(r, '.4f')):>9}{v['ticks']:>8}", file=sys.stderr)
+    print(json.dumps(record))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(record, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
