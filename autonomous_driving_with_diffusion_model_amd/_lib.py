@@ -85,6 +85,12 @@ class SelectCfg(C.Structure):
                 ("w_consensus", f32)]
 
 
+class SelectGuideCfg(C.Structure):
+    """adx_select_guide_cfg ("selection cost v2", include/adx.h)."""
+    _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("w_goal", f32), ("w_smooth", f32),
+                ("w_consensus", f32), ("w_guide", f32), ("hard", i32)]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -217,6 +223,7 @@ _LAZY_SIGS = {
     "adx_dpm_step_guide": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc), vp, vp,
                                  i32, i32, i32, vp]),
     "adx_guide_cost": (i32, [vp, C.POINTER(GuideDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_traj_select_guide": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), vp, vp, vp, vp, vp, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)

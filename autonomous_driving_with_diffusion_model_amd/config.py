@@ -54,7 +54,8 @@ def create_cfg() -> CfgNode:
                                               PRED_TYPE="sample"))
     c.GUIDANCE = CfgNode(USE_COND="NO_GUIDANCE", LOSS_LIST=None, STEP=1, CLASSIFIER_SCALE=0.1, FREE_SCALE=1.0)
     # CANDIDATES / SELECT: best-of-K sampling (no reference counterpart; sampling.generate_traj, control/select.py) --
-    # candidates per scene and the selector's (w_goal, w_smooth, w_consensus); 1 = one sample per scene, as the reference
+    # candidates per scene and the selector's (w_goal, w_smooth, w_consensus[, w_guide[, hard]]): 3, 4 or 5 values, the last two
+    # score against the tick's Guide and need one; 1 = one sample per scene, as the reference
     # WARM_STEPS / WARM_SHIFT: warm starting (no reference counterpart; sampling.WarmStart) -- the steps a warm tick runs
     # (0 = off: every tick starts from noise, as the reference) and the waypoints passed between two ticks
     # PIN_MODE: what a Pin whose mode is None does (no reference counterpart; pin.py) -- "clean" or "repaint"

@@ -67,6 +67,8 @@ int embed_forward(const adx_embed_weights* w, int dim, const int64_t* t, int t_r
                   const float* feat, int feat_rows, int rows, float* time_embed, float* mish_cond, hipStream_t s);
 int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
                 hipStream_t s);
+int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide, float* cost,
+                      int32_t* active, int32_t* index, int32_t* blocked, float* best, hipStream_t s);
 size_t control_state_bytes(int scenes, int n_turn, int n_speed);
 int control_step(const adx_control_cfg* c, const float* traj, const float* velocity, const float* target, void* state,
                  float* control, hipStream_t s);
@@ -243,6 +245,10 @@ int adx_pin_apply(float* x, const adx_pin* pin, const uint32_t* noise_state, int
 int adx_traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index,
                     float* best, adx_stream s) {
   return adx::traj_select(c, trajs, target, cost, index, best, (hipStream_t)s);
+}
+int adx_traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
+                          float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s) {
+  return adx::traj_select_guide(c, trajs, target, guide, cost, active, index, blocked, best, (hipStream_t)s);
 }
 size_t adx_control_state_bytes(int32_t scenes, int32_t n_turn, int32_t n_speed) {
   return adx::control_state_bytes(scenes, n_turn, n_speed);

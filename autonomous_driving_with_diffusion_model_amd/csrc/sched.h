@@ -2,6 +2,7 @@
 // api.cpp fill a StepCall / DpmCall and step_run / dpm_run validate it, pick the kernel instantiation and launch.
 #pragma once
 #include "adx_common.h"
+#include "guide.h"
 
 namespace adx {
 
@@ -45,6 +46,11 @@ struct DpmCall {
 
 int step_run(const StepCall& k);
 int dpm_run(const DpmCall& k);
+// The refusals of "cost guidance v1" that every guided launch shares, filling the kernels' GuideArgs: dim >= 2, the counts, the
+// arrays, scene_rows against `batch` rows, and `out` [on bytes] / `out2` [on2 bytes, may be null] against discs and planes.
+// `step`: a sampler step, which also reads iters, cap and lambda and refuses `inpaint`.  `what` prefixes every text.
+int guide_check(const adx_guide* g, const char* what, bool step, bool inpaint, const void* out, size_t on, const void* out2,
+                size_t on2, int batch, int dim, GuideArgs* a);
 int guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s);
 int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int batch, int horizon, int dim, hipStream_t s);
 int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);

@@ -25,14 +25,14 @@
 //
 // "Cost guidance v1" (include/adx.h) is one more compile-time variant (GUIDE): after the step's own clip, an xy thread recomputes
 // its partner element's x0, walks the waypoint down the gradient of the scene's disc and half-plane cost and, where its own element
-// moved, runs the rest of the step from the moved x0.  The gradient is one __device__ helper, shared with guide_cost_kernel.  The
+// moved, runs the rest of the step from the moved x0.  The gradient is one __device__ helper (guide.h), shared with guide_cost_kernel.  The
 // unguided instantiations do not read the guide fields, which sit behind the pin's: their code is what it was.
 //
 // Host side (sched.h): every step export fills one record, StepCall or DpmCall, and one function, step_run or dpm_run, checks it
 // and picks the kernel instantiation from what the record holds (schedule, noise state or not, pin or not, guide or not).  Every refusal of a
 // step lives in those two functions and the helpers they share with pin_apply, warm_init and add_noise: shape_check (non-empty,
 // fits the kernels' 32-bit index), noise_rows (the launch's rows inside the stream), pin_check (what is pin-specific) and guide_check
-// (what is guide-specific; guide_cost shares it).
+// (what is guide-specific; guide_cost and select.hip share it).
 // Device side: the arithmetic two kernels share is written once, in __device__ helpers that keep the reference's operation order.
 #include "sched.h"
 #include "noise.h"
@@ -61,14 +61,6 @@ __device__ __forceinline__ float repaint_blend(const float* known, const float* 
   const float u = mk * kp, v = (1.0f - mk) * prev;
   return u + v;
 }
-
-// Cost guidance v1: discs [scene_rows][M][5], planes [scene_rows][P][3]; row r of a launch reads scene r % scene_rows
-struct GuideArgs {
-  const float* discs;
-  const float* planes;
-  int scene_rows, M, P, iters;
-  float lambda, cap;
-};
 
 __device__ __forceinline__ float pin_blend(const PinArgs& p, int e, float z, float prev) {
   return repaint_blend(p.known, p.mask, e % p.span, p.c_known, p.c_known_noise, p.known_noise, z, prev);
@@ -128,52 +120,6 @@ struct StepArgs {
 __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
   // torch.clamp propagates NaN
   return v < lo ? lo : (v > hi ? hi : v);
-}
-
-// Cost guidance v1: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs and P planes, its
-// gradient and the number of active terms; the contract's operations in the contract's order, each rounded on its own
-__device__ __forceinline__ void guide_grad(const float* discs, int M, const float* planes, int P, float hf, float x, float y,
-                                           float& J, float& gx, float& gy, int& active) {
-#pragma clang fp contract(off)
-  J = 0.f; gx = 0.f; gy = 0.f; active = 0;
-  for (int i = 0; i < M; ++i) {
-    const float* q = discs + i * 5;
-    const float r = q[4];
-    if (!(r > 0.f)) continue;                  // an empty slot (a NaN radius too)
-    const float hx = hf * q[2], hy = hf * q[3];
-    const float ox = q[0] + hx, oy = q[1] + hy;
-    const float dx = x - ox, dy = y - oy;
-    const float xx = dx * dx, yy = dy * dy;
-    const float d2 = xx + yy;
-    const float rr = r * r;
-    const float inv = 1.0f / rr;
-    const float sd = d2 * inv;
-    const float phi = 1.0f - sd;
-    if (phi > 0.f) {
-      const float pp = phi * phi;
-      J = J + pp / 2.0f;
-      const float k2 = 2.0f * phi;
-      const float k = k2 * inv;
-      const float kx = k * dx, ky = k * dy;
-      gx = gx - kx;
-      gy = gy - ky;
-      ++active;
-    }
-  }
-  for (int i = 0; i < P; ++i) {
-    const float* q = planes + i * 3;
-    const float nx = q[0], ny = q[1];
-    const float ax = nx * x, ay = ny * y;
-    const float psi = (ax + ay) - q[2];
-    if (psi > 0.f) {
-      const float pp = psi * psi;
-      J = J + pp / 2.0f;
-      const float px = psi * nx, py = psi * ny;
-      gx = gx + px;
-      gy = gy + py;
-      ++active;
-    }
-  }
 }
 
 // The guide of one step at element e, whose clipped pred_original_sample is x0.  An xy element (d < 2; the host checked dim >= 2)
@@ -325,10 +271,10 @@ static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const
   return ADX_OK;
 }
 
-// the refusals of "cost guidance v1" that every guided launch and guide_cost share; `step`: a step, which also reads iters, cap
-// and lambda; `out2` may be null
-static int guide_check(const adx_guide* g, const char* what, bool step, bool inpaint, const void* out, size_t on, const void* out2,
-                       size_t on2, int batch, int dim, GuideArgs* a) {
+// the refusals of "cost guidance v1" that every guided launch, guide_cost and the guided selection share (sched.h); `step`: a
+// step, which also reads iters, cap and lambda; `out2` may be null
+int guide_check(const adx_guide* g, const char* what, bool step, bool inpaint, const void* out, size_t on, const void* out2,
+                size_t on2, int batch, int dim, GuideArgs* a) {
   ADX_REQUIRE(dim >= 2, "%s: cost guidance moves (x, y), dim is %d", what, dim);
   ADX_REQUIRE(g->n_discs >= 0 && g->n_discs <= ADX_GUIDE_MAX_DISCS, "%s: n_discs %d outside 0..%d", what, g->n_discs,
               ADX_GUIDE_MAX_DISCS);

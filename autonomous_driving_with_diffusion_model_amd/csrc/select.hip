@@ -12,7 +12,14 @@
 //   4. all threads copy the winning row word for word.
 // No atomics and no inter-workgroup traffic: a given input gives the same bits on every launch.  Every product and sum is
 // rounded on its own (no contraction), so the bits do not depend on what the compiler would fuse either.
-#include "adx_common.h"
+//
+// "Selection cost v2" (adx_traj_select_guide) is a second instantiation of the same kernel (kGuide): the scene's discs and planes
+// are staged in LDS beside xs / ys (every lane of a wave reads the same constraint word: a broadcast, no bank conflict), step 2
+// also evaluates each waypoint's "cost guidance v1" cost and active count with the routine the step kernels use (guide.h) from the
+// LDS copy of xy, reduces them with the butterflies adx_guide_cost uses and takes a wave-wide vote on "every xy finite"; step 3
+// searches the free candidates alone when `hard` is set and one of them has a finite cost, and reports whether the winner is
+// blocked.  The kGuide = false instantiation reads none of the fields behind w_consensus: its code is what it was.
+#include "sched.h"
 
 namespace adx {
 
@@ -28,6 +35,12 @@ struct SelectArgs {
   float* best;
   int scenes, K, H, D;
   float w_goal, w_smooth, w_consensus;
+  // selection cost v2 (the kGuide kernel only)
+  GuideArgs guide;
+  float w_guide;
+  int hard;
+  int32_t* active;       // [scenes][K]
+  int32_t* blocked;      // [scenes]
 };
 
 // minimum that a NaN wins (numpy's min): the goal term of a candidate with a NaN waypoint is NaN
@@ -39,12 +52,16 @@ __device__ __forceinline__ float wave_min_nan(float v) {
   return v;
 }
 
+template <bool kGuide>
 __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
 #pragma clang fp contract(off)
   __shared__ float xs[kSelMaxK * kSelMaxH], ys[kSelMaxK * kSelMaxH];
   __shared__ float part_x[kSelWaves][kSelMaxH], part_y[kSelWaves][kSelMaxH];
   __shared__ float cost_s[kSelMaxK];
   __shared__ int win_s;
+  // kGuide only (an instantiation that never touches them allocates none of it): the scene's constraints and free[k]
+  __shared__ float disc_s[ADX_GUIDE_MAX_DISCS * 5], plane_s[ADX_GUIDE_MAX_PLANES * 3];
+  __shared__ int free_s[kSelMaxK];
   const int s = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int K = a.K, H = a.H, D = a.D;
   const size_t row_floats = (size_t)H * D;
@@ -55,6 +72,13 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
     const float* p = a.trajs + ((size_t)k * a.scenes + s) * row_floats + (size_t)h * D;
     xs[i] = p[0];
     ys[i] = D > 1 ? p[1] : 0.f;
+  }
+  if constexpr (kGuide) {      // the scene's discs and planes, once: the M * 5 and P * 3 words are within the arrays (the host checked)
+    const int scene = s % a.guide.scene_rows;
+    const float* discs = a.guide.discs + (size_t)scene * a.guide.M * 5;
+    const float* planes = a.guide.planes + (size_t)scene * a.guide.P * 3;
+    for (int i = tid; i < a.guide.M * 5; i += 256) disc_s[i] = discs[i];
+    for (int i = tid; i < a.guide.P * 3; i += 256) plane_s[i] = planes[i];
   }
   __syncthreads();
 
@@ -109,6 +133,29 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
       const float cons = wave_sum(t) / (float)H;
       cost = cost + a.w_consensus * cons;
     }
+    if constexpr (kGuide) {
+      // violation and active count exactly as guide_cost_kernel forms them: lane = waypoint, lanes h >= H hold 0, the same two
+      // butterflies.  The count and the vote run whatever the weights; the weighted term only when asked for
+      float J = 0.f;
+      int act = 0;
+      if (live) {
+        float jx, jy;
+        guide_grad(disc_s, a.guide.M, plane_s, a.guide.P, (float)lane, px, py, J, jx, jy, act);
+      }
+      if (a.w_guide != 0.f) {
+        const float violation = wave_sum(J);
+        cost = cost + a.w_guide * violation;
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) act += __shfl_xor(act, off, 64);
+      // a NaN waypoint compares false against every constraint: it must not count as "violates nothing"
+      const bool odd = live && !(__builtin_fabsf(px) < __builtin_inff() && __builtin_fabsf(py) < __builtin_inff());
+      const bool all_finite = __ballot(odd) == 0ull;
+      if (lane == 0) {
+        a.active[(size_t)s * K + k] = act;
+        free_s[k] = (act == 0 && all_finite) ? 1 : 0;
+      }
+    }
     if (lane == 0) {
       cost_s[k] = cost;
       a.cost[(size_t)s * K + k] = cost;
@@ -124,6 +171,14 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
       const float c = cost_s[lane];
       if (__builtin_fabsf(c) < __builtin_inff()) v = c;     // false for inf and NaN
     }
+    if constexpr (kGuide) {
+      // the two-set rule: when some free candidate has a finite cost, the others' keys become +inf and the same search runs on
+      // what is left (the winner then has a finite key, so a masked lane can never be picked by the tie rule)
+      if (a.hard) {
+        const bool free_finite = lane < K && free_s[lane] != 0 && v < __builtin_inff();
+        if (__ballot(free_finite) != 0ull && !free_finite) v = __builtin_inff();
+      }
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       const float ov = __shfl_xor(v, off, 64);
@@ -133,6 +188,7 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
     if (lane == 0) {
       win_s = idx;
       a.index[s] = idx;
+      if constexpr (kGuide) a.blocked[s] = free_s[idx] != 0 ? 0 : 1;
     }
   }
   __syncthreads();
@@ -149,30 +205,82 @@ bool overlaps(const void* p, size_t pn, const void* q, size_t qn) {
   return a < b + qn && b < a + pn;
 }
 
-}  // namespace
-
-int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
-                hipStream_t s) {
-  ADX_REQUIRE(c != nullptr, "traj select: null configuration");
-  ADX_REQUIRE(c->candidates >= 1 && c->candidates <= kSelMaxK, "traj select: %d candidates, supported 1..%d", c->candidates, kSelMaxK);
-  ADX_REQUIRE(c->horizon >= 1 && c->horizon <= kSelMaxH, "traj select: horizon %d, supported 1..%d", c->horizon, kSelMaxH);
-  ADX_REQUIRE(c->dim >= 1 && c->dim <= kSelMaxD, "traj select: transition dim %d, supported 1..%d", c->dim, kSelMaxD);
-  ADX_REQUIRE(c->scenes >= 1 && c->scenes <= 65535, "traj select: %d scenes, supported 1..65535", c->scenes);
+// the refusals of "selection cost v1", which v2 inherits: the limits, the pointers both versions have, their overlaps
+int select_check(int scenes, int K, int H, int D, const float* trajs, const float* cost, const int32_t* index, const float* best) {
+  ADX_REQUIRE(K >= 1 && K <= kSelMaxK, "traj select: %d candidates, supported 1..%d", K, kSelMaxK);
+  ADX_REQUIRE(H >= 1 && H <= kSelMaxH, "traj select: horizon %d, supported 1..%d", H, kSelMaxH);
+  ADX_REQUIRE(D >= 1 && D <= kSelMaxD, "traj select: transition dim %d, supported 1..%d", D, kSelMaxD);
+  ADX_REQUIRE(scenes >= 1 && scenes <= 65535, "traj select: %d scenes, supported 1..65535", scenes);
   ADX_REQUIRE(trajs != nullptr && cost != nullptr && index != nullptr && best != nullptr, "traj select: null tensor");
-  const size_t row = (size_t)c->horizon * c->dim * sizeof(float);
-  const size_t in_bytes = (size_t)c->candidates * c->scenes * row, best_bytes = (size_t)c->scenes * row;
-  const size_t cost_bytes = (size_t)c->scenes * c->candidates * sizeof(float), index_bytes = (size_t)c->scenes * sizeof(int32_t);
+  const size_t row = (size_t)H * D * sizeof(float);
+  const size_t in_bytes = (size_t)K * scenes * row, best_bytes = (size_t)scenes * row;
+  const size_t cost_bytes = (size_t)scenes * K * sizeof(float), index_bytes = (size_t)scenes * sizeof(int32_t);
   ADX_REQUIRE(!overlaps(best, best_bytes, trajs, in_bytes) && !overlaps(cost, cost_bytes, trajs, in_bytes) &&
                   !overlaps(index, index_bytes, trajs, in_bytes),
               "traj select: an output aliases trajs");
   ADX_REQUIRE(!overlaps(best, best_bytes, cost, cost_bytes) && !overlaps(best, best_bytes, index, index_bytes) &&
                   !overlaps(cost, cost_bytes, index, index_bytes),
               "traj select: outputs alias each other");
-  SelectArgs a;
+  return ADX_OK;
+}
+
+}  // namespace
+
+int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
+                hipStream_t s) {
+  ADX_REQUIRE(c != nullptr, "traj select: null configuration");
+  const int rc = select_check(c->scenes, c->candidates, c->horizon, c->dim, trajs, cost, index, best);
+  if (rc != ADX_OK) return rc;
+  SelectArgs a = {};
   a.trajs = trajs; a.target = target; a.cost = cost; a.index = index; a.best = best;
   a.scenes = c->scenes; a.K = c->candidates; a.H = c->horizon; a.D = c->dim;
   a.w_goal = c->w_goal; a.w_smooth = c->w_smooth; a.w_consensus = c->w_consensus;
-  traj_select_kernel<<<dim3(c->scenes), dim3(256), 0, s>>>(a);
+  traj_select_kernel<false><<<dim3(c->scenes), dim3(256), 0, s>>>(a);
+  ADX_LAUNCH_CHECK();
+  return ADX_OK;
+}
+
+// "Selection cost v2": v1's refusals first, then what the guide adds
+int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide, float* cost,
+                      int32_t* active, int32_t* index, int32_t* blocked, float* best, hipStream_t s) {
+  const char* const what = "traj select guide";
+  ADX_REQUIRE(c != nullptr, "traj select: null configuration");
+  int rc = select_check(c->scenes, c->candidates, c->horizon, c->dim, trajs, cost, index, best);
+  if (rc != ADX_OK) return rc;
+  ADX_REQUIRE(c->dim >= 2, "traj select guide: the guide scores (x, y), dim is %d", c->dim);
+  ADX_REQUIRE(guide != nullptr, "traj select guide: null guide");
+  ADX_REQUIRE(active != nullptr, "traj select guide: null active");
+  ADX_REQUIRE(blocked != nullptr, "traj select guide: null blocked");
+  const int S = c->scenes, K = c->candidates;
+  const size_t row = (size_t)c->horizon * c->dim * sizeof(float);
+  const size_t in_bytes = (size_t)K * S * row, best_bytes = (size_t)S * row;
+  const size_t sk_bytes = (size_t)S * K * sizeof(float), s_bytes = (size_t)S * sizeof(int32_t);
+  SelectArgs a = {};
+  rc = guide_check(guide, what, false, false, cost, sk_bytes, active, sk_bytes, S * K, c->dim, &a.guide);
+  if (rc != ADX_OK) return rc;
+  const bool bare = guide->n_discs == 0 && guide->n_planes == 0;
+  ADX_REQUIRE(guide->scene_rows == S || (guide->scene_rows == 1 && bare),
+              "traj select guide: the guide holds %d scenes, the selection %d (1 is accepted of a guide without discs and planes)",
+              guide->scene_rows, S);
+  const size_t dn = (size_t)guide->scene_rows * guide->n_discs * 5 * sizeof(float);
+  const size_t pn = (size_t)guide->scene_rows * guide->n_planes * 3 * sizeof(float);
+  const void* const outs[3] = {index, blocked, best};
+  const size_t out_bytes[3] = {s_bytes, s_bytes, best_bytes};
+  for (int i = 0; i < 3; ++i)
+    ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], guide->discs, dn) && !overlaps(outs[i], out_bytes[i], guide->planes, pn),
+                "traj select guide: an output overlaps discs or planes");
+  ADX_REQUIRE(!overlaps(active, sk_bytes, trajs, in_bytes) && !overlaps(blocked, s_bytes, trajs, in_bytes),
+              "traj select guide: an output aliases trajs");
+  ADX_REQUIRE(!overlaps(active, sk_bytes, cost, sk_bytes) && !overlaps(active, sk_bytes, index, s_bytes) &&
+                  !overlaps(active, sk_bytes, best, best_bytes) && !overlaps(active, sk_bytes, blocked, s_bytes) &&
+                  !overlaps(blocked, s_bytes, cost, sk_bytes) && !overlaps(blocked, s_bytes, index, s_bytes) &&
+                  !overlaps(blocked, s_bytes, best, best_bytes),
+              "traj select guide: outputs alias each other");
+  a.trajs = trajs; a.target = target; a.cost = cost; a.index = index; a.best = best;
+  a.scenes = S; a.K = K; a.H = c->horizon; a.D = c->dim;
+  a.w_goal = c->w_goal; a.w_smooth = c->w_smooth; a.w_consensus = c->w_consensus;
+  a.w_guide = c->w_guide; a.hard = c->hard != 0; a.active = active; a.blocked = blocked;
+  traj_select_kernel<true><<<dim3(S), dim3(256), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }

@@ -24,6 +24,10 @@ decided through the tick, inside the step kernels ("pinned waypoints v1" of incl
 say `trajs[:, 0, :3] = 0`.
 An eighth says where NOT to go: `guide=Guide(discs, planes, ...)` bends every step's predicted clean trajectory away from the
 caller's obstacles, inside the step kernels ("cost guidance v1" of include/adx.h, guide.py).
+The fourth and the eighth meet in the selector: one with `w_guide` or `hard` (`TrajectorySelector.uses_guide`) is handed the
+tick's guide and scores every candidate against the obstacles in the select launch itself ("selection cost v2" of include/adx.h):
+with `hard` a candidate that violates nothing beats every candidate that violates something, and `Selection.blocked` says per scene
+whether the chosen plan is still blocked.  A plain selector on a guided tick runs as it always did.
 """
 from __future__ import annotations
 
@@ -124,7 +128,10 @@ class TickPlan:
     # k * S + s of the noise stream), the targets are tiled K times, the conditioning table keeps the image batch at S (the encoder
     # runs once per scene) and after the final clamp `selector` picks the [S, H, D] winners.  Needs `hoisted` and an unsharded noise
     K: int
-    selector: Optional[TrajectorySelector]   # baked (its three weights).  At K > 1: the argument, or TrajectorySelector(*EVAL.SELECT)
+    # baked (its weights, and `hard`).  At K > 1: the argument, or TrajectorySelector(*EVAL.SELECT) -- 3, 4 or 5 values: w_goal,
+    # w_smooth, w_consensus[, w_guide[, hard]].  One with `uses_guide` is called with the tick's `guide` (whose static buffers a
+    # graph's select node then reads: new obstacle values replay); any other is called without, guide or no guide
+    selector: Optional[TrajectorySelector]
     rows: int               # baked.  Rows of the loop: init_trajs.shape[0] when init_trajs is given, else K * S
     H: int                  # baked.  MODEL.HORIZON
     D: int                  # baked.  MODEL.TRANSITION_DIM
@@ -185,7 +192,10 @@ class TickPlan:
     def key(self) -> tuple:
         """Everything baked, as a hashable: two plans with equal keys capture the same graph over the same shapes."""
         sel, ctl, pin, guide = self.selector, self.controller, self.pin, self.guide
-        return (self.S, self.K, None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus), self.rows, self.H, self.D,
+        weights = None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus)
+        if sel is not None and sel.uses_guide:
+            weights += (sel.w_guide, sel.hard)
+        return (self.S, self.K, weights, self.rows, self.H, self.D,
                 self.n, self.use, self.free_scale, self.fuse, self.hoisted, self.is_ddpm,
                 "init" if self.start == "randn" else self.start,
                 self.m_warm, self.shift, self.is_warm, self.motion is None,
@@ -253,8 +263,8 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
     """The TickPlan of a `generate_traj` call with these arguments (`graphed`: of a GraphedSampler call).  Pure: no launch, no device
     allocation (but one: a strided `motion` is packed, as it always was), no tick of the noise stream, nothing written to the
     scheduler, `warm` or the controller -- so every refusal comes before any of those and before a capture opens, in the order
-    candidates, `noise` / `step_noise`, warm, control, pin, guide.  `scheduler` is read for a warm tick on the caller's own timesteps
-    (`set_timesteps=False`), for a pin and for a guide; `is_ddpm` asks it with defaults."""
+    candidates, `noise` / `step_noise`, warm, control, pin, guide, a selector that needs a guide.  `scheduler` is read for a warm
+    tick on the caller's own timesteps (`set_timesteps=False`), for a pin and for a guide; `is_ddpm` asks it with defaults."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     S, device = int(image.shape[0]), image.device
     hoisted = bool(fuse) and _hoists(model)
@@ -264,7 +274,11 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
         raise ValueError(f"candidates must be 1..{MAX_CANDIDATES}, got {K}")
     if K > 1:
         if selector is None:
-            selector = TrajectorySelector(*getattr(cfg.EVAL, "SELECT", (1.0, 0.0, 0.0)))
+            select = tuple(getattr(cfg.EVAL, "SELECT", (1.0, 0.0, 0.0)))
+            if not 3 <= len(select) <= 5:
+                raise ValueError("EVAL.SELECT holds 3, 4 or 5 values (w_goal, w_smooth, w_consensus[, w_guide[, hard]]), got "
+                                 f"{len(select)}")
+            selector = TrajectorySelector(*select)
         if not hoisted:
             raise ValueError("generate_traj: candidates > 1 needs the hoisted conditioning path: fuse=True and "
                              "model.cache_perception on (the per-step path would run the encoder on K * S rows)")
@@ -328,6 +342,8 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
             raise ValueError(f"velocity must be a float32 tensor [{S}] on {device}, got {what}")
     pin = _pin_plan(cfg, pin, image, scheduler, noise, step_noise, graphed)
     guide = _guide_plan(cfg, guide, image, scheduler)
+    if K > 1 and selector.uses_guide and guide is None:
+        raise ValueError(f"generate_traj: {selector!r} scores the candidates against a guide; pass guide=Guide(...) for the tick")
     rows = K * S if init_trajs is None else int(init_trajs.shape[0])
     free = use == GuidanceType.FREE_GUIDANCE
     return TickPlan(S=S, K=K, selector=selector if K > 1 else None, rows=rows, H=H, D=D, n=n, use=use,
@@ -410,7 +426,8 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     trajs = trajs.to(torch.float32).clamp(-1, 1)
     best, sel = trajs, None                            # at K = 1 the trajectory is its own winner
     if K > 1:
-        sel = plan.selector(trajs, S, scene_tgt)       # the cost is taken in the model's own units (the units of `target`)
+        # the cost is taken in the model's own units (the units of `target` and of the guide)
+        sel = plan.selector(trajs, S, scene_tgt, plan.guide) if plan.selector.uses_guide else plan.selector(trajs, S, scene_tgt)
         best = sel.best
     if plan.m_warm > 0:
         warm._store(best)
@@ -421,7 +438,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         cands = trajs.reshape(K, S, trajs.shape[1], trajs.shape[2])
         if scale_xy:
             cands[..., :2] *= model.magic_num
-        sel = Selection(best, sel.index, sel.cost, cands)
+        sel = Selection(best, sel.index, sel.cost, cands, sel.active, sel.blocked)
     return _tick_result(best, sel, control, return_selection, controller is not None)
 
 
@@ -540,7 +557,8 @@ class GraphedSampler:
     Eval mode, fused step path.  Inputs are copied into static buffers; the camera frame's perception pass is part of
     the graph, so every replay sees the new frame.
     `candidates=K` > 1 (or EVAL.CANDIDATES when left at 1): best-of-K sampling as in `generate_traj`; the select kernel is a
-    node of the graph, the call returns the [S, H, D] winners and `last_selection` the last replay's index and cost.
+    node of the graph, the call returns the [S, H, D] winners and `last_selection` the last replay's index and cost (and, when the
+    selector scores against the call's guide, `active` and `blocked`: the select node reads the guide's static buffers).
     `warm=WarmStart(...)` (or EVAL.WARM_STEPS > 0 when left at None): warm starting as in `generate_traj`.  The sampler then holds
     two graphs, a cold and a warm one, and picks by the host flag `warm.valid`; both end with the copy into the static
     `warm.prev`, so replay k + 1 starts from replay k's result without leaving the device.  `motion` travels through a static
@@ -655,11 +673,13 @@ class GraphedSampler:
 
     @property
     def last_selection(self) -> Optional[Selection]:
-        """Clones of the static `index` [S] and `cost` [S, K] buffers as the last replay left them (`best` and `candidates`
-        are not kept: the call returned the winners); None before the first call and at one candidate per scene."""
+        """Clones of the static `index` [S] and `cost` [S, K] buffers as the last replay left them, and of `active` [S, K] and
+        `blocked` [S] when the selector ran against a guide (`best` and `candidates` are not kept: the call returned the winners);
+        None before the first call and at one candidate per scene."""
         if self._sel is None:
             return None
-        return Selection(None, self._sel.index.clone(), self._sel.cost.clone())
+        clone = lambda t: None if t is None else t.clone()  # noqa: E731
+        return Selection(None, self._sel.index.clone(), self._sel.cost.clone(), None, clone(self._sel.active), clone(self._sel.blocked))
 
     @property
     def last_control(self) -> Optional[torch.Tensor]:

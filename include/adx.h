@@ -869,6 +869,48 @@ int adx_guide_cost(const float* traj, const adx_guide* guide, float* cost, int32
                    int32_t dim, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Selection cost v2: best-of-K selection that sees the guide.  Selection cost v1 with one more term -- what a candidate still
+ * violates of the scene's discs and planes -- and a hard rule: a candidate that violates nothing beats every candidate that
+ * violates something.  One launch, the launch that already holds every candidate's xy on chip, no host decision (a node of a
+ * captured graph).  Selection cost v1, adx_traj_select and adx_select_cfg stay as they are; this stands beside them.  Callers and
+ * fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ * From selection cost v1, word for word: the layout (candidate-major rows), the points and units, the goal, smooth and consensus
+ * terms and their arithmetic, "a weight of exactly 0 is not evaluated", the copy of `best` bit for bit, the limits on candidates,
+ * horizon and scenes, and the arithmetic (fp32, every operation rounded on its own, fixed trees, no atomics: the same input gives
+ * the same bits on every launch).
+ *
+ *   violation  violation[s][k] = the cost J of cost guidance v1 of candidate k's waypoints under scene s's discs and planes: per
+ *              waypoint exactly as that contract writes it, with h = the waypoint index; the H values summed by the fixed xor
+ *              butterfly of adx_guide_cost (lane = waypoint, lanes h >= H hold 0).  So violation[s][k] is bit for bit
+ *              adx_guide_cost's cost[k * scenes + s] on the same trajs and guide.
+ *   active     active[s][k] (int32) = adx_guide_cost's active[k * scenes + s], exactly.  Always written, whatever the weights.
+ *   cost       ((w_goal * goal + w_smooth * smooth) + w_consensus * consensus) + w_guide * violation: v1's sum in v1's order, the
+ *              new term last.  w_guide == 0: the term is not evaluated.
+ *   free       free[s][k] = active[s][k] == 0 AND every x and y of the candidate is finite.  (A NaN waypoint compares false
+ *              against every constraint and would otherwise count as "violates nothing": a plan with a NaN in it never wins on
+ *              safety grounds.)
+ *   index      hard == 0: v1's rule on cost.  hard != 0: if at least one candidate of the scene is free and has a finite cost,
+ *              v1's rule over those candidates alone; otherwise v1's rule over all candidates.  v1's rule: the smallest k among
+ *              the smallest finite costs; no finite cost -> 0.
+ *   blocked    blocked[s] (int32) = 1 if the chosen candidate is not free, else 0.  Written in both modes.
+ *   guide      not NULL.  n_discs == n_planes == 0 is legal: everything is then free unless non-finite.  scene_rows equals
+ *              `scenes`, or is 1 for a guide without discs and planes.  iters, lambda and cap are not read.
+ *
+ * ADX_ERR_INVALID before any GPU work, each with its own text: v1's refusals; dim < 2; a NULL guide, active or blocked; the
+ * guide's own shape refusals (the check of adx_guide_cost); scene_rows that is neither of the two above; an output overlapping
+ * trajs, discs, planes or another output.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_select_guide_cfg {
+  int32_t scenes, candidates, horizon, dim;
+  float w_goal, w_smooth, w_consensus, w_guide;
+  int32_t hard;
+} adx_select_guide_cfg;
+/* trajs, target, cost, index, best as adx_traj_select; active [scenes][candidates] and blocked [scenes] (int32). */
+int adx_traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
+                          float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Control v1: waypoints -> (throttle, steer, brake) on the device, the step after the sampling loop in the reference's agents
  * (control/controller.py:29-76 `control_pid`, control/pid.py, `post_process_control` of interact.py:218-229 and
  * e2e_driving/diffusion_agent.py:268-277).  One launch per tick for all scenes, no host decision; the PID windows live in

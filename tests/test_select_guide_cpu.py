@@ -1,0 +1,282 @@
+"""CPU: "selection cost v2" (include/adx.h: adx_traj_select_guide) without a device -- the restatement's rule on hand-built scenes
+(tests/select_guide_ref.py), the promise of its case generator that every scene is decided beyond fp32 rounding, the selector in
+`plan_tick` (on the stubs of tests/test_tick_plan_cpu.py), the new struct and prototype, and every refusal of the new export
+through libadx.so (placeholder addresses, never dereferenced: the checks run before any GPU work)."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import select_guide_ref as V
+import select_ref as R
+import test_tick_plan_cpu as T
+from autonomous_driving_with_diffusion_model_amd.control.select import Selection, TrajectorySelector
+from autonomous_driving_with_diffusion_model_amd.guide import Guide
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+S, H, D = T.S, T.H, T.D
+
+
+# ---- 1. the rule -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(V.hand_scenes()))
+def test_the_rule_on_hand_built_scenes(name):
+    sc = V.hand_scenes()[name]
+    for hard in (True, False):
+        got = V.hand_select(sc, hard)
+        assert (got["index"].tolist(), got["blocked"].tolist()) == sc["want"][hard], (name, hard, got["cost"], got["free"])
+
+
+def test_what_each_hand_built_scene_is_about():
+    sc = V.hand_scenes()
+    one = V.hand_select(sc["free beats blocked"], True)
+    assert one["free"].tolist() == [[False, False, True]] and one["cost"][0].argmax() == 2        # the free one costs the most
+    assert V.hand_select(sc["free beats blocked"], False)["index"].tolist() == [0]                 # ... and loses without `hard`
+    none = V.hand_select(sc["all blocked"], True)
+    assert not none["free"].any() and none["index"].tolist() == R.pick(none["cost"]).tolist() and none["blocked"].tolist() == [1]
+    nan = V.hand_select(sc["free with a NaN cost"], True)
+    assert np.isnan(nan["cost"][0, 0]) and nan["free"].tolist() == [[True, False, True]] and nan["index"].tolist() == [2]
+    alone = V.hand_select(sc["only free one has a NaN cost"], True)
+    assert np.isnan(alone["cost"][0, 0]) and alone["free"].tolist() == [[True, False, False]] and alone["index"].tolist() == [1]
+    xy = V.hand_select(sc["a NaN waypoint is never free"], True)
+    assert xy["active"].tolist() == [[2, 0, 2]] and not xy["free"].any() and np.array_equal(xy["cost"], np.zeros((1, 3)))
+    paid = V.hand_select(sc["w_guide alone"], False)
+    assert paid["cost"][0, 2] == 0.0 and (paid["cost"][0, :2] > 0).all() and np.array_equal(paid["cost"], paid["violation"])
+
+
+def test_the_rule_itself():
+    inf, nan = np.inf, np.nan
+    cost = np.array([[3.0, 1.0, 2.0, 1.0], [nan, inf, -inf, nan], [5.0, nan, 4.0, 6.0]])
+    free = np.array([[True, False, True, False], [True, True, False, False], [False, True, False, True]])
+    assert [a.tolist() for a in V.pick(cost, free, False)] == [[1, 0, 2], [1, 0, 1]]
+    # scene 0: the free ones are 0 and 2; scene 1: no finite cost at all -> 0; scene 2: the free one with a NaN cost is passed over
+    assert [a.tolist() for a in V.pick(cost, free, True)] == [[2, 0, 3], [0, 0, 0]]
+    assert [a.tolist() for a in V.pick(cost, np.zeros_like(free), True)] == [[1, 0, 2], [1, 1, 1]]
+    tie = np.array([[2.0, 1.0, 1.0, 1.0]])
+    assert V.pick(tie, np.array([[False, False, True, True]]), True)[0].tolist() == [2]           # ties to the lowest k of the set
+    assert V.searched(cost, free, True).tolist() == [[True, False, True, False], [False] * 4, [False, False, False, True]]
+
+
+# ---- 2. the generated cases --------------------------------------------------------------------------------------------------------
+def test_every_generated_scene_is_decided_and_both_branches_of_the_rule_occur():
+    cases = V.cases()
+    assert len(cases) == len(V.SHAPES) * len(V.WEIGHTS) == 16
+    assert [(c["S"], c["K"], c["H"], c["D"], c["M"], c["P"]) for c in cases[::len(V.WEIGHTS)]] == list(V.SHAPES)
+    narrowed = fell_back = 0
+    for c in cases:
+        Sn, K = c["S"], c["K"]
+        assert c["trajs"].shape == (K * Sn, c["H"], c["D"]) and c["trajs"].dtype == np.float32 and np.abs(c["trajs"]).max() <= 1.0
+        got = V.select(c["trajs"], Sn, c["target"], c["weights"], c["hard"], c["discs"], c["planes"])
+        bound = V.cost_bound(c["trajs"], Sn, c["weights"], True, c["discs"], c["planes"])
+        assert np.array_equal(bound, c["bound"]) and np.isfinite(got["cost"]).all() and (bound >= 0).all()
+        assert (bound >= R.cost_bound(K, c["H"], c["weights"][:3], True)).all()
+        where = V.searched(got["cost"], got["free"], c["hard"])
+        for s in range(Sn):
+            cs = np.sort(got["cost"][s][where[s]])
+            assert len(cs) == 1 or cs[1] - cs[0] > V.GAP * bound[s].max(), (c["name"], s)
+            assert got["index"][s] == np.flatnonzero(where[s])[got["cost"][s][where[s]].argmin()]
+            if c["hard"]:
+                narrowed += bool(got["free"][s].any())
+                fell_back += not got["free"][s].any()
+                assert got["blocked"][s] == (0 if got["free"][s].any() else 1)
+        assert np.array_equal(got["free"].any(-1), c["some_free"])
+        rows = c["trajs"].reshape(K, Sn, c["H"], c["D"])
+        assert all(V.hinges_clear(rows[:, s], None if c["discs"] is None else c["discs"][s:s + 1],
+                                  None if c["planes"] is None else c["planes"][s:s + 1]) for s in range(Sn))
+    assert narrowed >= 3 and fell_back >= 3
+    special = cases[3 * len(V.WEIGHTS)]["discs"]
+    assert special[0, 0, 4] == 0.0 and np.isnan(special[1, 1, 4])
+    assert all(V.violation(c["trajs"], c["S"], c["discs"], c["planes"])[1].max() > 0 for c in cases if c["K"] > 1)
+
+
+def test_fp32_evaluation_on_the_host_stays_inside_the_bound():
+    """The bound is derived, not measured; this guards the derivation against a slip: the violation in fp32 NumPy (guide_ref's
+    bit-for-bit restatement of the kernel's sum) weighted and added in fp32 to select_ref's fp64 v1 sum must sit inside it."""
+    for c in V.cases():
+        if c["weights"][3] == 0:
+            continue
+        Sn, K = c["S"], c["K"]
+        wave = V.G.row_cost_wave(c["trajs"], c["discs"], c["planes"]).reshape(K, Sn).T
+        v1 = R.select(c["trajs"], Sn, c["target"], c["weights"][:3])[0]
+        cost32 = (v1.astype(np.float32) + np.float32(c["weights"][3]) * wave).astype(np.float64)
+        want = V.select(c["trajs"], Sn, c["target"], c["weights"], c["hard"], c["discs"], c["planes"])["cost"]
+        # (v1 rounded to fp32 once more: u T1 at most, which the gamma_4 T1 inside B1 holds with room)
+        assert (np.abs(cost32 - want) <= c["bound"]).all(), c["name"]
+
+
+# ---- 3. the plan -------------------------------------------------------------------------------------------------------------------
+class _Scheduler(T._Scheduler):
+    supports_guide = True
+
+
+def _plan(began=None, **kw):
+    return T._plan(began, scheduler=kw.pop("scheduler", None) or _Scheduler(), **kw)
+
+
+def _guide():
+    return Guide(torch.zeros(S, 3, 5), torch.zeros(S, 2, 3))
+
+
+def test_selector_surface():
+    s = TrajectorySelector()
+    assert (s.w_goal, s.w_smooth, s.w_consensus, s.w_guide, s.hard, s.uses_guide) == (1.0, 0.0, 0.0, 0.0, False, False)
+    assert TrajectorySelector(w_guide=0.5).uses_guide and TrajectorySelector(hard=True).uses_guide
+    assert not TrajectorySelector(1, 2, 3, 0.0, 0).uses_guide and TrajectorySelector(1, 2, 3, 0.0, 1).hard is True
+    assert "hard=True" in repr(TrajectorySelector(hard=True)) and "hard" not in repr(TrajectorySelector(1, 2, 3))
+    old = Selection(1, 2, 3)
+    assert (old.candidates, old.active, old.blocked) == (None, None, None) and Selection(1, 2, 3, 4).candidates == 4
+    assert Selection._fields == ("best", "index", "cost", "candidates", "active", "blocked")
+    with pytest.raises(ValueError, match="scores against a guide"):
+        TrajectorySelector(hard=True)(torch.zeros(4, 8, 7), 2)                     # before the device check: no guide, no call
+    with pytest.raises(TypeError, match="must be a Guide or None"):
+        TrajectorySelector()(torch.zeros(4, 8, 7), 2, None, {"discs": None})
+
+
+def test_a_selector_that_needs_a_guide_is_refused_without_one_after_the_guide_section():
+    began = []
+    for sel in (TrajectorySelector(hard=True), TrajectorySelector(1.0, 0.0, 0.0, 0.5)):
+        with pytest.raises(ValueError, match="scores the candidates against a guide; pass guide="):
+            _plan(began, candidates=3, selector=sel)
+        assert _plan(began, candidates=3, selector=sel, guide=_guide()).selector is sel
+        assert _plan(began, candidates=1, selector=sel).selector is None              # K = 1: no selector runs, nothing to refuse
+    cfg = T._cfg()
+    cfg.EVAL.CANDIDATES, cfg.EVAL.SELECT = 3, (1.0, 0.0, 0.0, 0.0, True)
+    with pytest.raises(ValueError, match="scores the candidates against a guide"):
+        _plan(began, cfg=cfg)
+    # the guide's own refusals come first, and everything ahead of them
+    with pytest.raises(ValueError, match="guide.discs must hold"):
+        _plan(began, candidates=3, selector=TrajectorySelector(hard=True), guide=Guide(torch.zeros(3, 3, 5)))
+    with pytest.raises(ValueError, match="velocity must be"):
+        _plan(began, candidates=3, selector=TrajectorySelector(hard=True), controller=T._controller(), velocity=torch.zeros(S + 1))
+    # a plain selector on a guided tick is fine, and so is a guide nobody scores against
+    assert not _plan(began, candidates=3, guide=_guide()).selector.uses_guide
+    assert not began
+
+
+def test_eval_select_takes_three_four_or_five_values():
+    for select, want in (((0.5, 1.0, 2.0), (0.5, 1.0, 2.0, 0.0, False)), ((0.5, 1.0, 2.0, 0.25), (0.5, 1.0, 2.0, 0.25, False)),
+                         ((0.5, 1.0, 2.0, 0.0, 1), (0.5, 1.0, 2.0, 0.0, True)), ([1.0, 0.0, 0.0, 3.0, False], (1.0, 0.0, 0.0, 3.0, False))):
+        cfg = T._cfg()
+        cfg.EVAL.CANDIDATES, cfg.EVAL.SELECT = 2, select
+        sel = _plan(cfg=cfg, guide=_guide()).selector
+        assert (sel.w_goal, sel.w_smooth, sel.w_consensus, sel.w_guide, sel.hard) == want
+    for bad in ((1.0, 0.0), (1.0, 0.0, 0.0, 0.0, True, 1.0)):
+        cfg = T._cfg()
+        cfg.EVAL.CANDIDATES, cfg.EVAL.SELECT = 2, bad
+        with pytest.raises(ValueError, match="EVAL.SELECT holds 3, 4 or 5 values"):
+            _plan(cfg=cfg, guide=_guide())
+    from autonomous_driving_with_diffusion_model_amd.config import create_cfg
+    assert tuple(create_cfg().EVAL.SELECT) == (1.0, 0.0, 0.0)                        # the default stays the 3-tuple
+
+
+def test_key_tells_w_guide_and_hard_apart_and_is_unchanged_for_a_plain_selector():
+    g = _guide()
+    key = lambda sel, **kw: _plan(candidates=2, selector=sel, guide=g, **kw).key()  # noqa: E731
+    plain = key(TrajectorySelector(1.0, 0.5, 0.25))
+    assert plain[2] == (1.0, 0.5, 0.25)                                              # what it was before there was a w_guide
+    assert plain == key(TrajectorySelector(1.0, 0.5, 0.25, 0.0, False))
+    assert T._plan(candidates=2, selector=TrajectorySelector(1.0, 0.5, 0.25)).key() == plain[:-1] + (None,)
+    keys = [plain, key(TrajectorySelector(1.0, 0.5, 0.25, 0.5)), key(TrajectorySelector(1.0, 0.5, 0.25, 0.75)),
+            key(TrajectorySelector(1.0, 0.5, 0.25, hard=True)), key(TrajectorySelector(1.0, 0.5, 0.25, 0.5, True))]
+    hash(tuple(keys))
+    assert len(set(keys)) == len(keys)
+    assert keys[4][2] == (1.0, 0.5, 0.25, 0.5, True)
+    moved = Guide(torch.ones(S, 3, 5), torch.ones(S, 2, 3))                          # obstacle values travel through static buffers
+    assert _plan(candidates=2, selector=TrajectorySelector(1.0, 0.5, 0.25, hard=True), guide=moved).key() == keys[3]
+
+
+# ---- 4. the C ABI ------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def built():
+    import __graft_entry__ as g
+    g.build()
+    from autonomous_driving_with_diffusion_model_amd import _lib
+    return _lib
+
+
+def test_the_abi_has_the_new_entry_beside_the_old_one(built):
+    header = open(os.path.join(ROOT, "include", "adx.h")).read()
+    assert "Selection cost v2" in header and "Selection cost v1" in header
+    assert re.search(r"\bint\s+adx_traj_select_guide\s*\(", header) and "adx_select_guide_cfg" in header
+    assert hasattr(ctypes.CDLL(built.LIB_PATH), "adx_traj_select_guide") and "adx_traj_select_guide" in built.EXPORTED_SYMBOLS
+    fn = built.lazy("adx_traj_select_guide")
+    assert fn.restype is built.i32 and len(fn.argtypes) == 10
+    assert [f[0] for f in built.SelectGuideCfg._fields_] == ["scenes", "candidates", "horizon", "dim", "w_goal", "w_smooth",
+                                                             "w_consensus", "w_guide", "hard"]
+    assert ctypes.sizeof(built.SelectGuideCfg) == 36 and built.SelectGuideCfg.w_guide.offset == 28 and built.SelectGuideCfg.hard.offset == 32
+    assert all(getattr(built.SelectGuideCfg, n).offset == getattr(built.SelectCfg, n).offset for n, _ in built.SelectCfg._fields_)
+    assert ctypes.sizeof(built.SelectCfg) == 28                                      # v1's struct is what it was
+
+
+ROW = 16 * 7 * 4
+TRAJS, TARGET, COST, ACTIVE, INDEX, BLOCKED, BEST, DISCS, PLANES = (0x10000000 * (i + 1) for i in range(9))
+P1, P2, P3 = "traj select: ", "traj select guide: ", "traj select guide: "
+# (overrides of a good call at S = 2, K = 4, H = 16, D = 7 with M = 3 discs and P = 2 planes, the whole adx_last_error() text)
+TABLE = [
+    # ---- v1's refusals
+    (dict(c=None), P1 + "null configuration"),
+    (dict(K=0), P1 + "0 candidates, supported 1..64"), (dict(K=65), P1 + "65 candidates, supported 1..64"),
+    (dict(H=0), P1 + "horizon 0, supported 1..64"), (dict(H=65), P1 + "horizon 65, supported 1..64"),
+    (dict(D=0), P1 + "transition dim 0, supported 1..16"), (dict(D=17), P1 + "transition dim 17, supported 1..16"),
+    (dict(S=0), P1 + "0 scenes, supported 1..65535"), (dict(S=65536, guide=dict(scene_rows=65536)), P1 + "65536 scenes, supported 1..65535"),
+    (dict(trajs=None), P1 + "null tensor"), (dict(cost=None), P1 + "null tensor"), (dict(index=None), P1 + "null tensor"),
+    (dict(best=None), P1 + "null tensor"),
+    (dict(best=TRAJS + 7 * ROW), P1 + "an output aliases trajs"), (dict(cost=TRAJS + 4), P1 + "an output aliases trajs"),
+    (dict(index=TRAJS + 8 * ROW - 4), P1 + "an output aliases trajs"), (dict(cost=BEST + ROW), P1 + "outputs alias each other"),
+    (dict(index=COST + 28), P1 + "outputs alias each other"),
+    # ---- what the guide adds
+    (dict(D=1), P2 + "the guide scores (x, y), dim is 1"),
+    (dict(guide=None), P2 + "null guide"), (dict(active=None), P2 + "null active"), (dict(blocked=None), P2 + "null blocked"),
+    # ---- the guide's own shape refusals: the check adx_guide_cost uses, with its texts
+    (dict(guide=dict(n_discs=33)), P3 + "n_discs 33 outside 0..32"), (dict(guide=dict(n_discs=-1)), P3 + "n_discs -1 outside 0..32"),
+    (dict(guide=dict(n_planes=9)), P3 + "n_planes 9 outside 0..8"),
+    (dict(guide=dict(discs=None)), P3 + "null discs with n_discs 3"), (dict(guide=dict(planes=None)), P3 + "null planes with n_planes 2"),
+    (dict(guide=dict(scene_rows=0)), P3 + "batch 8 must be a positive multiple of scene_rows 0"),
+    (dict(guide=dict(scene_rows=3)), P3 + "batch 8 must be a positive multiple of scene_rows 3"),
+    (dict(cost=DISCS + 4), P3 + "an output overlaps discs or planes"), (dict(active=PLANES), P3 + "an output overlaps discs or planes"),
+    # ---- scene_rows is `scenes`, or 1 for a guide without arrays
+    (dict(guide=dict(scene_rows=1)), P2 + "the guide holds 1 scenes, the selection 2 (1 is accepted of a guide without discs and planes)"),
+    (dict(guide=dict(scene_rows=4)), P2 + "the guide holds 4 scenes, the selection 2 (1 is accepted of a guide without discs and planes)"),
+    (dict(guide=dict(scene_rows=8, n_discs=0, n_planes=0)),
+     P2 + "the guide holds 8 scenes, the selection 2 (1 is accepted of a guide without discs and planes)"),
+    # ---- the other outputs against discs, planes, trajs and each other
+    (dict(index=DISCS + 2 * 3 * 5 * 4 - 4), P2 + "an output overlaps discs or planes"),
+    (dict(blocked=PLANES + 8), P2 + "an output overlaps discs or planes"), (dict(best=DISCS - 2 * ROW + 4), P2 + "an output overlaps discs or planes"),
+    (dict(active=TRAJS + 8 * ROW - 4), P2 + "an output aliases trajs"), (dict(blocked=TRAJS), P2 + "an output aliases trajs"),
+    (dict(active=COST + 28), P2 + "outputs alias each other"), (dict(active=INDEX - 28), P2 + "outputs alias each other"),
+    (dict(active=BEST + 2 * ROW - 4), P2 + "outputs alias each other"), (dict(blocked=ACTIVE + 28), P2 + "outputs alias each other"),
+    (dict(blocked=COST), P2 + "outputs alias each other"), (dict(blocked=INDEX + 4), P2 + "outputs alias each other"),
+    (dict(blocked=BEST), P2 + "outputs alias each other"),
+]
+
+
+def _call(L, over):
+    a = dict(c=True, S=2, K=4, H=16, D=7, trajs=TRAJS, target=TARGET, guide={}, cost=COST, active=ACTIVE, index=INDEX, blocked=BLOCKED,
+             best=BEST)
+    a.update(over)
+    cfg = L.SelectGuideCfg(a["S"], a["K"], a["H"], a["D"], 1.0, 0.5, 0.25, 2.0, 1)
+    guide = None
+    if a["guide"] is not None:
+        g = L.GuideDesc()
+        g.discs, g.planes, g.scene_rows, g.n_discs, g.n_planes, g.iters, g.lambda_, g.cap = DISCS, PLANES, 2, 3, 2, 0, float("nan"), -1.0
+        for k, v in a["guide"].items():
+            setattr(g, k, v)
+        guide = ctypes.byref(g)
+    return L.lazy("adx_traj_select_guide")(ctypes.byref(cfg) if a["c"] else None, a["trajs"], a["target"], guide, a["cost"], a["active"],
+                                           a["index"], a["blocked"], a["best"], None)
+
+
+@pytest.mark.parametrize("row", TABLE, ids=lambda row: ",".join("%s=%s" % kv for kv in row[0].items())[:60])
+def test_refusal_text(built, row):
+    """iters = 0, lambda = NaN and cap = -1 ride along in every call: a step would refuse each, the selection does not read them."""
+    assert (_call(built, row[0]), built.lib().adx_last_error().decode()) == (-1, row[1]), row[0]
+
+
+def test_python_surface_checks_the_guide_before_any_launch(built):
+    sel = TrajectorySelector(hard=True)
+    with pytest.raises(built.AdxError):
+        sel(torch.zeros(8, 16, 7), 2, None, _guide())                                # a CPU tensor: there is no CPU path
+    with pytest.raises(ValueError, match="scores against a guide"):
+        sel(torch.zeros(8, 16, 7), 2)
