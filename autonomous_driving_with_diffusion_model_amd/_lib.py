@@ -80,6 +80,12 @@ class GuideDesc(C.Structure):
                 ("lambda_", f32), ("cap", f32)]
 
 
+class FieldDesc(C.Structure):
+    """adx_guide_field ("cost guidance v2", include/adx.h)."""
+    _fields_ = [("cells", vp), ("scene_rows", i32), ("gx", i32), ("gy", i32), ("x_min", f32), ("y_min", f32), ("inv_dx", f32),
+                ("inv_dy", f32), ("weight", f32)]
+
+
 class SelectCfg(C.Structure):
     _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("w_goal", f32), ("w_smooth", f32),
                 ("w_consensus", f32)]
@@ -224,6 +230,16 @@ _LAZY_SIGS = {
                                  i32, i32, i32, vp]),
     "adx_guide_cost": (i32, [vp, C.POINTER(GuideDesc), vp, vp, i32, i32, i32, vp]),
     "adx_traj_select_guide": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), vp, vp, vp, vp, vp, vp]),
+    "adx_ddim_step_field": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                  C.POINTER(FieldDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_ddpm_step_field": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                  C.POINTER(FieldDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_dpm_step_field": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                 C.POINTER(FieldDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_guide_cost_field": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_traj_select_guide_field": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), vp, vp, vp, vp,
+                                          vp, vp]),
+    "adx_cost_field_from_occupancy": (i32, [vp, vp, i32, i32, i32, f32, f32, f32, i32, i32, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)

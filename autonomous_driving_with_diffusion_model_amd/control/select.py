@@ -94,9 +94,11 @@ class TrajectorySelector:
         active = torch.empty((scenes, K), dtype=torch.int32, device=dev)
         blocked = torch.empty((scenes,), dtype=torch.int32, device=dev)
         cfg = L.SelectGuideCfg(scenes, K, H, D, self.w_goal, self.w_smooth, self.w_consensus, self.w_guide, int(self.hard))
-        L.check(L.lazy("adx_traj_select_guide")(C.byref(cfg), trajs.data_ptr(), L.ptr(target), C.byref(g), cost.data_ptr(),
-                                                active.data_ptr(), index.data_ptr(), blocked.data_ptr(), best.data_ptr(),
-                                                L.stream_ptr(dev)), "adx_traj_select_guide")
+        f = guide.field_desc(trajs)            # a field: "cost guidance v2" in the same launch, through the _field export
+        name = "adx_traj_select_guide" if f is None else "adx_traj_select_guide_field"
+        guides = (C.byref(g),) if f is None else (C.byref(g), C.byref(f))
+        L.check(L.lazy(name)(C.byref(cfg), trajs.data_ptr(), L.ptr(target), *guides, cost.data_ptr(), active.data_ptr(),
+                             index.data_ptr(), blocked.data_ptr(), best.data_ptr(), L.stream_ptr(dev)), name)
         return Selection(best, index, cost, None, active, blocked)
 
     def __repr__(self):

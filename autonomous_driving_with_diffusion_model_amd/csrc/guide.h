@@ -1,10 +1,18 @@
-// "Cost guidance v1" (include/adx.h) on the device: the argument record of a guided launch and the ONE routine that evaluates a
-// waypoint's cost.  The step kernels and guide_cost_kernel (sched.hip) and the guided select kernel (select.hip) all call it, so
-// what a step steers by, what adx_guide_cost reports and what a selection scores are the same bits.
+// "Cost guidance v1" and "cost guidance v2" (include/adx.h) on the device: the argument record of a guided launch and the ONE routine
+// that evaluates a waypoint's cost.  The step kernels and guide_cost_kernel (sched.hip) and the guided select kernel (select.hip) all
+// call it, so what a step steers by, what adx_guide_cost reports and what a selection scores are the same bits.
 #pragma once
 #include "adx_common.h"
 
 namespace adx {
+
+// Cost guidance v2: cells [scene_rows][Gy][Gx], node [0][0] at (x_min, y_min); row r of a launch reads scene r % scene_rows.
+// cells == nullptr: no field, and nothing else of the record is read
+struct FieldArgs {
+  const float* cells;
+  int scene_rows, Gx, Gy;
+  float x_min, y_min, inv_dx, inv_dy, weight;
+};
 
 // Cost guidance v1: discs [scene_rows][M][5], planes [scene_rows][P][3]; row r of a launch reads scene r % scene_rows
 struct GuideArgs {
@@ -12,12 +20,19 @@ struct GuideArgs {
   const float* planes;
   int scene_rows, M, P, iters;
   float lambda, cap;
+  FieldArgs field;      // cost guidance v2
 };
 
-// Cost guidance v1: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs and P planes, its
-// gradient and the number of active terms; the contract's operations in the contract's order, each rounded on its own
-__device__ __forceinline__ void guide_grad(const float* discs, int M, const float* planes, int P, float hf, float x, float y,
-                                           float& J, float& gx, float& gy, int& active) {
+// The raster of row `row`'s scene, or nullptr without a field (uniform across a launch)
+__device__ __forceinline__ const float* field_cells(const FieldArgs& f, int row) {
+  return f.cells == nullptr ? nullptr : f.cells + (size_t)(row % f.scene_rows) * f.Gy * f.Gx;
+}
+
+// Cost guidance v1 / v2: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs, P planes and, when
+// `cells` (the scene's raster, field_cells) is not null, the field `f`; its gradient and the number of active terms; the contracts'
+// operations in the contracts' order, each rounded on its own.  Without a field the accumulation is v1's, bit for bit.
+__device__ __forceinline__ void guide_grad(const float* discs, int M, const float* planes, int P, const float* cells, const FieldArgs& f,
+                                           float hf, float x, float y, float& J, float& gx, float& gy, int& active) {
 #pragma clang fp contract(off)
   J = 0.f; gx = 0.f; gy = 0.f; active = 0;
   for (int i = 0; i < M; ++i) {
@@ -56,6 +71,36 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
       gx = gx + px;
       gy = gy + py;
       ++active;
+    }
+  }
+  if (cells != nullptr) {      // the field term: the bilinear interpolant of the cell the waypoint lies in, and its exact gradient
+    const float ux = x - f.x_min, vy = y - f.y_min;
+    const float u = ux * f.inv_dx, v = vy * f.inv_dy;
+    const int Gx = f.Gx, Gy = f.Gy;
+    if (u >= 0.f && u <= (float)(Gx - 1) && v >= 0.f && v <= (float)(Gy - 1)) {      // a NaN is outside
+      const int ju = (int)u, iv = (int)v;
+      const int j = ju < Gx - 2 ? ju : Gx - 2, i = iv < Gy - 2 ? iv : Gy - 2;       // 0 <= j <= Gx - 2, 0 <= i <= Gy - 2
+      const float fu = u - (float)j, fv = v - (float)i;
+      const float* c = cells + (size_t)i * Gx + j;
+      const float c00 = c[0], c01 = c[1], c10 = c[Gx], c11 = c[Gx + 1];
+      const float a = c01 - c00, b = c11 - c10;
+      const float ta = fu * a, tb = fu * b;
+      const float top = c00 + ta, bot = c10 + tb;
+      const float dv = bot - top;
+      const float tv = fv * dv;
+      const float C = top + tv;
+      if (C > 0.f) {
+        const float ba = b - a;
+        const float tu = fv * ba;
+        const float du = a + tu;
+        const float wc = f.weight * C;
+        J = J + wc;
+        const float wu = f.weight * du, wv = f.weight * dv;
+        const float sx = wu * f.inv_dx, sy = wv * f.inv_dy;
+        gx = gx + sx;
+        gy = gy + sy;
+        ++active;
+      }
     }
   }
 }

@@ -6,7 +6,8 @@
 
 namespace adx {
 
-// One DDIM / DDPM step.  The kernel is step_kernel<ddpm, ns != null, pin != null, guide != null>; z and ns may not both be given.
+// One DDIM / DDPM step.  The kernel is step_kernel<ddpm, ns != null, pin != null, guide != null || field != null>; z and ns may not
+// both be given.
 struct StepCall {
   bool ddpm = false;                  // which schedule: false DDIM, true DDPM
   const adx_step_coef* c = nullptr;
@@ -20,14 +21,15 @@ struct StepCall {
   const float* mask = nullptr;        // its mask
   const adx_pin* pin = nullptr;       // pinned waypoints v1
   const adx_guide* guide = nullptr;   // cost guidance v1
+  const adx_guide_field* field = nullptr;      // cost guidance v2: the GUIDE kernel with a raster
   float* prev = nullptr;
   float* x0 = nullptr;                // optional
   int batch = 0, horizon = 0, dim = 0;
   hipStream_t stream = nullptr;
 };
 
-// One DPM-Solver++ step.  The kernel is dpm_step_kernel<pin != null, guide != null>; without a pin the noise fields are not
-// looked at.
+// One DPM-Solver++ step.  The kernel is dpm_step_kernel<pin != null, guide != null || field != null>; without a pin the noise
+// fields are not looked at.
 struct DpmCall {
   const adx_dpm_coef* c = nullptr;
   const float* mo = nullptr;
@@ -38,6 +40,7 @@ struct DpmCall {
   int64_t row_offset = 0;
   const adx_pin* pin = nullptr;
   const adx_guide* guide = nullptr;   // cost guidance v1
+  const adx_guide_field* field = nullptr;      // cost guidance v2
   float* prev = nullptr;
   float* x0 = nullptr;                // always written
   int batch = 0, horizon = 0, dim = 0;
@@ -49,9 +52,15 @@ int dpm_run(const DpmCall& k);
 // The refusals of "cost guidance v1" that every guided launch shares, filling the kernels' GuideArgs: dim >= 2, the counts, the
 // arrays, scene_rows against `batch` rows, and `out` [on bytes] / `out2` [on2 bytes, may be null] against discs and planes.
 // `step`: a sampler step, which also reads iters, cap and lambda and refuses `inpaint`.  `what` prefixes every text.
-int guide_check(const adx_guide* g, const char* what, bool step, bool inpaint, const void* out, size_t on, const void* out2,
-                size_t on2, int batch, int dim, GuideArgs* a);
-int guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s);
+// `f`: the field of "cost guidance v2" or null; with a field `g` may be null (no discs, no planes) unless `step`.  The field's
+// refusals follow the guide's: cells, the node counts, its scene_rows against `batch` and against the guide's, the geometry, the
+// weight, and the outputs against cells.
+int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, bool step, bool inpaint, const void* out, size_t on,
+                const void* out2, size_t on2, int batch, int dim, GuideArgs* a);
+int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, float* cost, int32_t* active, int rows,
+               int horizon, int dim, hipStream_t s);
+int field_from_occupancy(const float* occ, float* cells, int scenes, int gy, int gx, float dx, float dy, float inv_m2, int ry, int rx,
+                         hipStream_t s);
 int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int batch, int horizon, int dim, hipStream_t s);
 int noise_normal(const uint32_t* state, int32_t slot, int64_t first, float* out, int64_t n, hipStream_t s);
 int noise_words(const uint32_t* state, int32_t slot, int64_t first, uint32_t* out, int64_t n, hipStream_t s);

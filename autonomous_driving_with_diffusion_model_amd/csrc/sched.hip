@@ -27,6 +27,8 @@
 // its partner element's x0, walks the waypoint down the gradient of the scene's disc and half-plane cost and, where its own element
 // moved, runs the rest of the step from the moved x0.  The gradient is one __device__ helper (guide.h), shared with guide_cost_kernel.  The
 // unguided instantiations do not read the guide fields, which sit behind the pin's: their code is what it was.
+// "Cost guidance v2" adds a cost raster to that helper and no kernel variant: the GUIDE instantiations branch on the record's
+// `cells != nullptr`, which is the same in every thread of a launch.
 //
 // Host side (sched.h): every step export fills one record, StepCall or DpmCall, and one function, step_run or dpm_run, checks it
 // and picks the kernel instantiation from what the record holds (schedule, noise state or not, pin or not, guide or not).  Every refusal of a
@@ -132,19 +134,20 @@ __device__ __forceinline__ bool guide_x0(const GuideArgs& g, const float* mo, co
   const int d = e % dim;
   if (d >= 2) return false;
   const int w = e / dim;
-  const int h = w % horizon, scene = (w / horizon) % g.scene_rows;
+  const int h = w % horizon, row = w / horizon, scene = row % g.scene_rows;
   const int ep = d == 0 ? e + 1 : e - 1;                 // the waypoint's other xy element
   float xp = x0_from(pt, sa, sb, x[ep], cfg_model_output(mo, ep, total, cfg_combine, free_scale));
   if (clip) xp = clamp_nan(xp, -clip_range, clip_range);
   float px = d == 0 ? x0 : xp, py = d == 0 ? xp : x0;
   const float* discs = g.discs + (size_t)scene * g.M * 5;
   const float* planes = g.planes + (size_t)scene * g.P * 3;
+  const float* cells = field_cells(g.field, row);      // cost guidance v2: null without a field, the same in every thread
   const float hf = (float)h;
   bool moved = false;
   for (int it = 0; it < g.iters; ++it) {
     float J, gx, gy;
     int active;
-    guide_grad(discs, g.M, planes, g.P, hf, px, py, J, gx, gy, active);
+    guide_grad(discs, g.M, planes, g.P, cells, g.field, hf, px, py, J, gx, gy, active);
     const float lx = g.lambda * gx, ly = g.lambda * gy;
     const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
     moved = moved || (d == 0 ? sx : sy) != 0.f;
@@ -273,8 +276,42 @@ static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const
 
 // the refusals of "cost guidance v1" that every guided launch, guide_cost and the guided selection share (sched.h); `step`: a
 // step, which also reads iters, cap and lambda; `out2` may be null
-int guide_check(const adx_guide* g, const char* what, bool step, bool inpaint, const void* out, size_t on, const void* out2,
-                size_t on2, int batch, int dim, GuideArgs* a) {
+static const FieldArgs kNoField = {nullptr, 1, 2, 2, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+static bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for inf and NaN
+
+// the refusals of "cost guidance v2" that are the field's own, after the guide's; `g` is the checked guide beside it
+static int field_check(const adx_guide_field* f, const adx_guide* g, const char* what, const void* out, size_t on, const void* out2,
+                       size_t on2, int batch, FieldArgs* a) {
+  ADX_REQUIRE(f->cells != nullptr, "%s: null field cells", what);
+  ADX_REQUIRE(f->gx >= ADX_FIELD_MIN_NODES && f->gx <= ADX_FIELD_MAX_NODES && f->gy >= ADX_FIELD_MIN_NODES &&
+              f->gy <= ADX_FIELD_MAX_NODES, "%s: field of %d x %d nodes (gy x gx), supported %d..%d each", what, f->gy, f->gx,
+              ADX_FIELD_MIN_NODES, ADX_FIELD_MAX_NODES);
+  ADX_REQUIRE(f->scene_rows >= 1 && batch % f->scene_rows == 0, "%s: batch %d must be a positive multiple of the field's scene_rows %d",
+              what, batch, f->scene_rows);
+  ADX_REQUIRE((g->n_discs == 0 && g->n_planes == 0) || g->scene_rows == f->scene_rows,
+              "%s: the field holds %d scenes, the guide's discs and planes %d", what, f->scene_rows, g->scene_rows);
+  ADX_REQUIRE(finite_f(f->inv_dx) && f->inv_dx > 0.f && finite_f(f->inv_dy) && f->inv_dy > 0.f,
+              "%s: field inv_dx %g and inv_dy %g must be finite and > 0", what, (double)f->inv_dx, (double)f->inv_dy);
+  ADX_REQUIRE(f->weight >= 0.f, "%s: field weight %g is negative or NaN", what, (double)f->weight);
+  ADX_REQUIRE(finite_f(f->x_min) && finite_f(f->y_min), "%s: field origin (%g, %g) is not finite", what, (double)f->x_min,
+              (double)f->y_min);
+  const size_t cn = (size_t)f->scene_rows * f->gy * f->gx * sizeof(float);
+  ADX_REQUIRE(!byte_ranges_overlap(out, on, f->cells, cn) && (out2 == nullptr || !byte_ranges_overlap(out2, on2, f->cells, cn)),
+              "%s: an output overlaps the field's cells", what);
+  a->cells = f->cells; a->scene_rows = f->scene_rows; a->Gx = f->gx; a->Gy = f->gy;
+  a->x_min = f->x_min; a->y_min = f->y_min; a->inv_dx = f->inv_dx; a->inv_dy = f->inv_dy; a->weight = f->weight;
+  return ADX_OK;
+}
+
+int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, bool step, bool inpaint, const void* out, size_t on,
+                const void* out2, size_t on2, int batch, int dim, GuideArgs* a) {
+  static const adx_guide bare = {nullptr, nullptr, 1, 0, 0, 1, 0.f, 0.f};      // a field without a guide: no discs, no planes
+  if (g == nullptr) {
+    ADX_REQUIRE(f != nullptr, "%s: null guide", what);
+    ADX_REQUIRE(!step, "%s: a field without a guide: a step reads iters, lambda and cap from the guide", what);
+    g = &bare;
+  }
   ADX_REQUIRE(dim >= 2, "%s: cost guidance moves (x, y), dim is %d", what, dim);
   ADX_REQUIRE(g->n_discs >= 0 && g->n_discs <= ADX_GUIDE_MAX_DISCS, "%s: n_discs %d outside 0..%d", what, g->n_discs,
               ADX_GUIDE_MAX_DISCS);
@@ -297,10 +334,11 @@ int guide_check(const adx_guide* g, const char* what, bool step, bool inpaint, c
               "%s: an output overlaps discs or planes", what);
   a->discs = g->discs; a->planes = g->planes; a->scene_rows = g->scene_rows; a->M = g->n_discs; a->P = g->n_planes;
   a->iters = g->iters; a->lambda = g->lambda; a->cap = g->cap;
-  return ADX_OK;
+  a->field = kNoField;
+  return f == nullptr ? ADX_OK : field_check(f, g, what, out, on, out2, on2, batch, &a->field);
 }
 
-static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f};
+static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f, kNoField};
 
 int step_run(const StepCall& k) {
   using Kernel = void (*)(const StepArgs);
@@ -311,7 +349,7 @@ int step_run(const StepCall& k) {
 #undef ADX_STEP_KERNELS
   const char* const what = "scheduler step";
   const adx_step_coef* c = k.c;
-  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr, guided = k.guide != nullptr;
+  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr, guided = k.guide != nullptr || k.field != nullptr;
   ADX_REQUIRE(k.z == nullptr || !rng, "scheduler step: a noise tensor and a noise state are both given");
   ADX_REQUIRE(c && k.mo && k.x && k.prev, "scheduler step: null tensor");
   int rc = shape_check(what, k.batch, k.horizon, k.dim);
@@ -329,7 +367,7 @@ int step_run(const StepCall& k) {
   a.guide = kNoGuide;
   if (guided) {
     const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
-    rc = guide_check(k.guide, what, true, c->inpaint != 0, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
+    rc = guide_check(k.guide, k.field, what, true, c->inpaint != 0, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
     if (rc != ADX_OK) return rc;
   }
   if (rng) {
@@ -428,15 +466,16 @@ int dpm_run(const DpmCall& k) {
     }
   }
   a.guide = kNoGuide;
-  if (k.guide != nullptr) {
+  const bool guided = k.guide != nullptr || k.field != nullptr;
+  if (guided) {
     const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
-    rc = guide_check(k.guide, what, true, false, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
+    rc = guide_check(k.guide, k.field, what, true, false, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
     if (rc != ADX_OK) return rc;
   }
   a.c = *c;
   a.mo = k.mo; a.x = k.x; a.px0 = k.px0; a.prev = k.prev; a.x0 = k.x0;
   a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
-  kernels[k.pin != nullptr][k.guide != nullptr]<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, k.stream>>>(a);
+  kernels[k.pin != nullptr][guided]<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, k.stream>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }
@@ -465,8 +504,8 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
     const float* p = a.traj + ((size_t)r * a.horizon + lane) * a.dim;
     const int scene = r % a.g.scene_rows;
     float gx, gy;
-    guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, (float)lane, p[0], p[1],
-               J, gx, gy, active);
+    guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, field_cells(a.g.field, r),
+               a.g.field, (float)lane, p[0], p[1], J, gx, gy, active);
   }
   J = wave_sum(J);
 #pragma unroll
@@ -477,15 +516,17 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
   }
 }
 
-int guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s) {
+int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, float* cost, int32_t* active, int rows,
+               int horizon, int dim, hipStream_t s) {
   const char* const what = "guide cost";
-  ADX_REQUIRE(traj != nullptr && guide != nullptr && cost != nullptr && active != nullptr, "guide cost: null traj, guide, cost or active");
+  ADX_REQUIRE(traj != nullptr && (guide != nullptr || field != nullptr) && cost != nullptr && active != nullptr,
+              "guide cost: null traj, guide, cost or active");
   ADX_REQUIRE(horizon >= 1 && horizon <= kWave, "guide cost: horizon %d outside 1..%d", horizon, kWave);
   int rc = shape_check(what, rows, horizon, dim);
   if (rc != ADX_OK) return rc;
   GuideCostArgs a;
   const size_t cn = (size_t)rows * sizeof(float);
-  rc = guide_check(guide, what, false, false, cost, cn, active, cn, rows, dim, &a.g);
+  rc = guide_check(guide, field, what, false, false, cost, cn, active, cn, rows, dim, &a.g);
   if (rc != ADX_OK) return rc;
   const size_t tn = (size_t)rows * horizon * dim * sizeof(float);
   ADX_REQUIRE(!byte_ranges_overlap(cost, cn, traj, tn) && !byte_ranges_overlap(active, cn, traj, tn) &&

@@ -19,6 +19,7 @@
 // LDS copy of xy, reduces them with the butterflies adx_guide_cost uses and takes a wave-wide vote on "every xy finite"; step 3
 // searches the free candidates alone when `hard` is set and one of them has a finite cost, and reports whether the winner is
 // blocked.  The kGuide = false instantiation reads none of the fields behind w_consensus: its code is what it was.
+// With a field ("cost guidance v2") the same routine also reads the scene's raster, from global memory: four cells per waypoint.
 #include "sched.h"
 
 namespace adx {
@@ -140,7 +141,8 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
       int act = 0;
       if (live) {
         float jx, jy;
-        guide_grad(disc_s, a.guide.M, plane_s, a.guide.P, (float)lane, px, py, J, jx, jy, act);
+        guide_grad(disc_s, a.guide.M, plane_s, a.guide.P, field_cells(a.guide.field, s), a.guide.field, (float)lane, px, py, J, jx, jy,
+                   act);
       }
       if (a.w_guide != 0.f) {
         const float violation = wave_sum(J);
@@ -240,15 +242,17 @@ int traj_select(const adx_select_cfg* c, const float* trajs, const float* target
   return ADX_OK;
 }
 
-// "Selection cost v2": v1's refusals first, then what the guide adds
-int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide, float* cost,
-                      int32_t* active, int32_t* index, int32_t* blocked, float* best, hipStream_t s) {
+// "Selection cost v2": v1's refusals first, then what the guide adds; `field` (cost guidance v2) may be null, and with a field the
+// guide may be null too (no discs, no planes)
+int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
+                      const adx_guide_field* field, float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best,
+                      hipStream_t s) {
   const char* const what = "traj select guide";
   ADX_REQUIRE(c != nullptr, "traj select: null configuration");
   int rc = select_check(c->scenes, c->candidates, c->horizon, c->dim, trajs, cost, index, best);
   if (rc != ADX_OK) return rc;
   ADX_REQUIRE(c->dim >= 2, "traj select guide: the guide scores (x, y), dim is %d", c->dim);
-  ADX_REQUIRE(guide != nullptr, "traj select guide: null guide");
+  ADX_REQUIRE(guide != nullptr || field != nullptr, "traj select guide: null guide");
   ADX_REQUIRE(active != nullptr, "traj select guide: null active");
   ADX_REQUIRE(blocked != nullptr, "traj select guide: null blocked");
   const int S = c->scenes, K = c->candidates;
@@ -256,19 +260,27 @@ int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const f
   const size_t in_bytes = (size_t)K * S * row, best_bytes = (size_t)S * row;
   const size_t sk_bytes = (size_t)S * K * sizeof(float), s_bytes = (size_t)S * sizeof(int32_t);
   SelectArgs a = {};
-  rc = guide_check(guide, what, false, false, cost, sk_bytes, active, sk_bytes, S * K, c->dim, &a.guide);
+  rc = guide_check(guide, field, what, false, false, cost, sk_bytes, active, sk_bytes, S * K, c->dim, &a.guide);
   if (rc != ADX_OK) return rc;
-  const bool bare = guide->n_discs == 0 && guide->n_planes == 0;
-  ADX_REQUIRE(guide->scene_rows == S || (guide->scene_rows == 1 && bare),
-              "traj select guide: the guide holds %d scenes, the selection %d (1 is accepted of a guide without discs and planes)",
-              guide->scene_rows, S);
-  const size_t dn = (size_t)guide->scene_rows * guide->n_discs * 5 * sizeof(float);
-  const size_t pn = (size_t)guide->scene_rows * guide->n_planes * 3 * sizeof(float);
   const void* const outs[3] = {index, blocked, best};
   const size_t out_bytes[3] = {s_bytes, s_bytes, best_bytes};
-  for (int i = 0; i < 3; ++i)
-    ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], guide->discs, dn) && !overlaps(outs[i], out_bytes[i], guide->planes, pn),
-                "traj select guide: an output overlaps discs or planes");
+  if (guide != nullptr) {
+    const bool bare = guide->n_discs == 0 && guide->n_planes == 0;
+    ADX_REQUIRE(guide->scene_rows == S || (guide->scene_rows == 1 && bare),
+                "traj select guide: the guide holds %d scenes, the selection %d (1 is accepted of a guide without discs and planes)",
+                guide->scene_rows, S);
+    const size_t dn = (size_t)guide->scene_rows * guide->n_discs * 5 * sizeof(float);
+    const size_t pn = (size_t)guide->scene_rows * guide->n_planes * 3 * sizeof(float);
+    for (int i = 0; i < 3; ++i)
+      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], guide->discs, dn) && !overlaps(outs[i], out_bytes[i], guide->planes, pn),
+                  "traj select guide: an output overlaps discs or planes");
+  }
+  if (field != nullptr) {      // candidate k of scene s is row k * S + s: only scene_rows == S makes r % scene_rows the scene
+    ADX_REQUIRE(field->scene_rows == S, "traj select guide: the field holds %d scenes, the selection %d", field->scene_rows, S);
+    const size_t cn = (size_t)field->scene_rows * field->gy * field->gx * sizeof(float);
+    for (int i = 0; i < 3; ++i)
+      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], field->cells, cn), "traj select guide: an output overlaps the field's cells");
+  }
   ADX_REQUIRE(!overlaps(active, sk_bytes, trajs, in_bytes) && !overlaps(blocked, s_bytes, trajs, in_bytes),
               "traj select guide: an output aliases trajs");
   ADX_REQUIRE(!overlaps(active, sk_bytes, cost, sk_bytes) && !overlaps(active, sk_bytes, index, s_bytes) &&

@@ -13,6 +13,11 @@ as Diffuser-style planners use it, and how the reference's classifier guidance a
              clean, Diffuser's Sigma-scaling), "constant" uses it as it is.
     cap      the largest move of one coordinate in one iteration (inf: none); `iters`: gradient iterations per step, 1..8.
 
+A guide may also hold a FIELD ("cost guidance v2"): `field=CostField(cells, origin, cell, weight)`, a cost raster [S, Gy, Gx] a
+perception stack produces (drivable area, kerbs, parked-car blobs), read bilinearly at every waypoint after the discs and planes.
+`CostField.from_occupancy` makes one from a binary occupancy raster in one launch ("cost field from occupancy v1").  A guide
+without a field is cost guidance v1, bit for bit.
+
 No reference counterpart as a caller-facing object: the reference names the idea (GUIDANCE.LOSS_LIST) and has one entry, under
 CLASSIFIER_GUIDANCE only.  Whether guided plans drive better is a property of trained weights and is not measured in this
 repository.
@@ -29,15 +34,127 @@ from . import _lib as L
 
 SCHEDULES = ("variance", "constant")
 MAX_DISCS, MAX_PLANES, MAX_ITERS = 32, 8, 8
+MIN_NODES, MAX_NODES, MAX_RADIUS = 2, 256, 16
+
+
+def _f32(v: float) -> float:
+    """The fp32 number nearest v, as a Python float."""
+    return C.c_float(v).value
+
+
+def _pair(v, name: str) -> Tuple[float, float]:
+    try:
+        a, b = v
+        return float(a), float(b)
+    except (TypeError, ValueError):
+        raise ValueError(f"CostField: {name} must be a pair of numbers, got {v!r}") from None
+
+
+def _geometry(origin, cell) -> Tuple[float, float, float, float]:
+    """(x_min, y_min, dx, dy) of a raster, or a refusal: a finite origin, finite cell sizes > 0 whose fp32 reciprocals are finite."""
+    (x_min, y_min), (dx, dy) = _pair(origin, "origin"), _pair(cell, "cell")
+    if not (math.isfinite(x_min) and math.isfinite(y_min)):
+        raise ValueError(f"CostField: origin must be finite, got ({x_min}, {y_min})")
+    for name, d in (("dx", dx), ("dy", dy)):
+        if not (math.isfinite(d) and d > 0.0 and math.isfinite(_f32(1.0 / d)) and _f32(1.0 / d) > 0.0):
+            raise ValueError(f"CostField: cell {name} must be finite and > 0 with a finite fp32 reciprocal, got {d}")
+    return x_min, y_min, dx, dy
+
+
+def _raster(t, what: str) -> None:
+    if not torch.is_tensor(t):
+        raise TypeError(f"CostField: {what} must be a tensor, got {type(t).__name__}")
+    if t.dim() != 3 or t.shape[0] < 1:
+        raise ValueError(f"CostField: {what} must be [S, Gy, Gx], got {tuple(t.shape)}")
+    if not (MIN_NODES <= t.shape[1] <= MAX_NODES and MIN_NODES <= t.shape[2] <= MAX_NODES):
+        raise ValueError(f"CostField: {what} holds {t.shape[1]} x {t.shape[2]} nodes (Gy x Gx), supported {MIN_NODES}..{MAX_NODES} each")
+    if t.dtype != torch.float32:
+        raise TypeError(f"CostField: {what} must be float32, got {t.dtype}")
+
+
+class CostField:
+    """The field of "cost guidance v2" (include/adx.h): `cells` float32 `[S, Gy, Gx]`, 2 <= Gy, Gx <= 256, node `[i][j]` at
+    `(x_min + j * dx, y_min + i * dy)` in the model's units and this tick's ego frame; `origin` = (x_min, y_min), `cell` =
+    (dx, dy), `weight` >= 0.  A waypoint inside the raster pays `weight` times the bilinear interpolant where that is positive;
+    outside the raster the field says nothing (add planes for "off the map is forbidden").  The cells are read at every step:
+    new values need no new object (and, in a GraphedSampler, no new capture); shape, geometry and weight are baked."""
+
+    def __init__(self, cells: torch.Tensor, origin=(0.0, 0.0), cell=(1.0, 1.0), weight: float = 1.0):
+        _raster(cells, "cells")
+        self.x_min, self.y_min, self.dx, self.dy = _geometry(origin, cell)
+        weight = float(weight)
+        if not weight >= 0.0:
+            raise ValueError(f"CostField: weight must be >= 0, got {weight}")
+        self.cells, self.weight = cells.contiguous(), weight
+
+    @property
+    def scenes(self) -> int:
+        return int(self.cells.shape[0])
+
+    @property
+    def device(self) -> torch.device:
+        return self.cells.device
+
+    def key(self) -> tuple:
+        """What a captured graph bakes: everything but the values of the cells."""
+        return (int(self.cells.shape[1]), int(self.cells.shape[2]), self.x_min, self.y_min, self.dx, self.dy, self.weight)
+
+    def like(self, cells: torch.Tensor) -> "CostField":
+        """The same geometry and weight over other cells."""
+        return CostField(cells, (self.x_min, self.y_min), (self.dx, self.dy), self.weight)
+
+    def desc(self, x: torch.Tensor) -> L.FieldDesc:
+        """The `adx_guide_field` of a launch on `x` [B, H, D].  The struct holds an address: keep this object alive until the
+        launch is enqueued."""
+        if L.require_gpu_f32(self.cells, "guide.field.cells").device != x.device:
+            raise ValueError(f"guide.field.cells lives on {self.cells.device}, the sample on {x.device}")
+        f = L.FieldDesc()
+        f.cells, f.scene_rows, f.gy, f.gx = self.cells.data_ptr(), self.scenes, int(self.cells.shape[1]), int(self.cells.shape[2])
+        f.x_min, f.y_min, f.inv_dx, f.inv_dy, f.weight = self.x_min, self.y_min, 1.0 / self.dx, 1.0 / self.dy, self.weight
+        return f
+
+    @staticmethod
+    def from_occupancy(occ: torch.Tensor, origin, cell, margin: float, weight: float = 1.0,
+                       out: Optional[torch.Tensor] = None) -> "CostField":
+        """A field from a binary occupancy raster `occ` float32 [S, Gy, Gx] (occupied iff > 0.5), one launch of
+        `adx_cost_field_from_occupancy` ("cost field from occupancy v1"): 0.5 on an occupied node, falling to 0 at distance
+        `margin` from the nearest one -- the disc potential of cost guidance v1 around it.  The search window is
+        ceil(margin / dx) x ceil(margin / dy) nodes, at most 16 each.  `out`: cells to write (a static buffer of a captured
+        graph); None allocates."""
+        _raster(occ, "occ")
+        x_min, y_min, dx, dy = _geometry(origin, cell)
+        margin = float(margin)
+        if not (math.isfinite(margin) and margin > 0.0):
+            raise ValueError(f"CostField.from_occupancy: margin must be finite and > 0, got {margin}")
+        rx, ry = math.ceil(margin / dx), math.ceil(margin / dy)
+        if rx > MAX_RADIUS or ry > MAX_RADIUS:
+            raise ValueError(f"CostField.from_occupancy: margin {margin} spans {ry} x {rx} cells (dy {dy}, dx {dx}), at most "
+                             f"{MAX_RADIUS} each: use a coarser raster or a smaller margin")
+        occ = L.require_gpu_f32(occ, "occ")
+        if out is None:
+            out = torch.empty_like(occ)
+        else:
+            _raster(out, "out")
+            if out.shape != occ.shape or out.device != occ.device or not out.is_contiguous():
+                raise ValueError(f"CostField.from_occupancy: out must be contiguous {tuple(occ.shape)} on {occ.device}, got "
+                                 f"{tuple(out.shape)} on {out.device}")
+        S, Gy, Gx = occ.shape
+        L.check(L.lazy("adx_cost_field_from_occupancy")(occ.data_ptr(), out.data_ptr(), S, Gy, Gx, dx, dy, 1.0 / (margin * margin), ry, rx,
+                                                        L.stream_ptr(occ.device)), "adx_cost_field_from_occupancy")
+        return CostField(out, (x_min, y_min), (dx, dy), weight)
+
+    def __repr__(self):
+        return (f"CostField(cells={tuple(self.cells.shape)}, origin=({self.x_min}, {self.y_min}), cell=({self.dx}, {self.dy}), "
+                f"weight={self.weight})")
 
 
 class Guide:
     """`discs` float32 `[S, M, 5]` and / or `planes` float32 `[S, P, 3]` on one device (None: no such constraint); `scale`,
-    `schedule`, `cap`, `iters` as the module docstring says.  The tensors are read at every step: new values need no new object
-    (and, in a GraphedSampler, no new capture)."""
+    `schedule`, `cap`, `iters` as the module docstring says; `field`: a CostField or None (keyword only).  The tensors are read
+    at every step: new values need no new object (and, in a GraphedSampler, no new capture)."""
 
     def __init__(self, discs: Optional[torch.Tensor] = None, planes: Optional[torch.Tensor] = None, scale: float = 1.0,
-                 schedule: str = "variance", cap: float = float("inf"), iters: int = 1):
+                 schedule: str = "variance", cap: float = float("inf"), iters: int = 1, *, field: Optional[CostField] = None):
         for name, t, last, most in (("discs", discs, 5, MAX_DISCS), ("planes", planes, 3, MAX_PLANES)):
             if t is None:
                 continue
@@ -54,6 +171,16 @@ class Guide:
                 raise ValueError(f"Guide: discs live on {discs.device}, planes on {planes.device}")
             if discs.shape[0] != planes.shape[0]:
                 raise ValueError(f"Guide: discs hold {discs.shape[0]} scenes, planes {planes.shape[0]}")
+        if field is not None:
+            if not isinstance(field, CostField):
+                raise TypeError(f"Guide: field must be a CostField or None, got {type(field).__name__}")
+            for name, t in (("discs", discs), ("planes", planes)):
+                if t is None or t.shape[1] == 0:      # no constraint of this kind: nothing to agree with
+                    continue
+                if t.device != field.device:
+                    raise ValueError(f"Guide: {name} live on {t.device}, the field on {field.device}")
+                if t.shape[0] != field.scenes:
+                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the field {field.scenes}")
         if schedule not in SCHEDULES:
             raise ValueError(f"Guide: schedule must be one of {SCHEDULES}, got {schedule!r}")
         scale, cap = float(scale), float(cap)
@@ -66,6 +193,7 @@ class Guide:
         self.discs = None if discs is None else discs.contiguous()
         self.planes = None if planes is None else planes.contiguous()
         self.scale, self.schedule, self.cap, self.iters = scale, schedule, cap, int(iters)
+        self.field = field
 
     # ---- shape ----
     @property
@@ -79,21 +207,31 @@ class Guide:
     @property
     def scenes(self) -> Optional[int]:
         """S of the tensors; None for a guide without any (which fits every batch)."""
-        t = self.discs if self.discs is not None else self.planes
+        t = self._first()
         return None if t is None else int(t.shape[0])
 
     @property
     def device(self) -> Optional[torch.device]:
-        t = self.discs if self.discs is not None else self.planes
+        t = self._first()
         return None if t is None else t.device
 
-    def key(self) -> tuple:
-        """What a captured graph bakes: everything but the values of discs and planes."""
-        return (self.M, self.P, self.scale, self.schedule, self.cap, self.iters)
+    def _first(self) -> Optional[torch.Tensor]:
+        """The tensor that says how many scenes the guide holds and where: discs, else planes, else the field's cells."""
+        if self.discs is not None:
+            return self.discs
+        if self.planes is not None:
+            return self.planes
+        return None if self.field is None else self.field.cells
 
-    def like(self, discs: Optional[torch.Tensor], planes: Optional[torch.Tensor]) -> "Guide":
+    def key(self) -> tuple:
+        """What a captured graph bakes: everything but the values of discs, planes and the field's cells.  Without a field the
+        6-tuple of cost guidance v1; with one, the field's key appended."""
+        key = (self.M, self.P, self.scale, self.schedule, self.cap, self.iters)
+        return key if self.field is None else key + (self.field.key(),)
+
+    def like(self, discs: Optional[torch.Tensor], planes: Optional[torch.Tensor], field: Optional[CostField] = None) -> "Guide":
         """The same settings over other tensors."""
-        return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters)
+        return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters, field=field)
 
     # ---- launches ----
     def desc(self, x: torch.Tensor, lam: float = 0.0) -> L.GuideDesc:
@@ -108,9 +246,15 @@ class Guide:
                              "of the guide's scenes")
         g = L.GuideDesc()
         g.discs, g.planes = L.ptr(self.discs), L.ptr(self.planes)
-        g.scene_rows, g.n_discs, g.n_planes = 1 if S is None else S, self.M, self.P
+        t = self.discs if self.discs is not None else self.planes
+        g.scene_rows, g.n_discs, g.n_planes = 1 if t is None else int(t.shape[0]), self.M, self.P
         g.iters, g.lambda_, g.cap = self.iters, float(lam), self.cap
         return g
+
+    def field_desc(self, x: torch.Tensor) -> Optional[L.FieldDesc]:
+        """The `adx_guide_field` of a launch on `x` ("cost guidance v2"), or None for a guide without a field: the launch then
+        goes through the `_guide` export."""
+        return None if self.field is None else self.field.desc(x)
 
     def cost(self, traj: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """What a plan still violates, one launch of `adx_guide_cost`: `(cost [rows] float32, active [rows] int32)` of `traj`
@@ -121,11 +265,16 @@ class Guide:
         rows, H, D = traj.shape
         cost = torch.empty(rows, dtype=torch.float32, device=traj.device)
         active = torch.empty(rows, dtype=torch.int32, device=traj.device)
-        L.check(L.lazy("adx_guide_cost")(traj.data_ptr(), C.byref(g), cost.data_ptr(), active.data_ptr(), rows, H, D,
-                                         L.stream_ptr(traj.device)), "adx_guide_cost")
+        f = self.field_desc(traj)
+        if f is None:
+            L.check(L.lazy("adx_guide_cost")(traj.data_ptr(), C.byref(g), cost.data_ptr(), active.data_ptr(), rows, H, D,
+                                             L.stream_ptr(traj.device)), "adx_guide_cost")
+        else:
+            L.check(L.lazy("adx_guide_cost_field")(traj.data_ptr(), C.byref(g), C.byref(f), cost.data_ptr(), active.data_ptr(), rows, H, D,
+                                                   L.stream_ptr(traj.device)), "adx_guide_cost_field")
         return cost, active
 
     def __repr__(self):
         return (f"Guide(discs={None if self.discs is None else tuple(self.discs.shape)}, "
                 f"planes={None if self.planes is None else tuple(self.planes.shape)}, scale={self.scale}, schedule={self.schedule!r}, "
-                f"cap={self.cap}, iters={self.iters})")
+                f"cap={self.cap}, iters={self.iters}" + ("" if self.field is None else f", field={self.field!r}") + ")")

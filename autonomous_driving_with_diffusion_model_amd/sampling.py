@@ -28,6 +28,10 @@ The fourth and the eighth meet in the selector: one with `w_guide` or `hard` (`T
 tick's guide and scores every candidate against the obstacles in the select launch itself ("selection cost v2" of include/adx.h):
 with `hard` a candidate that violates nothing beats every candidate that violates something, and `Selection.blocked` says per scene
 whether the chosen plan is still blocked.  A plain selector on a guided tick runs as it always did.
+A ninth reads the scene as a perception stack draws it: `guide=Guide(..., field=CostField(cells, origin, cell))` adds a cost raster
+to the guide ("cost guidance v2" of include/adx.h), read bilinearly at every waypoint by the same routine of the same kernels, so
+the steps, `Guide.cost`, the guided selector, the warm state, the controller and the graph all see it;
+`CostField.from_occupancy` makes the raster from an occupancy grid in one launch ("cost field from occupancy v1").
 """
 from __future__ import annotations
 
@@ -186,7 +190,8 @@ class TickPlan:
     # discs and planes: buffers; presence, M, P, scale, schedule, cap and iters: baked (lambda, which scale and schedule give per
     # timestep, is a by-value argument of every step node).  Every `scheduler.step` of the loop gets it (fused or not, all three
     # guidance branches) and moves its x0 inside its kernel; the K * S rows read the [S, ..] obstacles directly (row r reads scene
-    # r % S), nothing is tiled
+    # r % S), nothing is tiled.  A guide's field ("cost guidance v2"): the cells are a buffer like discs and planes; presence, (Gy, Gx),
+    # origin, cell size and weight are baked (by-value arguments of every step node) -- all of it through `Guide.key()`
     guide: Optional[Guide]
 
     def key(self) -> tuple:
@@ -242,7 +247,7 @@ def _guide_plan(cfg, guide: Optional[Guide], image, scheduler) -> Optional[Guide
     if not isinstance(guide, Guide):
         raise TypeError(f"generate_traj: `guide` must be a Guide, got {type(guide).__name__}")
     S = int(image.shape[0])
-    for name, t in (("discs", guide.discs), ("planes", guide.planes)):
+    for name, t in (("discs", guide.discs), ("planes", guide.planes), ("field.cells", None if guide.field is None else guide.field.cells)):
         if t is not None and (int(t.shape[0]) != S or t.device != image.device):
             raise ValueError(f"guide.{name} must hold {S} scenes (image.shape[0]) on {image.device}, got {tuple(t.shape)} on {t.device}")
     if int(cfg.MODEL.TRANSITION_DIM) < 2:
@@ -574,7 +579,8 @@ class GraphedSampler:
     `repaint` pin needs `noise=DeviceNoise(...)` at construction (a captured noise tensor would replay) and is refused without.
     `guide=Guide(...)` per call: cost guidance as in `generate_traj`.  `discs` and `planes` travel through static buffers; presence,
     M, P, scale, schedule, cap and iters are part of the graph key (every step node holds its lambda by value), new obstacle values
-    never capture again.
+    never capture again.  A guide's `field` travels the same way: the cells through a static buffer, its presence, shape, geometry
+    and weight through the key.
     """
 
     MAX_GRAPHS = 4
@@ -614,7 +620,8 @@ class GraphedSampler:
         g.vel = None if velocity is None else velocity.clone()
         g.pin = None if pin is None else Pin(pin.known.clone(), pin.mask.clone(), pin.mode)
         g.guide = None if guide is None else guide.like(None if guide.discs is None else guide.discs.clone(),
-                                                        None if guide.planes is None else guide.planes.clone())
+                                                        None if guide.planes is None else guide.planes.clone(),
+                                                        None if guide.field is None else guide.field.like(guide.field.cells.clone()))
         ctl = self.controller
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
@@ -726,6 +733,8 @@ class GraphedSampler:
                     g.guide.discs.copy_(guide.discs)
                 if guide.P > 0:
                     g.guide.planes.copy_(guide.planes)
+                if guide.field is not None:
+                    g.guide.field.cells.copy_(guide.field.cells)
         self._key, self._graph, self._sel, self._ctl = key, g.graph, g.sel, g.ctl
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured

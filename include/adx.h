@@ -911,6 +911,91 @@ int adx_traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, con
                           float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Cost guidance v2: cost guidance v1 plus a FIELD term -- a cost raster a perception stack produces (drivable area, kerbs,
+ * parked-car blobs), read bilinearly at every waypoint.  v1 stays as it is: adx_guide, the _guide exports and their bits; v2
+ * stands beside it as the _field exports, each the _guide export with one more argument.  The term is one more per-waypoint term
+ * of the same routine, so it reaches everything that routine reaches: the three step kernels, adx_guide_cost and the guided
+ * selection.  Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ *   cells    float32 [scene_rows][Gy][Gx], 2 <= Gx, Gy <= 256, row-major (x is the fast axis).  Row r of a launch reads scene
+ *            r % scene_rows, like discs and planes.  Node [i][j] lies at (x_min + j * dx, y_min + i * dy) in the model's own units
+ *            and this tick's ego frame.  The geometry is one per launch, not per scene, and does not move with h.
+ *   scalars  x_min, y_min, inv_dx = fp32(1 / dx), inv_dy = fp32(1 / dy) (formed on the host) and weight, by value.
+ *   term     of one waypoint (x, y), evaluated AFTER the discs and planes of v1 into the same J, gx, gy and active count (a guide
+ *            without a field therefore accumulates exactly v1's bits).  fp32, no contraction, every operation rounded on its
+ *            own, in this order:
+ *              u = (x - x_min) * inv_dx;  v = (y - y_min) * inv_dy
+ *              inside iff u >= 0 && u <= (float)(Gx-1) && v >= 0 && v <= (float)(Gy-1)            (a NaN is outside)
+ *              j = min((int)u, Gx-2);  i = min((int)v, Gy-2);  fu = u - (float)j;  fv = v - (float)i
+ *              c00 = cells[i][j];  c01 = cells[i][j+1];  c10 = cells[i+1][j];  c11 = cells[i+1][j+1]
+ *              a = c01 - c00;  b = c11 - c10;  top = c00 + fu * a;  bot = c10 + fu * b;  dv = bot - top
+ *              C = top + fv * dv;  active iff inside && C > 0
+ *              du = a + fv * (b - a)
+ *              J = J + weight * C;  gx = gx + (weight * du) * inv_dx;  gy = gy + (weight * dv) * inv_dy
+ *            (du, dv) / (dx, dy) is the exact gradient of the bilinear interpolant inside a cell.  Outside the raster the term is
+ *            inactive: a caller who wants "off the map is forbidden" adds planes.  Negative and zero cells are legal; the term is
+ *            inactive wherever the interpolant is not positive.  An active field term counts 1 in `active`.
+ *   the rest everything else is v1, word for word: the per-step loop (lambda, cap, clip, moved), the partner recomputation, the
+ *            order of the step, the wave butterfly of the cost, and the selection's violation, active, free and blocked.
+ *   guide    the adx_guide beside the field may be NULL for adx_guide_cost_field and adx_traj_select_guide_field: no discs and no
+ *            planes.  A step reads iters, lambda and cap from it: the step exports refuse a field without a guide.  A guide
+ *            without tensors (n_discs == n_planes == 0) fits any field; one with tensors must hold the field's scene_rows.
+ *            adx_traj_select_guide_field: the field's scene_rows equals `scenes`.
+ *   NULL     a NULL field is exactly the _guide export.
+ *
+ * ADX_ERR_INVALID before any GPU work, each with its own text: NULL cells; gx or gy outside 2..256; scene_rows < 1 or not
+ * dividing batch; scene_rows disagreeing with the guide's when both hold tensors; inv_dx or inv_dy not finite or not > 0; weight
+ * NaN or negative; x_min or y_min not finite; an output overlapping cells; a step with a field and no guide; and whatever the
+ * _guide export refuses.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_FIELD_MIN_NODES 2
+#define ADX_FIELD_MAX_NODES 256
+typedef struct adx_guide_field {
+  const float* cells;          /* [scene_rows][gy][gx] */
+  int32_t scene_rows, gx, gy;
+  float x_min, y_min, inv_dx, inv_dy, weight;
+} adx_guide_field;
+int adx_ddim_step_field(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        const adx_guide_field* field, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
+                        adx_stream s);
+int adx_ddpm_step_field(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        const adx_guide_field* field, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
+                        adx_stream s);
+int adx_dpm_step_field(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                       const adx_guide_field* field, float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim,
+                       adx_stream s);
+int adx_guide_cost_field(const float* traj, const adx_guide* guide, const adx_guide_field* field, float* cost, int32_t* active,
+                         int32_t rows, int32_t horizon, int32_t dim, adx_stream s);
+int adx_traj_select_guide_field(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
+                                const adx_guide_field* field, float* cost, int32_t* active, int32_t* index, int32_t* blocked,
+                                float* best, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
+ * Cost field from occupancy v1: a cost raster for cost guidance v2 from a binary occupancy raster, one launch.  The value at a
+ * node is the disc potential of cost guidance v1 around the NEAREST occupied node: 0.5 on an obstacle, falling to 0 at distance
+ * `margin`.  No square root.  Capturable: no allocation, no synchronisation, no host decision.  Callers and fixtures depend on
+ * this definition -- a change is a new version, never an edit.
+ *
+ *   occ      float32 [scenes][gy][gx], 2 <= gx, gy <= 256, 1 <= scenes <= 65535.  A node is occupied iff occ > 0.5f (a NaN is
+ *            free).
+ *   d2       per node (i, j): the minimum over the occupied nodes (i + di, j + dj) of the raster with |di| <= ry, |dj| <= rx
+ *            (0 <= rx, ry <= 16) of  ((float)dj * dx) * ((float)dj * dx) + ((float)di * dy) * ((float)di * dy),  fp32, each
+ *            product and the sum rounded on its own.  A minimum is exact: the search order is free.
+ *   cells    phi = 1 - d2 * inv_m2;  cells[i][j] = phi > 0 ? (phi * phi) / 2 : 0;  no occupied node in the window: 0.
+ *            inv_m2 = fp32(1 / margin^2), formed on the host.  Nodes further than the window see nothing: a caller picks
+ *            rx >= margin / dx and ry >= margin / dy.
+ *
+ * ADX_ERR_INVALID before any GPU work: a NULL pointer; scenes, gx or gy out of range; rx or ry outside 0..16; dx, dy or inv_m2
+ * not finite or not > 0; cells overlapping occ.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_FIELD_MAX_RADIUS 16
+int adx_cost_field_from_occupancy(const float* occ, float* cells, int32_t scenes, int32_t gy, int32_t gx, float dx, float dy,
+                                  float inv_m2, int32_t ry, int32_t rx, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Control v1: waypoints -> (throttle, steer, brake) on the device, the step after the sampling loop in the reference's agents
  * (control/controller.py:29-76 `control_pid`, control/pid.py, `post_process_control` of interact.py:218-229 and
  * e2e_driving/diffusion_agent.py:268-277).  One launch per tick for all scenes, no host decision; the PID windows live in

@@ -6,11 +6,18 @@ one scene (H = 16) and at 64 scenes (H = 32):
     m4p2i1       guide=Guide(discs [S, 4, 5], planes [S, 2, 3], iters=1): the GUIDE variant of every step, a light scene
     m32p8i8      guide=Guide(discs [S, 32, 5], planes [S, 8, 3], iters=8): the contract's largest scene, 320 constraint
                  evaluations per xy element and step
+    f64i1        guide=Guide(field=CostField([S, 64, 64]), iters=1): "cost guidance v2", a cost raster alone -- four cells read per
+                 xy element, iteration and step
+    m4p2i1.f256  the m4p2i1 guide with a [S, 256, 256] field beside it (64 scenes: 16 MiB of cells, read where the waypoints are)
+    m4p2i8.f256  the same at iters=8
+    m4p2i1.occ   m4p2i1.f256 with `CostField.from_occupancy` (256 x 256, window radius 16: "cost field from occupancy v1") run on
+                 every tick before the replay, into the buffer the tick's field then reads: one more launch per tick
 
 The obstacles lie where a clamped trajectory meets them (centres in [-0.5, 0.5]^2, radii 0.2 .. 0.5, no empty slot), and their
 values travel through the sampler's static buffers on every tick.  The arms alternate in one process, `--rounds` times, each
 window timed with device events around >= `--ticks` ticks (at least `--seconds` of them).  Nobody has measured the guided step
-before, so there is no expectation to hold it against; the step stays one launch of a few hundred to a few tens of thousands of
+before, so there is no expectation to hold it against (the field arms have none either: their ratios over `none` and over
+`m4p2i1` are recorded); the step stays one launch of a few hundred to a few tens of thousands of
 threads, two in seven of which loop over the constraints.  Prints a table and one JSON line; `--json PATH` also writes the
 record.  This measures time only: what a guide does to a trained model's driving quality is not something the repository can
 measure (it has no trained weights).
@@ -27,7 +34,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from autonomous_driving_with_diffusion_model_amd import DeviceNoise, Guide  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd import CostField, DeviceNoise, Guide  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd import scheduler as S  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd.config import create_cfg  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd.modeling import build_model  # noqa: E402
@@ -37,7 +44,11 @@ from autonomous_driving_with_diffusion_model_amd.utils import procedural as P  #
 SCHED_KW = dict(num_train_timesteps=100, prediction_type="sample", beta_schedule="squaredcos_cap_v2", beta_start=1e-4, beta_end=0.02)
 IMG = (256, 900)
 SIZES = ((1, 16), (64, 32))            # (scenes, horizon)
-ARMS = (("none", None), ("m4p2i1", (4, 2, 1)), ("m32p8i8", (32, 8, 8)))      # (M, P, iters)
+# (name, (M, P, iters) or None, G of a [S, G, G] field or None, from_occupancy on every tick)
+ARMS = (("none", None, None, False), ("m4p2i1", (4, 2, 1), None, False), ("m32p8i8", (32, 8, 8), None, False),
+        ("f64i1", (0, 0, 1), 64, False), ("m4p2i1.f256", (4, 2, 1), 256, False), ("m4p2i8.f256", (4, 2, 8), 256, False),
+        ("m4p2i1.occ", (4, 2, 1), 256, True))
+MARGIN = 0.125                         # of the occupancy arm: 16 cells of 2 / 256
 
 
 def make_cfg(steps, horizon):
@@ -48,7 +59,19 @@ def make_cfg(steps, horizon):
     return cfg
 
 
-def obstacles(scenes, M, P, iters, dev):
+def occupancy(scenes, G, dev):
+    """About one node in 200 occupied, over [-1, 1]^2."""
+    g = torch.Generator().manual_seed(13)
+    return (torch.rand(scenes, G, G, generator=g) < 0.005).float().to(dev)
+
+
+def field(scenes, G, dev):
+    """A [scenes, G, G] field over [-1, 1]^2 (where a clamped trajectory lives), made from `occupancy` with margin 16 cells."""
+    cell = 2.0 / (G - 1)
+    return CostField.from_occupancy(occupancy(scenes, G, dev), (-1.0, -1.0), (cell, cell), 16 * cell)
+
+
+def obstacles(scenes, M, P, iters, dev, field=None):
     g = torch.Generator().manual_seed(11)
     discs = torch.zeros(scenes, M, 5)
     discs[..., :2] = torch.rand(scenes, M, 2, generator=g) - 0.5
@@ -57,10 +80,11 @@ def obstacles(scenes, M, P, iters, dev):
     planes = torch.zeros(scenes, P, 3)
     planes[..., :2] = torch.rand(scenes, P, 2, generator=g) * 2 - 1
     planes[..., 2] = torch.rand(scenes, P, generator=g) * 0.5
-    return Guide(discs.to(dev), planes.to(dev), scale=0.2, schedule="variance", cap=0.1, iters=iters)
+    return Guide(discs.to(dev) if M else None, planes.to(dev) if P else None, scale=0.2, schedule="variance", cap=0.1, iters=iters,
+                 field=field)
 
 
-def arms(dev, n):
+def arms(dev, n, only=None):
     fns, meta = {}, {}
     for scenes, horizon in SIZES:
         cfg = make_cfg(n, horizon)
@@ -70,12 +94,22 @@ def arms(dev, n):
         model = model.to(dev).eval()
         d = {k: v.to(dev) for k, v in P.synthetic_batch(scenes, horizon, image_hw=IMG, seed=3).items()}
         img, tgt = d["imgs"], d["target"]
-        for arm, mpi in ARMS:
+        for arm, mpi, G, per_tick in ARMS:
+            if only is not None and arm not in only:
+                continue
             sch = S.GuidanceDDIMScheduler(cfg=cfg, thresholding=True, **SCHED_KW)
             gs = GraphedSampler(model, sch, cfg, noise=DeviceNoise(7, dev))
-            guide = None if mpi is None else obstacles(scenes, *mpi, dev)
+            guide = None if mpi is None else obstacles(scenes, *mpi, dev, None if G is None else field(scenes, G, dev))
             name = f"s{scenes}.{arm}"
-            fns[name] = (lambda gs=gs, img=img, tgt=tgt, guide=guide: gs(img, tgt, guide=guide))
+            if per_tick:
+                occ, f = occupancy(scenes, G, dev), guide.field
+
+                def tick(gs=gs, img=img, tgt=tgt, guide=guide, occ=occ, f=f):
+                    CostField.from_occupancy(occ, (f.x_min, f.y_min), (f.dx, f.dy), 16 * f.dx, out=f.cells)
+                    return gs(img, tgt, guide=guide)
+                fns[name] = tick
+            else:
+                fns[name] = (lambda gs=gs, img=img, tgt=tgt, guide=guide: gs(img, tgt, guide=guide))
             meta[name] = (scenes, horizon, arm)
     return fns, meta
 
@@ -97,11 +131,12 @@ def main():
     ap.add_argument("--ticks", type=int, default=50, help="least number of ticks per window (x rounds = ticks per arm)")
     ap.add_argument("--seconds", type=float, default=0.5, help="least length of a window")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--arms", default=None, help="comma-separated arm names (default: all); the ratios need `none` and `m4p2i1` among them")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     n = a.steps
     with torch.no_grad():
-        fns, meta = arms(dev, n)
+        fns, meta = arms(dev, n, None if a.arms is None else a.arms.split(","))
         ticks = {}
         for fn in fns.values():                 # warm every arm: the capture, then replays ...
             for _ in range(3):
@@ -116,7 +151,8 @@ def main():
             for k, fn in fns.items():
                 ms[k].append(timed(fn, ticks[k]))
     record = {"device": torch.cuda.get_device_name(0), "image": list(IMG), "guidance": "FREE_GUIDANCE", "sampler": "ddim",
-              "sample_steps": n, "rounds": a.rounds, "guide": "scale 0.2, variance schedule, cap 0.1", "arms": {}, "guided_over_none": {}}
+              "sample_steps": n, "rounds": a.rounds, "guide": "scale 0.2, variance schedule, cap 0.1", "arms": {}, "guided_over_none": {},
+              "guided_over_m4p2i1": {}}
     for k in fns:
         scenes, horizon, mode = meta[k]
         med = statistics.median(ms[k])
@@ -124,14 +160,17 @@ def main():
                              "ms_per_tick": [round(v, 4) for v in ms[k]], "median_ms": round(med, 4), "min_ms": round(min(ms[k]), 4),
                              "max_ms": round(max(ms[k]), 4), "spread_pct": round(100 * (max(ms[k]) - min(ms[k])) / med, 2)}
     for k, v in record["arms"].items():
-        if v["guide"] != "none":
-            record["guided_over_none"][k] = round(v["median_ms"] / record["arms"][f"s{v['scenes']}.none"]["median_ms"], 4)
+        for over, base in (("guided_over_none", "none"), ("guided_over_m4p2i1", "m4p2i1")):
+            ref = record["arms"].get(f"s{v['scenes']}.{base}")
+            if v["guide"] != "none" and ref is not None:
+                record[over][k] = round(v["median_ms"] / ref["median_ms"], 4)
     print(f"FREE guidance, DDIM, {IMG[0]}x{IMG[1]} frame, n = {n}, graph ticks ({a.rounds} alternating rounds)", file=sys.stderr)
-    print(f"{'arm':<14}{'scenes':>7}{'H':>4}{'median ms':>11}{'min':>9}{'max':>9}{'spread %':>10}{'/ none':>9}{'ticks':>8}", file=sys.stderr)
+    print(f"{'arm':<14}{'scenes':>7}{'H':>4}{'median ms':>11}{'min':>9}{'max':>9}{'spread %':>10}{'/ none':>9}{'/ m4p2i1':>10}{'ticks':>8}", file=sys.stderr)
     for k, v in record["arms"].items():
-        r = record["guided_over_none"].get(k)
+        r, r1 = record["guided_over_none"].get(k), record["guided_over_m4p2i1"].get(k)
         print(f"{k:<14}{v['scenes']:>7}{v['horizon']:>4}{v['median_ms']:>11.3f}{v['min_ms']:>9.3f}{v['max_ms']:>9.3f}"
-              f"{v['spread_pct']:>10.2f}{('' if r is None else format(r, '.4f')):>9}{v['ticks']:>8}", file=sys.stderr)
+              f"{v['spread_pct']:>10.2f}{('' if r is None else format(r, '.4f')):>9}{('' if r1 is None else format(r1, '.4f')):>10}"
+              f"{v['ticks']:>8}", file=sys.stderr)
     print(json.dumps(record))
     if a.json:
         with open(a.json, "w") as f:
