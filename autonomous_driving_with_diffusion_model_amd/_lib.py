@@ -86,6 +86,11 @@ class FieldDesc(C.Structure):
                 ("inv_dy", f32), ("weight", f32)]
 
 
+class MotionDesc(C.Structure):
+    """adx_guide_motion ("cost guidance v3", include/adx.h)."""
+    _fields_ = [("limits", vp), ("scene_rows", i32), ("w_speed", f32), ("w_accel", f32)]
+
+
 class SelectCfg(C.Structure):
     _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("w_goal", f32), ("w_smooth", f32),
                 ("w_consensus", f32)]
@@ -240,6 +245,15 @@ _LAZY_SIGS = {
     "adx_traj_select_guide_field": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), vp, vp, vp, vp,
                                           vp, vp]),
     "adx_cost_field_from_occupancy": (i32, [vp, vp, i32, i32, i32, f32, f32, f32, i32, i32, vp]),
+    "adx_ddim_step_motion": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                   C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_ddpm_step_motion": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                   C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_dpm_step_motion": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                  C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_guide_cost_motion": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_traj_select_guide_motion": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
+                                           C.POINTER(MotionDesc), vp, vp, vp, vp, vp, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)

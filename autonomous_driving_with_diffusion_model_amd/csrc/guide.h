@@ -1,6 +1,8 @@
 // "Cost guidance v1" and "cost guidance v2" (include/adx.h) on the device: the argument record of a guided launch and the ONE routine
 // that evaluates a waypoint's cost.  The step kernels and guide_cost_kernel (sched.hip) and the guided select kernel (select.hip) all
 // call it, so what a step steers by, what adx_guide_cost reports and what a selection scores are the same bits.
+// "Cost guidance v3" adds motion_grad beside it: a waypoint's share of the terms that couple it to its neighbours, for the row-wise
+// step kernels, guide_cost_kernel<true> and traj_select_kernel<true, true>.
 #pragma once
 #include "adx_common.h"
 
@@ -101,6 +103,102 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
         gy = gy + sy;
         ++active;
       }
+    }
+  }
+}
+
+// Cost guidance v3: limits [scene_rows][2] = (s_max, a_max); row r of a launch reads scene r % scene_rows.
+// limits == nullptr: no motion limits, and nothing else of the record is read
+struct MotionArgs {
+  const float* limits;
+  int scene_rows;
+  float w_speed, w_accel;
+};
+
+// (S2, A2) of row `row`'s scene: the squares of its limits, each one rounded product
+__device__ __forceinline__ void motion_limits(const MotionArgs& m, int row, float& S2, float& A2) {
+#pragma clang fp contract(off)
+  const float* q = m.limits + (size_t)(row % m.scene_rows) * 2;
+  const float s = q[0], a = q[1];
+  S2 = s * s;
+  A2 = a * a;
+}
+
+// The segment from a to b against S2: e = b - a and k = w * (2 * phi) where phi = |e|^2 - S2 > 0, else inactive (a NaN too)
+__device__ __forceinline__ bool motion_segment(float ax, float ay, float bx, float by, float S2, float w, float& ex, float& ey, float& phi,
+                                               float& k) {
+#pragma clang fp contract(off)
+  ex = bx - ax; ey = by - ay;
+  const float xx = ex * ex, yy = ey * ey;
+  const float s2 = xx + yy;
+  phi = s2 - S2;
+  if (!(phi > 0.f)) return false;
+  const float p2 = 2.0f * phi;
+  k = w * p2;
+  return true;
+}
+
+// The second difference at b between a and c against A2: c = (c - b) - (b - a) and q = w * (2 * psi) where psi = |c|^2 - A2 > 0
+__device__ __forceinline__ bool motion_curvature(float ax, float ay, float bx, float by, float cx_, float cy_, float A2, float w, float& cx,
+                                                 float& cy, float& psi, float& q) {
+#pragma clang fp contract(off)
+  const float fx = cx_ - bx, fy = cy_ - by;
+  const float bx_ = bx - ax, by_ = by - ay;
+  cx = fx - bx_; cy = fy - by_;
+  const float xx = cx * cx, yy = cy * cy;
+  const float a2 = xx + yy;
+  psi = a2 - A2;
+  if (!(psi > 0.f)) return false;
+  const float p2 = 2.0f * psi;
+  q = w * p2;
+  return true;
+}
+
+// Cost guidance v3: waypoint h's share of the segment and curvature terms of a row of H waypoints, added to J, gx, gy and active
+// AFTER guide_grad filled them.  (x[j], y[j]) = p_{h-2+j}, j = 0..4; a point outside 0..H-1 is never read into a result (its term
+// does not exist).  The contract's operations in the contract's order, each rounded on its own; an inactive or absent term adds
+// nothing, not even a zero.  The neighbours are the caller's to bring: a shuffle in the row-wise kernels, LDS in the selection.
+__device__ __forceinline__ void motion_grad(const float* x, const float* y, int h, int H, float S2, float A2, float w_speed, float w_accel,
+                                            float& J, float& gx, float& gy, int& active) {
+#pragma clang fp contract(off)
+  float ex, ey, phi, k, cx, cy, psi, q;
+  const bool anchor = h == 0;      // the ego's present pose takes no motion gradient
+  if (w_speed != 0.f) {
+    if (h >= 1 && motion_segment(x[1], y[1], x[2], y[2], S2, w_speed, ex, ey, phi, k)) {        // segment h - 1: p_h is its far end
+      const float pp = phi * phi;
+      const float wp = w_speed * pp;
+      J = J + wp / 2.0f;
+      ++active;
+      const float kx = k * ex, ky = k * ey;
+      gx = gx + kx;
+      gy = gy + ky;
+    }
+    if (!anchor && h <= H - 2 && motion_segment(x[2], y[2], x[3], y[3], S2, w_speed, ex, ey, phi, k)) {      // segment h: its near end
+      const float kx = k * ex, ky = k * ey;
+      gx = gx - kx;
+      gy = gy - ky;
+    }
+  }
+  if (w_accel != 0.f) {
+    if (h >= 2 && motion_curvature(x[0], y[0], x[1], y[1], x[2], y[2], A2, w_accel, cx, cy, psi, q)) {      // curvature h - 1
+      const float qx = q * cx, qy = q * cy;
+      gx = gx + qx;
+      gy = gy + qy;
+    }
+    if (h >= 1 && h <= H - 2 && motion_curvature(x[1], y[1], x[2], y[2], x[3], y[3], A2, w_accel, cx, cy, psi, q)) {      // curvature h
+      const float pp = psi * psi;
+      const float wp = w_accel * pp;
+      J = J + wp / 2.0f;
+      ++active;
+      const float q2 = 2.0f * q;
+      const float qx = q2 * cx, qy = q2 * cy;
+      gx = gx - qx;
+      gy = gy - qy;
+    }
+    if (!anchor && h <= H - 3 && motion_curvature(x[2], y[2], x[3], y[3], x[4], y[4], A2, w_accel, cx, cy, psi, q)) {      // curvature h + 1
+      const float qx = q * cx, qy = q * cy;
+      gx = gx + qx;
+      gy = gy + qy;
     }
   }
 }

@@ -29,6 +29,9 @@
 // unguided instantiations do not read the guide fields, which sit behind the pin's: their code is what it was.
 // "Cost guidance v2" adds a cost raster to that helper and no kernel variant: the GUIDE instantiations branch on the record's
 // `cells != nullptr`, which is the same in every thread of a launch.
+// "Cost guidance v3" (motion limits) couples neighbouring waypoints and gets kernels of its own, step_rows_kernel and
+// dpm_step_rows_kernel: a wave per row, the iterate exchanged by shuffles.  The body of one element's step is text both kernel
+// shapes include (sched_step_body.h, sched_dpm_body.h), so the element-wise instantiations compile from the tokens they had.
 //
 // Host side (sched.h): every step export fills one record, StepCall or DpmCall, and one function, step_run or dpm_run, checks it
 // and picks the kernel instantiation from what the record holds (schedule, noise state or not, pin or not, guide or not).  Every refusal of a
@@ -167,65 +170,96 @@ __global__ void __launch_bounds__(256) step_kernel(const StepArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= a.total) return;
+  constexpr bool ROWS = false, row_moved = false;
+  constexpr float row_x0 = 0.f;
+#include "sched_step_body.h"
+}
+
+// "Cost guidance v3" (include/adx.h): the motion terms couple a waypoint to its neighbours, so the iterations cannot be local to
+// an element.  The row-wise kernels give a row to a wave: lane = waypoint, four rows per workgroup, nothing shared between the
+// waves (no LDS, no atomics, no barrier).  A lane owns both xy elements of its waypoint, so there is no partner recomputation; the
+// iterate travels to the neighbours through wave shuffles after every move (Jacobi), and all 64 lanes stay alive through them:
+// lanes h >= H hold zeros, take no step and touch no memory.  Every trip count is the launch's.
+constexpr int kRowWaves = 4;
+
+// The clipped pred_original_sample of one element: where a row's iterations start
+__device__ __forceinline__ float x0_clipped(int pt, float sa, float sb, float xs, float m, int clip, float clip_range) {
+  const float x0 = x0_from(pt, sa, sb, xs, m);
+  return clip ? clamp_nan(x0, -clip_range, clip_range) : x0;
+}
+
+// The iterations of one row: (px, py) is the lane's clipped x0 on entry and the iterate on exit, (mx, my) whether a component
+// moved.  `live`: lane < H.
+__device__ __forceinline__ void guide_rows(const GuideArgs& g, const MotionArgs& mo, int row, int lane, int H, bool live, int clip,
+                                           float clip_range, float& px, float& py, bool& mx, bool& my) {
+#pragma clang fp contract(off)
+  const int scene = row % g.scene_rows;
+  const float* discs = g.discs + (size_t)scene * g.M * 5;
+  const float* planes = g.planes + (size_t)scene * g.P * 3;
+  const float* cells = field_cells(g.field, row);
+  float S2, A2;
+  motion_limits(mo, row, S2, A2);
+  const float hf = (float)lane;
+  mx = false; my = false;
+  for (int it = 0; it < g.iters; ++it) {
+    float nx[5], ny[5];
+    nx[0] = __shfl_up(px, 2, kWave); ny[0] = __shfl_up(py, 2, kWave);
+    nx[1] = __shfl_up(px, 1, kWave); ny[1] = __shfl_up(py, 1, kWave);
+    nx[2] = px; ny[2] = py;
+    nx[3] = __shfl_down(px, 1, kWave); ny[3] = __shfl_down(py, 1, kWave);
+    nx[4] = __shfl_down(px, 2, kWave); ny[4] = __shfl_down(py, 2, kWave);
+    if (live) {
+      float J, gx, gy;
+      int active;
+      guide_grad(discs, g.M, planes, g.P, cells, g.field, hf, px, py, J, gx, gy, active);
+      motion_grad(nx, ny, lane, H, S2, A2, mo.w_speed, mo.w_accel, J, gx, gy, active);
+      const float lx = g.lambda * gx, ly = g.lambda * gy;
+      const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
+      mx = mx || sx != 0.f;
+      my = my || sy != 0.f;
+      px = px - sx;
+      py = py - sy;
+      if (clip) {
+        px = clamp_nan(px, -clip_range, clip_range);
+        py = clamp_nan(py, -clip_range, clip_range);
+      }
+    }
+  }
+}
+
+struct StepRowsArgs {
+  StepArgs s;
+  MotionArgs motion;      // cost guidance v3
+};
+
+template <bool DDPM, bool RNG, bool PIN>
+__global__ void __launch_bounds__(kRowWaves * kWave) step_rows_kernel(const StepRowsArgs k) {
+#pragma clang fp contract(off)
+  const StepArgs& a = k.s;
   const adx_step_coef& c = a.c;
-  const float m = cfg_model_output(a.mo, e, a.total, c.cfg_combine, c.free_scale);
-  const float xs = a.x[e];
-  const float sa = c.sqrt_alpha_t, sb = c.sqrt_beta_t;
-  float x0 = x0_from(c.prediction_type, sa, sb, xs, m);
-  float eps;
-  if (c.prediction_type == ADX_PRED_EPSILON) {
-    eps = m;
-  } else if (c.prediction_type == ADX_PRED_SAMPLE) {
-    const float p = sa * x0;
-    eps = (xs - p) / sb;
-  } else {
-    const float p2 = sa * m, q2 = sb * xs;
-    eps = p2 + q2;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int H = a.horizon, D = a.dim;
+  const int row = blockIdx.x * kRowWaves + (threadIdx.x >> 6);
+  if (row >= a.total / (H * D)) return;              // whole waves leave: the shuffles always see all 64 lanes
+  const bool live = lane < H;
+  const int e0 = (row * H + lane) * D;               // the waypoint's x element; live lanes only read or write there
+  float px = 0.f, py = 0.f;
+  if (live) {
+    px = x0_clipped(c.prediction_type, c.sqrt_alpha_t, c.sqrt_beta_t, a.x[e0], cfg_model_output(a.mo, e0, a.total, c.cfg_combine, c.free_scale),
+                    c.clip, c.clip_range);
+    py = x0_clipped(c.prediction_type, c.sqrt_alpha_t, c.sqrt_beta_t, a.x[e0 + 1],
+                    cfg_model_output(a.mo, e0 + 1, a.total, c.cfg_combine, c.free_scale), c.clip, c.clip_range);
   }
-  if (c.clip) x0 = clamp_nan(x0, -c.clip_range, c.clip_range);
-  bool moved = false;
-  if (GUIDE)
-    moved = guide_x0(a.guide, a.mo, a.x, e, a.total, a.horizon, a.dim, c.prediction_type, sa, sb, c.clip, c.clip_range, c.cfg_combine,
-                     c.free_scale, x0);
-  const bool known = c.inpaint && a.tgt != nullptr && a.mask != nullptr;
-  float zn;
-  if (RNG) {
-    // the element's index in the LOGICAL tensor, not in this launch: a shard of rows draws what the full batch draws there
-    const bool need = c.add_noise || (known && c.known_noise) || (PIN && a.pin.known_noise);
-    zn = need ? noise_normal_at(a.ns, a.slot, a.base + (uint64_t)e) : 0.f;
-  } else {
-    zn = (a.z != nullptr) ? a.z[e] : 0.f;
+  bool mx, my;
+  guide_rows(a.guide, k.motion, row, lane, H, live, c.clip, c.clip_range, px, py, mx, my);
+  if (!live) return;                                  // no shuffle below this line
+  constexpr bool GUIDE = false, ROWS = true;
+  for (int d = 0; d < D; ++d) {                       // the waypoint's D elements, each through the element kernel's own body
+    const int e = e0 + d;
+    const float row_x0 = d == 0 ? px : py;
+    const bool row_moved = d == 0 ? mx : (d == 1 ? my : false);
+#include "sched_step_body.h"
   }
-  float prev;
-  if (!DDPM) {
-    if (c.use_clipped_model_output || (GUIDE && moved)) {      // a moved x0 re-derives its eps
-      const float p = sa * x0;
-      eps = (xs - p) / sb;
-    }
-    const float dir = c.c_dir * eps;
-    const float p = c.c_x0 * x0;
-    prev = p + dir;
-    if (c.inpaint) {
-      prev = prev + c.c_const;
-      if (known) prev = repaint_blend(a.tgt, a.mask, e, c.c_known, c.c_known_noise, c.known_noise, zn, prev);
-    }
-    if (c.add_noise) {
-      const float nz = c.c_noise * zn;
-      prev = prev + nz;
-    }
-  } else {
-    const float p = c.c_x0 * x0, q = c.c_x * xs;
-    prev = p + q;
-    if (c.add_noise) {
-      const float nz = c.c_noise * zn;
-      prev = prev + nz;
-    }
-    if (known) prev = repaint_blend(a.tgt, a.mask, e, c.c_known, c.c_known_noise, c.known_noise, zn, prev);
-  }
-  if (PIN) prev = pin_blend(a.pin, e, zn, prev);      // the step's own z: no second draw
-  if (c.zero_first && first_pose(e, a.horizon, a.dim)) prev = 0.f;
-  a.prev[e] = prev;
-  if (a.x0 != nullptr) a.x0[e] = x0;          // as computed (guided where it moved): never pinned
 }
 
 // e >> 2 is the stream's 32-bit counter word: logical elements live in [0, 2^34)
@@ -340,6 +374,35 @@ int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, 
 
 static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f, kNoField};
 
+// the refusals of "cost guidance v3" that are the motion limits' own, after guide_check (sched.h)
+int motion_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, const void* out, size_t on,
+                 const void* out2, size_t on2, int batch, int horizon, MotionArgs* a) {
+  ADX_REQUIRE(m->limits != nullptr, "%s: null motion limits", what);
+  ADX_REQUIRE(m->scene_rows >= 1 && batch % m->scene_rows == 0, "%s: batch %d must be a positive multiple of the limits' scene_rows %d",
+              what, batch, m->scene_rows);
+  ADX_REQUIRE(g == nullptr || (g->n_discs == 0 && g->n_planes == 0) || g->scene_rows == m->scene_rows,
+              "%s: the limits hold %d scenes, the guide's discs and planes %d", what, m->scene_rows, g == nullptr ? 0 : g->scene_rows);
+  ADX_REQUIRE(f == nullptr || f->scene_rows == m->scene_rows, "%s: the limits hold %d scenes, the field %d", what, m->scene_rows,
+              f == nullptr ? 0 : f->scene_rows);
+  ADX_REQUIRE(m->w_speed >= 0.f, "%s: motion w_speed %g is negative or NaN", what, (double)m->w_speed);
+  ADX_REQUIRE(m->w_accel >= 0.f, "%s: motion w_accel %g is negative or NaN", what, (double)m->w_accel);
+  ADX_REQUIRE(horizon <= kWave, "%s: motion limits give a row to a wave: horizon %d, supported 1..%d", what, horizon, kWave);
+  const size_t ln = (size_t)m->scene_rows * 2 * sizeof(float);
+  ADX_REQUIRE(!byte_ranges_overlap(out, on, m->limits, ln) && (out2 == nullptr || !byte_ranges_overlap(out2, on2, m->limits, ln)),
+              "%s: an output overlaps the motion limits", what);
+  a->limits = m->limits; a->scene_rows = m->scene_rows; a->w_speed = m->w_speed; a->w_accel = m->w_accel;
+  return ADX_OK;
+}
+
+// a step with motion limits: guide_check's refusals with the limits' own text where there is no adx_guide to read iters from
+static int motion_step_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, bool inpaint,
+                             float* prev, float* x0, int batch, int horizon, int dim, GuideArgs* ga, MotionArgs* ma) {
+  ADX_REQUIRE(g != nullptr, "%s: motion limits without a guide: a step reads iters, lambda and cap from the guide", what);
+  const size_t on = (size_t)batch * horizon * dim * sizeof(float);
+  const int rc = guide_check(g, f, what, true, inpaint, prev, on, x0, on, batch, dim, ga);
+  return rc != ADX_OK ? rc : motion_check(m, g, f, what, prev, on, x0, on, batch, horizon, ma);
+}
+
 int step_run(const StepCall& k) {
   using Kernel = void (*)(const StepArgs);
 #define ADX_STEP_KERNELS(ddpm, rng) {{step_kernel<ddpm, rng, false, false>, step_kernel<ddpm, rng, false, true>}, \
@@ -365,7 +428,11 @@ int step_run(const StepCall& k) {
     if (rc != ADX_OK) return rc;
   }
   a.guide = kNoGuide;
-  if (guided) {
+  StepRowsArgs ra;
+  if (k.motion != nullptr) {      // cost guidance v3: the row-wise kernel
+    rc = motion_step_check(k.motion, k.guide, k.field, what, c->inpaint != 0, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.guide, &ra.motion);
+    if (rc != ADX_OK) return rc;
+  } else if (guided) {
     const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
     rc = guide_check(k.guide, k.field, what, true, c->inpaint != 0, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
     if (rc != ADX_OK) return rc;
@@ -381,6 +448,17 @@ int step_run(const StepCall& k) {
   a.c = *c;
   a.mo = k.mo; a.x = k.x; a.z = k.z; a.tgt = k.tgt; a.mask = k.mask; a.prev = k.prev; a.x0 = k.x0;
   a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
+  if (k.motion != nullptr) {
+    using RowsKernel = void (*)(const StepRowsArgs);
+#define ADX_ROWS_KERNELS(ddpm) {{step_rows_kernel<ddpm, false, false>, step_rows_kernel<ddpm, false, true>}, \
+                                {step_rows_kernel<ddpm, true, false>, step_rows_kernel<ddpm, true, true>}}
+    static const RowsKernel rows_kernels[2][2][2] = {ADX_ROWS_KERNELS(false), ADX_ROWS_KERNELS(true)};      // [ddpm][noise stream][pin]
+#undef ADX_ROWS_KERNELS
+    ra.s = a;
+    rows_kernels[k.ddpm][rng][pinned]<<<dim3(ceil_div(k.batch, kRowWaves)), dim3(kRowWaves * kWave), 0, k.stream>>>(ra);
+    ADX_LAUNCH_CHECK();
+    return ADX_OK;
+  }
   kernels[k.ddpm][rng][pinned][guided]<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, k.stream>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
@@ -412,30 +490,45 @@ __global__ void __launch_bounds__(256) dpm_step_kernel(const DpmArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= a.total) return;
+  constexpr bool ROWS = false, row_moved = false;
+  constexpr float row_x0 = 0.f;
+#include "sched_dpm_body.h"
+}
+
+struct DpmRowsArgs {
+  DpmArgs s;
+  MotionArgs motion;      // cost guidance v3
+};
+
+// step_rows_kernel's shape around the solver's arithmetic
+template <bool PIN>
+__global__ void __launch_bounds__(kRowWaves * kWave) dpm_step_rows_kernel(const DpmRowsArgs k) {
+#pragma clang fp contract(off)
+  const DpmArgs& a = k.s;
   const adx_dpm_coef& c = a.c;
-  const float m = cfg_model_output(a.mo, e, a.total, c.cfg_combine, c.free_scale);
-  const float xs = a.x[e];
-  float x0 = x0_from(c.prediction_type, c.alpha_s, c.sigma_s, xs, m);
-  if (c.clip) x0 = clamp_nan(x0, -c.clip_range, c.clip_range);
-  if (GUIDE)      // a moved x0 is the solver's x0 from here on, the history it writes included
-    guide_x0(a.guide, a.mo, a.x, e, a.total, a.horizon, a.dim, c.prediction_type, c.alpha_s, c.sigma_s, c.clip, c.clip_range,
-             c.cfg_combine, c.free_scale, x0);
-  const float p = c.r * xs, q = c.k * x0;
-  float prev = p - q;
-  if (c.second_order && a.px0 != nullptr) {
-    const float d0 = x0 - a.px0[e];
-    const float d1 = c.inv_r0 * d0;
-    const float u = c.half_k * d1;
-    prev = prev - u;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int H = a.horizon, D = a.dim;
+  const int row = blockIdx.x * kRowWaves + (threadIdx.x >> 6);
+  if (row >= a.total / (H * D)) return;              // whole waves leave: the shuffles always see all 64 lanes
+  const bool live = lane < H;
+  const int e0 = (row * H + lane) * D;
+  float px = 0.f, py = 0.f;
+  if (live) {
+    px = x0_clipped(c.prediction_type, c.alpha_s, c.sigma_s, a.x[e0], cfg_model_output(a.mo, e0, a.total, c.cfg_combine, c.free_scale), c.clip,
+                    c.clip_range);
+    py = x0_clipped(c.prediction_type, c.alpha_s, c.sigma_s, a.x[e0 + 1], cfg_model_output(a.mo, e0 + 1, a.total, c.cfg_combine, c.free_scale),
+                    c.clip, c.clip_range);
   }
-  if (PIN) {
-    // the solver has no noise of its own: the draw exists for the blend alone, at the element's LOGICAL index as in step_kernel
-    const float zn = a.pin.known_noise ? noise_normal_at(a.ns, a.slot, a.base + (uint64_t)e) : 0.f;
-    prev = pin_blend(a.pin, e, zn, prev);
+  bool mx, my;
+  guide_rows(a.guide, k.motion, row, lane, H, live, c.clip, c.clip_range, px, py, mx, my);
+  if (!live) return;                                  // no shuffle below this line
+  constexpr bool GUIDE = false, ROWS = true;
+  for (int d = 0; d < D; ++d) {                       // the waypoint's D elements, each through the element kernel's own body
+    const int e = e0 + d;
+    const float row_x0 = d == 0 ? px : py;
+    const bool row_moved = d == 0 ? mx : (d == 1 ? my : false);
+#include "sched_dpm_body.h"
   }
-  if (c.zero_first && first_pose(e, a.horizon, a.dim)) prev = 0.f;
-  a.prev[e] = prev;
-  a.x0[e] = x0;          // as computed (not zeroed; guided where it moved): the next step's history
 }
 
 // a NULL pin is adx_dpm_step: the solver itself draws nothing, the noise fields are then not looked at
@@ -467,7 +560,11 @@ int dpm_run(const DpmCall& k) {
   }
   a.guide = kNoGuide;
   const bool guided = k.guide != nullptr || k.field != nullptr;
-  if (guided) {
+  DpmRowsArgs ra;
+  if (k.motion != nullptr) {      // cost guidance v3: the row-wise kernel
+    rc = motion_step_check(k.motion, k.guide, k.field, what, false, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.guide, &ra.motion);
+    if (rc != ADX_OK) return rc;
+  } else if (guided) {
     const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
     rc = guide_check(k.guide, k.field, what, true, false, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
     if (rc != ADX_OK) return rc;
@@ -475,6 +572,13 @@ int dpm_run(const DpmCall& k) {
   a.c = *c;
   a.mo = k.mo; a.x = k.x; a.px0 = k.px0; a.prev = k.prev; a.x0 = k.x0;
   a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
+  if (k.motion != nullptr) {
+    ra.s = a;
+    if (k.pin != nullptr) dpm_step_rows_kernel<true><<<dim3(ceil_div(k.batch, kRowWaves)), dim3(kRowWaves * kWave), 0, k.stream>>>(ra);
+    else dpm_step_rows_kernel<false><<<dim3(ceil_div(k.batch, kRowWaves)), dim3(kRowWaves * kWave), 0, k.stream>>>(ra);
+    ADX_LAUNCH_CHECK();
+    return ADX_OK;
+  }
   kernels[k.pin != nullptr][guided]<<<dim3(ceil_div(a.total, 256)), dim3(256), 0, k.stream>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
@@ -491,8 +595,12 @@ struct GuideCostArgs {
   float* cost;
   int32_t* active;
   int rows, horizon, dim;
+  MotionArgs motion;      // cost guidance v3 (the MOTION kernel only)
 };
 
+// MOTION ("cost guidance v3"): a waypoint's share of the segment and curvature terms after its v1 / v2 terms; the neighbours'
+// xy come by shuffle, so lanes h >= H stay to the end and hold zeros
+template <bool MOTION>
 __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const GuideCostArgs a) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & (kWave - 1);
@@ -500,7 +608,27 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
   if (r >= a.rows) return;                       // whole waves leave: the shuffles below always see all 64 lanes
   float J = 0.f;
   int active = 0;
-  if (lane < a.horizon) {
+  if constexpr (MOTION) {
+    const bool live = lane < a.horizon;
+    float nx[5], ny[5];
+    nx[2] = 0.f; ny[2] = 0.f;
+    if (live) {
+      const float* p = a.traj + ((size_t)r * a.horizon + lane) * a.dim;
+      nx[2] = p[0]; ny[2] = p[1];
+    }
+    nx[0] = __shfl_up(nx[2], 2, kWave); ny[0] = __shfl_up(ny[2], 2, kWave);
+    nx[1] = __shfl_up(nx[2], 1, kWave); ny[1] = __shfl_up(ny[2], 1, kWave);
+    nx[3] = __shfl_down(nx[2], 1, kWave); ny[3] = __shfl_down(ny[2], 1, kWave);
+    nx[4] = __shfl_down(nx[2], 2, kWave); ny[4] = __shfl_down(ny[2], 2, kWave);
+    if (live) {
+      const int scene = r % a.g.scene_rows;
+      float gx, gy, S2, A2;
+      motion_limits(a.motion, r, S2, A2);
+      guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, field_cells(a.g.field, r),
+                 a.g.field, (float)lane, nx[2], ny[2], J, gx, gy, active);
+      motion_grad(nx, ny, lane, a.horizon, S2, A2, a.motion.w_speed, a.motion.w_accel, J, gx, gy, active);
+    }
+  } else if (lane < a.horizon) {
     const float* p = a.traj + ((size_t)r * a.horizon + lane) * a.dim;
     const int scene = r % a.g.scene_rows;
     float gx, gy;
@@ -516,8 +644,8 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
   }
 }
 
-int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, float* cost, int32_t* active, int rows,
-               int horizon, int dim, hipStream_t s) {
+int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion, float* cost,
+               int32_t* active, int rows, int horizon, int dim, hipStream_t s) {
   const char* const what = "guide cost";
   ADX_REQUIRE(traj != nullptr && (guide != nullptr || field != nullptr) && cost != nullptr && active != nullptr,
               "guide cost: null traj, guide, cost or active");
@@ -531,8 +659,14 @@ int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field*
   const size_t tn = (size_t)rows * horizon * dim * sizeof(float);
   ADX_REQUIRE(!byte_ranges_overlap(cost, cn, traj, tn) && !byte_ranges_overlap(active, cn, traj, tn) &&
               !byte_ranges_overlap(cost, cn, active, cn), "guide cost: an output overlaps traj or the other output");
+  a.motion = MotionArgs{nullptr, 1, 0.f, 0.f};
+  if (motion != nullptr) {
+    rc = motion_check(motion, guide, field, what, cost, cn, active, cn, rows, horizon, &a.motion);
+    if (rc != ADX_OK) return rc;
+  }
   a.traj = traj; a.cost = cost; a.active = active; a.rows = rows; a.horizon = horizon; a.dim = dim;
-  guide_cost_kernel<<<dim3(ceil_div(rows, kCostWaves)), dim3(kCostWaves * kWave), 0, s>>>(a);
+  if (motion != nullptr) guide_cost_kernel<true><<<dim3(ceil_div(rows, kCostWaves)), dim3(kCostWaves * kWave), 0, s>>>(a);
+  else guide_cost_kernel<false><<<dim3(ceil_div(rows, kCostWaves)), dim3(kCostWaves * kWave), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }

@@ -20,6 +20,8 @@
 // searches the free candidates alone when `hard` is set and one of them has a finite cost, and reports whether the winner is
 // blocked.  The kGuide = false instantiation reads none of the fields behind w_consensus: its code is what it was.
 // With a field ("cost guidance v2") the same routine also reads the scene's raster, from global memory: four cells per waypoint.
+// With motion limits ("cost guidance v3", the kMotion instantiation) a waypoint's share of the segment and curvature terms follows,
+// through guide.h's motion_grad; its four neighbours are read from the xy planes in LDS.
 #include "sched.h"
 
 namespace adx {
@@ -42,6 +44,7 @@ struct SelectArgs {
   int hard;
   int32_t* active;       // [scenes][K]
   int32_t* blocked;      // [scenes]
+  MotionArgs motion;     // cost guidance v3 (the kMotion kernel only)
 };
 
 // minimum that a NaN wins (numpy's min): the goal term of a candidate with a NaN waypoint is NaN
@@ -53,7 +56,7 @@ __device__ __forceinline__ float wave_min_nan(float v) {
   return v;
 }
 
-template <bool kGuide>
+template <bool kGuide, bool kMotion = false>
 __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
 #pragma clang fp contract(off)
   __shared__ float xs[kSelMaxK * kSelMaxH], ys[kSelMaxK * kSelMaxH];
@@ -143,6 +146,18 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
         float jx, jy;
         guide_grad(disc_s, a.guide.M, plane_s, a.guide.P, field_cells(a.guide.field, s), a.guide.field, (float)lane, px, py, J, jx, jy,
                    act);
+        if constexpr (kMotion) {      // the neighbours from the planes; a point outside the row is a zero no term reads
+          float nx[5], ny[5], S2, A2;
+#pragma unroll
+          for (int j = 0; j < 5; ++j) {
+            const int h = lane - 2 + j;
+            const bool in = h >= 0 && h < H;
+            nx[j] = in ? xs[base + h] : 0.f;
+            ny[j] = in ? ys[base + h] : 0.f;
+          }
+          motion_limits(a.motion, s, S2, A2);
+          motion_grad(nx, ny, lane, H, S2, A2, a.motion.w_speed, a.motion.w_accel, J, jx, jy, act);
+        }
       }
       if (a.w_guide != 0.f) {
         const float violation = wave_sum(J);
@@ -245,8 +260,8 @@ int traj_select(const adx_select_cfg* c, const float* trajs, const float* target
 // "Selection cost v2": v1's refusals first, then what the guide adds; `field` (cost guidance v2) may be null, and with a field the
 // guide may be null too (no discs, no planes)
 int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
-                      const adx_guide_field* field, float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best,
-                      hipStream_t s) {
+                      const adx_guide_field* field, const adx_guide_motion* motion, float* cost, int32_t* active, int32_t* index,
+                      int32_t* blocked, float* best, hipStream_t s) {
   const char* const what = "traj select guide";
   ADX_REQUIRE(c != nullptr, "traj select: null configuration");
   int rc = select_check(c->scenes, c->candidates, c->horizon, c->dim, trajs, cost, index, best);
@@ -281,6 +296,15 @@ int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const f
     for (int i = 0; i < 3; ++i)
       ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], field->cells, cn), "traj select guide: an output overlaps the field's cells");
   }
+  a.motion = MotionArgs{nullptr, 1, 0.f, 0.f};
+  if (motion != nullptr) {      // cost guidance v3; scene_rows == S for the reason the field gives
+    rc = motion_check(motion, guide, field, what, cost, sk_bytes, active, sk_bytes, S * K, c->horizon, &a.motion);
+    if (rc != ADX_OK) return rc;
+    ADX_REQUIRE(motion->scene_rows == S, "traj select guide: the limits hold %d scenes, the selection %d", motion->scene_rows, S);
+    const size_t ln = (size_t)motion->scene_rows * 2 * sizeof(float);
+    for (int i = 0; i < 3; ++i)
+      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], motion->limits, ln), "traj select guide: an output overlaps the motion limits");
+  }
   ADX_REQUIRE(!overlaps(active, sk_bytes, trajs, in_bytes) && !overlaps(blocked, s_bytes, trajs, in_bytes),
               "traj select guide: an output aliases trajs");
   ADX_REQUIRE(!overlaps(active, sk_bytes, cost, sk_bytes) && !overlaps(active, sk_bytes, index, s_bytes) &&
@@ -292,7 +316,8 @@ int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const f
   a.scenes = S; a.K = K; a.H = c->horizon; a.D = c->dim;
   a.w_goal = c->w_goal; a.w_smooth = c->w_smooth; a.w_consensus = c->w_consensus;
   a.w_guide = c->w_guide; a.hard = c->hard != 0; a.active = active; a.blocked = blocked;
-  traj_select_kernel<true><<<dim3(S), dim3(256), 0, s>>>(a);
+  if (motion != nullptr) traj_select_kernel<true, true><<<dim3(S), dim3(256), 0, s>>>(a);
+  else traj_select_kernel<true><<<dim3(S), dim3(256), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;
 }

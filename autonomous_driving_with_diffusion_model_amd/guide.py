@@ -18,6 +18,12 @@ perception stack produces (drivable area, kerbs, parked-car blobs), read bilinea
 `CostField.from_occupancy` makes one from a binary occupancy raster in one launch ("cost field from occupancy v1").  A guide
 without a field is cost guidance v1, bit for bit.
 
+A guide may also hold MOTION LIMITS ("cost guidance v3"): `motion=MotionLimits(limits)`, per scene `(s_max, a_max)`: no segment of
+the plan longer than s_max, no second difference longer than a_max, in the model's units per waypoint interval.  For this model
+speed IS the spacing of the waypoints (the controller derives its desired speed from it), so these are a speed and an acceleration
+limit; `MotionLimits.from_physical` converts from m/s and m/s^2.  The terms couple neighbouring waypoints: a step with limits
+runs the row-wise step kernel (one wave per row, H <= 64).  A guide without limits is v1 / v2, bit for bit.
+
 No reference counterpart as a caller-facing object: the reference names the idea (GUIDANCE.LOSS_LIST) and has one entry, under
 CLASSIFIER_GUIDANCE only.  Whether guided plans drive better is a property of trained weights and is not measured in this
 repository.
@@ -148,13 +154,92 @@ class CostField:
                 f"weight={self.weight})")
 
 
+class MotionLimits:
+    """The motion limits of "cost guidance v3" (include/adx.h): `limits` float32 `[S, 2]` = per scene `(s_max, a_max)` in the
+    model's own units (the clamped result before xy scaling) per waypoint interval.  `s_max` caps the length of a segment
+    `|p[i+1] - p[i]|`, `a_max` the length of a second difference `|p[i+1] - 2 p[i] + p[i-1]|`; `inf` switches a term off for that
+    scene (a NaN does too), `s_max = 0` means "do not move".  A plan over a limit pays `w * (excess of the squared length)^2 / 2`;
+    `w_speed`, `w_accel` >= 0, and a weight of exactly 0 switches its term off everywhere.  The squared excess is small in the
+    model's units: weights that make the terms dimensionless are `1 / s_ref**4` and `1 / a_ref**4` for a typical segment `s_ref`
+    and second difference `a_ref` (an excess of s_ref^2 then costs 1/2, like a waypoint on a disc's centre).  The first waypoint,
+    the ego's present pose, is never moved by these terms.  The limits are read at every step: new values need no new object
+    (and, in a GraphedSampler, no new capture); the weights are baked.
+
+    With `TrajectorySelector(hard=True)` the limits inherit v1's property: a candidate that sits one ulp over a limit is "not
+    free".  A separate tolerance for selection does not exist."""
+
+    def __init__(self, limits: torch.Tensor, w_speed: float = 1.0, w_accel: float = 1.0):
+        if not torch.is_tensor(limits):
+            raise TypeError(f"MotionLimits: limits must be a tensor, got {type(limits).__name__}")
+        if limits.dim() != 2 or limits.shape[1] != 2 or limits.shape[0] < 1:
+            raise ValueError(f"MotionLimits: limits must be [S, 2] = (s_max, a_max) per scene, got {tuple(limits.shape)}")
+        if limits.dtype != torch.float32:
+            raise TypeError(f"MotionLimits: limits must be float32, got {limits.dtype}")
+        w_speed, w_accel = float(w_speed), float(w_accel)
+        for name, w in (("w_speed", w_speed), ("w_accel", w_accel)):
+            if not w >= 0.0:
+                raise ValueError(f"MotionLimits: {name} must be >= 0, got {w}")
+        self.limits, self.w_speed, self.w_accel = limits.contiguous(), w_speed, w_accel
+
+    @property
+    def scenes(self) -> int:
+        return int(self.limits.shape[0])
+
+    @property
+    def device(self) -> torch.device:
+        return self.limits.device
+
+    def key(self) -> tuple:
+        """What a captured graph bakes: everything but the values of the limits."""
+        return (self.w_speed, self.w_accel)
+
+    def like(self, limits: torch.Tensor) -> "MotionLimits":
+        """The same weights over other limits."""
+        return MotionLimits(limits, self.w_speed, self.w_accel)
+
+    def desc(self, x: torch.Tensor) -> L.MotionDesc:
+        """The `adx_guide_motion` of a launch on `x` [B, H, D].  The struct holds an address: keep this object alive until the
+        launch is enqueued."""
+        if L.require_gpu_f32(self.limits, "guide.motion.limits").device != x.device:
+            raise ValueError(f"guide.motion.limits lives on {self.limits.device}, the sample on {x.device}")
+        m = L.MotionDesc()
+        m.limits, m.scene_rows, m.w_speed, m.w_accel = self.limits.data_ptr(), self.scenes, self.w_speed, self.w_accel
+        return m
+
+    @staticmethod
+    def from_physical(v_max, a_max, dt: float, xy_scale: float, w_speed: float = 1.0, w_accel: float = 1.0,
+                      device=None) -> "MotionLimits":
+        """Limits from physical ones, on the host: `v_max` (m/s) and `a_max` (m/s^2) are numbers or sequences of S numbers (one
+        per scene; a number stands for all), `dt` the seconds between two waypoints, `xy_scale` the metres of one model unit
+        (`model.magic_num`).  s_max = v_max * dt / xy_scale and a_max = a_max * dt * dt / xy_scale, formed in double and rounded
+        to fp32 once.  `inf` stays `inf`."""
+        dt, xy_scale = float(dt), float(xy_scale)
+        if not (math.isfinite(dt) and dt > 0.0 and math.isfinite(xy_scale) and xy_scale > 0.0):
+            raise ValueError(f"MotionLimits.from_physical: dt and xy_scale must be finite and > 0, got {dt} and {xy_scale}")
+        v = [float(t) for t in (v_max if hasattr(v_max, "__len__") else [v_max])]
+        a = [float(t) for t in (a_max if hasattr(a_max, "__len__") else [a_max])]
+        S = max(len(v), len(a))
+        if len(v) not in (1, S) or len(a) not in (1, S) or S < 1:
+            raise ValueError(f"MotionLimits.from_physical: v_max holds {len(v)} scenes, a_max {len(a)}")
+        v, a = v * (S // len(v)), a * (S // len(a))
+        for name, t in (("v_max", v), ("a_max", a)):
+            if not all(q >= 0.0 for q in t):
+                raise ValueError(f"MotionLimits.from_physical: {name} must be >= 0 (inf: no limit), got {t}")
+        rows = [[v[i] * dt / xy_scale, a[i] * dt * dt / xy_scale] for i in range(S)]
+        return MotionLimits(torch.tensor(rows, dtype=torch.float64).to(torch.float32).to(device or "cpu"), w_speed, w_accel)
+
+    def __repr__(self):
+        return f"MotionLimits(limits={tuple(self.limits.shape)}, w_speed={self.w_speed}, w_accel={self.w_accel})"
+
+
 class Guide:
     """`discs` float32 `[S, M, 5]` and / or `planes` float32 `[S, P, 3]` on one device (None: no such constraint); `scale`,
-    `schedule`, `cap`, `iters` as the module docstring says; `field`: a CostField or None (keyword only).  The tensors are read
-    at every step: new values need no new object (and, in a GraphedSampler, no new capture)."""
+    `schedule`, `cap`, `iters` as the module docstring says; `field`: a CostField or None, `motion`: a MotionLimits or None
+    (both keyword only).  The tensors are read at every step: new values need no new object (and, in a GraphedSampler, no new capture)."""
 
     def __init__(self, discs: Optional[torch.Tensor] = None, planes: Optional[torch.Tensor] = None, scale: float = 1.0,
-                 schedule: str = "variance", cap: float = float("inf"), iters: int = 1, *, field: Optional[CostField] = None):
+                 schedule: str = "variance", cap: float = float("inf"), iters: int = 1, *, field: Optional[CostField] = None,
+                 motion: Optional[MotionLimits] = None):
         for name, t, last, most in (("discs", discs, 5, MAX_DISCS), ("planes", planes, 3, MAX_PLANES)):
             if t is None:
                 continue
@@ -181,6 +266,17 @@ class Guide:
                     raise ValueError(f"Guide: {name} live on {t.device}, the field on {field.device}")
                 if t.shape[0] != field.scenes:
                     raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the field {field.scenes}")
+        if motion is not None:
+            if not isinstance(motion, MotionLimits):
+                raise TypeError(f"Guide: motion must be a MotionLimits or None, got {type(motion).__name__}")
+            others = (("discs", discs), ("planes", planes), ("field", None if field is None else field.cells))
+            for name, t in others:
+                if t is None or (name != "field" and t.shape[1] == 0):
+                    continue
+                if t.device != motion.device:
+                    raise ValueError(f"Guide: {name} live on {t.device}, the motion limits on {motion.device}")
+                if t.shape[0] != motion.scenes:
+                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the motion limits {motion.scenes}")
         if schedule not in SCHEDULES:
             raise ValueError(f"Guide: schedule must be one of {SCHEDULES}, got {schedule!r}")
         scale, cap = float(scale), float(cap)
@@ -193,7 +289,7 @@ class Guide:
         self.discs = None if discs is None else discs.contiguous()
         self.planes = None if planes is None else planes.contiguous()
         self.scale, self.schedule, self.cap, self.iters = scale, schedule, cap, int(iters)
-        self.field = field
+        self.field, self.motion = field, motion
 
     # ---- shape ----
     @property
@@ -216,22 +312,29 @@ class Guide:
         return None if t is None else t.device
 
     def _first(self) -> Optional[torch.Tensor]:
-        """The tensor that says how many scenes the guide holds and where: discs, else planes, else the field's cells."""
+        """The tensor that says how many scenes the guide holds and where: discs, else planes, else the field's cells, else the
+        motion limits."""
         if self.discs is not None:
             return self.discs
         if self.planes is not None:
             return self.planes
-        return None if self.field is None else self.field.cells
+        if self.field is not None:
+            return self.field.cells
+        return None if self.motion is None else self.motion.limits
 
     def key(self) -> tuple:
         """What a captured graph bakes: everything but the values of discs, planes and the field's cells.  Without a field the
-        6-tuple of cost guidance v1; with one, the field's key appended."""
+        6-tuple of cost guidance v1; with one, the field's key appended.  With motion limits: the 6-tuple followed by the field's
+        key or None and the limits' key."""
         key = (self.M, self.P, self.scale, self.schedule, self.cap, self.iters)
+        if self.motion is not None:
+            return key + (None if self.field is None else self.field.key(), self.motion.key())
         return key if self.field is None else key + (self.field.key(),)
 
-    def like(self, discs: Optional[torch.Tensor], planes: Optional[torch.Tensor], field: Optional[CostField] = None) -> "Guide":
+    def like(self, discs: Optional[torch.Tensor], planes: Optional[torch.Tensor], field: Optional[CostField] = None,
+             motion: Optional[MotionLimits] = None) -> "Guide":
         """The same settings over other tensors."""
-        return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters, field=field)
+        return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters, field=field, motion=motion)
 
     # ---- launches ----
     def desc(self, x: torch.Tensor, lam: float = 0.0) -> L.GuideDesc:
@@ -256,6 +359,21 @@ class Guide:
         goes through the `_guide` export."""
         return None if self.field is None else self.field.desc(x)
 
+    def motion_desc(self, x: torch.Tensor) -> Optional[L.MotionDesc]:
+        """The `adx_guide_motion` of a launch on `x` ("cost guidance v3"), or None for a guide without motion limits: the launch
+        then goes through the `_field` or `_guide` export."""
+        return None if self.motion is None else self.motion.desc(x)
+
+    def descs(self, x: torch.Tensor, lam: float = 0.0):
+        """`(export suffix, byref arguments, the structs)` of a guided launch on `x`: "guide", "field" or "motion" and the
+        records that export takes after the pin, in its order.  Keep the structs alive until the launch is enqueued."""
+        g, f, m = self.desc(x, lam), self.field_desc(x), self.motion_desc(x)
+        if m is not None:
+            return "motion", (C.byref(g), None if f is None else C.byref(f), C.byref(m)), (g, f, m)
+        if f is not None:
+            return "field", (C.byref(g), C.byref(f)), (g, f)
+        return "guide", (C.byref(g),), (g,)
+
     def cost(self, traj: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """What a plan still violates, one launch of `adx_guide_cost`: `(cost [rows] float32, active [rows] int32)` of `traj`
         [rows, H, D] -- the contract's cost summed over a row's waypoints and the number of active (waypoint, constraint) pairs.
@@ -265,8 +383,12 @@ class Guide:
         rows, H, D = traj.shape
         cost = torch.empty(rows, dtype=torch.float32, device=traj.device)
         active = torch.empty(rows, dtype=torch.int32, device=traj.device)
-        f = self.field_desc(traj)
-        if f is None:
+        f, m = self.field_desc(traj), self.motion_desc(traj)
+        if m is not None:
+            L.check(L.lazy("adx_guide_cost_motion")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f), C.byref(m),
+                                                    cost.data_ptr(), active.data_ptr(), rows, H, D, L.stream_ptr(traj.device)),
+                    "adx_guide_cost_motion")
+        elif f is None:
             L.check(L.lazy("adx_guide_cost")(traj.data_ptr(), C.byref(g), cost.data_ptr(), active.data_ptr(), rows, H, D,
                                              L.stream_ptr(traj.device)), "adx_guide_cost")
         else:
@@ -277,4 +399,5 @@ class Guide:
     def __repr__(self):
         return (f"Guide(discs={None if self.discs is None else tuple(self.discs.shape)}, "
                 f"planes={None if self.planes is None else tuple(self.planes.shape)}, scale={self.scale}, schedule={self.schedule!r}, "
-                f"cap={self.cap}, iters={self.iters}" + ("" if self.field is None else f", field={self.field!r}") + ")")
+                f"cap={self.cap}, iters={self.iters}" + ("" if self.field is None else f", field={self.field!r}") +
+                ("" if self.motion is None else f", motion={self.motion!r}") + ")")

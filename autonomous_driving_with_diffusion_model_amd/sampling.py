@@ -32,6 +32,8 @@ A ninth reads the scene as a perception stack draws it: `guide=Guide(..., field=
 to the guide ("cost guidance v2" of include/adx.h), read bilinearly at every waypoint by the same routine of the same kernels, so
 the steps, `Guide.cost`, the guided selector, the warm state, the controller and the graph all see it;
 `CostField.from_occupancy` makes the raster from an occupancy grid in one launch ("cost field from occupancy v1").
+A tenth says how fast to go: `guide=Guide(..., motion=MotionLimits(limits))` caps the length of a segment and of a second difference
+per scene ("cost guidance v3"); every step then runs the row-wise step kernel, one wave per row.
 """
 from __future__ import annotations
 
@@ -191,7 +193,8 @@ class TickPlan:
     # timestep, is a by-value argument of every step node).  Every `scheduler.step` of the loop gets it (fused or not, all three
     # guidance branches) and moves its x0 inside its kernel; the K * S rows read the [S, ..] obstacles directly (row r reads scene
     # r % S), nothing is tiled.  A guide's field ("cost guidance v2"): the cells are a buffer like discs and planes; presence, (Gy, Gx),
-    # origin, cell size and weight are baked (by-value arguments of every step node) -- all of it through `Guide.key()`
+    # origin, cell size and weight are baked (by-value arguments of every step node) -- all of it through `Guide.key()`.  A guide's
+    # motion limits ("cost guidance v3"): the [S, 2] limits are a buffer; presence and the two weights are baked, the same way
     guide: Optional[Guide]
 
     def key(self) -> tuple:
@@ -247,11 +250,14 @@ def _guide_plan(cfg, guide: Optional[Guide], image, scheduler) -> Optional[Guide
     if not isinstance(guide, Guide):
         raise TypeError(f"generate_traj: `guide` must be a Guide, got {type(guide).__name__}")
     S = int(image.shape[0])
-    for name, t in (("discs", guide.discs), ("planes", guide.planes), ("field.cells", None if guide.field is None else guide.field.cells)):
+    for name, t in (("discs", guide.discs), ("planes", guide.planes), ("field.cells", None if guide.field is None else guide.field.cells),
+                    ("motion.limits", None if guide.motion is None else guide.motion.limits)):
         if t is not None and (int(t.shape[0]) != S or t.device != image.device):
             raise ValueError(f"guide.{name} must hold {S} scenes (image.shape[0]) on {image.device}, got {tuple(t.shape)} on {t.device}")
     if int(cfg.MODEL.TRANSITION_DIM) < 2:
         raise ValueError(f"generate_traj: a guide moves (x, y) and needs MODEL.TRANSITION_DIM >= 2, got {int(cfg.MODEL.TRANSITION_DIM)}")
+    if guide.motion is not None and int(cfg.MODEL.HORIZON) > 64:
+        raise ValueError(f"generate_traj: motion limits give a row to a wave and need MODEL.HORIZON <= 64, got {int(cfg.MODEL.HORIZON)}")
     if not getattr(scheduler, "supports_guide", False):
         raise ValueError(f"{type(scheduler).__name__}.step takes no guide: use GuidanceDDIMScheduler, GuidanceDDPMScheduler or "
                          "GuidanceDPMSolverMultistepScheduler")
@@ -580,7 +586,7 @@ class GraphedSampler:
     `guide=Guide(...)` per call: cost guidance as in `generate_traj`.  `discs` and `planes` travel through static buffers; presence,
     M, P, scale, schedule, cap and iters are part of the graph key (every step node holds its lambda by value), new obstacle values
     never capture again.  A guide's `field` travels the same way: the cells through a static buffer, its presence, shape, geometry
-    and weight through the key.
+    and weight through the key.  So do a guide's motion limits: the limits through a static buffer, presence and weights through the key.
     """
 
     MAX_GRAPHS = 4
@@ -621,7 +627,8 @@ class GraphedSampler:
         g.pin = None if pin is None else Pin(pin.known.clone(), pin.mask.clone(), pin.mode)
         g.guide = None if guide is None else guide.like(None if guide.discs is None else guide.discs.clone(),
                                                         None if guide.planes is None else guide.planes.clone(),
-                                                        None if guide.field is None else guide.field.like(guide.field.cells.clone()))
+                                                        None if guide.field is None else guide.field.like(guide.field.cells.clone()),
+                                                        None if guide.motion is None else guide.motion.like(guide.motion.limits.clone()))
         ctl = self.controller
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
@@ -735,6 +742,8 @@ class GraphedSampler:
                     g.guide.planes.copy_(guide.planes)
                 if guide.field is not None:
                     g.guide.field.cells.copy_(guide.field.cells)
+                if guide.motion is not None:
+                    g.guide.motion.limits.copy_(guide.motion.limits)
         self._key, self._graph, self._sel, self._ctl = key, g.graph, g.sel, g.ctl
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured

@@ -279,17 +279,16 @@ class SchedulerBase:
     def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True, slot: int = 0, pin=None, guide=None):
         """`noise`: as `_noise_args` takes it; the stream is drawn at `slot` (the integer timestep).  `pin`: the `adx_pin` of a
         pinned step (the PIN variant of the kernel, "pinned waypoints v1"); `guide`: what `_guide_desc` made of a guided step (the
-        GUIDE variant): the `adx_guide` of "cost guidance v1" and the `adx_guide_field` of v2 or None; None is the call as it was."""
+        GUIDE variant): the export's suffix -- "guide" (cost guidance v1), "field" (v2) or "motion" (v3, the row-wise kernel) --
+        with its records; None is the call as it was."""
         B, H, D = x.shape
         prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
         z, state, row_offset = self._noise_args(noise, x)
         if guide is not None:
-            g, f = guide
-            fn = L.lazy(("adx_ddpm_step_" if ddpm else "adx_ddim_step_") + ("guide" if f is None else "field"))
-            source = (z, state, int(slot), row_offset, None if pin is None else C.byref(pin), C.byref(g))
-            if f is not None:
-                source += (C.byref(f),)
+            suffix, refs, _alive = guide
+            fn = L.lazy(("adx_ddpm_step_" if ddpm else "adx_ddim_step_") + suffix)
+            source = (z, state, int(slot), row_offset, None if pin is None else C.byref(pin), *refs)
         elif pin is not None:
             fn = L.lazy("adx_ddpm_step_pin" if ddpm else "adx_ddim_step_pin")
             source = (z, state, int(slot), row_offset, C.byref(pin))
@@ -344,9 +343,9 @@ class SchedulerBase:
             return float(scale * np.float32(sb * sb))
 
     def _guide_desc(self, guide, timestep, x):
-        """(adx_guide, adx_guide_field or None) of this step, or None without a guide: a guide with a field goes through the
-        `_field` export ("cost guidance v2"), any other through the `_guide` export."""
-        return None if guide is None else (guide.desc(x, self.guide_level(timestep, guide)), guide.field_desc(x))
+        """`Guide.descs` of this step, or None without a guide: a guide with motion limits goes through the `_motion` export
+        ("cost guidance v3"), one with a field through the `_field` export (v2), any other through the `_guide` export."""
+        return None if guide is None else guide.descs(x, self.guide_level(timestep, guide))
 
     @staticmethod
     def _noise(shape, generator, device, dtype, variance_noise=None):

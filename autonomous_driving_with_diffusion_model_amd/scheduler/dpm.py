@@ -201,10 +201,9 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
         g = self._guide_desc(guide, timestep, x)
         prev, x0 = torch.empty_like(x), torch.empty_like(x)
         if g is not None:
-            g, f = g
+            suffix, guides, _alive = g                                                     # "guide", "field" (v2) or "motion" (v3)
             _, state, row_offset = self._noise_args(generator if stream else None, x)      # the stream or nothing
-            guides = (C.byref(g),) if f is None else (C.byref(g), C.byref(f))              # a field: "cost guidance v2"
-            L.check(L.lazy("adx_dpm_step_guide" if f is None else "adx_dpm_step_field")(
+            L.check(L.lazy("adx_dpm_step_" + suffix)(
                 C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history), state, timestep_to_int(timestep), row_offset,
                 None if p is None else C.byref(p), *guides, prev.data_ptr(), x0.data_ptr(), B, H, D, L.stream_ptr(x.device)),
                 "scheduler step")

@@ -974,6 +974,80 @@ int adx_traj_select_guide_field(const adx_select_guide_cfg* c, const float* traj
                                 float* best, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Cost guidance v3: cost guidance v2 plus MOTION LIMITS -- how fast to go.  For this model speed is the spacing of the
+ * waypoints (the controller derives its desired speed from the mean segment length), so a per-scene cap on the length of a
+ * segment is a speed limit and a cap on the length of a second difference is an acceleration limit.  v1 and v2 stay as they are:
+ * the _guide and _field exports and their bits; v3 stands beside them as the _motion exports, each the _field export with one
+ * more argument.  These are the first terms that couple a waypoint to its neighbours.  Callers and fixtures depend on this
+ * definition -- a change is a new version, never an edit.
+ *
+ *   limits   float32 [scene_rows][2] = (s_max, a_max) in device memory, read at every launch.  Row r of a launch reads scene
+ *            r % scene_rows.  Units are the model's own (the clamped result BEFORE xy scaling), per waypoint interval: s_max caps
+ *            |p[i+1] - p[i]|, a_max caps |p[i+1] - 2 p[i] + p[i-1]|.  +inf switches a term off for that scene; so does a NaN,
+ *            because every comparison with it is false.  s_max = 0 is legal: "do not move".
+ *   weights  w_speed and w_accel, host scalars by value, >= 0.  A weight of exactly 0: the term is not evaluated and counts
+ *            nothing in `active`.
+ *   terms    of a row p[0..H-1], p[i] = (x, y) of waypoint i.  fp32, no contraction, every operation rounded on its own, in this
+ *            order; S2 = s_max * s_max and A2 = a_max * a_max (one rounded product each, formed in the kernel):
+ *              segment i, 0 <= i <= H-2:
+ *                ex = x[i+1] - x[i];  ey = y[i+1] - y[i];  s2 = ex * ex + ey * ey;  phi = s2 - S2;  active iff phi > 0
+ *                cost  (w_speed * (phi * phi)) / 2;   k = w_speed * (2 * phi)
+ *                d/dp[i+1] = +(k * ex, k * ey);   d/dp[i] = -(k * ex, k * ey)
+ *              curvature i, 1 <= i <= H-2:
+ *                cx = (x[i+1] - x[i]) - (x[i] - x[i-1]);  cy likewise;  a2 = cx * cx + cy * cy;  psi = a2 - A2;  active iff psi > 0
+ *                cost  (w_accel * (psi * psi)) / 2;   q = w_accel * (2 * psi)
+ *                d/dp[i-1] = +(q * cx, q * cy);   d/dp[i] = -((2 * q) * cx, (2 * q) * cy);   d/dp[i+1] = +(q * cx, q * cy)
+ *            No square root and no singular point.  H = 1 has no term, H = 2 one segment and no curvature.
+ *   share    of waypoint h, evaluated AFTER v1's discs and planes and v2's field term into the same J, gx, gy and active count:
+ *              J and active:  segment h-1 (h >= 1), then curvature h (1 <= h <= H-2): J = J + cost, active = active + 1
+ *              gx, gy:        segment h-1 (+k e), segment h (-k e), curvature h-1 (+q c), curvature h (-(2 q) c),
+ *                             curvature h+1 (+q c), in this order, each as g = g + t or g = g - t with t the rounded product
+ *            A term that does not exist at that h is not added, and neither is an inactive one -- not even as a zero: a guide
+ *            whose motion terms are all inactive accumulates exactly v2's bits.  Every waypoint that touches a term evaluates it
+ *            anew from the same operands, so all agree on its bits.  Summed over a row, J counts every term once.
+ *   anchor   the motion terms' gradient at h = 0 is not applied: the ego's present pose is not moved to satisfy a limit on its
+ *            future.  Waypoint 0 still takes the v1 and v2 gradient, and segment 0 and curvature 1 read it as the value it has.
+ *   per step the iterations of v1 become Jacobi iterations of the whole row.  From p = the step's clipped pred_original_sample
+ *            of every waypoint; for it = 0..iters-1: every waypoint's g = the total gradient (v1, v2, v3) on iterate `it` of the
+ *            whole row; then every waypoint moves, p = p - clamp(lambda * g, -cap, +cap), followed by the step's clip.  iters,
+ *            lambda, cap, `moved` and everything after the guide are v1's, word for word: DDIM re-derives eps, DDPM and DPM
+ *            read x0, the x0 output is the guided value, and an element that did not move runs the unguided step bit for bit.
+ *   kernels  a wave owns a row (lane = waypoint), which needs horizon <= 64.  A step with a motion record always runs the
+ *            row-wise kernel, whatever the weights and limits; with both weights 0, or every limit +inf, its results are the
+ *            _field export's bit for bit.
+ *   cost     adx_guide_cost_motion: per waypoint J as above, summed by v1's butterfly.  adx_traj_select_guide_motion: violation,
+ *            active, free and blocked of selection cost v2 with these terms among them; the limits' scene_rows equals `scenes`.
+ *            `hard` inherits v1's property: a candidate one ulp over a limit is not free.
+ *   NULL     a NULL motion record is exactly the _field export (and the element-wise kernels).
+ *
+ * ADX_ERR_INVALID before any GPU work, each with its own text: NULL limits; scene_rows < 1 or not dividing batch; scene_rows
+ * disagreeing with the guide's (when it holds discs or planes) or with the field's; a weight negative or NaN; horizon > 64; an
+ * output overlapping limits; a step with motion limits and no adx_guide; and whatever the _field export refuses.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_guide_motion {
+  const float* limits;         /* [scene_rows][2] = (s_max, a_max) */
+  int32_t scene_rows;
+  float w_speed, w_accel;
+} adx_guide_motion;
+int adx_ddim_step_motion(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                         const adx_guide_field* field, const adx_guide_motion* motion, float* prev, float* x0, int32_t batch,
+                         int32_t horizon, int32_t dim, adx_stream s);
+int adx_ddpm_step_motion(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                         const adx_guide_field* field, const adx_guide_motion* motion, float* prev, float* x0, int32_t batch,
+                         int32_t horizon, int32_t dim, adx_stream s);
+int adx_dpm_step_motion(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        const adx_guide_field* field, const adx_guide_motion* motion, float* prev_sample, float* x0, int32_t batch,
+                        int32_t horizon, int32_t dim, adx_stream s);
+int adx_guide_cost_motion(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+                          float* cost, int32_t* active, int32_t rows, int32_t horizon, int32_t dim, adx_stream s);
+int adx_traj_select_guide_motion(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
+                                 const adx_guide_field* field, const adx_guide_motion* motion, float* cost, int32_t* active,
+                                 int32_t* index, int32_t* blocked, float* best, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Cost field from occupancy v1: a cost raster for cost guidance v2 from a binary occupancy raster, one launch.  The value at a
  * node is the disc potential of cost guidance v1 around the NEAREST occupied node: 0.5 on an obstacle, falling to 0 at distance
  * `margin`.  No square root.  Capturable: no allocation, no synchronisation, no host decision.  Callers and fixtures depend on

@@ -22,7 +22,13 @@ threads, two in seven of which loop over the constraints.  Prints a table and on
 record.  This measures time only: what a guide does to a trained model's driving quality is not something the repository can
 measure (it has no trained weights).
 
+`--motion` runs another leg instead ("cost guidance v3", motion limits): the graph tick with the largest guide with and without
+limits (`m32p8i8` and `m32p8i8.lim`, beside `none`) at 1 and 64 scenes, and the three step launches alone -- DDIM, DDPM and
+DPM-Solver++ `scheduler.step` with that guide, 20 calls captured in one graph and replayed, with limits (the row-wise kernel: a
+wave per row) and without (the element-wise kernel), per launch.  The limits (0.05, 0.03) are ones a fresh draw exceeds.
+
     python tools/guide_tick_probe.py --json profiles/guide_tick_probe.json
+    python tools/guide_tick_probe.py --motion --json profiles/motion_tick_probe.json
 """
 import argparse
 import contextlib
@@ -34,7 +40,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from autonomous_driving_with_diffusion_model_amd import CostField, DeviceNoise, Guide  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd import CostField, DeviceNoise, Guide, MotionLimits  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd import scheduler as S  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd.config import create_cfg  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd.modeling import build_model  # noqa: E402
@@ -49,6 +55,10 @@ ARMS = (("none", None, None, False), ("m4p2i1", (4, 2, 1), None, False), ("m32p8
         ("f64i1", (0, 0, 1), 64, False), ("m4p2i1.f256", (4, 2, 1), 256, False), ("m4p2i8.f256", (4, 2, 8), 256, False),
         ("m4p2i1.occ", (4, 2, 1), 256, True))
 MARGIN = 0.125                         # of the occupancy arm: 16 cells of 2 / 256
+# the --motion leg: (name, (M, P, iters) or None, motion limits or not)
+MOTION_ARMS = (("none", None, False), ("m32p8i8", (32, 8, 8), False), ("m32p8i8.lim", (32, 8, 8), True))
+LIMITS = (0.05, 0.03)                  # (s_max, a_max) of every scene
+STEP_CALLS = 20                        # step launches per captured graph
 
 
 def make_cfg(steps, horizon):
@@ -71,7 +81,7 @@ def field(scenes, G, dev):
     return CostField.from_occupancy(occupancy(scenes, G, dev), (-1.0, -1.0), (cell, cell), 16 * cell)
 
 
-def obstacles(scenes, M, P, iters, dev, field=None):
+def obstacles(scenes, M, P, iters, dev, field=None, motion=False):
     g = torch.Generator().manual_seed(11)
     discs = torch.zeros(scenes, M, 5)
     discs[..., :2] = torch.rand(scenes, M, 2, generator=g) - 0.5
@@ -81,7 +91,59 @@ def obstacles(scenes, M, P, iters, dev, field=None):
     planes[..., :2] = torch.rand(scenes, P, 2, generator=g) * 2 - 1
     planes[..., 2] = torch.rand(scenes, P, generator=g) * 0.5
     return Guide(discs.to(dev) if M else None, planes.to(dev) if P else None, scale=0.2, schedule="variance", cap=0.1, iters=iters,
-                 field=field)
+                 field=field, motion=MotionLimits(torch.tensor([LIMITS] * scenes, device=dev)) if motion else None)
+
+
+def motion_arms(dev, n):
+    """The graph ticks of the --motion leg: `arms` with MOTION_ARMS."""
+    fns, meta = {}, {}
+    for scenes, horizon in SIZES:
+        cfg = make_cfg(n, horizon)
+        with contextlib.redirect_stdout(sys.stderr):
+            model = build_model(cfg)
+        P.load_procedural(model, 0)
+        model = model.to(dev).eval()
+        d = {k: v.to(dev) for k, v in P.synthetic_batch(scenes, horizon, image_hw=IMG, seed=3).items()}
+        for arm, mpi, lim in MOTION_ARMS:
+            sch = S.GuidanceDDIMScheduler(cfg=cfg, thresholding=True, **SCHED_KW)
+            gs = GraphedSampler(model, sch, cfg, noise=DeviceNoise(7, dev))
+            guide = None if mpi is None else obstacles(scenes, *mpi, dev, motion=lim)
+            fns[f"s{scenes}.{arm}"] = (lambda gs=gs, img=d["imgs"], tgt=d["target"], guide=guide: gs(img, tgt, guide=guide))
+            meta[f"s{scenes}.{arm}"] = (scenes, horizon, arm)
+    return fns, meta
+
+
+def step_launches(dev, rounds):
+    """us per `scheduler.step` launch with the largest guide, with and without limits: STEP_CALLS calls in one captured graph."""
+    out = {}
+    for scenes, horizon in SIZES:
+        cfg = make_cfg(20, horizon)
+        g = torch.Generator().manual_seed(5)
+        x = torch.randn(scenes, horizon, 7, generator=g).to(dev)
+        mo = (torch.randn(scenes, horizon, 7, generator=g) * 0.7).to(dev)
+        for sampler in ("ddim", "ddpm", "dpm"):
+            for lim in (False, True):
+                q = {"ddim": lambda: S.GuidanceDDIMScheduler(cfg=cfg, thresholding=True, **SCHED_KW),
+                     "ddpm": lambda: S.GuidanceDDPMScheduler(cfg=cfg, **SCHED_KW),
+                     "dpm": lambda: S.GuidanceDPMSolverMultistepScheduler(cfg=cfg, thresholding=True, lambda_min_clipped=-5.1, **SCHED_KW)}[sampler]()
+                q.set_timesteps(20, device=dev)
+                guide, noise, t = obstacles(scenes, 32, 8, 8, dev, motion=lim), DeviceNoise(3, dev), q.timesteps[0]
+                noise.begin_tick()
+
+                def run():
+                    for _ in range(STEP_CALLS):
+                        q.step(mo, t, x, generator=noise, guide=guide)
+                run()
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    run()
+                for _ in range(5):
+                    graph.replay()
+                us = [1e3 * timed(graph.replay, 200) / STEP_CALLS for _ in range(rounds)]
+                out[f"s{scenes}.{sampler}.{'rows' if lim else 'element'}"] = {
+                    "scenes": scenes, "horizon": horizon, "us_per_launch": [round(v, 3) for v in us], "median_us": round(statistics.median(us), 3)}
+    return out
 
 
 def arms(dev, n, only=None):
@@ -132,11 +194,12 @@ def main():
     ap.add_argument("--seconds", type=float, default=0.5, help="least length of a window")
     ap.add_argument("--json", default=None)
     ap.add_argument("--arms", default=None, help="comma-separated arm names (default: all); the ratios need `none` and `m4p2i1` among them")
+    ap.add_argument("--motion", action="store_true", help="the motion-limits leg instead: see the module docstring")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     n = a.steps
     with torch.no_grad():
-        fns, meta = arms(dev, n, None if a.arms is None else a.arms.split(","))
+        fns, meta = motion_arms(dev, n) if a.motion else arms(dev, n, None if a.arms is None else a.arms.split(","))
         ticks = {}
         for fn in fns.values():                 # warm every arm: the capture, then replays ...
             for _ in range(3):
@@ -153,6 +216,10 @@ def main():
     record = {"device": torch.cuda.get_device_name(0), "image": list(IMG), "guidance": "FREE_GUIDANCE", "sampler": "ddim",
               "sample_steps": n, "rounds": a.rounds, "guide": "scale 0.2, variance schedule, cap 0.1", "arms": {}, "guided_over_none": {},
               "guided_over_m4p2i1": {}}
+    if a.motion:
+        with torch.no_grad():
+            record["limits"], record["step_launches"] = list(LIMITS), step_launches(dev, a.rounds)
+        record["limits_over_m32p8i8"] = {}
     for k in fns:
         scenes, horizon, mode = meta[k]
         med = statistics.median(ms[k])
@@ -164,6 +231,12 @@ def main():
             ref = record["arms"].get(f"s{v['scenes']}.{base}")
             if v["guide"] != "none" and ref is not None:
                 record[over][k] = round(v["median_ms"] / ref["median_ms"], 4)
+    if a.motion:
+        for scenes, _ in SIZES:
+            record["limits_over_m32p8i8"][f"s{scenes}"] = round(record["arms"][f"s{scenes}.m32p8i8.lim"]["median_ms"] /
+                                                                record["arms"][f"s{scenes}.m32p8i8"]["median_ms"], 4)
+        for k, v in record["step_launches"].items():
+            print(f"{k:<24}{v['median_us']:>9.3f} us per launch", file=sys.stderr)
     print(f"FREE guidance, DDIM, {IMG[0]}x{IMG[1]} frame, n = {n}, graph ticks ({a.rounds} alternating rounds)", file=sys.stderr)
     print(f"{'arm':<14}{'scenes':>7}{'H':>4}{'median ms':>11}{'min':>9}{'max':>9}{'spread %':>10}{'/ none':>9}{'/ m4p2i1':>10}{'ticks':>8}", file=sys.stderr)
     for k, v in record["arms"].items():
