@@ -91,6 +91,11 @@ class MotionDesc(C.Structure):
     _fields_ = [("limits", vp), ("scene_rows", i32), ("w_speed", f32), ("w_accel", f32)]
 
 
+class RouteDesc(C.Structure):
+    """adx_guide_route ("cost guidance v4", include/adx.h)."""
+    _fields_ = [("points", vp), ("half_width", vp), ("scene_rows", i32), ("n_points", i32), ("weight", f32)]
+
+
 class SelectCfg(C.Structure):
     _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("w_goal", f32), ("w_smooth", f32),
                 ("w_consensus", f32)]
@@ -254,6 +259,16 @@ _LAZY_SIGS = {
     "adx_guide_cost_motion": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
     "adx_traj_select_guide_motion": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
                                            C.POINTER(MotionDesc), vp, vp, vp, vp, vp, vp]),
+    "adx_ddim_step_route": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                  C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_ddpm_step_route": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                  C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_dpm_step_route": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                 C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_guide_cost_route": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp,
+                                   i32, i32, i32, vp]),
+    "adx_traj_select_guide_route": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
+                                          C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, vp, vp, vp, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)

@@ -1,6 +1,7 @@
 // "Cost guidance v1" and "cost guidance v2" (include/adx.h) on the device: the argument record of a guided launch and the ONE routine
 // that evaluates a waypoint's cost.  The step kernels and guide_cost_kernel (sched.hip) and the guided select kernel (select.hip) all
 // call it, so what a step steers by, what adx_guide_cost reports and what a selection scores are the same bits.
+// "Cost guidance v4" adds the route corridor to that routine, after the field term: a per-scene polyline and a half-width.
 // "Cost guidance v3" adds motion_grad beside it: a waypoint's share of the terms that couple it to its neighbours, for the row-wise
 // step kernels, guide_cost_kernel<true> and traj_select_kernel<true, true>.
 #pragma once
@@ -16,6 +17,15 @@ struct FieldArgs {
   float x_min, y_min, inv_dx, inv_dy, weight;
 };
 
+// Cost guidance v4: points [scene_rows][R][2], half_width [scene_rows]; row r of a launch reads scene r % scene_rows.
+// points == nullptr: no route, and nothing else of the record is read
+struct RouteArgs {
+  const float* points;
+  const float* half_width;
+  int scene_rows, R;
+  float weight;
+};
+
 // Cost guidance v1: discs [scene_rows][M][5], planes [scene_rows][P][3]; row r of a launch reads scene r % scene_rows
 struct GuideArgs {
   const float* discs;
@@ -23,6 +33,7 @@ struct GuideArgs {
   int scene_rows, M, P, iters;
   float lambda, cap;
   FieldArgs field;      // cost guidance v2
+  RouteArgs route;      // cost guidance v4
 };
 
 // The raster of row `row`'s scene, or nullptr without a field (uniform across a launch)
@@ -30,11 +41,29 @@ __device__ __forceinline__ const float* field_cells(const FieldArgs& f, int row)
   return f.cells == nullptr ? nullptr : f.cells + (size_t)(row % f.scene_rows) * f.Gy * f.Gx;
 }
 
-// Cost guidance v1 / v2: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs, P planes and, when
+// The polyline of row `row`'s scene, or nullptr without a route or at weight 0, where the term is not evaluated (uniform across a
+// launch).  Read from global memory as it lies: a scene's points are at most 256 bytes that every lane of the scene reads at the
+// same address.
+__device__ __forceinline__ const float* route_points(const RouteArgs& r, int row) {
+  return r.points == nullptr || r.weight == 0.f ? nullptr : r.points + (size_t)(row % r.scene_rows) * r.R * 2;
+}
+
+// W2 of row `row`'s scene: the square of its half-width, one rounded product; `pts` is route_points(r, row)
+__device__ __forceinline__ float route_w2(const RouteArgs& r, const float* pts, int row) {
+#pragma clang fp contract(off)
+  if (pts == nullptr) return 0.f;
+  const float w = r.half_width[row % r.scene_rows];
+  return w * w;
+}
+
+// Cost guidance v1 / v2 / v4: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs, P planes and, when
 // `cells` (the scene's raster, field_cells) is not null, the field `f`; its gradient and the number of active terms; the contracts'
-// operations in the contracts' order, each rounded on its own.  Without a field the accumulation is v1's, bit for bit.
+// operations in the contracts' order, each rounded on its own.  Without a field the accumulation is v1's, bit for bit.  When `pts`
+// (the scene's polyline, route_points) is not null, the route term of v4 follows: the nearest of the R - 1 segments against W2
+// (route_w2) at weight rw.  Without a route the accumulation is v2's, bit for bit.
 __device__ __forceinline__ void guide_grad(const float* discs, int M, const float* planes, int P, const float* cells, const FieldArgs& f,
-                                           float hf, float x, float y, float& J, float& gx, float& gy, int& active) {
+                                           const float* pts, int R, float W2, float rw, float hf, float x, float y, float& J, float& gx,
+                                           float& gy, int& active) {
 #pragma clang fp contract(off)
   J = 0.f; gx = 0.f; gy = 0.f; active = 0;
   for (int i = 0; i < M; ++i) {
@@ -103,6 +132,39 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
         gy = gy + sy;
         ++active;
       }
+    }
+  }
+  if (pts != nullptr) {      // the route term: the squared distance to the nearest segment over W2; no square root
+    float best = __builtin_inff(), qx = 0.f, qy = 0.f;
+    float ax = pts[0], ay = pts[1];
+    for (int i = 1; i < R; ++i) {
+      const float bx = pts[2 * i], by = pts[2 * i + 1];
+      const float ex = bx - ax, ey = by - ay;
+      const float ux = x - ax, uy = y - ay;
+      const float exx = ex * ex, eyy = ey * ey;
+      const float ee = exx + eyy;
+      const float uxe = ux * ex, uye = uy * ey;
+      const float ue = uxe + uye;
+      float t = ee > 0.f ? ue / ee : 0.f;       // a degenerate segment is its first point
+      t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);      // a NaN passes through
+      const float tx = t * ex, ty = t * ey;
+      const float rx = ux - tx, ry = uy - ty;
+      const float rxx = rx * rx, ryy = ry * ry;
+      const float d2 = rxx + ryy;
+      if (d2 < best) { best = d2; qx = rx; qy = ry; }      // strict: the first of equals wins; a NaN never wins
+      ax = bx; ay = by;
+    }
+    const float phi = best - W2;
+    if (best < __builtin_inff() && phi > 0.f) {
+      const float pp = phi * phi;
+      const float wp = rw * pp;
+      J = J + wp / 2.0f;
+      const float p2 = 2.0f * phi;
+      const float k = rw * p2;
+      const float kx = k * qx, ky = k * qy;
+      gx = gx + kx;
+      gy = gy + ky;
+      ++active;
     }
   }
 }

@@ -23,6 +23,7 @@ struct StepCall {
   const adx_guide* guide = nullptr;   // cost guidance v1
   const adx_guide_field* field = nullptr;      // cost guidance v2: the GUIDE kernel with a raster
   const adx_guide_motion* motion = nullptr;    // cost guidance v3: step_rows_kernel<ddpm, ns != null, pin != null> instead
+  const adx_guide_route* route = nullptr;      // cost guidance v4: a route corridor in whichever kernel runs
   float* prev = nullptr;
   float* x0 = nullptr;                // optional
   int batch = 0, horizon = 0, dim = 0;
@@ -43,6 +44,7 @@ struct DpmCall {
   const adx_guide* guide = nullptr;   // cost guidance v1
   const adx_guide_field* field = nullptr;      // cost guidance v2
   const adx_guide_motion* motion = nullptr;    // cost guidance v3: dpm_step_rows_kernel<pin != null> instead
+  const adx_guide_route* route = nullptr;      // cost guidance v4
   float* prev = nullptr;
   float* x0 = nullptr;                // always written
   int batch = 0, horizon = 0, dim = 0;
@@ -64,8 +66,14 @@ int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, 
 // against the limits.  `g` and `f` are the (checked) guide and field beside it; either may be null.
 int motion_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, const void* out, size_t on,
                  const void* out2, size_t on2, int batch, int horizon, MotionArgs* a);
-int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion, float* cost,
-               int32_t* active, int rows, int horizon, int dim, hipStream_t s);
+// The refusals of "cost guidance v4" that every launch with a route shares, after guide_check (which leaves GuideArgs without a
+// route) and motion_check, filling RouteArgs: the arrays, the point count, scene_rows against `batch` and against the guide's, the
+// field's and the limits', the weight and the outputs against the arrays.  `g`, `f` and `m` are the (checked) records beside it;
+// each may be null.
+int route_check(const adx_guide_route* r, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m, const char* what,
+                const void* out, size_t on, const void* out2, size_t on2, int batch, RouteArgs* a);
+int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+               const adx_guide_route* route, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s);
 int field_from_occupancy(const float* occ, float* cells, int scenes, int gy, int gx, float dx, float dy, float inv_m2, int ry, int rx,
                          hipStream_t s);
 int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int batch, int horizon, int dim, hipStream_t s);

@@ -145,12 +145,14 @@ __device__ __forceinline__ bool guide_x0(const GuideArgs& g, const float* mo, co
   const float* discs = g.discs + (size_t)scene * g.M * 5;
   const float* planes = g.planes + (size_t)scene * g.P * 3;
   const float* cells = field_cells(g.field, row);      // cost guidance v2: null without a field, the same in every thread
+  const float* pts = route_points(g.route, row);       // cost guidance v4: null without a route, the same in every thread
+  const float W2 = route_w2(g.route, pts, row);
   const float hf = (float)h;
   bool moved = false;
   for (int it = 0; it < g.iters; ++it) {
     float J, gx, gy;
     int active;
-    guide_grad(discs, g.M, planes, g.P, cells, g.field, hf, px, py, J, gx, gy, active);
+    guide_grad(discs, g.M, planes, g.P, cells, g.field, pts, g.route.R, W2, g.route.weight, hf, px, py, J, gx, gy, active);
     const float lx = g.lambda * gx, ly = g.lambda * gy;
     const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
     moved = moved || (d == 0 ? sx : sy) != 0.f;
@@ -197,6 +199,8 @@ __device__ __forceinline__ void guide_rows(const GuideArgs& g, const MotionArgs&
   const float* discs = g.discs + (size_t)scene * g.M * 5;
   const float* planes = g.planes + (size_t)scene * g.P * 3;
   const float* cells = field_cells(g.field, row);
+  const float* pts = route_points(g.route, row);
+  const float W2 = route_w2(g.route, pts, row);
   float S2, A2;
   motion_limits(mo, row, S2, A2);
   const float hf = (float)lane;
@@ -211,7 +215,7 @@ __device__ __forceinline__ void guide_rows(const GuideArgs& g, const MotionArgs&
     if (live) {
       float J, gx, gy;
       int active;
-      guide_grad(discs, g.M, planes, g.P, cells, g.field, hf, px, py, J, gx, gy, active);
+      guide_grad(discs, g.M, planes, g.P, cells, g.field, pts, g.route.R, W2, g.route.weight, hf, px, py, J, gx, gy, active);
       motion_grad(nx, ny, lane, H, S2, A2, mo.w_speed, mo.w_accel, J, gx, gy, active);
       const float lx = g.lambda * gx, ly = g.lambda * gy;
       const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
@@ -311,6 +315,7 @@ static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const
 // the refusals of "cost guidance v1" that every guided launch, guide_cost and the guided selection share (sched.h); `step`: a
 // step, which also reads iters, cap and lambda; `out2` may be null
 static const FieldArgs kNoField = {nullptr, 1, 2, 2, 0.f, 0.f, 0.f, 0.f, 0.f};
+static const RouteArgs kNoRoute = {nullptr, nullptr, 1, 2, 0.f};
 
 static bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for inf and NaN
 
@@ -369,10 +374,11 @@ int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, 
   a->discs = g->discs; a->planes = g->planes; a->scene_rows = g->scene_rows; a->M = g->n_discs; a->P = g->n_planes;
   a->iters = g->iters; a->lambda = g->lambda; a->cap = g->cap;
   a->field = kNoField;
+  a->route = kNoRoute;
   return f == nullptr ? ADX_OK : field_check(f, g, what, out, on, out2, on2, batch, &a->field);
 }
 
-static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f, kNoField};
+static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f, kNoField, kNoRoute};
 
 // the refusals of "cost guidance v3" that are the motion limits' own, after guide_check (sched.h)
 int motion_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, const void* out, size_t on,
@@ -394,6 +400,30 @@ int motion_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_
   return ADX_OK;
 }
 
+// the refusals of "cost guidance v4" that are the route's own, after guide_check and motion_check (sched.h)
+int route_check(const adx_guide_route* r, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m, const char* what,
+                const void* out, size_t on, const void* out2, size_t on2, int batch, RouteArgs* a) {
+  ADX_REQUIRE(r->points != nullptr, "%s: null route points", what);
+  ADX_REQUIRE(r->half_width != nullptr, "%s: null route half_width", what);
+  ADX_REQUIRE(r->n_points >= ADX_ROUTE_MIN_POINTS && r->n_points <= ADX_ROUTE_MAX_POINTS, "%s: route of %d points, supported %d..%d", what,
+              r->n_points, ADX_ROUTE_MIN_POINTS, ADX_ROUTE_MAX_POINTS);
+  ADX_REQUIRE(r->scene_rows >= 1 && batch % r->scene_rows == 0, "%s: batch %d must be a positive multiple of the route's scene_rows %d",
+              what, batch, r->scene_rows);
+  ADX_REQUIRE(g == nullptr || (g->n_discs == 0 && g->n_planes == 0) || g->scene_rows == r->scene_rows,
+              "%s: the route holds %d scenes, the guide's discs and planes %d", what, r->scene_rows, g == nullptr ? 0 : g->scene_rows);
+  ADX_REQUIRE(f == nullptr || f->scene_rows == r->scene_rows, "%s: the route holds %d scenes, the field %d", what, r->scene_rows,
+              f == nullptr ? 0 : f->scene_rows);
+  ADX_REQUIRE(m == nullptr || m->scene_rows == r->scene_rows, "%s: the route holds %d scenes, the motion limits %d", what, r->scene_rows,
+              m == nullptr ? 0 : m->scene_rows);
+  ADX_REQUIRE(r->weight >= 0.f, "%s: route weight %g is negative or NaN", what, (double)r->weight);
+  const size_t pn = (size_t)r->scene_rows * r->n_points * 2 * sizeof(float), wn = (size_t)r->scene_rows * sizeof(float);
+  ADX_REQUIRE(!byte_ranges_overlap(out, on, r->points, pn) && !byte_ranges_overlap(out, on, r->half_width, wn) &&
+                  (out2 == nullptr || (!byte_ranges_overlap(out2, on2, r->points, pn) && !byte_ranges_overlap(out2, on2, r->half_width, wn))),
+              "%s: an output overlaps the route's points or half_width", what);
+  a->points = r->points; a->half_width = r->half_width; a->scene_rows = r->scene_rows; a->R = r->n_points; a->weight = r->weight;
+  return ADX_OK;
+}
+
 // a step with motion limits: guide_check's refusals with the limits' own text where there is no adx_guide to read iters from
 static int motion_step_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, bool inpaint,
                              float* prev, float* x0, int batch, int horizon, int dim, GuideArgs* ga, MotionArgs* ma) {
@@ -401,6 +431,19 @@ static int motion_step_check(const adx_guide_motion* m, const adx_guide* g, cons
   const size_t on = (size_t)batch * horizon * dim * sizeof(float);
   const int rc = guide_check(g, f, what, true, inpaint, prev, on, x0, on, batch, dim, ga);
   return rc != ADX_OK ? rc : motion_check(m, g, f, what, prev, on, x0, on, batch, horizon, ma);
+}
+
+// a step's guide records, checked in the contracts' order into GuideArgs (and MotionArgs when there are limits): a route without an
+// adx_guide gets its own text, as limits do
+static int guided_step_check(const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m, const adx_guide_route* r,
+                             const char* what, bool inpaint, float* prev, float* x0, int batch, int horizon, int dim, GuideArgs* ga,
+                             MotionArgs* ma) {
+  ADX_REQUIRE(r == nullptr || g != nullptr, "%s: a route without a guide: a step reads iters, lambda and cap from the guide", what);
+  const size_t on = (size_t)batch * horizon * dim * sizeof(float);
+  const int rc = m != nullptr ? motion_step_check(m, g, f, what, inpaint, prev, x0, batch, horizon, dim, ga, ma)
+                              : guide_check(g, f, what, true, inpaint, prev, on, x0, on, batch, dim, ga);
+  if (rc != ADX_OK || r == nullptr) return rc;
+  return route_check(r, g, f, m, what, prev, on, x0, on, batch, &ga->route);
 }
 
 int step_run(const StepCall& k) {
@@ -412,7 +455,7 @@ int step_run(const StepCall& k) {
 #undef ADX_STEP_KERNELS
   const char* const what = "scheduler step";
   const adx_step_coef* c = k.c;
-  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr, guided = k.guide != nullptr || k.field != nullptr;
+  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr, guided = k.guide != nullptr || k.field != nullptr || k.route != nullptr;
   ADX_REQUIRE(k.z == nullptr || !rng, "scheduler step: a noise tensor and a noise state are both given");
   ADX_REQUIRE(c && k.mo && k.x && k.prev, "scheduler step: null tensor");
   int rc = shape_check(what, k.batch, k.horizon, k.dim);
@@ -429,12 +472,9 @@ int step_run(const StepCall& k) {
   }
   a.guide = kNoGuide;
   StepRowsArgs ra;
-  if (k.motion != nullptr) {      // cost guidance v3: the row-wise kernel
-    rc = motion_step_check(k.motion, k.guide, k.field, what, c->inpaint != 0, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.guide, &ra.motion);
-    if (rc != ADX_OK) return rc;
-  } else if (guided) {
-    const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
-    rc = guide_check(k.guide, k.field, what, true, c->inpaint != 0, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
+  if (guided || k.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route): in whichever runs
+    rc = guided_step_check(k.guide, k.field, k.motion, k.route, what, c->inpaint != 0, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.guide,
+                           &ra.motion);
     if (rc != ADX_OK) return rc;
   }
   if (rng) {
@@ -559,14 +599,10 @@ int dpm_run(const DpmCall& k) {
     }
   }
   a.guide = kNoGuide;
-  const bool guided = k.guide != nullptr || k.field != nullptr;
+  const bool guided = k.guide != nullptr || k.field != nullptr || k.route != nullptr;
   DpmRowsArgs ra;
-  if (k.motion != nullptr) {      // cost guidance v3: the row-wise kernel
-    rc = motion_step_check(k.motion, k.guide, k.field, what, false, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.guide, &ra.motion);
-    if (rc != ADX_OK) return rc;
-  } else if (guided) {
-    const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
-    rc = guide_check(k.guide, k.field, what, true, false, k.prev, on, k.x0, on, k.batch, k.dim, &a.guide);
+  if (guided || k.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route): in whichever runs
+    rc = guided_step_check(k.guide, k.field, k.motion, k.route, what, false, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.guide, &ra.motion);
     if (rc != ADX_OK) return rc;
   }
   a.c = *c;
@@ -624,16 +660,18 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
       const int scene = r % a.g.scene_rows;
       float gx, gy, S2, A2;
       motion_limits(a.motion, r, S2, A2);
+      const float* pts = route_points(a.g.route, r);
       guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, field_cells(a.g.field, r),
-                 a.g.field, (float)lane, nx[2], ny[2], J, gx, gy, active);
+                 a.g.field, pts, a.g.route.R, route_w2(a.g.route, pts, r), a.g.route.weight, (float)lane, nx[2], ny[2], J, gx, gy, active);
       motion_grad(nx, ny, lane, a.horizon, S2, A2, a.motion.w_speed, a.motion.w_accel, J, gx, gy, active);
     }
   } else if (lane < a.horizon) {
     const float* p = a.traj + ((size_t)r * a.horizon + lane) * a.dim;
     const int scene = r % a.g.scene_rows;
     float gx, gy;
+    const float* pts = route_points(a.g.route, r);
     guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, field_cells(a.g.field, r),
-               a.g.field, (float)lane, p[0], p[1], J, gx, gy, active);
+               a.g.field, pts, a.g.route.R, route_w2(a.g.route, pts, r), a.g.route.weight, (float)lane, p[0], p[1], J, gx, gy, active);
   }
   J = wave_sum(J);
 #pragma unroll
@@ -644,8 +682,8 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
   }
 }
 
-int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion, float* cost,
-               int32_t* active, int rows, int horizon, int dim, hipStream_t s) {
+int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+               const adx_guide_route* route, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s) {
   const char* const what = "guide cost";
   ADX_REQUIRE(traj != nullptr && (guide != nullptr || field != nullptr) && cost != nullptr && active != nullptr,
               "guide cost: null traj, guide, cost or active");
@@ -662,6 +700,10 @@ int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field*
   a.motion = MotionArgs{nullptr, 1, 0.f, 0.f};
   if (motion != nullptr) {
     rc = motion_check(motion, guide, field, what, cost, cn, active, cn, rows, horizon, &a.motion);
+    if (rc != ADX_OK) return rc;
+  }
+  if (route != nullptr) {
+    rc = route_check(route, guide, field, motion, what, cost, cn, active, cn, rows, &a.g.route);
     if (rc != ADX_OK) return rc;
   }
   a.traj = traj; a.cost = cost; a.active = active; a.rows = rows; a.horizon = horizon; a.dim = dim;

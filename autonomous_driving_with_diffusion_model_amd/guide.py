@@ -1,4 +1,4 @@
-"""Guide: where a sampling tick must NOT go ("cost guidance v1", include/adx.h).
+"""Guide: where a sampling tick must NOT go ("cost guidance v1", include/adx.h) -- and, since v4, where the road is.
 
 A guide is what the caller knows of the scene's obstacles -- moving discs (a parked car, a crossing pedestrian) and half-planes (a
 stop line, a lane edge) -- per scene, in the model's own units (the units of `target` and of the clamped result before xy
@@ -24,6 +24,12 @@ speed IS the spacing of the waypoints (the controller derives its desired speed 
 limit; `MotionLimits.from_physical` converts from m/s and m/s^2.  The terms couple neighbouring waypoints: a step with limits
 runs the row-wise step kernel (one wave per row, H <= 64).  A guide without limits is v1 / v2, bit for bit.
 
+A guide may also hold a ROUTE ("cost guidance v4"): `route=Route(points, half_width)`, per scene a polyline of R <= 32 points and a
+half-width: a waypoint further than the half-width from the polyline pays for it and is pulled back -- "stay in this lane / on this
+route", the one thing the reference's own driver has in hand every tick (its route planner's future waypoints).  The term is
+point-wise, so it runs in whichever step kernel the guide's other terms pick; `Route.from_physical` converts from metres.  A guide
+without a route is v1 / v2 / v3, bit for bit.
+
 No reference counterpart as a caller-facing object: the reference names the idea (GUIDANCE.LOSS_LIST) and has one entry, under
 CLASSIFIER_GUIDANCE only.  Whether guided plans drive better is a property of trained weights and is not measured in this
 repository.
@@ -41,6 +47,7 @@ from . import _lib as L
 SCHEDULES = ("variance", "constant")
 MAX_DISCS, MAX_PLANES, MAX_ITERS = 32, 8, 8
 MIN_NODES, MAX_NODES, MAX_RADIUS = 2, 256, 16
+MIN_ROUTE_POINTS, MAX_ROUTE_POINTS = 2, 32
 
 
 def _f32(v: float) -> float:
@@ -232,14 +239,111 @@ class MotionLimits:
         return f"MotionLimits(limits={tuple(self.limits.shape)}, w_speed={self.w_speed}, w_accel={self.w_accel})"
 
 
+class Route:
+    """The route corridor of "cost guidance v4" (include/adx.h): `points` float32 `[S, R, 2]` = per scene a polyline of R points
+    (x, y), 2 <= R <= 32, in the model's own units (the clamped result before xy scaling) and THIS tick's ego frame; segment i
+    joins point i and point i + 1, and a scene with fewer points pads by repeating its last one.  `half_width` float32 `[S]`, or a
+    number that stands for every scene: a waypoint whose squared distance d2 to the nearest segment exceeds `half_width**2` pays
+    `weight * (d2 - half_width**2)**2 / 2` and is pulled straight back toward the polyline; `inf` switches the term off for that
+    scene (a NaN does too), `0` means "pull onto the route".  `weight` >= 0; exactly 0 switches the term off everywhere.  The
+    squared excess is small in the model's units: a weight that makes the term dimensionless is `1 / w_ref**4` for a typical
+    half-width `w_ref` (an excess of w_ref^2 then costs 1/2, like a waypoint on a disc's centre).  The points and widths are read
+    at every step: new values need no new object (and, in a GraphedSampler, no new capture); R and the weight are baked.
+
+    With `TrajectorySelector(hard=True)` a candidate that leaves the corridor, by one ulp, is "not free"."""
+
+    def __init__(self, points: torch.Tensor, half_width, weight: float = 1.0):
+        if not torch.is_tensor(points):
+            raise TypeError(f"Route: points must be a tensor, got {type(points).__name__}")
+        if points.dim() != 3 or points.shape[2] != 2 or points.shape[0] < 1:
+            raise ValueError(f"Route: points must be [S, R, 2] = (x, y) per scene, got {tuple(points.shape)}")
+        if not MIN_ROUTE_POINTS <= points.shape[1] <= MAX_ROUTE_POINTS:
+            raise ValueError(f"Route: {points.shape[1]} points per scene, supported {MIN_ROUTE_POINTS}..{MAX_ROUTE_POINTS}")
+        if points.dtype != torch.float32:
+            raise TypeError(f"Route: points must be float32, got {points.dtype}")
+        S = int(points.shape[0])
+        if not torch.is_tensor(half_width):
+            try:
+                half_width = torch.full((S,), float(half_width), dtype=torch.float32, device=points.device)
+            except (TypeError, ValueError):
+                raise TypeError(f"Route: half_width must be a tensor [S] or a number, got {type(half_width).__name__}") from None
+        if half_width.dim() != 1 or half_width.shape[0] != S:
+            raise ValueError(f"Route: half_width must be [S] = [{S}] (or a number), got {tuple(half_width.shape)}")
+        if half_width.dtype != torch.float32:
+            raise TypeError(f"Route: half_width must be float32, got {half_width.dtype}")
+        if half_width.device != points.device:
+            raise ValueError(f"Route: points live on {points.device}, half_width on {half_width.device}")
+        weight = float(weight)
+        if not weight >= 0.0:
+            raise ValueError(f"Route: weight must be >= 0, got {weight}")
+        self.points, self.half_width, self.weight = points.contiguous(), half_width.contiguous(), weight
+
+    @property
+    def scenes(self) -> int:
+        return int(self.points.shape[0])
+
+    @property
+    def R(self) -> int:
+        return int(self.points.shape[1])
+
+    @property
+    def device(self) -> torch.device:
+        return self.points.device
+
+    def key(self) -> tuple:
+        """What a captured graph bakes: everything but the values of the points and widths."""
+        return (self.R, self.weight)
+
+    def like(self, points: torch.Tensor, half_width) -> "Route":
+        """The same weight over other points and widths."""
+        return Route(points, half_width, self.weight)
+
+    def desc(self, x: torch.Tensor) -> L.RouteDesc:
+        """The `adx_guide_route` of a launch on `x` [B, H, D].  The struct holds addresses: keep this object alive until the
+        launch is enqueued."""
+        for name, t in (("guide.route.points", self.points), ("guide.route.half_width", self.half_width)):
+            if L.require_gpu_f32(t, name).device != x.device:
+                raise ValueError(f"{name} lives on {t.device}, the sample on {x.device}")
+        r = L.RouteDesc()
+        r.points, r.half_width = self.points.data_ptr(), self.half_width.data_ptr()
+        r.scene_rows, r.n_points, r.weight = self.scenes, self.R, self.weight
+        return r
+
+    @staticmethod
+    def from_physical(points_m, half_width_m, xy_scale: float, weight: float = 1.0, device=None) -> "Route":
+        """A route from metres, on the host: `points_m` [S, R, 2] (a tensor or nested sequences) in metres in this tick's ego
+        frame, `half_width_m` a number or a sequence of S numbers (one per scene; a number stands for all), `xy_scale` the metres
+        of one model unit (`model.magic_num`).  Each coordinate and width is divided by `xy_scale` in double and rounded to fp32
+        once.  `inf` stays `inf`."""
+        xy_scale = float(xy_scale)
+        if not (math.isfinite(xy_scale) and xy_scale > 0.0):
+            raise ValueError(f"Route.from_physical: xy_scale must be finite and > 0, got {xy_scale}")
+        pts = torch.as_tensor(points_m).detach().to("cpu", torch.float64)
+        if pts.dim() != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
+            raise ValueError(f"Route.from_physical: points_m must be [S, R, 2], got {tuple(pts.shape)}")
+        S = int(pts.shape[0])
+        w = [float(t) for t in (half_width_m if hasattr(half_width_m, "__len__") else [half_width_m])]
+        if len(w) not in (1, S):
+            raise ValueError(f"Route.from_physical: points_m hold {S} scenes, half_width_m {len(w)}")
+        w = w * (S // len(w))
+        if not all(q >= 0.0 for q in w):
+            raise ValueError(f"Route.from_physical: half_width_m must be >= 0 (inf: no corridor), got {w}")
+        dev = device or "cpu"
+        return Route((pts / xy_scale).to(torch.float32).to(dev),
+                     (torch.tensor(w, dtype=torch.float64) / xy_scale).to(torch.float32).to(dev), weight)
+
+    def __repr__(self):
+        return f"Route(points={tuple(self.points.shape)}, half_width={tuple(self.half_width.shape)}, weight={self.weight})"
+
+
 class Guide:
     """`discs` float32 `[S, M, 5]` and / or `planes` float32 `[S, P, 3]` on one device (None: no such constraint); `scale`,
-    `schedule`, `cap`, `iters` as the module docstring says; `field`: a CostField or None, `motion`: a MotionLimits or None
-    (both keyword only).  The tensors are read at every step: new values need no new object (and, in a GraphedSampler, no new capture)."""
+    `schedule`, `cap`, `iters` as the module docstring says; `field`: a CostField or None, `motion`: a MotionLimits or None,
+    `route`: a Route or None (all keyword only).  The tensors are read at every step: new values need no new object (and, in a GraphedSampler, no new capture)."""
 
     def __init__(self, discs: Optional[torch.Tensor] = None, planes: Optional[torch.Tensor] = None, scale: float = 1.0,
                  schedule: str = "variance", cap: float = float("inf"), iters: int = 1, *, field: Optional[CostField] = None,
-                 motion: Optional[MotionLimits] = None):
+                 motion: Optional[MotionLimits] = None, route: Optional[Route] = None):
         for name, t, last, most in (("discs", discs, 5, MAX_DISCS), ("planes", planes, 3, MAX_PLANES)):
             if t is None:
                 continue
@@ -277,6 +381,18 @@ class Guide:
                     raise ValueError(f"Guide: {name} live on {t.device}, the motion limits on {motion.device}")
                 if t.shape[0] != motion.scenes:
                     raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the motion limits {motion.scenes}")
+        if route is not None:
+            if not isinstance(route, Route):
+                raise TypeError(f"Guide: route must be a Route or None, got {type(route).__name__}")
+            others = (("discs", discs), ("planes", planes), ("field", None if field is None else field.cells),
+                      ("motion limits", None if motion is None else motion.limits))
+            for name, t in others:
+                if t is None or (name in ("discs", "planes") and t.shape[1] == 0):
+                    continue
+                if t.device != route.device:
+                    raise ValueError(f"Guide: {name} live on {t.device}, the route on {route.device}")
+                if t.shape[0] != route.scenes:
+                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the route {route.scenes}")
         if schedule not in SCHEDULES:
             raise ValueError(f"Guide: schedule must be one of {SCHEDULES}, got {schedule!r}")
         scale, cap = float(scale), float(cap)
@@ -289,7 +405,7 @@ class Guide:
         self.discs = None if discs is None else discs.contiguous()
         self.planes = None if planes is None else planes.contiguous()
         self.scale, self.schedule, self.cap, self.iters = scale, schedule, cap, int(iters)
-        self.field, self.motion = field, motion
+        self.field, self.motion, self.route = field, motion, route
 
     # ---- shape ----
     @property
@@ -313,28 +429,34 @@ class Guide:
 
     def _first(self) -> Optional[torch.Tensor]:
         """The tensor that says how many scenes the guide holds and where: discs, else planes, else the field's cells, else the
-        motion limits."""
+        motion limits, else the route's points."""
         if self.discs is not None:
             return self.discs
         if self.planes is not None:
             return self.planes
         if self.field is not None:
             return self.field.cells
-        return None if self.motion is None else self.motion.limits
+        if self.motion is not None:
+            return self.motion.limits
+        return None if self.route is None else self.route.points
 
     def key(self) -> tuple:
         """What a captured graph bakes: everything but the values of discs, planes and the field's cells.  Without a field the
         6-tuple of cost guidance v1; with one, the field's key appended.  With motion limits: the 6-tuple followed by the field's
-        key or None and the limits' key."""
+        key or None and the limits' key.  With a route: the 6-tuple, the field's key or None, the limits' key or None, the
+        route's key.  A guide without a route keeps the key it had."""
         key = (self.M, self.P, self.scale, self.schedule, self.cap, self.iters)
+        if self.route is not None:
+            return key + (None if self.field is None else self.field.key(), None if self.motion is None else self.motion.key(),
+                          self.route.key())
         if self.motion is not None:
             return key + (None if self.field is None else self.field.key(), self.motion.key())
         return key if self.field is None else key + (self.field.key(),)
 
     def like(self, discs: Optional[torch.Tensor], planes: Optional[torch.Tensor], field: Optional[CostField] = None,
-             motion: Optional[MotionLimits] = None) -> "Guide":
+             motion: Optional[MotionLimits] = None, route: Optional[Route] = None) -> "Guide":
         """The same settings over other tensors."""
-        return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters, field=field, motion=motion)
+        return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters, field=field, motion=motion, route=route)
 
     # ---- launches ----
     def desc(self, x: torch.Tensor, lam: float = 0.0) -> L.GuideDesc:
@@ -364,10 +486,17 @@ class Guide:
         then goes through the `_field` or `_guide` export."""
         return None if self.motion is None else self.motion.desc(x)
 
+    def route_desc(self, x: torch.Tensor) -> Optional[L.RouteDesc]:
+        """The `adx_guide_route` of a launch on `x` ("cost guidance v4"), or None for a guide without a route: the launch then
+        goes through the `_motion`, `_field` or `_guide` export."""
+        return None if self.route is None else self.route.desc(x)
+
     def descs(self, x: torch.Tensor, lam: float = 0.0):
-        """`(export suffix, byref arguments, the structs)` of a guided launch on `x`: "guide", "field" or "motion" and the
-        records that export takes after the pin, in its order.  Keep the structs alive until the launch is enqueued."""
-        g, f, m = self.desc(x, lam), self.field_desc(x), self.motion_desc(x)
+        """`(export suffix, byref arguments, the structs)` of a guided launch on `x`: "guide", "field", "motion" or "route" and
+        the records that export takes after the pin, in its order.  Keep the structs alive until the launch is enqueued."""
+        g, f, m, r = self.desc(x, lam), self.field_desc(x), self.motion_desc(x), self.route_desc(x)
+        if r is not None:
+            return "route", (C.byref(g), None if f is None else C.byref(f), None if m is None else C.byref(m), C.byref(r)), (g, f, m, r)
         if m is not None:
             return "motion", (C.byref(g), None if f is None else C.byref(f), C.byref(m)), (g, f, m)
         if f is not None:
@@ -383,8 +512,12 @@ class Guide:
         rows, H, D = traj.shape
         cost = torch.empty(rows, dtype=torch.float32, device=traj.device)
         active = torch.empty(rows, dtype=torch.int32, device=traj.device)
-        f, m = self.field_desc(traj), self.motion_desc(traj)
-        if m is not None:
+        f, m, r = self.field_desc(traj), self.motion_desc(traj), self.route_desc(traj)
+        if r is not None:
+            L.check(L.lazy("adx_guide_cost_route")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f),
+                                                   None if m is None else C.byref(m), C.byref(r), cost.data_ptr(), active.data_ptr(),
+                                                   rows, H, D, L.stream_ptr(traj.device)), "adx_guide_cost_route")
+        elif m is not None:
             L.check(L.lazy("adx_guide_cost_motion")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f), C.byref(m),
                                                     cost.data_ptr(), active.data_ptr(), rows, H, D, L.stream_ptr(traj.device)),
                     "adx_guide_cost_motion")
@@ -400,4 +533,5 @@ class Guide:
         return (f"Guide(discs={None if self.discs is None else tuple(self.discs.shape)}, "
                 f"planes={None if self.planes is None else tuple(self.planes.shape)}, scale={self.scale}, schedule={self.schedule!r}, "
                 f"cap={self.cap}, iters={self.iters}" + ("" if self.field is None else f", field={self.field!r}") +
-                ("" if self.motion is None else f", motion={self.motion!r}") + ")")
+                ("" if self.motion is None else f", motion={self.motion!r}") +
+                ("" if self.route is None else f", route={self.route!r}") + ")")

@@ -34,6 +34,8 @@ the steps, `Guide.cost`, the guided selector, the warm state, the controller and
 `CostField.from_occupancy` makes the raster from an occupancy grid in one launch ("cost field from occupancy v1").
 A tenth says how fast to go: `guide=Guide(..., motion=MotionLimits(limits))` caps the length of a segment and of a second difference
 per scene ("cost guidance v3"); every step then runs the row-wise step kernel, one wave per row.
+An eleventh says where the road is: `guide=Guide(..., route=Route(points, half_width))` keeps the plan within a half-width of a
+per-scene polyline ("cost guidance v4"), a point-wise term of the same routine, so it runs in whichever step kernel the rest picks.
 """
 from __future__ import annotations
 
@@ -194,7 +196,8 @@ class TickPlan:
     # guidance branches) and moves its x0 inside its kernel; the K * S rows read the [S, ..] obstacles directly (row r reads scene
     # r % S), nothing is tiled.  A guide's field ("cost guidance v2"): the cells are a buffer like discs and planes; presence, (Gy, Gx),
     # origin, cell size and weight are baked (by-value arguments of every step node) -- all of it through `Guide.key()`.  A guide's
-    # motion limits ("cost guidance v3"): the [S, 2] limits are a buffer; presence and the two weights are baked, the same way
+    # motion limits ("cost guidance v3"): the [S, 2] limits are a buffer; presence and the two weights are baked, the same way.  A
+    # guide's route ("cost guidance v4"): the [S, R, 2] points and [S] half-widths are buffers; presence, R and the weight are baked
     guide: Optional[Guide]
 
     def key(self) -> tuple:
@@ -251,7 +254,9 @@ def _guide_plan(cfg, guide: Optional[Guide], image, scheduler) -> Optional[Guide
         raise TypeError(f"generate_traj: `guide` must be a Guide, got {type(guide).__name__}")
     S = int(image.shape[0])
     for name, t in (("discs", guide.discs), ("planes", guide.planes), ("field.cells", None if guide.field is None else guide.field.cells),
-                    ("motion.limits", None if guide.motion is None else guide.motion.limits)):
+                    ("motion.limits", None if guide.motion is None else guide.motion.limits),
+                    ("route.points", None if guide.route is None else guide.route.points),
+                    ("route.half_width", None if guide.route is None else guide.route.half_width)):
         if t is not None and (int(t.shape[0]) != S or t.device != image.device):
             raise ValueError(f"guide.{name} must hold {S} scenes (image.shape[0]) on {image.device}, got {tuple(t.shape)} on {t.device}")
     if int(cfg.MODEL.TRANSITION_DIM) < 2:
@@ -587,6 +592,7 @@ class GraphedSampler:
     M, P, scale, schedule, cap and iters are part of the graph key (every step node holds its lambda by value), new obstacle values
     never capture again.  A guide's `field` travels the same way: the cells through a static buffer, its presence, shape, geometry
     and weight through the key.  So do a guide's motion limits: the limits through a static buffer, presence and weights through the key.
+    And a guide's route: points and half-widths through static buffers, presence, R and weight through the key.
     """
 
     MAX_GRAPHS = 4
@@ -628,7 +634,9 @@ class GraphedSampler:
         g.guide = None if guide is None else guide.like(None if guide.discs is None else guide.discs.clone(),
                                                         None if guide.planes is None else guide.planes.clone(),
                                                         None if guide.field is None else guide.field.like(guide.field.cells.clone()),
-                                                        None if guide.motion is None else guide.motion.like(guide.motion.limits.clone()))
+                                                        None if guide.motion is None else guide.motion.like(guide.motion.limits.clone()),
+                                                        None if guide.route is None else guide.route.like(guide.route.points.clone(),
+                                                                                                         guide.route.half_width.clone()))
         ctl = self.controller
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
@@ -744,6 +752,9 @@ class GraphedSampler:
                     g.guide.field.cells.copy_(guide.field.cells)
                 if guide.motion is not None:
                     g.guide.motion.limits.copy_(guide.motion.limits)
+                if guide.route is not None:
+                    g.guide.route.points.copy_(guide.route.points)
+                    g.guide.route.half_width.copy_(guide.route.half_width)
         self._key, self._graph, self._sel, self._ctl = key, g.graph, g.sel, g.ctl
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured

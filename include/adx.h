@@ -1048,6 +1048,86 @@ int adx_traj_select_guide_motion(const adx_select_guide_cfg* c, const float* tra
                                  int32_t* index, int32_t* blocked, float* best, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Cost guidance v4: cost guidance v3 plus a ROUTE CORRIDOR -- where the road is.  v1 to v3 say where not to go and how fast; the
+ * route is a per-scene polyline and a half-width, and a waypoint further than the half-width from the polyline pays for it and
+ * is pulled back.  v1, v2 and v3 stay as they are: the _guide, _field and _motion exports, their structs and their bits; v4 stands
+ * beside them as the _route exports, each the _motion export with one more argument.  The term is point-wise and couples no
+ * neighbours, so it is one more term of the routine every guided kernel calls and reaches all of them: the element-wise step
+ * kernels (no limits), the row-wise ones (limits), adx_guide_cost and the guided selection, which agree on its bits.  Callers and
+ * fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ * Everything is in the model's own units (the clamped result BEFORE xy scaling) and this tick's ego frame, as in v1.
+ *
+ *   points      float32 [scene_rows][R][2] = (x, y) in device memory, 2 <= R <= 32 (ADX_ROUTE_MAX_POINTS), read at every launch.
+ *               Segment i joins point i and point i+1, 0 <= i <= R-2.  Row r of a launch reads scene r % scene_rows.  Scenes with
+ *               fewer points pad by repeating their last point: a degenerate segment is a legal segment, the point itself
+ *               (t = 0, r = u).  Where that point is the nearest of the route, a padding segment's residual p - b may beat the last
+ *               real segment's (p - a) - (b - a) by a rounding; nowhere else does padding change a bit.
+ *   half_width  float32 [scene_rows] in device memory, read at every launch.  W2 = w * w, one rounded product, formed in the
+ *               kernel.  +inf switches the term off for that scene; so does a NaN, because every comparison with it is false.
+ *               0 is legal: "pull onto the route".
+ *   weight      a host scalar by value, >= 0.  At exactly 0 the term is not evaluated and counts nothing in `active`.
+ *   term        of one waypoint (x, y), evaluated AFTER v2's field term and BEFORE v3's motion terms into the same J, gx, gy and
+ *               active count.  fp32, no contraction, every operation rounded on its own, in this order (px[i], py[i] are the
+ *               points'):
+ *                 best = +inf;  qx = qy = 0
+ *                 for i = 0 .. R-2, in index order:
+ *                   ax = px[i];  ay = py[i];  ex = px[i+1] - ax;  ey = py[i+1] - ay
+ *                   ux = x - ax;  uy = y - ay
+ *                   ee = ex * ex + ey * ey;  ue = ux * ex + uy * ey
+ *                   t  = ee > 0 ? ue / ee : 0;   t = t < 0 ? 0 : (t > 1 ? 1 : t)            (a NaN passes through)
+ *                   rx = ux - t * ex;  ry = uy - t * ey;  d2 = rx * rx + ry * ry
+ *                   if d2 < best: best = d2; qx = rx; qy = ry       (strict: the first of equals wins; a NaN never wins)
+ *                 phi = best - W2;   active iff best < +inf and phi > 0
+ *                 J = J + (weight * (phi * phi)) / 2;   k = weight * (2 * phi)
+ *                 gx = gx + k * qx;   gy = gy + k * qy;   active = active + 1
+ *               No square root.  The gradient is exact (d best / dp = 2 q) except on the medial axis, where it is the first
+ *               winner's.  An inactive term adds nothing, not even a zero: a guide whose route term is off (weight 0, every
+ *               width +inf) accumulates exactly the bits of v3 (or v2, or v1).
+ *   the rest    iters, lambda, cap, `moved`, the order inside a step and everything after the guide are v1's (or v3's, with
+ *               limits), word for word.  In the element-wise kernels the x and the y thread of a waypoint each repeat its
+ *               iterations, as in v1, so the term is evaluated twice per waypoint there.
+ *   kernels     `field` and `motion` may each be NULL.  A NULL motion runs the element-wise kernels, a non-NULL one the row-wise
+ *               ones (and needs horizon <= 64, as in v3).  No kernel is added: the guided kernels branch on points != NULL, which
+ *               is the same in every thread of a launch.
+ *   cost        adx_guide_cost_route: per waypoint J as above, summed by v1's butterfly.  adx_traj_select_guide_route: violation,
+ *               active, free and blocked of selection cost v2 carry the route term among the others; the route's scene_rows
+ *               equals `scenes`.  With `hard`, a candidate that leaves the corridor -- by one ulp of best - W2 -- is "not free".
+ *   NULL        a NULL route is exactly the _motion export.
+ *
+ * ADX_ERR_INVALID before any GPU work, each with its own text: NULL points or half_width; n_points outside 2..32; scene_rows < 1
+ * or not dividing batch; scene_rows disagreeing with the guide's (when it holds discs or planes), the field's or the limits'; a
+ * weight negative or NaN; an output overlapping points or half_width; a step with a route and no adx_guide; and whatever the
+ * _motion export refuses.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_ROUTE_MIN_POINTS 2
+#define ADX_ROUTE_MAX_POINTS 32
+typedef struct adx_guide_route {
+  const float* points;         /* [scene_rows][n_points][2] = (x, y) */
+  const float* half_width;     /* [scene_rows] */
+  int32_t scene_rows, n_points;
+  float weight;
+} adx_guide_route;
+int adx_ddim_step_route(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route, float* prev,
+                        float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+int adx_ddpm_step_route(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route, float* prev,
+                        float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+int adx_dpm_step_route(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                       const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route, float* prev_sample,
+                       float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s);
+int adx_guide_cost_route(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+                         const adx_guide_route* route, float* cost, int32_t* active, int32_t rows, int32_t horizon, int32_t dim,
+                         adx_stream s);
+int adx_traj_select_guide_route(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
+                                const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                                float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Cost field from occupancy v1: a cost raster for cost guidance v2 from a binary occupancy raster, one launch.  The value at a
  * node is the disc potential of cost guidance v1 around the NEAREST occupied node: 0.5 on an obstacle, falling to 0 at distance
  * `margin`.  No square root.  Capturable: no allocation, no synchronisation, no host decision.  Callers and fixtures depend on

@@ -27,8 +27,15 @@ limits (`m32p8i8` and `m32p8i8.lim`, beside `none`) at 1 and 64 scenes, and the 
 DPM-Solver++ `scheduler.step` with that guide, 20 calls captured in one graph and replayed, with limits (the row-wise kernel: a
 wave per row) and without (the element-wise kernel), per launch.  The limits (0.05, 0.03) are ones a fresh draw exceeds.
 
+`--route` runs a third leg instead ("cost guidance v4", a route corridor): the graph tick at 1 and 64 scenes with no guide, with
+the largest guide (`m32p8i8`) and with the same plus a route of 32 points (`m32p8i8.r32`, iters=8 like the rest: 31 segments with
+one division each per iteration, twice per waypoint in the element-wise kernel), and the last two again with limits beside them
+(`m32p8i8.lim`, `m32p8i8.lim.r32`: the row-wise kernel, once per waypoint).  The route winds through [-0.8, 0.8]^2 at half-width
+0.1, which a fresh draw mostly lies outside of.
+
     python tools/guide_tick_probe.py --json profiles/guide_tick_probe.json
     python tools/guide_tick_probe.py --motion --json profiles/motion_tick_probe.json
+    python tools/guide_tick_probe.py --route --json profiles/route_tick_probe.json
 """
 import argparse
 import contextlib
@@ -40,7 +47,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from autonomous_driving_with_diffusion_model_amd import CostField, DeviceNoise, Guide, MotionLimits  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd import CostField, DeviceNoise, Guide, MotionLimits, Route  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd import scheduler as S  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd.config import create_cfg  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd.modeling import build_model  # noqa: E402
@@ -55,8 +62,12 @@ ARMS = (("none", None, None, False), ("m4p2i1", (4, 2, 1), None, False), ("m32p8
         ("f64i1", (0, 0, 1), 64, False), ("m4p2i1.f256", (4, 2, 1), 256, False), ("m4p2i8.f256", (4, 2, 8), 256, False),
         ("m4p2i1.occ", (4, 2, 1), 256, True))
 MARGIN = 0.125                         # of the occupancy arm: 16 cells of 2 / 256
-# the --motion leg: (name, (M, P, iters) or None, motion limits or not)
-MOTION_ARMS = (("none", None, False), ("m32p8i8", (32, 8, 8), False), ("m32p8i8.lim", (32, 8, 8), True))
+# the --motion leg: (name, (M, P, iters) or None, motion limits or not, points of a route or 0)
+MOTION_ARMS = (("none", None, False, 0), ("m32p8i8", (32, 8, 8), False, 0), ("m32p8i8.lim", (32, 8, 8), True, 0))
+# the --route leg
+ROUTE_ARMS = (("none", None, False, 0), ("m32p8i8", (32, 8, 8), False, 0), ("m32p8i8.r32", (32, 8, 8), False, 32),
+              ("m32p8i8.lim", (32, 8, 8), True, 0), ("m32p8i8.lim.r32", (32, 8, 8), True, 32))
+HALF_WIDTH = 0.1                       # of every scene's route
 LIMITS = (0.05, 0.03)                  # (s_max, a_max) of every scene
 STEP_CALLS = 20                        # step launches per captured graph
 
@@ -81,7 +92,14 @@ def field(scenes, G, dev):
     return CostField.from_occupancy(occupancy(scenes, G, dev), (-1.0, -1.0), (cell, cell), 16 * cell)
 
 
-def obstacles(scenes, M, P, iters, dev, field=None, motion=False):
+def route(scenes, R, dev):
+    """A [scenes, R, 2] polyline: x walks from -0.8 to 0.8, y = 0.5 sin(3 x + the scene's phase)."""
+    x = torch.linspace(-0.8, 0.8, R).repeat(scenes, 1)
+    y = 0.5 * torch.sin(3.0 * x + torch.arange(scenes, dtype=torch.float32)[:, None])
+    return Route(torch.stack([x, y], dim=2).to(dev), HALF_WIDTH)
+
+
+def obstacles(scenes, M, P, iters, dev, field=None, motion=False, points=0):
     g = torch.Generator().manual_seed(11)
     discs = torch.zeros(scenes, M, 5)
     discs[..., :2] = torch.rand(scenes, M, 2, generator=g) - 0.5
@@ -91,11 +109,12 @@ def obstacles(scenes, M, P, iters, dev, field=None, motion=False):
     planes[..., :2] = torch.rand(scenes, P, 2, generator=g) * 2 - 1
     planes[..., 2] = torch.rand(scenes, P, generator=g) * 0.5
     return Guide(discs.to(dev) if M else None, planes.to(dev) if P else None, scale=0.2, schedule="variance", cap=0.1, iters=iters,
-                 field=field, motion=MotionLimits(torch.tensor([LIMITS] * scenes, device=dev)) if motion else None)
+                 field=field, motion=MotionLimits(torch.tensor([LIMITS] * scenes, device=dev)) if motion else None,
+                 route=route(scenes, points, dev) if points else None)
 
 
-def motion_arms(dev, n):
-    """The graph ticks of the --motion leg: `arms` with MOTION_ARMS."""
+def motion_arms(dev, n, which=MOTION_ARMS):
+    """The graph ticks of the --motion and --route legs: `arms` with MOTION_ARMS or ROUTE_ARMS."""
     fns, meta = {}, {}
     for scenes, horizon in SIZES:
         cfg = make_cfg(n, horizon)
@@ -104,10 +123,10 @@ def motion_arms(dev, n):
         P.load_procedural(model, 0)
         model = model.to(dev).eval()
         d = {k: v.to(dev) for k, v in P.synthetic_batch(scenes, horizon, image_hw=IMG, seed=3).items()}
-        for arm, mpi, lim in MOTION_ARMS:
+        for arm, mpi, lim, points in which:
             sch = S.GuidanceDDIMScheduler(cfg=cfg, thresholding=True, **SCHED_KW)
             gs = GraphedSampler(model, sch, cfg, noise=DeviceNoise(7, dev))
-            guide = None if mpi is None else obstacles(scenes, *mpi, dev, motion=lim)
+            guide = None if mpi is None else obstacles(scenes, *mpi, dev, motion=lim, points=points)
             fns[f"s{scenes}.{arm}"] = (lambda gs=gs, img=d["imgs"], tgt=d["target"], guide=guide: gs(img, tgt, guide=guide))
             meta[f"s{scenes}.{arm}"] = (scenes, horizon, arm)
     return fns, meta
@@ -195,11 +214,17 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--arms", default=None, help="comma-separated arm names (default: all); the ratios need `none` and `m4p2i1` among them")
     ap.add_argument("--motion", action="store_true", help="the motion-limits leg instead: see the module docstring")
+    ap.add_argument("--route", action="store_true", help="the route-corridor leg instead: see the module docstring")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     n = a.steps
     with torch.no_grad():
-        fns, meta = motion_arms(dev, n) if a.motion else arms(dev, n, None if a.arms is None else a.arms.split(","))
+        if a.route:
+            fns, meta = motion_arms(dev, n, ROUTE_ARMS)
+        elif a.motion:
+            fns, meta = motion_arms(dev, n)
+        else:
+            fns, meta = arms(dev, n, None if a.arms is None else a.arms.split(","))
         ticks = {}
         for fn in fns.values():                 # warm every arm: the capture, then replays ...
             for _ in range(3):
@@ -220,6 +245,9 @@ def main():
         with torch.no_grad():
             record["limits"], record["step_launches"] = list(LIMITS), step_launches(dev, a.rounds)
         record["limits_over_m32p8i8"] = {}
+    if a.route:
+        record["route"] = {"points": 32, "half_width": HALF_WIDTH, "weight": 1.0}
+        record["added_ms"] = {}
     for k in fns:
         scenes, horizon, mode = meta[k]
         med = statistics.median(ms[k])
@@ -231,6 +259,13 @@ def main():
             ref = record["arms"].get(f"s{v['scenes']}.{base}")
             if v["guide"] != "none" and ref is not None:
                 record[over][k] = round(v["median_ms"] / ref["median_ms"], 4)
+    if a.route:                     # what each layer adds to the tick: the 32 discs and 8 planes over none, the route over those
+        for scenes, _ in SIZES:
+            med = {arm: record["arms"][f"s{scenes}.{arm}"]["median_ms"] for arm, _, _, _ in ROUTE_ARMS}
+            record["added_ms"][f"s{scenes}"] = {"m32p8i8 over none": round(med["m32p8i8"] - med["none"], 4),
+                                                "r32 over m32p8i8": round(med["m32p8i8.r32"] - med["m32p8i8"], 4),
+                                                "r32 over m32p8i8.lim": round(med["m32p8i8.lim.r32"] - med["m32p8i8.lim"], 4)}
+        print(json.dumps(record["added_ms"]), file=sys.stderr)
     if a.motion:
         for scenes, _ in SIZES:
             record["limits_over_m32p8i8"][f"s{scenes}"] = round(record["arms"][f"s{scenes}.m32p8i8.lim"]["median_ms"] /
