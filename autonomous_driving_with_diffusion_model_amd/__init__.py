@@ -14,6 +14,7 @@ Public surface mirrors the reference's packages:
     CostField                                         (no reference counterpart: a cost raster in a Guide, guide.py)
     MotionLimits                                      (no reference counterpart: speed and acceleration limits in a Guide, guide.py)
     Route                                             (no reference counterpart: a route corridor in a Guide, guide.py)
+    Capsules                                          (no reference counterpart: moving capsules in a Guide, guide.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -35,9 +36,9 @@ from .scheduler import GuidanceDPMSolverMultistepScheduler  # noqa: E402
 from .control.select import Selection, TrajectorySelector  # noqa: E402
 from .control.device import DeviceController  # noqa: E402
 from .pin import Pin  # noqa: E402
-from .guide import CostField, Guide, MotionLimits, Route  # noqa: E402
+from .guide import Capsules, CostField, Guide, MotionLimits, Route  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
-           "Route"]
+           "Route", "Capsules"]

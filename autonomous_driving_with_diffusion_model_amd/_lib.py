@@ -96,6 +96,11 @@ class RouteDesc(C.Structure):
     _fields_ = [("points", vp), ("half_width", vp), ("scene_rows", i32), ("n_points", i32), ("weight", f32)]
 
 
+class CapsuleDesc(C.Structure):
+    """adx_guide_capsules ("cost guidance v5", include/adx.h)."""
+    _fields_ = [("capsules", vp), ("scene_rows", i32), ("n_capsules", i32), ("weight", f32)]
+
+
 class SelectCfg(C.Structure):
     _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("w_goal", f32), ("w_smooth", f32),
                 ("w_consensus", f32)]
@@ -269,6 +274,20 @@ _LAZY_SIGS = {
                                    i32, i32, i32, vp]),
     "adx_traj_select_guide_route": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
                                           C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, vp, vp, vp, vp]),
+    "adx_ddim_step_capsule": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                    C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp,
+                                    i32, i32, i32, vp]),
+    "adx_ddpm_step_capsule": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                    C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp,
+                                    i32, i32, i32, vp]),
+    "adx_dpm_step_capsule": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
+                                   C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp,
+                                   i32, i32, i32, vp]),
+    "adx_guide_cost_capsule": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc),
+                                     C.POINTER(CapsuleDesc), vp, vp, i32, i32, i32, vp]),
+    "adx_traj_select_guide_capsule": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
+                                            C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp, vp, vp, vp, vp]),
+    "adx_capsules_from_boxes": (i32, [vp, vp, i32, i32, f32, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)

@@ -68,8 +68,9 @@ int embed_forward(const adx_embed_weights* w, int dim, const int64_t* t, int t_r
 int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
                 hipStream_t s);
 int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
-                      const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route, float* cost,
-                      int32_t* active, int32_t* index, int32_t* blocked, float* best, hipStream_t s);
+                      const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                      const adx_guide_capsules* capsules, float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best,
+                      hipStream_t s);
 size_t control_state_bytes(int scenes, int n_turn, int n_speed);
 int control_step(const adx_control_cfg* c, const float* traj, const float* velocity, const float* target, void* state,
                  float* control, hipStream_t s);
@@ -237,7 +238,7 @@ int adx_dpm_step_guide(const adx_dpm_coef* c, const float* model_output, const f
 }
 int adx_guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int32_t rows, int32_t horizon,
                    int32_t dim, adx_stream s) {
-  return adx::guide_cost(traj, guide, nullptr, nullptr, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
+  return adx::guide_cost(traj, guide, nullptr, nullptr, nullptr, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
 }
 int adx_pin_apply(float* x, const adx_pin* pin, const uint32_t* noise_state, int64_t row_offset, int32_t batch, int32_t horizon,
                   int32_t dim, adx_stream s) {
@@ -249,7 +250,7 @@ int adx_traj_select(const adx_select_cfg* c, const float* trajs, const float* ta
 }
 int adx_traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                           float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, nullptr, nullptr, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
+  return adx::traj_select_guide(c, trajs, target, guide, nullptr, nullptr, nullptr, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
 }
 // "cost guidance v2": the _guide exports with a field; the same records through the same run functions
 int adx_ddim_step_field(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
@@ -284,12 +285,12 @@ int adx_dpm_step_field(const adx_dpm_coef* c, const float* model_output, const f
 }
 int adx_guide_cost_field(const float* traj, const adx_guide* guide, const adx_guide_field* field, float* cost, int32_t* active,
                          int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::guide_cost(traj, guide, field, nullptr, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
+  return adx::guide_cost(traj, guide, field, nullptr, nullptr, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
 }
 int adx_traj_select_guide_field(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                                 const adx_guide_field* field, float* cost, int32_t* active, int32_t* index, int32_t* blocked,
                                 float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, field, nullptr, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
+  return adx::traj_select_guide(c, trajs, target, guide, field, nullptr, nullptr, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
 }
 // "cost guidance v3": the _field exports with motion limits; the same records through the same run functions, which launch the
 // row-wise kernels when the record holds limits
@@ -325,12 +326,12 @@ int adx_dpm_step_motion(const adx_dpm_coef* c, const float* model_output, const 
 }
 int adx_guide_cost_motion(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
                           float* cost, int32_t* active, int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::guide_cost(traj, guide, field, motion, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
+  return adx::guide_cost(traj, guide, field, motion, nullptr, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
 }
 int adx_traj_select_guide_motion(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                                  const adx_guide_field* field, const adx_guide_motion* motion, float* cost, int32_t* active,
                                  int32_t* index, int32_t* blocked, float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, field, motion, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
+  return adx::traj_select_guide(c, trajs, target, guide, field, motion, nullptr, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
 }
 // "cost guidance v4": the _motion exports with a route corridor; the same records through the same run functions.  The route is a
 // term of guide_grad, so it rides in whichever kernel the record picks: element-wise without limits, row-wise with them
@@ -367,12 +368,62 @@ int adx_dpm_step_route(const adx_dpm_coef* c, const float* model_output, const f
 int adx_guide_cost_route(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
                          const adx_guide_route* route, float* cost, int32_t* active, int32_t rows, int32_t horizon, int32_t dim,
                          adx_stream s) {
-  return adx::guide_cost(traj, guide, field, motion, route, cost, active, rows, horizon, dim, (hipStream_t)s);
+  return adx::guide_cost(traj, guide, field, motion, route, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
 }
 int adx_traj_select_guide_route(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                                 const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
                                 float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, field, motion, route, cost, active, index, blocked, best, (hipStream_t)s);
+  return adx::traj_select_guide(c, trajs, target, guide, field, motion, route, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
+}
+// "cost guidance v5": the _route exports with moving capsules; the same records through the same run functions.  The capsules are a
+// term of guide_grad, like the route, so they ride in whichever kernel the record picks
+int adx_ddim_step_capsule(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                          const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                          const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                          const adx_guide_capsules* capsules, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
+                          adx_stream s) {
+  adx::StepCall k;
+  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
+  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route;
+  k.capsules = capsules; k.prev = prev; k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
+}
+int adx_ddpm_step_capsule(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                          const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                          const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                          const adx_guide_capsules* capsules, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
+                          adx_stream s) {
+  adx::StepCall k;
+  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
+  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route;
+  k.capsules = capsules; k.prev = prev; k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::step_run(k);
+}
+int adx_dpm_step_capsule(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                         const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                         const adx_guide_capsules* capsules, float* prev_sample, float* x0, int32_t batch, int32_t horizon,
+                         int32_t dim, adx_stream s) {
+  adx::DpmCall k;
+  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
+  k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route; k.capsules = capsules; k.prev = prev_sample;
+  k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return adx::dpm_run(k);
+}
+int adx_guide_cost_capsule(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+                           const adx_guide_route* route, const adx_guide_capsules* capsules, float* cost, int32_t* active,
+                           int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::guide_cost(traj, guide, field, motion, route, capsules, cost, active, rows, horizon, dim, (hipStream_t)s);
+}
+int adx_traj_select_guide_capsule(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
+                                  const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                                  const adx_guide_capsules* capsules, float* cost, int32_t* active, int32_t* index, int32_t* blocked,
+                                  float* best, adx_stream s) {
+  return adx::traj_select_guide(c, trajs, target, guide, field, motion, route, capsules, cost, active, index, blocked, best,
+                                (hipStream_t)s);
+}
+int adx_capsules_from_boxes(const float* boxes, float* out, int32_t scenes, int32_t n_boxes, float inflate, adx_stream s) {
+  return adx::capsules_from_boxes(boxes, out, scenes, n_boxes, inflate, (hipStream_t)s);
 }
 int adx_cost_field_from_occupancy(const float* occ, float* cells, int32_t scenes, int32_t gy, int32_t gx, float dx, float dy,
                                   float inv_m2, int32_t ry, int32_t rx, adx_stream s) {

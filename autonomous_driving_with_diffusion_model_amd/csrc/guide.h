@@ -2,6 +2,7 @@
 // that evaluates a waypoint's cost.  The step kernels and guide_cost_kernel (sched.hip) and the guided select kernel (select.hip) all
 // call it, so what a step steers by, what adx_guide_cost reports and what a selection scores are the same bits.
 // "Cost guidance v4" adds the route corridor to that routine, after the field term: a per-scene polyline and a half-width.
+// "Cost guidance v5" adds moving capsules to that routine, after the route term: per scene up to 32 segments with a radius.
 // "Cost guidance v3" adds motion_grad beside it: a waypoint's share of the terms that couple it to its neighbours, for the row-wise
 // step kernels, guide_cost_kernel<true> and traj_select_kernel<true, true>.
 #pragma once
@@ -26,6 +27,14 @@ struct RouteArgs {
   float weight;
 };
 
+// Cost guidance v5: slots [scene_rows][C][7] = (ax, ay, bx, by, vx, vy, r); row r of a launch reads scene r % scene_rows.
+// slots == nullptr: no capsules, and nothing else of the record is read
+struct CapsuleArgs {
+  const float* slots;
+  int scene_rows, C;
+  float weight;
+};
+
 // Cost guidance v1: discs [scene_rows][M][5], planes [scene_rows][P][3]; row r of a launch reads scene r % scene_rows
 struct GuideArgs {
   const float* discs;
@@ -34,6 +43,7 @@ struct GuideArgs {
   float lambda, cap;
   FieldArgs field;      // cost guidance v2
   RouteArgs route;      // cost guidance v4
+  CapsuleArgs capsule;  // cost guidance v5
 };
 
 // The raster of row `row`'s scene, or nullptr without a field (uniform across a launch)
@@ -48,6 +58,13 @@ __device__ __forceinline__ const float* route_points(const RouteArgs& r, int row
   return r.points == nullptr || r.weight == 0.f ? nullptr : r.points + (size_t)(row % r.scene_rows) * r.R * 2;
 }
 
+// The capsules of row `row`'s scene, or nullptr without capsules or at weight 0, where the term is not evaluated (uniform across a
+// launch).  Read from global memory as they lie: a scene's capsules are at most 896 bytes that every lane of the scene reads at the
+// same addresses.
+__device__ __forceinline__ const float* capsule_slots(const CapsuleArgs& c, int row) {
+  return c.slots == nullptr || c.weight == 0.f ? nullptr : c.slots + (size_t)(row % c.scene_rows) * c.C * 7;
+}
+
 // W2 of row `row`'s scene: the square of its half-width, one rounded product; `pts` is route_points(r, row)
 __device__ __forceinline__ float route_w2(const RouteArgs& r, const float* pts, int row) {
 #pragma clang fp contract(off)
@@ -56,14 +73,16 @@ __device__ __forceinline__ float route_w2(const RouteArgs& r, const float* pts, 
   return w * w;
 }
 
-// Cost guidance v1 / v2 / v4: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs, P planes and, when
+// Cost guidance v1 / v2 / v4 / v5: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs, P planes and, when
 // `cells` (the scene's raster, field_cells) is not null, the field `f`; its gradient and the number of active terms; the contracts'
 // operations in the contracts' order, each rounded on its own.  Without a field the accumulation is v1's, bit for bit.  When `pts`
 // (the scene's polyline, route_points) is not null, the route term of v4 follows: the nearest of the R - 1 segments against W2
-// (route_w2) at weight rw.  Without a route the accumulation is v2's, bit for bit.
+// (route_w2) at weight rw.  Without a route the accumulation is v2's, bit for bit.  When `caps` (the scene's capsules,
+// capsule_slots) is not null, the capsule term of v5 follows: the Cn slots at weight cw, each v1's disc potential around the nearest
+// point of its moved segment.  Without capsules the accumulation is v4's, bit for bit.
 __device__ __forceinline__ void guide_grad(const float* discs, int M, const float* planes, int P, const float* cells, const FieldArgs& f,
-                                           const float* pts, int R, float W2, float rw, float hf, float x, float y, float& J, float& gx,
-                                           float& gy, int& active) {
+                                           const float* pts, int R, float W2, float rw, const float* caps, int Cn, float cw, float hf,
+                                           float x, float y, float& J, float& gx, float& gy, int& active) {
 #pragma clang fp contract(off)
   J = 0.f; gx = 0.f; gy = 0.f; active = 0;
   for (int i = 0; i < M; ++i) {
@@ -165,6 +184,44 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
       gx = gx + kx;
       gy = gy + ky;
       ++active;
+    }
+  }
+  if (caps != nullptr) {      // the capsule term: v1's disc potential around the nearest point of each moved segment; no square root
+    for (int i = 0; i < Cn; ++i) {
+      const float* q = caps + i * 7;
+      const float r = q[6];
+      if (!(r > 0.f)) continue;                  // an empty slot (a NaN radius too)
+      const float ax = q[0], ay = q[1];
+      const float hx = hf * q[4], hy = hf * q[5];
+      const float px = ax + hx, py = ay + hy;
+      const float ex = q[2] - ax, ey = q[3] - ay;      // from the unmoved ends: both move alike
+      const float ux = x - px, uy = y - py;
+      const float exx = ex * ex, eyy = ey * ey;
+      const float ee = exx + eyy;
+      const float uxe = ux * ex, uye = uy * ey;
+      const float ue = uxe + uye;
+      float t = ee > 0.f ? ue / ee : 0.f;       // a == b: a disc around a
+      t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);      // a NaN passes through
+      const float tx = t * ex, ty = t * ey;
+      const float rx = ux - tx, ry = uy - ty;
+      const float rxx = rx * rx, ryy = ry * ry;
+      const float d2 = rxx + ryy;
+      const float rr = r * r;
+      const float inv = 1.0f / rr;
+      const float sd = d2 * inv;
+      const float phi = 1.0f - sd;
+      if (phi > 0.f) {
+        const float pp = phi * phi;
+        const float wp = cw * pp;
+        J = J + wp / 2.0f;
+        const float p2 = 2.0f * phi;
+        const float pk = p2 * inv;
+        const float k = cw * pk;
+        const float kx = k * rx, ky = k * ry;
+        gx = gx - kx;
+        gy = gy - ky;
+        ++active;
+      }
     }
   }
 }

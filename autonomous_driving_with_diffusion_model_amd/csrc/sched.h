@@ -24,6 +24,7 @@ struct StepCall {
   const adx_guide_field* field = nullptr;      // cost guidance v2: the GUIDE kernel with a raster
   const adx_guide_motion* motion = nullptr;    // cost guidance v3: step_rows_kernel<ddpm, ns != null, pin != null> instead
   const adx_guide_route* route = nullptr;      // cost guidance v4: a route corridor in whichever kernel runs
+  const adx_guide_capsules* capsules = nullptr;      // cost guidance v5: moving capsules in whichever kernel runs
   float* prev = nullptr;
   float* x0 = nullptr;                // optional
   int batch = 0, horizon = 0, dim = 0;
@@ -45,6 +46,7 @@ struct DpmCall {
   const adx_guide_field* field = nullptr;      // cost guidance v2
   const adx_guide_motion* motion = nullptr;    // cost guidance v3: dpm_step_rows_kernel<pin != null> instead
   const adx_guide_route* route = nullptr;      // cost guidance v4
+  const adx_guide_capsules* capsules = nullptr;      // cost guidance v5
   float* prev = nullptr;
   float* x0 = nullptr;                // always written
   int batch = 0, horizon = 0, dim = 0;
@@ -72,8 +74,18 @@ int motion_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_
 // each may be null.
 int route_check(const adx_guide_route* r, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m, const char* what,
                 const void* out, size_t on, const void* out2, size_t on2, int batch, RouteArgs* a);
+// The refusals of "cost guidance v5" that every launch with capsules shares, after guide_check (which leaves GuideArgs without
+// capsules), motion_check and route_check, filling CapsuleArgs: the array, the slot count, scene_rows against `batch` and against the
+// guide's, the field's, the limits' and the route's, the weight and the outputs against the array.  `g`, `f`, `m` and `r` are the
+// (checked) records beside it; each may be null.
+int capsule_check(const adx_guide_capsules* c, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m,
+                  const adx_guide_route* r, const char* what, const void* out, size_t on, const void* out2, size_t on2, int batch,
+                  CapsuleArgs* a);
 int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
-               const adx_guide_route* route, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s);
+               const adx_guide_route* route, const adx_guide_capsules* capsules, float* cost, int32_t* active, int rows, int horizon,
+               int dim, hipStream_t s);
+// "Capsules from boxes v1" (capsule.hip)
+int capsules_from_boxes(const float* boxes, float* out, int scenes, int n_boxes, float inflate, hipStream_t s);
 int field_from_occupancy(const float* occ, float* cells, int scenes, int gy, int gx, float dx, float dy, float inv_m2, int ry, int rx,
                          hipStream_t s);
 int pin_apply(float* x, const adx_pin* pin, const uint32_t* ns, int64_t row_offset, int batch, int horizon, int dim, hipStream_t s);

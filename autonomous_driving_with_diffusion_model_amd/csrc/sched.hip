@@ -147,12 +147,14 @@ __device__ __forceinline__ bool guide_x0(const GuideArgs& g, const float* mo, co
   const float* cells = field_cells(g.field, row);      // cost guidance v2: null without a field, the same in every thread
   const float* pts = route_points(g.route, row);       // cost guidance v4: null without a route, the same in every thread
   const float W2 = route_w2(g.route, pts, row);
+  const float* caps = capsule_slots(g.capsule, row);   // cost guidance v5: null without capsules, the same in every thread
   const float hf = (float)h;
   bool moved = false;
   for (int it = 0; it < g.iters; ++it) {
     float J, gx, gy;
     int active;
-    guide_grad(discs, g.M, planes, g.P, cells, g.field, pts, g.route.R, W2, g.route.weight, hf, px, py, J, gx, gy, active);
+    guide_grad(discs, g.M, planes, g.P, cells, g.field, pts, g.route.R, W2, g.route.weight, caps, g.capsule.C, g.capsule.weight, hf, px, py,
+               J, gx, gy, active);
     const float lx = g.lambda * gx, ly = g.lambda * gy;
     const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
     moved = moved || (d == 0 ? sx : sy) != 0.f;
@@ -201,6 +203,7 @@ __device__ __forceinline__ void guide_rows(const GuideArgs& g, const MotionArgs&
   const float* cells = field_cells(g.field, row);
   const float* pts = route_points(g.route, row);
   const float W2 = route_w2(g.route, pts, row);
+  const float* caps = capsule_slots(g.capsule, row);
   float S2, A2;
   motion_limits(mo, row, S2, A2);
   const float hf = (float)lane;
@@ -215,7 +218,8 @@ __device__ __forceinline__ void guide_rows(const GuideArgs& g, const MotionArgs&
     if (live) {
       float J, gx, gy;
       int active;
-      guide_grad(discs, g.M, planes, g.P, cells, g.field, pts, g.route.R, W2, g.route.weight, hf, px, py, J, gx, gy, active);
+      guide_grad(discs, g.M, planes, g.P, cells, g.field, pts, g.route.R, W2, g.route.weight, caps, g.capsule.C, g.capsule.weight, hf, px, py,
+               J, gx, gy, active);
       motion_grad(nx, ny, lane, H, S2, A2, mo.w_speed, mo.w_accel, J, gx, gy, active);
       const float lx = g.lambda * gx, ly = g.lambda * gy;
       const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
@@ -316,6 +320,7 @@ static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const
 // step, which also reads iters, cap and lambda; `out2` may be null
 static const FieldArgs kNoField = {nullptr, 1, 2, 2, 0.f, 0.f, 0.f, 0.f, 0.f};
 static const RouteArgs kNoRoute = {nullptr, nullptr, 1, 2, 0.f};
+static const CapsuleArgs kNoCapsule = {nullptr, 1, 1, 0.f};
 
 static bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for inf and NaN
 
@@ -375,10 +380,11 @@ int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, 
   a->iters = g->iters; a->lambda = g->lambda; a->cap = g->cap;
   a->field = kNoField;
   a->route = kNoRoute;
+  a->capsule = kNoCapsule;
   return f == nullptr ? ADX_OK : field_check(f, g, what, out, on, out2, on2, batch, &a->field);
 }
 
-static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f, kNoField, kNoRoute};
+static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f, kNoField, kNoRoute, kNoCapsule};
 
 // the refusals of "cost guidance v3" that are the motion limits' own, after guide_check (sched.h)
 int motion_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, const void* out, size_t on,
@@ -424,6 +430,31 @@ int route_check(const adx_guide_route* r, const adx_guide* g, const adx_guide_fi
   return ADX_OK;
 }
 
+// the refusals of "cost guidance v5" that are the capsules' own, after guide_check, motion_check and route_check (sched.h)
+int capsule_check(const adx_guide_capsules* c, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m,
+                  const adx_guide_route* r, const char* what, const void* out, size_t on, const void* out2, size_t on2, int batch,
+                  CapsuleArgs* a) {
+  ADX_REQUIRE(c->capsules != nullptr, "%s: null capsules", what);
+  ADX_REQUIRE(c->n_capsules >= 1 && c->n_capsules <= ADX_CAPSULE_MAX, "%s: n_capsules %d outside 1..%d", what, c->n_capsules,
+              ADX_CAPSULE_MAX);
+  ADX_REQUIRE(c->scene_rows >= 1 && batch % c->scene_rows == 0, "%s: batch %d must be a positive multiple of the capsules' scene_rows %d",
+              what, batch, c->scene_rows);
+  ADX_REQUIRE(g == nullptr || (g->n_discs == 0 && g->n_planes == 0) || g->scene_rows == c->scene_rows,
+              "%s: the capsules hold %d scenes, the guide's discs and planes %d", what, c->scene_rows, g == nullptr ? 0 : g->scene_rows);
+  ADX_REQUIRE(f == nullptr || f->scene_rows == c->scene_rows, "%s: the capsules hold %d scenes, the field %d", what, c->scene_rows,
+              f == nullptr ? 0 : f->scene_rows);
+  ADX_REQUIRE(m == nullptr || m->scene_rows == c->scene_rows, "%s: the capsules hold %d scenes, the motion limits %d", what,
+              c->scene_rows, m == nullptr ? 0 : m->scene_rows);
+  ADX_REQUIRE(r == nullptr || r->scene_rows == c->scene_rows, "%s: the capsules hold %d scenes, the route %d", what, c->scene_rows,
+              r == nullptr ? 0 : r->scene_rows);
+  ADX_REQUIRE(c->weight >= 0.f, "%s: capsule weight %g is negative or NaN", what, (double)c->weight);
+  const size_t cn = (size_t)c->scene_rows * c->n_capsules * 7 * sizeof(float);
+  ADX_REQUIRE(!byte_ranges_overlap(out, on, c->capsules, cn) && (out2 == nullptr || !byte_ranges_overlap(out2, on2, c->capsules, cn)),
+              "%s: an output overlaps the capsules", what);
+  a->slots = c->capsules; a->scene_rows = c->scene_rows; a->C = c->n_capsules; a->weight = c->weight;
+  return ADX_OK;
+}
+
 // a step with motion limits: guide_check's refusals with the limits' own text where there is no adx_guide to read iters from
 static int motion_step_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, bool inpaint,
                              float* prev, float* x0, int batch, int horizon, int dim, GuideArgs* ga, MotionArgs* ma) {
@@ -433,17 +464,22 @@ static int motion_step_check(const adx_guide_motion* m, const adx_guide* g, cons
   return rc != ADX_OK ? rc : motion_check(m, g, f, what, prev, on, x0, on, batch, horizon, ma);
 }
 
-// a step's guide records, checked in the contracts' order into GuideArgs (and MotionArgs when there are limits): a route without an
-// adx_guide gets its own text, as limits do
+// a step's guide records, checked in the contracts' order into GuideArgs (and MotionArgs when there are limits): a route or
+// capsules without an adx_guide get their own text, as limits do
 static int guided_step_check(const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m, const adx_guide_route* r,
-                             const char* what, bool inpaint, float* prev, float* x0, int batch, int horizon, int dim, GuideArgs* ga,
-                             MotionArgs* ma) {
+                             const adx_guide_capsules* cp, const char* what, bool inpaint, float* prev, float* x0, int batch, int horizon,
+                             int dim, GuideArgs* ga, MotionArgs* ma) {
   ADX_REQUIRE(r == nullptr || g != nullptr, "%s: a route without a guide: a step reads iters, lambda and cap from the guide", what);
+  ADX_REQUIRE(cp == nullptr || g != nullptr, "%s: capsules without a guide: a step reads iters, lambda and cap from the guide", what);
   const size_t on = (size_t)batch * horizon * dim * sizeof(float);
   const int rc = m != nullptr ? motion_step_check(m, g, f, what, inpaint, prev, x0, batch, horizon, dim, ga, ma)
                               : guide_check(g, f, what, true, inpaint, prev, on, x0, on, batch, dim, ga);
-  if (rc != ADX_OK || r == nullptr) return rc;
-  return route_check(r, g, f, m, what, prev, on, x0, on, batch, &ga->route);
+  if (rc != ADX_OK) return rc;
+  if (r != nullptr) {
+    const int rr = route_check(r, g, f, m, what, prev, on, x0, on, batch, &ga->route);
+    if (rr != ADX_OK) return rr;
+  }
+  return cp == nullptr ? ADX_OK : capsule_check(cp, g, f, m, r, what, prev, on, x0, on, batch, &ga->capsule);
 }
 
 int step_run(const StepCall& k) {
@@ -455,7 +491,8 @@ int step_run(const StepCall& k) {
 #undef ADX_STEP_KERNELS
   const char* const what = "scheduler step";
   const adx_step_coef* c = k.c;
-  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr, guided = k.guide != nullptr || k.field != nullptr || k.route != nullptr;
+  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr, guided = k.guide != nullptr || k.field != nullptr || k.route != nullptr ||
+                                                                          k.capsules != nullptr;
   ADX_REQUIRE(k.z == nullptr || !rng, "scheduler step: a noise tensor and a noise state are both given");
   ADX_REQUIRE(c && k.mo && k.x && k.prev, "scheduler step: null tensor");
   int rc = shape_check(what, k.batch, k.horizon, k.dim);
@@ -472,9 +509,9 @@ int step_run(const StepCall& k) {
   }
   a.guide = kNoGuide;
   StepRowsArgs ra;
-  if (guided || k.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route): in whichever runs
-    rc = guided_step_check(k.guide, k.field, k.motion, k.route, what, c->inpaint != 0, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.guide,
-                           &ra.motion);
+  if (guided || k.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route), v5 (capsules): in whichever runs
+    rc = guided_step_check(k.guide, k.field, k.motion, k.route, k.capsules, what, c->inpaint != 0, k.prev, k.x0, k.batch, k.horizon,
+                           k.dim, &a.guide, &ra.motion);
     if (rc != ADX_OK) return rc;
   }
   if (rng) {
@@ -599,10 +636,11 @@ int dpm_run(const DpmCall& k) {
     }
   }
   a.guide = kNoGuide;
-  const bool guided = k.guide != nullptr || k.field != nullptr || k.route != nullptr;
+  const bool guided = k.guide != nullptr || k.field != nullptr || k.route != nullptr || k.capsules != nullptr;
   DpmRowsArgs ra;
-  if (guided || k.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route): in whichever runs
-    rc = guided_step_check(k.guide, k.field, k.motion, k.route, what, false, k.prev, k.x0, k.batch, k.horizon, k.dim, &a.guide, &ra.motion);
+  if (guided || k.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route), v5 (capsules): in whichever runs
+    rc = guided_step_check(k.guide, k.field, k.motion, k.route, k.capsules, what, false, k.prev, k.x0, k.batch, k.horizon, k.dim,
+                           &a.guide, &ra.motion);
     if (rc != ADX_OK) return rc;
   }
   a.c = *c;
@@ -662,7 +700,8 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
       motion_limits(a.motion, r, S2, A2);
       const float* pts = route_points(a.g.route, r);
       guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, field_cells(a.g.field, r),
-                 a.g.field, pts, a.g.route.R, route_w2(a.g.route, pts, r), a.g.route.weight, (float)lane, nx[2], ny[2], J, gx, gy, active);
+                 a.g.field, pts, a.g.route.R, route_w2(a.g.route, pts, r), a.g.route.weight,
+                 capsule_slots(a.g.capsule, r), a.g.capsule.C, a.g.capsule.weight, (float)lane, nx[2], ny[2], J, gx, gy, active);
       motion_grad(nx, ny, lane, a.horizon, S2, A2, a.motion.w_speed, a.motion.w_accel, J, gx, gy, active);
     }
   } else if (lane < a.horizon) {
@@ -671,7 +710,8 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
     float gx, gy;
     const float* pts = route_points(a.g.route, r);
     guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, field_cells(a.g.field, r),
-               a.g.field, pts, a.g.route.R, route_w2(a.g.route, pts, r), a.g.route.weight, (float)lane, p[0], p[1], J, gx, gy, active);
+               a.g.field, pts, a.g.route.R, route_w2(a.g.route, pts, r), a.g.route.weight,
+               capsule_slots(a.g.capsule, r), a.g.capsule.C, a.g.capsule.weight, (float)lane, p[0], p[1], J, gx, gy, active);
   }
   J = wave_sum(J);
 #pragma unroll
@@ -683,7 +723,8 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
 }
 
 int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
-               const adx_guide_route* route, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s) {
+               const adx_guide_route* route, const adx_guide_capsules* capsules, float* cost, int32_t* active, int rows, int horizon,
+               int dim, hipStream_t s) {
   const char* const what = "guide cost";
   ADX_REQUIRE(traj != nullptr && (guide != nullptr || field != nullptr) && cost != nullptr && active != nullptr,
               "guide cost: null traj, guide, cost or active");
@@ -704,6 +745,10 @@ int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field*
   }
   if (route != nullptr) {
     rc = route_check(route, guide, field, motion, what, cost, cn, active, cn, rows, &a.g.route);
+    if (rc != ADX_OK) return rc;
+  }
+  if (capsules != nullptr) {
+    rc = capsule_check(capsules, guide, field, motion, route, what, cost, cn, active, cn, rows, &a.g.capsule);
     if (rc != ADX_OK) return rc;
   }
   a.traj = traj; a.cost = cost; a.active = active; a.rows = rows; a.horizon = horizon; a.dim = dim;

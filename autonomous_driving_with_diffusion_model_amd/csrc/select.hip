@@ -23,6 +23,7 @@
 // With motion limits ("cost guidance v3", the kMotion instantiation) a waypoint's share of the segment and curvature terms follows,
 // through guide.h's motion_grad; its four neighbours are read from the xy planes in LDS.
 // With a route ("cost guidance v4") guide_grad also reads the scene's polyline, from global memory: no kernel variant, a uniform branch.
+// With capsules ("cost guidance v5") it reads the scene's slots the same way.
 #include "sched.h"
 
 namespace adx {
@@ -147,7 +148,8 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
         float jx, jy;
         const float* pts = route_points(a.guide.route, s);      // cost guidance v4: from global memory, like the raster
         guide_grad(disc_s, a.guide.M, plane_s, a.guide.P, field_cells(a.guide.field, s), a.guide.field, pts, a.guide.route.R,
-                   route_w2(a.guide.route, pts, s), a.guide.route.weight, (float)lane, px, py, J, jx, jy, act);
+                   route_w2(a.guide.route, pts, s), a.guide.route.weight, capsule_slots(a.guide.capsule, s), a.guide.capsule.C,
+                   a.guide.capsule.weight, (float)lane, px, py, J, jx, jy, act);
         if constexpr (kMotion) {      // the neighbours from the planes; a point outside the row is a zero no term reads
           float nx[5], ny[5], S2, A2;
 #pragma unroll
@@ -262,8 +264,9 @@ int traj_select(const adx_select_cfg* c, const float* trajs, const float* target
 // "Selection cost v2": v1's refusals first, then what the guide adds; `field` (cost guidance v2) may be null, and with a field the
 // guide may be null too (no discs, no planes)
 int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
-                      const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route, float* cost,
-                      int32_t* active, int32_t* index, int32_t* blocked, float* best, hipStream_t s) {
+                      const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                      const adx_guide_capsules* capsules, float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best,
+                      hipStream_t s) {
   const char* const what = "traj select guide";
   ADX_REQUIRE(c != nullptr, "traj select: null configuration");
   int rc = select_check(c->scenes, c->candidates, c->horizon, c->dim, trajs, cost, index, best);
@@ -315,6 +318,14 @@ int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const f
     for (int i = 0; i < 3; ++i)
       ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], route->points, pn) && !overlaps(outs[i], out_bytes[i], route->half_width, wn),
                   "traj select guide: an output overlaps the route's points or half_width");
+  }
+  if (capsules != nullptr) {      // cost guidance v5; scene_rows == S for the reason the field gives
+    rc = capsule_check(capsules, guide, field, motion, route, what, cost, sk_bytes, active, sk_bytes, S * K, &a.guide.capsule);
+    if (rc != ADX_OK) return rc;
+    ADX_REQUIRE(capsules->scene_rows == S, "traj select guide: the capsules hold %d scenes, the selection %d", capsules->scene_rows, S);
+    const size_t cn = (size_t)capsules->scene_rows * capsules->n_capsules * 7 * sizeof(float);
+    for (int i = 0; i < 3; ++i)
+      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], capsules->capsules, cn), "traj select guide: an output overlaps the capsules");
   }
   ADX_REQUIRE(!overlaps(active, sk_bytes, trajs, in_bytes) && !overlaps(blocked, s_bytes, trajs, in_bytes),
               "traj select guide: an output aliases trajs");

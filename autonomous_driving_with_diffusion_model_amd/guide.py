@@ -30,6 +30,12 @@ route", the one thing the reference's own driver has in hand every tick (its rou
 point-wise, so it runs in whichever step kernel the guide's other terms pick; `Route.from_physical` converts from metres.  A guide
 without a route is v1 / v2 / v3, bit for bit.
 
+A guide may also hold CAPSULES ("cost guidance v5"): `capsules=Capsules(slots)`, per scene up to 32 moving segments with a radius
+-- the other road users as a perception stack reports them, oriented boxes with a heading, which one disc fits badly.  The
+potential is the disc's around the nearest point of the segment, so a disc is the capsule of zero length.  The term is point-wise,
+like the route; `Capsules.from_boxes` converts boxes on the device in one launch, `Capsules.boxes_from_physical` prepares them from
+metres, m/s and a yaw angle.  A guide without capsules is v1 .. v4, bit for bit.
+
 No reference counterpart as a caller-facing object: the reference names the idea (GUIDANCE.LOSS_LIST) and has one entry, under
 CLASSIFIER_GUIDANCE only.  Whether guided plans drive better is a property of trained weights and is not measured in this
 repository.
@@ -48,6 +54,7 @@ SCHEDULES = ("variance", "constant")
 MAX_DISCS, MAX_PLANES, MAX_ITERS = 32, 8, 8
 MIN_NODES, MAX_NODES, MAX_RADIUS = 2, 256, 16
 MIN_ROUTE_POINTS, MAX_ROUTE_POINTS = 2, 32
+MAX_CAPSULES = 32
 
 
 def _f32(v: float) -> float:
@@ -336,14 +343,138 @@ class Route:
         return f"Route(points={tuple(self.points.shape)}, half_width={tuple(self.half_width.shape)}, weight={self.weight})"
 
 
+class Capsules:
+    """The moving capsules of "cost guidance v5" (include/adx.h): `slots` float32 `[S, C, 7]` = per scene C slots
+    `(ax, ay, bx, by, vx, vy, r)`, 1 <= C <= 32, in the model's own units (the clamped result before xy scaling) and THIS tick's
+    ego frame: the segment from a to b with radius r, both ends moving by `(vx, vy)` per waypoint.  A waypoint closer than r to
+    the moved segment pays `weight * (1 - d2 / r^2)^2 / 2` -- v1's disc potential around the nearest point of the axis -- and is
+    pushed straight away from it; a slot with `r <= 0` (or NaN) is empty, so scenes with fewer vehicles pad with zeros, and
+    `a == b` is a disc.  `weight` >= 0; exactly 0 switches the term off everywhere.  The slots are read at every step: new values
+    need no new object (and, in a GraphedSampler, no new capture); C and the weight are baked.
+
+    `Capsules.from_boxes` makes the slots from oriented boxes in one launch ("capsules from boxes v1"); the capsule is a box's
+    INSCRIBED stadium, so its corners stick out by up to `(sqrt(2) - 1) * width / 2`: cover that, and the ego's own radius, with
+    `inflate`.  With `TrajectorySelector(hard=True)` a candidate inside a capsule, by one ulp, is "not free"."""
+
+    def __init__(self, slots: torch.Tensor, weight: float = 1.0):
+        if not torch.is_tensor(slots):
+            raise TypeError(f"Capsules: slots must be a tensor, got {type(slots).__name__}")
+        if slots.dim() != 3 or slots.shape[2] != 7 or slots.shape[0] < 1:
+            raise ValueError(f"Capsules: slots must be [S, C, 7] = (ax, ay, bx, by, vx, vy, r) per slot, got {tuple(slots.shape)}")
+        if not 1 <= slots.shape[1] <= MAX_CAPSULES:
+            raise ValueError(f"Capsules: {slots.shape[1]} slots per scene, supported 1..{MAX_CAPSULES}")
+        if slots.dtype != torch.float32:
+            raise TypeError(f"Capsules: slots must be float32, got {slots.dtype}")
+        weight = float(weight)
+        if not weight >= 0.0:
+            raise ValueError(f"Capsules: weight must be >= 0, got {weight}")
+        self.slots, self.weight = slots.contiguous(), weight
+
+    @property
+    def scenes(self) -> int:
+        return int(self.slots.shape[0])
+
+    @property
+    def C(self) -> int:
+        return int(self.slots.shape[1])
+
+    @property
+    def device(self) -> torch.device:
+        return self.slots.device
+
+    def key(self) -> tuple:
+        """What a captured graph bakes: everything but the values of the slots."""
+        return (self.C, self.weight)
+
+    def like(self, slots: torch.Tensor) -> "Capsules":
+        """The same weight over other slots."""
+        return Capsules(slots, self.weight)
+
+    def desc(self, x: torch.Tensor) -> L.CapsuleDesc:
+        """The `adx_guide_capsules` of a launch on `x` [B, H, D].  The struct holds an address: keep this object alive until the
+        launch is enqueued."""
+        if L.require_gpu_f32(self.slots, "guide.capsules.slots").device != x.device:
+            raise ValueError(f"guide.capsules.slots lives on {self.slots.device}, the sample on {x.device}")
+        c = L.CapsuleDesc()
+        c.capsules, c.scene_rows, c.n_capsules, c.weight = self.slots.data_ptr(), self.scenes, self.C, self.weight
+        return c
+
+    @staticmethod
+    def _boxes(t, what: str, last: int) -> None:
+        if not torch.is_tensor(t):
+            raise TypeError(f"Capsules.from_boxes: {what} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 3 or t.shape[2] != last or t.shape[0] < 1:
+            raise ValueError(f"Capsules.from_boxes: {what} must be [S, N, {last}], got {tuple(t.shape)}")
+        if not 1 <= t.shape[1] <= MAX_CAPSULES:
+            raise ValueError(f"Capsules.from_boxes: {t.shape[1]} boxes per scene, supported 1..{MAX_CAPSULES}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"Capsules.from_boxes: {what} must be float32, got {t.dtype}")
+
+    @staticmethod
+    def from_boxes(boxes: torch.Tensor, inflate: float = 0.0, weight: float = 1.0, out: Optional[torch.Tensor] = None) -> "Capsules":
+        """Capsules from oriented boxes `boxes` float32 [S, N, 8] = (cx, cy, vx, vy, ux, uy, length, width), one launch of
+        `adx_capsules_from_boxes` ("capsules from boxes v1"): `(ux, uy)` is the UNIT heading along `length` (the caller
+        normalises it; `boxes_from_physical` does), everything in the model's units.  Box j becomes slot j: the inscribed stadium
+        along the longer side with radius `shorter / 2 + inflate`; a box with a size <= 0 or NaN becomes an empty slot.
+        `inflate`: finite and >= 0, the ego's own radius (and the corners' overhang).  `out`: slots [S, N, 7] to write (a static
+        buffer of a captured graph); None allocates."""
+        Capsules._boxes(boxes, "boxes", 8)
+        inflate = float(inflate)
+        if not (math.isfinite(inflate) and inflate >= 0.0):
+            raise ValueError(f"Capsules.from_boxes: inflate must be finite and >= 0, got {inflate}")
+        weight = float(weight)
+        if not weight >= 0.0:
+            raise ValueError(f"Capsules: weight must be >= 0, got {weight}")
+        boxes = L.require_gpu_f32(boxes, "boxes").contiguous()
+        S, N, _ = boxes.shape
+        if out is None:
+            out = torch.empty((S, N, 7), dtype=torch.float32, device=boxes.device)
+        else:
+            Capsules._boxes(out, "out", 7)
+            if out.shape[:2] != boxes.shape[:2] or out.device != boxes.device or not out.is_contiguous():
+                raise ValueError(f"Capsules.from_boxes: out must be contiguous {(S, N, 7)} on {boxes.device}, got "
+                                 f"{tuple(out.shape)} on {out.device}")
+        L.check(L.lazy("adx_capsules_from_boxes")(boxes.data_ptr(), out.data_ptr(), S, N, inflate, L.stream_ptr(boxes.device)),
+                "adx_capsules_from_boxes")
+        return Capsules(out, weight)
+
+    @staticmethod
+    def boxes_from_physical(boxes_m, dt: float, xy_scale: float, device=None) -> torch.Tensor:
+        """The `[S, N, 8]` device format of `from_boxes` from a detector's boxes, on the host: `boxes_m` [S, N, 7] =
+        (cx, cy, vx, vy, yaw, length, width) (a tensor or nested sequences) with positions and sizes in metres in this tick's ego
+        frame, speeds in m/s and yaw in radians; `dt` the seconds between two waypoints, `xy_scale` the metres of one model unit
+        (`model.magic_num`).  Positions and sizes are divided by `xy_scale`, speeds multiplied by `dt / xy_scale`, the heading is
+        `(cos yaw, sin yaw)`; all in double, rounded to fp32 once."""
+        dt, xy_scale = float(dt), float(xy_scale)
+        if not (math.isfinite(xy_scale) and xy_scale > 0.0):
+            raise ValueError(f"Capsules.boxes_from_physical: xy_scale must be finite and > 0, got {xy_scale}")
+        if not (math.isfinite(dt) and dt > 0.0):
+            raise ValueError(f"Capsules.boxes_from_physical: dt must be finite and > 0, got {dt}")
+        # nested sequences of Python floats are doubles: read them as such, not through torch's default float32
+        b = boxes_m.detach().to("cpu", torch.float64) if torch.is_tensor(boxes_m) else torch.as_tensor(boxes_m, dtype=torch.float64)
+        if b.dim() != 3 or b.shape[2] != 7 or b.shape[0] < 1:
+            raise ValueError(f"Capsules.boxes_from_physical: boxes_m must be [S, N, 7] = (cx, cy, vx, vy, yaw, length, width), got "
+                             f"{tuple(b.shape)}")
+        out = torch.empty(b.shape[:2] + (8,), dtype=torch.float64)
+        out[..., 0:2] = b[..., 0:2] / xy_scale
+        out[..., 2:4] = b[..., 2:4] * (dt / xy_scale)
+        out[..., 4] = torch.cos(b[..., 4])
+        out[..., 5] = torch.sin(b[..., 4])
+        out[..., 6:8] = b[..., 5:7] / xy_scale
+        return out.to(torch.float32).to(device or "cpu")
+
+    def __repr__(self):
+        return f"Capsules(slots={tuple(self.slots.shape)}, weight={self.weight})"
+
+
 class Guide:
     """`discs` float32 `[S, M, 5]` and / or `planes` float32 `[S, P, 3]` on one device (None: no such constraint); `scale`,
     `schedule`, `cap`, `iters` as the module docstring says; `field`: a CostField or None, `motion`: a MotionLimits or None,
-    `route`: a Route or None (all keyword only).  The tensors are read at every step: new values need no new object (and, in a GraphedSampler, no new capture)."""
+    `route`: a Route or None, `capsules`: a Capsules or None (all keyword only).  The tensors are read at every step: new values need no new object (and, in a GraphedSampler, no new capture)."""
 
     def __init__(self, discs: Optional[torch.Tensor] = None, planes: Optional[torch.Tensor] = None, scale: float = 1.0,
                  schedule: str = "variance", cap: float = float("inf"), iters: int = 1, *, field: Optional[CostField] = None,
-                 motion: Optional[MotionLimits] = None, route: Optional[Route] = None):
+                 motion: Optional[MotionLimits] = None, route: Optional[Route] = None, capsules: Optional[Capsules] = None):
         for name, t, last, most in (("discs", discs, 5, MAX_DISCS), ("planes", planes, 3, MAX_PLANES)):
             if t is None:
                 continue
@@ -393,6 +524,18 @@ class Guide:
                     raise ValueError(f"Guide: {name} live on {t.device}, the route on {route.device}")
                 if t.shape[0] != route.scenes:
                     raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the route {route.scenes}")
+        if capsules is not None:
+            if not isinstance(capsules, Capsules):
+                raise TypeError(f"Guide: capsules must be a Capsules or None, got {type(capsules).__name__}")
+            others = (("discs", discs), ("planes", planes), ("field", None if field is None else field.cells),
+                      ("motion limits", None if motion is None else motion.limits), ("route", None if route is None else route.points))
+            for name, t in others:
+                if t is None or (name in ("discs", "planes") and t.shape[1] == 0):
+                    continue
+                if t.device != capsules.device:
+                    raise ValueError(f"Guide: {name} live on {t.device}, the capsules on {capsules.device}")
+                if t.shape[0] != capsules.scenes:
+                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the capsules {capsules.scenes}")
         if schedule not in SCHEDULES:
             raise ValueError(f"Guide: schedule must be one of {SCHEDULES}, got {schedule!r}")
         scale, cap = float(scale), float(cap)
@@ -405,7 +548,7 @@ class Guide:
         self.discs = None if discs is None else discs.contiguous()
         self.planes = None if planes is None else planes.contiguous()
         self.scale, self.schedule, self.cap, self.iters = scale, schedule, cap, int(iters)
-        self.field, self.motion, self.route = field, motion, route
+        self.field, self.motion, self.route, self.capsules = field, motion, route, capsules
 
     # ---- shape ----
     @property
@@ -429,7 +572,7 @@ class Guide:
 
     def _first(self) -> Optional[torch.Tensor]:
         """The tensor that says how many scenes the guide holds and where: discs, else planes, else the field's cells, else the
-        motion limits, else the route's points."""
+        motion limits, else the route's points, else the capsules' slots."""
         if self.discs is not None:
             return self.discs
         if self.planes is not None:
@@ -438,14 +581,20 @@ class Guide:
             return self.field.cells
         if self.motion is not None:
             return self.motion.limits
-        return None if self.route is None else self.route.points
+        if self.route is not None:
+            return self.route.points
+        return None if self.capsules is None else self.capsules.slots
 
     def key(self) -> tuple:
         """What a captured graph bakes: everything but the values of discs, planes and the field's cells.  Without a field the
         6-tuple of cost guidance v1; with one, the field's key appended.  With motion limits: the 6-tuple followed by the field's
         key or None and the limits' key.  With a route: the 6-tuple, the field's key or None, the limits' key or None, the
-        route's key.  A guide without a route keeps the key it had."""
+        route's key.  A guide without a route keeps the key it had.  With capsules: the 6-tuple, the field's key or None, the
+        limits' key or None, the route's key or None, the capsules' key.  A guide without capsules keeps the key it had."""
         key = (self.M, self.P, self.scale, self.schedule, self.cap, self.iters)
+        if self.capsules is not None:
+            return key + (None if self.field is None else self.field.key(), None if self.motion is None else self.motion.key(),
+                          None if self.route is None else self.route.key(), self.capsules.key())
         if self.route is not None:
             return key + (None if self.field is None else self.field.key(), None if self.motion is None else self.motion.key(),
                           self.route.key())
@@ -454,9 +603,10 @@ class Guide:
         return key if self.field is None else key + (self.field.key(),)
 
     def like(self, discs: Optional[torch.Tensor], planes: Optional[torch.Tensor], field: Optional[CostField] = None,
-             motion: Optional[MotionLimits] = None, route: Optional[Route] = None) -> "Guide":
+             motion: Optional[MotionLimits] = None, route: Optional[Route] = None, capsules: Optional[Capsules] = None) -> "Guide":
         """The same settings over other tensors."""
-        return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters, field=field, motion=motion, route=route)
+        return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters, field=field, motion=motion, route=route,
+                     capsules=capsules)
 
     # ---- launches ----
     def desc(self, x: torch.Tensor, lam: float = 0.0) -> L.GuideDesc:
@@ -491,10 +641,20 @@ class Guide:
         goes through the `_motion`, `_field` or `_guide` export."""
         return None if self.route is None else self.route.desc(x)
 
+    def capsule_desc(self, x: torch.Tensor) -> Optional[L.CapsuleDesc]:
+        """The `adx_guide_capsules` of a launch on `x` ("cost guidance v5"), or None for a guide without capsules: the launch then
+        goes through the `_route`, `_motion`, `_field` or `_guide` export."""
+        return None if self.capsules is None else self.capsules.desc(x)
+
     def descs(self, x: torch.Tensor, lam: float = 0.0):
-        """`(export suffix, byref arguments, the structs)` of a guided launch on `x`: "guide", "field", "motion" or "route" and
-        the records that export takes after the pin, in its order.  Keep the structs alive until the launch is enqueued."""
+        """`(export suffix, byref arguments, the structs)` of a guided launch on `x`: "guide", "field", "motion", "route" or
+        "capsule" and the records that export takes after the pin, in its order.  Keep the structs alive until the launch is
+        enqueued."""
         g, f, m, r = self.desc(x, lam), self.field_desc(x), self.motion_desc(x), self.route_desc(x)
+        c = self.capsule_desc(x)
+        if c is not None:
+            return "capsule", (C.byref(g), None if f is None else C.byref(f), None if m is None else C.byref(m),
+                               None if r is None else C.byref(r), C.byref(c)), (g, f, m, r, c)
         if r is not None:
             return "route", (C.byref(g), None if f is None else C.byref(f), None if m is None else C.byref(m), C.byref(r)), (g, f, m, r)
         if m is not None:
@@ -512,8 +672,13 @@ class Guide:
         rows, H, D = traj.shape
         cost = torch.empty(rows, dtype=torch.float32, device=traj.device)
         active = torch.empty(rows, dtype=torch.int32, device=traj.device)
-        f, m, r = self.field_desc(traj), self.motion_desc(traj), self.route_desc(traj)
-        if r is not None:
+        f, m, r, c = self.field_desc(traj), self.motion_desc(traj), self.route_desc(traj), self.capsule_desc(traj)
+        if c is not None:
+            L.check(L.lazy("adx_guide_cost_capsule")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f),
+                                                     None if m is None else C.byref(m), None if r is None else C.byref(r), C.byref(c),
+                                                     cost.data_ptr(), active.data_ptr(), rows, H, D, L.stream_ptr(traj.device)),
+                    "adx_guide_cost_capsule")
+        elif r is not None:
             L.check(L.lazy("adx_guide_cost_route")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f),
                                                    None if m is None else C.byref(m), C.byref(r), cost.data_ptr(), active.data_ptr(),
                                                    rows, H, D, L.stream_ptr(traj.device)), "adx_guide_cost_route")
@@ -534,4 +699,5 @@ class Guide:
                 f"planes={None if self.planes is None else tuple(self.planes.shape)}, scale={self.scale}, schedule={self.schedule!r}, "
                 f"cap={self.cap}, iters={self.iters}" + ("" if self.field is None else f", field={self.field!r}") +
                 ("" if self.motion is None else f", motion={self.motion!r}") +
-                ("" if self.route is None else f", route={self.route!r}") + ")")
+                ("" if self.route is None else f", route={self.route!r}") +
+                ("" if self.capsules is None else f", capsules={self.capsules!r}") + ")")

@@ -36,6 +36,8 @@ A tenth says how fast to go: `guide=Guide(..., motion=MotionLimits(limits))` cap
 per scene ("cost guidance v3"); every step then runs the row-wise step kernel, one wave per row.
 An eleventh says where the road is: `guide=Guide(..., route=Route(points, half_width))` keeps the plan within a half-width of a
 per-scene polyline ("cost guidance v4"), a point-wise term of the same routine, so it runs in whichever step kernel the rest picks.
+A twelfth says where the other vehicles are: `guide=Guide(..., capsules=Capsules(slots))` steers around per-scene moving capsules
+("cost guidance v5"), point-wise like the route; `Capsules.from_boxes` makes them from oriented boxes in one capturable launch.
 """
 from __future__ import annotations
 
@@ -197,7 +199,8 @@ class TickPlan:
     # r % S), nothing is tiled.  A guide's field ("cost guidance v2"): the cells are a buffer like discs and planes; presence, (Gy, Gx),
     # origin, cell size and weight are baked (by-value arguments of every step node) -- all of it through `Guide.key()`.  A guide's
     # motion limits ("cost guidance v3"): the [S, 2] limits are a buffer; presence and the two weights are baked, the same way.  A
-    # guide's route ("cost guidance v4"): the [S, R, 2] points and [S] half-widths are buffers; presence, R and the weight are baked
+    # guide's route ("cost guidance v4"): the [S, R, 2] points and [S] half-widths are buffers; presence, R and the weight are baked.
+    # A guide's capsules ("cost guidance v5"): the [S, C, 7] slots are a buffer; presence, C and the weight are baked
     guide: Optional[Guide]
 
     def key(self) -> tuple:
@@ -256,7 +259,8 @@ def _guide_plan(cfg, guide: Optional[Guide], image, scheduler) -> Optional[Guide
     for name, t in (("discs", guide.discs), ("planes", guide.planes), ("field.cells", None if guide.field is None else guide.field.cells),
                     ("motion.limits", None if guide.motion is None else guide.motion.limits),
                     ("route.points", None if guide.route is None else guide.route.points),
-                    ("route.half_width", None if guide.route is None else guide.route.half_width)):
+                    ("route.half_width", None if guide.route is None else guide.route.half_width),
+                    ("capsules.slots", None if guide.capsules is None else guide.capsules.slots)):
         if t is not None and (int(t.shape[0]) != S or t.device != image.device):
             raise ValueError(f"guide.{name} must hold {S} scenes (image.shape[0]) on {image.device}, got {tuple(t.shape)} on {t.device}")
     if int(cfg.MODEL.TRANSITION_DIM) < 2:
@@ -593,6 +597,7 @@ class GraphedSampler:
     never capture again.  A guide's `field` travels the same way: the cells through a static buffer, its presence, shape, geometry
     and weight through the key.  So do a guide's motion limits: the limits through a static buffer, presence and weights through the key.
     And a guide's route: points and half-widths through static buffers, presence, R and weight through the key.
+    And a guide's capsules: the slots through a static buffer, presence, C and weight through the key.
     """
 
     MAX_GRAPHS = 4
@@ -636,7 +641,8 @@ class GraphedSampler:
                                                         None if guide.field is None else guide.field.like(guide.field.cells.clone()),
                                                         None if guide.motion is None else guide.motion.like(guide.motion.limits.clone()),
                                                         None if guide.route is None else guide.route.like(guide.route.points.clone(),
-                                                                                                         guide.route.half_width.clone()))
+                                                                                                         guide.route.half_width.clone()),
+                                                        None if guide.capsules is None else guide.capsules.like(guide.capsules.slots.clone()))
         ctl = self.controller
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
@@ -755,6 +761,8 @@ class GraphedSampler:
                 if guide.route is not None:
                     g.guide.route.points.copy_(guide.route.points)
                     g.guide.route.half_width.copy_(guide.route.half_width)
+                if guide.capsules is not None:
+                    g.guide.capsules.slots.copy_(guide.capsules.slots)
         self._key, self._graph, self._sel, self._ctl = key, g.graph, g.sel, g.ctl
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured

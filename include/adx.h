@@ -1128,6 +1128,121 @@ int adx_traj_select_guide_route(const adx_select_guide_cfg* c, const float* traj
                                 float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Cost guidance v5: cost guidance v4 plus MOVING CAPSULES -- the other road users as what they are.  v1's moving obstacles are
+ * discs; a 4.5 m x 2 m car is not one.  A capsule is a segment with a radius, moving at a constant velocity: its distance is the
+ * point-to-segment distance of v4, its potential exactly v1's disc potential around the nearest point of the segment, so a disc is
+ * the capsule of zero length.  v1 to v4 stay as they are: the _guide, _field, _motion and _route exports, their structs and their
+ * bits; v5 stands beside them as the _capsule exports, each the _route export with one more argument.  The term is point-wise and
+ * couples no neighbours, so it is one more term of the routine every guided kernel calls and reaches all of them: the element-wise
+ * step kernels (no limits), the row-wise ones (limits), adx_guide_cost and the guided selection, which agree on its bits.  Callers
+ * and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ * Everything is in the model's own units (the clamped result BEFORE xy scaling) and this tick's ego frame, as in v1.
+ *
+ *   capsules    float32 [scene_rows][C][7] = (ax, ay, bx, by, vx, vy, r) in device memory, 1 <= C <= 32 (ADX_CAPSULE_MAX), read at
+ *               every launch.  Row r of a launch reads scene r % scene_rows.  (ax, ay) and (bx, by) are the ends of the axis at
+ *               waypoint 0; at waypoint h both have moved by h * (vx, vy), v1's constant-velocity model.  A slot with r <= 0 or
+ *               a NaN r is empty.  a == b is legal: a disc.
+ *   weight      a host scalar by value, >= 0.  At exactly 0 the term is not evaluated and counts nothing in `active`.
+ *   term        of one waypoint (x, y) at index h (hf = (float)h), evaluated AFTER v4's route term and BEFORE v3's motion terms
+ *               into the same J, gx, gy and active count.  fp32, no contraction, every operation rounded on its own, in this
+ *               order, for i = 0 .. C-1 in index order (q = capsules[scene][i]):
+ *                 r = q[6];  skip unless r > 0
+ *                 hx = hf * vx;  hy = hf * vy;  px = ax + hx;  py = ay + hy
+ *                 ex = bx - ax;  ey = by - ay                      (from the unmoved ends: both move alike)
+ *                 ux = x - px;   uy = y - py
+ *                 ee = ex * ex + ey * ey;   ue = ux * ex + uy * ey
+ *                 t  = ee > 0 ? ue / ee : 0;   t = t < 0 ? 0 : (t > 1 ? 1 : t)            (a NaN passes through)
+ *                 rx = ux - t * ex;  ry = uy - t * ey;  d2 = rx * rx + ry * ry
+ *                 rr = r * r;  inv = 1 / rr;  sd = d2 * inv;  phi = 1 - sd;   active iff phi > 0
+ *                 J  = J + (weight * (phi * phi)) / 2
+ *                 k  = weight * ((2 * phi) * inv)
+ *                 gx = gx - k * rx;  gy = gy - k * ry;  active = active + 1
+ *               No square root.  The potential is v1's: 1/2 on the axis, falling to 0 at distance r from it, so the capsule is
+ *               the set of points within r of the segment.  The gradient is exact off the axis (d d2 / dp = 2 (rx, ry), also
+ *               where t is clamped); ON the axis it is zero, as at a disc's centre: a waypoint exactly there is not pushed.
+ *               An inactive or empty slot adds nothing, not even a zero: a guide whose capsule term is off (weight 0, every
+ *               radius 0 or NaN) accumulates exactly the bits of v4 (or v3, v2, v1).  A capsule with a == b at weight 1
+ *               accumulates exactly the bits of v1's disc (ax, ay, vx, vy, r): ee = 0, t = 0, (rx, ry) = (ux, uy).  A NaN in
+ *               a slot's ends or velocity stays in that slot: phi is NaN and the slot is inactive.
+ *   the rest    iters, lambda, cap, `moved`, the order inside a step and everything after the guide are v1's (or v3's, with
+ *               limits), word for word.  In the element-wise kernels the x and the y thread of a waypoint each repeat its
+ *               iterations, as in v1 and v4, so the term is evaluated twice per waypoint there; the row-wise kernels evaluate it
+ *               once per lane.
+ *   kernels     `field`, `motion` and `route` may each be NULL.  A NULL motion runs the element-wise kernels, a non-NULL one the
+ *               row-wise ones (and needs horizon <= 64, as in v3).  No kernel is added: the guided kernels branch on
+ *               capsules != NULL, which is the same in every thread of a launch.  The slots are read from global memory as they
+ *               lie: a scene's capsules are at most 896 bytes that every lane of the scene reads at the same addresses.
+ *   cost        adx_guide_cost_capsule: per waypoint J as above, summed by v1's butterfly.  adx_traj_select_guide_capsule:
+ *               violation, active, free and blocked of selection cost v2 carry the capsule term among the others; the capsules'
+ *               scene_rows equals `scenes`.  With `hard`, a candidate inside a capsule -- by one ulp of phi -- is "not free".
+ *   NULL        NULL capsules are exactly the _route export.
+ *
+ * ADX_ERR_INVALID before any GPU work, each with its own text: NULL capsules data; n_capsules outside 1..32; scene_rows < 1 or
+ * not dividing batch; scene_rows disagreeing with the guide's (when it holds discs or planes), the field's, the limits' or the
+ * route's; a weight negative or NaN; an output overlapping the capsules; a step with capsules and no adx_guide; and whatever the
+ * _route export refuses.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_CAPSULE_MAX 32
+typedef struct adx_guide_capsules {
+  const float* capsules;       /* [scene_rows][n_capsules][7] = (ax, ay, bx, by, vx, vy, r) */
+  int32_t scene_rows, n_capsules;
+  float weight;
+} adx_guide_capsules;
+int adx_ddim_step_capsule(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                          const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                          const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                          const adx_guide_capsules* capsules, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
+                          adx_stream s);
+int adx_ddpm_step_capsule(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                          const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                          const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                          const adx_guide_capsules* capsules, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
+                          adx_stream s);
+int adx_dpm_step_capsule(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                         const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                         const adx_guide_capsules* capsules, float* prev_sample, float* x0, int32_t batch, int32_t horizon,
+                         int32_t dim, adx_stream s);
+int adx_guide_cost_capsule(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+                           const adx_guide_route* route, const adx_guide_capsules* capsules, float* cost, int32_t* active,
+                           int32_t rows, int32_t horizon, int32_t dim, adx_stream s);
+int adx_traj_select_guide_capsule(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
+                                  const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                                  const adx_guide_capsules* capsules, float* cost, int32_t* active, int32_t* index, int32_t* blocked,
+                                  float* best, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
+ * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
+ * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
+ * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
+ * never an edit.
+ *
+ *   boxes    float32 [scenes][N][8] = (cx, cy, vx, vy, ux, uy, length, width) in device memory, 1 <= N <= 32: centre, velocity per
+ *            waypoint, UNIT heading (ux, uy) along `length`, and the two sizes, in cost guidance v5's units and frame.  The
+ *            caller normalises the heading, so the device needs no sin or cos and the result can be checked bit for bit; a
+ *            heading that is not unit scales the axis, nothing checks it.
+ *   inflate  a host scalar by value, finite and >= 0: added to every live capsule's radius -- the ego's own radius.
+ *   out      float32 [scenes][N][7]: the slots of adx_guide_capsules, box j of scene s at slot j of scene s.
+ *   per box  fp32, no contraction, every operation rounded on its own:
+ *              live = length > 0 && width > 0        (a NaN is not live: the slot becomes seven zeros, an empty capsule)
+ *              lon  = length >= width
+ *              a = lon ? length : width;   b = lon ? width : length
+ *              s = a / 2 - b / 2
+ *              dx = lon ? ux : -uy;   dy = lon ? uy : ux
+ *              ox = s * dx;  oy = s * dy
+ *              out = (cx - ox, cy - oy, cx + ox, cy + oy, vx, vy, b / 2 + inflate)
+ *            The capsule is the box's INSCRIBED stadium: its axis runs along the longer side (turned by a quarter when the
+ *            width is the longer one), and a square box is a disc (s = 0, a == b).  The box's corners stick out of it by up to
+ *            (sqrt(2) - 1) * b / 2; `inflate` is where the caller covers that.
+ *   launch   one thread per box, 256 threads per workgroup.
+ *
+ * ADX_ERR_INVALID before any GPU work: NULL boxes or out; n_boxes outside 1..32; scenes < 1 (or above 2^20); an inflate that is
+ * negative or not finite; out overlapping boxes.
+ * -----------------------------------------------------------------------------------*/
+int adx_capsules_from_boxes(const float* boxes, float* out, int32_t scenes, int32_t n_boxes, float inflate, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Cost field from occupancy v1: a cost raster for cost guidance v2 from a binary occupancy raster, one launch.  The value at a
  * node is the disc potential of cost guidance v1 around the NEAREST occupied node: 0.5 on an obstacle, falling to 0 at distance
  * `margin`.  No square root.  Capturable: no allocation, no synchronisation, no host decision.  Callers and fixtures depend on

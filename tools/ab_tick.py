@@ -4,7 +4,8 @@
     python tools/ab_tick.py --guided libadx_parent.so autonomous_driving_with_diffusion_model_amd/libadx.so
 
 `--guided`: the 20-step graph ticks of tools/guide_tick_probe.py instead, without a guide and with the largest v1 guide (`none` and
-`m32p8i8` at 1 and 64 scenes, three rounds per process): what a change to the guide's routine can move in a tick that does not use it."""
+`m32p8i8` at 1 and 64 scenes, three rounds per process): what a change to the guide's routine can move in a tick that does not use it
+-- the routeless tick when the route corridor (v4) joined that routine, the capsule-free one when the moving capsules (v5) did."""
 import json, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = "import sys; sys.path.insert(0, %r); import torch, bench, json; print(json.dumps(bench.deployed_leg(torch.device('cuda:0'))))" % root

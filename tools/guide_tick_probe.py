@@ -33,9 +33,15 @@ one division each per iteration, twice per waypoint in the element-wise kernel),
 (`m32p8i8.lim`, `m32p8i8.lim.r32`: the row-wise kernel, once per waypoint).  The route winds through [-0.8, 0.8]^2 at half-width
 0.1, which a fresh draw mostly lies outside of.
 
+`--capsule` runs a fourth leg instead ("cost guidance v5", moving capsules): the graph tick at 1 and 64 scenes with no guide, with
+32 discs alone (`m32i8`), with 32 capsules alone (`c32i8`: the discs' potential around a segment -- one division, a clamp and a
+residual more per slot), with the largest v1 guide (`m32p8i8`), with the route beside it (`m32p8i8.r32`) and with 32 capsules
+beside it (`m32p8i8.c32`), all at iters=8 in one run.  The capsules lie where the discs do, about 0.25 long.
+
     python tools/guide_tick_probe.py --json profiles/guide_tick_probe.json
     python tools/guide_tick_probe.py --motion --json profiles/motion_tick_probe.json
     python tools/guide_tick_probe.py --route --json profiles/route_tick_probe.json
+    python tools/guide_tick_probe.py --capsule --json profiles/capsule_tick_probe.json
 """
 import argparse
 import contextlib
@@ -47,7 +53,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from autonomous_driving_with_diffusion_model_amd import CostField, DeviceNoise, Guide, MotionLimits, Route  # noqa: E402
+from autonomous_driving_with_diffusion_model_amd import Capsules, CostField, DeviceNoise, Guide, MotionLimits, Route  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd import scheduler as S  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd.config import create_cfg  # noqa: E402
 from autonomous_driving_with_diffusion_model_amd.modeling import build_model  # noqa: E402
@@ -67,6 +73,9 @@ MOTION_ARMS = (("none", None, False, 0), ("m32p8i8", (32, 8, 8), False, 0), ("m3
 # the --route leg
 ROUTE_ARMS = (("none", None, False, 0), ("m32p8i8", (32, 8, 8), False, 0), ("m32p8i8.r32", (32, 8, 8), False, 32),
               ("m32p8i8.lim", (32, 8, 8), True, 0), ("m32p8i8.lim.r32", (32, 8, 8), True, 32))
+# the --capsule leg: one more entry, the number of capsule slots
+CAPSULE_ARMS = (("none", None, False, 0, 0), ("m32i8", (32, 0, 8), False, 0, 0), ("c32i8", (0, 0, 8), False, 0, 32),
+                ("m32p8i8", (32, 8, 8), False, 0, 0), ("m32p8i8.r32", (32, 8, 8), False, 32, 0), ("m32p8i8.c32", (32, 8, 8), False, 0, 32))
 HALF_WIDTH = 0.1                       # of every scene's route
 LIMITS = (0.05, 0.03)                  # (s_max, a_max) of every scene
 STEP_CALLS = 20                        # step launches per captured graph
@@ -99,7 +108,21 @@ def route(scenes, R, dev):
     return Route(torch.stack([x, y], dim=2).to(dev), HALF_WIDTH)
 
 
-def obstacles(scenes, M, P, iters, dev, field=None, motion=False, points=0):
+def capsules(scenes, C, dev):
+    """[scenes, C, 7] slots where `obstacles` puts its discs: middles in [-0.5, 0.5]^2, a quarter long in a random direction, the
+    discs' velocities and radii, no empty slot."""
+    g = torch.Generator().manual_seed(17)
+    mid = torch.rand(scenes, C, 2, generator=g) - 0.5
+    yaw = torch.rand(scenes, C, generator=g) * 6.2831853
+    half = 0.125 * torch.stack([torch.cos(yaw), torch.sin(yaw)], dim=2)
+    s = torch.zeros(scenes, C, 7)
+    s[..., 0:2], s[..., 2:4] = mid - half, mid + half
+    s[..., 4:6] = (torch.rand(scenes, C, 2, generator=g) - 0.5) * 0.02
+    s[..., 6] = 0.2 + 0.3 * torch.rand(scenes, C, generator=g)
+    return Capsules(s.to(dev))
+
+
+def obstacles(scenes, M, P, iters, dev, field=None, motion=False, points=0, slots=0):
     g = torch.Generator().manual_seed(11)
     discs = torch.zeros(scenes, M, 5)
     discs[..., :2] = torch.rand(scenes, M, 2, generator=g) - 0.5
@@ -110,11 +133,11 @@ def obstacles(scenes, M, P, iters, dev, field=None, motion=False, points=0):
     planes[..., 2] = torch.rand(scenes, P, generator=g) * 0.5
     return Guide(discs.to(dev) if M else None, planes.to(dev) if P else None, scale=0.2, schedule="variance", cap=0.1, iters=iters,
                  field=field, motion=MotionLimits(torch.tensor([LIMITS] * scenes, device=dev)) if motion else None,
-                 route=route(scenes, points, dev) if points else None)
+                 route=route(scenes, points, dev) if points else None, capsules=capsules(scenes, slots, dev) if slots else None)
 
 
 def motion_arms(dev, n, which=MOTION_ARMS):
-    """The graph ticks of the --motion and --route legs: `arms` with MOTION_ARMS or ROUTE_ARMS."""
+    """The graph ticks of the --motion, --route and --capsule legs: `arms` with MOTION_ARMS, ROUTE_ARMS or CAPSULE_ARMS."""
     fns, meta = {}, {}
     for scenes, horizon in SIZES:
         cfg = make_cfg(n, horizon)
@@ -123,10 +146,10 @@ def motion_arms(dev, n, which=MOTION_ARMS):
         P.load_procedural(model, 0)
         model = model.to(dev).eval()
         d = {k: v.to(dev) for k, v in P.synthetic_batch(scenes, horizon, image_hw=IMG, seed=3).items()}
-        for arm, mpi, lim, points in which:
+        for arm, mpi, lim, points, *rest in which:
             sch = S.GuidanceDDIMScheduler(cfg=cfg, thresholding=True, **SCHED_KW)
             gs = GraphedSampler(model, sch, cfg, noise=DeviceNoise(7, dev))
-            guide = None if mpi is None else obstacles(scenes, *mpi, dev, motion=lim, points=points)
+            guide = None if mpi is None else obstacles(scenes, *mpi, dev, motion=lim, points=points, slots=rest[0] if rest else 0)
             fns[f"s{scenes}.{arm}"] = (lambda gs=gs, img=d["imgs"], tgt=d["target"], guide=guide: gs(img, tgt, guide=guide))
             meta[f"s{scenes}.{arm}"] = (scenes, horizon, arm)
     return fns, meta
@@ -215,11 +238,14 @@ def main():
     ap.add_argument("--arms", default=None, help="comma-separated arm names (default: all); the ratios need `none` and `m4p2i1` among them")
     ap.add_argument("--motion", action="store_true", help="the motion-limits leg instead: see the module docstring")
     ap.add_argument("--route", action="store_true", help="the route-corridor leg instead: see the module docstring")
+    ap.add_argument("--capsule", action="store_true", help="the moving-capsules leg instead: see the module docstring")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     n = a.steps
     with torch.no_grad():
-        if a.route:
+        if a.capsule:
+            fns, meta = motion_arms(dev, n, CAPSULE_ARMS)
+        elif a.route:
             fns, meta = motion_arms(dev, n, ROUTE_ARMS)
         elif a.motion:
             fns, meta = motion_arms(dev, n)
@@ -245,8 +271,11 @@ def main():
         with torch.no_grad():
             record["limits"], record["step_launches"] = list(LIMITS), step_launches(dev, a.rounds)
         record["limits_over_m32p8i8"] = {}
-    if a.route:
+    if a.route and not a.capsule:
         record["route"] = {"points": 32, "half_width": HALF_WIDTH, "weight": 1.0}
+        record["added_ms"] = {}
+    if a.capsule:
+        record["capsules"] = {"slots": 32, "length": 0.25, "weight": 1.0}
         record["added_ms"] = {}
     for k in fns:
         scenes, horizon, mode = meta[k]
@@ -259,7 +288,16 @@ def main():
             ref = record["arms"].get(f"s{v['scenes']}.{base}")
             if v["guide"] != "none" and ref is not None:
                 record[over][k] = round(v["median_ms"] / ref["median_ms"], 4)
-    if a.route:                     # what each layer adds to the tick: the 32 discs and 8 planes over none, the route over those
+    if a.capsule:                   # what 32 capsules add to the tick next to what 32 discs and the 32-point route add, in one run
+        for scenes, _ in SIZES:
+            med = {arm[0]: record["arms"][f"s{scenes}.{arm[0]}"]["median_ms"] for arm in CAPSULE_ARMS}
+            record["added_ms"][f"s{scenes}"] = {"m32i8 over none": round(med["m32i8"] - med["none"], 4),
+                                                "c32i8 over none": round(med["c32i8"] - med["none"], 4),
+                                                "m32p8i8 over none": round(med["m32p8i8"] - med["none"], 4),
+                                                "r32 over m32p8i8": round(med["m32p8i8.r32"] - med["m32p8i8"], 4),
+                                                "c32 over m32p8i8": round(med["m32p8i8.c32"] - med["m32p8i8"], 4)}
+        print(json.dumps(record["added_ms"]), file=sys.stderr)
+    if a.route and not a.capsule:   # what each layer adds to the tick: the 32 discs and 8 planes over none, the route over those
         for scenes, _ in SIZES:
             med = {arm: record["arms"][f"s{scenes}.{arm}"]["median_ms"] for arm, _, _, _ in ROUTE_ARMS}
             record["added_ms"][f"s{scenes}"] = {"m32p8i8 over none": round(med["m32p8i8"] - med["none"], 4),
