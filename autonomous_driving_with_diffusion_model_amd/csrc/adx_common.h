@@ -64,6 +64,10 @@ struct DebugSwitches {
   bool hs_dma = true;          // ADX_HS_DMA=0       conv2d_hs3x3q stages its operands through registers instead of with LDS-DMA loads (conv2d_hs16.hip)
   bool hs_s2q = true;          // ADX_HS_S2Q=0       the stride-2 block entries stay on conv2d_hs_kernel (32x32x16) where conv2d_hs3x3q_s2_kernel would serve them
   bool hs_persist = true;      // ADX_HS_PERSIST=0   conv2d_hs3x3q launches one workgroup per tile instead of one per CU that walks the tiles
+  int hs_reserve_cus = -1;     // ADX_HS_RESERVE_CUS=<n>  compute units (a multiple of 8; default 0) the persistent conv2d_hs3x3q launches leave
+                               //                    free: grid = 8 x ((CUs - n) / 8) workgroups.  Set, it also overrides the eval plan's own reserve
+  int hs_grid_cap = 0;         // ADX_HS_GRID_CAP=<n>  (tests) at most n workgroups (a multiple of 8) per persistent conv2d_hs3x3q launch: deep
+                               //                    unit walks on small shapes
   int resnet_streams = 2;      // ADX_RESNET_STREAMS=1..4  sub-batches of an inference perception pass at B >= 32, each on a stream of its own
   int resnet_split_from = -1;  // ADX_RESNET_SPLIT_FROM=<block>  first BasicBlock that runs per sub-batch (default: the first downsample block; 0: the stem too)
   bool check_range = false;    // ADX_CHECK_RANGE=1  perception forward: fail with the first layer whose activations leave the

@@ -56,6 +56,8 @@ const DebugSwitches& debug_switches() {
     d.wgrad_deterministic = is("ADX_WGRAD_DETERMINISTIC", '1');
     if (const char* e = getenv("ADX_CHAIN_MASK")) d.chain_mask = (unsigned)strtoul(e, nullptr, 0);
     if (const char* e = getenv("ADX_HS_MODE")) d.hs_mode = atoi(e);
+    if (const char* e = getenv("ADX_HS_RESERVE_CUS")) d.hs_reserve_cus = atoi(e) < 0 ? 0 : (atoi(e) & ~7);
+    if (const char* e = getenv("ADX_HS_GRID_CAP")) d.hs_grid_cap = atoi(e) < 8 ? 0 : (atoi(e) & ~7);
     if (const char* e = getenv("ADX_RESNET_SPLIT_FROM")) d.resnet_split_from = atoi(e) < 0 ? -1 : atoi(e);
     if (const char* e = getenv("ADX_RESNET_STREAMS")) d.resnet_streams = atoi(e) < 1 ? 1 : (atoi(e) > 4 ? 4 : atoi(e));
     return d;

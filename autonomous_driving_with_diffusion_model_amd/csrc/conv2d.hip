@@ -410,6 +410,16 @@ int device_cus(int* cus) {
   *cus = n.load(std::memory_order_relaxed);
   return ADX_OK;
 }
+static thread_local int t_reserve_cus = -1;
+void conv2d_set_reserve_cus(int reserve) { t_reserve_cus = reserve; }
+int launch_cus(int* cus) {
+  int dev = 0;
+  const int rc = device_cus(&dev);
+  if (rc != ADX_OK) return rc;
+  const DebugSwitches& sw = debug_switches();
+  *cus = hs_usable_cus(dev, t_reserve_cus >= 0 ? t_reserve_cus : sw.hs_reserve_cus, sw.hs_grid_cap);
+  return ADX_OK;
+}
 static thread_local uint32_t* t_status = nullptr;
 void conv2d_set_status(uint32_t* word) { t_status = word; }
 uint32_t* conv2d_status() { return t_status; }
@@ -450,7 +460,7 @@ int conv2d_launch_raw(const ConvSpec& L, const float* x, const float* w, const f
   q.y_aligned = (reinterpret_cast<uintptr_t>(y) & 15) == 0; q.res_aligned = (reinterpret_cast<uintptr_t>(res) & 15) == 0;
   q.split_floats = t_split_floats;
   if (L.k == 3 && L.stride == 1) {      // (the persistent grid of the 16x16x32 kernel)
-    const int rc = device_cus(&q.cus);
+    const int rc = launch_cus(&q.cus);
     if (rc != ADX_OK) return rc;
   }
   const Hs3x3Plan plan = conv2d_hs3x3_plan(L, q);
@@ -756,10 +766,16 @@ extern "C++" int adx::resnet_eval_plan(const adx_resnet& r, const ResnetEvalQuer
   p.lay = resnet_layout(q.batch, q.h, q.w);
   // not inside a stream capture: a replayed graph with the forked branches measured 2 % SLOWER per tick than the single chain
   // (profiles/README.md, round 5), and streams are not created while capturing
+  // The sub-batches and the reserve are ONE choice: what runs beside the pass (the caller's other streams: the temporal stack of the
+  // next tick) gets CUs either between the launches of two interleaved chains or on CUs the persistent launches never take.
+  // Candidates at B = 64: {two sub-batch streams, one chain} x {reserve 0, 16} (profiles/README.md, "The unit walk").
+  p.reserve_cus = kEvalReserveCus[0];
   if (q.batch >= 32 && !sw.check_range && stem_fused && !q.capturing) {
     p.nsub = std::min(sw.resnet_streams, adx_resnet::kMaxSub);
     while (p.nsub > 1 && q.batch / p.nsub < 16) --p.nsub;
+    p.reserve_cus = kEvalReserveCus[1];
   }
+  if (sw.hs_reserve_cus >= 0) p.reserve_cus = sw.hs_reserve_cus;        // ADX_HS_RESERVE_CUS pins it for every pass
   // The stem and the first layer (the blocks in front of the first downsample block) run as ONE chain on the whole batch, the fork
   // comes behind them: their launches are thousands of two-per-CU workgroups whose last round hardly matters, and split they
   // only stream their operands twice (-1.6 % per faithful step, profiles/README.md).  Only blocks of the FIRST layer: their maps
@@ -915,6 +931,88 @@ int adx_resnet_plan_describe(const adx_resnet* r, int32_t batch, int32_t h, int3
   return ADX_OK;
 }
 
+// The grids of the same plan's launches on a device of `cus` compute units: what conv2d_hs3x3_plan / conv2d_hs_s2_plan answer for
+// every record of adx_resnet_plan_describe under the plan's reserve (the launch functions ask them the same question).
+int adx_resnet_plan_grids(const adx_resnet* r, int32_t batch, int32_t h, int32_t w, int32_t flags, int32_t cus, int32_t reserve,
+                          int32_t* n_records, int32_t* ints, int32_t max_records) {
+  ADX_REQUIRE(r && n_records && ints, "adx_resnet_plan_grids: null argument");
+  ADX_REQUIRE((flags & ~ADX_RESNET_PLAN_CAPTURING) == 0 && max_records >= 1 && cus >= 8, "adx_resnet_plan_grids: flags 0x%x, max_records %d, %d CUs",
+              (unsigned)flags, max_records, cus);
+  ResnetEvalQuery q;
+  q.batch = batch; q.h = h; q.w = w; q.capturing = (flags & ADX_RESNET_PLAN_CAPTURING) != 0;
+  ResnetEvalPlan p;
+  const int rc = resnet_eval_plan(*r, q, &p);
+  if (rc != ADX_OK) return rc;
+  if (reserve >= 0) p.reserve_cus = reserve;        // (as ADX_HS_RESERVE_CUS pins it in resnet_eval_plan)
+  const DebugSwitches& sw = debug_switches();
+  const int usable = hs_usable_cus(cus, p.reserve_cus, sw.hs_grid_cap);
+  int n = 0;
+  auto put = [&](int persistent, int units, int slots, size_t grid) {
+    if (n < max_records) {
+      const int32_t rec[ADX_RESNET_GRID_INTS] = {persistent, units, slots, (int32_t)grid, p.reserve_cus, usable};
+      memcpy(ints + (size_t)n * ADX_RESNET_GRID_INTS, rec, sizeof(rec));
+    }
+    ++n;
+  };
+  auto conv = [&](const ConvSpec& c, int nf, int H, int W, int fmt, bool has_res) {
+    Hs3x3Query hq;
+    hq.N = nf; hq.H = H; hq.W = W; hq.fmt = fmt; hq.affine = true; hq.relu = true; hq.has_res = has_res; hq.cus = usable;
+    const Hs3x3Plan hp = c.k == 3 && c.stride == 1 ? conv2d_hs3x3_plan(c, hq, sw) : Hs3x3Plan{};
+    if (hp.family == kHs3x3q) put(1, hp.cout_tiles * hp.tiles_x * hp.tiles_y, hp.q_slots, hp.grid);
+    else put(0, 0, 0, hp.family == kHs3x3 ? hp.grid : 0);
+  };
+  auto record = [&](const ResnetSegment& g, int i) -> int {
+    if (i < 0) {
+      put(0, 0, 0, 0);
+      if (!g.stem_fused) put(0, 0, 0, 0);
+    } else if (i == g.nsteps) {
+      put(0, 0, 0, 0);
+    } else {
+      const ResnetBlockStep& t = g.steps[i];
+      const ConvSpec& c1 = r->convs[t.c1];
+      if (t.fused_ds) {
+        HsS2Query sq;
+        sq.N = g.n; sq.H = t.H; sq.W = t.W; sq.x_cells = t.in_cells; sq.y_cells = t.mid_cells; sq.cus = usable;
+        const HsS2Plan sp = conv2d_hs_s2_plan(c1, r->convs[t.c1 + 2], sq, sw);
+        if (sp.q) put(1, sp.cout_tiles * sp.tiles_x * sp.tiles_y, sp.q_slots, sp.grid);
+        else put(0, 0, 0, 0);
+      } else {
+        conv(c1, g.n, t.H, t.W, (t.in_cells ? kFmtXCells : 0) | (t.mid_cells ? kFmtYCells : 0), false);
+        if (r->block_has_ds[t.block]) put(0, 0, 0, 0);
+      }
+      conv(r->convs[t.c1 + 1], g.n, t.OH, t.OW,
+           (t.mid_cells ? kFmtXCells : 0) | (t.out_cells ? kFmtYCells : 0) | (t.id_cells ? kFmtResCells : 0), true);
+    }
+    return ADX_OK;
+  };
+  (void)resnet_plan_each(p.seg, p.nseg - p.nsub, record);
+  (void)resnet_plan_each(p.seg + p.nseg - p.nsub, p.nsub, record);
+  *n_records = n;
+  ADX_REQUIRE(n <= max_records, "adx_resnet_plan_grids: %d launches, room for %d", n, max_records);
+  return ADX_OK;
+}
+
+// The unit walk of conv2d_hs3x3q_kernel from the kernel's own range and unit functions (hs3x3q_walk, hs3x3q_unit; the stepping by Q
+// is this function's copy of the kernel's loop, which the GPU bit-identity tests cover): workgroup b of `grid` visits counts[b]
+// units; visits holds them workgroup after workgroup, in visiting order, as (spatial tile, cout tile) pairs.
+int adx_conv2d_hs3x3q_walk(int32_t units, int32_t cout_tiles, int32_t grid, int32_t* counts, int32_t* visits) {
+  ADX_REQUIRE(counts && visits && units >= 1 && cout_tiles >= 1 && units % cout_tiles == 0 && grid >= 8 && grid % 8 == 0,
+              "adx_conv2d_hs3x3q_walk: %d units of %d cout tiles on %d workgroups", units, cout_tiles, grid);
+  const int Q = grid / 8;
+  int n = 0;
+  for (int b = 0; b < grid; ++b) {
+    const HsQWalk wk = hs3x3q_walk(b & 7, b >> 3, units);
+    counts[b] = 0;
+    for (int u = wk.first; u < wk.end; u += Q, ++counts[b], ++n) {
+      ADX_REQUIRE(n < units, "adx_conv2d_hs3x3q_walk: internal error (more visits than units)");
+      const HsQUnit un = hs3x3q_unit(u, cout_tiles);
+      visits[2 * n] = un.sp;
+      visits[2 * n + 1] = un.ct;
+    }
+  }
+  return ADX_OK;
+}
+
 static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspace, const float* img,
                                const uint8_t* frames_u8, const float* mean, const float* stdv, int32_t batch, int32_t h,
                                int32_t w, float* feature, adx_stream stream);
@@ -1018,7 +1116,11 @@ static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspac
     void set(float* p, size_t n) { conv2d_set_split_scratch(p, n); }
     ~ScratchScope() { conv2d_set_split_scratch(nullptr, 0); }
   } scratch_scope;
-  uint32_t* const words = r->status;       // range status (adx_resnet_set_status): [0] stem, [1 + b] block b, [1 + nblocks] fc
+  struct ReserveScope {     // the plan's reserve, for the persistent launches of THIS call
+    explicit ReserveScope(int n) { conv2d_set_reserve_cus(n); }
+    ~ReserveScope() { conv2d_set_reserve_cus(-1); }
+  } reserve_scope(plan.reserve_cus);
+  uint32_t* const words = r->status;      // range status (adx_resnet_set_status): [0] stem, [1 + b] block b, [1 + nblocks] fc
   StatusScope status_scope(words);
 
   auto issue = [&](const ResnetSegment& g, int i) -> int {

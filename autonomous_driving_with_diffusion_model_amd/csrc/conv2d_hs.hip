@@ -1676,7 +1676,7 @@ int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const floa
   HsS2Query q;
   q.N = N; q.H = H; q.W = W; q.x_cells = x_cells != 0; q.y_cells = y_cells != 0;
   if (q.x_cells && q.y_cells && !force_32) {      // (the persistent grid of the 16x16x32 kernel)
-    const int rc = device_cus(&q.cus);
+    const int rc = launch_cus(&q.cus);
     if (rc != ADX_OK) return rc;
     const HsS2Plan plan = conv2d_hs_s2_plan(c1, ds, q);
     if (plan.q) return conv2d_hs3x3q_s2_launch(plan, a, s);
@@ -1699,10 +1699,9 @@ HsS2Plan conv2d_hs_s2_plan(const ConvSpec& c1, const ConvSpec& ds, const HsS2Que
   p.tiles_x = (int)(((long)N * p.vw - (N > 1 ? 1 : 0) + kTileW - 1) / kTileW);
   p.tiles_y = ceil_div(OH, kQTH);
   p.cout_tiles = c1.cout / 128;
-  // workgroup = (XCD, cout tile, slot), as for the stride-1 launches of the kernel: one workgroup per CU where the tiles allow
-  p.q_slots = ceil_div(p.tiles_x * p.tiles_y, 8);
-  if (sw.hs_persist) p.q_slots = std::min(p.q_slots, std::max(1, q.cus / (8 * p.cout_tiles)));
-  p.grid = (size_t)8 * p.cout_tiles * p.q_slots;
+  // workgroup = (XCD, slot), as for the stride-1 launches of the kernel: one workgroup per CU the launch may use where the units allow
+  p.q_slots = hs3x3q_slots(p.cout_tiles * p.tiles_x * p.tiles_y, q.cus, sw.hs_persist);
+  p.grid = (size_t)8 * p.q_slots;
   p.threads = kQNT;
   p.lds = kQLdsS2;
   return p;
@@ -1817,12 +1816,11 @@ Hs3x3Plan conv2d_hs3x3_plan(const ConvSpec& L, const Hs3x3Query& q, const DebugS
     p.family = kHs3x3q; p.dma = sw.hs_dma; p.threads = kQNT;
     p.lds = p.dma ? kQLdsD : kQLds;
     p.vw = vw; p.tiles_x = vtiles_x; p.tiles_y = ceil_div(OH, kQTH); p.cout_tiles = L.cout / 128;
-    // workgroup = (XCD, cout tile, slot); slots per (XCD, cout tile): as many as the longest eighth of the spatial tiles (one tile
-    // per workgroup: ADX_HS_PERSIST=0 and the register-staged form), or -- the LDS-DMA form -- as many as fit one workgroup per CU,
-    // each walking its XCD's range in steps of that count (bit-identical results either way)
-    p.q_slots = ceil_div(p.tiles_x * p.tiles_y, 8);
-    if (sw.hs_dma && sw.hs_persist) p.q_slots = std::min(p.q_slots, std::max(1, q.cus / (8 * p.cout_tiles)));
-    p.grid = (size_t)8 * p.cout_tiles * p.q_slots;
+    // workgroup = (XCD, slot); slots per XCD: as many as the longest eighth of the units (spatial tile, cout tile) (one unit per
+    // workgroup: ADX_HS_PERSIST=0 and the register-staged form), or -- the LDS-DMA form -- one workgroup per CU the launch may
+    // use (q.cus: the device's less a reserve), each walking its XCD's range in steps of that count (bit-identical results either way)
+    p.q_slots = hs3x3q_slots(p.cout_tiles * p.tiles_x * p.tiles_y, q.cus, sw.hs_dma && sw.hs_persist);
+    p.grid = (size_t)8 * p.q_slots;
     return p;
   }
   p.lds = hs3x3_lds(mode, p.stats);

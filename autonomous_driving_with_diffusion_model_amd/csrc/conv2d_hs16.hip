@@ -79,20 +79,23 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int rowpair = wave & 3, slab = wave >> 2;
   const int j = lane & 15, kq = lane >> 4;
-  // Persistent over tiles (round 6): workgroup b = (XCD x = b & 7, cout tile ct, slot q) walks the spatial tiles x's eighth of the
-  // tile space holds -- one contiguous range per XCD, so shared halos meet in one L2, and the cout tiles of one spatial tile run
-  // side by side on it -- in steps of Q = slots per (XCD, cout tile).  While a tile's LAST chunk is multiplied, the idle patch
-  // buffer and the idle weight buffer receive the NEXT tile's first chunk and first tap -- the transfers that used to re-fetch
-  // the last chunk into buffers nobody read -- so only a workgroup's first tile has a prologue (a 128-channel layer at B = 64 is
-  // 3.6 tiles per CU: 2-3 us of exposed transfer latency per 45 us tile).  The cout tile never changes inside a workgroup, so
-  // neither do its weights' addresses nor its per-channel constants.  Q = the longest range: one tile per workgroup, the old launch.
+  // Persistent over tiles (round 6): workgroup b = (XCD x = b & 7, slot q = b >> 3) walks the UNITS u = spatial tile * cout tiles
+  // + cout tile that x's eighth of the unit space holds (hs3x3q_walk, conv2d_internal.h) -- one contiguous range per XCD, so shared
+  // halos meet in one L2, and the cout tiles of one spatial tile run side by side on it -- in steps of Q = workgroups per XCD.  Any
+  // Q serves any launch: a grid that leaves CUs free costs a round only where the UNITS of an XCD no longer fit, not where the
+  // spatial tiles of one cout tile do not.  While a tile's LAST chunk is multiplied, the idle patch buffer and the idle weight
+  // buffer receive the NEXT unit's first chunk and first tap -- the transfers that used to re-fetch the last chunk into buffers
+  // nobody read -- so only a workgroup's first tile has a prologue (a 128-channel layer at B = 64 is 3.6 tiles per CU: 2-3 us of
+  // exposed transfer latency per 45 us tile).  The cout tile may change from one unit to the next (Q % cout tiles != 0): the
+  // weights' addresses follow it (a wave-uniform offset) and the per-channel constants are reloaded behind the epilogue.
+  // Q = the longest range: one tile per workgroup, the old launch.
   const int Qs = a.q_slots;
-  const int xcd = blockIdx.x & 7, rr_ = blockIdx.x >> 3;
-  const int ct = rr_ % a.cout_tiles, slot = rr_ / a.cout_tiles;
-  const int nsp = a.tiles_x * a.tiles_y;
-  const int sp_end = (int)(((long)(xcd + 1) * nsp) >> 3);
-  int sp = (int)(((long)xcd * nsp) >> 3) + slot;
-  if (sp >= sp_end) return;                    // (uniform: a padding workgroup of a short range)
+  const HsQWalk wk = hs3x3q_walk((int)(blockIdx.x & 7), (int)(blockIdx.x >> 3), a.ntiles);
+  const int u_end = wk.end;
+  int u = wk.first;
+  if (u >= u_end) return;                      // (uniform: a padding workgroup of a short range)
+  HsQUnit un = hs3x3q_unit(u, a.cout_tiles);
+  int sp = un.sp, ct = un.ct;
   int ty = sp / a.tiles_x, tx = sp - ty * a.tiles_x;
   int oy0 = ty * kQTH, vx0 = tx * 32;
   auto vdiv = [&](int v) { return (int)(((float)v + 0.5f) * a.inv_vw); };     // v / vw for 0 <= v < 2^21 (launch check)
@@ -151,20 +154,37 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
     const int sl = e >> 9, half16 = (e >> 8) & 1, within = e & 255;
     wsrc_off[k] = (((ct * 2 + sl) * nch16 + half16) * 9) * 256 + within;
   }
-  float ssv = 0.f;
-  if (tid < 256) {
-    const int c = ct * 128 + (tid & 127);
-    ssv = a.scale == nullptr ? (tid < 128 ? 1.f : 0.f) : (tid < 128 ? a.scale[c] : a.shift[c]);
-  }
+  // the per-channel constants of cout tile ct_, into LDS: scale | shift, the consumer BatchNorm's (TRAIN == 2), the downsample's (S2)
+  auto load_consts = [&](int ct_) {
+    int z_ = 0;
+    asm volatile("" : "+s"(z_));
+    const int tid = threadIdx.x + z_;       // (re-derived, like the stage loop's lane constants: nothing of this may live across a tile)
+    if (tid < 256) {
+      const int c = ct_ * 128 + (tid & 127);
+      ss[tid] = a.scale == nullptr ? (tid < 128 ? 1.f : 0.f) : (tid < 128 ? a.scale[c] : a.shift[c]);
+    }
+    if constexpr (TRAIN == 2) {
+      const int which = tid >> 7, c = ct_ * 128 + (tid & 127);
+      const float mu = a.bs_mean[c], rs = a.bs_rstd[c];
+      const float sc = a.bs_gamma[c] * rs;          // the mask's affine form exactly as the forward pass applied it (resnet_train.hip: bn_affine)
+      bsl[tid] = which == 0 ? mu : (which == 1 ? rs : (which == 2 ? sc : __builtin_fmaf(-mu, sc, a.bs_beta[c])));
+    }
+    if constexpr (S2) {      // the downsample's constants, where TRAIN == 2 keeps the consumer BatchNorm's
+      if (tid < 256) {
+        const int c = ct_ * 128 + (tid & 127);
+        bsl[tid] = a.scale_ds == nullptr ? (tid < 128 ? 1.f : 0.f) : (tid < 128 ? a.scale_ds[c] : a.shift_ds[c]);
+      }
+    }
+  };
 
   f32x4 accm[4][4], accl[4][4];            // [channel block][pixel block]: hi*hi sums, cross-term sums (scaled by 2^11)
 
   u32x4 wv[2][2], pvh[2], pvl[2];          // register sets: weights of stage s in wv[s & 1]; the patch round fetched at stage s in pv*[s & 1]
   // DMA: the wave's first cell of round k (a wave-uniform LDS address goes into M0; lane l lands l cells further)
   const int wcell = __builtin_amdgcn_readfirstlane(tid & ~63);
-  auto load_w = [&](int stage, int set) {           // DMA: `set` is the LDS weight buffer
+  auto load_w = [&](int stage, int set, int ctoff = 0) {     // DMA: `set` is the LDS weight buffer; ctoff: cells from this cout tile's image to another's
     const int chunk = stage / 9, tap = stage - chunk * 9;
-    const u32x4* ws = wsrc + (size_t)(chunk * 18 + tap) * 256;
+    const u32x4* ws = wsrc + ((long)(chunk * 18 + tap) * 256 + ctoff);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       if constexpr (DMA) __builtin_amdgcn_global_load_lds(ws + wsrc_off[k], (lds_void*)(wl + set * WST + wcell + NT * k), 16, 0, 0);
@@ -179,11 +199,11 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
       const_cast<float*>(a.w), 0, (int)((size_t)a.Cout * a.cin_pad * 9 * sizeof(float)), 0x00020000);
   const __amdgpu_buffer_rsrc_t wdrsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(S2 ? a.w_ds : a.w), 0, S2 ? (int)((size_t)a.Cout * a.cin_pad * sizeof(float)) : 0, 0x00020000);
-  auto load_w_tap = [&](int chunk, int tap, int set) {
+  auto load_w_tap = [&](int ct_, int chunk, int tap, int set) {
 #pragma unroll
     for (int k = 0; k < 2; ++k)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (lds_void*)(wl + set * WST + wcell + NT * k), 16, (uint32_t)(tid * 16),
-                                               (uint32_t)(((ct * 2 + k) * nch16 * 9 + chunk * 18 + tap + (wave >> 2) * 8) * 256 * 16), 0, 0);
+                                               (uint32_t)(((ct_ * 2 + k) * nch16 * 9 + chunk * 18 + tap + (wave >> 2) * 8) * 256 * 16), 0, 0);
   };
   auto load_w_ds = [&](int chunk, int set) {
 #pragma unroll
@@ -225,25 +245,13 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   // A (channels) of lane (j, kq): weight cell slab * 512 + (kq >> 1) * 256 + plane * 128 + (kq & 1) * 64 + 16 cb + j
 
   // prologue (a workgroup's FIRST tile only): stage 0 complete in LDS, the weights of stage 1 in flight
-  if constexpr (S2) load_w_tap(0, kTap[0], 0);
+  if constexpr (S2) load_w_tap(ct, 0, kTap[0], 0);
   else load_w(0, 0);
   store_w(0, 0);
 #pragma unroll
   for (int k = 0; k < PIT; ++k) { load_p(0, k, 0); store_p(0, k, 0); }
   if constexpr (!DMA) load_w(1, 1);
-  if (tid < 256) ss[tid] = ssv;
-  if constexpr (TRAIN == 2) {
-    const int which = tid >> 7, c = ct * 128 + (tid & 127);
-    const float mu = a.bs_mean[c], rs = a.bs_rstd[c];
-    const float sc = a.bs_gamma[c] * rs;          // the mask's affine form exactly as the forward pass applied it (resnet_train.hip: bn_affine)
-    bsl[tid] = which == 0 ? mu : (which == 1 ? rs : (which == 2 ? sc : __builtin_fmaf(-mu, sc, a.bs_beta[c])));
-  }
-  if constexpr (S2) {      // the downsample's constants, where TRAIN == 2 keeps the consumer BatchNorm's
-    if (tid < 256) {
-      const int c = ct * 128 + (tid & 127);
-      bsl[tid] = a.scale_ds == nullptr ? (tid < 128 ? 1.f : 0.f) : (tid < 128 ? a.scale_ds[c] : a.shift_ds[c]);
-    }
-  }
+  load_consts(ct);
   if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -255,11 +263,9 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   int zero_ = 0;
   asm volatile("" : "+s"(zero_));
   const int tl = tid + zero_;
-  if constexpr (DMA) {
-    if constexpr (!S2) {
+  if constexpr (DMA && !S2) {      // (S2 addresses its weights through a descriptor and parks its gather offsets in LDS)
 #pragma unroll
-      for (int k = 0; k < PIT; ++k) goff[k] = goff_of(tl, k, oy0, vx0);
-    }
+    for (int k = 0; k < PIT; ++k) goff[k] = goff_of(tl, k, oy0, vx0);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int e = tl + NT * k;
@@ -270,9 +276,13 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   const int j_l = tl & 15, kq_l = (tl & 63) >> 4;
   const int pb_lane = kq_l * GST + (rowpair * 2) * PW + j_l;
   const int wa_lane = slab * 512 + (kq_l >> 1) * 256 + (kq_l & 1) * 64 + j_l;
-  // the next tile (DMA only: the register-staged form runs one tile per workgroup)
-  const int sp_next = sp + Qs;
-  const bool has_next = DMA && sp_next < sp_end;
+  // the next unit (DMA only: the register-staged form runs one tile per workgroup)
+  const int u_next = u + Qs;
+  const bool has_next = DMA && u_next < u_end;
+  const HsQUnit un_next = hs3x3q_unit(u_next, a.cout_tiles);
+  const int sp_next = un_next.sp;
+  const int ct_next = has_next ? un_next.ct : ct;
+  const int wct_next = (ct_next - ct) * (2 * 9 * 256) * nch16;     // cells from this cout tile's weight image to the next unit's
   const int nty = sp_next / a.tiles_x, ntx = sp_next - nty * a.tiles_x;
   const int n_oy0 = nty * kQTH, n_vx0 = ntx * 32;
   // the next tile's gather offsets: parked in LDS (a thread's own words) until the last chunk asks for them -- in registers they
@@ -341,8 +351,8 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
       for (int i = 0; i < 18; ++i) {
         const int cpar = i / 9, t = i % 9, c = cp + cpar, kh = kTap[t] / 3, kw = kTap[t] % 3;
         const bool last = cpar == 1 && c + 1 >= nch32;        // conv1's last chunk: the downsample's first stage comes next
-        if (t < 8) load_w_tap(c, kTap[t + 1], (i + 1) & 1);
-        else if (!last) load_w_tap(c + 1, kTap[0], (i + 1) & 1);
+        if (t < 8) load_w_tap(ct, c, kTap[t + 1], (i + 1) & 1);
+        else if (!last) load_w_tap(ct, c + 1, kTap[0], (i + 1) & 1);
         else load_w_ds(0, 0);
         const int nplane = t >= 5 && last ? 3 : kPlaneNext[t];
         const int nchunk = t < 5 ? c : (last ? 0 : c + 1);
@@ -364,7 +374,7 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
         // stage's barrier), and at a kernel row's first tap one round of the NEXT chunk's patch into the idle patch buffer
         // -- past the tile's end: the NEXT tile's first tap / first chunk (buffers 0: the last stage is odd, the last chunk is
         // chunk parity 1), or, without a next tile, the last stage / chunk again (never read)
-        load_w(s + 1 < nstages ? s + 1 : (has_next ? 0 : nstages - 1), (i + 1) & 1);
+        load_w(s + 1 < nstages ? s + 1 : (has_next ? 0 : nstages - 1), (i + 1) & 1, s + 1 < nstages ? 0 : wct_next);
         if (kw == 0) {
           // (the tile's last chunk has chunk parity 1: the channel chunks come in pairs)
           if (cpar == 0 || cp + cpar + 1 < nch32) load_p(cp + cpar + 1, kh, (cpar + 1) & 1);
@@ -614,7 +624,7 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
 #pragma unroll
             for (int k = 0; k < PIT; ++k) load_p_at(c + 1, k, (i + 1) & 1, gpl[(3 * PIT + k) * NT + tid]);
           } else {
-            load_w_tap(0, kTap[0], 0);
+            load_w_tap(ct_next, 0, kTap[0], 0);
 #pragma unroll
             for (int k = 0; k < PIT; ++k) load_p_at(0, k, 0, gnext[k * NT + tid]);
           }
@@ -710,7 +720,17 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   // ---- on to this workgroup's next tile: its first chunk and first tap are in LDS already ----
   if (!has_next) break;
   if constexpr (TRAIN == 1 || TRAIN == 2) __syncthreads();        // every wave is done with this tile's statistics area (patch buffer 1)
-  sp = sp_next; tx = ntx; ty = nty; oy0 = n_oy0; vx0 = n_vx0;
+  if (ct_next != ct) {             // (uniform) another cout tile: its constants, once every wave has read this tile's; the stage
+    if constexpr (TRAIN == 0 || S2) __syncthreads();              // barriers of the next tile stand between these writes and their readers
+    load_consts(ct_next);
+  }
+  // (the next unit's coordinates derived AGAIN, behind an opaque copy: carried through the stage loop they are six more scalars)
+  u += Qs;
+  asm volatile("" : "+s"(u));
+  un = hs3x3q_unit(u, a.cout_tiles);
+  sp = un.sp; ct = un.ct;
+  ty = sp / a.tiles_x; tx = sp - ty * a.tiles_x;
+  oy0 = ty * kQTH; vx0 = tx * 32;
   }
   range_flag(a.status, bad);
 }

@@ -1,5 +1,6 @@
 // Shared between the inference (conv2d.hip) and training (resnet_train.hip) perception executors.
 #pragma once
+#include <algorithm>
 #include <vector>
 
 #include "adx_common.h"
@@ -39,7 +40,7 @@ struct Conv2dArgs {
   int N, Cin, H, W, Cout, OH, OW, KH, KW, stride, pad, relu;
   int cin_pad, cc;      // channels padded to the chunk size, chunk size (16, or 4 for the stem)
   int tiles_x, tiles_y, cout_tiles, ntiles;
-  int q_slots;          // conv2d_hs3x3q only: workgroups per (XCD, cout tile); each walks its XCD's spatial tiles in steps of q_slots
+  int q_slots;          // conv2d_hs3x3q only: workgroups per XCD; each walks its XCD's units (hs3x3q_walk) in steps of q_slots
   int PH, PW, PWp;      // staged patch rows, columns, padded row pitch
   // conv2d_hs3x3 only: the input-channel chunks split over `ksplit` workgroups per tile (small batches: a 512->512 layer
   // on one 8x29 map is 8 tiles); part kpart covers chunks [kpart * cper, (kpart + 1) * cper) and writes its raw sums to
@@ -140,7 +141,7 @@ struct Hs3x3Query {
   bool affine = false, relu = false, has_res = false;
   bool y_aligned = true, res_aligned = true;       // 16-byte alignment (the split reduction's vector accesses)
   size_t split_floats = 0;        // capacity of the split-reduction scratch (0: none)
-  int cus = 0;                    // compute units of the device (sizes the persistent grid only)
+  int cus = 0;                    // compute units the launch may use (launch_cus; sizes the persistent grid only)
 };
 struct Hs3x3Plan {
   bool admitted = false;          // the operand formats of the query are ones the launch can take (fmt == 0 always is)
@@ -158,6 +159,25 @@ struct Hs3x3Plan {
   size_t stats_need = 0;          // floats those take: the sums and (data gradient) max |dz| per 64-channel slab
 };
 Hs3x3Plan conv2d_hs3x3_plan(const ConvSpec& L, const Hs3x3Query& q, const DebugSwitches& sw = debug_switches());
+// ---- the unit walk of conv2d_hs3x3q_kernel (conv2d_hs16.hip) ----
+// A launch's work is `units` = spatial tiles x cout tiles pieces, unit u = spatial tile * cout_tiles + cout tile.  XCD x (workgroup
+// b runs on XCD b & 7) owns the contiguous range [x units / 8, (x + 1) units / 8); workgroup (x, slot = b >> 3) visits first,
+// first + Q, ... below end, Q = grid / 8 workgroups per XCD.  The kernel and the export (adx_conv2d_hs3x3q_walk) share the range
+// (hs3x3q_walk) and the split of a unit (hs3x3q_unit); the loop `u += Q while u < end` is written in each.
+struct HsQWalk { int first, end; };
+__host__ __device__ inline HsQWalk hs3x3q_walk(int xcd, int slot, int units) {
+  return HsQWalk{(int)(((long)xcd * units) >> 3) + slot, (int)(((long)(xcd + 1) * units) >> 3)};
+}
+struct HsQUnit { int sp, ct; };
+__host__ __device__ inline HsQUnit hs3x3q_unit(int u, int cout_tiles) {
+  const int sp = u / cout_tiles;
+  return HsQUnit{sp, u - sp * cout_tiles};
+}
+// workgroups per XCD of such a launch: one unit per workgroup (the longest range), or as many as `cus` compute units hold
+inline int hs3x3q_slots(int units, int cus, bool persistent) {
+  const int longest = (units + 7) / 8;
+  return persistent ? std::min(longest, std::max(1, cus / 8)) : longest;
+}
 // true when this launch will run the pipelined 3x3 stride-1 kernel as ONE launch (no split reduction): the launches whose
 // input / output / residual may be in the cell layout (fmt: kFmt*)
 inline bool conv2d_hs3x3_plain(const ConvSpec& L, int N, int H, int W) {
@@ -244,7 +264,7 @@ int conv2d_hs_launch_block_s2(const ConvSpec& c1, const ConvSpec& ds, const floa
 struct HsS2Query {
   int N = 0, H = 0, W = 0;        // the INPUT's size
   bool x_cells = false, y_cells = false;
-  int cus = 0;                    // compute units of the device (sizes the persistent grid only)
+  int cus = 0;                    // compute units the launch may use (launch_cus; sizes the persistent grid only)
 };
 struct HsS2Plan {
   bool q = false;                 // conv2d_hs3x3q_s2_kernel serves the launch
@@ -257,6 +277,15 @@ HsS2Plan conv2d_hs_s2_plan(const ConvSpec& c1, const ConvSpec& ds, const HsS2Que
 int conv2d_hs3x3q_s2_launch(const HsS2Plan& p, Conv2dArgs a, hipStream_t s);
 // compute units of the calling thread's current device (conv2d.hip)
 int device_cus(int* cus);
+// ... that a conv2d_hs3x3q launch issued by this thread may use: the device's less the reserve -- the executor's while one is set
+// (conv2d_set_reserve_cus; -1 clears it), ADX_HS_RESERVE_CUS otherwise -- a multiple of 8, at least 8, at most ADX_HS_GRID_CAP
+int launch_cus(int* cus);
+void conv2d_set_reserve_cus(int reserve);
+inline int hs_usable_cus(int device, int reserve, int cap) {
+  int n = std::max(8, (device - std::max(0, reserve)) & ~7);
+  if (cap > 0) n = std::min(n, std::max(8, cap & ~7));
+  return n;
+}
 // conv1 3x3 stride 2 on the split-fp16 kernel + a 1x1 stride-2 downsample of the same shape: one fused launch (conv2d.hip)
 inline bool resnet_fuses_ds(const ConvSpec& c1, const ConvSpec& ds, const DebugSwitches& sw = debug_switches()) {
   return conv2d_hs_eligible(c1, sw) && c1.k == 3 && c1.stride == 2 && c1.pad == 1 && ds.k == 1 && ds.stride == 2 && ds.pad == 0 &&
@@ -330,10 +359,14 @@ struct ResnetSegment {                      // the whole-batch prefix, or one su
 };
 struct ResnetEvalPlan {
   int nsub = 1, first_split = 0;            // blocks [0, first_split) run once, on the whole batch (with the stem when first_split > 0)
+  int reserve_cus = 0;                      // compute units the pass's persistent conv2d_hs3x3q launches leave free (chosen with nsub)
   ResnetLayout lay;
   int nseg = 0;                             // (first_split > 0) + nsub: the prefix first
   ResnetSegment seg[1 + adx_resnet::kMaxSub];
 };
+// the reserve of a pass that keeps one chain as today (small batches, captures, ADX_CHECK_RANGE=1) / of an eval pass of B >= 32
+// outside a capture: what the measurement of the four candidates chose (profiles/README.md, "The unit walk")
+constexpr int kEvalReserveCus[2] = {0, 0};
 // ADX_ERR_INVALID (with the message set) for a shape or format hand-off the executor cannot run
 int resnet_eval_plan(const adx_resnet& r, const ResnetEvalQuery& q, ResnetEvalPlan* plan, const DebugSwitches& sw = debug_switches());
 // ADX_CHECK_RANGE=1 (no-op otherwise): fails with ADX_ERR_RANGE naming (what, index) when the tensor holds |x| >= 65504 or a

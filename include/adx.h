@@ -358,6 +358,21 @@ enum { ADX_RESNET_PLAN_STEM_POOL = 0, ADX_RESNET_PLAN_STEM = 1, ADX_RESNET_PLAN_
        ADX_RESNET_PLAN_ENTRY = 4, ADX_RESNET_PLAN_AVGPOOL_FC = 5 };
 int adx_resnet_plan_describe(const adx_resnet* r, int32_t batch, int32_t h, int32_t w, int32_t flags, int32_t* n_records, int32_t* ints,
                              int32_t max_records);
+/* For tests only, beside adx_resnet_plan_describe (same arguments, same records in the same order; its own record width so that
+ * the other's stays what it is): the grid each launch of that plan gets on a device of `cus` compute units.  The pass's persistent
+ * 3x3 launches (conv2d_hs3x3q: the 16x16x32 kernel's unit walk) use 8 x ((cus - reserve) / 8) workgroups at most; the reserve is
+ * chosen with the sub-batches (ADX_HS_RESERVE_CUS=<n> pins it; so does reserve >= 0 here, -1: the plan's own).  ADX_RESNET_GRID_INTS
+ * words per record:
+ *   [0] 1: a persistent unit-walk launch, 0: any other (then [1], [2] are 0 and [3] is the grid of a one-tile-per-workgroup 3x3
+ *       launch, or 0); [1] units = spatial tiles x cout tiles; [2] workgroups per XCD; [3] grid = 8 x [2]
+ *   [4] the plan's reserve, [5] the compute units its launches may use (the same in every record) */
+#define ADX_RESNET_GRID_INTS 6
+int adx_resnet_plan_grids(const adx_resnet* r, int32_t batch, int32_t h, int32_t w, int32_t flags, int32_t cus, int32_t reserve,
+                          int32_t* n_records, int32_t* ints, int32_t max_records);
+/* For tests only: the unit walk of a persistent 3x3 launch of `grid` workgroups (a multiple of 8) over `units` = spatial tiles x
+ * cout_tiles units, from the range and unit functions the kernel itself uses.  counts[b]: units workgroup b visits (grid words);
+ * visits: (spatial tile, cout tile) pairs, workgroup after workgroup in visiting order (2 x units words). */
+int adx_conv2d_hs3x3q_walk(int32_t units, int32_t cout_tiles, int32_t grid, int32_t* counts, int32_t* visits);
 int32_t adx_resnet_status_words(const adx_resnet* r);
 int adx_resnet_set_status(adx_resnet* r, uint32_t* words /* device, adx_resnet_status_words(r) words, or NULL */);
 const char* adx_resnet_status_name(const adx_resnet* r, int32_t group);
