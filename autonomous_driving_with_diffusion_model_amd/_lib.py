@@ -149,6 +149,9 @@ _SIGS = {
     "adx_gn_mish_backward": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "adx_tconv_wgrad": (i32, [C.POINTER(TConvDesc), C.POINTER(TConvIO), vp, vp, vp]),
     "adx_bias_grad": (i32, [vp, vp, i32, i32, i32, vp]),
+    "adx_gn_mish_backward_ex": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "adx_bias_grad_ex": (i32, [vp, i64, i64, i64, vp, i32, i32, i32, i32, vp]),
+    "adx_tconv_wgrad_plan_describe": (i32, [C.POINTER(TConvDesc), i32, C.POINTER(i32)]),
     "adx_chan_layernorm_forward": (i32, [vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "adx_chan_layernorm_backward": (i32, [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "adx_linattn_forward": (i32, [vp, vp, i32, i32, i32, vp]),

@@ -277,6 +277,48 @@ __global__ void __launch_bounds__(256) tconv_wgrad_kernel(const WgradArgs a) {
   }
 }
 
+// The launch geometry of tconv_wgrad for `batch` samples: host arithmetic only (no HIP call, no state), shared by the launch
+// below and by the export for tests (include/adx.h: adx_tconv_wgrad_plan_describe).
+struct WgradPlan {
+  int per4, nfo;                 // samples per MFMA K-step (lout < 4: 4 / lout); 16-column fragments per workgroup
+  int n_ci_tiles, n_co_tiles, tiles;
+  int nsplit, nb;                // workgroups sharing one weight tile, samples per workgroup
+  int sbt, pl, lp, rs;           // samples per staged super-tile, left pad, per-sample pitch, LDS row stride
+  size_t lds_stage, lds_red, lds_bytes;   // staging / reduction footprint and their maximum, bytes
+  int grid;
+};
+
+static WgradPlan tconv_wgrad_plan(const adx_tconv_desc* d, int batch) {
+  WgradPlan p;
+  const int cin = d->c0 + d->c1;
+  // (sample, position) rows are consumed 4 at a time; staged super-tiles hold whole K-steps when possible
+  p.per4 = d->lout >= 4 ? 1 : 4 / d->lout;   // samples per MFMA K-step
+  p.nfo = d->cout >= 64 ? 4 : (d->cout > 16 ? 2 : 1);
+  p.n_ci_tiles = ceil_div(cin, 16);
+  p.n_co_tiles = ceil_div(d->cout, 16 * p.nfo);
+  p.tiles = p.n_ci_tiles * p.n_co_tiles;
+  // split the batch so that ~256 workgroups exist, each with at least `per4` samples
+  int nsplit = ceil_div(256, p.tiles);
+  int nb = ceil_div(batch, nsplit);
+  nb = round_up(nb < p.per4 ? p.per4 : nb, p.per4);
+  nsplit = ceil_div(batch, nb);
+  p.nb = nb; p.nsplit = nsplit;
+  const int pr = (d->lout - 1) * d->stride + d->taps - 1 - d->pad - (d->lin - 1);
+  p.pl = d->pad;
+  p.lp = p.pl + d->lin + (pr > 0 ? pr : 0);
+  int sbt = 128 / d->lout;                 // 128 (sample, position) rows = 8 K-steps per wave per super-tile
+  if (sbt < p.per4) sbt = p.per4;
+  sbt = sbt / p.per4 * p.per4;
+  if (sbt > nb) sbt = nb;
+  p.sbt = sbt;
+  p.rs = sbt * p.lp + 1;                   // odd pitch: the 16 channel rows of an A fragment hit distinct banks
+  const size_t lds_stage = (size_t)16 * p.rs, lds_red = (size_t)16 * p.nfo * 16 * d->taps;
+  p.lds_stage = sizeof(float) * lds_stage; p.lds_red = sizeof(float) * lds_red;
+  p.lds_bytes = sizeof(float) * (lds_stage > lds_red ? lds_stage : lds_red);
+  p.grid = p.tiles * nsplit;
+  return p;
+}
+
 int tconv_wgrad(const adx_tconv_desc* d, const adx_tconv_io* io, const float* dc, float* dw, hipStream_t s, bool zero) {
   int rc = tconv_check(d);
   if (rc != ADX_OK) return rc;
@@ -295,33 +337,16 @@ int tconv_wgrad(const adx_tconv_desc* d, const adx_tconv_io* io, const float* dc
   while ((1 << a.log2_lout) < d->lout) ++a.log2_lout;
   a.taps = d->taps; a.stride = d->stride; a.pad = d->pad;
   a.batch = io->batch;
-  // (sample, position) rows are consumed 4 at a time; staged super-tiles hold whole K-steps when possible
-  const int per4 = d->lout >= 4 ? 1 : 4 / d->lout;   // samples per MFMA K-step
-  const int nfo = d->cout >= 64 ? 4 : (d->cout > 16 ? 2 : 1);
-  a.n_ci_tiles = ceil_div(a.cin, 16);
-  a.n_co_tiles = ceil_div(d->cout, 16 * nfo);
-  const int tiles = a.n_ci_tiles * a.n_co_tiles;
-  // split the batch so that ~256 workgroups exist, each with at least `per4` samples
-  int nsplit = ceil_div(256, tiles);
-  int nb = ceil_div(io->batch, nsplit);
-  nb = round_up(nb < per4 ? per4 : nb, per4);
-  nsplit = ceil_div(io->batch, nb);
-  a.nb = nb; a.nsplit = nsplit;
-  const int pr = (d->lout - 1) * d->stride + d->taps - 1 - d->pad - (d->lin - 1);
-  a.pl = d->pad;
-  a.lp = a.pl + d->lin + (pr > 0 ? pr : 0);
-  int sbt = 128 / d->lout;                 // 128 (sample, position) rows = 8 K-steps per wave per super-tile
-  if (sbt < per4) sbt = per4;
-  sbt = sbt / per4 * per4;
-  if (sbt > nb) sbt = nb;
-  a.sbt = sbt;
-  a.rs = sbt * a.lp + 1;                   // odd pitch: the 16 channel rows of an A fragment hit distinct banks
-  ADX_REQUIRE((sbt * d->lout) % 4 == 0, "tconv_wgrad: staged tile not a multiple of 4 rows");
+  const WgradPlan p = tconv_wgrad_plan(d, io->batch);
+  a.n_ci_tiles = p.n_ci_tiles; a.n_co_tiles = p.n_co_tiles;
+  a.nb = p.nb; a.nsplit = p.nsplit;
+  a.pl = p.pl; a.lp = p.lp; a.sbt = p.sbt; a.rs = p.rs;
+  ADX_REQUIRE((p.sbt * d->lout) % 4 == 0, "tconv_wgrad: staged tile not a multiple of 4 rows");
   a.dw_so = (int64_t)a.cin * d->taps; a.dw_si = d->taps;
   if (zero) ADX_CHECK_HIP(hipMemsetAsync(dw, 0, sizeof(float) * (size_t)d->cout * a.cin * d->taps, s));   // else: pre-zeroed by the caller
-  const size_t lds_stage = (size_t)16 * a.rs, lds_red = (size_t)16 * nfo * 16 * d->taps;
-  const size_t lds = sizeof(float) * (lds_stage > lds_red ? lds_stage : lds_red);
-  const dim3 grid((unsigned)(tiles * nsplit)), blk(256);
+  const int nfo = p.nfo;
+  const size_t lds = p.lds_bytes;
+  const dim3 grid((unsigned)p.grid), blk(256);
 #define ADX_WG(NFO, TAPS) tconv_wgrad_kernel<NFO, TAPS><<<grid, blk, lds, s>>>(a)
 #define ADX_WG_T(NFO)                                  \
   switch (d->taps) {                                   \
@@ -361,12 +386,40 @@ int adx_gn_mish_backward(const float* dy, int64_t dy_sb, int64_t dy_sc, int64_t 
   return gn_mish_backward(a, (hipStream_t)stream);
 }
 
+int adx_gn_mish_backward_ex(const float* dy, int64_t dy_sb, int64_t dy_sc, int64_t dy_sl, const float* pre,
+                            const float* stats, const float* gamma, const float* beta, float* dc, float* dgamma,
+                            float* dbeta, float* dbias, float* dtb, int64_t dtb_stride, int32_t B, int32_t C, int32_t L,
+                            int32_t groups, int32_t L_valid, adx_stream stream) {
+  ADX_REQUIRE(B >= 1 && C >= 1 && L >= 1 && groups >= 1 && C % groups == 0 && L_valid >= 0, "adx_gn_mish_backward_ex: bad shape");
+  return gn_mish_backward_raw(dy, dy_sb, dy_sc, dy_sl, pre, stats, gamma, beta, dc, dgamma, dbeta, dbias, dtb, dtb_stride, B, C, L,
+                              groups, (hipStream_t)stream, L_valid);
+}
+
 int adx_tconv_wgrad(const adx_tconv_desc* d, const adx_tconv_io* io, const float* dc, float* dw, adx_stream stream) {
   return tconv_wgrad(d, io, dc, dw, (hipStream_t)stream, true);
 }
 
+int adx_tconv_wgrad_plan_describe(const adx_tconv_desc* d, int32_t batch, int32_t* ints) {
+  ADX_REQUIRE(d != nullptr && ints != nullptr, "adx_tconv_wgrad_plan_describe: null argument");
+  ADX_REQUIRE(batch >= 1, "adx_tconv_wgrad_plan_describe: batch must be >= 1");
+  int rc = tconv_check(d);
+  if (rc != ADX_OK) return rc;
+  ADX_REQUIRE(d->kind == 0, "adx_tconv_wgrad_plan_describe: a transposed conv's weight gradient runs as the mirrored strided conv");
+  const WgradPlan p = tconv_wgrad_plan(d, batch);
+  const int32_t v[ADX_WGRAD_PLAN_INTS] = {p.per4, p.nfo, p.n_ci_tiles, p.n_co_tiles, p.tiles, p.nsplit, p.nb, p.sbt, p.pl, p.lp, p.rs,
+                                          (int32_t)p.lds_stage, (int32_t)p.lds_red, (int32_t)p.lds_bytes, p.grid, 0};
+  for (int i = 0; i < ADX_WGRAD_PLAN_INTS; ++i) ints[i] = v[i];
+  return ADX_OK;
+}
+
 int adx_bias_grad(const float* dc, float* db, int32_t B, int32_t C, int32_t L, adx_stream stream) {
   return bias_grad(dc, (int64_t)C * L, L, 1, db, B, C, L, (hipStream_t)stream, 0);
+}
+
+int adx_bias_grad_ex(const float* dc, int64_t sb, int64_t sc, int64_t sl, float* db, int32_t B, int32_t C, int32_t L,
+                     int32_t L_valid, adx_stream stream) {
+  ADX_REQUIRE(L_valid >= 0 && L_valid <= L, "adx_bias_grad_ex: L_valid %d outside [0, %d]", L_valid, L);
+  return bias_grad(dc, sb, sc, sl, db, B, C, L, (hipStream_t)stream, L_valid);
 }
 
 }  // extern "C"

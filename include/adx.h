@@ -275,6 +275,29 @@ int adx_gn_mish_backward(const float* dy, int64_t dy_sb, int64_t dy_sc, int64_t 
 /* op level: dW[cout][cin][taps] of a (kind 0) temporal conv from its input (io->x0/x1) and d(conv out) */
 int adx_tconv_wgrad(const adx_tconv_desc* d, const adx_tconv_io* io, const float* dc, float* dw, adx_stream s);
 int adx_bias_grad(const float* dc, float* db, int32_t B, int32_t C, int32_t L, adx_stream s);
+/* The same two ops with the arguments the training executor passes.  adx_gn_mish_backward_ex: L is the padded (power of
+ * two) length, L_valid the real one (0: L): positions >= L_valid are not read, count in no sum, and come out zero in dc.
+ * dgamma, dbeta, dbias (may be NULL) are added to (the caller zeroes them); dtb (may be NULL) is written where L <= 64 and
+ * added to beyond.  adx_bias_grad_ex: db[c] = sum over b and l < L_valid of dc[b * sb + c * sc + l * sl] (written). */
+int adx_gn_mish_backward_ex(const float* dy, int64_t dy_sb, int64_t dy_sc, int64_t dy_sl, const float* pre,
+                            const float* stats, const float* gamma, const float* beta, float* dc, float* dgamma,
+                            float* dbeta, float* dbias, float* dtb, int64_t dtb_stride, int32_t B, int32_t C, int32_t L,
+                            int32_t groups, int32_t L_valid, adx_stream s);
+int adx_bias_grad_ex(const float* dc, int64_t sb, int64_t sc, int64_t sl, float* db, int32_t B, int32_t C, int32_t L,
+                     int32_t L_valid, adx_stream s);
+/* For tests only: the launch geometry adx_tconv_wgrad (and the training executor) uses for `batch` samples -- the function
+ * the launch itself calls; host arithmetic, needs no GPU.  ints: ADX_WGRAD_PLAN_INTS words
+ *   [0] per4        samples per MFMA K-step of 4 (sample, position) rows: 1 for lout >= 4, else 4 / lout
+ *   [1] nfo         16-channel output fragments per workgroup (4, 2 or 1)
+ *   [2] n_ci_tiles  16-channel input tiles, [3] n_co_tiles: (16 nfo)-channel output tiles, [4] tiles = their product
+ *   [5] nsplit      workgroups that share one weight tile (1: plain stores, more: float atomics onto the zeroed dW)
+ *   [6] nb          samples per workgroup: split i reduces samples [i nb, min((i + 1) nb, batch))
+ *   [7] sbt         samples per staged super-tile (the kernel walks its nb samples sbt at a time; sbt lout <= 128 rows)
+ *   [8] pl, [9] lp  left zero pad and per-sample pitch of the staged input, [10] rs: LDS row stride = sbt lp + 1
+ *   [11] staging bytes, [12] reduction bytes, [13] dynamic LDS bytes (their maximum)
+ *   [14] grid = tiles nsplit, [15] 0 */
+#define ADX_WGRAD_PLAN_INTS 16
+int adx_tconv_wgrad_plan_describe(const adx_tconv_desc* d, int32_t batch, int32_t* ints);
 /* op level, the attention block's own kernels (csrc/attn.hip); L is the padded length (<= 64 for the core), L_valid the
  * real one (0: L).  LayerNorm over channels of x [B][C][L] (strided) -> dense xn [B][C][L] and, when not NULL, the
  * per-(sample, position) mean and rstd [B][L] the backward needs. */
