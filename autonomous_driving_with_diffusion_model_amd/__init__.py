@@ -15,6 +15,8 @@ Public surface mirrors the reference's packages:
     MotionLimits                                      (no reference counterpart: speed and acceleration limits in a Guide, guide.py)
     Route                                             (no reference counterpart: a route corridor in a Guide, guide.py)
     Capsules                                          (no reference counterpart: moving capsules in a Guide, guide.py)
+    StopShort, StopResult                             (no reference counterpart: re-time a blocked plan to halt before its
+                                                       conflict, control/fallback.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -35,10 +37,11 @@ from .noise import DeviceNoise  # noqa: E402
 from .scheduler import GuidanceDPMSolverMultistepScheduler  # noqa: E402
 from .control.select import Selection, TrajectorySelector  # noqa: E402
 from .control.device import DeviceController  # noqa: E402
+from .control.fallback import StopResult, StopShort  # noqa: E402
 from .pin import Pin  # noqa: E402
 from .guide import Capsules, CostField, Guide, MotionLimits, Route  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
-           "Route", "Capsules"]
+           "Route", "Capsules", "StopShort", "StopResult"]

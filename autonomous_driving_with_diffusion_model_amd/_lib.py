@@ -293,6 +293,8 @@ _LAZY_SIGS = {
     "adx_traj_select_guide_capsule": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
                                             C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp, vp, vp, vp, vp]),
     "adx_capsules_from_boxes": (i32, [vp, vp, i32, i32, f32, vp]),
+    "adx_stop_short": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, i32, vp, vp,
+                             vp, vp, vp, i32, i32, i32, vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)

@@ -3,7 +3,8 @@ from .device import DeviceController
 from .guidance import GuidanceLoss
 from .guidance_loss import TargetGuidance
 from .pid import PIDController
+from .fallback import StopResult, StopShort
 from .select import Selection, TrajectorySelector
 
 __all__ = ["GuidanceLoss", "TargetGuidance", "Controller", "PIDController", "post_process_control", "Selection",
-           "TrajectorySelector", "DeviceController"]
+           "TrajectorySelector", "DeviceController", "StopShort", "StopResult"]

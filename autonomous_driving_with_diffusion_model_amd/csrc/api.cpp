@@ -77,6 +77,9 @@ size_t control_state_bytes(int scenes, int n_turn, int n_speed);
 int control_step(const adx_control_cfg* c, const float* traj, const float* velocity, const float* target, void* state,
                  float* control, hipStream_t s);
 int control_reset(void* state, int scenes, int n_turn, int n_speed, const uint8_t* mask, hipStream_t s);
+int stop_short(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_route* route,
+               const adx_guide_capsules* capsules, const float* params, int param_rows, float* out, int32_t* first, int32_t* status,
+               float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);
 }  // namespace adx
 
 extern "C" {
@@ -440,6 +443,12 @@ int adx_control_step(const adx_control_cfg* c, const float* traj, const float* v
 }
 int adx_control_reset(void* state, int32_t scenes, int32_t n_turn, int32_t n_speed, const uint8_t* mask, adx_stream s) {
   return adx::control_reset(state, scenes, n_turn, n_speed, mask, (hipStream_t)s);
+}
+int adx_stop_short(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_route* route,
+                   const adx_guide_capsules* capsules, const float* params, int32_t param_rows, float* out, int32_t* first,
+                   int32_t* status, float* stop_at, int32_t* active_after, int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::stop_short(traj, guide, field, route, capsules, params, param_rows, out, first, status, stop_at, active_after, rows,
+                         horizon, dim, (hipStream_t)s);
 }
 int adx_noise_normal(const uint32_t* state, int32_t slot, int64_t first_elem, float* out, int64_t n, adx_stream s) {
   return adx::noise_normal(state, slot, first_elem, out, n, (hipStream_t)s);

@@ -38,6 +38,9 @@ An eleventh says where the road is: `guide=Guide(..., route=Route(points, half_w
 per-scene polyline ("cost guidance v4"), a point-wise term of the same routine, so it runs in whichever step kernel the rest picks.
 A twelfth says where the other vehicles are: `guide=Guide(..., capsules=Capsules(slots))` steers around per-scene moving capsules
 ("cost guidance v5"), point-wise like the route; `Capsules.from_boxes` makes them from oriented boxes in one capturable launch.
+A thirteenth is the last resort when the plan a tick ends with still runs into something: `fallback=StopShort(params)` keeps its
+path and re-times it to brake to a halt before its first conflict with the guide ("stop-short fallback v1", control/fallback.py),
+one launch between selection and control; the controller and the caller get the re-timed plan, the warm state the sampler's own.
 """
 from __future__ import annotations
 
@@ -51,6 +54,7 @@ import torch
 from . import _lib as L
 from ._lib import AdxRangeError
 from .control.device import DeviceController
+from .control.fallback import MAX_HORIZON as FALLBACK_MAX_HORIZON, NO_POINTWISE_TERM, StopResult, StopShort, pointwise
 from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
 from .noise import DeviceNoise
@@ -202,19 +206,27 @@ class TickPlan:
     # guide's route ("cost guidance v4"): the [S, R, 2] points and [S] half-widths are buffers; presence, R and the weight are baked.
     # A guide's capsules ("cost guidance v5"): the [S, C, 7] slots are a buffer; presence, C and the weight are baked
     guide: Optional[Guide]
+    # ---- fallback ----
+    # params: a buffer; presence: baked.  After selection and the copy into warm.prev, one launch of `fallback(best, guide)`
+    # re-times the [S, H, D] result (the winners at K > 1) in place, against the tick's guide and before the control launch: the
+    # controller and the caller get the re-timed plan, warm.prev keeps the sampler's own winner (a warm start from a stopped plan
+    # would teach the next tick to stop).  Needs a guide with a point-wise term, H <= 64, D >= 2 and no `source="action"` controller
+    fallback: Optional[StopShort] = None
 
     def key(self) -> tuple:
-        """Everything baked, as a hashable: two plans with equal keys capture the same graph over the same shapes."""
+        """Everything baked, as a hashable: two plans with equal keys capture the same graph over the same shapes.  A plan without
+        a fallback keeps the key it had."""
         sel, ctl, pin, guide = self.selector, self.controller, self.pin, self.guide
         weights = None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus)
         if sel is not None and sel.uses_guide:
             weights += (sel.w_guide, sel.hard)
-        return (self.S, self.K, weights, self.rows, self.H, self.D,
-                self.n, self.use, self.free_scale, self.fuse, self.hoisted, self.is_ddpm,
-                "init" if self.start == "randn" else self.start,
-                self.m_warm, self.shift, self.is_warm, self.motion is None,
-                None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), self.velocity is None),
-                None if pin is None else (pin.mode, tuple(pin.known.shape)), None if guide is None else guide.key())
+        key = (self.S, self.K, weights, self.rows, self.H, self.D,
+               self.n, self.use, self.free_scale, self.fuse, self.hoisted, self.is_ddpm,
+               "init" if self.start == "randn" else self.start,
+               self.m_warm, self.shift, self.is_warm, self.motion is None,
+               None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), self.velocity is None),
+               None if pin is None else (pin.mode, tuple(pin.known.shape)), None if guide is None else guide.key())
+        return key if self.fallback is None else key + (self.fallback.key(),)
 
 
 def _hoists(model) -> bool:
@@ -273,18 +285,43 @@ def _guide_plan(cfg, guide: Optional[Guide], image, scheduler) -> Optional[Guide
     return guide
 
 
+def _fallback_plan(cfg, fallback: Optional[StopShort], guide: Optional[Guide], controller: Optional[DeviceController],
+                   image) -> Optional[StopShort]:
+    """The fallback section of `plan_tick`: the fallback (None without one), or a refusal."""
+    if fallback is None:
+        return None
+    if not isinstance(fallback, StopShort):
+        raise TypeError(f"generate_traj: `fallback` must be a StopShort, got {type(fallback).__name__}")
+    if guide is None:
+        raise ValueError("generate_traj: a fallback re-times the plan against a guide; pass guide=Guide(...) for the tick")
+    if not pointwise(guide):
+        raise ValueError(NO_POINTWISE_TERM)
+    H, D, S = int(cfg.MODEL.HORIZON), int(cfg.MODEL.TRANSITION_DIM), int(image.shape[0])
+    if H > FALLBACK_MAX_HORIZON:
+        raise ValueError(f"generate_traj: a fallback gives a row to a wave and needs MODEL.HORIZON <= {FALLBACK_MAX_HORIZON}, got {H}")
+    if D < 2:
+        raise ValueError(f"generate_traj: a fallback re-times (x, y) and needs MODEL.TRANSITION_DIM >= 2, got {D}")
+    if fallback.scenes != S or fallback.device != image.device:
+        raise ValueError(f"fallback.params must hold {S} scenes (image.shape[0]) on {image.device}, got "
+                         f"{tuple(fallback.params.shape)} on {fallback.device}")
+    if controller is not None and controller.source == "action":
+        raise ValueError("generate_traj: a controller with source='action' reads the model's action columns and would not see a "
+                         "re-timing; use source='pid' with a fallback")
+    return fallback
+
+
 def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
               init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, set_timesteps: bool = True,
               noise: Optional[DeviceNoise] = None, step_noise=None, candidates: int = 1,
               selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
               motion: Optional[torch.Tensor] = None, controller: Optional[DeviceController] = None,
               velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, guide: Optional[Guide] = None,
-              graphed: bool = False) -> TickPlan:
+              fallback: Optional[StopShort] = None, graphed: bool = False) -> TickPlan:
     """The TickPlan of a `generate_traj` call with these arguments (`graphed`: of a GraphedSampler call).  Pure: no launch, no device
     allocation (but one: a strided `motion` is packed, as it always was), no tick of the noise stream, nothing written to the
     scheduler, `warm` or the controller -- so every refusal comes before any of those and before a capture opens, in the order
-    candidates, `noise` / `step_noise`, warm, control, pin, guide, a selector that needs a guide.  `scheduler` is read for a warm
-    tick on the caller's own timesteps (`set_timesteps=False`), for a pin and for a guide; `is_ddpm` asks it with defaults."""
+    candidates, `noise` / `step_noise`, warm, control, pin, guide, a selector that needs a guide, fallback.  `scheduler` is read for
+    a warm tick on the caller's own timesteps (`set_timesteps=False`), for a pin and for a guide; `is_ddpm` asks it with defaults."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     S, device = int(image.shape[0]), image.device
     hoisted = bool(fuse) and _hoists(model)
@@ -364,6 +401,7 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
     guide = _guide_plan(cfg, guide, image, scheduler)
     if K > 1 and selector.uses_guide and guide is None:
         raise ValueError(f"generate_traj: {selector!r} scores the candidates against a guide; pass guide=Guide(...) for the tick")
+    fallback = _fallback_plan(cfg, fallback, guide, controller, image)
     rows = K * S if init_trajs is None else int(init_trajs.shape[0])
     free = use == GuidanceType.FREE_GUIDANCE
     return TickPlan(S=S, K=K, selector=selector if K > 1 else None, rows=rows, H=H, D=D, n=n, use=use,
@@ -373,7 +411,7 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
                     start="warm" if is_warm else "init" if init_trajs is not None else "randn" if noise is None else "stream",
                     m_warm=m_warm, shift=shift, is_warm=is_warm, motion=motion, i0=n - m_warm if is_warm else 0,
                     controller=controller, velocity=velocity, pin=pin, entry_blend=pin is not None and pin.mode == "clean",
-                    guide=guide)
+                    guide=guide, fallback=fallback)
 
 
 def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
@@ -383,17 +421,19 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
                   selector: Optional[TrajectorySelector] = None, return_selection: bool = False,
                   warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
                   controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None,
-                  pin: Optional[Pin] = None, guide: Optional[Guide] = None):
+                  pin: Optional[Pin] = None, guide: Optional[Guide] = None, fallback: Optional[StopShort] = None):
     """One sampling tick: `plan_tick` decides (what each argument means is written on the TickPlan field it becomes), this
     function runs the plan.  With S = image.shape[0] scenes:
 
     `target` [2] or [S, 2]; `init_trajs` [K * S, H, D] or None (a draw); `noise`: a DeviceNoise, of which the call is one tick
     (`begin_tick()` first); `step_noise`: injected DDPM noise tensors instead; `candidates` = K and `selector`: best-of-K;
-    `warm` and `motion`: warm start; `controller` and `velocity`: the device controller; `pin`: pinned waypoints; `guide`: cost guidance; `fuse`,
+    `warm` and `motion`: warm start; `controller` and `velocity`: the device controller; `pin`: pinned waypoints; `guide`: cost guidance;
+    `fallback`: the stop-short fallback (its report of this tick is `fallback.last`, a StopResult without `traj`); `fuse`,
     `set_timesteps`, `scale_xy`: as the module docstring says.
 
-    The order at the end of a tick is fixed: clamp, selection (K > 1), the copy into `warm.prev`, the control launch, xy scaling
-    -- so the warm state and the controller see the clamped, unscaled, pinned, guided result.
+    The order at the end of a tick is fixed: clamp, selection (K > 1), the copy into `warm.prev`, the fallback, the control launch,
+    xy scaling -- so the warm state sees the clamped, unscaled, pinned, guided result, and the controller and the caller that
+    result re-timed by the fallback (when there is one).
 
     Returns `traj` [S, H, D] (the winners at K > 1); `(traj, selection)` with `return_selection=True` (a Selection whose
     `candidates` is the [K, S, H, D] tensor scaled like `traj`; None at K = 1, where no selector runs); with a controller
@@ -401,7 +441,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     bit what the call without a controller returns."""
     plan = plan_tick(model, scheduler, cfg, image, target, init_trajs, fuse=fuse, set_timesteps=set_timesteps, noise=noise,
                      step_noise=step_noise, candidates=candidates, selector=selector, warm=warm, motion=motion,
-                     controller=controller, velocity=velocity, pin=pin, guide=guide)
+                     controller=controller, velocity=velocity, pin=pin, guide=guide, fallback=fallback)
     model.eval()
     device, K, S = image.device, plan.K, plan.S
     noise, controller = plan.noise, plan.controller    # from here on the plan is the one source
@@ -451,6 +491,10 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         best = sel.best
     if plan.m_warm > 0:
         warm._store(best)
+    if plan.fallback is not None:
+        # in place: warm.prev already holds its own copy of the sampler's winner
+        res = plan.fallback(best, plan.guide, out=best if best.is_contiguous() else None)
+        best, plan.fallback.last = res.traj, StopResult(None, *res[1:])
     control = None if controller is None else controller.step(best, plan.velocity, scene_tgt, xy_scale=model.magic_num)
     if scale_xy:
         best[..., :2] *= model.magic_num
@@ -598,13 +642,16 @@ class GraphedSampler:
     and weight through the key.  So do a guide's motion limits: the limits through a static buffer, presence and weights through the key.
     And a guide's route: points and half-widths through static buffers, presence, R and weight through the key.
     And a guide's capsules: the slots through a static buffer, presence, C and weight through the key.
+    `fallback=StopShort(...)`: the stop-short launch is a node of the graph after selection and before control
+    (`generate_traj(fallback=...)`).  Its params are copied into a static buffer at every call, so new values never capture again;
+    its presence is part of the graph key.  The call returns the re-timed plan and `last_fallback` the report of the last replay.
     """
 
     MAX_GRAPHS = 4
 
     def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None,
                  candidates: int = 1, selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
-                 controller: Optional[DeviceController] = None):
+                 controller: Optional[DeviceController] = None, fallback: Optional[StopShort] = None):
         deterministic = getattr(scheduler, "_is_ddim", False) or getattr(scheduler, "deterministic", False)
         if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not deterministic):
             raise ValueError("GraphedSampler needs a deterministic sampler (DDIM with eta = 0, DPM-Solver++), or a DeviceNoise for "
@@ -616,11 +663,13 @@ class GraphedSampler:
         self.model, self.scheduler, self.cfg, self.scale_xy, self.noise = model, scheduler, cfg, scale_xy, noise
         self.candidates, self.selector, self.warm = int(candidates), selector, warm
         self.controller = controller
+        self.fallback = fallback
         self._graphs = {}                      # key -> the captured graph and its static buffers
         self._key = None
         self._graph = None                     # the graph of the last call
         self._sel = None
         self._ctl = None
+        self._fb = None
 
     def _capture(self, image, target, init_trajs, motion, velocity=None, pin=None, guide=None):
         dev = image.device
@@ -644,10 +693,12 @@ class GraphedSampler:
                                                                                                          guide.route.half_width.clone()),
                                                         None if guide.capsules is None else guide.capsules.like(guide.capsules.slots.clone()))
         ctl = self.controller
+        g.fb = None if self.fallback is None else self.fallback.like(self.fallback.params.clone())
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
                                     candidates=self.candidates, selector=self.selector, return_selection=True,
-                                    warm=warm, motion=g.motion, controller=ctl, velocity=g.vel, pin=g.pin, guide=g.guide)
+                                    warm=warm, motion=g.motion, controller=ctl, velocity=g.vel, pin=g.pin, guide=g.guide,
+                                    fallback=g.fb)
         tick = None if self.noise is None else self.noise.tick()
         # the warm-up pass below is a real tick: it moves the noise stream on and overwrites the warm state.  Both are given
         # back, so that the first replay is the next tick and starts from the result of the tick before it
@@ -673,6 +724,7 @@ class GraphedSampler:
         # thread captures; in the default global mode that would invalidate the capture
         with torch.cuda.graph(g.graph, capture_error_mode="thread_local"):
             g.out, g.sel, g.ctl = run() if ctl is not None else (*run(), None)
+        g.fbres = None if g.fb is None else g.fb.last      # the static first, status, stop_at and active_after of the stop-short node
         self.model._feat_cache = None          # the memo now points at the static frame buffer: drop it
         g.pointers = self._model_pointers()
         return g
@@ -692,7 +744,7 @@ class GraphedSampler:
         """Forget the captured graphs (call after the model's weights changed: the weight images are packed outside
         the graph, during the warm-up pass of the next capture).  The warm state is the WarmStart's: `warm.reset()`."""
         self._graphs = {}
-        self._key, self._graph, self._sel, self._ctl = None, None, None, None
+        self._key, self._graph, self._sel, self._ctl, self._fb = None, None, None, None, None
 
     @property
     def captured(self) -> int:
@@ -715,6 +767,12 @@ class GraphedSampler:
         call and without a controller."""
         return None if self._ctl is None else self._ctl.clone()
 
+    @property
+    def last_fallback(self) -> Optional[StopResult]:
+        """Clones of the static `first`, `status`, `stop_at` and `active_after` [S] as the last replay left them (`traj` is not
+        kept: the call returned the re-timed plan); None before the first call and without a fallback."""
+        return None if self._fb is None else StopResult(None, *(t.clone() for t in self._fb[1:]))
+
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None,
@@ -722,7 +780,7 @@ class GraphedSampler:
         warm = self.warm
         plan = plan_tick(self.model, self.scheduler, self.cfg, image, target, init_trajs, noise=self.noise,
                          candidates=self.candidates, selector=self.selector, warm=warm, motion=motion,
-                         controller=self.controller, velocity=velocity, pin=pin, guide=guide, graphed=True)
+                         controller=self.controller, velocity=velocity, pin=pin, guide=guide, fallback=self.fallback, graphed=True)
         motion, pin, guide = plan.motion, plan.pin, plan.guide
         if plan.start == "randn":
             init_trajs = torch.randn((plan.rows, plan.H, plan.D), device=image.device)
@@ -763,7 +821,9 @@ class GraphedSampler:
                     g.guide.route.half_width.copy_(guide.route.half_width)
                 if guide.capsules is not None:
                     g.guide.capsules.slots.copy_(guide.capsules.slots)
-        self._key, self._graph, self._sel, self._ctl = key, g.graph, g.sel, g.ctl
+            if g.fb is not None:
+                g.fb.params.copy_(self.fallback.params)
+        self._key, self._graph, self._sel, self._ctl, self._fb = key, g.graph, g.sel, g.ctl, g.fbres
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured
         guard = getattr(self.model, "range_guard", "off") == "raise"

@@ -1371,6 +1371,64 @@ int adx_control_step(const adx_control_cfg* c, const float* traj, const float* v
 /* Fresh windows for the scenes with mask[s] != 0 (mask: [scenes] bytes on the device, NULL = every scene); a capturable launch. */
 int adx_control_reset(void* state, int32_t scenes, int32_t n_turn, int32_t n_speed, const uint8_t* mask, adx_stream s);
 
+/* ------------------------------------------------------------------------------------
+ * Stop-short fallback v1: re-time a plan so that it brakes to a halt before its first conflicting waypoint.  The deterministic
+ * last resort of a sampling planner: the guide pushes samples away from obstacles and a hard selection prefers a free candidate,
+ * but neither promises that the plan a tick ends with is free.  This launch keeps the GEOMETRY of that plan -- every output
+ * waypoint lies on the input's polyline before the conflict -- and changes its SPEED PROFILE; control v1 takes its desired
+ * speed from the spacing of the first waypoints, so a re-timed plan brakes through the controller as it is.  One launch for all
+ * rows, no host decision, no allocation, no synchronisation: a node of a captured graph between selection and control.  No
+ * reference counterpart.  Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ *   traj, out  float32 [rows][H][D] in the model's own units (the clamped result before xy scaling, the units of selection
+ *              and control), 1 <= H <= 64, D >= 2.  out == traj (the same pointer) is allowed: the wave that owns a row reads
+ *              all of it before it writes.
+ *   guide ..   the records of cost guidance v1 / v2 / v4 / v5, as adx_guide_cost_capsule takes them; row r reads scene
+ *              r % scene_rows.  Motion limits (v3) are not places and take no part: there is no such argument.  iters, lambda
+ *              and cap are not read.
+ *   params     float32 [param_rows][2] = (gap, decel) in device memory, read at every launch; row r reads r % param_rows.
+ *              gap: the arc length to keep before the conflict.  decel: the most a step's length may shrink per waypoint.
+ *
+ * All arithmetic is fp32, no contraction; every +, -, *, /, sqrtf and compare below is one correctly rounded operation, in the
+ * order written.  Per row, with p_h = (x_h, y_h) = traj[r][h][0..1]:
+ *
+ *   conflict   waypoint h conflicts when the `active` count of cost guidance's waypoint routine (discs at time h, planes,
+ *              field, route, capsules -- exactly what adx_guide_cost_capsule counts for that waypoint without motion limits) is
+ *              > 0, or when x_h or y_h is not finite (a NaN compares false against every constraint and must not pass as free).
+ *   first      the lowest conflicting h, or H when there is none.
+ *   free row   first == H:  out row = traj row bit for bit (all D columns), status = 0, stop_at = +inf, active_after = 0.
+ *   arc        seg_0 = 0;  seg_h = sqrtf(dx * dx + dy * dy), (dx, dy) = p_h - p_{h-1}, for 1 <= h < first;  seg_h = 0 for
+ *              h >= first: nothing at or beyond the conflict is read as geometry.  s_0 = 0, s_h = s_{h-1} + seg_h, summed in
+ *              index order (so that q_h == s_h bit for bit while the plan's own speed governs).
+ *   stop       g = gap >= 0 ? gap : 0 (a NaN gives 0).  first >= 1: t = s_{first-1} - g, L = t > 0 ? t : 0.  first == 0: L = 0.
+ *              stop_at = L.
+ *   profile    q_0 = 0.  For h = 1 .. H-1 in order:  d = L - q_{h-1};  w = h < first ? seg_h : +inf;  u = d < w ? d : w;
+ *              when decel is finite and >= 0 (a = decel; otherwise the limit is off, as inf is in the motion limits):
+ *              e = (sqrtf(a * a + (8 * a) * d) - a) * 0.5 and u = e < u ? e : u;  then u_h = u, q_h = q_{h-1} + u.
+ *              e(d) is the step length from which a body that sheds `a` per step still stops within d: e(d - u) = u - a when
+ *              u = e(d).  A binding envelope sheds exactly decel per step; only the last approach, which lands on L through
+ *              d, may shed more.  decel = 0: do not move.
+ *   status     2 when H > 1, first > 1, the limit is on and seg_1 - u_1 > a: the first step already has to shed more than the
+ *              limit, the plan cannot stop in time and a consumer may want full brake.  Otherwise 1 (0: a free row).
+ *   resample   j = the largest k in 0 .. first-1 with s_k <= q_h.  first == 0: out_h = p_0.  j == first - 1 or q_h == s_j:
+ *              out_h = p_j, a select and not an addition (the sign of a zero survives).  Otherwise
+ *              t = (q_h - s_j) / (s_{j+1} - s_j) and out_h = p_j + t * (p_{j+1} - p_j) per component.  Columns >= 2 of row
+ *              h are traj's, unchanged.  out_0 == p_0 in bits; while the plan's own speed governs, out_h == p_h in bits.
+ *   residual   active_after = the active count of the out row under the same records: the lane evaluation and butterfly of
+ *              adx_guide_cost.  It is NOT promised to be 0: the launch looks at waypoints only, as the guide does, and a moving
+ *              obstacle can reach a stopped ego.  The caller gets the number instead of a promise.
+ *   outputs    first, status, active_after int32 [rows]; stop_at float32 [rows].
+ *
+ * ADX_ERR_INVALID before any GPU work, each with its own text: a NULL traj, out, params or output; NULL guide and NULL field;
+ * horizon outside 1..64; dim < 2; param_rows < 1; an empty shape or one beyond the 32-bit element index; whatever cost guidance
+ * v1, v2, v4 and v5 refuse of their records; records without a point-wise term (no discs, planes, field, route or capsules); an
+ * output overlapping traj, params, a record's array or another output, except out == traj.
+ * -----------------------------------------------------------------------------------*/
+int adx_stop_short(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_route* route,
+                   const adx_guide_capsules* capsules, const float* params /* [param_rows][2] = (gap, decel) */, int32_t param_rows,
+                   float* out, int32_t* first, int32_t* status, float* stop_at, int32_t* active_after, int32_t rows,
+                   int32_t horizon, int32_t dim, adx_stream s);
+
 /* add_noise (train.py:234) fused with the [...,0,:3] = 0 of train.py:235 when zero_first != 0.
  * sqrt_ab / sqrt_1mab are the host tables sqrt(abar), sqrt(1-abar) of length n_train.  Refused: batch * horizon * dim above
  * 0x3fffffff, more elements than the kernel's 32-bit index holds. */
