@@ -116,6 +116,12 @@ constexpr int kWave = 64;
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// [p, p + pn) and [q, q + qn) share a byte: the one overlap test of every host check
+inline bool byte_ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + qn && b < a + pn;
+}
+
 // Mish(x) = x * tanh(softplus(x)), softplus threshold 20 as in torch (modeling/helpers.py:108).
 // tanh(log(1+e^x)) = n / (n + 2) with n = e^x (e^x + 2): one exp, one divide, no cancellation.
 __device__ __forceinline__ float mish_f(float x) {

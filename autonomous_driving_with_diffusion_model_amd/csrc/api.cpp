@@ -67,19 +67,32 @@ const DebugSwitches& debug_switches() {
 
 int embed_forward(const adx_embed_weights* w, int dim, const int64_t* t, int t_rows, const float* cond,
                   const float* feat, int feat_rows, int rows, float* time_embed, float* mish_cond, hipStream_t s);
-int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
-                hipStream_t s);
-int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
-                      const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
-                      const adx_guide_capsules* capsules, float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best,
-                      hipStream_t s);
 size_t control_state_bytes(int scenes, int n_turn, int n_speed);
 int control_step(const adx_control_cfg* c, const float* traj, const float* velocity, const float* target, void* state,
                  float* control, hipStream_t s);
 int control_reset(void* state, int scenes, int n_turn, int n_speed, const uint8_t* mask, hipStream_t s);
-int stop_short(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_route* route,
-               const adx_guide_capsules* capsules, const float* params, int param_rows, float* out, int32_t* first, int32_t* status,
-               float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);
+
+// The step exports: each names its schedule, its noise source, its pin and its guide records; these two fill the one record of
+// sched.h, and step_run / dpm_run check it and pick the kernel instantiation.  The order every call below keeps: the schedule, the
+// model output and the sample, then the noise (z: a tensor, or ns, slot, row_offset: a state), then tgt and mask (the inpainting
+// blend; step only), the pin, the records, the two outputs and the shape.  Adjacent pointers of one type are (z, ns), (tgt, mask)
+// and (prev, x0); each family of exports below names which of them it leaves null.
+static int step(bool ddpm, const adx_step_coef* c, const float* mo, const float* x, const float* z, const uint32_t* ns, int32_t slot,
+                int64_t row_offset, const float* tgt, const float* mask, const adx_pin* pin, const GuideRecords& g, float* prev, float* x0,
+                int batch, int horizon, int dim, adx_stream s) {
+  StepCall k;
+  k.ddpm = ddpm; k.c = c; k.mo = mo; k.x = x; k.z = z; k.ns = ns; k.slot = slot; k.row_offset = row_offset; k.tgt = tgt; k.mask = mask;
+  k.pin = pin; k.g = g; k.prev = prev; k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return step_run(k);
+}
+static int dpm(const adx_dpm_coef* c, const float* mo, const float* x, const float* px0, const uint32_t* ns, int32_t slot,
+               int64_t row_offset, const adx_pin* pin, const GuideRecords& g, float* prev, float* x0, int batch, int horizon, int dim,
+               adx_stream s) {
+  DpmCall k;
+  k.c = c; k.mo = mo; k.x = x; k.px0 = px0; k.ns = ns; k.slot = slot; k.row_offset = row_offset; k.pin = pin; k.g = g; k.prev = prev;
+  k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
+  return dpm_run(k);
+}
 }  // namespace adx
 
 extern "C" {
@@ -143,107 +156,52 @@ int adx_embed_forward(const adx_embed_weights* w, int32_t dim, const int64_t* t,
   return adx::embed_forward(w, dim, t, t_rows, cond, img_feature, feat_rows, rows, time_embed, mish_cond,
                             (hipStream_t)s);
 }
-// The step exports: each fills the one record of sched.h; step_run / dpm_run check it and pick the kernel instantiation.
+// The plain, _rng and _pin exports: no guide records.  Plain: z alone, tgt and mask, no pin.  _rng: ns alone (refused when null),
+// tgt and mask, no pin.  _pin: z and ns as the caller gives them (step_run refuses both at once), no tgt and mask, the pin.
 int adx_ddim_step(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                   const float* target, const float* mask, float* prev, float* x0, int32_t batch, int32_t horizon,
                   int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.tgt = target; k.mask = mask; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(false, c, model_output, sample, noise, nullptr, 0, 0, target, mask, nullptr, {}, prev, x0, batch, horizon, dim, s);
 }
 int adx_ddpm_step(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                   const float* target, const float* mask, float* prev, float* x0, int32_t batch, int32_t horizon,
                   int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.tgt = target; k.mask = mask; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(true, c, model_output, sample, noise, nullptr, 0, 0, target, mask, nullptr, {}, prev, x0, batch, horizon, dim, s);
 }
 int adx_ddim_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
                       int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
   ADX_REQUIRE(noise_state != nullptr, "scheduler step: null noise state");      // to step_run, no state is the tensor path
-  adx::StepCall k;
-  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
-  k.tgt = target; k.mask = mask; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(false, c, model_output, sample, nullptr, noise_state, slot, row_offset, target, mask, nullptr, {}, prev, x0, batch,
+                   horizon, dim, s);
 }
 int adx_ddpm_step_rng(const adx_step_coef* c, const float* model_output, const float* sample, const uint32_t* noise_state,
                       int32_t slot, int64_t row_offset, const float* target, const float* mask, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
   ADX_REQUIRE(noise_state != nullptr, "scheduler step: null noise state");      // to step_run, no state is the tensor path
-  adx::StepCall k;
-  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
-  k.tgt = target; k.mask = mask; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(true, c, model_output, sample, nullptr, noise_state, slot, row_offset, target, mask, nullptr, {}, prev, x0, batch,
+                   horizon, dim, s);
 }
 int adx_dpm_step(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                  float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::DpmCall k;
-  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.prev = prev_sample; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::dpm_run(k);
+  return adx::dpm(c, model_output, sample, prev_x0, nullptr, 0, 0, nullptr, {}, prev_sample, x0, batch, horizon, dim, s);
 }
 int adx_ddim_step_pin(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(false, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin, {}, prev, x0, batch,
+                   horizon, dim, s);
 }
 int adx_ddpm_step_pin(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev, float* x0,
                       int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(true, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin, {}, prev, x0, batch,
+                   horizon, dim, s);
 }
 int adx_dpm_step_pin(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                      const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, float* prev_sample,
                      float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::DpmCall k;
-  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
-  k.pin = pin; k.prev = prev_sample; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::dpm_run(k);
-}
-int adx_ddim_step_guide(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
-                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                        float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
-}
-int adx_ddpm_step_guide(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
-                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                        float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
-}
-int adx_dpm_step_guide(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
-                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                       float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::DpmCall k;
-  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
-  k.pin = pin; k.guide = guide; k.prev = prev_sample; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::dpm_run(k);
-}
-int adx_guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int32_t rows, int32_t horizon,
-                   int32_t dim, adx_stream s) {
-  return adx::guide_cost(traj, guide, nullptr, nullptr, nullptr, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
+  return adx::dpm(c, model_output, sample, prev_x0, noise_state, slot, row_offset, pin, {}, prev_sample, x0, batch, horizon, dim, s);
 }
 int adx_pin_apply(float* x, const adx_pin* pin, const uint32_t* noise_state, int64_t row_offset, int32_t batch, int32_t horizon,
                   int32_t dim, adx_stream s) {
@@ -253,179 +211,161 @@ int adx_traj_select(const adx_select_cfg* c, const float* trajs, const float* ta
                     float* best, adx_stream s) {
   return adx::traj_select(c, trajs, target, cost, index, best, (hipStream_t)s);
 }
+// "Cost guidance v1" to "v5": one family of exports per version (_guide, _field, _motion, _route, _capsule), each the one before
+// with one more record.  All of them hand their records to the same functions as one GuideRecords; what runs (element-wise or
+// row-wise step kernel, which terms of guide_grad) follows from which records are there, not from the export's name.
+// Every step export of these families passes what _pin passes (z and ns, no tgt and mask, the pin) and then its records.
+int adx_ddim_step_guide(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::step(false, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin, {guide}, prev, x0,
+                   batch, horizon, dim, s);
+}
+int adx_ddpm_step_guide(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
+                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                        float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::step(true, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin, {guide}, prev, x0,
+                   batch, horizon, dim, s);
+}
+int adx_dpm_step_guide(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
+                       const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
+                       float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::dpm(c, model_output, sample, prev_x0, noise_state, slot, row_offset, pin, {guide}, prev_sample, x0, batch, horizon,
+                  dim, s);
+}
+int adx_guide_cost(const float* traj, const adx_guide* guide, float* cost, int32_t* active, int32_t rows, int32_t horizon,
+                   int32_t dim, adx_stream s) {
+  return adx::guide_cost(traj, {guide}, cost, active, rows, horizon, dim, (hipStream_t)s);
+}
 int adx_traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                           float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, nullptr, nullptr, nullptr, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
+  return adx::traj_select_guide(c, trajs, target, {guide}, cost, active, index, blocked, best, (hipStream_t)s);
 }
-// "cost guidance v2": the _guide exports with a field; the same records through the same run functions
 int adx_ddim_step_field(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
                         const adx_guide_field* field, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
                         adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(false, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin, {guide, field},
+                   prev, x0, batch, horizon, dim, s);
 }
 int adx_ddpm_step_field(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
                         const adx_guide_field* field, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
                         adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(true, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin, {guide, field},
+                   prev, x0, batch, horizon, dim, s);
 }
 int adx_dpm_step_field(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
                        const adx_guide_field* field, float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim,
                        adx_stream s) {
-  adx::DpmCall k;
-  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
-  k.pin = pin; k.guide = guide; k.field = field; k.prev = prev_sample; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::dpm_run(k);
+  return adx::dpm(c, model_output, sample, prev_x0, noise_state, slot, row_offset, pin, {guide, field}, prev_sample, x0, batch,
+                  horizon, dim, s);
 }
 int adx_guide_cost_field(const float* traj, const adx_guide* guide, const adx_guide_field* field, float* cost, int32_t* active,
                          int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::guide_cost(traj, guide, field, nullptr, nullptr, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
+  return adx::guide_cost(traj, {guide, field}, cost, active, rows, horizon, dim, (hipStream_t)s);
 }
 int adx_traj_select_guide_field(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                                 const adx_guide_field* field, float* cost, int32_t* active, int32_t* index, int32_t* blocked,
                                 float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, field, nullptr, nullptr, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
+  return adx::traj_select_guide(c, trajs, target, {guide, field}, cost, active, index, blocked, best, (hipStream_t)s);
 }
-// "cost guidance v3": the _field exports with motion limits; the same records through the same run functions, which launch the
-// row-wise kernels when the record holds limits
 int adx_ddim_step_motion(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
-                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                         const adx_guide_field* field, const adx_guide_motion* motion, float* prev, float* x0, int32_t batch,
-                         int32_t horizon, int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin,
+                         const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion, float* prev,
+                         float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::step(false, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin,
+                   {guide, field, motion}, prev, x0, batch, horizon, dim, s);
 }
 int adx_ddpm_step_motion(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
-                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                         const adx_guide_field* field, const adx_guide_motion* motion, float* prev, float* x0, int32_t batch,
-                         int32_t horizon, int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.prev = prev; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin,
+                         const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion, float* prev,
+                         float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::step(true, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin,
+                   {guide, field, motion}, prev, x0, batch, horizon, dim, s);
 }
 int adx_dpm_step_motion(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                        const adx_guide_field* field, const adx_guide_motion* motion, float* prev_sample, float* x0, int32_t batch,
-                        int32_t horizon, int32_t dim, adx_stream s) {
-  adx::DpmCall k;
-  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
-  k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.prev = prev_sample; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::dpm_run(k);
+                        const adx_guide_field* field, const adx_guide_motion* motion, float* prev_sample, float* x0,
+                        int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::dpm(c, model_output, sample, prev_x0, noise_state, slot, row_offset, pin, {guide, field, motion}, prev_sample, x0,
+                  batch, horizon, dim, s);
 }
 int adx_guide_cost_motion(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
                           float* cost, int32_t* active, int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::guide_cost(traj, guide, field, motion, nullptr, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
+  return adx::guide_cost(traj, {guide, field, motion}, cost, active, rows, horizon, dim, (hipStream_t)s);
 }
 int adx_traj_select_guide_motion(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                                  const adx_guide_field* field, const adx_guide_motion* motion, float* cost, int32_t* active,
                                  int32_t* index, int32_t* blocked, float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, field, motion, nullptr, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
+  return adx::traj_select_guide(c, trajs, target, {guide, field, motion}, cost, active, index, blocked, best, (hipStream_t)s);
 }
-// "cost guidance v4": the _motion exports with a route corridor; the same records through the same run functions.  The route is a
-// term of guide_grad, so it rides in whichever kernel the record picks: element-wise without limits, row-wise with them
 int adx_ddim_step_route(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
                         const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route, float* prev,
                         float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route; k.prev = prev;
-  k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(false, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin,
+                   {guide, field, motion, route}, prev, x0, batch, horizon, dim, s);
 }
 int adx_ddpm_step_route(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
                         const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route, float* prev,
                         float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route; k.prev = prev;
-  k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+  return adx::step(true, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin,
+                   {guide, field, motion, route}, prev, x0, batch, horizon, dim, s);
 }
 int adx_dpm_step_route(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
                        const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                       const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route, float* prev_sample,
-                       float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
-  adx::DpmCall k;
-  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
-  k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route; k.prev = prev_sample; k.x0 = x0;
-  k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::dpm_run(k);
+                       const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
+                       float* prev_sample, float* x0, int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::dpm(c, model_output, sample, prev_x0, noise_state, slot, row_offset, pin, {guide, field, motion, route},
+                  prev_sample, x0, batch, horizon, dim, s);
 }
 int adx_guide_cost_route(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
                          const adx_guide_route* route, float* cost, int32_t* active, int32_t rows, int32_t horizon, int32_t dim,
                          adx_stream s) {
-  return adx::guide_cost(traj, guide, field, motion, route, nullptr, cost, active, rows, horizon, dim, (hipStream_t)s);
+  return adx::guide_cost(traj, {guide, field, motion, route}, cost, active, rows, horizon, dim, (hipStream_t)s);
 }
 int adx_traj_select_guide_route(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                                 const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
                                 float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, field, motion, route, nullptr, cost, active, index, blocked, best, (hipStream_t)s);
+  return adx::traj_select_guide(c, trajs, target, {guide, field, motion, route}, cost, active, index, blocked, best, (hipStream_t)s);
 }
-// "cost guidance v5": the _route exports with moving capsules; the same records through the same run functions.  The capsules are a
-// term of guide_grad, like the route, so they ride in whichever kernel the record picks
 int adx_ddim_step_capsule(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
-                          const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                          const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
-                          const adx_guide_capsules* capsules, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
-                          adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = false; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route;
-  k.capsules = capsules; k.prev = prev; k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+                          const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin,
+                          const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+                          const adx_guide_route* route, const adx_guide_capsules* capsules, float* prev, float* x0, int32_t batch,
+                          int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::step(false, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin,
+                   {guide, field, motion, route, capsules}, prev, x0, batch, horizon, dim, s);
 }
 int adx_ddpm_step_capsule(const adx_step_coef* c, const float* model_output, const float* sample, const float* noise,
-                          const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                          const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
-                          const adx_guide_capsules* capsules, float* prev, float* x0, int32_t batch, int32_t horizon, int32_t dim,
-                          adx_stream s) {
-  adx::StepCall k;
-  k.ddpm = true; k.c = c; k.mo = model_output; k.x = sample; k.z = noise; k.ns = noise_state; k.slot = slot;
-  k.row_offset = row_offset; k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route;
-  k.capsules = capsules; k.prev = prev; k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::step_run(k);
+                          const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin,
+                          const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+                          const adx_guide_route* route, const adx_guide_capsules* capsules, float* prev, float* x0, int32_t batch,
+                          int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::step(true, c, model_output, sample, noise, noise_state, slot, row_offset, nullptr, nullptr, pin,
+                   {guide, field, motion, route, capsules}, prev, x0, batch, horizon, dim, s);
 }
 int adx_dpm_step_capsule(const adx_dpm_coef* c, const float* model_output, const float* sample, const float* prev_x0,
-                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin, const adx_guide* guide,
-                         const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
-                         const adx_guide_capsules* capsules, float* prev_sample, float* x0, int32_t batch, int32_t horizon,
-                         int32_t dim, adx_stream s) {
-  adx::DpmCall k;
-  k.c = c; k.mo = model_output; k.x = sample; k.px0 = prev_x0; k.ns = noise_state; k.slot = slot; k.row_offset = row_offset;
-  k.pin = pin; k.guide = guide; k.field = field; k.motion = motion; k.route = route; k.capsules = capsules; k.prev = prev_sample;
-  k.x0 = x0; k.batch = batch; k.horizon = horizon; k.dim = dim; k.stream = (hipStream_t)s;
-  return adx::dpm_run(k);
+                         const uint32_t* noise_state, int32_t slot, int64_t row_offset, const adx_pin* pin,
+                         const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
+                         const adx_guide_route* route, const adx_guide_capsules* capsules, float* prev_sample, float* x0,
+                         int32_t batch, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::dpm(c, model_output, sample, prev_x0, noise_state, slot, row_offset, pin, {guide, field, motion, route, capsules},
+                  prev_sample, x0, batch, horizon, dim, s);
 }
-int adx_guide_cost_capsule(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
-                           const adx_guide_route* route, const adx_guide_capsules* capsules, float* cost, int32_t* active,
-                           int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::guide_cost(traj, guide, field, motion, route, capsules, cost, active, rows, horizon, dim, (hipStream_t)s);
+int adx_guide_cost_capsule(const float* traj, const adx_guide* guide, const adx_guide_field* field,
+                           const adx_guide_motion* motion, const adx_guide_route* route, const adx_guide_capsules* capsules,
+                           float* cost, int32_t* active, int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
+  return adx::guide_cost(traj, {guide, field, motion, route, capsules}, cost, active, rows, horizon, dim, (hipStream_t)s);
 }
 int adx_traj_select_guide_capsule(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
                                   const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
-                                  const adx_guide_capsules* capsules, float* cost, int32_t* active, int32_t* index, int32_t* blocked,
-                                  float* best, adx_stream s) {
-  return adx::traj_select_guide(c, trajs, target, guide, field, motion, route, capsules, cost, active, index, blocked, best,
-                                (hipStream_t)s);
+                                  const adx_guide_capsules* capsules, float* cost, int32_t* active, int32_t* index,
+                                  int32_t* blocked, float* best, adx_stream s) {
+  return adx::traj_select_guide(c, trajs, target, {guide, field, motion, route, capsules}, cost, active, index, blocked, best, (hipStream_t)s);
 }
 int adx_capsules_from_boxes(const float* boxes, float* out, int32_t scenes, int32_t n_boxes, float inflate, adx_stream s) {
   return adx::capsules_from_boxes(boxes, out, scenes, n_boxes, inflate, (hipStream_t)s);
@@ -447,8 +387,8 @@ int adx_control_reset(void* state, int32_t scenes, int32_t n_turn, int32_t n_spe
 int adx_stop_short(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_route* route,
                    const adx_guide_capsules* capsules, const float* params, int32_t param_rows, float* out, int32_t* first,
                    int32_t* status, float* stop_at, int32_t* active_after, int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {
-  return adx::stop_short(traj, guide, field, route, capsules, params, param_rows, out, first, status, stop_at, active_after, rows,
-                         horizon, dim, (hipStream_t)s);
+  return adx::stop_short(traj, {guide, field, nullptr, route, capsules}, params, param_rows, out, first, status, stop_at, active_after,
+                         rows, horizon, dim, (hipStream_t)s);
 }
 int adx_noise_normal(const uint32_t* state, int32_t slot, int64_t first_elem, float* out, int64_t n, adx_stream s) {
   return adx::noise_normal(state, slot, first_elem, out, n, (hipStream_t)s);

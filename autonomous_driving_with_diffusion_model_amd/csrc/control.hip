@@ -157,11 +157,6 @@ __global__ void __launch_bounds__(256) control_reset_kernel(uint32_t* state, con
   if (mask == nullptr || mask[i / stride] != 0) state[i] = 0u;
 }
 
-bool overlaps(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qn && b < a + pn;
-}
-
 bool windows_ok(int scenes, int n_turn, int n_speed) {
   return scenes >= 1 && scenes <= 65535 && n_turn >= 1 && n_turn <= ADX_CONTROL_MAX_WINDOW && n_speed >= 1 &&
          n_speed <= ADX_CONTROL_MAX_WINDOW;
@@ -193,11 +188,11 @@ int control_step(const adx_control_cfg* c, const float* traj, const float* veloc
   const size_t traj_bytes = (size_t)c->scenes * c->horizon * c->dim * sizeof(float), vel_bytes = (size_t)c->scenes * sizeof(float);
   const size_t tgt_bytes = target != nullptr ? (size_t)c->scenes * 2 * sizeof(float) : 0, ctl_bytes = (size_t)c->scenes * 3 * sizeof(float);
   const size_t state_bytes = control_state_bytes(c->scenes, c->n_turn, c->n_speed);
-  ADX_REQUIRE(!overlaps(control, ctl_bytes, traj, traj_bytes) && !overlaps(control, ctl_bytes, velocity, vel_bytes) &&
-                  !(target != nullptr && overlaps(control, ctl_bytes, target, tgt_bytes)) && !overlaps(control, ctl_bytes, state, state_bytes),
+  ADX_REQUIRE(!byte_ranges_overlap(control, ctl_bytes, traj, traj_bytes) && !byte_ranges_overlap(control, ctl_bytes, velocity, vel_bytes) &&
+                  !(target != nullptr && byte_ranges_overlap(control, ctl_bytes, target, tgt_bytes)) && !byte_ranges_overlap(control, ctl_bytes, state, state_bytes),
               "control step: control overlaps an input or the state");
-  ADX_REQUIRE(!overlaps(state, state_bytes, traj, traj_bytes) && !overlaps(state, state_bytes, velocity, vel_bytes) &&
-                  !(target != nullptr && overlaps(state, state_bytes, target, tgt_bytes)),
+  ADX_REQUIRE(!byte_ranges_overlap(state, state_bytes, traj, traj_bytes) && !byte_ranges_overlap(state, state_bytes, velocity, vel_bytes) &&
+                  !(target != nullptr && byte_ranges_overlap(state, state_bytes, target, tgt_bytes)),
               "control step: the state overlaps an input");
   ControlArgs a;
   a.traj = traj; a.velocity = velocity; a.target = target; a.state = static_cast<uint32_t*>(state); a.control = control;
@@ -212,7 +207,7 @@ int control_reset(void* state, int scenes, int n_turn, int n_speed, const uint8_
               n_turn, n_speed, ADX_CONTROL_MAX_WINDOW);
   ADX_REQUIRE(state != nullptr, "control reset: null state");
   const int stride = 2 + n_turn + n_speed;
-  ADX_REQUIRE(mask == nullptr || !overlaps(state, (size_t)scenes * stride * sizeof(uint32_t), mask, (size_t)scenes),
+  ADX_REQUIRE(mask == nullptr || !byte_ranges_overlap(state, (size_t)scenes * stride * sizeof(uint32_t), mask, (size_t)scenes),
               "control reset: the mask overlaps the state");
   control_reset_kernel<<<dim3(ceil_div(scenes * stride, 256)), dim3(256), 0, s>>>(static_cast<uint32_t*>(state), mask, scenes, stride);
   ADX_LAUNCH_CHECK();

@@ -4,7 +4,8 @@
 // One wave per row, four rows per workgroup, lane = waypoint; the waves of a workgroup share nothing (no LDS, no atomics, no
 // barrier), so a row's result cannot depend on which rows share its launch.  Shaped like guide_cost_kernel (sched.hip) and
 // control_step_kernel (control.hip):
-//   1. lane h holds p_h and asks guide_grad (guide.h, as it is) whether it conflicts; `first` is one ballot and a find-first-set;
+//   1. lane h holds p_h and asks guide_grad (guide.h, as it is, under the scene view of its row) whether it conflicts; `first` is
+//      one ballot and a find-first-set;
 //   2. a free row is copied (a wave-uniform branch) and the wave leaves;
 //   3. lane h takes seg_h from its neighbour's waypoint (one shuffle up); the arc lengths s_h are summed in index order: H - 1
 //      trips, each a broadcast of lane h's seg, every lane advancing the same scalar and lane h keeping its s_h;
@@ -38,17 +39,11 @@ struct StopArgs {
   int rows, horizon, dim, param_rows;
 };
 
-__device__ __forceinline__ bool finite_d(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for inf and NaN
-
-// The active count of waypoint (x, y) at index `h` of row `r`: the arguments guide_cost_kernel<false> passes
+// The active count of waypoint (x, y) at index `h` of row `r`: what guide_cost_kernel<false> counts
 __device__ __forceinline__ int waypoint_active(const GuideArgs& g, int r, int h, float x, float y) {
-  const int scene = r % g.scene_rows;
   float J, gx, gy;
   int active;
-  const float* pts = route_points(g.route, r);
-  guide_grad(g.discs + (size_t)scene * g.M * 5, g.M, g.planes + (size_t)scene * g.P * 3, g.P, field_cells(g.field, r), g.field, pts,
-             g.route.R, route_w2(g.route, pts, r), g.route.weight, capsule_slots(g.capsule, r), g.capsule.C, g.capsule.weight, (float)h,
-             x, y, J, gx, gy, active);
+  guide_grad(scene_guide<true>(g, r), (float)h, x, y, J, gx, gy, active);
   return active;
 }
 
@@ -67,7 +62,7 @@ __global__ void __launch_bounds__(kStopWaves* kWave) stop_short_kernel(const Sto
   bool conflict = false;
   if (live) {
     x = src[0]; y = src[1];
-    conflict = waypoint_active(a.g, r, lane, x, y) > 0 || !finite_d(x) || !finite_d(y);
+    conflict = waypoint_active(a.g, r, lane, x, y) > 0 || !finite_f(x) || !finite_f(y);
   }
   const unsigned long long hits = __ballot(conflict);
   const int first = hits != 0ull ? __ffsll(hits) - 1 : H;
@@ -108,7 +103,7 @@ __global__ void __launch_bounds__(kStopWaves* kWave) stop_short_kernel(const Sto
     const float t = __shfl(s_h, first - 1, kWave) - g;
     L = t > 0.f ? t : 0.f;
   }
-  const bool limited = finite_d(decel) && decel >= 0.f;
+  const bool limited = finite_f(decel) && decel >= 0.f;
   const float aa = decel * decel, a8 = 8.0f * decel;
   float q = 0.f, q_h = 0.f, u1 = 0.f;
   for (int i = 1; i < H; ++i) {
@@ -164,50 +159,32 @@ __global__ void __launch_bounds__(kStopWaves* kWave) stop_short_kernel(const Sto
   }
 }
 
-bool overlaps(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qn && b < a + pn;
-}
-
 }  // namespace
 
-int stop_short(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_route* route,
-               const adx_guide_capsules* capsules, const float* params, int param_rows, float* out, int32_t* first, int32_t* status,
-               float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s) {
+int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
+               int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s) {
   const char* const what = "stop short";
   ADX_REQUIRE(traj != nullptr && out != nullptr && params != nullptr && first != nullptr && status != nullptr && stop_at != nullptr &&
                   active_after != nullptr, "stop short: null traj, out, params, first, status, stop_at or active_after");
-  ADX_REQUIRE(guide != nullptr || field != nullptr, "stop short: null guide and null field");
+  ADX_REQUIRE(g.guide != nullptr || g.field != nullptr, "stop short: null guide and null field");
   ADX_REQUIRE(horizon >= 1 && horizon <= kWave, "stop short: horizon %d outside 1..%d", horizon, kWave);
   ADX_REQUIRE(dim >= 2, "stop short: the fallback re-times (x, y), dim is %d", dim);
   ADX_REQUIRE(param_rows >= 1, "stop short: param_rows %d, at least 1", param_rows);
-  ADX_REQUIRE(rows >= 1, "stop short: empty shape");
-  ADX_REQUIRE((int64_t)horizon * dim <= 0x3fffffff && (int64_t)rows * horizon * dim <= 0x3fffffff,
-              "stop short: %lld elements do not fit the kernel's 32-bit index", (long long)((uint64_t)rows * (uint64_t)horizon * (uint64_t)dim));
+  int rc = shape_check(what, rows, horizon, dim);      // horizon and dim are in range by now: what is left is `rows`
+  if (rc != ADX_OK) return rc;
   StopArgs a;
   const size_t tn = (size_t)rows * horizon * dim * sizeof(float), cn = (size_t)rows * sizeof(float);
   const size_t pn = (size_t)param_rows * 2 * sizeof(float);
-  // the records' own refusals (sched.h) take two outputs at a time: the five go through in three rounds
-  const void* const outs[6] = {out, first, status, stop_at, active_after, nullptr};
-  const size_t out_bytes[6] = {tn, cn, cn, cn, cn, 0};
-  for (int i = 0; i < 6; i += 2) {
-    int rc = guide_check(guide, field, what, false, false, outs[i], out_bytes[i], outs[i + 1], out_bytes[i + 1], rows, dim, &a.g);
-    if (rc != ADX_OK) return rc;
-    if (route != nullptr) {
-      rc = route_check(route, guide, field, nullptr, what, outs[i], out_bytes[i], outs[i + 1], out_bytes[i + 1], rows, &a.g.route);
-      if (rc != ADX_OK) return rc;
-    }
-    if (capsules != nullptr) {
-      rc = capsule_check(capsules, guide, field, nullptr, route, what, outs[i], out_bytes[i], outs[i + 1], out_bytes[i + 1], rows,
-                         &a.g.capsule);
-      if (rc != ADX_OK) return rc;
-    }
-  }
+  const ByteSpan outs[5] = {{out, tn}, {first, cn}, {status, cn}, {stop_at, cn}, {active_after, cn}};
+  // no MotionArgs: the limits couple waypoints, the fallback asks about one waypoint at a time, so g.motion is neither checked nor read
+  rc = guide_records_check(g, what, false, false, outs, 5, rows, horizon, dim, &a.g, nullptr);
+  if (rc != ADX_OK) return rc;
   ADX_REQUIRE(a.g.M > 0 || a.g.P > 0 || a.g.field.cells != nullptr || a.g.route.points != nullptr || a.g.capsule.slots != nullptr,
               "stop short: the guide holds no point-wise term (discs, planes, a field, a route or capsules)");
   for (int i = 0; i < 5; ++i) {
-    bool bad = overlaps(outs[i], out_bytes[i], params, pn) || (!(i == 0 && out == traj) && overlaps(outs[i], out_bytes[i], traj, tn));
-    for (int k = i + 1; k < 5; ++k) bad = bad || overlaps(outs[i], out_bytes[i], outs[k], out_bytes[k]);
+    bool bad = byte_ranges_overlap(outs[i].p, outs[i].n, params, pn) ||
+               (!(i == 0 && out == traj) && byte_ranges_overlap(outs[i].p, outs[i].n, traj, tn));
+    for (int k = i + 1; k < 5; ++k) bad = bad || byte_ranges_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n);
     ADX_REQUIRE(!bad, "stop short: an output overlaps traj, params or another output (out == traj, the same pointer, is allowed)");
   }
   a.traj = traj; a.params = params; a.out = out; a.first = first; a.status = status; a.stop_at = stop_at;

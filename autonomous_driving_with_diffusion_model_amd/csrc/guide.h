@@ -1,6 +1,8 @@
-// "Cost guidance v1" and "cost guidance v2" (include/adx.h) on the device: the argument record of a guided launch and the ONE routine
-// that evaluates a waypoint's cost.  The step kernels and guide_cost_kernel (sched.hip) and the guided select kernel (select.hip) all
-// call it, so what a step steers by, what adx_guide_cost reports and what a selection scores are the same bits.
+// "Cost guidance v1" and "cost guidance v2" (include/adx.h) on the device: the argument record of a guided launch (GuideArgs), the
+// view of one scene of it that a row resolves once (SceneGuide, scene_guide) and the ONE routine that evaluates a waypoint's cost
+// under that view (guide_grad).  The step kernels and guide_cost_kernel (sched.hip), the guided select kernel (select.hip) and the
+// stop-short kernel (fallback.hip) all call it, so what a step steers by, what adx_guide_cost reports, what a selection scores and
+// what the fallback stops for are the same bits.
 // "Cost guidance v4" adds the route corridor to that routine, after the field term: a per-scene polyline and a half-width.
 // "Cost guidance v5" adds moving capsules to that routine, after the route term: per scene up to 32 segments with a radius.
 // "Cost guidance v3" adds motion_grad beside it: a waypoint's share of the terms that couple it to its neighbours, for the row-wise
@@ -46,47 +48,72 @@ struct GuideArgs {
   CapsuleArgs capsule;  // cost guidance v5
 };
 
-// The raster of row `row`'s scene, or nullptr without a field (uniform across a launch)
-__device__ __forceinline__ const float* field_cells(const FieldArgs& f, int row) {
-  return f.cells == nullptr ? nullptr : f.cells + (size_t)(row % f.scene_rows) * f.Gy * f.Gx;
-}
+// One scene of a guided launch: what guide_grad reads, resolved ONCE per row by scene_guide.  A pointer is null where its term is
+// not evaluated, which is the same in every thread of a launch.  A value that lives in registers: after inlining nothing of it
+// is left but the operands guide_grad uses.
+struct SceneGuide {
+  const float* discs;      // [M][5]
+  const float* planes;     // [P][3]
+  const float* cells;      // the scene's raster; null without a field
+  const float* pts;        // the scene's polyline [R][2]; null without a route or at weight 0
+  const float* caps;       // the scene's slots [C][7]; null without capsules or at weight 0
+  int M, P, R, C;
+  float W2, rw, cw;        // the route's squared half-width (one rounded product) and weight; the capsules' weight
+  FieldArgs field;         // the field's geometry and weight
+};
 
-// The polyline of row `row`'s scene, or nullptr without a route or at weight 0, where the term is not evaluated (uniform across a
-// launch).  Read from global memory as it lies: a scene's points are at most 256 bytes that every lane of the scene reads at the
-// same address.
+// The polyline of row `row`'s scene, or nullptr without a route or at weight 0, where the term is not evaluated
 __device__ __forceinline__ const float* route_points(const RouteArgs& r, int row) {
   return r.points == nullptr || r.weight == 0.f ? nullptr : r.points + (size_t)(row % r.scene_rows) * r.R * 2;
 }
 
-// The capsules of row `row`'s scene, or nullptr without capsules or at weight 0, where the term is not evaluated (uniform across a
-// launch).  Read from global memory as they lie: a scene's capsules are at most 896 bytes that every lane of the scene reads at the
-// same addresses.
-__device__ __forceinline__ const float* capsule_slots(const CapsuleArgs& c, int row) {
-  return c.slots == nullptr || c.weight == 0.f ? nullptr : c.slots + (size_t)(row % c.scene_rows) * c.C * 7;
-}
-
-// W2 of row `row`'s scene: the square of its half-width, one rounded product; `pts` is route_points(r, row)
-__device__ __forceinline__ float route_w2(const RouteArgs& r, const float* pts, int row) {
+// The view of row `row`'s scene.  The route's and the capsules' arrays are read from global memory as they lie: a scene's points
+// are at most 256 bytes and its capsules at most 896 that every lane of the scene reads at the same addresses.
+// What the view holds does not depend on the order its pointers are formed in; what a kernel's prologue costs does, by a per cent
+// or two (profiles/README.md, "One guide bundle").  So the two things a call site may want to place are explicit, and there are no
+// others: `scene`, which is row % g.scene_rows, is a parameter so that guide_x0 can form it ahead of its partner element's loads,
+// where the division costs nothing; kRouteFirst forms the route's pointer ahead of the discs' and planes', which is the order the
+// wave-per-row kernels (guide_cost_kernel, stop_short_kernel) were measured with.  Everyone else calls the plain two-argument form.
+template <bool kRouteFirst = false>
+__device__ __forceinline__ SceneGuide scene_guide(const GuideArgs& g, int row, int scene) {
 #pragma clang fp contract(off)
-  if (pts == nullptr) return 0.f;
-  const float w = r.half_width[row % r.scene_rows];
-  return w * w;
+  SceneGuide v;
+  const RouteArgs& r = g.route;
+  if constexpr (kRouteFirst) v.pts = route_points(r, row);
+  v.discs = g.discs + (size_t)scene * g.M * 5;
+  v.planes = g.planes + (size_t)scene * g.P * 3;
+  const FieldArgs& f = g.field;
+  v.cells = f.cells == nullptr ? nullptr : f.cells + (size_t)(row % f.scene_rows) * f.Gy * f.Gx;
+  if constexpr (!kRouteFirst) v.pts = route_points(r, row);
+  v.W2 = 0.f;
+  if (v.pts != nullptr) {
+    const float w = r.half_width[row % r.scene_rows];
+    v.W2 = w * w;
+  }
+  const CapsuleArgs& c = g.capsule;
+  v.caps = c.slots == nullptr || c.weight == 0.f ? nullptr : c.slots + (size_t)(row % c.scene_rows) * c.C * 7;
+  v.M = g.M; v.P = g.P; v.R = r.R; v.C = c.C;
+  v.rw = r.weight; v.cw = c.weight;
+  v.field = f;
+  return v;
 }
 
-// Cost guidance v1 / v2 / v4 / v5: the cost J of one waypoint (x, y) at index h (hf = (float)h) under one scene's M discs, P planes and, when
-// `cells` (the scene's raster, field_cells) is not null, the field `f`; its gradient and the number of active terms; the contracts'
-// operations in the contracts' order, each rounded on its own.  Without a field the accumulation is v1's, bit for bit.  When `pts`
-// (the scene's polyline, route_points) is not null, the route term of v4 follows: the nearest of the R - 1 segments against W2
-// (route_w2) at weight rw.  Without a route the accumulation is v2's, bit for bit.  When `caps` (the scene's capsules,
-// capsule_slots) is not null, the capsule term of v5 follows: the Cn slots at weight cw, each v1's disc potential around the nearest
-// point of its moved segment.  Without capsules the accumulation is v4's, bit for bit.
-__device__ __forceinline__ void guide_grad(const float* discs, int M, const float* planes, int P, const float* cells, const FieldArgs& f,
-                                           const float* pts, int R, float W2, float rw, const float* caps, int Cn, float cw, float hf,
-                                           float x, float y, float& J, float& gx, float& gy, int& active) {
+template <bool kRouteFirst = false>
+__device__ __forceinline__ SceneGuide scene_guide(const GuideArgs& g, int row) {
+  return scene_guide<kRouteFirst>(g, row, row % g.scene_rows);
+}
+
+// Cost guidance v1 / v2 / v4 / v5: the cost J of one waypoint (x, y) at index h (hf = (float)h) under its scene `s`: the M discs and
+// P planes, then the field where s.cells is not null, then the route (the nearest of the R - 1 segments against W2 at weight rw)
+// where s.pts is not null, then the C capsule slots at weight cw (each v1's disc potential around the nearest point of its moved
+// segment) where s.caps is not null; its gradient and the number of active terms.  The contracts' operations in the contracts'
+// order, each rounded on its own; an absent term adds nothing, so without it the accumulation is the earlier version's, bit for
+// bit.  A new term adds a field to SceneGuide and a block here, and touches no call site.
+__device__ __forceinline__ void guide_grad(const SceneGuide& s, float hf, float x, float y, float& J, float& gx, float& gy, int& active) {
 #pragma clang fp contract(off)
   J = 0.f; gx = 0.f; gy = 0.f; active = 0;
-  for (int i = 0; i < M; ++i) {
-    const float* q = discs + i * 5;
+  for (int i = 0; i < s.M; ++i) {
+    const float* q = s.discs + i * 5;
     const float r = q[4];
     if (!(r > 0.f)) continue;                  // an empty slot (a NaN radius too)
     const float hx = hf * q[2], hy = hf * q[3];
@@ -109,8 +136,8 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
       ++active;
     }
   }
-  for (int i = 0; i < P; ++i) {
-    const float* q = planes + i * 3;
+  for (int i = 0; i < s.P; ++i) {
+    const float* q = s.planes + i * 3;
     const float nx = q[0], ny = q[1];
     const float ax = nx * x, ay = ny * y;
     const float psi = (ax + ay) - q[2];
@@ -123,7 +150,8 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
       ++active;
     }
   }
-  if (cells != nullptr) {      // the field term: the bilinear interpolant of the cell the waypoint lies in, and its exact gradient
+  if (s.cells != nullptr) {      // the field term: the bilinear interpolant of the cell the waypoint lies in, and its exact gradient
+    const FieldArgs& f = s.field;
     const float ux = x - f.x_min, vy = y - f.y_min;
     const float u = ux * f.inv_dx, v = vy * f.inv_dy;
     const int Gx = f.Gx, Gy = f.Gy;
@@ -131,7 +159,7 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
       const int ju = (int)u, iv = (int)v;
       const int j = ju < Gx - 2 ? ju : Gx - 2, i = iv < Gy - 2 ? iv : Gy - 2;       // 0 <= j <= Gx - 2, 0 <= i <= Gy - 2
       const float fu = u - (float)j, fv = v - (float)i;
-      const float* c = cells + (size_t)i * Gx + j;
+      const float* c = s.cells + (size_t)i * Gx + j;
       const float c00 = c[0], c01 = c[1], c10 = c[Gx], c11 = c[Gx + 1];
       const float a = c01 - c00, b = c11 - c10;
       const float ta = fu * a, tb = fu * b;
@@ -153,10 +181,11 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
       }
     }
   }
-  if (pts != nullptr) {      // the route term: the squared distance to the nearest segment over W2; no square root
+  if (s.pts != nullptr) {      // the route term: the squared distance to the nearest segment over W2; no square root
+    const float* pts = s.pts;
     float best = __builtin_inff(), qx = 0.f, qy = 0.f;
     float ax = pts[0], ay = pts[1];
-    for (int i = 1; i < R; ++i) {
+    for (int i = 1; i < s.R; ++i) {
       const float bx = pts[2 * i], by = pts[2 * i + 1];
       const float ex = bx - ax, ey = by - ay;
       const float ux = x - ax, uy = y - ay;
@@ -173,22 +202,22 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
       if (d2 < best) { best = d2; qx = rx; qy = ry; }      // strict: the first of equals wins; a NaN never wins
       ax = bx; ay = by;
     }
-    const float phi = best - W2;
+    const float phi = best - s.W2;
     if (best < __builtin_inff() && phi > 0.f) {
       const float pp = phi * phi;
-      const float wp = rw * pp;
+      const float wp = s.rw * pp;
       J = J + wp / 2.0f;
       const float p2 = 2.0f * phi;
-      const float k = rw * p2;
+      const float k = s.rw * p2;
       const float kx = k * qx, ky = k * qy;
       gx = gx + kx;
       gy = gy + ky;
       ++active;
     }
   }
-  if (caps != nullptr) {      // the capsule term: v1's disc potential around the nearest point of each moved segment; no square root
-    for (int i = 0; i < Cn; ++i) {
-      const float* q = caps + i * 7;
+  if (s.caps != nullptr) {      // the capsule term: v1's disc potential around the nearest point of each moved segment; no square root
+    for (int i = 0; i < s.C; ++i) {
+      const float* q = s.caps + i * 7;
       const float r = q[6];
       if (!(r > 0.f)) continue;                  // an empty slot (a NaN radius too)
       const float ax = q[0], ay = q[1];
@@ -212,11 +241,11 @@ __device__ __forceinline__ void guide_grad(const float* discs, int M, const floa
       const float phi = 1.0f - sd;
       if (phi > 0.f) {
         const float pp = phi * phi;
-        const float wp = cw * pp;
+        const float wp = s.cw * pp;
         J = J + wp / 2.0f;
         const float p2 = 2.0f * phi;
         const float pk = p2 * inv;
-        const float k = cw * pk;
+        const float k = s.cw * pk;
         const float kx = k * rx, ky = k * ry;
         gx = gx - kx;
         gy = gy - ky;

@@ -6,7 +6,37 @@
 
 namespace adx {
 
-// One DDIM / DDPM step.  The kernel is step_kernel<ddpm, ns != null, pin != null, guide != null || field != null>; z and ns may not
+// The guide records of one launch (include/adx.h, "cost guidance v1" to "v5"), each null where the launch has none.  Exports fill
+// it, StepCall and DpmCall carry it, guide_cost, traj_select_guide and stop_short take it, and guide_records_check is the one
+// function that reads what it points at.
+struct GuideRecords {
+  const adx_guide* guide = nullptr;                // v1: discs and planes; iters, lambda and cap of a step
+  const adx_guide_field* field = nullptr;          // v2: a cost raster
+  const adx_guide_motion* motion = nullptr;        // v3: speed and acceleration limits (the row-wise kernels)
+  const adx_guide_route* route = nullptr;          // v4: a route corridor
+  const adx_guide_capsules* capsules = nullptr;    // v5: moving capsules
+};
+
+// An output of a launch, as the overlap refusals see it; p may be null (an optional output)
+struct ByteSpan {
+  const void* p;
+  size_t n;
+};
+
+inline __host__ __device__ bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for inf and NaN
+
+// A [rows][horizon][dim] launch: not empty, and small enough for the kernels' int element index (and the e + total of the
+// classifier-free combine)
+inline int shape_check(const char* what, int rows, int horizon, int dim) {
+  ADX_REQUIRE(rows >= 1 && horizon >= 1 && dim >= 1, "%s: empty shape", what);
+  const int64_t per = (int64_t)horizon * dim;        // < 2^62
+  const int64_t max = 0x3fffffff;
+  ADX_REQUIRE(per <= max && rows * per <= max, "%s: %lld elements do not fit the kernel's 32-bit index", what,
+              (long long)((uint64_t)rows * (uint64_t)per));
+  return ADX_OK;
+}
+
+// One DDIM / DDPM step.  The kernel is step_kernel<ddpm, ns != null, pin != null, a guide, a field, a route or capsules>; z and ns may not
 // both be given.
 struct StepCall {
   bool ddpm = false;                  // which schedule: false DDIM, true DDPM
@@ -20,18 +50,14 @@ struct StepCall {
   const float* tgt = nullptr;         // inpainting schedulers: known trajectory and
   const float* mask = nullptr;        // its mask
   const adx_pin* pin = nullptr;       // pinned waypoints v1
-  const adx_guide* guide = nullptr;   // cost guidance v1
-  const adx_guide_field* field = nullptr;      // cost guidance v2: the GUIDE kernel with a raster
-  const adx_guide_motion* motion = nullptr;    // cost guidance v3: step_rows_kernel<ddpm, ns != null, pin != null> instead
-  const adx_guide_route* route = nullptr;      // cost guidance v4: a route corridor in whichever kernel runs
-  const adx_guide_capsules* capsules = nullptr;      // cost guidance v5: moving capsules in whichever kernel runs
+  GuideRecords g;                     // cost guidance: limits pick step_rows_kernel<ddpm, ns != null, pin != null> instead
   float* prev = nullptr;
   float* x0 = nullptr;                // optional
   int batch = 0, horizon = 0, dim = 0;
   hipStream_t stream = nullptr;
 };
 
-// One DPM-Solver++ step.  The kernel is dpm_step_kernel<pin != null, guide != null || field != null>; without a pin the noise
+// One DPM-Solver++ step.  The kernel is dpm_step_kernel<pin != null, a guide, a field, a route or capsules>; without a pin the noise
 // fields are not looked at.
 struct DpmCall {
   const adx_dpm_coef* c = nullptr;
@@ -42,11 +68,7 @@ struct DpmCall {
   int32_t slot = 0;
   int64_t row_offset = 0;
   const adx_pin* pin = nullptr;
-  const adx_guide* guide = nullptr;   // cost guidance v1
-  const adx_guide_field* field = nullptr;      // cost guidance v2
-  const adx_guide_motion* motion = nullptr;    // cost guidance v3: dpm_step_rows_kernel<pin != null> instead
-  const adx_guide_route* route = nullptr;      // cost guidance v4
-  const adx_guide_capsules* capsules = nullptr;      // cost guidance v5
+  GuideRecords g;                     // cost guidance: limits pick dpm_step_rows_kernel<pin != null> instead
   float* prev = nullptr;
   float* x0 = nullptr;                // always written
   int batch = 0, horizon = 0, dim = 0;
@@ -55,35 +77,30 @@ struct DpmCall {
 
 int step_run(const StepCall& k);
 int dpm_run(const DpmCall& k);
-// The refusals of "cost guidance v1" that every guided launch shares, filling the kernels' GuideArgs: dim >= 2, the counts, the
-// arrays, scene_rows against `batch` rows, and `out` [on bytes] / `out2` [on2 bytes, may be null] against discs and planes.
-// `step`: a sampler step, which also reads iters, cap and lambda and refuses `inpaint`.  `what` prefixes every text.
-// `f`: the field of "cost guidance v2" or null; with a field `g` may be null (no discs, no planes) unless `step`.  The field's
-// refusals follow the guide's: cells, the node counts, its scene_rows against `batch` and against the guide's, the geometry, the
-// weight, and the outputs against cells.
-int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, bool step, bool inpaint, const void* out, size_t on,
-                const void* out2, size_t on2, int batch, int dim, GuideArgs* a);
-// The refusals of "cost guidance v3" that every launch with motion limits shares, after guide_check, filling MotionArgs: the
-// limits, their scene_rows against `batch` and against the guide's and the field's, the weights, horizon <= 64 and the outputs
-// against the limits.  `g` and `f` are the (checked) guide and field beside it; either may be null.
-int motion_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, const void* out, size_t on,
-                 const void* out2, size_t on2, int batch, int horizon, MotionArgs* a);
-// The refusals of "cost guidance v4" that every launch with a route shares, after guide_check (which leaves GuideArgs without a
-// route) and motion_check, filling RouteArgs: the arrays, the point count, scene_rows against `batch` and against the guide's, the
-// field's and the limits', the weight and the outputs against the arrays.  `g`, `f` and `m` are the (checked) records beside it;
-// each may be null.
-int route_check(const adx_guide_route* r, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m, const char* what,
-                const void* out, size_t on, const void* out2, size_t on2, int batch, RouteArgs* a);
-// The refusals of "cost guidance v5" that every launch with capsules shares, after guide_check (which leaves GuideArgs without
-// capsules), motion_check and route_check, filling CapsuleArgs: the array, the slot count, scene_rows against `batch` and against the
-// guide's, the field's, the limits' and the route's, the weight and the outputs against the array.  `g`, `f`, `m` and `r` are the
-// (checked) records beside it; each may be null.
-int capsule_check(const adx_guide_capsules* c, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m,
-                  const adx_guide_route* r, const char* what, const void* out, size_t on, const void* out2, size_t on2, int batch,
-                  CapsuleArgs* a);
-int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
-               const adx_guide_route* route, const adx_guide_capsules* capsules, float* cost, int32_t* active, int rows, int horizon,
-               int dim, hipStream_t s);
+// Every refusal of "cost guidance v1" to "v5" that guided launches share, record by record in the contracts' order, each with
+// `what` in front, filling the kernels' GuideArgs (field, route and capsules included) and MotionArgs.  A consumer that takes no
+// limits (stop_short) passes a null `ma`: then r.motion is neither checked nor read, as if it were null.
+//   the guide: dim >= 2, the counts, the arrays, scene_rows against `batch` rows; a field alone stands for a guide without discs
+//     and planes.  `step`: a sampler step, which also reads iters, cap and lambda, refuses `inpaint`, and refuses a field, limits,
+//     a route or capsules without a guide to read them from;
+//   the field: cells, the node counts, scene_rows, the geometry, the weight;
+//   the limits: the array, scene_rows, the weights, horizon <= 64;
+//   the route: the arrays, the point count, scene_rows, the weight;
+//   the capsules: the array, the slot count, scene_rows, the weight.
+// A record's scene_rows must divide `batch` and equal that of every earlier record present (a guide without discs and planes is
+// exempt), and its arrays may overlap none of the `n_outs` outputs: both refusals close the record's block.  A new term adds a
+// field to GuideRecords, GuideArgs and SceneGuide, one block here and one in guide_grad, and touches no call site.
+int guide_records_check(const GuideRecords& r, const char* what, bool step, bool inpaint, const ByteSpan* outs, int n_outs, int batch,
+                        int horizon, int dim, GuideArgs* ga, MotionArgs* ma);
+int guide_cost(const float* traj, const GuideRecords& g, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s);
+// selection cost v1 and v2 (select.hip)
+int traj_select(const adx_select_cfg* c, const float* trajs, const float* target, float* cost, int32_t* index, float* best,
+                hipStream_t s);
+int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const GuideRecords& g, float* cost,
+                      int32_t* active, int32_t* index, int32_t* blocked, float* best, hipStream_t s);
+// "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
+int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
+               int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);
 // "Capsules from boxes v1" (capsule.hip)
 int capsules_from_boxes(const float* boxes, float* out, int scenes, int n_boxes, float inflate, hipStream_t s);
 int field_from_occupancy(const float* occ, float* cells, int scenes, int gy, int gx, float dx, float dy, float inv_m2, int ry, int rx,

@@ -36,8 +36,8 @@
 // Host side (sched.h): every step export fills one record, StepCall or DpmCall, and one function, step_run or dpm_run, checks it
 // and picks the kernel instantiation from what the record holds (schedule, noise state or not, pin or not, guide or not).  Every refusal of a
 // step lives in those two functions and the helpers they share with pin_apply, warm_init and add_noise: shape_check (non-empty,
-// fits the kernels' 32-bit index), noise_rows (the launch's rows inside the stream), pin_check (what is pin-specific) and guide_check
-// (what is guide-specific; guide_cost and select.hip share it).
+// fits the kernels' 32-bit index), noise_rows (the launch's rows inside the stream), pin_check (what is pin-specific) and
+// guide_records_check (what the guide records of a launch ask, all five in one pass; guide_cost, select.hip and fallback.hip share it).
 // Device side: the arithmetic two kernels share is written once, in __device__ helpers that keep the reference's operation order.
 #include "sched.h"
 #include "noise.h"
@@ -137,24 +137,18 @@ __device__ __forceinline__ bool guide_x0(const GuideArgs& g, const float* mo, co
   const int d = e % dim;
   if (d >= 2) return false;
   const int w = e / dim;
-  const int h = w % horizon, row = w / horizon, scene = row % g.scene_rows;
+  const int h = w % horizon, row = w / horizon, scene_index = row % g.scene_rows;      // here, ahead of the partner's loads
   const int ep = d == 0 ? e + 1 : e - 1;                 // the waypoint's other xy element
   float xp = x0_from(pt, sa, sb, x[ep], cfg_model_output(mo, ep, total, cfg_combine, free_scale));
   if (clip) xp = clamp_nan(xp, -clip_range, clip_range);
   float px = d == 0 ? x0 : xp, py = d == 0 ? xp : x0;
-  const float* discs = g.discs + (size_t)scene * g.M * 5;
-  const float* planes = g.planes + (size_t)scene * g.P * 3;
-  const float* cells = field_cells(g.field, row);      // cost guidance v2: null without a field, the same in every thread
-  const float* pts = route_points(g.route, row);       // cost guidance v4: null without a route, the same in every thread
-  const float W2 = route_w2(g.route, pts, row);
-  const float* caps = capsule_slots(g.capsule, row);   // cost guidance v5: null without capsules, the same in every thread
+  const SceneGuide scene = scene_guide(g, row, scene_index);
   const float hf = (float)h;
   bool moved = false;
   for (int it = 0; it < g.iters; ++it) {
     float J, gx, gy;
     int active;
-    guide_grad(discs, g.M, planes, g.P, cells, g.field, pts, g.route.R, W2, g.route.weight, caps, g.capsule.C, g.capsule.weight, hf, px, py,
-               J, gx, gy, active);
+    guide_grad(scene, hf, px, py, J, gx, gy, active);
     const float lx = g.lambda * gx, ly = g.lambda * gy;
     const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
     moved = moved || (d == 0 ? sx : sy) != 0.f;
@@ -197,13 +191,7 @@ __device__ __forceinline__ float x0_clipped(int pt, float sa, float sb, float xs
 __device__ __forceinline__ void guide_rows(const GuideArgs& g, const MotionArgs& mo, int row, int lane, int H, bool live, int clip,
                                            float clip_range, float& px, float& py, bool& mx, bool& my) {
 #pragma clang fp contract(off)
-  const int scene = row % g.scene_rows;
-  const float* discs = g.discs + (size_t)scene * g.M * 5;
-  const float* planes = g.planes + (size_t)scene * g.P * 3;
-  const float* cells = field_cells(g.field, row);
-  const float* pts = route_points(g.route, row);
-  const float W2 = route_w2(g.route, pts, row);
-  const float* caps = capsule_slots(g.capsule, row);
+  const SceneGuide scene = scene_guide(g, row);
   float S2, A2;
   motion_limits(mo, row, S2, A2);
   const float hf = (float)lane;
@@ -218,8 +206,7 @@ __device__ __forceinline__ void guide_rows(const GuideArgs& g, const MotionArgs&
     if (live) {
       float J, gx, gy;
       int active;
-      guide_grad(discs, g.M, planes, g.P, cells, g.field, pts, g.route.R, W2, g.route.weight, caps, g.capsule.C, g.capsule.weight, hf, px, py,
-               J, gx, gy, active);
+      guide_grad(scene, hf, px, py, J, gx, gy, active);
       motion_grad(nx, ny, lane, H, S2, A2, mo.w_speed, mo.w_accel, J, gx, gy, active);
       const float lx = g.lambda * gx, ly = g.lambda * gy;
       const float sx = clamp_nan(lx, -g.cap, g.cap), sy = clamp_nan(ly, -g.cap, g.cap);
@@ -273,17 +260,6 @@ __global__ void __launch_bounds__(kRowWaves * kWave) step_rows_kernel(const Step
 // e >> 2 is the stream's 32-bit counter word: logical elements live in [0, 2^34)
 static const int64_t kNoiseElems = (int64_t)1 << 34;
 
-// A [rows][horizon][dim] launch: not empty, and small enough for the kernels' int element index (and the e + total of the
-// classifier-free combine)
-static int shape_check(const char* what, int rows, int horizon, int dim) {
-  ADX_REQUIRE(rows >= 1 && horizon >= 1 && dim >= 1, "%s: empty shape", what);
-  const int64_t per = (int64_t)horizon * dim;        // < 2^62
-  const int64_t max = 0x3fffffff;
-  ADX_REQUIRE(per <= max && rows * per <= max, "%s: %lld elements do not fit the kernel's 32-bit index", what,
-              (long long)((uint64_t)rows * (uint64_t)per));
-  return ADX_OK;
-}
-
 // Rows [row_offset, row_offset + rows) of `per` >= 1 elements each lie inside the noise stream; *base = their first logical element
 static int noise_rows(const char* what, int64_t row_offset, int rows, int64_t per, uint64_t* base) {
   ADX_REQUIRE(row_offset >= 0, "%s: negative row_offset %lld", what, (long long)row_offset);
@@ -292,11 +268,6 @@ static int noise_rows(const char* what, int64_t row_offset, int rows, int64_t pe
               (long long)row_offset + rows, (long long)per);
   *base = (uint64_t)row_offset * (uint64_t)per;
   return ADX_OK;
-}
-
-static bool byte_ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qn && b < a + pn;
 }
 
 // the refusals of "pinned waypoints v1" that every pinned launch shares, after shape_check; `out2` may be null
@@ -316,46 +287,62 @@ static int pin_check(const adx_pin* pin, const char* what, bool has_noise, const
   return ADX_OK;
 }
 
-// the refusals of "cost guidance v1" that every guided launch, guide_cost and the guided selection share (sched.h); `step`: a
-// step, which also reads iters, cap and lambda; `out2` may be null
 static const FieldArgs kNoField = {nullptr, 1, 2, 2, 0.f, 0.f, 0.f, 0.f, 0.f};
 static const RouteArgs kNoRoute = {nullptr, nullptr, 1, 2, 0.f};
 static const CapsuleArgs kNoCapsule = {nullptr, 1, 1, 0.f};
+static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f, kNoField, kNoRoute, kNoCapsule};
 
-static bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for inf and NaN
+// One record's scene count as the agreement refusals name it: "<holds> %d scenes, <beside> %d"
+struct SceneCount {
+  const char* holds;      // as the record that disagrees
+  const char* beside;     // as the earlier record it disagrees with
+  bool binds;             // present, and not a guide without discs and planes
+  int scenes;
+};
 
-// the refusals of "cost guidance v2" that are the field's own, after the guide's; `g` is the checked guide beside it
-static int field_check(const adx_guide_field* f, const adx_guide* g, const char* what, const void* out, size_t on, const void* out2,
-                       size_t on2, int batch, FieldArgs* a) {
-  ADX_REQUIRE(f->cells != nullptr, "%s: null field cells", what);
-  ADX_REQUIRE(f->gx >= ADX_FIELD_MIN_NODES && f->gx <= ADX_FIELD_MAX_NODES && f->gy >= ADX_FIELD_MIN_NODES &&
-              f->gy <= ADX_FIELD_MAX_NODES, "%s: field of %d x %d nodes (gy x gx), supported %d..%d each", what, f->gy, f->gx,
-              ADX_FIELD_MIN_NODES, ADX_FIELD_MAX_NODES);
-  ADX_REQUIRE(f->scene_rows >= 1 && batch % f->scene_rows == 0, "%s: batch %d must be a positive multiple of the field's scene_rows %d",
-              what, batch, f->scene_rows);
-  ADX_REQUIRE((g->n_discs == 0 && g->n_planes == 0) || g->scene_rows == f->scene_rows,
-              "%s: the field holds %d scenes, the guide's discs and planes %d", what, f->scene_rows, g->scene_rows);
-  ADX_REQUIRE(finite_f(f->inv_dx) && f->inv_dx > 0.f && finite_f(f->inv_dy) && f->inv_dy > 0.f,
-              "%s: field inv_dx %g and inv_dy %g must be finite and > 0", what, (double)f->inv_dx, (double)f->inv_dy);
-  ADX_REQUIRE(f->weight >= 0.f, "%s: field weight %g is negative or NaN", what, (double)f->weight);
-  ADX_REQUIRE(finite_f(f->x_min) && finite_f(f->y_min), "%s: field origin (%g, %g) is not finite", what, (double)f->x_min,
-              (double)f->y_min);
-  const size_t cn = (size_t)f->scene_rows * f->gy * f->gx * sizeof(float);
-  ADX_REQUIRE(!byte_ranges_overlap(out, on, f->cells, cn) && (out2 == nullptr || !byte_ranges_overlap(out2, on2, f->cells, cn)),
-              "%s: an output overlaps the field's cells", what);
-  a->cells = f->cells; a->scene_rows = f->scene_rows; a->Gx = f->gx; a->Gy = f->gy;
-  a->x_min = f->x_min; a->y_min = f->y_min; a->inv_dx = f->inv_dx; a->inv_dy = f->inv_dy; a->weight = f->weight;
+// record `i` of `t` against every earlier record that binds
+static int scenes_agree(const char* what, const SceneCount* t, int i) {
+  for (int j = 0; j < i; ++j)
+    ADX_REQUIRE(!t[j].binds || t[j].scenes == t[i].scenes, "%s: %s %d scenes, %s %d", what, t[i].holds, t[i].scenes, t[j].beside,
+                t[j].scenes);
   return ADX_OK;
 }
 
-int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, bool step, bool inpaint, const void* out, size_t on,
-                const void* out2, size_t on2, int batch, int dim, GuideArgs* a) {
+// some output shares a byte with [q, q + qn)
+static bool outputs_overlap(const ByteSpan* outs, int n_outs, const void* q, size_t qn) {
+  for (int i = 0; i < n_outs; ++i)
+    if (outs[i].p != nullptr && byte_ranges_overlap(outs[i].p, outs[i].n, q, qn)) return true;
+  return false;
+}
+
+// every refusal the guide records of a launch share (sched.h)
+int guide_records_check(const GuideRecords& r, const char* what, bool step, bool inpaint, const ByteSpan* outs, int n_outs, int batch,
+                        int horizon, int dim, GuideArgs* ga, MotionArgs* ma) {
   static const adx_guide bare = {nullptr, nullptr, 1, 0, 0, 1, 0.f, 0.f};      // a field without a guide: no discs, no planes
+  const adx_guide* g = r.guide;
+  const adx_guide_field* const f = r.field;
+  const adx_guide_motion* const m = ma != nullptr ? r.motion : nullptr;      // no MotionArgs to fill: the consumer takes no limits
+  const adx_guide_route* const rt = r.route;
+  const adx_guide_capsules* const c = r.capsules;
+  if (step) {
+    ADX_REQUIRE(rt == nullptr || g != nullptr, "%s: a route without a guide: a step reads iters, lambda and cap from the guide", what);
+    ADX_REQUIRE(c == nullptr || g != nullptr, "%s: capsules without a guide: a step reads iters, lambda and cap from the guide", what);
+    ADX_REQUIRE(m == nullptr || g != nullptr, "%s: motion limits without a guide: a step reads iters, lambda and cap from the guide", what);
+  }
   if (g == nullptr) {
     ADX_REQUIRE(f != nullptr, "%s: null guide", what);
     ADX_REQUIRE(!step, "%s: a field without a guide: a step reads iters, lambda and cap from the guide", what);
     g = &bare;
   }
+  const SceneCount held[5] = {
+      {nullptr, "the guide's discs and planes", g->n_discs != 0 || g->n_planes != 0, g->scene_rows},
+      {"the field holds", "the field", f != nullptr, f != nullptr ? f->scene_rows : 0},
+      {"the limits hold", "the motion limits", m != nullptr, m != nullptr ? m->scene_rows : 0},
+      {"the route holds", "the route", rt != nullptr, rt != nullptr ? rt->scene_rows : 0},
+      {"the capsules hold", nullptr, c != nullptr, c != nullptr ? c->scene_rows : 0}};
+  int rc;
+
+  // cost guidance v1: discs and planes
   ADX_REQUIRE(dim >= 2, "%s: cost guidance moves (x, y), dim is %d", what, dim);
   ADX_REQUIRE(g->n_discs >= 0 && g->n_discs <= ADX_GUIDE_MAX_DISCS, "%s: n_discs %d outside 0..%d", what, g->n_discs,
               ADX_GUIDE_MAX_DISCS);
@@ -372,114 +359,73 @@ int guide_check(const adx_guide* g, const adx_guide_field* f, const char* what, 
     ADX_REQUIRE(g->lambda == g->lambda, "%s: guide lambda is NaN", what);
     ADX_REQUIRE(!inpaint, "%s: c->inpaint (the inpainting schedulers' blend) and a guide do not compose", what);
   }
-  const size_t dn = (size_t)g->scene_rows * g->n_discs * 5 * sizeof(float), pn = (size_t)g->scene_rows * g->n_planes * 3 * sizeof(float);
-  ADX_REQUIRE(!byte_ranges_overlap(out, on, g->discs, dn) && !byte_ranges_overlap(out, on, g->planes, pn) &&
-              (out2 == nullptr || (!byte_ranges_overlap(out2, on2, g->discs, dn) && !byte_ranges_overlap(out2, on2, g->planes, pn))),
+  ADX_REQUIRE(!outputs_overlap(outs, n_outs, g->discs, (size_t)g->scene_rows * g->n_discs * 5 * sizeof(float)) &&
+                  !outputs_overlap(outs, n_outs, g->planes, (size_t)g->scene_rows * g->n_planes * 3 * sizeof(float)),
               "%s: an output overlaps discs or planes", what);
-  a->discs = g->discs; a->planes = g->planes; a->scene_rows = g->scene_rows; a->M = g->n_discs; a->P = g->n_planes;
-  a->iters = g->iters; a->lambda = g->lambda; a->cap = g->cap;
-  a->field = kNoField;
-  a->route = kNoRoute;
-  a->capsule = kNoCapsule;
-  return f == nullptr ? ADX_OK : field_check(f, g, what, out, on, out2, on2, batch, &a->field);
-}
+  *ga = kNoGuide;
+  ga->discs = g->discs; ga->planes = g->planes; ga->scene_rows = g->scene_rows; ga->M = g->n_discs; ga->P = g->n_planes;
+  ga->iters = g->iters; ga->lambda = g->lambda; ga->cap = g->cap;
+  if (ma != nullptr) *ma = MotionArgs{nullptr, 1, 0.f, 0.f};
 
-static const GuideArgs kNoGuide = {nullptr, nullptr, 1, 0, 0, 0, 0.f, 0.f, kNoField, kNoRoute, kNoCapsule};
-
-// the refusals of "cost guidance v3" that are the motion limits' own, after guide_check (sched.h)
-int motion_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, const void* out, size_t on,
-                 const void* out2, size_t on2, int batch, int horizon, MotionArgs* a) {
-  ADX_REQUIRE(m->limits != nullptr, "%s: null motion limits", what);
-  ADX_REQUIRE(m->scene_rows >= 1 && batch % m->scene_rows == 0, "%s: batch %d must be a positive multiple of the limits' scene_rows %d",
-              what, batch, m->scene_rows);
-  ADX_REQUIRE(g == nullptr || (g->n_discs == 0 && g->n_planes == 0) || g->scene_rows == m->scene_rows,
-              "%s: the limits hold %d scenes, the guide's discs and planes %d", what, m->scene_rows, g == nullptr ? 0 : g->scene_rows);
-  ADX_REQUIRE(f == nullptr || f->scene_rows == m->scene_rows, "%s: the limits hold %d scenes, the field %d", what, m->scene_rows,
-              f == nullptr ? 0 : f->scene_rows);
-  ADX_REQUIRE(m->w_speed >= 0.f, "%s: motion w_speed %g is negative or NaN", what, (double)m->w_speed);
-  ADX_REQUIRE(m->w_accel >= 0.f, "%s: motion w_accel %g is negative or NaN", what, (double)m->w_accel);
-  ADX_REQUIRE(horizon <= kWave, "%s: motion limits give a row to a wave: horizon %d, supported 1..%d", what, horizon, kWave);
-  const size_t ln = (size_t)m->scene_rows * 2 * sizeof(float);
-  ADX_REQUIRE(!byte_ranges_overlap(out, on, m->limits, ln) && (out2 == nullptr || !byte_ranges_overlap(out2, on2, m->limits, ln)),
-              "%s: an output overlaps the motion limits", what);
-  a->limits = m->limits; a->scene_rows = m->scene_rows; a->w_speed = m->w_speed; a->w_accel = m->w_accel;
-  return ADX_OK;
-}
-
-// the refusals of "cost guidance v4" that are the route's own, after guide_check and motion_check (sched.h)
-int route_check(const adx_guide_route* r, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m, const char* what,
-                const void* out, size_t on, const void* out2, size_t on2, int batch, RouteArgs* a) {
-  ADX_REQUIRE(r->points != nullptr, "%s: null route points", what);
-  ADX_REQUIRE(r->half_width != nullptr, "%s: null route half_width", what);
-  ADX_REQUIRE(r->n_points >= ADX_ROUTE_MIN_POINTS && r->n_points <= ADX_ROUTE_MAX_POINTS, "%s: route of %d points, supported %d..%d", what,
-              r->n_points, ADX_ROUTE_MIN_POINTS, ADX_ROUTE_MAX_POINTS);
-  ADX_REQUIRE(r->scene_rows >= 1 && batch % r->scene_rows == 0, "%s: batch %d must be a positive multiple of the route's scene_rows %d",
-              what, batch, r->scene_rows);
-  ADX_REQUIRE(g == nullptr || (g->n_discs == 0 && g->n_planes == 0) || g->scene_rows == r->scene_rows,
-              "%s: the route holds %d scenes, the guide's discs and planes %d", what, r->scene_rows, g == nullptr ? 0 : g->scene_rows);
-  ADX_REQUIRE(f == nullptr || f->scene_rows == r->scene_rows, "%s: the route holds %d scenes, the field %d", what, r->scene_rows,
-              f == nullptr ? 0 : f->scene_rows);
-  ADX_REQUIRE(m == nullptr || m->scene_rows == r->scene_rows, "%s: the route holds %d scenes, the motion limits %d", what, r->scene_rows,
-              m == nullptr ? 0 : m->scene_rows);
-  ADX_REQUIRE(r->weight >= 0.f, "%s: route weight %g is negative or NaN", what, (double)r->weight);
-  const size_t pn = (size_t)r->scene_rows * r->n_points * 2 * sizeof(float), wn = (size_t)r->scene_rows * sizeof(float);
-  ADX_REQUIRE(!byte_ranges_overlap(out, on, r->points, pn) && !byte_ranges_overlap(out, on, r->half_width, wn) &&
-                  (out2 == nullptr || (!byte_ranges_overlap(out2, on2, r->points, pn) && !byte_ranges_overlap(out2, on2, r->half_width, wn))),
-              "%s: an output overlaps the route's points or half_width", what);
-  a->points = r->points; a->half_width = r->half_width; a->scene_rows = r->scene_rows; a->R = r->n_points; a->weight = r->weight;
-  return ADX_OK;
-}
-
-// the refusals of "cost guidance v5" that are the capsules' own, after guide_check, motion_check and route_check (sched.h)
-int capsule_check(const adx_guide_capsules* c, const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m,
-                  const adx_guide_route* r, const char* what, const void* out, size_t on, const void* out2, size_t on2, int batch,
-                  CapsuleArgs* a) {
-  ADX_REQUIRE(c->capsules != nullptr, "%s: null capsules", what);
-  ADX_REQUIRE(c->n_capsules >= 1 && c->n_capsules <= ADX_CAPSULE_MAX, "%s: n_capsules %d outside 1..%d", what, c->n_capsules,
-              ADX_CAPSULE_MAX);
-  ADX_REQUIRE(c->scene_rows >= 1 && batch % c->scene_rows == 0, "%s: batch %d must be a positive multiple of the capsules' scene_rows %d",
-              what, batch, c->scene_rows);
-  ADX_REQUIRE(g == nullptr || (g->n_discs == 0 && g->n_planes == 0) || g->scene_rows == c->scene_rows,
-              "%s: the capsules hold %d scenes, the guide's discs and planes %d", what, c->scene_rows, g == nullptr ? 0 : g->scene_rows);
-  ADX_REQUIRE(f == nullptr || f->scene_rows == c->scene_rows, "%s: the capsules hold %d scenes, the field %d", what, c->scene_rows,
-              f == nullptr ? 0 : f->scene_rows);
-  ADX_REQUIRE(m == nullptr || m->scene_rows == c->scene_rows, "%s: the capsules hold %d scenes, the motion limits %d", what,
-              c->scene_rows, m == nullptr ? 0 : m->scene_rows);
-  ADX_REQUIRE(r == nullptr || r->scene_rows == c->scene_rows, "%s: the capsules hold %d scenes, the route %d", what, c->scene_rows,
-              r == nullptr ? 0 : r->scene_rows);
-  ADX_REQUIRE(c->weight >= 0.f, "%s: capsule weight %g is negative or NaN", what, (double)c->weight);
-  const size_t cn = (size_t)c->scene_rows * c->n_capsules * 7 * sizeof(float);
-  ADX_REQUIRE(!byte_ranges_overlap(out, on, c->capsules, cn) && (out2 == nullptr || !byte_ranges_overlap(out2, on2, c->capsules, cn)),
-              "%s: an output overlaps the capsules", what);
-  a->slots = c->capsules; a->scene_rows = c->scene_rows; a->C = c->n_capsules; a->weight = c->weight;
-  return ADX_OK;
-}
-
-// a step with motion limits: guide_check's refusals with the limits' own text where there is no adx_guide to read iters from
-static int motion_step_check(const adx_guide_motion* m, const adx_guide* g, const adx_guide_field* f, const char* what, bool inpaint,
-                             float* prev, float* x0, int batch, int horizon, int dim, GuideArgs* ga, MotionArgs* ma) {
-  ADX_REQUIRE(g != nullptr, "%s: motion limits without a guide: a step reads iters, lambda and cap from the guide", what);
-  const size_t on = (size_t)batch * horizon * dim * sizeof(float);
-  const int rc = guide_check(g, f, what, true, inpaint, prev, on, x0, on, batch, dim, ga);
-  return rc != ADX_OK ? rc : motion_check(m, g, f, what, prev, on, x0, on, batch, horizon, ma);
-}
-
-// a step's guide records, checked in the contracts' order into GuideArgs (and MotionArgs when there are limits): a route or
-// capsules without an adx_guide get their own text, as limits do
-static int guided_step_check(const adx_guide* g, const adx_guide_field* f, const adx_guide_motion* m, const adx_guide_route* r,
-                             const adx_guide_capsules* cp, const char* what, bool inpaint, float* prev, float* x0, int batch, int horizon,
-                             int dim, GuideArgs* ga, MotionArgs* ma) {
-  ADX_REQUIRE(r == nullptr || g != nullptr, "%s: a route without a guide: a step reads iters, lambda and cap from the guide", what);
-  ADX_REQUIRE(cp == nullptr || g != nullptr, "%s: capsules without a guide: a step reads iters, lambda and cap from the guide", what);
-  const size_t on = (size_t)batch * horizon * dim * sizeof(float);
-  const int rc = m != nullptr ? motion_step_check(m, g, f, what, inpaint, prev, x0, batch, horizon, dim, ga, ma)
-                              : guide_check(g, f, what, true, inpaint, prev, on, x0, on, batch, dim, ga);
-  if (rc != ADX_OK) return rc;
-  if (r != nullptr) {
-    const int rr = route_check(r, g, f, m, what, prev, on, x0, on, batch, &ga->route);
-    if (rr != ADX_OK) return rr;
+  if (f != nullptr) {      // cost guidance v2: the field
+    ADX_REQUIRE(f->cells != nullptr, "%s: null field cells", what);
+    ADX_REQUIRE(f->gx >= ADX_FIELD_MIN_NODES && f->gx <= ADX_FIELD_MAX_NODES && f->gy >= ADX_FIELD_MIN_NODES &&
+                f->gy <= ADX_FIELD_MAX_NODES, "%s: field of %d x %d nodes (gy x gx), supported %d..%d each", what, f->gy, f->gx,
+                ADX_FIELD_MIN_NODES, ADX_FIELD_MAX_NODES);
+    ADX_REQUIRE(f->scene_rows >= 1 && batch % f->scene_rows == 0, "%s: batch %d must be a positive multiple of the field's scene_rows %d",
+                what, batch, f->scene_rows);
+    if ((rc = scenes_agree(what, held, 1)) != ADX_OK) return rc;
+    ADX_REQUIRE(finite_f(f->inv_dx) && f->inv_dx > 0.f && finite_f(f->inv_dy) && f->inv_dy > 0.f,
+                "%s: field inv_dx %g and inv_dy %g must be finite and > 0", what, (double)f->inv_dx, (double)f->inv_dy);
+    ADX_REQUIRE(f->weight >= 0.f, "%s: field weight %g is negative or NaN", what, (double)f->weight);
+    ADX_REQUIRE(finite_f(f->x_min) && finite_f(f->y_min), "%s: field origin (%g, %g) is not finite", what, (double)f->x_min,
+                (double)f->y_min);
+    ADX_REQUIRE(!outputs_overlap(outs, n_outs, f->cells, (size_t)f->scene_rows * f->gy * f->gx * sizeof(float)),
+                "%s: an output overlaps the field's cells", what);
+    ga->field = FieldArgs{f->cells, f->scene_rows, f->gx, f->gy, f->x_min, f->y_min, f->inv_dx, f->inv_dy, f->weight};
   }
-  return cp == nullptr ? ADX_OK : capsule_check(cp, g, f, m, r, what, prev, on, x0, on, batch, &ga->capsule);
+
+  if (m != nullptr) {      // cost guidance v3: the motion limits
+    ADX_REQUIRE(m->limits != nullptr, "%s: null motion limits", what);
+    ADX_REQUIRE(m->scene_rows >= 1 && batch % m->scene_rows == 0, "%s: batch %d must be a positive multiple of the limits' scene_rows %d",
+                what, batch, m->scene_rows);
+    if ((rc = scenes_agree(what, held, 2)) != ADX_OK) return rc;
+    ADX_REQUIRE(m->w_speed >= 0.f, "%s: motion w_speed %g is negative or NaN", what, (double)m->w_speed);
+    ADX_REQUIRE(m->w_accel >= 0.f, "%s: motion w_accel %g is negative or NaN", what, (double)m->w_accel);
+    ADX_REQUIRE(horizon <= kWave, "%s: motion limits give a row to a wave: horizon %d, supported 1..%d", what, horizon, kWave);
+    ADX_REQUIRE(!outputs_overlap(outs, n_outs, m->limits, (size_t)m->scene_rows * 2 * sizeof(float)),
+                "%s: an output overlaps the motion limits", what);
+    *ma = MotionArgs{m->limits, m->scene_rows, m->w_speed, m->w_accel};
+  }
+
+  if (rt != nullptr) {      // cost guidance v4: the route
+    ADX_REQUIRE(rt->points != nullptr, "%s: null route points", what);
+    ADX_REQUIRE(rt->half_width != nullptr, "%s: null route half_width", what);
+    ADX_REQUIRE(rt->n_points >= ADX_ROUTE_MIN_POINTS && rt->n_points <= ADX_ROUTE_MAX_POINTS, "%s: route of %d points, supported %d..%d",
+                what, rt->n_points, ADX_ROUTE_MIN_POINTS, ADX_ROUTE_MAX_POINTS);
+    ADX_REQUIRE(rt->scene_rows >= 1 && batch % rt->scene_rows == 0, "%s: batch %d must be a positive multiple of the route's scene_rows %d",
+                what, batch, rt->scene_rows);
+    if ((rc = scenes_agree(what, held, 3)) != ADX_OK) return rc;
+    ADX_REQUIRE(rt->weight >= 0.f, "%s: route weight %g is negative or NaN", what, (double)rt->weight);
+    ADX_REQUIRE(!outputs_overlap(outs, n_outs, rt->points, (size_t)rt->scene_rows * rt->n_points * 2 * sizeof(float)) &&
+                    !outputs_overlap(outs, n_outs, rt->half_width, (size_t)rt->scene_rows * sizeof(float)),
+                "%s: an output overlaps the route's points or half_width", what);
+    ga->route = RouteArgs{rt->points, rt->half_width, rt->scene_rows, rt->n_points, rt->weight};
+  }
+
+  if (c != nullptr) {      // cost guidance v5: the capsules
+    ADX_REQUIRE(c->capsules != nullptr, "%s: null capsules", what);
+    ADX_REQUIRE(c->n_capsules >= 1 && c->n_capsules <= ADX_CAPSULE_MAX, "%s: n_capsules %d outside 1..%d", what, c->n_capsules,
+                ADX_CAPSULE_MAX);
+    ADX_REQUIRE(c->scene_rows >= 1 && batch % c->scene_rows == 0, "%s: batch %d must be a positive multiple of the capsules' scene_rows %d",
+                what, batch, c->scene_rows);
+    if ((rc = scenes_agree(what, held, 4)) != ADX_OK) return rc;
+    ADX_REQUIRE(c->weight >= 0.f, "%s: capsule weight %g is negative or NaN", what, (double)c->weight);
+    ADX_REQUIRE(!outputs_overlap(outs, n_outs, c->capsules, (size_t)c->scene_rows * c->n_capsules * 7 * sizeof(float)),
+                "%s: an output overlaps the capsules", what);
+    ga->capsule = CapsuleArgs{c->capsules, c->scene_rows, c->n_capsules, c->weight};
+  }
+  return ADX_OK;
 }
 
 int step_run(const StepCall& k) {
@@ -491,8 +437,8 @@ int step_run(const StepCall& k) {
 #undef ADX_STEP_KERNELS
   const char* const what = "scheduler step";
   const adx_step_coef* c = k.c;
-  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr, guided = k.guide != nullptr || k.field != nullptr || k.route != nullptr ||
-                                                                          k.capsules != nullptr;
+  const bool rng = k.ns != nullptr, pinned = k.pin != nullptr;
+  const bool guided = k.g.guide != nullptr || k.g.field != nullptr || k.g.route != nullptr || k.g.capsules != nullptr;
   ADX_REQUIRE(k.z == nullptr || !rng, "scheduler step: a noise tensor and a noise state are both given");
   ADX_REQUIRE(c && k.mo && k.x && k.prev, "scheduler step: null tensor");
   int rc = shape_check(what, k.batch, k.horizon, k.dim);
@@ -509,9 +455,10 @@ int step_run(const StepCall& k) {
   }
   a.guide = kNoGuide;
   StepRowsArgs ra;
-  if (guided || k.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route), v5 (capsules): in whichever runs
-    rc = guided_step_check(k.guide, k.field, k.motion, k.route, k.capsules, what, c->inpaint != 0, k.prev, k.x0, k.batch, k.horizon,
-                           k.dim, &a.guide, &ra.motion);
+  if (guided || k.g.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route), v5 (capsules): in whichever runs
+    const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
+    const ByteSpan outs[2] = {{k.prev, on}, {k.x0, on}};
+    rc = guide_records_check(k.g, what, true, c->inpaint != 0, outs, 2, k.batch, k.horizon, k.dim, &a.guide, &ra.motion);
     if (rc != ADX_OK) return rc;
   }
   if (rng) {
@@ -525,7 +472,7 @@ int step_run(const StepCall& k) {
   a.c = *c;
   a.mo = k.mo; a.x = k.x; a.z = k.z; a.tgt = k.tgt; a.mask = k.mask; a.prev = k.prev; a.x0 = k.x0;
   a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
-  if (k.motion != nullptr) {
+  if (k.g.motion != nullptr) {
     using RowsKernel = void (*)(const StepRowsArgs);
 #define ADX_ROWS_KERNELS(ddpm) {{step_rows_kernel<ddpm, false, false>, step_rows_kernel<ddpm, false, true>}, \
                                 {step_rows_kernel<ddpm, true, false>, step_rows_kernel<ddpm, true, true>}}
@@ -636,17 +583,18 @@ int dpm_run(const DpmCall& k) {
     }
   }
   a.guide = kNoGuide;
-  const bool guided = k.guide != nullptr || k.field != nullptr || k.route != nullptr || k.capsules != nullptr;
+  const bool guided = k.g.guide != nullptr || k.g.field != nullptr || k.g.route != nullptr || k.g.capsules != nullptr;
   DpmRowsArgs ra;
-  if (guided || k.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route), v5 (capsules): in whichever runs
-    rc = guided_step_check(k.guide, k.field, k.motion, k.route, k.capsules, what, false, k.prev, k.x0, k.batch, k.horizon, k.dim,
-                           &a.guide, &ra.motion);
+  if (guided || k.g.motion != nullptr) {      // cost guidance v3 (limits): the row-wise kernel; v4 (a route), v5 (capsules): in whichever runs
+    const size_t on = (size_t)k.batch * k.horizon * k.dim * sizeof(float);
+    const ByteSpan outs[2] = {{k.prev, on}, {k.x0, on}};
+    rc = guide_records_check(k.g, what, true, false, outs, 2, k.batch, k.horizon, k.dim, &a.guide, &ra.motion);
     if (rc != ADX_OK) return rc;
   }
   a.c = *c;
   a.mo = k.mo; a.x = k.x; a.px0 = k.px0; a.prev = k.prev; a.x0 = k.x0;
   a.total = k.batch * k.horizon * k.dim; a.horizon = k.horizon; a.dim = k.dim;
-  if (k.motion != nullptr) {
+  if (k.g.motion != nullptr) {
     ra.s = a;
     if (k.pin != nullptr) dpm_step_rows_kernel<true><<<dim3(ceil_div(k.batch, kRowWaves)), dim3(kRowWaves * kWave), 0, k.stream>>>(ra);
     else dpm_step_rows_kernel<false><<<dim3(ceil_div(k.batch, kRowWaves)), dim3(kRowWaves * kWave), 0, k.stream>>>(ra);
@@ -680,7 +628,7 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
   const int lane = threadIdx.x & (kWave - 1);
   const int r = blockIdx.x * kCostWaves + (threadIdx.x >> 6);
   if (r >= a.rows) return;                       // whole waves leave: the shuffles below always see all 64 lanes
-  float J = 0.f;
+  float J = 0.f, gx, gy;
   int active = 0;
   if constexpr (MOTION) {
     const bool live = lane < a.horizon;
@@ -695,23 +643,14 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
     nx[3] = __shfl_down(nx[2], 1, kWave); ny[3] = __shfl_down(ny[2], 1, kWave);
     nx[4] = __shfl_down(nx[2], 2, kWave); ny[4] = __shfl_down(ny[2], 2, kWave);
     if (live) {
-      const int scene = r % a.g.scene_rows;
-      float gx, gy, S2, A2;
+      float S2, A2;
       motion_limits(a.motion, r, S2, A2);
-      const float* pts = route_points(a.g.route, r);
-      guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, field_cells(a.g.field, r),
-                 a.g.field, pts, a.g.route.R, route_w2(a.g.route, pts, r), a.g.route.weight,
-                 capsule_slots(a.g.capsule, r), a.g.capsule.C, a.g.capsule.weight, (float)lane, nx[2], ny[2], J, gx, gy, active);
+      guide_grad(scene_guide<true>(a.g, r), (float)lane, nx[2], ny[2], J, gx, gy, active);
       motion_grad(nx, ny, lane, a.horizon, S2, A2, a.motion.w_speed, a.motion.w_accel, J, gx, gy, active);
     }
   } else if (lane < a.horizon) {
     const float* p = a.traj + ((size_t)r * a.horizon + lane) * a.dim;
-    const int scene = r % a.g.scene_rows;
-    float gx, gy;
-    const float* pts = route_points(a.g.route, r);
-    guide_grad(a.g.discs + (size_t)scene * a.g.M * 5, a.g.M, a.g.planes + (size_t)scene * a.g.P * 3, a.g.P, field_cells(a.g.field, r),
-               a.g.field, pts, a.g.route.R, route_w2(a.g.route, pts, r), a.g.route.weight,
-               capsule_slots(a.g.capsule, r), a.g.capsule.C, a.g.capsule.weight, (float)lane, p[0], p[1], J, gx, gy, active);
+    guide_grad(scene_guide<true>(a.g, r), (float)lane, p[0], p[1], J, gx, gy, active);
   }
   J = wave_sum(J);
 #pragma unroll
@@ -722,37 +661,23 @@ __global__ void __launch_bounds__(kCostWaves * kWave) guide_cost_kernel(const Gu
   }
 }
 
-int guide_cost(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_motion* motion,
-               const adx_guide_route* route, const adx_guide_capsules* capsules, float* cost, int32_t* active, int rows, int horizon,
-               int dim, hipStream_t s) {
+int guide_cost(const float* traj, const GuideRecords& g, float* cost, int32_t* active, int rows, int horizon, int dim, hipStream_t s) {
   const char* const what = "guide cost";
-  ADX_REQUIRE(traj != nullptr && (guide != nullptr || field != nullptr) && cost != nullptr && active != nullptr,
+  ADX_REQUIRE(traj != nullptr && (g.guide != nullptr || g.field != nullptr) && cost != nullptr && active != nullptr,
               "guide cost: null traj, guide, cost or active");
   ADX_REQUIRE(horizon >= 1 && horizon <= kWave, "guide cost: horizon %d outside 1..%d", horizon, kWave);
   int rc = shape_check(what, rows, horizon, dim);
   if (rc != ADX_OK) return rc;
   GuideCostArgs a;
   const size_t cn = (size_t)rows * sizeof(float);
-  rc = guide_check(guide, field, what, false, false, cost, cn, active, cn, rows, dim, &a.g);
+  const ByteSpan outs[2] = {{cost, cn}, {active, cn}};
+  rc = guide_records_check(g, what, false, false, outs, 2, rows, horizon, dim, &a.g, &a.motion);
   if (rc != ADX_OK) return rc;
   const size_t tn = (size_t)rows * horizon * dim * sizeof(float);
   ADX_REQUIRE(!byte_ranges_overlap(cost, cn, traj, tn) && !byte_ranges_overlap(active, cn, traj, tn) &&
               !byte_ranges_overlap(cost, cn, active, cn), "guide cost: an output overlaps traj or the other output");
-  a.motion = MotionArgs{nullptr, 1, 0.f, 0.f};
-  if (motion != nullptr) {
-    rc = motion_check(motion, guide, field, what, cost, cn, active, cn, rows, horizon, &a.motion);
-    if (rc != ADX_OK) return rc;
-  }
-  if (route != nullptr) {
-    rc = route_check(route, guide, field, motion, what, cost, cn, active, cn, rows, &a.g.route);
-    if (rc != ADX_OK) return rc;
-  }
-  if (capsules != nullptr) {
-    rc = capsule_check(capsules, guide, field, motion, route, what, cost, cn, active, cn, rows, &a.g.capsule);
-    if (rc != ADX_OK) return rc;
-  }
   a.traj = traj; a.cost = cost; a.active = active; a.rows = rows; a.horizon = horizon; a.dim = dim;
-  if (motion != nullptr) guide_cost_kernel<true><<<dim3(ceil_div(rows, kCostWaves)), dim3(kCostWaves * kWave), 0, s>>>(a);
+  if (g.motion != nullptr) guide_cost_kernel<true><<<dim3(ceil_div(rows, kCostWaves)), dim3(kCostWaves * kWave), 0, s>>>(a);
   else guide_cost_kernel<false><<<dim3(ceil_div(rows, kCostWaves)), dim3(kCostWaves * kWave), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;

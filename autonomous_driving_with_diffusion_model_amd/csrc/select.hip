@@ -15,10 +15,11 @@
 //
 // "Selection cost v2" (adx_traj_select_guide) is a second instantiation of the same kernel (kGuide): the scene's discs and planes
 // are staged in LDS beside xs / ys (every lane of a wave reads the same constraint word: a broadcast, no bank conflict), step 2
-// also evaluates each waypoint's "cost guidance v1" cost and active count with the routine the step kernels use (guide.h) from the
-// LDS copy of xy, reduces them with the butterflies adx_guide_cost uses and takes a wave-wide vote on "every xy finite"; step 3
-// searches the free candidates alone when `hard` is set and one of them has a finite cost, and reports whether the winner is
-// blocked.  The kGuide = false instantiation reads none of the fields behind w_consensus: its code is what it was.
+// also evaluates each waypoint's "cost guidance v1" cost and active count with the routine the step kernels use (guide.h: the
+// scene view of scene_guide, its discs and planes pointed at the LDS copies) from the LDS copy of xy, reduces them with the
+// butterflies adx_guide_cost uses and takes a wave-wide vote on "every xy finite"; step 3 searches the free candidates alone when
+// `hard` is set and one of them has a finite cost, and reports whether the winner is blocked.  The kGuide = false instantiation
+// reads none of the fields behind w_consensus: its code is what it was.
 // With a field ("cost guidance v2") the same routine also reads the scene's raster, from global memory: four cells per waypoint.
 // With motion limits ("cost guidance v3", the kMotion instantiation) a waypoint's share of the segment and curvature terms follows,
 // through guide.h's motion_grad; its four neighbours are read from the xy planes in LDS.
@@ -79,12 +80,13 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
     xs[i] = p[0];
     ys[i] = D > 1 ? p[1] : 0.f;
   }
+  SceneGuide scene = {};
   if constexpr (kGuide) {      // the scene's discs and planes, once: the M * 5 and P * 3 words are within the arrays (the host checked)
-    const int scene = s % a.guide.scene_rows;
-    const float* discs = a.guide.discs + (size_t)scene * a.guide.M * 5;
-    const float* planes = a.guide.planes + (size_t)scene * a.guide.P * 3;
-    for (int i = tid; i < a.guide.M * 5; i += 256) disc_s[i] = discs[i];
-    for (int i = tid; i < a.guide.P * 3; i += 256) plane_s[i] = planes[i];
+    scene = scene_guide(a.guide, s);
+    for (int i = tid; i < scene.M * 5; i += 256) disc_s[i] = scene.discs[i];
+    for (int i = tid; i < scene.P * 3; i += 256) plane_s[i] = scene.planes[i];
+    scene.discs = disc_s;      // from here on every lane of a wave reads the same constraint word of the LDS copy
+    scene.planes = plane_s;
   }
   __syncthreads();
 
@@ -146,10 +148,7 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
       int act = 0;
       if (live) {
         float jx, jy;
-        const float* pts = route_points(a.guide.route, s);      // cost guidance v4: from global memory, like the raster
-        guide_grad(disc_s, a.guide.M, plane_s, a.guide.P, field_cells(a.guide.field, s), a.guide.field, pts, a.guide.route.R,
-                   route_w2(a.guide.route, pts, s), a.guide.route.weight, capsule_slots(a.guide.capsule, s), a.guide.capsule.C,
-                   a.guide.capsule.weight, (float)lane, px, py, J, jx, jy, act);
+        guide_grad(scene, (float)lane, px, py, J, jx, jy, act);      // the raster, the route and the capsules from global memory
         if constexpr (kMotion) {      // the neighbours from the planes; a point outside the row is a zero no term reads
           float nx[5], ny[5], S2, A2;
 #pragma unroll
@@ -221,11 +220,6 @@ __global__ void __launch_bounds__(256) traj_select_kernel(const SelectArgs a) {
   for (int i = tid; i < H * D; i += 256) dst[i] = src[i];
 }
 
-bool overlaps(const void* p, size_t pn, const void* q, size_t qn) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a < b + qn && b < a + pn;
-}
-
 // the refusals of "selection cost v1", which v2 inherits: the limits, the pointers both versions have, their overlaps
 int select_check(int scenes, int K, int H, int D, const float* trajs, const float* cost, const int32_t* index, const float* best) {
   ADX_REQUIRE(K >= 1 && K <= kSelMaxK, "traj select: %d candidates, supported 1..%d", K, kSelMaxK);
@@ -236,11 +230,11 @@ int select_check(int scenes, int K, int H, int D, const float* trajs, const floa
   const size_t row = (size_t)H * D * sizeof(float);
   const size_t in_bytes = (size_t)K * scenes * row, best_bytes = (size_t)scenes * row;
   const size_t cost_bytes = (size_t)scenes * K * sizeof(float), index_bytes = (size_t)scenes * sizeof(int32_t);
-  ADX_REQUIRE(!overlaps(best, best_bytes, trajs, in_bytes) && !overlaps(cost, cost_bytes, trajs, in_bytes) &&
-                  !overlaps(index, index_bytes, trajs, in_bytes),
+  ADX_REQUIRE(!byte_ranges_overlap(best, best_bytes, trajs, in_bytes) && !byte_ranges_overlap(cost, cost_bytes, trajs, in_bytes) &&
+                  !byte_ranges_overlap(index, index_bytes, trajs, in_bytes),
               "traj select: an output aliases trajs");
-  ADX_REQUIRE(!overlaps(best, best_bytes, cost, cost_bytes) && !overlaps(best, best_bytes, index, index_bytes) &&
-                  !overlaps(cost, cost_bytes, index, index_bytes),
+  ADX_REQUIRE(!byte_ranges_overlap(best, best_bytes, cost, cost_bytes) && !byte_ranges_overlap(best, best_bytes, index, index_bytes) &&
+                  !byte_ranges_overlap(cost, cost_bytes, index, index_bytes),
               "traj select: outputs alias each other");
   return ADX_OK;
 }
@@ -261,18 +255,17 @@ int traj_select(const adx_select_cfg* c, const float* trajs, const float* target
   return ADX_OK;
 }
 
-// "Selection cost v2": v1's refusals first, then what the guide adds; `field` (cost guidance v2) may be null, and with a field the
-// guide may be null too (no discs, no planes)
-int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const adx_guide* guide,
-                      const adx_guide_field* field, const adx_guide_motion* motion, const adx_guide_route* route,
-                      const adx_guide_capsules* capsules, float* cost, int32_t* active, int32_t* index, int32_t* blocked, float* best,
-                      hipStream_t s) {
+// "Selection cost v2": v1's refusals first, then what the guide records ask of the five outputs (sched.h: with a field the guide
+// may be null), then what is the selection's own: candidate k of scene s is row k * S + s, so only scene_rows == S makes
+// row % scene_rows the scene; and the new outputs against trajs and against every other output
+int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const GuideRecords& g, float* cost,
+                      int32_t* active, int32_t* index, int32_t* blocked, float* best, hipStream_t s) {
   const char* const what = "traj select guide";
   ADX_REQUIRE(c != nullptr, "traj select: null configuration");
   int rc = select_check(c->scenes, c->candidates, c->horizon, c->dim, trajs, cost, index, best);
   if (rc != ADX_OK) return rc;
   ADX_REQUIRE(c->dim >= 2, "traj select guide: the guide scores (x, y), dim is %d", c->dim);
-  ADX_REQUIRE(guide != nullptr || field != nullptr, "traj select guide: null guide");
+  ADX_REQUIRE(g.guide != nullptr || g.field != nullptr, "traj select guide: null guide");
   ADX_REQUIRE(active != nullptr, "traj select guide: null active");
   ADX_REQUIRE(blocked != nullptr, "traj select guide: null blocked");
   const int S = c->scenes, K = c->candidates;
@@ -280,65 +273,35 @@ int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const f
   const size_t in_bytes = (size_t)K * S * row, best_bytes = (size_t)S * row;
   const size_t sk_bytes = (size_t)S * K * sizeof(float), s_bytes = (size_t)S * sizeof(int32_t);
   SelectArgs a = {};
-  rc = guide_check(guide, field, what, false, false, cost, sk_bytes, active, sk_bytes, S * K, c->dim, &a.guide);
+  const ByteSpan outs[5] = {{cost, sk_bytes}, {active, sk_bytes}, {index, s_bytes}, {blocked, s_bytes}, {best, best_bytes}};
+  rc = guide_records_check(g, what, false, false, outs, 5, S * K, c->horizon, c->dim, &a.guide, &a.motion);
   if (rc != ADX_OK) return rc;
-  const void* const outs[3] = {index, blocked, best};
-  const size_t out_bytes[3] = {s_bytes, s_bytes, best_bytes};
-  if (guide != nullptr) {
-    const bool bare = guide->n_discs == 0 && guide->n_planes == 0;
-    ADX_REQUIRE(guide->scene_rows == S || (guide->scene_rows == 1 && bare),
+  if (g.guide != nullptr) {
+    const bool bare = g.guide->n_discs == 0 && g.guide->n_planes == 0;
+    ADX_REQUIRE(g.guide->scene_rows == S || (g.guide->scene_rows == 1 && bare),
                 "traj select guide: the guide holds %d scenes, the selection %d (1 is accepted of a guide without discs and planes)",
-                guide->scene_rows, S);
-    const size_t dn = (size_t)guide->scene_rows * guide->n_discs * 5 * sizeof(float);
-    const size_t pn = (size_t)guide->scene_rows * guide->n_planes * 3 * sizeof(float);
-    for (int i = 0; i < 3; ++i)
-      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], guide->discs, dn) && !overlaps(outs[i], out_bytes[i], guide->planes, pn),
-                  "traj select guide: an output overlaps discs or planes");
+                g.guide->scene_rows, S);
   }
-  if (field != nullptr) {      // candidate k of scene s is row k * S + s: only scene_rows == S makes r % scene_rows the scene
-    ADX_REQUIRE(field->scene_rows == S, "traj select guide: the field holds %d scenes, the selection %d", field->scene_rows, S);
-    const size_t cn = (size_t)field->scene_rows * field->gy * field->gx * sizeof(float);
-    for (int i = 0; i < 3; ++i)
-      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], field->cells, cn), "traj select guide: an output overlaps the field's cells");
-  }
-  a.motion = MotionArgs{nullptr, 1, 0.f, 0.f};
-  if (motion != nullptr) {      // cost guidance v3; scene_rows == S for the reason the field gives
-    rc = motion_check(motion, guide, field, what, cost, sk_bytes, active, sk_bytes, S * K, c->horizon, &a.motion);
-    if (rc != ADX_OK) return rc;
-    ADX_REQUIRE(motion->scene_rows == S, "traj select guide: the limits hold %d scenes, the selection %d", motion->scene_rows, S);
-    const size_t ln = (size_t)motion->scene_rows * 2 * sizeof(float);
-    for (int i = 0; i < 3; ++i)
-      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], motion->limits, ln), "traj select guide: an output overlaps the motion limits");
-  }
-  if (route != nullptr) {      // cost guidance v4; scene_rows == S for the reason the field gives
-    rc = route_check(route, guide, field, motion, what, cost, sk_bytes, active, sk_bytes, S * K, &a.guide.route);
-    if (rc != ADX_OK) return rc;
-    ADX_REQUIRE(route->scene_rows == S, "traj select guide: the route holds %d scenes, the selection %d", route->scene_rows, S);
-    const size_t pn = (size_t)route->scene_rows * route->n_points * 2 * sizeof(float), wn = (size_t)route->scene_rows * sizeof(float);
-    for (int i = 0; i < 3; ++i)
-      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], route->points, pn) && !overlaps(outs[i], out_bytes[i], route->half_width, wn),
-                  "traj select guide: an output overlaps the route's points or half_width");
-  }
-  if (capsules != nullptr) {      // cost guidance v5; scene_rows == S for the reason the field gives
-    rc = capsule_check(capsules, guide, field, motion, route, what, cost, sk_bytes, active, sk_bytes, S * K, &a.guide.capsule);
-    if (rc != ADX_OK) return rc;
-    ADX_REQUIRE(capsules->scene_rows == S, "traj select guide: the capsules hold %d scenes, the selection %d", capsules->scene_rows, S);
-    const size_t cn = (size_t)capsules->scene_rows * capsules->n_capsules * 7 * sizeof(float);
-    for (int i = 0; i < 3; ++i)
-      ADX_REQUIRE(!overlaps(outs[i], out_bytes[i], capsules->capsules, cn), "traj select guide: an output overlaps the capsules");
-  }
-  ADX_REQUIRE(!overlaps(active, sk_bytes, trajs, in_bytes) && !overlaps(blocked, s_bytes, trajs, in_bytes),
+  ADX_REQUIRE(g.field == nullptr || g.field->scene_rows == S, "traj select guide: the field holds %d scenes, the selection %d",
+              g.field == nullptr ? 0 : g.field->scene_rows, S);
+  ADX_REQUIRE(g.motion == nullptr || g.motion->scene_rows == S, "traj select guide: the limits hold %d scenes, the selection %d",
+              g.motion == nullptr ? 0 : g.motion->scene_rows, S);
+  ADX_REQUIRE(g.route == nullptr || g.route->scene_rows == S, "traj select guide: the route holds %d scenes, the selection %d",
+              g.route == nullptr ? 0 : g.route->scene_rows, S);
+  ADX_REQUIRE(g.capsules == nullptr || g.capsules->scene_rows == S, "traj select guide: the capsules hold %d scenes, the selection %d",
+              g.capsules == nullptr ? 0 : g.capsules->scene_rows, S);
+  ADX_REQUIRE(!byte_ranges_overlap(active, sk_bytes, trajs, in_bytes) && !byte_ranges_overlap(blocked, s_bytes, trajs, in_bytes),
               "traj select guide: an output aliases trajs");
-  ADX_REQUIRE(!overlaps(active, sk_bytes, cost, sk_bytes) && !overlaps(active, sk_bytes, index, s_bytes) &&
-                  !overlaps(active, sk_bytes, best, best_bytes) && !overlaps(active, sk_bytes, blocked, s_bytes) &&
-                  !overlaps(blocked, s_bytes, cost, sk_bytes) && !overlaps(blocked, s_bytes, index, s_bytes) &&
-                  !overlaps(blocked, s_bytes, best, best_bytes),
+  ADX_REQUIRE(!byte_ranges_overlap(active, sk_bytes, cost, sk_bytes) && !byte_ranges_overlap(active, sk_bytes, index, s_bytes) &&
+                  !byte_ranges_overlap(active, sk_bytes, best, best_bytes) && !byte_ranges_overlap(active, sk_bytes, blocked, s_bytes) &&
+                  !byte_ranges_overlap(blocked, s_bytes, cost, sk_bytes) && !byte_ranges_overlap(blocked, s_bytes, index, s_bytes) &&
+                  !byte_ranges_overlap(blocked, s_bytes, best, best_bytes),
               "traj select guide: outputs alias each other");
   a.trajs = trajs; a.target = target; a.cost = cost; a.index = index; a.best = best;
   a.scenes = S; a.K = K; a.H = c->horizon; a.D = c->dim;
   a.w_goal = c->w_goal; a.w_smooth = c->w_smooth; a.w_consensus = c->w_consensus;
   a.w_guide = c->w_guide; a.hard = c->hard != 0; a.active = active; a.blocked = blocked;
-  if (motion != nullptr) traj_select_kernel<true, true><<<dim3(S), dim3(256), 0, s>>>(a);
+  if (g.motion != nullptr) traj_select_kernel<true, true><<<dim3(S), dim3(256), 0, s>>>(a);
   else traj_select_kernel<true><<<dim3(S), dim3(256), 0, s>>>(a);
   ADX_LAUNCH_CHECK();
   return ADX_OK;

@@ -161,7 +161,7 @@ TABLE = [
     (dict(param_rows=0), "stop short: param_rows 0, at least 1"),
     (dict(B=0), "stop short: empty shape"), (dict(B=-3), "stop short: empty shape"),
     (dict(B=1 << 25, H=64, D=16), "stop short: 34359738368 elements do not fit the kernel's 32-bit index"),
-    # what guide_check, route_check and capsule_check (csrc/sched.h) refuse, under this launch's name
+    # what guide_records_check (csrc/sched.h) refuses, under this launch's name
     (dict(guide=dict(n_discs=33)), "stop short: n_discs 33 outside 0..32"),
     (dict(guide=dict(n_planes=-1)), "stop short: n_planes -1 outside 0..8"),
     (dict(guide=dict(discs=None)), "stop short: null discs with n_discs 2"),
@@ -179,6 +179,8 @@ TABLE = [
     (dict(route=dict(n_points=1)), "stop short: route of 1 points, supported 2..32"),
     (dict(route=dict(scene_rows=3)), "stop short: the route holds 3 scenes, the guide's discs and planes 2"),
     (dict(route={}, after=WIDTH + 4), "stop short: an output overlaps the route's points or half_width"),
+    (dict(route={}, status=POINTS + 2 * 3 * 2 * 4 - 4), "stop short: an output overlaps the route's points or half_width"),
+    (dict(route={}, status=POINTS + 2 * 3 * 2 * 4, after=STOP), OVER),                 # one byte past the points: the next refusal
     (dict(capsules=dict(capsules=None)), "stop short: null capsules"),
     (dict(capsules=dict(n_capsules=33)), "stop short: n_capsules 33 outside 1..32"),
     (dict(capsules=dict(weight=-1.0)), "stop short: capsule weight -1 is negative or NaN"),

@@ -3,8 +3,9 @@ for bit, element-wise (no limits) and row-wise (limits), with and without a fiel
 the C ABI's NULL capsule record against the exports of v1 to v4 bit for bit; a degenerate capsule against v1's disc; `Guide.cost`
 with capsules against the fp64 restatement within a bound derived from the contract; the guided selection; `Capsules.from_boxes`
 ("capsules from boxes v1") bit for bit; generate_traj(guide=Guide(capsules=...)) against the loop written out from public
-`scheduler.step(guide=...)` calls; and GraphedSampler replays.  No timing is asserted anywhere (tools/guide_tick_probe.py
-measures), and nothing here says what capsules do to driving quality.
+`scheduler.step(guide=...)` calls; GraphedSampler replays; and every record of a guide at once through every kernel that reads
+one.  No timing is asserted anywhere (tools/guide_tick_probe.py measures), and nothing here says what capsules do to driving
+quality.
 
 Shapes are the smallest at which this can go wrong: C in {1, 3, 32} (one slot, an empty and a degenerate one among three, the
 maximum), H in {1, 5, 64}, D in {2, 3, 7}, iters in {1, 8}, rows in {1, 5} and 6 rows over 2 scenes.  Every step launch is at most
@@ -18,11 +19,13 @@ import pytest
 import torch
 
 import capsule_ref as CR
+import fallback_ref as FB
 import pin_ref as R
+import select_guide_ref as V
 import test_gpu_guide as TG
 import test_gpu_pin as TP
 import test_gpu_route as TRT
-from autonomous_driving_with_diffusion_model_amd import Capsules, DeviceNoise, Guide, MotionLimits, TrajectorySelector
+from autonomous_driving_with_diffusion_model_amd import Capsules, CostField, DeviceNoise, Guide, MotionLimits, StopShort, TrajectorySelector
 from autonomous_driving_with_diffusion_model_amd import _lib as L
 from autonomous_driving_with_diffusion_model_amd.sampling import GraphedSampler, generate_traj
 
@@ -345,6 +348,121 @@ def test_the_guided_selection_sees_the_capsules():
     assert sel.active.tolist() == [[0, 1]] and sel.index.tolist() == [0] and sel.blocked.tolist() == [0]
     with pytest.raises(ValueError, match="the guide holds 1 scenes; the selection has 2"):
         TrajectorySelector(hard=True)(x, Sn, None, Guide(capsules=Capsules(slots[:1].to(DEV))))
+
+
+# ---- 5b. every record at once, in every consumer -------------------------------------------------------------------------------
+class Full(Inputs):
+    """`Inputs` at 6 rows over 2 scenes and D = 3 with every record of a guide at once, each active over a part of [-1, 1]^2 only:
+    2 discs (slot 1 of scene 0 empty), 1 plane, a 3 x 3 field that is 0 left of x = 0, the 3-point route with half-widths (0.25,
+    0.15), 2 capsules (the second of scene 1 with a == b) and the limits of test_gpu_motion."""
+    GEO = dict(origin=(-1.0, -1.0), cell=(1.0, 1.0))
+
+    def __init__(self, H, seed):
+        super().__init__(3, 2, H, 3, 2, seed, False)
+        g = torch.Generator().manual_seed(seed + 6000)
+        self.discs = torch.tensor([[[0.8, 0.0, -0.002, 0.001, 0.3], [0.1, 0.2, 0.0, 0.0, 0.0]],
+                                   [[0.7, -0.2, 0.001, 0.0, 0.35], [0.5, 0.6, 0.0, -0.001, 0.2]]])
+        self.planes = torch.tensor([[[1.0, 0.0, 0.85]], [[0.6, 0.8, 0.7]]])
+        self.cells = torch.zeros(2, 3, 3)
+        self.cells[:, :, 2] = torch.rand(2, 3, generator=g) + 0.1
+        self.points = torch.tensor([[[-0.9, -0.1], [0.0, 0.1], [0.9, -0.1]], [[-0.9, 0.05], [0.1, -0.1], [0.9, 0.1]]])
+        self.widths = torch.tensor([0.25, 0.15])
+        self.slots = torch.tensor([[[0.5, -0.3, 0.7, 0.3, -0.002, 0.0, 0.15], [-0.2, 0.6, 0.2, 0.6, 0.0, -0.001, 0.1]],
+                                   [[0.4, 0.3, 0.6, -0.3, 0.0, 0.002, 0.15], [0.3, 0.0, 0.3, 0.0, 0.001, 0.0, 0.2]]])
+        self.d = {k: v.to(DEV) for k, v in vars(self).items() if torch.is_tensor(v)}
+
+    def field(self):
+        return CostField(self.d["cells"], weight=TRT.WEIGHT, **self.GEO)
+
+    def ref_field(self):
+        return TRT.FR.field(self.cells, weight=TRT.WEIGHT, **self.GEO)
+
+    def guide(self, limits=False, **kw):
+        return Guide(self.d["discs"], self.d["planes"], field=self.field(), motion=self.motion(limits), route=self.route(),
+                     capsules=self.caps(), **kw)
+
+    def ref(self, lam, cap, iters):
+        return dict(discs=self.discs, planes=self.planes, lam=lam, cap=cap, iters=iters)
+
+    def plans(self):
+        """[6, H, 3]: rows that start at x = -0.9 left of everything but the route and cross [-0.9, 0.9] at heights -0.25 .. 0.25, so
+        that a row meets the field, a disc, a capsule or the plane somewhere along it and some rows leave the corridor at once.
+        Rows 1 and 4 (one of each scene) jump sideways by 0.35 at the middle waypoint and back: past both limits of either scene
+        at any H, where the even spacing of a long row is under them."""
+        H = self.x.shape[1]
+        t = torch.zeros(6, H, 3)
+        t[:, :, 0] = -0.9 + 1.8 * torch.arange(H, dtype=torch.float32) / max(H - 1, 1)
+        t[:, :, 1] = torch.linspace(-0.25, 0.25, 6)[:, None] + 0.05 * torch.sin(torch.arange(H, dtype=torch.float32))[None, :]
+        t[1::3, H // 2, 1] += 0.35
+        t[:, :, 2] = 0.3
+        return t
+
+
+def _every_term_binds(inp, pts, limits):
+    """Each record alone has an active term somewhere on `pts` [6, H, >= 2], by the restatement, and the records' counts add up to
+    the count under all of them: a consumer that left a record out could not match the restatement of these points bit for bit."""
+    f, r, c, m = inp.ref_field(), inp.ref_route(), inp.ref_caps(), inp.ref_motion(limits)
+    alone = dict(discs=(inp.discs, None, None, None, None, None), planes=(None, inp.planes, None, None, None, None),
+                 field=(None, None, f, None, None, None), route=(None, None, None, r, None, None),
+                 capsules=(None, None, None, None, c, None))
+    if limits:
+        alone["limits"] = (None, None, None, None, None, m)
+    counts = {k: CR.row_cost(pts, *a, np.float32)[1] for k, a in alone.items()}
+    assert all(int(n.sum()) > 0 for n in counts.values()), {k: n.tolist() for k, n in counts.items()}
+    assert np.array_equal(sum(counts.values()), CR.row_cost(pts, inp.discs, inp.planes, f, r, c, m, np.float32)[1])
+
+
+@pytest.mark.parametrize("H", [5, 64])
+def test_every_consumer_with_every_record_at_once(H):
+    """Discs, planes, a field, a route and capsules in one launch, plus limits where the consumer takes them: the element-wise and
+    the row-wise step of DDIM and of DPM-Solver++ (2 iterations), the cost with and without limits, the selection with and without
+    limits and the stop-short fallback, each against the restatement on the int32 view, on inputs where each record alone has an
+    active term (`_every_term_binds`).  What the other cases leave out: the step
+    cases above and test_gpu_route's reach every record but planes (test_gpu_guide and test_gpu_field hold the planes, beside discs
+    and a field); the cost meets all records but planes with limits only, and without limits one record at a time; the selection
+    (here and in test_gpu_field, test_gpu_motion, test_gpu_route, test_gpu_select_guide) and the fallback (test_gpu_fallback) meet
+    discs with planes, or one other record alone."""
+    inp = Full(H, 2100 + H)
+    f, r, c = inp.ref_field(), inp.ref_route(), inp.ref_caps()
+    noise = DeviceNoise(21, DEV)
+    noise.begin_tick()
+    knobs = (0.05, "constant", 0.25, 2)
+    kw = dict(scale=knobs[0], schedule=knobs[1], cap=knobs[2], iters=knobs[3])
+    moved = 0
+    for case, limits in itertools.product((STEP_CASES[0], STEP_CASES[-1]), (False, True)):
+        q = TG._sched(case[1], "sample", True)
+        w = case[5][0]
+        guide = inp.guide(limits=limits, **kw)
+        suffix, refs, _alive = guide.descs(inp.d["x"])
+        assert suffix == "capsule" and [ref is not None for ref in refs] == [True, True, limits, True, True]
+        prev, x0, hist = TG._gpu_step(case, q, inp, w, None, guide, None, False, noise)
+        want_prev, want_x0, _ = _ref_step(inp, limits, True, case, q, inp, w, "sample", True, knobs, False, None, False, None, hist)
+        assert _same(x0, want_x0) and _same(prev, want_prev), (case[0], limits, (prev.cpu() - want_prev).abs().max().item())
+        _every_term_binds(inp, TG._ref_step(case, q, inp, w, "sample", True, None, False, None, False, None, hist)[1], limits)      # the x0 the iterations start from
+        moved += int(not torch.equal(x0, TG._gpu_step(case, q, inp, w, None, None, None, False, noise)[1]))
+    assert moved == 4
+    traj = inp.plans()
+    x = traj.to(DEV)
+    for limits in (False, True):
+        m = inp.ref_motion(limits)
+        guide = inp.guide(limits=limits)
+        cost, active = guide.cost(x)
+        want_active = CR.row_cost(traj, inp.discs, inp.planes, f, r, c, m, np.float32)[1]
+        assert np.array_equal(cost.cpu().numpy().view(np.int32), CR.row_cost_wave(traj, inp.discs, inp.planes, f, r, c, m).view(np.int32))
+        assert np.array_equal(active.cpu().numpy(), want_active), limits
+        _every_term_binds(inp, traj, limits)      # the cost's and the selection's rows; without limits the fallback's too
+        sel = TrajectorySelector(0.0, 0.0, 0.0, w_guide=1.0, hard=True)(x, 2, None, guide)
+        assert torch.equal(_bits(sel.cost), _bits(cost.view(3, 2).t().contiguous())), limits
+        assert torch.equal(sel.active, active.view(3, 2).t().contiguous()), limits
+        index, blocked = V.pick(sel.cost.cpu().numpy(), sel.active.cpu().numpy() == 0, True)
+        assert sel.index.tolist() == index.tolist() and sel.blocked.tolist() == blocked.tolist(), limits
+        assert all(torch.equal(_bits(sel.best[s]), _bits(x[int(index[s]) * 2 + s])) for s in range(2)), limits
+    params = torch.tensor([[0.05, 0.01], [0.0, math.inf]])
+    want = FB.stop_short(traj.numpy(), FB.guide(inp.discs, inp.planes, f, r, c), params.numpy(), np.float32)
+    got = StopShort(params.to(DEV))(x, inp.guide())
+    assert len(set(want["first"].tolist())) >= 3 and want["first"].min() == 0 and 1 < want["first"].max() < H, want["first"]
+    for name, a in (("out", got.traj), ("first", got.first), ("status", got.status), ("stop_at", got.stop_at), ("active_after", got.active_after)):
+        assert np.array_equal(a.cpu().numpy().view(np.int32), np.ascontiguousarray(want[name]).view(np.int32)), name
 
 
 # ---- 6. capsules from boxes -------------------------------------------------------------------------------------------------------

@@ -274,6 +274,45 @@ def test_refusal_text(built, row):
     assert (_call(built, row[0]), built.lib().adx_last_error().decode()) == (-1, row[1]), row[0]
 
 
+CELLS, LIMITS, POINTS, WIDTH, CAPS = (0x10000000 * (i + 10) for i in range(5))
+# (overrides of a good adx_traj_select_guide_capsule call with every record beside the guide, the text): the outputs the records'
+# shared check did not see before it took all five -- index, blocked and best -- against each later record's arrays
+RECORD_TABLE = [
+    (dict(index=CELLS + 2 * 3 * 5 * 4 - 4), P2 + "an output overlaps the field's cells"),
+    (dict(blocked=CELLS), P2 + "an output overlaps the field's cells"),
+    (dict(best=LIMITS - 2 * ROW + 4), P2 + "an output overlaps the motion limits"),
+    (dict(index=LIMITS + 12), P2 + "an output overlaps the motion limits"),
+    (dict(blocked=POINTS + 2 * 4 * 2 * 4 - 4), P2 + "an output overlaps the route's points or half_width"),
+    (dict(best=WIDTH + 4), P2 + "an output overlaps the route's points or half_width"),
+    (dict(index=CAPS), P2 + "an output overlaps the capsules"),
+    (dict(best=CAPS + 2 * 3 * 7 * 4 - 4), P2 + "an output overlaps the capsules"),
+    # one byte short of each array is no overlap: the call goes on to the next refusal, the selection's own
+    (dict(index=CELLS + 2 * 3 * 5 * 4, blocked=BEST), P2 + "outputs alias each other"),
+    (dict(blocked=CAPS - 8, active=TRAJS), P2 + "an output aliases trajs"),
+]
+
+
+@pytest.mark.parametrize("row", RECORD_TABLE, ids=lambda row: ",".join("%s=%#x" % kv for kv in row[0].items()))
+def test_refusal_text_of_the_later_outputs_against_every_record(built, row):
+    L = built
+    a = dict(cost=COST, active=ACTIVE, index=INDEX, blocked=BLOCKED, best=BEST)
+    a.update(row[0])
+    cfg = L.SelectGuideCfg(2, 4, 16, 7, 1.0, 0.5, 0.25, 2.0, 1)
+    recs = []
+    for cls, fields in ((L.GuideDesc, dict(discs=DISCS, planes=PLANES, scene_rows=2, n_discs=3, n_planes=2)),
+                        (L.FieldDesc, dict(cells=CELLS, scene_rows=2, gy=3, gx=5, inv_dx=1.0, inv_dy=1.0, weight=1.0)),
+                        (L.MotionDesc, dict(limits=LIMITS, scene_rows=2, w_speed=1.0, w_accel=0.5)),
+                        (L.RouteDesc, dict(points=POINTS, half_width=WIDTH, scene_rows=2, n_points=4, weight=1.0)),
+                        (L.CapsuleDesc, dict(capsules=CAPS, scene_rows=2, n_capsules=3, weight=1.0))):
+        rec = cls()
+        for k, v in fields.items():
+            setattr(rec, k, v)
+        recs.append(rec)
+    got = L.lazy("adx_traj_select_guide_capsule")(ctypes.byref(cfg), TRAJS, TARGET, *[ctypes.byref(r) for r in recs], a["cost"], a["active"],
+                                                  a["index"], a["blocked"], a["best"], None)
+    assert (got, L.lib().adx_last_error().decode()) == (-1, row[1]), row[0]
+
+
 def test_python_surface_checks_the_guide_before_any_launch(built):
     sel = TrajectorySelector(hard=True)
     with pytest.raises(built.AdxError):
