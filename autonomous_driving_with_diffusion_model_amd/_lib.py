@@ -242,60 +242,23 @@ _LAZY_SIGS = {
     "adx_ddpm_step_pin": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), vp, vp, i32, i32, i32, vp]),
     "adx_dpm_step_pin": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), vp, vp, i32, i32, i32, vp]),
     "adx_pin_apply": (i32, [vp, C.POINTER(PinDesc), vp, i64, i32, i32, i32, vp]),
-    "adx_ddim_step_guide": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc), vp, vp,
-                                  i32, i32, i32, vp]),
-    "adx_ddpm_step_guide": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc), vp, vp,
-                                  i32, i32, i32, vp]),
-    "adx_dpm_step_guide": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc), vp, vp,
-                                 i32, i32, i32, vp]),
-    "adx_guide_cost": (i32, [vp, C.POINTER(GuideDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_traj_select_guide": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), vp, vp, vp, vp, vp, vp]),
-    "adx_ddim_step_field": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                  C.POINTER(FieldDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_ddpm_step_field": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                  C.POINTER(FieldDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_dpm_step_field": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                 C.POINTER(FieldDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_guide_cost_field": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_traj_select_guide_field": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), vp, vp, vp, vp,
-                                          vp, vp]),
     "adx_cost_field_from_occupancy": (i32, [vp, vp, i32, i32, i32, f32, f32, f32, i32, i32, vp]),
-    "adx_ddim_step_motion": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                   C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_ddpm_step_motion": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                   C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_dpm_step_motion": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                  C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_guide_cost_motion": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(MotionDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_traj_select_guide_motion": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
-                                           C.POINTER(MotionDesc), vp, vp, vp, vp, vp, vp]),
-    "adx_ddim_step_route": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                  C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_ddpm_step_route": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                  C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_dpm_step_route": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                 C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_guide_cost_route": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp,
-                                   i32, i32, i32, vp]),
-    "adx_traj_select_guide_route": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
-                                          C.POINTER(MotionDesc), C.POINTER(RouteDesc), vp, vp, vp, vp, vp, vp]),
-    "adx_ddim_step_capsule": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                    C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp,
-                                    i32, i32, i32, vp]),
-    "adx_ddpm_step_capsule": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                    C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp,
-                                    i32, i32, i32, vp]),
-    "adx_dpm_step_capsule": (i32, [C.POINTER(DpmCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), C.POINTER(GuideDesc),
-                                   C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp,
-                                   i32, i32, i32, vp]),
-    "adx_guide_cost_capsule": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(MotionDesc), C.POINTER(RouteDesc),
-                                     C.POINTER(CapsuleDesc), vp, vp, i32, i32, i32, vp]),
-    "adx_traj_select_guide_capsule": (i32, [C.POINTER(SelectGuideCfg), vp, vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc),
-                                            C.POINTER(MotionDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, vp, vp, vp, vp, vp]),
     "adx_capsules_from_boxes": (i32, [vp, vp, i32, i32, f32, vp]),
     "adx_stop_short": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, i32, vp, vp,
                              vp, vp, vp, i32, i32, i32, vp]),
 }
+
+# the guided exports: five families (the three steps, the cost, the guided selection) times five suffixes, each suffix taking the
+# record of the one before it and one more -- the order of guide.py's RECORDS, which names the suffixes
+_records = ()
+for _suffix, _desc in (("guide", GuideDesc), ("field", FieldDesc), ("motion", MotionDesc), ("route", RouteDesc), ("capsule", CapsuleDesc)):
+    _records += (C.POINTER(_desc),)
+    for _step, _coef in (("ddim", StepCoef), ("ddpm", StepCoef), ("dpm", DpmCoef)):
+        _LAZY_SIGS[f"adx_{_step}_step_{_suffix}"] = (i32, [C.POINTER(_coef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), *_records,
+                                                          vp, vp, i32, i32, i32, vp])
+    _tail = "" if _suffix == "guide" else "_" + _suffix
+    _LAZY_SIGS["adx_guide_cost" + _tail] = (i32, [vp, *_records, vp, vp, i32, i32, i32, vp])
+    _LAZY_SIGS["adx_traj_select_guide" + _tail] = (i32, [C.POINTER(SelectGuideCfg), vp, vp, *_records, vp, vp, vp, vp, vp, vp])
 
 EXPORTED_SYMBOLS = tuple(_SIGS) + tuple(_LAZY_SIGS)
 

@@ -4,8 +4,8 @@
 guidance pushes samples away from obstacles and a hard selection prefers a free candidate, but neither promises that the plan a
 tick ends with is free; every sampling planner keeps a deterministic last resort for that case: keep the path, change the speed
 profile, stop short of the first conflict.  The launch keeps the plan's geometry, finds its first waypoint that conflicts with the
-guide's point-wise terms (discs, planes, field, route, capsules -- motion limits are not places) and moves the waypoints along the
-plan's own polyline so that the spacing shrinks by at most `decel` per waypoint and the last one rests `gap` before the
+guide's point-wise terms (discs, planes and the records guide.py declares POINTWISE -- motion limits are not places) and moves
+the waypoints along the plan's own polyline so that the spacing shrinks by at most `decel` per waypoint and the last one rests `gap` before the
 conflict.  `DeviceController` takes its desired speed from that spacing, so the re-timed plan brakes through the controller as it
 is.  No host decision and no synchronisation, so the call can be a node of a captured graph
 (`GraphedSampler(..., fallback=...)`).  No reference counterpart.
@@ -128,9 +128,9 @@ class StopShort:
         status = torch.empty(rows, dtype=torch.int32, device=traj.device)
         stop_at = torch.empty(rows, dtype=torch.float32, device=traj.device)
         after = torch.empty(rows, dtype=torch.int32, device=traj.device)
-        f, r, c = guide.field_desc(traj), guide.route_desc(traj), guide.capsule_desc(traj)
-        L.check(L.lazy("adx_stop_short")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f), None if r is None else C.byref(r),
-                                         None if c is None else C.byref(c), params.data_ptr(), self.scenes, out.data_ptr(),
+        records = [None if r is None else r.desc(traj) for r in guide.pointwise()]      # kept alive until the launch is enqueued
+        L.check(L.lazy("adx_stop_short")(traj.data_ptr(), C.byref(g), *(None if d is None else C.byref(d) for d in records),
+                                         params.data_ptr(), self.scenes, out.data_ptr(),
                                          first.data_ptr(), status.data_ptr(), stop_at.data_ptr(), after.data_ptr(), rows, H, D,
                                          L.stream_ptr(traj.device)), "adx_stop_short")
         return StopResult(out, first, status, stop_at, after)
@@ -141,4 +141,4 @@ class StopShort:
 
 def pointwise(guide: Guide) -> bool:
     """Whether the guide holds a term that names places: discs, planes, a field, a route or capsules (motion limits do not)."""
-    return guide.M > 0 or guide.P > 0 or guide.field is not None or guide.route is not None or guide.capsules is not None
+    return guide.M > 0 or guide.P > 0 or any(r is not None for r in guide.pointwise())

@@ -7,9 +7,8 @@ model's own units (the clamped trajectory before xy scaling).  No reference coun
 draws many trajectories for one image only to paint them (train.py:62-90).
 
 Given a `Guide` the call is one launch of `adx_traj_select_guide` instead ("selection cost v2"): the same three terms plus
-`w_guide` times what a candidate still violates of the scene's discs and planes -- and of its field, motion limits, route
-corridor and moving capsules, when the guide holds them; a candidate one ulp over a limit, outside the corridor or inside a capsule
-is "not free", there is no separate tolerance -- (bit for bit `Guide.cost` of
+`w_guide` times what a candidate still violates of the scene's discs and planes -- and of every record the guide holds (guide.py,
+RECORDS); a candidate one ulp into a violation is "not free", there is no separate tolerance -- (bit for bit `Guide.cost` of
 its row), and, with `hard`, the rule that a candidate which violates nothing beats every candidate that violates something.  `Selection.active` then
 holds every candidate's count of violated (waypoint, constraint) pairs and `Selection.blocked` says per scene whether the chosen
 plan still violates something -- on the device, where a later node can read it.
@@ -95,8 +94,7 @@ class TrajectorySelector:
         active = torch.empty((scenes, K), dtype=torch.int32, device=dev)
         blocked = torch.empty((scenes,), dtype=torch.int32, device=dev)
         cfg = L.SelectGuideCfg(scenes, K, H, D, self.w_goal, self.w_smooth, self.w_consensus, self.w_guide, int(self.hard))
-        # a field: "cost guidance v2" in the same launch, through the _field export; motion limits: v3, through the _motion export;
-        # a route: v4, through the _route export; capsules: v5, through the _capsule export
+        # the guide's records ride in the same launch, through the export guide.py's `Guide.descs` chooses for them
         suffix, guides, _alive = guide.descs(trajs)      # device, float32 and D >= 2 as every guided launch checks them
         name = "adx_traj_select_guide" + ("" if suffix == "guide" else "_" + suffix)
         L.check(L.lazy(name)(C.byref(cfg), trajs.data_ptr(), L.ptr(target), *guides, cost.data_ptr(), active.data_ptr(),

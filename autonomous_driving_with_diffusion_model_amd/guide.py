@@ -44,6 +44,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 from typing import Optional, Tuple
 
 import torch
@@ -92,12 +93,60 @@ def _raster(t, what: str) -> None:
         raise TypeError(f"CostField: {what} must be float32, got {t.dtype}")
 
 
-class CostField:
+class _Record:
+    """What the record classes of a guide share.  Each declares, as class attributes, what `Guide` and its consumers walk (RECORDS
+    below holds the classes in version order, the order of the exports' arguments):
+
+        ATTR       its attribute of a Guide, the keyword of `Guide.__init__` and `Guide.like`
+        NOUN       what a refusal about it calls it ("the field"); EARLIER: what a refusal about a later record calls it ("field")
+        SUFFIX     of the exports whose last record it is (`adx_ddim_step_<SUFFIX>`, ...)
+        POINTWISE  whether its term names places (the stop-short fallback looks for those)
+        TENSORS    the names of its tensors, in the order `like` takes them; the first, the lead tensor, says how many scenes the
+                   record holds and where they live
+    """
+    ATTR = NOUN = EARLIER = SUFFIX = ""
+    POINTWISE = False
+    TENSORS: Tuple[str, ...] = ()
+
+    def __init_subclass__(cls):
+        cls._PATHS = tuple((name, f"guide.{cls.ATTR}.{name}") for name in cls.TENSORS)      # what a refusal calls each tensor
+
+    @property
+    def lead(self) -> torch.Tensor:
+        return getattr(self, self.TENSORS[0])
+
+    @property
+    def scenes(self) -> int:
+        return int(self.lead.shape[0])
+
+    @property
+    def device(self) -> torch.device:
+        return self.lead.device
+
+    def tensors(self) -> tuple:
+        """((name, tensor), ...) in the order of TENSORS."""
+        return tuple((name, getattr(self, name)) for name in self.TENSORS)
+
+    def clone(self):
+        """The same settings over clones of the tensors."""
+        return self.like(*(t.clone() for _, t in self.tensors()))
+
+    def _on_device_of(self, x: torch.Tensor) -> None:
+        """Every tensor a float32 GPU tensor on the device of the sample `x`, or a refusal."""
+        dev = x.device                      # this runs on every step of an eager tick
+        for name, path in self._PATHS:
+            t = getattr(self, name)
+            if L.require_gpu_f32(t, path).device != dev:
+                raise ValueError(f"{path} lives on {t.device}, the sample on {dev}")
+
+
+class CostField(_Record):
     """The field of "cost guidance v2" (include/adx.h): `cells` float32 `[S, Gy, Gx]`, 2 <= Gy, Gx <= 256, node `[i][j]` at
     `(x_min + j * dx, y_min + i * dy)` in the model's units and this tick's ego frame; `origin` = (x_min, y_min), `cell` =
     (dx, dy), `weight` >= 0.  A waypoint inside the raster pays `weight` times the bilinear interpolant where that is positive;
     outside the raster the field says nothing (add planes for "off the map is forbidden").  The cells are read at every step:
     new values need no new object (and, in a GraphedSampler, no new capture); shape, geometry and weight are baked."""
+    ATTR, NOUN, EARLIER, SUFFIX, POINTWISE, TENSORS = "field", "the field", "field", "field", True, ("cells",)
 
     def __init__(self, cells: torch.Tensor, origin=(0.0, 0.0), cell=(1.0, 1.0), weight: float = 1.0):
         _raster(cells, "cells")
@@ -106,14 +155,6 @@ class CostField:
         if not weight >= 0.0:
             raise ValueError(f"CostField: weight must be >= 0, got {weight}")
         self.cells, self.weight = cells.contiguous(), weight
-
-    @property
-    def scenes(self) -> int:
-        return int(self.cells.shape[0])
-
-    @property
-    def device(self) -> torch.device:
-        return self.cells.device
 
     def key(self) -> tuple:
         """What a captured graph bakes: everything but the values of the cells."""
@@ -126,10 +167,10 @@ class CostField:
     def desc(self, x: torch.Tensor) -> L.FieldDesc:
         """The `adx_guide_field` of a launch on `x` [B, H, D].  The struct holds an address: keep this object alive until the
         launch is enqueued."""
-        if L.require_gpu_f32(self.cells, "guide.field.cells").device != x.device:
-            raise ValueError(f"guide.field.cells lives on {self.cells.device}, the sample on {x.device}")
+        self._on_device_of(x)
         f = L.FieldDesc()
-        f.cells, f.scene_rows, f.gy, f.gx = self.cells.data_ptr(), self.scenes, int(self.cells.shape[1]), int(self.cells.shape[2])
+        S, Gy, Gx = self.cells.shape
+        f.cells, f.scene_rows, f.gy, f.gx = self.cells.data_ptr(), S, Gy, Gx
         f.x_min, f.y_min, f.inv_dx, f.inv_dy, f.weight = self.x_min, self.y_min, 1.0 / self.dx, 1.0 / self.dy, self.weight
         return f
 
@@ -168,7 +209,7 @@ class CostField:
                 f"weight={self.weight})")
 
 
-class MotionLimits:
+class MotionLimits(_Record):
     """The motion limits of "cost guidance v3" (include/adx.h): `limits` float32 `[S, 2]` = per scene `(s_max, a_max)` in the
     model's own units (the clamped result before xy scaling) per waypoint interval.  `s_max` caps the length of a segment
     `|p[i+1] - p[i]|`, `a_max` the length of a second difference `|p[i+1] - 2 p[i] + p[i-1]|`; `inf` switches a term off for that
@@ -181,6 +222,7 @@ class MotionLimits:
 
     With `TrajectorySelector(hard=True)` the limits inherit v1's property: a candidate that sits one ulp over a limit is "not
     free".  A separate tolerance for selection does not exist."""
+    ATTR, NOUN, EARLIER, SUFFIX, POINTWISE, TENSORS = "motion", "the motion limits", "motion limits", "motion", False, ("limits",)
 
     def __init__(self, limits: torch.Tensor, w_speed: float = 1.0, w_accel: float = 1.0):
         if not torch.is_tensor(limits):
@@ -195,14 +237,6 @@ class MotionLimits:
                 raise ValueError(f"MotionLimits: {name} must be >= 0, got {w}")
         self.limits, self.w_speed, self.w_accel = limits.contiguous(), w_speed, w_accel
 
-    @property
-    def scenes(self) -> int:
-        return int(self.limits.shape[0])
-
-    @property
-    def device(self) -> torch.device:
-        return self.limits.device
-
     def key(self) -> tuple:
         """What a captured graph bakes: everything but the values of the limits."""
         return (self.w_speed, self.w_accel)
@@ -214,10 +248,9 @@ class MotionLimits:
     def desc(self, x: torch.Tensor) -> L.MotionDesc:
         """The `adx_guide_motion` of a launch on `x` [B, H, D].  The struct holds an address: keep this object alive until the
         launch is enqueued."""
-        if L.require_gpu_f32(self.limits, "guide.motion.limits").device != x.device:
-            raise ValueError(f"guide.motion.limits lives on {self.limits.device}, the sample on {x.device}")
+        self._on_device_of(x)
         m = L.MotionDesc()
-        m.limits, m.scene_rows, m.w_speed, m.w_accel = self.limits.data_ptr(), self.scenes, self.w_speed, self.w_accel
+        m.limits, m.scene_rows, m.w_speed, m.w_accel = self.limits.data_ptr(), self.limits.shape[0], self.w_speed, self.w_accel
         return m
 
     @staticmethod
@@ -246,7 +279,7 @@ class MotionLimits:
         return f"MotionLimits(limits={tuple(self.limits.shape)}, w_speed={self.w_speed}, w_accel={self.w_accel})"
 
 
-class Route:
+class Route(_Record):
     """The route corridor of "cost guidance v4" (include/adx.h): `points` float32 `[S, R, 2]` = per scene a polyline of R points
     (x, y), 2 <= R <= 32, in the model's own units (the clamped result before xy scaling) and THIS tick's ego frame; segment i
     joins point i and point i + 1, and a scene with fewer points pads by repeating its last one.  `half_width` float32 `[S]`, or a
@@ -258,6 +291,7 @@ class Route:
     at every step: new values need no new object (and, in a GraphedSampler, no new capture); R and the weight are baked.
 
     With `TrajectorySelector(hard=True)` a candidate that leaves the corridor, by one ulp, is "not free"."""
+    ATTR, NOUN, EARLIER, SUFFIX, POINTWISE, TENSORS = "route", "the route", "route", "route", True, ("points", "half_width")
 
     def __init__(self, points: torch.Tensor, half_width, weight: float = 1.0):
         if not torch.is_tensor(points):
@@ -286,16 +320,8 @@ class Route:
         self.points, self.half_width, self.weight = points.contiguous(), half_width.contiguous(), weight
 
     @property
-    def scenes(self) -> int:
-        return int(self.points.shape[0])
-
-    @property
     def R(self) -> int:
         return int(self.points.shape[1])
-
-    @property
-    def device(self) -> torch.device:
-        return self.points.device
 
     def key(self) -> tuple:
         """What a captured graph bakes: everything but the values of the points and widths."""
@@ -308,12 +334,10 @@ class Route:
     def desc(self, x: torch.Tensor) -> L.RouteDesc:
         """The `adx_guide_route` of a launch on `x` [B, H, D].  The struct holds addresses: keep this object alive until the
         launch is enqueued."""
-        for name, t in (("guide.route.points", self.points), ("guide.route.half_width", self.half_width)):
-            if L.require_gpu_f32(t, name).device != x.device:
-                raise ValueError(f"{name} lives on {t.device}, the sample on {x.device}")
+        self._on_device_of(x)
         r = L.RouteDesc()
         r.points, r.half_width = self.points.data_ptr(), self.half_width.data_ptr()
-        r.scene_rows, r.n_points, r.weight = self.scenes, self.R, self.weight
+        r.scene_rows, r.n_points, r.weight = self.points.shape[0], self.points.shape[1], self.weight
         return r
 
     @staticmethod
@@ -343,7 +367,7 @@ class Route:
         return f"Route(points={tuple(self.points.shape)}, half_width={tuple(self.half_width.shape)}, weight={self.weight})"
 
 
-class Capsules:
+class Capsules(_Record):
     """The moving capsules of "cost guidance v5" (include/adx.h): `slots` float32 `[S, C, 7]` = per scene C slots
     `(ax, ay, bx, by, vx, vy, r)`, 1 <= C <= 32, in the model's own units (the clamped result before xy scaling) and THIS tick's
     ego frame: the segment from a to b with radius r, both ends moving by `(vx, vy)` per waypoint.  A waypoint closer than r to
@@ -355,6 +379,7 @@ class Capsules:
     `Capsules.from_boxes` makes the slots from oriented boxes in one launch ("capsules from boxes v1"); the capsule is a box's
     INSCRIBED stadium, so its corners stick out by up to `(sqrt(2) - 1) * width / 2`: cover that, and the ego's own radius, with
     `inflate`.  With `TrajectorySelector(hard=True)` a candidate inside a capsule, by one ulp, is "not free"."""
+    ATTR, NOUN, EARLIER, SUFFIX, POINTWISE, TENSORS = "capsules", "the capsules", "capsules", "capsule", True, ("slots",)
 
     def __init__(self, slots: torch.Tensor, weight: float = 1.0):
         if not torch.is_tensor(slots):
@@ -371,16 +396,8 @@ class Capsules:
         self.slots, self.weight = slots.contiguous(), weight
 
     @property
-    def scenes(self) -> int:
-        return int(self.slots.shape[0])
-
-    @property
     def C(self) -> int:
         return int(self.slots.shape[1])
-
-    @property
-    def device(self) -> torch.device:
-        return self.slots.device
 
     def key(self) -> tuple:
         """What a captured graph bakes: everything but the values of the slots."""
@@ -393,10 +410,9 @@ class Capsules:
     def desc(self, x: torch.Tensor) -> L.CapsuleDesc:
         """The `adx_guide_capsules` of a launch on `x` [B, H, D].  The struct holds an address: keep this object alive until the
         launch is enqueued."""
-        if L.require_gpu_f32(self.slots, "guide.capsules.slots").device != x.device:
-            raise ValueError(f"guide.capsules.slots lives on {self.slots.device}, the sample on {x.device}")
+        self._on_device_of(x)
         c = L.CapsuleDesc()
-        c.capsules, c.scene_rows, c.n_capsules, c.weight = self.slots.data_ptr(), self.scenes, self.C, self.weight
+        c.capsules, c.scene_rows, c.n_capsules, c.weight = self.slots.data_ptr(), self.slots.shape[0], self.slots.shape[1], self.weight
         return c
 
     @staticmethod
@@ -467,10 +483,16 @@ class Capsules:
         return f"Capsules(slots={tuple(self.slots.shape)}, weight={self.weight})"
 
 
+RECORDS = (CostField, MotionLimits, Route, Capsules)        # version order: the order of the exports' arguments and suffixes
+_records_of = operator.attrgetter(*(kind.ATTR for kind in RECORDS))
+
+
 class Guide:
     """`discs` float32 `[S, M, 5]` and / or `planes` float32 `[S, P, 3]` on one device (None: no such constraint); `scale`,
     `schedule`, `cap`, `iters` as the module docstring says; `field`: a CostField or None, `motion`: a MotionLimits or None,
-    `route`: a Route or None, `capsules`: a Capsules or None (all keyword only).  The tensors are read at every step: new values need no new object (and, in a GraphedSampler, no new capture)."""
+    `route`: a Route or None, `capsules`: a Capsules or None (all keyword only; RECORDS holds their classes in this order, and
+    everything below that treats the records alike walks it).  The tensors are read at every step: new values need no new object
+    (and, in a GraphedSampler, no new capture)."""
 
     def __init__(self, discs: Optional[torch.Tensor] = None, planes: Optional[torch.Tensor] = None, scale: float = 1.0,
                  schedule: str = "variance", cap: float = float("inf"), iters: int = 1, *, field: Optional[CostField] = None,
@@ -491,51 +513,19 @@ class Guide:
                 raise ValueError(f"Guide: discs live on {discs.device}, planes on {planes.device}")
             if discs.shape[0] != planes.shape[0]:
                 raise ValueError(f"Guide: discs hold {discs.shape[0]} scenes, planes {planes.shape[0]}")
-        if field is not None:
-            if not isinstance(field, CostField):
-                raise TypeError(f"Guide: field must be a CostField or None, got {type(field).__name__}")
-            for name, t in (("discs", discs), ("planes", planes)):
-                if t is None or t.shape[1] == 0:      # no constraint of this kind: nothing to agree with
-                    continue
-                if t.device != field.device:
-                    raise ValueError(f"Guide: {name} live on {t.device}, the field on {field.device}")
-                if t.shape[0] != field.scenes:
-                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the field {field.scenes}")
-        if motion is not None:
-            if not isinstance(motion, MotionLimits):
-                raise TypeError(f"Guide: motion must be a MotionLimits or None, got {type(motion).__name__}")
-            others = (("discs", discs), ("planes", planes), ("field", None if field is None else field.cells))
-            for name, t in others:
-                if t is None or (name != "field" and t.shape[1] == 0):
-                    continue
-                if t.device != motion.device:
-                    raise ValueError(f"Guide: {name} live on {t.device}, the motion limits on {motion.device}")
-                if t.shape[0] != motion.scenes:
-                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the motion limits {motion.scenes}")
-        if route is not None:
-            if not isinstance(route, Route):
-                raise TypeError(f"Guide: route must be a Route or None, got {type(route).__name__}")
-            others = (("discs", discs), ("planes", planes), ("field", None if field is None else field.cells),
-                      ("motion limits", None if motion is None else motion.limits))
-            for name, t in others:
-                if t is None or (name in ("discs", "planes") and t.shape[1] == 0):
-                    continue
-                if t.device != route.device:
-                    raise ValueError(f"Guide: {name} live on {t.device}, the route on {route.device}")
-                if t.shape[0] != route.scenes:
-                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the route {route.scenes}")
-        if capsules is not None:
-            if not isinstance(capsules, Capsules):
-                raise TypeError(f"Guide: capsules must be a Capsules or None, got {type(capsules).__name__}")
-            others = (("discs", discs), ("planes", planes), ("field", None if field is None else field.cells),
-                      ("motion limits", None if motion is None else motion.limits), ("route", None if route is None else route.points))
-            for name, t in others:
-                if t is None or (name in ("discs", "planes") and t.shape[1] == 0):
-                    continue
-                if t.device != capsules.device:
-                    raise ValueError(f"Guide: {name} live on {t.device}, the capsules on {capsules.device}")
-                if t.shape[0] != capsules.scenes:
-                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, the capsules {capsules.scenes}")
+        # each record agrees with everything before it: the discs and planes that hold a constraint, then the earlier records
+        earlier = [(name, t) for name, t in (("discs", discs), ("planes", planes)) if t is not None and t.shape[1] > 0]
+        for kind, rec in zip(RECORDS, (field, motion, route, capsules)):
+            if rec is None:
+                continue
+            if not isinstance(rec, kind):
+                raise TypeError(f"Guide: {kind.ATTR} must be a {kind.__name__} or None, got {type(rec).__name__}")
+            for name, t in earlier:
+                if t.device != rec.device:
+                    raise ValueError(f"Guide: {name} live on {t.device}, {kind.NOUN} on {rec.device}")
+                if t.shape[0] != rec.scenes:
+                    raise ValueError(f"Guide: {name} hold {t.shape[0]} scenes, {kind.NOUN} {rec.scenes}")
+            earlier.append((kind.EARLIER, rec.lead))
         if schedule not in SCHEDULES:
             raise ValueError(f"Guide: schedule must be one of {SCHEDULES}, got {schedule!r}")
         scale, cap = float(scale), float(cap)
@@ -570,37 +560,41 @@ class Guide:
         t = self._first()
         return None if t is None else t.device
 
+    def records(self) -> tuple:
+        """The records in the order of RECORDS, None where the guide holds none of that kind."""
+        return _records_of(self)
+
+    def pointwise(self) -> tuple:
+        """The records whose terms name places, in order, None where absent: what `adx_stop_short` takes after the guide."""
+        return tuple(r for kind, r in zip(RECORDS, self.records()) if kind.POINTWISE)
+
+    def _held(self) -> tuple:
+        """The records up to the last one held: what the key spells out and what the narrowest export that fits takes."""
+        records = _records_of(self)
+        held = len(records)
+        while held and records[held - 1] is None:
+            held -= 1
+        return records[:held]
+
+    def tensors(self) -> tuple:
+        """((name, tensor), ...) of every tensor the guide holds: `discs`, `planes`, then `<attribute>.<name>` per record."""
+        own = tuple((name, t) for name, t in (("discs", self.discs), ("planes", self.planes)) if t is not None)
+        return own + tuple((f"{r.ATTR}.{name}", t) for r in self.records() if r is not None for name, t in r.tensors())
+
     def _first(self) -> Optional[torch.Tensor]:
-        """The tensor that says how many scenes the guide holds and where: discs, else planes, else the field's cells, else the
-        motion limits, else the route's points, else the capsules' slots."""
+        """The tensor that says how many scenes the guide holds and where: the first of `tensors()`."""
         if self.discs is not None:
             return self.discs
         if self.planes is not None:
             return self.planes
-        if self.field is not None:
-            return self.field.cells
-        if self.motion is not None:
-            return self.motion.limits
-        if self.route is not None:
-            return self.route.points
-        return None if self.capsules is None else self.capsules.slots
+        return next((r.lead for r in self.records() if r is not None), None)
 
     def key(self) -> tuple:
-        """What a captured graph bakes: everything but the values of discs, planes and the field's cells.  Without a field the
-        6-tuple of cost guidance v1; with one, the field's key appended.  With motion limits: the 6-tuple followed by the field's
-        key or None and the limits' key.  With a route: the 6-tuple, the field's key or None, the limits' key or None, the
-        route's key.  A guide without a route keeps the key it had.  With capsules: the 6-tuple, the field's key or None, the
-        limits' key or None, the route's key or None, the capsules' key.  A guide without capsules keeps the key it had."""
-        key = (self.M, self.P, self.scale, self.schedule, self.cap, self.iters)
-        if self.capsules is not None:
-            return key + (None if self.field is None else self.field.key(), None if self.motion is None else self.motion.key(),
-                          None if self.route is None else self.route.key(), self.capsules.key())
-        if self.route is not None:
-            return key + (None if self.field is None else self.field.key(), None if self.motion is None else self.motion.key(),
-                          self.route.key())
-        if self.motion is not None:
-            return key + (None if self.field is None else self.field.key(), self.motion.key())
-        return key if self.field is None else key + (self.field.key(),)
+        """What a captured graph bakes: everything but the values of the tensors.  The 6-tuple of cost guidance v1, then the keys
+        of the records up to the last one held, None for an absent one in between: a guide keeps the key it had before the
+        kinds of record it does not hold existed."""
+        return ((self.M, self.P, self.scale, self.schedule, self.cap, self.iters) +
+                tuple(None if r is None else r.key() for r in self._held()))
 
     def like(self, discs: Optional[torch.Tensor], planes: Optional[torch.Tensor], field: Optional[CostField] = None,
              motion: Optional[MotionLimits] = None, route: Optional[Route] = None, capsules: Optional[Capsules] = None) -> "Guide":
@@ -608,14 +602,31 @@ class Guide:
         return Guide(discs, planes, self.scale, self.schedule, self.cap, self.iters, field=field, motion=motion, route=route,
                      capsules=capsules)
 
+    def clone(self) -> "Guide":
+        """The same guide over clones of its tensors: the static buffers of a captured graph."""
+        return self.like(None if self.discs is None else self.discs.clone(), None if self.planes is None else self.planes.clone(),
+                         *(None if r is None else r.clone() for r in self.records()))
+
+    def copy_(self, src: "Guide") -> "Guide":
+        """The values of `src`, a guide of the same key and shapes, copied into this one's tensors.  Tensors meet by name, and one
+        without elements is skipped: of two guides with equal keys one may hold `discs=None` and the other an empty [S, 0, 5]."""
+        if src.key() != self.key():
+            raise ValueError(f"Guide.copy_: the keys differ, {src.key()} into {self.key()}")
+        mine = dict(self.tensors())
+        for name, t in src.tensors():
+            if t.numel() > 0:
+                mine[name].copy_(t)
+        return self
+
     # ---- launches ----
     def desc(self, x: torch.Tensor, lam: float = 0.0) -> L.GuideDesc:
         """The `adx_guide` of a launch on `x` [B, H, D] with lambda = `lam` (a scheduler's `guide_level`).  The struct holds
         addresses: keep this object alive until the launch is enqueued."""
-        S = self.scenes
+        first, dev = self._first(), x.device        # `self.scenes` without the property's hop: this runs on every step of an eager tick
+        S = None if first is None else int(first.shape[0])
         for name, t in (("guide.discs", self.discs), ("guide.planes", self.planes)):
-            if t is not None and (L.require_gpu_f32(t, name).device != x.device):
-                raise ValueError(f"{name} lives on {t.device}, the sample on {x.device}")
+            if t is not None and (L.require_gpu_f32(t, name).device != dev):
+                raise ValueError(f"{name} lives on {t.device}, the sample on {dev}")
         if x.dim() != 3 or x.shape[2] < 2 or (S is not None and x.shape[0] % S != 0):
             raise ValueError(f"the guide holds {S} scenes; the sample is {tuple(x.shape)}: [B, H, D] with D >= 2 and rows a multiple "
                              "of the guide's scenes")
@@ -627,77 +638,49 @@ class Guide:
         return g
 
     def field_desc(self, x: torch.Tensor) -> Optional[L.FieldDesc]:
-        """The `adx_guide_field` of a launch on `x` ("cost guidance v2"), or None for a guide without a field: the launch then
-        goes through the `_guide` export."""
+        """The `adx_guide_field` of a launch on `x`, or None for a guide without a field."""
         return None if self.field is None else self.field.desc(x)
 
     def motion_desc(self, x: torch.Tensor) -> Optional[L.MotionDesc]:
-        """The `adx_guide_motion` of a launch on `x` ("cost guidance v3"), or None for a guide without motion limits: the launch
-        then goes through the `_field` or `_guide` export."""
+        """The `adx_guide_motion` of a launch on `x`, or None for a guide without motion limits."""
         return None if self.motion is None else self.motion.desc(x)
 
     def route_desc(self, x: torch.Tensor) -> Optional[L.RouteDesc]:
-        """The `adx_guide_route` of a launch on `x` ("cost guidance v4"), or None for a guide without a route: the launch then
-        goes through the `_motion`, `_field` or `_guide` export."""
+        """The `adx_guide_route` of a launch on `x`, or None for a guide without a route."""
         return None if self.route is None else self.route.desc(x)
 
     def capsule_desc(self, x: torch.Tensor) -> Optional[L.CapsuleDesc]:
-        """The `adx_guide_capsules` of a launch on `x` ("cost guidance v5"), or None for a guide without capsules: the launch then
-        goes through the `_route`, `_motion`, `_field` or `_guide` export."""
+        """The `adx_guide_capsules` of a launch on `x`, or None for a guide without capsules."""
         return None if self.capsules is None else self.capsules.desc(x)
 
     def descs(self, x: torch.Tensor, lam: float = 0.0):
-        """`(export suffix, byref arguments, the structs)` of a guided launch on `x`: "guide", "field", "motion", "route" or
-        "capsule" and the records that export takes after the pin, in its order.  Keep the structs alive until the launch is
-        enqueued."""
-        g, f, m, r = self.desc(x, lam), self.field_desc(x), self.motion_desc(x), self.route_desc(x)
-        c = self.capsule_desc(x)
-        if c is not None:
-            return "capsule", (C.byref(g), None if f is None else C.byref(f), None if m is None else C.byref(m),
-                               None if r is None else C.byref(r), C.byref(c)), (g, f, m, r, c)
-        if r is not None:
-            return "route", (C.byref(g), None if f is None else C.byref(f), None if m is None else C.byref(m), C.byref(r)), (g, f, m, r)
-        if m is not None:
-            return "motion", (C.byref(g), None if f is None else C.byref(f), C.byref(m)), (g, f, m)
-        if f is not None:
-            return "field", (C.byref(g), C.byref(f)), (g, f)
-        return "guide", (C.byref(g),), (g,)
+        """`(export suffix, byref arguments, the structs)` of a guided launch on `x`: the narrowest export that fits.  The suffix
+        is the SUFFIX of the last record held ("guide" with none); the arguments are what that export takes after the pin, in
+        its order: the `adx_guide`, then the records up to that one, None for an absent one.  Keep the structs alive until the
+        launch is enqueued."""
+        g, held, byref = self.desc(x, lam), self._held(), C.byref
+        structs, refs = [g], [byref(g)]
+        for r in held:                      # this runs on every step of an eager tick: one plain loop
+            s = None if r is None else r.desc(x)
+            structs.append(s)
+            refs.append(None if s is None else byref(s))
+        return held[-1].SUFFIX if held else "guide", tuple(refs), tuple(structs)
 
     def cost(self, traj: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """What a plan still violates, one launch of `adx_guide_cost`: `(cost [rows] float32, active [rows] int32)` of `traj`
         [rows, H, D] -- the contract's cost summed over a row's waypoints and the number of active (waypoint, constraint) pairs.
         `traj` is in the MODEL's units: a result before xy scaling (`scale_xy=False`, `warm.prev`), row r against scene r % S."""
         traj = L.require_gpu_f32(traj, "traj")
-        g = self.desc(traj)
+        suffix, refs, _alive = self.descs(traj)
         rows, H, D = traj.shape
         cost = torch.empty(rows, dtype=torch.float32, device=traj.device)
         active = torch.empty(rows, dtype=torch.int32, device=traj.device)
-        f, m, r, c = self.field_desc(traj), self.motion_desc(traj), self.route_desc(traj), self.capsule_desc(traj)
-        if c is not None:
-            L.check(L.lazy("adx_guide_cost_capsule")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f),
-                                                     None if m is None else C.byref(m), None if r is None else C.byref(r), C.byref(c),
-                                                     cost.data_ptr(), active.data_ptr(), rows, H, D, L.stream_ptr(traj.device)),
-                    "adx_guide_cost_capsule")
-        elif r is not None:
-            L.check(L.lazy("adx_guide_cost_route")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f),
-                                                   None if m is None else C.byref(m), C.byref(r), cost.data_ptr(), active.data_ptr(),
-                                                   rows, H, D, L.stream_ptr(traj.device)), "adx_guide_cost_route")
-        elif m is not None:
-            L.check(L.lazy("adx_guide_cost_motion")(traj.data_ptr(), C.byref(g), None if f is None else C.byref(f), C.byref(m),
-                                                    cost.data_ptr(), active.data_ptr(), rows, H, D, L.stream_ptr(traj.device)),
-                    "adx_guide_cost_motion")
-        elif f is None:
-            L.check(L.lazy("adx_guide_cost")(traj.data_ptr(), C.byref(g), cost.data_ptr(), active.data_ptr(), rows, H, D,
-                                             L.stream_ptr(traj.device)), "adx_guide_cost")
-        else:
-            L.check(L.lazy("adx_guide_cost_field")(traj.data_ptr(), C.byref(g), C.byref(f), cost.data_ptr(), active.data_ptr(), rows, H, D,
-                                                   L.stream_ptr(traj.device)), "adx_guide_cost_field")
+        name = "adx_guide_cost" + ("" if suffix == "guide" else "_" + suffix)
+        L.check(L.lazy(name)(traj.data_ptr(), *refs, cost.data_ptr(), active.data_ptr(), rows, H, D, L.stream_ptr(traj.device)), name)
         return cost, active
 
     def __repr__(self):
-        return (f"Guide(discs={None if self.discs is None else tuple(self.discs.shape)}, "
-                f"planes={None if self.planes is None else tuple(self.planes.shape)}, scale={self.scale}, schedule={self.schedule!r}, "
-                f"cap={self.cap}, iters={self.iters}" + ("" if self.field is None else f", field={self.field!r}") +
-                ("" if self.motion is None else f", motion={self.motion!r}") +
-                ("" if self.route is None else f", route={self.route!r}") +
-                ("" if self.capsules is None else f", capsules={self.capsules!r}") + ")")
+        return ", ".join([f"Guide(discs={None if self.discs is None else tuple(self.discs.shape)}, "
+                          f"planes={None if self.planes is None else tuple(self.planes.shape)}, scale={self.scale}, "
+                          f"schedule={self.schedule!r}, cap={self.cap}, iters={self.iters}"] +
+                         [f"{r.ATTR}={r!r}" for r in self.records() if r is not None]) + ")"

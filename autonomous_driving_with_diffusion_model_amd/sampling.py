@@ -200,11 +200,8 @@ class TickPlan:
     # discs and planes: buffers; presence, M, P, scale, schedule, cap and iters: baked (lambda, which scale and schedule give per
     # timestep, is a by-value argument of every step node).  Every `scheduler.step` of the loop gets it (fused or not, all three
     # guidance branches) and moves its x0 inside its kernel; the K * S rows read the [S, ..] obstacles directly (row r reads scene
-    # r % S), nothing is tiled.  A guide's field ("cost guidance v2"): the cells are a buffer like discs and planes; presence, (Gy, Gx),
-    # origin, cell size and weight are baked (by-value arguments of every step node) -- all of it through `Guide.key()`.  A guide's
-    # motion limits ("cost guidance v3"): the [S, 2] limits are a buffer; presence and the two weights are baked, the same way.  A
-    # guide's route ("cost guidance v4"): the [S, R, 2] points and [S] half-widths are buffers; presence, R and the weight are baked.
-    # A guide's capsules ("cost guidance v5"): the [S, C, 7] slots are a buffer; presence, C and the weight are baked
+    # r % S), nothing is tiled.  A guide's records (guide.py, RECORDS) travel the same way: their tensors (`Guide.tensors()`) are
+    # buffers; presence and what each record's `key()` holds are baked (by-value arguments of every step node), through `Guide.key()`
     guide: Optional[Guide]
     # ---- fallback ----
     # params: a buffer; presence: baked.  After selection and the copy into warm.prev, one launch of `fallback(best, guide)`
@@ -268,12 +265,8 @@ def _guide_plan(cfg, guide: Optional[Guide], image, scheduler) -> Optional[Guide
     if not isinstance(guide, Guide):
         raise TypeError(f"generate_traj: `guide` must be a Guide, got {type(guide).__name__}")
     S = int(image.shape[0])
-    for name, t in (("discs", guide.discs), ("planes", guide.planes), ("field.cells", None if guide.field is None else guide.field.cells),
-                    ("motion.limits", None if guide.motion is None else guide.motion.limits),
-                    ("route.points", None if guide.route is None else guide.route.points),
-                    ("route.half_width", None if guide.route is None else guide.route.half_width),
-                    ("capsules.slots", None if guide.capsules is None else guide.capsules.slots)):
-        if t is not None and (int(t.shape[0]) != S or t.device != image.device):
+    for name, t in guide.tensors():
+        if int(t.shape[0]) != S or t.device != image.device:
             raise ValueError(f"guide.{name} must hold {S} scenes (image.shape[0]) on {image.device}, got {tuple(t.shape)} on {t.device}")
     if int(cfg.MODEL.TRANSITION_DIM) < 2:
         raise ValueError(f"generate_traj: a guide moves (x, y) and needs MODEL.TRANSITION_DIM >= 2, got {int(cfg.MODEL.TRANSITION_DIM)}")
@@ -638,10 +631,8 @@ class GraphedSampler:
     `repaint` pin needs `noise=DeviceNoise(...)` at construction (a captured noise tensor would replay) and is refused without.
     `guide=Guide(...)` per call: cost guidance as in `generate_traj`.  `discs` and `planes` travel through static buffers; presence,
     M, P, scale, schedule, cap and iters are part of the graph key (every step node holds its lambda by value), new obstacle values
-    never capture again.  A guide's `field` travels the same way: the cells through a static buffer, its presence, shape, geometry
-    and weight through the key.  So do a guide's motion limits: the limits through a static buffer, presence and weights through the key.
-    And a guide's route: points and half-widths through static buffers, presence, R and weight through the key.
-    And a guide's capsules: the slots through a static buffer, presence, C and weight through the key.
+    never capture again.  A guide's records (guide.py, RECORDS) travel the same way: their tensors through static buffers
+    (`Guide.clone`, `Guide.copy_`), their presence and what each one's `key()` holds through the key.
     `fallback=StopShort(...)`: the stop-short launch is a node of the graph after selection and before control
     (`generate_traj(fallback=...)`).  Its params are copied into a static buffer at every call, so new values never capture again;
     its presence is part of the graph key.  The call returns the re-timed plan and `last_fallback` the report of the last replay.
@@ -685,13 +676,7 @@ class GraphedSampler:
         g.motion = None if motion is None else motion.clone()
         g.vel = None if velocity is None else velocity.clone()
         g.pin = None if pin is None else Pin(pin.known.clone(), pin.mask.clone(), pin.mode)
-        g.guide = None if guide is None else guide.like(None if guide.discs is None else guide.discs.clone(),
-                                                        None if guide.planes is None else guide.planes.clone(),
-                                                        None if guide.field is None else guide.field.like(guide.field.cells.clone()),
-                                                        None if guide.motion is None else guide.motion.like(guide.motion.limits.clone()),
-                                                        None if guide.route is None else guide.route.like(guide.route.points.clone(),
-                                                                                                         guide.route.half_width.clone()),
-                                                        None if guide.capsules is None else guide.capsules.like(guide.capsules.slots.clone()))
+        g.guide = None if guide is None else guide.clone()
         ctl = self.controller
         g.fb = None if self.fallback is None else self.fallback.like(self.fallback.params.clone())
         run = lambda: generate_traj(self.model, self.scheduler, self.cfg, g.img, g.tgt, g.init,  # noqa: E731
@@ -808,19 +793,7 @@ class GraphedSampler:
                 g.pin.known.copy_(pin.known)
                 g.pin.mask.copy_(pin.mask)
             if guide is not None:
-                if guide.M > 0:
-                    g.guide.discs.copy_(guide.discs)
-                if guide.P > 0:
-                    g.guide.planes.copy_(guide.planes)
-                if guide.field is not None:
-                    g.guide.field.cells.copy_(guide.field.cells)
-                if guide.motion is not None:
-                    g.guide.motion.limits.copy_(guide.motion.limits)
-                if guide.route is not None:
-                    g.guide.route.points.copy_(guide.route.points)
-                    g.guide.route.half_width.copy_(guide.route.half_width)
-                if guide.capsules is not None:
-                    g.guide.capsules.slots.copy_(guide.capsules.slots)
+                g.guide.copy_(guide)
             if g.fb is not None:
                 g.fb.params.copy_(self.fallback.params)
         self._key, self._graph, self._sel, self._ctl, self._fb = key, g.graph, g.sel, g.ctl, g.fbres

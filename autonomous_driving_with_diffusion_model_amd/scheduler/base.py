@@ -279,9 +279,7 @@ class SchedulerBase:
     def _launch(self, ddpm: bool, c: L.StepCoef, mo, x, noise, target, mask, want_x0=True, slot: int = 0, pin=None, guide=None):
         """`noise`: as `_noise_args` takes it; the stream is drawn at `slot` (the integer timestep).  `pin`: the `adx_pin` of a
         pinned step (the PIN variant of the kernel, "pinned waypoints v1"); `guide`: what `_guide_desc` made of a guided step (the
-        GUIDE variant): the export's suffix -- "guide" (cost guidance v1), "field" (v2), "motion" (v3, the row-wise kernel), "route" (v4) or
-        "capsule" (v5) --
-        with its records; None is the call as it was."""
+        GUIDE variant): the export's suffix with its records, as guide.py's `Guide.descs` chooses them; None is the call as it was."""
         B, H, D = x.shape
         prev = torch.empty_like(x)
         x0 = torch.empty_like(x) if want_x0 else None
@@ -344,9 +342,7 @@ class SchedulerBase:
             return float(scale * np.float32(sb * sb))
 
     def _guide_desc(self, guide, timestep, x):
-        """`Guide.descs` of this step, or None without a guide: a guide with motion limits goes through the `_motion` export
-        ("cost guidance v3"), one with a field through the `_field` export (v2), any other through the `_guide` export; one with a route goes through
-        the `_route` export (v4) whatever else it holds, and one with capsules through the `_capsule` export (v5)."""
+        """`Guide.descs` of this step (guide.py: the narrowest export that fits and its records), or None without a guide."""
         return None if guide is None else guide.descs(x, self.guide_level(timestep, guide))
 
     @staticmethod

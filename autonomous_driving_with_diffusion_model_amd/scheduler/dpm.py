@@ -201,7 +201,7 @@ class GuidanceDPMSolverMultistepScheduler(SchedulerBase):
         g = self._guide_desc(guide, timestep, x)
         prev, x0 = torch.empty_like(x), torch.empty_like(x)
         if g is not None:
-            suffix, guides, _alive = g                                                     # "guide", "field", "motion", "route", "capsule"
+            suffix, guides, _alive = g                                                     # as guide.py's `Guide.descs` chooses them
             _, state, row_offset = self._noise_args(generator if stream else None, x)      # the stream or nothing
             L.check(L.lazy("adx_dpm_step_" + suffix)(
                 C.byref(c), mo.data_ptr(), x.data_ptr(), L.ptr(history), state, timestep_to_int(timestep), row_offset,
