@@ -119,6 +119,12 @@ class ControlCfg(C.Structure):
                                     "max_throttle")])
 
 
+class MetricsCfg(C.Structure):
+    """adx_metrics_cfg ("open-loop metrics v1", include/adx.h)."""
+    _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("h0", i32), ("miss_radius", f32),
+                ("xy_scale", f32)]
+
+
 _SIGS = {
     "adx_version": (i32, []),
     "adx_last_error": (C.c_char_p, []),
@@ -225,6 +231,10 @@ _SIGS = {
     "adx_control_state_bytes": (C.c_size_t, [i32, i32, i32]),
     "adx_control_step": (i32, [C.POINTER(ControlCfg), vp, vp, vp, vp, vp, vp]),
     "adx_control_reset": (i32, [vp, i32, i32, i32, vp, vp]),
+    "adx_traj_metrics": (i32, [C.POINTER(MetricsCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_metrics_state_bytes": (C.c_size_t, []),
+    "adx_metrics_reset": (i32, [vp, vp]),
+    "adx_metrics_accumulate": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "adx_noise_normal": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_words": (i32, [vp, i32, i64, vp, i64, vp]),
     "adx_noise_advance": (i32, [vp, vp]),

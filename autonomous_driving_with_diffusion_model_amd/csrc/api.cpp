@@ -384,6 +384,16 @@ int adx_control_step(const adx_control_cfg* c, const float* traj, const float* v
 int adx_control_reset(void* state, int32_t scenes, int32_t n_turn, int32_t n_speed, const uint8_t* mask, adx_stream s) {
   return adx::control_reset(state, scenes, n_turn, n_speed, mask, (hipStream_t)s);
 }
+int adx_traj_metrics(const adx_metrics_cfg* c, const float* trajs, const float* gt, const int32_t* valid, const int32_t* index,
+                     float* ade, float* fde, int32_t* best, float* rec, int32_t* flags, float* disp_sel, adx_stream s) {
+  return adx::traj_metrics(c, trajs, gt, valid, index, ade, fde, best, rec, flags, disp_sel, (hipStream_t)s);
+}
+size_t adx_metrics_state_bytes(void) { return adx::metrics_state_bytes(); }
+int adx_metrics_reset(void* state, adx_stream s) { return adx::metrics_reset(state, (hipStream_t)s); }
+int adx_metrics_accumulate(void* state, const float* rec, const int32_t* flags, const int32_t* best, const int32_t* index,
+                           const float* disp_sel, const int32_t* blocked, int32_t scenes, int32_t horizon, adx_stream s) {
+  return adx::metrics_accumulate(state, rec, flags, best, index, disp_sel, blocked, scenes, horizon, (hipStream_t)s);
+}
 int adx_stop_short(const float* traj, const adx_guide* guide, const adx_guide_field* field, const adx_guide_route* route,
                    const adx_guide_capsules* capsules, const float* params, int32_t param_rows, float* out, int32_t* first,
                    int32_t* status, float* stop_at, int32_t* active_after, int32_t rows, int32_t horizon, int32_t dim, adx_stream s) {

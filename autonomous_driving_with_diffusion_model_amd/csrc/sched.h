@@ -101,6 +101,13 @@ int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const f
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);
+// "Open-loop metrics v1" (metrics.hip)
+int traj_metrics(const adx_metrics_cfg* c, const float* trajs, const float* gt, const int32_t* valid, const int32_t* index, float* ade,
+                 float* fde, int32_t* best, float* rec, int32_t* flags, float* disp_sel, hipStream_t s);
+size_t metrics_state_bytes();
+int metrics_reset(void* state, hipStream_t s);
+int metrics_accumulate(void* state, const float* rec, const int32_t* flags, const int32_t* best, const int32_t* index,
+                       const float* disp_sel, const int32_t* blocked, int scenes, int horizon, hipStream_t s);
 // "Capsules from boxes v1" (capsule.hip)
 int capsules_from_boxes(const float* boxes, float* out, int scenes, int n_boxes, float inflate, hipStream_t s);
 int field_from_occupancy(const float* occ, float* cells, int scenes, int gy, int gx, float dx, float dy, float inv_m2, int ry, int rx,

@@ -747,6 +747,12 @@ class GraphedSampler:
         return Selection(None, self._sel.index.clone(), self._sel.cost.clone(), None, clone(self._sel.active), clone(self._sel.blocked))
 
     @property
+    def last_candidates(self) -> Optional[torch.Tensor]:
+        """A clone of the static [K, S, H, D] candidates as the last replay left them (scaled like the result: `scale_xy`); None
+        before the first call and at one candidate per scene.  What `evaluation.OpenLoopMetrics` scores after a replay."""
+        return None if self._sel is None or self._sel.candidates is None else self._sel.candidates.clone()
+
+    @property
     def last_control(self) -> Optional[torch.Tensor]:
         """A clone of the static control [S, 3] = (throttle, steer, brake) as the last replay left it; None before the first
         call and without a controller."""

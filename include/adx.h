@@ -1429,6 +1429,86 @@ int adx_stop_short(const float* traj, const adx_guide* guide, const adx_guide_fi
                    float* out, int32_t* first, int32_t* status, float* stop_at, int32_t* active_after, int32_t rows,
                    int32_t horizon, int32_t dim, adx_stream s);
 
+/* ------------------------------------------------------------------------------------
+ * Open-loop metrics v1: how far sampled plans lie from logged waypoints -- ADE / FDE of the chosen plan, minADE_K / minFDE_K
+ * over a scene's candidates, miss flags, the chosen plan's displacement per waypoint and its final error split along and across
+ * the logged heading.  One launch per batch (adx_traj_metrics) and one launch that folds the batch into a device-resident state
+ * (adx_metrics_accumulate): no host decision, no allocation, no synchronisation, so both can follow a captured tick.  No
+ * reference counterpart: the reference's train.evaluate paints dots (train.py:62-90).  Callers and fixtures depend on this
+ * definition -- a change is a new version, never an edit.
+ *
+ *   trajs     float32 [K * S][H][D], candidate-major as adx_traj_select takes them: candidate k of scene s is row k * S + s.
+ *             1 <= K <= 64, 1 <= H <= 64, D >= 2; columns 0, 1 are (x, y) in the model's own units.
+ *   gt        float32 [S][H][2], the logged waypoints in the units of trajs.
+ *   valid     int32 [S] or NULL: n_s, how many of the scene's logged waypoints count, clamped to [0, H]; NULL: H.
+ *   index     int32 [S] or NULL: the chosen candidate (adx_traj_select's index); NULL: candidate 0.  A value outside [0, K)
+ *             makes the scene unscored; it is compared, never used as an address.
+ *   cfg       h0: the first scored waypoint (callers pass 1: waypoint 0 is the ego pose the sampling loops zero); waypoints
+ *             h0 <= h < n_s are scored.  xy_scale: metres per model unit (model.magic_num).  miss_radius: metres.
+ *
+ * A scene is scored when n_s > h0 and its index is in range.  An unscored scene writes zeros to every output, flags 0.  All
+ * arithmetic is fp32, no contraction; every +, -, *, / and sqrtf below is one correctly rounded operation, in the order written.
+ * Per scored scene, with n = n_s:
+ *
+ *   disp      per candidate k and scored h: ex = (x - gx) * xy_scale, ey = (y - gy) * xy_scale, disp_h = sqrtf(ex * ex + ey * ey);
+ *             disp_h = 0 for every other h < 64.
+ *   ade[s][k] p_l = disp_l for l = 0..63, then six rounds p_l = p_l + p_{l ^ off}, off = 32, 16, 8, 4, 2, 1, and
+ *             ade = p_0 / (float)(n - h0).
+ *   fde[s][k] disp_{n-1}.
+ *   search    argmin(v): the smallest k among the smallest finite v_k; no finite v_k: 0 (ties to the lowest k, a non-finite
+ *             value loses to every finite one: the rule of selection cost v1).
+ *   best[s]   argmin(ade).
+ *   rec[s]    8 floats: min_ade = ade[best], min_fde = fde[argmin(fde)] (its own search), sel_ade = ade[index],
+ *             sel_fde = fde[index], along, cross, miss_sel = sel_fde > miss_radius ? 1 : 0, miss_any = min_fde > miss_radius ? 1 : 0
+ *             (a NaN is not a miss; bit 2 of the flags tells).
+ *   heading   d = gt[n-1] - gt[n-2] (model units), len = sqrtf(d.x * d.x + d.y * d.y); valid when n - h0 >= 2 and
+ *             0 < len < inf.  u = (d.x / len, d.y / len); with (ex, ey) the chosen candidate's error at h = n - 1:
+ *             along = ex * u.x + ey * u.y (longitudinal), cross = ey * u.x - ex * u.y (lateral, left positive).  Not valid: both 0.
+ *   flags[s]  bit 0: scored.  bit 1: heading valid.  bit 2: sel_ade is finite (every scored disp of the chosen candidate is
+ *             finite and so is their sum).  Bits 8..14: n.  Bits 16..22: h0.  (The upper fields let the accumulation know the
+ *             scored range of disp_sel without a second look at valid.)
+ *   disp_sel  [S][H]: the chosen candidate's disp_h, 0 outside the scored range.
+ *   rounding  the float outputs are defined up to fp32 rounding of the operations above (tests/metrics_ref.py restates them in
+ *             fp64 and derives the bound); best and the miss fields exactly wherever their margins exceed that rounding.  A
+ *             scene's result does not depend on the other scenes of the launch; no atomics, fixed trees: the same input
+ *             gives the same bits on every launch.
+ *
+ * Accumulation.  The state is one device buffer of adx_metrics_state_bytes() bytes, opaque to callers, all zero bytes = empty
+ * (today 144 8-byte words: int64 counts and fp64 sums).  adx_metrics_accumulate walks the scenes of one batch in index order, each
+ * statistic in fp64 on a thread of its own (one workgroup), so the state's bits depend on the batches and their order alone:
+ *   words 0..4    int64: scenes scored; of those, scenes whose chosen plan is not finite (bit 2 clear) -- counted here and left
+ *                 out of everything below; heading-valid scenes; scenes with best == index (index NULL: 0); scenes with
+ *                 blocked != 0 (blocked NULL: none)
+ *   words 5..12   fp64 sums of rec[0..7]
+ *   word 13       fp64 sum of (double)sel_ade - (double)min_ade, the selector's regret
+ *   words 14, 15  fp64 sums of |along| and |cross| over the heading-valid scenes
+ *   words 16+h    fp64 sum of disp_sel[s][h] over the scenes with h0 <= h < n;  words 80+h: int64, how many those are
+ *
+ * ADX_ERR_INVALID before any GPU work, each with its own text: a NULL configuration or required pointer; candidates or horizon
+ * outside 1..64, dim < 2, scenes outside 1..65535; h0 outside 0..horizon-1; xy_scale not finite or not > 0; miss_radius negative
+ * or NaN; an output overlapping an input or another output; K * S * H * D above 0x3fffffff.  Accumulate and reset: a NULL
+ * pointer other than index and blocked, scenes or horizon out of range, the state overlapping an input.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_METRICS_REC 8
+#define ADX_METRICS_FLAG_SCORED 1
+#define ADX_METRICS_FLAG_HEADING 2
+#define ADX_METRICS_FLAG_FINITE 4
+typedef struct adx_metrics_cfg {
+  int32_t scenes, candidates, horizon, dim, h0;
+  float miss_radius, xy_scale;
+} adx_metrics_cfg;
+/* trajs, gt, valid, index as above; ade, fde float32 [scenes][candidates]; best int32 [scenes]; rec float32 [scenes][8];
+ * flags int32 [scenes]; disp_sel float32 [scenes][horizon]. */
+int adx_traj_metrics(const adx_metrics_cfg* c, const float* trajs, const float* gt, const int32_t* valid, const int32_t* index,
+                     float* ade, float* fde, int32_t* best, float* rec, int32_t* flags, float* disp_sel, adx_stream s);
+size_t adx_metrics_state_bytes(void);
+/* An empty state; a capturable launch. */
+int adx_metrics_reset(void* state, adx_stream s);
+/* rec, flags, best, disp_sel: one adx_traj_metrics launch's outputs; index: what that launch was given (or NULL); blocked int32
+ * [scenes] or NULL: 1 where the chosen plan still violates the guide (selection cost v2's `blocked`, or active > 0). */
+int adx_metrics_accumulate(void* state, const float* rec, const int32_t* flags, const int32_t* best, const int32_t* index,
+                           const float* disp_sel, const int32_t* blocked, int32_t scenes, int32_t horizon, adx_stream s);
+
 /* add_noise (train.py:234) fused with the [...,0,:3] = 0 of train.py:235 when zero_first != 0.
  * sqrt_ab / sqrt_1mab are the host tables sqrt(abar), sqrt(1-abar) of length n_train.  Refused: batch * horizon * dim above
  * 0x3fffffff, more elements than the kernel's 32-bit index holds. */
