@@ -17,6 +17,8 @@ Public surface mirrors the reference's packages:
     Capsules                                          (no reference counterpart: moving capsules in a Guide, guide.py)
     StopShort, StopResult                             (no reference counterpart: re-time a blocked plan to halt before its
                                                        conflict, control/fallback.py)
+    TrajectoryModes, ModeSet                          (no reference counterpart: the manoeuvres a scene's K candidates contain and
+                                                       the sample mass behind each, control/modes.py)
     OpenLoopMetrics, evaluate_open_loop               (no reference counterpart: ADE / FDE, minADE_K / minFDE_K and miss rates
                                                        against logged waypoints, on the device, evaluation.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
@@ -40,6 +42,7 @@ from .scheduler import GuidanceDPMSolverMultistepScheduler  # noqa: E402
 from .control.select import Selection, TrajectorySelector  # noqa: E402
 from .control.device import DeviceController  # noqa: E402
 from .control.fallback import StopResult, StopShort  # noqa: E402
+from .control.modes import ModeSet, TrajectoryModes  # noqa: E402
 from .pin import Pin  # noqa: E402
 from .guide import Capsules, CostField, Guide, MotionLimits, Route  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
@@ -47,4 +50,4 @@ from .evaluation import MetricsBatch, OpenLoopMetrics, evaluate_open_loop  # noq
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
-           "Route", "Capsules", "StopShort", "StopResult", "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop"]
+           "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop"]

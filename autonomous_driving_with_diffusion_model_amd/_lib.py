@@ -112,6 +112,12 @@ class SelectGuideCfg(C.Structure):
                 ("w_consensus", f32), ("w_guide", f32), ("hard", i32)]
 
 
+class ModesCfg(C.Structure):
+    """adx_modes_cfg ("trajectory modes v1", include/adx.h)."""
+    _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("max_modes", i32), ("h0", i32),
+                ("radius", f32)]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -256,6 +262,7 @@ _LAZY_SIGS = {
     "adx_capsules_from_boxes": (i32, [vp, vp, i32, i32, f32, vp]),
     "adx_stop_short": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, i32, vp, vp,
                              vp, vp, vp, i32, i32, i32, vp]),
+    "adx_traj_modes": (i32, [C.POINTER(ModesCfg), vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 # the guided exports: five families (the three steps, the cost, the guided selection) times five suffixes, each suffix taking the

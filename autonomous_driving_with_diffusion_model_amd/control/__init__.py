@@ -4,7 +4,8 @@ from .guidance import GuidanceLoss
 from .guidance_loss import TargetGuidance
 from .pid import PIDController
 from .fallback import StopResult, StopShort
+from .modes import ModeSet, TrajectoryModes
 from .select import Selection, TrajectorySelector
 
 __all__ = ["GuidanceLoss", "TargetGuidance", "Controller", "PIDController", "post_process_control", "Selection",
-           "TrajectorySelector", "DeviceController", "StopShort", "StopResult"]
+           "TrajectorySelector", "DeviceController", "StopShort", "StopResult", "TrajectoryModes", "ModeSet"]

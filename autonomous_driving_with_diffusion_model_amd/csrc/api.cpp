@@ -367,6 +367,10 @@ int adx_traj_select_guide_capsule(const adx_select_guide_cfg* c, const float* tr
                                   int32_t* blocked, float* best, adx_stream s) {
   return adx::traj_select_guide(c, trajs, target, {guide, field, motion, route, capsules}, cost, active, index, blocked, best, (hipStream_t)s);
 }
+int adx_traj_modes(const adx_modes_cfg* c, const float* trajs, float* modes, int32_t* index, int32_t* mass, int32_t* assign,
+                   int32_t* count, float* dist2, adx_stream s) {
+  return adx::traj_modes(c, trajs, modes, index, mass, assign, count, dist2, (hipStream_t)s);
+}
 int adx_capsules_from_boxes(const float* boxes, float* out, int32_t scenes, int32_t n_boxes, float inflate, adx_stream s) {
   return adx::capsules_from_boxes(boxes, out, scenes, n_boxes, inflate, (hipStream_t)s);
 }

@@ -98,6 +98,9 @@ int traj_select(const adx_select_cfg* c, const float* trajs, const float* target
                 hipStream_t s);
 int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const float* target, const GuideRecords& g, float* cost,
                       int32_t* active, int32_t* index, int32_t* blocked, float* best, hipStream_t s);
+// "Trajectory modes v1" (modes.hip)
+int traj_modes(const adx_modes_cfg* c, const float* trajs, float* modes, int32_t* index, int32_t* mass, int32_t* assign,
+               int32_t* count, float* dist2, hipStream_t s);
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);

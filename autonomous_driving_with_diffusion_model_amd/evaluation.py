@@ -10,7 +10,10 @@ reference's `train.evaluate` paints dots on a BEV image (train.py:62-90).
 `evaluate_open_loop` walks a loader of the dataset reader (`dataset.get_loader`: frames, logged waypoints, target points) through
 `generate_traj` and returns `compute()`: ADE / FDE of the plan that was chosen, minADE_K / minFDE_K over the candidates, the miss
 rates, what the selector loses against the best candidate, the displacement per waypoint.  Distances are metres: `xy_scale` turns
-the model's units into them (`model.magic_num`).
+the model's units into them (`model.magic_num`).  With `modes=TrajectoryModes(...)` the tick also clusters each scene's candidates
+(control/modes.py) and a second `OpenLoopMetrics` scores the M modes as an M-candidate set whose chosen plan is mode 0, the
+heaviest: minADE over M modes -- the figure motion-prediction work is compared on -- and the majority-vote plan beside the
+selector's.
 """
 from __future__ import annotations
 
@@ -20,6 +23,7 @@ from typing import Callable, NamedTuple, Optional
 import torch
 
 from . import _lib as L
+from .control.modes import OUTLIER, TrajectoryModes
 from .control.select import MAX_CANDIDATES, Selection
 from .guide import Guide
 
@@ -154,7 +158,7 @@ class OpenLoopMetrics:
 
 def evaluate_open_loop(model, scheduler, cfg, loader, *, candidates: int = 1, selector=None, noise=None, warm=None,
                        guide_fn: Optional[Callable] = None, graphed: bool = False, max_batches: Optional[int] = None,
-                       metrics: Optional[OpenLoopMetrics] = None) -> dict:
+                       metrics: Optional[OpenLoopMetrics] = None, modes: Optional[TrajectoryModes] = None) -> dict:
     """Open-loop metrics of `generate_traj` over `loader`, whose batches are `(image, waypoints [B, H, D], target [B, 2])` as
     `dataset.get_loader` yields them (uint8 HWC frames go through `ops.image_transform` on the device; float frames are taken as
     they are).  Per batch: one tick (`generate_traj(..., scale_xy=False, return_selection=True)`, or a `GraphedSampler` replay
@@ -162,7 +166,14 @@ def evaluate_open_loop(model, scheduler, cfg, loader, *, candidates: int = 1, se
     and `blocked` are the Selection's where there is one, and `Guide.cost`'s `active > 0` of the plan where a guide ran without a
     selector that reads it.  `guide_fn(batch) -> Guide | None` supplies a batch's logged obstacles.  `metrics`: an OpenLoopMetrics
     to fold into (default: a fresh one, h0 = 1, miss radius 2 m, `model.magic_num`).  Nothing inside the loop reads the device;
-    the call returns `metrics.compute()`."""
+    the call returns `metrics.compute()`.
+
+    `modes`: a TrajectoryModes (K > 1) the tick runs with; each batch's mode set is folded into a second OpenLoopMetrics (the
+    settings of `metrics`) with the M modes as the candidates and mode 0 as the chosen one.  The returned dict then has one more
+    entry, `"modes"`: `m`; `min_ade_m`, `min_fde_m`, `miss_rate_any_m` over the modes; `top_ade`, `top_fde`, `top_miss_rate` of
+    mode 0 (the majority-vote plan, to read beside `ade`); `mean_count` (modes formed per scene), `mean_top_prob` (mode 0's share
+    of the finite candidates) and `outlier_rate` (candidates no mode took, over all candidates) -- means over every scene of the
+    run, accumulated with device-side adds."""
     from . import ops
     from .misc.constant import GuidanceType
     from .sampling import GraphedSampler, generate_traj
@@ -171,10 +182,15 @@ def evaluate_open_loop(model, scheduler, cfg, loader, *, candidates: int = 1, se
         raise ValueError(f"candidates must be 1..{MAX_CANDIDATES}, got {K}")
     if metrics is None:
         metrics = OpenLoopMetrics(xy_scale=float(model.magic_num))
+    if modes is not None and not isinstance(modes, TrajectoryModes):
+        raise TypeError(f"evaluate_open_loop: `modes` must be a TrajectoryModes, got {type(modes).__name__}")
     dev = next(model.parameters()).device
+    mode_metrics = None if modes is None else OpenLoopMetrics(metrics.h0, metrics.miss_radius, metrics.xy_scale)
+    mode_sums = None if modes is None else torch.zeros(3, dtype=torch.float64, device=dev)   # count, top prob, outliers
+    mode_scenes = 0
     with_target = GuidanceType[cfg.GUIDANCE.USE_COND] != GuidanceType.NO_GUIDANCE
-    sampler = GraphedSampler(model, scheduler, cfg, scale_xy=False, noise=noise, candidates=K, selector=selector, warm=warm) \
-        if graphed else None
+    sampler = GraphedSampler(model, scheduler, cfg, scale_xy=False, noise=noise, candidates=K, selector=selector, warm=warm,
+                             modes=modes) if graphed else None
     for i, batch in enumerate(loader):
         if max_batches is not None and i >= max_batches:
             break
@@ -191,13 +207,27 @@ def evaluate_open_loop(model, scheduler, cfg, loader, *, candidates: int = 1, se
             if sampler is not None:
                 traj = sampler(image, tgt, guide=guide)
                 sel, cands = sampler.last_selection, sampler.last_candidates
+                mset = sampler.last_modes
             else:
                 traj, sel = generate_traj(model, scheduler, cfg, image, tgt, noise=noise, candidates=K, selector=selector,
-                                          warm=warm, guide=guide, scale_xy=False, return_selection=True)
+                                          warm=warm, guide=guide, scale_xy=False, return_selection=True, modes=modes)
                 cands = None if sel is None else sel.candidates
+                mset = None if modes is None else modes.last
             index = None if sel is None else sel.index
             blocked = None if sel is None else sel.blocked
             if blocked is None and guide is not None:
                 blocked = (guide.cost(traj)[1] > 0).to(torch.int32)      # a comparison on the device: no read
             metrics.update(traj if cands is None else cands, gt, index=index, blocked=blocked)
-    return metrics.compute()
+            if mset is not None:
+                mode_metrics.update(mset.modes, gt)          # index None: candidate 0 = mode 0, the heaviest
+                mode_scenes += int(gt.shape[0])
+                mode_sums += torch.stack([t.sum().to(torch.float64) for t in (mset.count, mset.prob()[:, 0], mset.assign == OUTLIER)])
+    out = metrics.compute()
+    if modes is not None:
+        m, sums = mode_metrics.compute(), mode_sums.cpu().tolist()
+        per = lambda v, d: v / d if d > 0 else float("nan")      # noqa: E731
+        out["modes"] = {"m": modes.max_modes, "min_ade_m": m["min_ade_k"], "min_fde_m": m["min_fde_k"],
+                        "miss_rate_any_m": m["miss_rate_any"], "top_ade": m["ade"], "top_fde": m["fde"],
+                        "top_miss_rate": m["miss_rate"], "mean_count": per(sums[0], mode_scenes),
+                        "mean_top_prob": per(sums[1], mode_scenes), "outlier_rate": per(sums[2], mode_scenes * K)}
+    return out

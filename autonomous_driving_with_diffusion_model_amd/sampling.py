@@ -41,6 +41,9 @@ A twelfth says where the other vehicles are: `guide=Guide(..., capsules=Capsules
 A thirteenth is the last resort when the plan a tick ends with still runs into something: `fallback=StopShort(params)` keeps its
 path and re-times it to brake to a halt before its first conflict with the guide ("stop-short fallback v1", control/fallback.py),
 one launch between selection and control; the controller and the caller get the re-timed plan, the warm state the sampler's own.
+A fourteenth says what the K candidates contain: `modes=TrajectoryModes(...)` clusters them per scene into the manoeuvres they
+stand for and counts the sample mass behind each ("trajectory modes v1", control/modes.py), one launch directly after selection
+that alters nothing the tick returns; the result is left in `modes.last`.
 """
 from __future__ import annotations
 
@@ -55,6 +58,7 @@ from . import _lib as L
 from ._lib import AdxRangeError
 from .control.device import DeviceController
 from .control.fallback import MAX_HORIZON as FALLBACK_MAX_HORIZON, NO_POINTWISE_TERM, StopResult, StopShort, pointwise
+from .control.modes import MAX_HORIZON as MODES_MAX_HORIZON, ModeSet, TrajectoryModes
 from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
 from .noise import DeviceNoise
@@ -203,6 +207,11 @@ class TickPlan:
     # r % S), nothing is tiled.  A guide's records (guide.py, RECORDS) travel the same way: their tensors (`Guide.tensors()`) are
     # buffers; presence and what each record's `key()` holds are baked (by-value arguments of every step node), through `Guide.key()`
     guide: Optional[Guide]
+    # ---- modes ----
+    # baked (max_modes, radius, h0: by-value arguments of the node).  At K > 1, directly after selection: one launch of
+    # `modes(trajs, S)` on the clamped, unscaled K * S candidates.  It reads them and writes buffers of its own: nothing the tick
+    # returns changes.  The ModeSet is left in `modes.last`, in model units whatever `scale_xy` says
+    modes: Optional[TrajectoryModes] = None
     # ---- fallback ----
     # params: a buffer; presence: baked.  After selection and the copy into warm.prev, one launch of `fallback(best, guide)`
     # re-times the [S, H, D] result (the winners at K > 1) in place, against the tick's guide and before the control launch: the
@@ -212,7 +221,7 @@ class TickPlan:
 
     def key(self) -> tuple:
         """Everything baked, as a hashable: two plans with equal keys capture the same graph over the same shapes.  A plan without
-        a fallback keeps the key it had."""
+        a fallback keeps the key it had, and so does one without modes."""
         sel, ctl, pin, guide = self.selector, self.controller, self.pin, self.guide
         weights = None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus)
         if sel is not None and sel.uses_guide:
@@ -223,7 +232,8 @@ class TickPlan:
                self.m_warm, self.shift, self.is_warm, self.motion is None,
                None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), self.velocity is None),
                None if pin is None else (pin.mode, tuple(pin.known.shape)), None if guide is None else guide.key())
-        return key if self.fallback is None else key + (self.fallback.key(),)
+        key = key if self.fallback is None else key + (self.fallback.key(),)
+        return key if self.modes is None else key + (self.modes.key(),)
 
 
 def _hoists(model) -> bool:
@@ -303,17 +313,33 @@ def _fallback_plan(cfg, fallback: Optional[StopShort], guide: Optional[Guide], c
     return fallback
 
 
+def _modes_plan(cfg, modes: Optional[TrajectoryModes], K: int) -> Optional[TrajectoryModes]:
+    """The modes section of `plan_tick`: the modes (None without them), or a refusal."""
+    if modes is None:
+        return None
+    if not isinstance(modes, TrajectoryModes):
+        raise TypeError(f"generate_traj: `modes` must be a TrajectoryModes, got {type(modes).__name__}")
+    if K == 1:
+        raise ValueError("generate_traj: `modes` clusters a scene's candidates and needs candidates > 1 (or EVAL.CANDIDATES > 1)")
+    H = int(cfg.MODEL.HORIZON)
+    if H > MODES_MAX_HORIZON:
+        raise ValueError(f"generate_traj: modes stage a scene's candidates in LDS and need MODEL.HORIZON <= {MODES_MAX_HORIZON}, got {H}")
+    if modes.h0 > H - 1:
+        raise ValueError(f"generate_traj: modes.h0 = {modes.h0} leaves no waypoint of MODEL.HORIZON = {H} to score")
+    return modes
+
+
 def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
               init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, set_timesteps: bool = True,
               noise: Optional[DeviceNoise] = None, step_noise=None, candidates: int = 1,
               selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
               motion: Optional[torch.Tensor] = None, controller: Optional[DeviceController] = None,
               velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, guide: Optional[Guide] = None,
-              fallback: Optional[StopShort] = None, graphed: bool = False) -> TickPlan:
+              fallback: Optional[StopShort] = None, graphed: bool = False, modes: Optional[TrajectoryModes] = None) -> TickPlan:
     """The TickPlan of a `generate_traj` call with these arguments (`graphed`: of a GraphedSampler call).  Pure: no launch, no device
     allocation (but one: a strided `motion` is packed, as it always was), no tick of the noise stream, nothing written to the
     scheduler, `warm` or the controller -- so every refusal comes before any of those and before a capture opens, in the order
-    candidates, `noise` / `step_noise`, warm, control, pin, guide, a selector that needs a guide, fallback.  `scheduler` is read for
+    candidates, `noise` / `step_noise`, warm, control, pin, guide, a selector that needs a guide, fallback, modes.  `scheduler` is read for
     a warm tick on the caller's own timesteps (`set_timesteps=False`), for a pin and for a guide; `is_ddpm` asks it with defaults."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     S, device = int(image.shape[0]), image.device
@@ -395,6 +421,7 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
     if K > 1 and selector.uses_guide and guide is None:
         raise ValueError(f"generate_traj: {selector!r} scores the candidates against a guide; pass guide=Guide(...) for the tick")
     fallback = _fallback_plan(cfg, fallback, guide, controller, image)
+    modes = _modes_plan(cfg, modes, K)
     rows = K * S if init_trajs is None else int(init_trajs.shape[0])
     free = use == GuidanceType.FREE_GUIDANCE
     return TickPlan(S=S, K=K, selector=selector if K > 1 else None, rows=rows, H=H, D=D, n=n, use=use,
@@ -404,7 +431,7 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
                     start="warm" if is_warm else "init" if init_trajs is not None else "randn" if noise is None else "stream",
                     m_warm=m_warm, shift=shift, is_warm=is_warm, motion=motion, i0=n - m_warm if is_warm else 0,
                     controller=controller, velocity=velocity, pin=pin, entry_blend=pin is not None and pin.mode == "clean",
-                    guide=guide, fallback=fallback)
+                    guide=guide, fallback=fallback, modes=modes)
 
 
 def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
@@ -414,18 +441,20 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
                   selector: Optional[TrajectorySelector] = None, return_selection: bool = False,
                   warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
                   controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None,
-                  pin: Optional[Pin] = None, guide: Optional[Guide] = None, fallback: Optional[StopShort] = None):
+                  pin: Optional[Pin] = None, guide: Optional[Guide] = None, fallback: Optional[StopShort] = None,
+                  modes: Optional[TrajectoryModes] = None):
     """One sampling tick: `plan_tick` decides (what each argument means is written on the TickPlan field it becomes), this
     function runs the plan.  With S = image.shape[0] scenes:
 
     `target` [2] or [S, 2]; `init_trajs` [K * S, H, D] or None (a draw); `noise`: a DeviceNoise, of which the call is one tick
     (`begin_tick()` first); `step_noise`: injected DDPM noise tensors instead; `candidates` = K and `selector`: best-of-K;
     `warm` and `motion`: warm start; `controller` and `velocity`: the device controller; `pin`: pinned waypoints; `guide`: cost guidance;
-    `fallback`: the stop-short fallback (its report of this tick is `fallback.last`, a StopResult without `traj`); `fuse`,
-    `set_timesteps`, `scale_xy`: as the module docstring says.
+    `fallback`: the stop-short fallback (its report of this tick is `fallback.last`, a StopResult without `traj`); `modes`:
+    trajectory modes of the K candidates (K > 1; the tick's ModeSet is `modes.last`, in model units; nothing returned changes);
+    `fuse`, `set_timesteps`, `scale_xy`: as the module docstring says.
 
-    The order at the end of a tick is fixed: clamp, selection (K > 1), the copy into `warm.prev`, the fallback, the control launch,
-    xy scaling -- so the warm state sees the clamped, unscaled, pinned, guided result, and the controller and the caller that
+    The order at the end of a tick is fixed: clamp, selection (K > 1), the modes, the copy into `warm.prev`, the fallback, the
+    control launch, xy scaling -- so the warm state sees the clamped, unscaled, pinned, guided result, and the controller and the caller that
     result re-timed by the fallback (when there is one).
 
     Returns `traj` [S, H, D] (the winners at K > 1); `(traj, selection)` with `return_selection=True` (a Selection whose
@@ -434,7 +463,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     bit what the call without a controller returns."""
     plan = plan_tick(model, scheduler, cfg, image, target, init_trajs, fuse=fuse, set_timesteps=set_timesteps, noise=noise,
                      step_noise=step_noise, candidates=candidates, selector=selector, warm=warm, motion=motion,
-                     controller=controller, velocity=velocity, pin=pin, guide=guide, fallback=fallback)
+                     controller=controller, velocity=velocity, pin=pin, guide=guide, fallback=fallback, modes=modes)
     model.eval()
     device, K, S = image.device, plan.K, plan.S
     noise, controller = plan.noise, plan.controller    # from here on the plan is the one source
@@ -482,6 +511,8 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         # the cost is taken in the model's own units (the units of `target` and of the guide)
         sel = plan.selector(trajs, S, scene_tgt, plan.guide) if plan.selector.uses_guide else plan.selector(trajs, S, scene_tgt)
         best = sel.best
+        if plan.modes is not None:
+            plan.modes.last = plan.modes(trajs, S)      # reads the candidates, writes buffers of its own
     if plan.m_warm > 0:
         warm._store(best)
     if plan.fallback is not None:
@@ -636,13 +667,16 @@ class GraphedSampler:
     `fallback=StopShort(...)`: the stop-short launch is a node of the graph after selection and before control
     (`generate_traj(fallback=...)`).  Its params are copied into a static buffer at every call, so new values never capture again;
     its presence is part of the graph key.  The call returns the re-timed plan and `last_fallback` the report of the last replay.
+    `modes=TrajectoryModes(...)`: the modes launch is a node of the graph directly after selection (`generate_traj(modes=...)`); its
+    settings are part of the graph key.  The call returns what it returns without it and `last_modes` the ModeSet of the last replay.
     """
 
     MAX_GRAPHS = 4
 
     def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None,
                  candidates: int = 1, selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
-                 controller: Optional[DeviceController] = None, fallback: Optional[StopShort] = None):
+                 controller: Optional[DeviceController] = None, fallback: Optional[StopShort] = None,
+                 modes: Optional[TrajectoryModes] = None):
         deterministic = getattr(scheduler, "_is_ddim", False) or getattr(scheduler, "deterministic", False)
         if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not deterministic):
             raise ValueError("GraphedSampler needs a deterministic sampler (DDIM with eta = 0, DPM-Solver++), or a DeviceNoise for "
@@ -655,12 +689,14 @@ class GraphedSampler:
         self.candidates, self.selector, self.warm = int(candidates), selector, warm
         self.controller = controller
         self.fallback = fallback
+        self.modes = modes
         self._graphs = {}                      # key -> the captured graph and its static buffers
         self._key = None
         self._graph = None                     # the graph of the last call
         self._sel = None
         self._ctl = None
         self._fb = None
+        self._modes = None
 
     def _capture(self, image, target, init_trajs, motion, velocity=None, pin=None, guide=None):
         dev = image.device
@@ -683,7 +719,7 @@ class GraphedSampler:
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
                                     candidates=self.candidates, selector=self.selector, return_selection=True,
                                     warm=warm, motion=g.motion, controller=ctl, velocity=g.vel, pin=g.pin, guide=g.guide,
-                                    fallback=g.fb)
+                                    fallback=g.fb, modes=self.modes)
         tick = None if self.noise is None else self.noise.tick()
         # the warm-up pass below is a real tick: it moves the noise stream on and overwrites the warm state.  Both are given
         # back, so that the first replay is the next tick and starts from the result of the tick before it
@@ -710,6 +746,7 @@ class GraphedSampler:
         with torch.cuda.graph(g.graph, capture_error_mode="thread_local"):
             g.out, g.sel, g.ctl = run() if ctl is not None else (*run(), None)
         g.fbres = None if g.fb is None else g.fb.last      # the static first, status, stop_at and active_after of the stop-short node
+        g.modes = None if self.modes is None else self.modes.last      # the static outputs of the modes node
         self.model._feat_cache = None          # the memo now points at the static frame buffer: drop it
         g.pointers = self._model_pointers()
         return g
@@ -729,7 +766,7 @@ class GraphedSampler:
         """Forget the captured graphs (call after the model's weights changed: the weight images are packed outside
         the graph, during the warm-up pass of the next capture).  The warm state is the WarmStart's: `warm.reset()`."""
         self._graphs = {}
-        self._key, self._graph, self._sel, self._ctl, self._fb = None, None, None, None, None
+        self._key, self._graph, self._sel, self._ctl, self._fb, self._modes = None, None, None, None, None, None
 
     @property
     def captured(self) -> int:
@@ -764,6 +801,12 @@ class GraphedSampler:
         kept: the call returned the re-timed plan); None before the first call and without a fallback."""
         return None if self._fb is None else StopResult(None, *(t.clone() for t in self._fb[1:]))
 
+    @property
+    def last_modes(self) -> Optional[ModeSet]:
+        """Clones of the static `modes` [M, S, H, D], `index`, `mass`, `assign` and `count` as the last replay left them, in model
+        units; None before the first call and without modes."""
+        return None if self._modes is None else ModeSet(*(None if t is None else t.clone() for t in self._modes))
+
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None,
@@ -771,7 +814,8 @@ class GraphedSampler:
         warm = self.warm
         plan = plan_tick(self.model, self.scheduler, self.cfg, image, target, init_trajs, noise=self.noise,
                          candidates=self.candidates, selector=self.selector, warm=warm, motion=motion,
-                         controller=self.controller, velocity=velocity, pin=pin, guide=guide, fallback=self.fallback, graphed=True)
+                         controller=self.controller, velocity=velocity, pin=pin, guide=guide, fallback=self.fallback, graphed=True,
+                         modes=self.modes)
         motion, pin, guide = plan.motion, plan.pin, plan.guide
         if plan.start == "randn":
             init_trajs = torch.randn((plan.rows, plan.H, plan.D), device=image.device)
@@ -802,7 +846,9 @@ class GraphedSampler:
                 g.guide.copy_(guide)
             if g.fb is not None:
                 g.fb.params.copy_(self.fallback.params)
-        self._key, self._graph, self._sel, self._ctl, self._fb = key, g.graph, g.sel, g.ctl, g.fbres
+        self._key, self._graph, self._sel, self._ctl, self._fb, self._modes = key, g.graph, g.sel, g.ctl, g.fbres, g.modes
+        if self.modes is not None:
+            self.modes.last = g.modes          # the static buffers of the graph that replays now (`last_modes` hands out clones)
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured
         guard = getattr(self.model, "range_guard", "off") == "raise"

@@ -1251,6 +1251,54 @@ int adx_traj_select_guide_capsule(const adx_select_guide_cfg* c, const float* tr
                                   float* best, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Trajectory modes v1: which different manoeuvres a scene's K candidates contain, and how many candidates back each one.  The
+ * candidates are clustered by a greedy cover under a radius, in one launch with no host decision (a node of a captured graph).
+ * No reference counterpart: the reference's train.evaluate draws many trajectories for one image only to paint them
+ * (train.py:62-90).  Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ *   layout   trajs [candidates * scenes][H][D], CANDIDATE-MAJOR as adx_traj_select takes them: candidate k of scene s is row
+ *            k * scenes + s.  modes [max_modes * scenes][H][D], MODE-MAJOR in the same way: mode m of scene s is row
+ *            m * scenes + s, so that the tensor is an M-candidate set to adx_traj_select, adx_traj_metrics and adx_guide_cost as
+ *            it is.  index and mass int32 [scenes][max_modes]; assign int32 [scenes][candidates]; count int32 [scenes]; dist2
+ *            float32 [scenes][candidates][candidates] or NULL (not written).  With K = candidates, M = max_modes, S = scenes:
+ *   points   p_h = (x, y) = the first min(D, 2) columns of waypoint h; a missing y column (D = 1) counts as 0.  Only the waypoints
+ *            h0 <= h <= H-1 are scored, n = H - h0 of them (callers pass h0 = 1: waypoint 0 is the ego pose the sampling loops
+ *            zero).  Units are those of trajs.
+ *   finite   candidate k is finite when every scored x and y of it is finite.  Columns >= 2 and waypoints below h0 are never read
+ *            for a decision (only copied, by `modes`).
+ *   dist2    dist2[i][j] = the mean over the scored h of |p_i,h - p_j,h|^2, in fp32: per h, dx = x_i - x_j, dy = y_i - y_j,
+ *            t_h = dx * dx + dy * dy; the t_h are added one by one in the order h = h0, h0 + 1, .. H-1, starting from t_h0, and the
+ *            sum is divided by (float)n.  Every product, sum and the division is rounded on its own (no contraction).  So
+ *            dist2[i][j] and dist2[j][i] hold the same bits and dist2[i][i] is 0 for a finite i.  Entries that involve a
+ *            non-finite candidate are unspecified and enter no decision.
+ *   near     i and j are near when both are finite and dist2[i][j] <= r2, r2 = radius * radius rounded once in fp32.  A finite
+ *            candidate is near itself.
+ *   greedy cover  alive = the finite candidates.  For m = 0 .. M-1, while alive is not empty: for every alive i, n_i = the number
+ *            of alive j (i included) near i; rep = the smallest i with the largest n_i; index[m] = rep, mass[m] = n_rep; every
+ *            alive j near rep gets assign[j] = m and leaves alive.  count[s] = the number of modes formed.  The masses are
+ *            non-increasing by construction (what is alive only shrinks).
+ *   the rest candidates still alive after M modes are outliers: assign = -1.  Non-finite candidates: assign = -2.  Slots
+ *            m >= count: index = -1, mass = 0.
+ *   modes    for m < count, row m * S + s of modes is row index[m] * S + s of trajs, all H * D values bit for bit.  For
+ *            m >= count it is a copy of mode 0's row (a downstream min over the M rows is then never won by a filler); when
+ *            count = 0 (no finite candidate) all M rows are zeros.
+ *   arithmetic  no atomics and no traffic between workgroups, fixed orders everywhere: the same input gives the same bits on
+ *            every launch, and a scene's result does not depend on the other scenes of the launch.  dist2 is defined up to fp32
+ *            rounding of the operations above (tests/modes_ref.py restates it in fp64 and derives the bound); every integer
+ *            output and modes exactly wherever no |dist2[i][j] - r2| of a finite pair lies within that rounding.
+ *
+ * Limits: 1 <= candidates <= 64, 1 <= max_modes <= 64, 1 <= horizon <= 64, 1 <= dim <= 16, 1 <= scenes <= 65535,
+ * 0 <= h0 <= horizon - 1, radius finite and >= 0.  ADX_ERR_INVALID before any GPU work, each with its own text, for a value out of
+ * range, a NULL pointer other than dist2, or an output that overlaps trajs or another output.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_modes_cfg {
+  int32_t scenes, candidates, horizon, dim, max_modes, h0;
+  float radius;
+} adx_modes_cfg;
+int adx_traj_modes(const adx_modes_cfg* c, const float* trajs, float* modes, int32_t* index, int32_t* mass, int32_t* assign,
+                   int32_t* count, float* dist2 /* or NULL */, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
  * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
  * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
