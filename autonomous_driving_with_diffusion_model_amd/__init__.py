@@ -19,6 +19,8 @@ Public surface mirrors the reference's packages:
                                                        conflict, control/fallback.py)
     TrajectoryModes, ModeSet                          (no reference counterpart: the manoeuvres a scene's K candidates contain and
                                                        the sample mass behind each, control/modes.py)
+    ManoeuvreCommit, CommitResult                     (no reference counterpart: hold the previous tick's manoeuvre unless the
+                                                       selector's new choice is clearly better, control/commit.py)
     OpenLoopMetrics, evaluate_open_loop               (no reference counterpart: ADE / FDE, minADE_K / minFDE_K and miss rates
                                                        against logged waypoints, on the device, evaluation.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
@@ -43,6 +45,7 @@ from .control.select import Selection, TrajectorySelector  # noqa: E402
 from .control.device import DeviceController  # noqa: E402
 from .control.fallback import StopResult, StopShort  # noqa: E402
 from .control.modes import ModeSet, TrajectoryModes  # noqa: E402
+from .control.commit import CommitResult, ManoeuvreCommit  # noqa: E402
 from .pin import Pin  # noqa: E402
 from .guide import Capsules, CostField, Guide, MotionLimits, Route  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
@@ -50,4 +53,5 @@ from .evaluation import MetricsBatch, OpenLoopMetrics, evaluate_open_loop  # noq
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
-           "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop"]
+           "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "ManoeuvreCommit", "CommitResult",
+           "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop"]

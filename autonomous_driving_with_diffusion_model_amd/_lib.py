@@ -118,6 +118,12 @@ class ModesCfg(C.Structure):
                 ("radius", f32)]
 
 
+class CommitCfg(C.Structure):
+    """adx_commit_cfg ("manoeuvre commitment v1", include/adx.h)."""
+    _fields_ = [("scenes", i32), ("candidates", i32), ("horizon", i32), ("dim", i32), ("h0", i32), ("shift", i32), ("max_hold", i32),
+                ("radius", f32), ("margin", f32), ("ratio", f32)]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -263,6 +269,9 @@ _LAZY_SIGS = {
     "adx_stop_short": (i32, [vp, C.POINTER(GuideDesc), C.POINTER(FieldDesc), C.POINTER(RouteDesc), C.POINTER(CapsuleDesc), vp, i32, vp, vp,
                              vp, vp, vp, i32, i32, i32, vp]),
     "adx_traj_modes": (i32, [C.POINTER(ModesCfg), vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_commit_state_bytes": (C.c_size_t, [i32, i32]),
+    "adx_commit_reset": (i32, [vp, i32, i32, vp, vp]),
+    "adx_traj_commit": (i32, [C.POINTER(CommitCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 # the guided exports: five families (the three steps, the cost, the guided selection) times five suffixes, each suffix taking the

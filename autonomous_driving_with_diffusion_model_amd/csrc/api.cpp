@@ -371,6 +371,16 @@ int adx_traj_modes(const adx_modes_cfg* c, const float* trajs, float* modes, int
                    int32_t* count, float* dist2, adx_stream s) {
   return adx::traj_modes(c, trajs, modes, index, mass, assign, count, dist2, (hipStream_t)s);
 }
+size_t adx_commit_state_bytes(int32_t scenes, int32_t horizon) { return adx::commit_state_bytes(scenes, horizon); }
+int adx_commit_reset(void* state, int32_t scenes, int32_t horizon, const uint8_t* mask, adx_stream s) {
+  return adx::commit_reset(state, scenes, horizon, mask, (hipStream_t)s);
+}
+int adx_traj_commit(const adx_commit_cfg* c, const float* trajs, const float* cost, const int32_t* selected, const int32_t* active,
+                    const float* motion, void* state, float* best, int32_t* index, int32_t* status, int32_t* follower,
+                    int32_t* blocked, float* dist2, adx_stream s) {
+  return adx::traj_commit(c, trajs, cost, selected, active, motion, state, best, index, status, follower, blocked, dist2,
+                          (hipStream_t)s);
+}
 int adx_capsules_from_boxes(const float* boxes, float* out, int32_t scenes, int32_t n_boxes, float inflate, adx_stream s) {
   return adx::capsules_from_boxes(boxes, out, scenes, n_boxes, inflate, (hipStream_t)s);
 }

@@ -25,6 +25,19 @@ struct ByteSpan {
 
 inline __host__ __device__ bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for inf and NaN
 
+// u[h][d] of "warm start v1": the waypoint `shift` steps on; past the end xy go on in a straight line, the rest is held.  Shared by
+// warm_init_kernel (sched.hip) and the prior of "manoeuvre commitment v1" (commit.hip), which reads a stored [H][2] plan
+__device__ __forceinline__ float warm_advance(const float* p, int h, int d, int H, int D, int shift) {
+#pragma clang fp contract(off)
+  const int j = h + shift;
+  if (j <= H - 1) return p[j * D + d];
+  const float last = p[(H - 1) * D + d];
+  if (d >= 2) return last;
+  const float step = last - p[(H - 2) * D + d];
+  const float run = (float)(j - (H - 1)) * step;
+  return last + run;
+}
+
 // A [rows][horizon][dim] launch: not empty, and small enough for the kernels' int element index (and the e + total of the
 // classifier-free combine)
 inline int shape_check(const char* what, int rows, int horizon, int dim) {
@@ -101,6 +114,12 @@ int traj_select_guide(const adx_select_guide_cfg* c, const float* trajs, const f
 // "Trajectory modes v1" (modes.hip)
 int traj_modes(const adx_modes_cfg* c, const float* trajs, float* modes, int32_t* index, int32_t* mass, int32_t* assign,
                int32_t* count, float* dist2, hipStream_t s);
+// "Manoeuvre commitment v1" (commit.hip)
+size_t commit_state_bytes(int scenes, int horizon);
+int commit_reset(void* state, int scenes, int horizon, const uint8_t* mask, hipStream_t s);
+int traj_commit(const adx_commit_cfg* c, const float* trajs, const float* cost, const int32_t* selected, const int32_t* active,
+                const float* motion, void* state, float* best, int32_t* index, int32_t* status, int32_t* follower, int32_t* blocked,
+                float* dist2, hipStream_t s);
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);

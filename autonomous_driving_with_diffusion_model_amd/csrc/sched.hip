@@ -781,18 +781,6 @@ struct WarmArgs {
   int total, prev_rows, horizon, dim, shift, zero_first;
 };
 
-// u[h][d] of the contract: the waypoint `shift` steps on; past the end xy go on in a straight line, the rest is held
-__device__ __forceinline__ float warm_advance(const float* p, int h, int d, int H, int D, int shift) {
-#pragma clang fp contract(off)
-  const int j = h + shift;
-  if (j <= H - 1) return p[j * D + d];
-  const float last = p[(H - 1) * D + d];
-  if (d >= 2) return last;
-  const float step = last - p[(H - 2) * D + d];
-  const float run = (float)(j - (H - 1)) * step;
-  return last + run;
-}
-
 __global__ void __launch_bounds__(256) warm_init_kernel(const WarmArgs a) {
 #pragma clang fp contract(off)
   const int e = blockIdx.x * 256 + threadIdx.x;

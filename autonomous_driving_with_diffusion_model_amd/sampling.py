@@ -44,6 +44,10 @@ one launch between selection and control; the controller and the caller get the 
 A fourteenth says what the K candidates contain: `modes=TrajectoryModes(...)` clusters them per scene into the manoeuvres they
 stand for and counts the sample mass behind each ("trajectory modes v1", control/modes.py), one launch directly after selection
 that alters nothing the tick returns; the result is left in `modes.last`.
+A fifteenth keeps the plan from flickering between two manoeuvres of nearly equal cost: `commit=ManoeuvreCommit(...)` holds the
+manoeuvre the previous tick chose unless the selector's new choice is clearly better ("manoeuvre commitment v1",
+control/commit.py), one launch directly after selection whose state lives on the device; everything after it -- the warm state,
+the fallback, the controller, the caller -- follows the committed plan, the selector's own choice stays in `commit.selected`.
 """
 from __future__ import annotations
 
@@ -58,6 +62,7 @@ from . import _lib as L
 from ._lib import AdxRangeError
 from .control.device import DeviceController
 from .control.fallback import MAX_HORIZON as FALLBACK_MAX_HORIZON, NO_POINTWISE_TERM, StopResult, StopShort, pointwise
+from .control.commit import MAX_HORIZON as COMMIT_MAX_HORIZON, CommitResult, ManoeuvreCommit
 from .control.modes import MAX_HORIZON as MODES_MAX_HORIZON, ModeSet, TrajectoryModes
 from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
@@ -212,6 +217,17 @@ class TickPlan:
     # `modes(trajs, S)` on the clamped, unscaled K * S candidates.  It reads them and writes buffers of its own: nothing the tick
     # returns changes.  The ModeSet is left in `modes.last`, in model units whatever `scale_xy` says
     modes: Optional[TrajectoryModes] = None
+    # ---- commit ----
+    # baked (every setting and the state's address: `commit.key()`, and the resolved `commit_shift`); the state itself is read and
+    # advanced through its address.  At K > 1, directly after selection and before the modes: one launch of `commit(trajs, S, sel,
+    # commit_motion, commit_shift)` on the clamped, unscaled K * S candidates.  Past it `best`, `Selection.index` and
+    # `Selection.blocked` are the committed ones: warm.prev, the fallback, the controller and the caller all follow the plan the
+    # vehicle follows.  The CommitResult without `best` is left in `commit.last`; the selector's own index is kept as
+    # `commit.selected` (it differs from the committed `commit.last.index` exactly where `commit.last.status` is HELD)
+    commit: Optional[ManoeuvreCommit] = None
+    commit_shift: int = 0   # baked.  commit.shift, or EVAL.WARM_SHIFT (1) where that is None
+    # buffer; whether it is there is baked.  The tick's `motion` as given, on every tick (`motion` above is None on a cold one)
+    commit_motion: Optional[torch.Tensor] = None
     # ---- fallback ----
     # params: a buffer; presence: baked.  After selection and the copy into warm.prev, one launch of `fallback(best, guide)`
     # re-times the [S, H, D] result (the winners at K > 1) in place, against the tick's guide and before the control launch: the
@@ -221,7 +237,7 @@ class TickPlan:
 
     def key(self) -> tuple:
         """Everything baked, as a hashable: two plans with equal keys capture the same graph over the same shapes.  A plan without
-        a fallback keeps the key it had, and so does one without modes."""
+        a fallback keeps the key it had, and so does one without modes and one without a commit."""
         sel, ctl, pin, guide = self.selector, self.controller, self.pin, self.guide
         weights = None if sel is None else (sel.w_goal, sel.w_smooth, sel.w_consensus)
         if sel is not None and sel.uses_guide:
@@ -233,7 +249,8 @@ class TickPlan:
                None if ctl is None else (id(ctl), ctl.state.data_ptr(), ctl.key(), self.velocity is None),
                None if pin is None else (pin.mode, tuple(pin.known.shape)), None if guide is None else guide.key())
         key = key if self.fallback is None else key + (self.fallback.key(),)
-        return key if self.modes is None else key + (self.modes.key(),)
+        key = key if self.modes is None else key + (self.modes.key(),)
+        return key if self.commit is None else key + ((self.commit.key(), self.commit_shift, self.commit_motion is None),)
 
 
 def _hoists(model) -> bool:
@@ -329,17 +346,43 @@ def _modes_plan(cfg, modes: Optional[TrajectoryModes], K: int) -> Optional[Traje
     return modes
 
 
+def _commit_plan(cfg, commit: Optional[ManoeuvreCommit], K: int, image) -> Tuple[Optional[ManoeuvreCommit], int]:
+    """The commit section of `plan_tick`: (the commit, its resolved shift) -- (None, 0) without one --, or a refusal."""
+    if commit is None:
+        return None, 0
+    if not isinstance(commit, ManoeuvreCommit):
+        raise TypeError(f"generate_traj: `commit` must be a ManoeuvreCommit, got {type(commit).__name__}")
+    if K == 1:
+        raise ValueError("generate_traj: `commit` chooses among a scene's candidates and needs candidates > 1 (or EVAL.CANDIDATES > 1)")
+    H, S = int(cfg.MODEL.HORIZON), int(image.shape[0])
+    if H > COMMIT_MAX_HORIZON:
+        raise ValueError(f"generate_traj: a commit stages a scene's candidates in LDS and needs MODEL.HORIZON <= {COMMIT_MAX_HORIZON}, "
+                         f"got {H}")
+    if commit.scenes != S:
+        raise ValueError(f"the ManoeuvreCommit holds the state of {commit.scenes} scenes, this tick has {S} (image.shape[0]); use a "
+                         "commit of its own for another batch")
+    if commit.horizon != H:
+        raise ValueError(f"the ManoeuvreCommit holds plans of {commit.horizon} waypoints, MODEL.HORIZON is {H}")
+    if commit.device != image.device:
+        raise ValueError(f"the ManoeuvreCommit lives on {commit.device}, the image on {image.device}")
+    shift = commit.resolve_shift(cfg)
+    if not 0 <= shift <= H - 1:
+        raise ValueError(f"ManoeuvreCommit: shift = {shift} must be in 0..{H - 1} (MODEL.HORIZON = {H})")
+    return commit, shift
+
+
 def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
               init_trajs: Optional[torch.Tensor] = None, *, fuse: bool = True, set_timesteps: bool = True,
               noise: Optional[DeviceNoise] = None, step_noise=None, candidates: int = 1,
               selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
               motion: Optional[torch.Tensor] = None, controller: Optional[DeviceController] = None,
               velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, guide: Optional[Guide] = None,
-              fallback: Optional[StopShort] = None, graphed: bool = False, modes: Optional[TrajectoryModes] = None) -> TickPlan:
+              fallback: Optional[StopShort] = None, graphed: bool = False, modes: Optional[TrajectoryModes] = None,
+              commit: Optional[ManoeuvreCommit] = None) -> TickPlan:
     """The TickPlan of a `generate_traj` call with these arguments (`graphed`: of a GraphedSampler call).  Pure: no launch, no device
     allocation (but one: a strided `motion` is packed, as it always was), no tick of the noise stream, nothing written to the
     scheduler, `warm` or the controller -- so every refusal comes before any of those and before a capture opens, in the order
-    candidates, `noise` / `step_noise`, warm, control, pin, guide, a selector that needs a guide, fallback, modes.  `scheduler` is read for
+    candidates, `noise` / `step_noise`, warm, control, pin, guide, a selector that needs a guide, fallback, modes, commit.  `scheduler` is read for
     a warm tick on the caller's own timesteps (`set_timesteps=False`), for a pin and for a guide; `is_ddpm` asks it with defaults."""
     use = GuidanceType[cfg.GUIDANCE.USE_COND]
     S, device = int(image.shape[0]), image.device
@@ -368,13 +411,14 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
     n, H, D = int(cfg.EVAL.SAMPLE_STEPS), int(cfg.MODEL.HORIZON), int(cfg.MODEL.TRANSITION_DIM)
     # ---- warm ----
     if motion is not None:
-        if warm is None:
+        if warm is None and commit is None:
             raise ValueError("generate_traj: `motion` is the odometry of a warm start; pass warm=WarmStart(...) with it")
         # checked on every tick it is given, cold ones included (which do not read it): a wrong shape shows on the first call
         motion = L.require_gpu_f32(motion, "motion")
         if tuple(motion.shape) != (S, 3) or motion.device != device:
             raise ValueError(f"motion must be [{S}, 3] = (tx, ty, phi) per scene on {device}, got {tuple(motion.shape)} "
                              f"on {motion.device}")
+    given_motion = motion          # checked; a commit reads it on every tick, a warm start on a warm one
     m_warm, shift = (0, 0) if warm is None else warm.resolve(cfg)
     is_warm = False
     if m_warm == 0:
@@ -422,6 +466,7 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
         raise ValueError(f"generate_traj: {selector!r} scores the candidates against a guide; pass guide=Guide(...) for the tick")
     fallback = _fallback_plan(cfg, fallback, guide, controller, image)
     modes = _modes_plan(cfg, modes, K)
+    commit, commit_shift = _commit_plan(cfg, commit, K, image)
     rows = K * S if init_trajs is None else int(init_trajs.shape[0])
     free = use == GuidanceType.FREE_GUIDANCE
     return TickPlan(S=S, K=K, selector=selector if K > 1 else None, rows=rows, H=H, D=D, n=n, use=use,
@@ -431,7 +476,8 @@ def plan_tick(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch
                     start="warm" if is_warm else "init" if init_trajs is not None else "randn" if noise is None else "stream",
                     m_warm=m_warm, shift=shift, is_warm=is_warm, motion=motion, i0=n - m_warm if is_warm else 0,
                     controller=controller, velocity=velocity, pin=pin, entry_blend=pin is not None and pin.mode == "clean",
-                    guide=guide, fallback=fallback, modes=modes)
+                    guide=guide, fallback=fallback, modes=modes, commit=commit, commit_shift=commit_shift,
+                    commit_motion=given_motion if commit is not None else None)
 
 
 def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[torch.Tensor] = None,
@@ -442,7 +488,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
                   warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
                   controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None,
                   pin: Optional[Pin] = None, guide: Optional[Guide] = None, fallback: Optional[StopShort] = None,
-                  modes: Optional[TrajectoryModes] = None):
+                  modes: Optional[TrajectoryModes] = None, commit: Optional[ManoeuvreCommit] = None):
     """One sampling tick: `plan_tick` decides (what each argument means is written on the TickPlan field it becomes), this
     function runs the plan.  With S = image.shape[0] scenes:
 
@@ -451,11 +497,15 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     `warm` and `motion`: warm start; `controller` and `velocity`: the device controller; `pin`: pinned waypoints; `guide`: cost guidance;
     `fallback`: the stop-short fallback (its report of this tick is `fallback.last`, a StopResult without `traj`); `modes`:
     trajectory modes of the K candidates (K > 1; the tick's ModeSet is `modes.last`, in model units; nothing returned changes);
-    `fuse`, `set_timesteps`, `scale_xy`: as the module docstring says.
+    `commit`: manoeuvre commitment (K > 1; it takes `motion` with or without a `warm`, on every tick); `fuse`, `set_timesteps`,
+    `scale_xy`: as the module docstring says.
 
-    The order at the end of a tick is fixed: clamp, selection (K > 1), the modes, the copy into `warm.prev`, the fallback, the
-    control launch, xy scaling -- so the warm state sees the clamped, unscaled, pinned, guided result, and the controller and the caller that
-    result re-timed by the fallback (when there is one).
+    The order at the end of a tick is fixed: clamp, selection (K > 1), the commit, the modes, the copy into `warm.prev`, the
+    fallback, the control launch, xy scaling -- so the warm state sees the clamped, unscaled, pinned, guided result, and the
+    controller and the caller that result re-timed by the fallback (when there is one).  Past the commit node `traj`,
+    `Selection.index` and `Selection.blocked` are the COMMITTED ones -- `warm.prev`, the fallback, the controller and the caller all
+    follow the plan the vehicle follows --; the selector's own choice stays readable as `commit.selected` beside `Selection.cost`
+    and `commit.last.index` (`commit.last`: the tick's CommitResult without `best`, which is what the call returns).
 
     Returns `traj` [S, H, D] (the winners at K > 1); `(traj, selection)` with `return_selection=True` (a Selection whose
     `candidates` is the [K, S, H, D] tensor scaled like `traj`; None at K = 1, where no selector runs); with a controller
@@ -463,7 +513,7 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     bit what the call without a controller returns."""
     plan = plan_tick(model, scheduler, cfg, image, target, init_trajs, fuse=fuse, set_timesteps=set_timesteps, noise=noise,
                      step_noise=step_noise, candidates=candidates, selector=selector, warm=warm, motion=motion,
-                     controller=controller, velocity=velocity, pin=pin, guide=guide, fallback=fallback, modes=modes)
+                     controller=controller, velocity=velocity, pin=pin, guide=guide, fallback=fallback, modes=modes, commit=commit)
     model.eval()
     device, K, S = image.device, plan.K, plan.S
     noise, controller = plan.noise, plan.controller    # from here on the plan is the one source
@@ -511,6 +561,13 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
         # the cost is taken in the model's own units (the units of `target` and of the guide)
         sel = plan.selector(trajs, S, scene_tgt, plan.guide) if plan.selector.uses_guide else plan.selector(trajs, S, scene_tgt)
         best = sel.best
+        if plan.commit is not None:
+            # reads the candidates and the selector's outputs, advances its own state; from here on the committed plan is the plan
+            res = plan.commit(trajs, S, sel, plan.commit_motion, plan.commit_shift)
+            plan.commit.selected = sel.index
+            plan.commit.last = CommitResult(None, *res[1:])      # `best` is the tick's result: later nodes re-time and scale it in place
+            best = res.best
+            sel = Selection(best, res.index, sel.cost, None, sel.active, sel.blocked if res.blocked is None else res.blocked)
         if plan.modes is not None:
             plan.modes.last = plan.modes(trajs, S)      # reads the candidates, writes buffers of its own
     if plan.m_warm > 0:
@@ -669,6 +726,12 @@ class GraphedSampler:
     its presence is part of the graph key.  The call returns the re-timed plan and `last_fallback` the report of the last replay.
     `modes=TrajectoryModes(...)`: the modes launch is a node of the graph directly after selection (`generate_traj(modes=...)`); its
     settings are part of the graph key.  The call returns what it returns without it and `last_modes` the ModeSet of the last replay.
+    `commit=ManoeuvreCommit(...)`: the commit launch is a node of the graph between selection and the modes
+    (`generate_traj(commit=...)`); its settings and the address of its state are part of the graph key.  The state lives in the
+    commit's own device buffer, which the graph reads and advances through its address: the first tick and every later one are the
+    same graph, and replay k of a fresh sampler sees the state k eager ticks leave (the capture's warm-up pass, a real tick, is
+    undone).  `motion` is copied into its static buffer at every call and reaches the node on every tick, with or without a `warm`.
+    The call returns the committed plan, `last_selection` the committed index and `last_commit` the CommitResult of the last replay.
     """
 
     MAX_GRAPHS = 4
@@ -676,7 +739,7 @@ class GraphedSampler:
     def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None,
                  candidates: int = 1, selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
                  controller: Optional[DeviceController] = None, fallback: Optional[StopShort] = None,
-                 modes: Optional[TrajectoryModes] = None):
+                 modes: Optional[TrajectoryModes] = None, commit: Optional[ManoeuvreCommit] = None):
         deterministic = getattr(scheduler, "_is_ddim", False) or getattr(scheduler, "deterministic", False)
         if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not deterministic):
             raise ValueError("GraphedSampler needs a deterministic sampler (DDIM with eta = 0, DPM-Solver++), or a DeviceNoise for "
@@ -690,6 +753,7 @@ class GraphedSampler:
         self.controller = controller
         self.fallback = fallback
         self.modes = modes
+        self.commit = commit
         self._graphs = {}                      # key -> the captured graph and its static buffers
         self._key = None
         self._graph = None                     # the graph of the last call
@@ -697,6 +761,7 @@ class GraphedSampler:
         self._ctl = None
         self._fb = None
         self._modes = None
+        self._commit = None
 
     def _capture(self, image, target, init_trajs, motion, velocity=None, pin=None, guide=None):
         dev = image.device
@@ -719,13 +784,14 @@ class GraphedSampler:
                                     fuse=True, scale_xy=self.scale_xy, set_timesteps=False, noise=self.noise,
                                     candidates=self.candidates, selector=self.selector, return_selection=True,
                                     warm=warm, motion=g.motion, controller=ctl, velocity=g.vel, pin=g.pin, guide=g.guide,
-                                    fallback=g.fb, modes=self.modes)
+                                    fallback=g.fb, modes=self.modes, commit=self.commit)
         tick = None if self.noise is None else self.noise.tick()
         # the warm-up pass below is a real tick: it moves the noise stream on and overwrites the warm state.  Both are given
         # back, so that the first replay is the next tick and starts from the result of the tick before it
         valid = warm is not None and warm.valid
         prev = warm.prev.clone() if valid else None
         windows = None if ctl is None else ctl.state_snapshot()       # ... and pushes a sample into every PID window
+        held = None if self.commit is None else self.commit.state_snapshot()      # ... and moves the commit state on one tick
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):          # warm-up off the capture: lazy packs, workspaces, tile tables (and warm.prev)
@@ -739,6 +805,8 @@ class GraphedSampler:
                 warm.prev.copy_(prev)
         if windows is not None:
             ctl.state_restore(windows)
+        if held is not None:
+            self.commit.state_restore(held)
         self.model._feat_cache = None          # the perception pass must be IN the graph (new frame every tick)
         g.graph = torch.cuda.CUDAGraph()
         # thread-local capture mode: a process group's watchdog thread (multi-rank runs) may query events while this
@@ -747,6 +815,8 @@ class GraphedSampler:
             g.out, g.sel, g.ctl = run() if ctl is not None else (*run(), None)
         g.fbres = None if g.fb is None else g.fb.last      # the static first, status, stop_at and active_after of the stop-short node
         g.modes = None if self.modes is None else self.modes.last      # the static outputs of the modes node
+        g.commit = None if self.commit is None else self.commit.last   # ... and of the commit node
+        g.selected = None if self.commit is None else self.commit.selected
         self.model._feat_cache = None          # the memo now points at the static frame buffer: drop it
         g.pointers = self._model_pointers()
         return g
@@ -767,6 +837,7 @@ class GraphedSampler:
         the graph, during the warm-up pass of the next capture).  The warm state is the WarmStart's: `warm.reset()`."""
         self._graphs = {}
         self._key, self._graph, self._sel, self._ctl, self._fb, self._modes = None, None, None, None, None, None
+        self._commit = None
 
     @property
     def captured(self) -> int:
@@ -807,6 +878,12 @@ class GraphedSampler:
         units; None before the first call and without modes."""
         return None if self._modes is None else ModeSet(*(None if t is None else t.clone() for t in self._modes))
 
+    @property
+    def last_commit(self) -> Optional[CommitResult]:
+        """Clones of the static `index`, `status`, `follower`, `dist2` and `blocked` as the last replay left them (`best` is not
+        kept: the call returned the committed plan); None before the first call and without a commit."""
+        return None if self._commit is None else CommitResult(*(None if t is None else t.clone() for t in self._commit))
+
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None,
@@ -815,8 +892,9 @@ class GraphedSampler:
         plan = plan_tick(self.model, self.scheduler, self.cfg, image, target, init_trajs, noise=self.noise,
                          candidates=self.candidates, selector=self.selector, warm=warm, motion=motion,
                          controller=self.controller, velocity=velocity, pin=pin, guide=guide, fallback=self.fallback, graphed=True,
-                         modes=self.modes)
-        motion, pin, guide = plan.motion, plan.pin, plan.guide
+                         modes=self.modes, commit=self.commit)
+        # one static buffer serves the warm start (warm ticks) and the commit node (every tick)
+        motion, pin, guide = plan.motion if plan.commit_motion is None else plan.commit_motion, plan.pin, plan.guide
         if plan.start == "randn":
             init_trajs = torch.randn((plan.rows, plan.H, plan.D), device=image.device)
         # init_trajs None (with a DeviceNoise): the initial trajectory is drawn inside the graph, from INIT_SLOT
@@ -849,6 +927,9 @@ class GraphedSampler:
         self._key, self._graph, self._sel, self._ctl, self._fb, self._modes = key, g.graph, g.sel, g.ctl, g.fbres, g.modes
         if self.modes is not None:
             self.modes.last = g.modes          # the static buffers of the graph that replays now (`last_modes` hands out clones)
+        self._commit = g.commit
+        if self.commit is not None:
+            self.commit.last, self.commit.selected = g.commit, g.selected
         # range_guard = "raise": what an eager forward does around its pass (clear, run, read), here around the replay -- the
         # check is skipped while the graph is captured
         guard = getattr(self.model, "range_guard", "off") == "raise"

@@ -1299,6 +1299,81 @@ int adx_traj_modes(const adx_modes_cfg* c, const float* trajs, float* modes, int
                    int32_t* count, float* dist2 /* or NULL */, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Manoeuvre commitment v1: hold the manoeuvre the previous tick chose unless the selector's new choice is clearly better.  A
+ * selector that takes the arg-min of a cost over fresh samples changes its mind on sampling noise alone wherever two manoeuvres
+ * cost nearly the same; this node, one launch between selection and everything that consumes the winner, compares the K
+ * candidates with the plan the last tick chose (moved on by the odometry) and keeps the cheapest candidate near that plan while
+ * the selector's own is not better by a threshold.  Everything it needs is on the device and it advances its own state there: no
+ * host decision, the same node on the first tick and on every later one (a node of a captured graph).  No reference counterpart:
+ * the reference samples one trajectory per tick (interact.py:110-140).  Callers and fixtures depend on this definition -- a change
+ * is a new version, never an edit.
+ *
+ *   layout   trajs [candidates * scenes][H][D], CANDIDATE-MAJOR exactly as adx_traj_select takes them (candidate k of scene s is
+ *            row k * scenes + s): the clamped, unscaled candidates.  cost float32 [scenes][candidates] and selected int32 [scenes]:
+ *            the selector's cost and index outputs.  active int32 [scenes][candidates]: the guided selector's violation counts, or
+ *            NULL.  motion float32 [scenes][3] = (tx, ty, phi) with warm start v1's meaning, or NULL.  best [scenes][H][D]; index,
+ *            status, follower int32 [scenes]; blocked int32 [scenes] or NULL; dist2 float32 [scenes][candidates].  With
+ *            K = candidates, S = scenes:
+ *   state    one device buffer of adx_commit_state_bytes(scenes, horizon) bytes: 32-bit words [scenes][2 + 2H].  Word 0: `valid`,
+ *            int32.  Word 1: `held`, int32, the consecutive ticks the node has overridden the selector.  Words 2 + 2h and 3 + 2h:
+ *            x and y (float32) of waypoint h of the plan chosen on the last tick, in that tick's frame.  All zero bytes = fresh.
+ *            Every launch reads and advances the state through its address -- nothing about it is a by-value argument -- so a
+ *            captured graph carries it from replay to replay, the first tick included.  A scene's state is read completely
+ *            before any word of it is written.
+ *   prior    for valid != 0: q_h, h = 0 .. H-1, is warm start v1's `advance` followed by its `re-base`, applied to the stored
+ *            [H][2] plan (columns 0 and 1 alone) with this launch's `shift` and `motion`: the same operations in the same order,
+ *            every one rounded on its own (no contraction); without motion the origin is the stored waypoint `shift`.  It is not
+ *            clamped and draws no noise.  With motion, cos(phi) and sin(phi) are the device library's cosf and sinf.  The prior is
+ *            ABSENT when valid == 0 or any scored q_h (below) has a non-finite x or y.
+ *   points   p_k,h = (x, y) = the first min(D, 2) columns of waypoint h of candidate k; a missing y column (D = 1) counts as 0.
+ *            Only the waypoints h0 <= h <= H-1 are scored, n = H - h0 of them.
+ *   dist2    d_k = the mean over the scored h of |p_k,h - q_h|^2 in trajectory modes v1's arithmetic: per h, dx = x_k - qx,
+ *            dy = y_k - qy, t_h = dx * dx + dy * dy; the t_h are added one by one in the order h = h0 .. H-1 starting from t_h0,
+ *            and the sum is divided by (float)n; every operation rounded on its own.  dist2[s][k] = d_k.  Entries of non-finite
+ *            candidates are unspecified; all of dist2 is unspecified when the prior is absent.
+ *   finite   candidate k is finite when every scored x and y of it is finite.
+ *   near     k is near when it is finite and d_k <= r2, r2 = radius * radius rounded once in fp32.
+ *   eligible k is eligible when it is near, cost[k] is finite, and (active is NULL, or active[k] == 0, or active[sel] != 0): a
+ *            violating follower never replaces a free winner.
+ *   decision with sel = selected[s] (a value outside 0..K-1 cannot be refused on the host: the kernel CLAMPS it into range), the
+ *            first rule that matches:
+ *              status 0  NO_PRIOR   the prior is absent                                              chosen = sel
+ *              status 1  SAME       sel is near                                                      chosen = sel
+ *              status 2  LOST       no candidate is eligible                                         chosen = sel
+ *              status 3  HELD       f = the eligible candidate of smallest cost (ties: the lowest index); cost[f] <= t with
+ *                                   t = (cost[sel] + margin) + ratio * fabsf(cost[sel]), every operation rounded on its own; and
+ *                                   max_hold == 0 or held < max_hold                                 chosen = f
+ *              status 4  SWITCHED   otherwise                                                        chosen = sel
+ *            A NaN in any comparison makes it false.  follower[s] = f, or -1 where no f was formed (statuses 0, 1, 2).
+ *   outputs  best[s] = row chosen * S + s of trajs, all H * D words bit for bit; index[s] = chosen; status[s]; follower[s];
+ *            blocked[s] = (active[chosen] != 0), written only when both active and blocked are given.
+ *   update   held' = held + 1 on HELD, otherwise 0.  When the chosen candidate is finite: valid' = 1 and the stored x and y become
+ *            its columns 0 and 1 of ALL H waypoints (y = 0 when D = 1).  Otherwise valid' = 0 and the stored plan keeps its words.
+ *   arithmetic  no atomics and no traffic between workgroups, fixed orders everywhere: the same input and state give the same bits
+ *            on every launch, and a scene's result does not depend on the other scenes of the launch.  Without motion nothing
+ *            above is transcendental and every output and the next state are defined to the bit (tests/commit_ref.py restates
+ *            them in fp32); with motion dist2 is defined up to the rounding tests/commit_ref.py derives (dist2_bound), and the
+ *            decisions exactly wherever no finite candidate's |d_k - r2| lies within it.
+ *
+ * adx_commit_reset zeroes the state of every scene (mask NULL) or of the scenes whose mask byte is not 0 (uint8 [scenes]): one
+ * small capturable launch.  adx_commit_state_bytes is 0 for a value out of range.
+ *
+ * Limits: 1 <= candidates <= 64, 2 <= horizon <= 64 (advance reads waypoint H-2), 1 <= dim <= 16, 1 <= scenes <= 65535,
+ * 0 <= h0 <= horizon - 1, 0 <= shift <= horizon - 1, max_hold >= 0, radius, margin and ratio finite and >= 0.  ADX_ERR_INVALID
+ * before any GPU work, each with its own text, for a value out of range, a NULL pointer other than active, motion and blocked,
+ * blocked given without active, an output that overlaps an input, the state or another output, or a state that overlaps an input.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_commit_cfg {
+  int32_t scenes, candidates, horizon, dim, h0, shift, max_hold;
+  float radius, margin, ratio;
+} adx_commit_cfg;
+size_t adx_commit_state_bytes(int32_t scenes, int32_t horizon);
+int adx_commit_reset(void* state, int32_t scenes, int32_t horizon, const uint8_t* mask /* or NULL: all */, adx_stream s);
+int adx_traj_commit(const adx_commit_cfg* c, const float* trajs, const float* cost, const int32_t* selected,
+                    const int32_t* active /* or NULL */, const float* motion /* or NULL */, void* state, float* best, int32_t* index,
+                    int32_t* status, int32_t* follower, int32_t* blocked /* or NULL */, float* dist2, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
  * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
  * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
