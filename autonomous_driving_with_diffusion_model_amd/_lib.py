@@ -258,6 +258,8 @@ _SIGS = {
 _LAZY_SIGS = {
     "adx_resnet_plan_grids": (i32, [vp, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32]),
     "adx_conv2d_hs3x3q_walk": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+    "adx_conv2d_hs3x3_pair_walk": (i32, [i32, C.POINTER(i32), C.POINTER(i32), i32]),
+    "adx_conv2d_hs3x3_plan_query": (i32, [C.POINTER(Conv2dDesc), i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "adx_conv2d_pack_ds": (i32, [i32, i32, vp, vp, vp]),
     "adx_conv2d_block_s2_cells": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "adx_ddim_step_pin": (i32, [C.POINTER(StepCoef), vp, vp, vp, vp, i32, i64, C.POINTER(PinDesc), vp, vp, i32, i32, i32, vp]),

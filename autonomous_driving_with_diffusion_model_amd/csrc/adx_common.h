@@ -63,7 +63,8 @@ struct DebugSwitches {
                                //                    sums in index order instead of with float atomics: bit-reproducible, one more pass
   bool hs_dma = true;          // ADX_HS_DMA=0       conv2d_hs3x3q stages its operands through registers instead of with LDS-DMA loads (conv2d_hs16.hip)
   bool hs_s2q = true;          // ADX_HS_S2Q=0       the stride-2 block entries stay on conv2d_hs_kernel (32x32x16) where conv2d_hs3x3q_s2_kernel would serve them
-  bool hs_persist = true;      // ADX_HS_PERSIST=0   conv2d_hs3x3q launches one workgroup per tile instead of one per CU that walks the tiles
+  bool hs_pair = true;         // ADX_HS_PAIR=0      the 4-wave tile of conv2d_hs3x3_kernel stays on 32x32x16 MFMAs (A/B runs of the PAIR form)
+  bool hs_persist = true;      // ADX_HS_PERSIST=0  conv2d_hs3x3q launches one workgroup per tile instead of one per CU that walks the tiles
   int hs_reserve_cus = -1;     // ADX_HS_RESERVE_CUS=<n>  compute units (a multiple of 8; default 0) the persistent conv2d_hs3x3q launches leave
                                //                    free: grid = 8 x ((CUs - n) / 8) workgroups.  Set, it also overrides the eval plan's own reserve
   int hs_grid_cap = 0;         // ADX_HS_GRID_CAP=<n>  (tests) at most n workgroups (a multiple of 8) per persistent conv2d_hs3x3q launch: deep

@@ -52,6 +52,7 @@ const DebugSwitches& debug_switches() {
     d.check_range = is("ADX_CHECK_RANGE", '1');
     d.hs_dma = !is("ADX_HS_DMA", '0');
     d.hs_persist = !is("ADX_HS_PERSIST", '0');
+    d.hs_pair = !is("ADX_HS_PAIR", '0');
     d.hs_s2q = !is("ADX_HS_S2Q", '0');
     d.wgrad_deterministic = is("ADX_WGRAD_DETERMINISTIC", '1');
     if (const char* e = getenv("ADX_CHAIN_MASK")) d.chain_mask = (unsigned)strtoul(e, nullptr, 0);

@@ -1013,6 +1013,62 @@ int adx_conv2d_hs3x3q_walk(int32_t units, int32_t cout_tiles, int32_t grid, int3
   return ADX_OK;
 }
 
+// The stage walk of conv2d_hs3x3_kernel's PAIR form over `nchunks` 16-channel chunks, from the tables the kernel's stage loop reads
+// (hs_pair_stage, hs_pair_run); which stage fetches and writes what is this function's copy of that loop (prologue = stage -1),
+// which the GPU tests cover.  Events of ADX_PAIR_EVENT_INTS words: include/adx.h.
+int adx_conv2d_hs3x3_pair_walk(int32_t nchunks, int32_t* n_events, int32_t* events, int32_t max_events) {
+  ADX_REQUIRE(n_events && events && nchunks >= 2 && nchunks % 2 == 0 && max_events >= 1, "adx_conv2d_hs3x3_pair_walk: %d chunks, room for %d events",
+              nchunks, max_events);
+  const int npairs = nchunks / 2, nstages = 9 * npairs;
+  int n = 0;
+  auto put = [&](int stage, int kind, int chunk, int tr, int cb, int rs, int idle) {
+    if (n < max_events) {
+      const int32_t e[ADX_PAIR_EVENT_INTS] = {stage, kind, chunk, tr, cb, rs, idle};
+      memcpy(events + (size_t)n * ADX_PAIR_EVENT_INTS, e, sizeof(e));
+    }
+    ++n;
+  };
+  // prologue: stage 0's weights and the first chunk complete in LDS; stage 1's weights and chunk 1's first round in flight
+  put(-1, ADX_PAIR_FETCH_W, -1, -1, -1, 0, 0);
+  put(-1, ADX_PAIR_WRITE_W, -1, -1, 0, 0, 0);
+  for (int k = 0; k < 3; ++k) { put(-1, ADX_PAIR_FETCH_P, 0, k, -1, -1, 0); put(-1, ADX_PAIR_WRITE_P, 0, k, 0, -1, 0); }
+  put(-1, ADX_PAIR_FETCH_W, -1, -1, -1, 1, 0);
+  put(-1, ADX_PAIR_FETCH_P, 1, 0, -1, -1, 0);
+  for (int pair = 0; pair < npairs; ++pair)
+    for (int i = 0; i < 9; ++i) {
+      const int s = 9 * pair + i;
+      const HsPairStage st = hs_pair_stage(i), nx = hs_pair_stage((i + 1) % 9);
+      put(s, ADX_PAIR_FETCH_W, -1, -1, -1, s + 2 < nstages ? s + 2 : nstages - 1, s + 2 >= nstages);
+      if (nx.pround >= 0) {
+        const int c = 2 * pair + 1 + (i == 8 ? 2 : nx.pnext);
+        put(s, ADX_PAIR_FETCH_P, c < nchunks ? c : nchunks - 1, nx.pround, -1, -1, c >= nchunks);
+      }
+      for (int t = 0; t < 2; ++t)
+        put(s, ADX_PAIR_READ, 2 * pair + st.tap[t].odd, st.tap[t].kh * 3 + i % 3, st.tap[t].odd, hs_pair_run(pair, i, t) / 256, s & 1);
+      put(s, ADX_PAIR_WRITE_W, -1, -1, (s + 1) & 1, s + 1 < nstages ? s + 1 : nstages - 1, s + 1 >= nstages);
+      if (st.pround >= 0) {
+        const int c = 2 * pair + 1 + st.pnext;
+        put(s, ADX_PAIR_WRITE_P, c < nchunks ? c : nchunks - 1, st.pround, st.pnext ? 0 : 1, -1, c >= nchunks);
+      }
+    }
+  *n_events = n;
+  ADX_REQUIRE(n <= max_events, "adx_conv2d_hs3x3_pair_walk: %d events, room for %d", n, max_events);
+  return ADX_OK;
+}
+
+// What conv2d_hs3x3_plan answers for a launch of this conv (no device needed): out = [family, tile mode, ksplit, PAIR form, admitted]
+int adx_conv2d_hs3x3_plan_query(const adx_conv2d_desc* d, int32_t n, int32_t h, int32_t w, int32_t fmt, int32_t has_res, int32_t* out) {
+  ConvSpec L;
+  const int rc = spec_from_desc(d, &L);
+  if (rc != ADX_OK) return rc;
+  ADX_REQUIRE(out && n >= 1 && h >= 1 && w >= 1 && fmt >= 0 && fmt <= 7, "adx_conv2d_hs3x3_plan_query: n %d, %d x %d, fmt %d", n, h, w, fmt);
+  Hs3x3Query q;
+  q.N = n; q.H = h; q.W = w; q.fmt = fmt; q.affine = true; q.relu = true; q.has_res = has_res != 0; q.cus = 256;
+  const Hs3x3Plan p = L.k == 3 && L.stride == 1 ? conv2d_hs3x3_plan(L, q) : Hs3x3Plan{};
+  out[0] = p.family; out[1] = p.mode; out[2] = p.ksplit; out[3] = p.pair ? 1 : 0; out[4] = p.admitted ? 1 : 0;
+  return ADX_OK;
+}
+
 static int resnet_forward_impl(adx_resnet* r, const void* packed, void* workspace, const float* img,
                                const uint8_t* frames_u8, const float* mean, const float* stdv, int32_t batch, int32_t h,
                                int32_t w, float* feature, adx_stream stream);

@@ -478,15 +478,28 @@ __device__ __forceinline__ void hs_trace_id() {
 // VR: the column tiles run over the virtual row of the whole batch (below) although the OUTPUT is fp32 NCHW -- the training
 // forward and data-gradient launches (round 5): a map 225 / 113 / 57 / 29 columns wide pays one padded MFMA column per image
 // instead of the round-up to 32, like the cell launches; YCELLS implies it.
-template <int MODE, int STATS = 0, bool XCELLS = false, bool YCELLS = false, bool VR = false>
+// PAIR (MODE 0, STATS 0): the same tile, patch images and packed weights on v_mfma_f32_16x16x32_f16 -- K = 32 is TWO TAPS x the
+// 16 channels of a chunk (conv2d_internal.h: hs_pair_stage), so the patch copies stay what MODE 0 stages (a 32-channel chunk
+// would double them: conv2d_hs16.hip needs 8 waves and a whole CU for that) and a stage's weights are two 256-cell runs, 16 KB
+// double-buffered: 60 KB, two workgroups per CU as before.  Lane (j = lane & 15, kq = lane >> 4), kq = (tap of the stage's
+// pair, k-half of the chunk): the B fragment of pixel block pb is the cell of the lane's tap and k-half at row pb >> 1, column
+// 16 (pb & 1) + j -- from the patch copy of that tap's chunk, a per-lane base where the two taps come from different chunks --
+// and the A fragment of channel block cb the cell tap * 256 + plane * 128 + k-half * 64 + 16 cb + j of the stage's buffer.  The
+// two k-groups that share a ds_read_b128 lane group (MI355X: lanes 0-3, 12-15, 20-27 | ...) differ in the k-half only.  Their
+// weight cells lie 64 cells apart (0 mod 16: complementary banks, conflict-free); their patch cells lie 2 PLANE = 680 cells apart,
+// 8 mod 16, so lanes 20-27 fall on the banks of lanes 0-3 and 12-15: every patch read is 2-way (SQ_LDS_BANK_CONFLICT: a quarter
+// of the launch's LDS cycles, profiles/README.md).  A k-half pitch of 688 cells would remove it; not done yet.  Wave tile 64 channels x (2 rows x 32 columns) as 4 x 4 blocks of 16 x 16: 16
+// fragment reads and 48 MFMAs per stage; the products and their order per accumulator as in conv2d_hs3x3q_kernel.
+template <int MODE, int STATS = 0, bool XCELLS = false, bool YCELLS = false, bool VR = false, bool PAIR = false>
 __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(const Conv2dArgs a) {
+  static_assert(!PAIR || (MODE == 0 && STATS == 0), "the PAIR form is the plain 4-wave tile");
   constexpr bool VROW = YCELLS || VR;
   constexpr int NT = MODE == 0 ? 256 : 512;            // threads
   constexpr int TH = MODE == 1 ? 16 : 8;               // output rows per workgroup
   constexpr int CT = MODE == 2 ? 2 : 1;                // 64-channel slabs per workgroup
   constexpr int K = 3, PH = TH + 2, PW = 34, PLANE = PH * PW, NITEM = 2 * PLANE;
   constexpr int PIT = (NITEM + NT - 1) / NT;           // patch rounds = slices, one per stage while they last
-  constexpr int NW = 9 * 256, WST = 3 * 256 * CT;      // weight cells per chunk and 64-channel slab / per stage
+  constexpr int NW = 9 * 256, WST = PAIR ? 2 * 256 : 3 * 256 * CT;      // weight cells per chunk and 64-channel slab / per stage
   constexpr int WIT = (WST + NT - 1) / NT;
   static_assert(PIT <= K, "a patch slice travels with each stage of a chunk");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -526,7 +539,8 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
   // segment of a tile its own two halo cells, i.e. lanes behind an image boundary read two cells further: a 2-way conflict in
   // nearly every 16-lane group of a tile that holds a boundary -- 25 % of the LDS cycles of the 512-channel layers.)
   const int vx0 = tx * kTileW;
-  const int vl = vx0 + l31;
+  const int ecol = PAIR ? 16 * ((lane >> 4) & 1) + (lane & 15) : l31;      // the tile column this lane's epilogue stores
+  const int vl = vx0 + ecol;
   auto vdiv = [&](int v) { return (int)(((float)v + 0.5f) * a.inv_vw); };     // v / vw for 0 <= v < 2^21 (launch check)
   const int nl = VROW ? vdiv(vl) : 0, xl = VROW ? vl - nl * a.vw : 0;
   const bool lane_valid = !VROW || (nl < a.N && xl < a.W);
@@ -629,6 +643,11 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
   u32x4 wv[2][WIT];
   float pv[2][8];
   auto load_w = [&](int stage, int set) {
+    if constexpr (PAIR) {       // (the prologue's stages 0 and 1 of chunk pair 0; the stage loop passes its runs to load_runs)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) wv[set][k] = wsrc[hs_pair_run(0, stage, k) + tid];
+      return;
+    }
     const u32x4* ws = wsrc + (size_t)stage * 768;
 #pragma unroll
     for (int k = 0; k < WIT; ++k) wv[set][k] = ws[wsrc_off[k]];
@@ -674,6 +693,16 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
     *d1 = lo;
   };
 
+  // 4 channels of a cell pair: hi + lo / 2^11, one v_fma_mix_f32 per value (fp16 operands converted inside the instruction; the
+  // product with a power of two is exact, so this is the same value as convert, multiply, add -- in a third of the instructions)
+  auto half4 = [](uint32_t h0, uint32_t h1, uint32_t l0, uint32_t l1, float* out) {
+    const float inv = 1.f / kLoScale;
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(out[0]) : "v"(l0), "s"(inv), "v"(h0));
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(out[1]) : "v"(l0), "s"(inv), "v"(h0));
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(out[2]) : "v"(l1), "s"(inv), "v"(h1));
+    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(out[3]) : "v"(l1), "s"(inv), "v"(h1));
+  };
+
   const int pb_lane = khalf * 2 * PLANE + (rowpair * 2) * PW + l31;
   const int wa_lane = slab * 768 + khalf * 64 + l31;
 
@@ -689,6 +718,183 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
   HS_TRACE(1);
   __syncthreads();
   HS_TRACE(2);
+
+  if constexpr (PAIR) {
+    const int j = lane & 15, kq = lane >> 4, ts = kq >> 1, kh2 = kq & 1;     // tap slot and k-half of the lane's k-group
+    const int npairs = nchunks >> 1;
+    f32x4 am[4][4], al[4][4];            // [channel block][pixel block]: hi*hi sums, cross-term sums (scaled by 2^11)
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int pb = 0; pb < 4; ++pb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { am[cb][pb][i] = 0.f; al[cb][pb][i] = 0.f; }
+    // the lane's patch cell at column j of the wave's first row, per group of three stages (one pair of kernel rows and copies)
+    const u32x4* pb_g[3];
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+      const HsPairTap t0 = hs_pair_stage(3 * g).tap[0], t1 = hs_pair_stage(3 * g).tap[1];
+      pb_g[g] = patch + kh2 * 2 * PLANE + (rowpair * 2) * PW + j + (ts ? t1.odd * 4 * PLANE + t1.kh * PW : t0.odd * 4 * PLANE + t0.kh * PW);
+    }
+    const int wa_pair = ts * 256 + kh2 * 64 + j;
+    auto load_runs = [&](int o0, int o1, int set) {
+      wv[set][0] = wsrc[o0 + tid];
+      wv[set][1] = wsrc[o1 + tid];
+    };
+    // The nine stages of chunk pair `pair`; par = parity of the pair's first global stage (nine is odd: the register sets and the
+    // weight buffers of a stage alternate with the GLOBAL stage, so the body exists once per parity and every index is a constant).
+    // As in the 32x32x16 loop: weights two stages ahead into the set consumed last stage, a patch round one stage ahead of its
+    // write; past the end the last stage / chunk is fetched again into buffers nobody reads.
+    auto pair_stages = [&](const int par, const int pair) __attribute__((always_inline)) {
+      const bool more = pair + 1 < npairs;
+#pragma unroll
+      for (int i = 0; i < 9; ++i) {
+        const int gp = (i + par) & 1;
+        const HsPairStage st = hs_pair_stage(i), nx = hs_pair_stage((i + 1) % 9);
+        if (i + 2 < 9) load_runs(hs_pair_run(pair, i + 2, 0), hs_pair_run(pair, i + 2, 1), gp);
+        else load_runs(more ? hs_pair_run(pair + 1, i + 2 - 9, 0) : hs_pair_run(pair, 8, 0), more ? hs_pair_run(pair + 1, i + 2 - 9, 1) : hs_pair_run(pair, 8, 1), gp);
+        if (nx.pround >= 0) {        // the round stage i + 1 writes: of this pair's o, the next pair's e or (i == 8) the next pair's o
+          const int c = 2 * pair + 1 + (i == 8 ? 2 : nx.pnext);
+          load_p(c < nchunks ? c : nchunks - 1, nx.pround, gp);
+        }
+        __builtin_amdgcn_sched_barrier(0);      // the fetches stay at the top of the stage
+        const u32x4* pb0 = pb_g[i / 3] + i % 3;
+        const u32x4* wa0 = wl + gp * WST + wa_pair;
+        f16x8 A[2][4], B[2][4];
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+          for (int cb = 0; cb < 4; ++cb) A[pl][cb] = __builtin_bit_cast(f16x8, wa0[pl * 128 + cb * 16]);
+#pragma unroll
+          for (int pb = 0; pb < (XCELLS ? 4 : 2); ++pb) B[pl][pb] = __builtin_bit_cast(f16x8, pb0[pl * PLANE + (pb >> 1) * PW + (pb & 1) * 16]);
+        }
+#pragma unroll
+        for (int pb = 0; pb < 4; ++pb) {
+          if (!XCELLS && pb == 1) {
+            // an fp32 input keeps eight staged values and the split's temporaries beside the accumulators: the second row's
+            // fragments are read once the first pixel block's are dead
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+              for (int q = 2; q < 4; ++q) B[pl][q] = __builtin_bit_cast(f16x8, pb0[pl * PLANE + (q >> 1) * PW + (q & 1) * 16]);
+          }
+#pragma unroll
+          for (int cb = 0; cb < 4; ++cb) {
+            am[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[0][cb], B[0][pb], am[cb][pb], 0, 0, 0);
+            al[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[0][cb], B[1][pb], al[cb][pb], 0, 0, 0);
+          }
+#pragma unroll
+          for (int cb = 0; cb < 4; ++cb) al[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[1][cb], B[0][pb], al[cb][pb], 0, 0, 0);
+          if (pb == (XCELLS ? 0 : 1)) {
+            // what arrived during the previous stage goes to LDS under this stage's remaining MFMAs (an fp32 input is split on
+            // the way: behind the second pixel block, whose fragment registers the split's temporaries then take)
+            store_w(gp ^ 1, gp ^ 1);
+            if (st.pround >= 0) store_p(gp ^ 1, st.pround, st.pnext ? 0 : 1);
+          }
+        }
+        __syncthreads();
+      }
+    };
+    int pair = 0;
+    for (; pair + 1 < npairs; pair += 2) {
+      pair_stages(0, pair);
+      pair_stages(1, pair + 1);
+    }
+    if (pair < npairs) pair_stages(0, pair);
+
+    // ---- epilogue.  Accumulator lane (j, kq) holds channels 16 cb + 4 kq + i of pixel (row pb >> 1, column 16 (pb & 1) + j); the
+    // v_permlane16_swap of a row's two pixel blocks leaves lane (j, kq) with channels 16 cb + 8 (kq >> 1) .. + 7 -- one cell -- of
+    // the pixel at column ecol = 16 (kq & 1) + j: a half wave is 32 consecutive pixels of a channel plane (fp32 output: 128-byte
+    // runs) or 32 consecutive cells.  Affine, residual (fp32, or cells through half4), ReLU and the range status as in MODE 0.
+    const int ox = VROW ? xl : ox0 + ecol;
+    const uint32_t plane_ob = (uint32_t)(a.OH * a.OW) * (uint32_t)sizeof(float);
+    const uint32_t cplane = (uint32_t)(a.OH * a.OW) * 16u;
+    const size_t img = (size_t)n * a.Cout * a.OH * a.OW;
+    const int img_bytes = (int)(uint32_t)((VROW ? (uint32_t)a.N : 1u) * (uint32_t)a.Cout * plane_ob);
+    const uint32_t img_off = VROW ? (uint32_t)nl * (uint32_t)a.Cout * plane_ob : 0u;
+    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(a.y + img, 0, img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.res != nullptr ? a.res + img : a.y), 0, a.res != nullptr ? img_bytes : 0, 0x00020000);
+    const uint32_t cbase_o = (uint32_t)cout0 * plane_ob;
+    const uint32_t cell0 = (uint32_t)(cout0 >> 3) * 2u * cplane;
+    const bool rcells = YCELLS && a.res_cells;
+    bool inside[2];
+    uint32_t vout[2], vres[2];
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+      const int oy = oy0 + rowpair * 2 + rr;
+      inside[rr] = lane_valid && oy < a.OH && ox < a.OW;
+      const uint32_t pix = (uint32_t)(oy * a.OW + ox);
+      const uint32_t vc = img_off + pix * 16u + (uint32_t)ts * 2u * cplane, vf = img_off + pix * 4u + (uint32_t)(8 * ts) * plane_ob;
+      vout[rr] = !inside[rr] ? kOutside : (YCELLS ? vc : vf);
+      vres[rr] = !inside[rr] ? kOutside : (rcells ? vc : vf);
+    }
+    uint32_t rraw[4][2][8];         // residual of the lane's cell (cb, rr): 8 floats, or the hi and lo cells as they are
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        if (rcells) {
+          const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
+          const u32x4 h4 = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vres[rr], so, 0);
+          const u32x4 l4 = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vres[rr], so + cplane, 0);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) { rraw[cb][rr][c] = h4[c]; rraw[cb][rr][4 + c] = l4[c]; }
+        } else {
+#pragma unroll
+          for (int c = 0; c < 8; ++c)
+            rraw[cb][rr][c] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, vres[rr], cbase_o + (uint32_t)(16 * cb + c) * plane_ob, 0);
+        }
+      }
+    float amax = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        float o[8], r8[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int cl = 16 * cb + 4 * kq + i;
+          float x = (am[cb][2 * rr][i] + al[cb][2 * rr][i] * (1.f / kLoScale)) * xs_inv;
+          float y = (am[cb][2 * rr + 1][i] + al[cb][2 * rr + 1][i] * (1.f / kLoScale)) * xs_inv;
+          x = x * ss[cl] + ss[64 + cl];
+          y = y * ss[cl] + ss[64 + cl];
+          const auto sw = __builtin_amdgcn_permlane16_swap(f2u(x), f2u(y), false, false);
+          o[i] = u2f(sw[0]);
+          o[4 + i] = u2f(sw[1]);
+        }
+        if (rcells) {
+          half4(rraw[cb][rr][0], rraw[cb][rr][1], rraw[cb][rr][4], rraw[cb][rr][5], r8);
+          half4(rraw[cb][rr][2], rraw[cb][rr][3], rraw[cb][rr][6], rraw[cb][rr][7], r8 + 4);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 8; ++c) r8[c] = u2f(rraw[cb][rr][c]);
+        }
+        float lm = 0.f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const float t = o[c] + r8[c];
+          o[c] = a.relu ? __builtin_fmaxf(t, 0.f) : t;
+          lm = fp16_amax(lm, o[c]);
+        }
+        amax = fp16_amax(amax, inside[rr] ? lm : 0.f);
+        if constexpr (YCELLS) {
+          u32x4 hi, lo;
+          split8(o, 1.f, hi, lo);
+          const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
+          __builtin_amdgcn_raw_buffer_store_b128(hi, yrsrc, vout[rr], so, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(lo, yrsrc, vout[rr], so + cplane, 0);
+          asm volatile("s_nop 0" ::"v"(hi), "v"(lo));      // (cells_store32: a VALU write in the store's next issue slot)
+        } else {
+#pragma unroll
+          for (int c = 0; c < 8; ++c)
+            __builtin_amdgcn_raw_buffer_store_b32(f2u(o[c]), yrsrc, vout[rr], cbase_o + (uint32_t)(16 * cb + c) * plane_ob, 0);
+        }
+      }
+    range_flag(a.status, out_of_fp16(amax));
+    return;
+  }
 
   for (int cp = 0; cp < nchunks; cp += 2) {
 #pragma unroll
@@ -735,7 +941,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
   // epilogue through buffer descriptors: one instruction per access (wave-uniform channel offset in an SGPR, the
   // lane's pixel in one 32-bit VGPR); lanes outside the map carry the out-of-range offset, so their loads return 0
   // and their stores are dropped; without a residual the descriptor is empty and every load returns 0
-  const int ox = VROW ? xl : ox0 + l31;
+  const int ox = VROW ? xl : ox0 + ecol;
   const uint32_t plane_ob = (uint32_t)(a.OH * a.OW) * (uint32_t)sizeof(float);
   const size_t img = (size_t)n * a.Cout * a.OH * a.OW;
   // YCELLS: the descriptors cover the whole tensors and the lane's image rides in its offset
@@ -757,15 +963,6 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
     inside[rr] = lane_valid && oy < a.OH && ox < a.OW;
     pix[rr] = (uint32_t)(oy * a.OW + ox);
   }
-  // 4 channels of a cell pair: hi + lo / 2^11, one v_fma_mix_f32 per value (fp16 operands converted inside the instruction; the
-  // product with a power of two is exact, so this is the same value as convert, multiply, add -- in a third of the instructions)
-  auto half4 = [](uint32_t h0, uint32_t h1, uint32_t l0, uint32_t l1, float* out) {
-    const float inv = 1.f / kLoScale;
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(out[0]) : "v"(l0), "s"(inv), "v"(h0));
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(out[1]) : "v"(l0), "s"(inv), "v"(h0));
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(out[2]) : "v"(l1), "s"(inv), "v"(h1));
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(out[3]) : "v"(l1), "s"(inv), "v"(h1));
-  };
   float amax = 0.f;        // range status (adx_common.h: fp16_amax); a.status is null for the partial sums of a split reduction
   if constexpr (YCELLS) {
     // cell output (cells_store32); the residual is fetched first: as cells, or as fp32 values at the channels the lane owns AFTER the swap
@@ -1740,12 +1937,13 @@ __global__ void __launch_bounds__(256) conv2d_split_reduce_kernel(const float* _
 }
 
 // LDS bytes of conv2d_hs3x3_kernel<MODE, STATS>: the patch and weight buffers, the BN constants (STATS == 2: + the consumer BatchNorm's)
-static constexpr size_t hs3x3_lds(int mode, int stats) {
+static constexpr size_t hs3x3_lds(int mode, int stats, bool pair = false) {
   const int th = mode == 1 ? 16 : 8, ct = mode == 2 ? 2 : 1;
-  return (size_t)2 * 64 * (th + 2) * 34 + (size_t)2 * 3 * 256 * ct * 16 + (2 * 64 * ct + 8) * sizeof(float) + 48 +
+  return (size_t)2 * 64 * (th + 2) * 34 + (size_t)2 * (pair ? 2 : 3 * ct) * 256 * 16 + (2 * 64 * ct + 8) * sizeof(float) + 48 +
          (stats == 2 ? 4 * 64 * ct * sizeof(float) : 0);
 }
 static_assert(hs3x3_lds(0, 2) <= 80 * 1024 && hs3x3_lds(1, 2) <= 160 * 1024 && hs3x3_lds(2, 2) <= 160 * 1024, "LDS budget");
+static_assert(hs3x3_lds(0, 0, true) <= 80 * 1024, "LDS budget: two workgroups of the PAIR form per CU");
 
 Hs3x3Plan conv2d_hs3x3_plan(const ConvSpec& L, const Hs3x3Query& q, const DebugSwitches& sw) {
   Hs3x3Plan p;
@@ -1823,7 +2021,10 @@ Hs3x3Plan conv2d_hs3x3_plan(const ConvSpec& L, const Hs3x3Query& q, const DebugS
     p.grid = (size_t)8 * p.q_slots;
     return p;
   }
-  p.lds = hs3x3_lds(mode, p.stats);
+  // the PAIR form: every plain launch of the 4-wave tile, whatever its operand formats (a rule on the formats would give the fp32
+  // and the cell launch of one conv different summation orders); ADX_HS_MODE pins the 32x32x16 code
+  p.pair = sw.hs_pair && sw.hs_mode < 0 && mode == 0 && p.ksplit == 1 && !stats;
+  p.lds = hs3x3_lds(mode, p.stats, p.pair);
   if (p.ksplit > 1) return p;
   p.xcells = xc; p.ycells = cells_out;
   p.vr = !cells_out && (!(xc || yc || rc) || ((stats || xscaled) && !yc && !rc)) && vrow_ok;
@@ -1851,16 +2052,26 @@ static const HsKernel* hs3x3_kernels() {
   return table;
 }
 
+// the PAIR instantiations (MODE 0, STATS 0), at the same index
+static const HsKernel* hs3x3_pair_kernels() {
+#define HS_K(X, Y, V) &conv2d_hs3x3_kernel<0, 0, X, Y, V, true>
+  static const HsKernel table[8] = {HS_K(false, false, false), HS_K(false, false, true), HS_K(false, true, false), nullptr,
+                                    HS_K(true, false, false),  HS_K(true, false, true),  HS_K(true, true, false),  nullptr};
+#undef HS_K
+  return table;
+}
+
 static int hs3x3_launch(const Hs3x3Plan& p, Conv2dArgs a, hipStream_t s) {
-  const HsKernel* const table = p.mode == 1 ? hs3x3_kernels<1>() : (p.mode == 2 ? hs3x3_kernels<2>() : hs3x3_kernels<0>());
-  static std::atomic<uint64_t> attr[3];
-  if (DeviceOnce once{attr[p.mode]}; once) {
-    for (int v = 0; v < 3 * 8; ++v)
+  const HsKernel* const table = p.pair ? hs3x3_pair_kernels() : (p.mode == 1 ? hs3x3_kernels<1>() : (p.mode == 2 ? hs3x3_kernels<2>() : hs3x3_kernels<0>()));
+  static std::atomic<uint64_t> attr[4];
+  if (DeviceOnce once{attr[p.pair ? 3 : p.mode]}; once) {
+    for (int v = 0; v < (p.pair ? 8 : 3 * 8); ++v)
       if (table[v] != nullptr)
         ADX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(table[v]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)hs3x3_lds(p.mode, v / 8)));
+                                          (int)hs3x3_lds(p.mode, v / 8, p.pair)));
     once.commit();
   }
+  ADX_REQUIRE(!p.pair || (p.mode == 0 && p.stats == 0 && p.ksplit == 1), "conv2d_hs: the PAIR form is the plain 4-wave tile (internal error)");
   ADX_REQUIRE(p.grid < (1u << 31), "conv2d_hs: grid too large");
   ADX_REQUIRE((size_t)a.Cout * a.OH * a.OW * sizeof(float) < 0x7FFFFFFFu, "conv2d_hs: one image of the output exceeds the 32-bit byte offsets");
   if (p.ycells) {

@@ -157,7 +157,27 @@ struct Hs3x3Plan {
   size_t lds = 0;
   int stats_tiles = 0;            // partial-sum slots per channel when stats != 0
   size_t stats_need = 0;          // floats those take: the sums and (data gradient) max |dz| per 64-channel slab
+  bool pair = false;              // conv2d_hs3x3_kernel's PAIR form (16x16x32 MFMAs over two taps x 16 channels): a rule on the shape
+                                  // and the switches only, never on the operand formats -- every format of a launch sums in one order
 };
+// ---- the stage table of conv2d_hs3x3_kernel's PAIR form (conv2d_hs.hip) ----
+// K = 32 of a 16x16x32 MFMA = two taps x the 16 channels of a chunk.  A pair of chunks (e, o) -- e staged in patch copy E = 0, o
+// in copy O = 1 -- is nine stages of two taps with one kernel column kw = stage % 3.  Copy E is read by stages 0-5 and copy O by
+// stages 3-8, so chunk o lands in O during stages 0-2 of its own pair and the next pair's e in E during stages 6-8, one patch
+// round per stage.  The kernel's stage loop and the export (adx_conv2d_hs3x3_pair_walk) both read this table.
+struct HsPairTap { int odd, kh; };      // chunk of the pair (0: e, 1: o) = the patch copy read; kernel row
+struct HsPairStage {
+  HsPairTap tap[2];
+  int pround;           // patch round written to LDS during this stage (fetched one stage earlier); -1: none
+  int pnext;            // ... a round of 0: this pair's chunk o (copy O), 1: the next pair's chunk e (copy E)
+};
+__host__ __device__ constexpr HsPairStage hs_pair_stage(int i) {
+  return i < 3 ? HsPairStage{{{0, 0}, {0, 1}}, i, 0} : (i < 6 ? HsPairStage{{{0, 2}, {1, 0}}, -1, 0} : HsPairStage{{{1, 1}, {1, 2}}, i - 6, 1});
+}
+// first cell of the weight run of tap slot t of stage i of chunk pair `pair`, from the image of the (64-channel slab, chunk 0)
+__host__ __device__ constexpr int hs_pair_run(int pair, int i, int t) {
+  return ((2 * pair + hs_pair_stage(i).tap[t].odd) * 9 + hs_pair_stage(i).tap[t].kh * 3 + i % 3) * 256;
+}
 Hs3x3Plan conv2d_hs3x3_plan(const ConvSpec& L, const Hs3x3Query& q, const DebugSwitches& sw = debug_switches());
 // ---- the unit walk of conv2d_hs3x3q_kernel (conv2d_hs16.hip) ----
 // A launch's work is `units` = spatial tiles x cout tiles pieces, unit u = spatial tile * cout_tiles + cout tile.  XCD x (workgroup

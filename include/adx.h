@@ -396,6 +396,16 @@ int adx_resnet_plan_grids(const adx_resnet* r, int32_t batch, int32_t h, int32_t
  * cout_tiles units, from the range and unit functions the kernel itself uses.  counts[b]: units workgroup b visits (grid words);
  * visits: (spatial tile, cout tile) pairs, workgroup after workgroup in visiting order (2 x units words). */
 int adx_conv2d_hs3x3q_walk(int32_t units, int32_t cout_tiles, int32_t grid, int32_t* counts, int32_t* visits);
+/* For tests only: the stage walk of the PAIR form of the 4-wave 3x3 stride-1 kernel (16x16x32 MFMAs over two taps x 16 channels) over
+ * `nchunks` (even) 16-channel chunks, as events in program order.  Stage -1 is the prologue; a stage ends with a barrier, so what a
+ * stage writes to LDS is readable from the next stage on.  ADX_PAIR_EVENT_INTS words per event:
+ *   [0] stage  [1] kind  [6] 1: past the end (the last chunk / stage again, into a copy / buffer nobody reads afterwards)
+ *   READ     one of the stage's two taps: [2] chunk [3] tap = 3 kh + kw [4] patch copy [5] weight run = 9 chunk + tap; [6] weight buffer
+ *   FETCH_P  a patch round requested from memory: [2] chunk [3] round      WRITE_P  ... written to LDS: [2] chunk [3] round [4] copy
+ *   FETCH_W  a stage's two weight runs requested: [5] the stage            WRITE_W  ... written to LDS: [4] buffer [5] the stage */
+#define ADX_PAIR_EVENT_INTS 7
+enum { ADX_PAIR_READ = 0, ADX_PAIR_FETCH_P = 1, ADX_PAIR_WRITE_P = 2, ADX_PAIR_FETCH_W = 3, ADX_PAIR_WRITE_W = 4 };
+int adx_conv2d_hs3x3_pair_walk(int32_t nchunks, int32_t* n_events, int32_t* events, int32_t max_events);
 int32_t adx_resnet_status_words(const adx_resnet* r);
 int adx_resnet_set_status(adx_resnet* r, uint32_t* words /* device, adx_resnet_status_words(r) words, or NULL */);
 const char* adx_resnet_status_name(const adx_resnet* r, int32_t group);
@@ -416,6 +426,10 @@ int adx_conv2d_forward(const adx_conv2d_desc* d, const float* x, const float* pa
  * BasicBlock chain); these two entry points expose the launch for tests and other callers.  fmt: bit 0 = x is a cell tensor,
  * bit 1 = y is (required), bit 2 = res is.  adx_conv2d_cells_supported: 1 when (desc, n, h, w) runs as one such launch. */
 int adx_conv2d_cells_supported(const adx_conv2d_desc* d, int32_t n, int32_t h, int32_t w);
+/* For tests only (no device needed): what the launch plan of a 3x3 stride-1 conv answers for n x h x w with the operand formats fmt
+ * (bits as above; 0: all fp32): out = [family (0 none, 1 conv2d_hs3x3_kernel, 2 the 16x16x32 tile walk), tile mode, parts of a
+ * split reduction, 1: the PAIR form, 1: the formats are admitted]. */
+int adx_conv2d_hs3x3_plan_query(const adx_conv2d_desc* d, int32_t n, int32_t h, int32_t w, int32_t fmt, int32_t has_res, int32_t* out);
 int adx_conv2d_forward_cells(const adx_conv2d_desc* d, const void* x, const float* packed_w, const float* scale,
                              const float* shift, const void* res, void* y, int32_t n, int32_t h, int32_t w, int32_t relu,
                              int32_t fmt, adx_stream s);
