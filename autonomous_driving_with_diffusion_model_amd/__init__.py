@@ -21,6 +21,9 @@ Public surface mirrors the reference's packages:
                                                        the sample mass behind each, control/modes.py)
     ManoeuvreCommit, CommitResult                     (no reference counterpart: hold the previous tick's manoeuvre unless the
                                                        selector's new choice is clearly better, control/commit.py)
+    Navigator, EgoFrame                               (planner.RoutePlanner.run_step, process_next_waypoint, get_future_waypoints
+                                                       and agent_to_world for all scenes on the device, and the odometry a
+                                                       warm start takes, navigation.py)
     OpenLoopMetrics, evaluate_open_loop               (no reference counterpart: ADE / FDE, minADE_K / minFDE_K and miss rates
                                                        against logged waypoints, on the device, evaluation.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
@@ -48,10 +51,11 @@ from .control.modes import ModeSet, TrajectoryModes  # noqa: E402
 from .control.commit import CommitResult, ManoeuvreCommit  # noqa: E402
 from .pin import Pin  # noqa: E402
 from .guide import Capsules, CostField, Guide, MotionLimits, Route  # noqa: E402
+from .navigation import EgoFrame, Navigator  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
 from .evaluation import MetricsBatch, OpenLoopMetrics, evaluate_open_loop  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
            "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "ManoeuvreCommit", "CommitResult",
-           "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop"]
+           "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop", "Navigator", "EgoFrame"]

@@ -124,6 +124,12 @@ class CommitCfg(C.Structure):
                 ("radius", f32), ("margin", f32), ("ratio", f32)]
 
 
+class NavCfg(C.Structure):
+    """adx_nav_cfg ("route planner v1", include/adx.h)."""
+    _fields_ = [("scenes", i32), ("max_points", i32), ("window", i32), ("first", i32), ("min_distance", C.c_double),
+                ("max_distance", C.c_double), ("xy_scale", C.c_double)]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -274,6 +280,11 @@ _LAZY_SIGS = {
     "adx_commit_state_bytes": (C.c_size_t, [i32, i32]),
     "adx_commit_reset": (i32, [vp, i32, i32, vp, vp]),
     "adx_traj_commit": (i32, [C.POINTER(CommitCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_nav_state_bytes": (C.c_size_t, [i32]),
+    "adx_nav_reset": (i32, [vp, i32, vp, vp]),
+    "adx_nav_step": (i32, [C.POINTER(NavCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_world_to_ego": (i32, [i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]),
+    "adx_ego_to_world": (i32, [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp]),
 }
 
 # the guided exports: five families (the three steps, the cost, the guided selection) times five suffixes, each suffix taking the

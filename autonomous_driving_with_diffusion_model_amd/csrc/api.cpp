@@ -382,6 +382,22 @@ int adx_traj_commit(const adx_commit_cfg* c, const float* trajs, const float* co
   return adx::traj_commit(c, trajs, cost, selected, active, motion, state, best, index, status, follower, blocked, dist2,
                           (hipStream_t)s);
 }
+size_t adx_nav_state_bytes(int32_t scenes) { return adx::nav_state_bytes(scenes); }
+int adx_nav_reset(void* state, int32_t scenes, const uint8_t* mask, adx_stream s) {
+  return adx::nav_reset(state, scenes, mask, (hipStream_t)s);
+}
+int adx_nav_step(const adx_nav_cfg* c, const double* route, const int32_t* cmd, const int32_t* len, const double* pose, void* state,
+                 float* target, int32_t* command, float* window, float* motion, int32_t* fresh, int32_t* head_out, adx_stream s) {
+  return adx::nav_step(c, route, cmd, len, pose, state, target, command, window, motion, fresh, head_out, (hipStream_t)s);
+}
+int adx_world_to_ego(int32_t kind, const double* in, const double* pose, float* out, int32_t scenes, int32_t n, double xy_scale,
+                     double vel_scale, adx_stream s) {
+  return adx::world_to_ego(kind, in, pose, out, scenes, n, xy_scale, vel_scale, (hipStream_t)s);
+}
+int adx_ego_to_world(const float* plans, const double* pose, double* out, int32_t rows, int32_t scenes, int32_t horizon,
+                     int32_t dim, double xy_scale, adx_stream s) {
+  return adx::ego_to_world(plans, pose, out, rows, scenes, horizon, dim, xy_scale, (hipStream_t)s);
+}
 int adx_capsules_from_boxes(const float* boxes, float* out, int32_t scenes, int32_t n_boxes, float inflate, adx_stream s) {
   return adx::capsules_from_boxes(boxes, out, scenes, n_boxes, inflate, (hipStream_t)s);
 }

@@ -120,6 +120,15 @@ int commit_reset(void* state, int scenes, int horizon, const uint8_t* mask, hipS
 int traj_commit(const adx_commit_cfg* c, const float* trajs, const float* cost, const int32_t* selected, const int32_t* active,
                 const float* motion, void* state, float* best, int32_t* index, int32_t* status, int32_t* follower, int32_t* blocked,
                 float* dist2, hipStream_t s);
+// "Ego frame v1" and "route planner v1" (nav.hip)
+size_t nav_state_bytes(int scenes);
+int nav_reset(void* state, int scenes, const uint8_t* mask, hipStream_t s);
+int nav_step(const adx_nav_cfg* c, const double* route, const int32_t* cmd, const int32_t* len, const double* pose, void* state,
+             float* target, int32_t* command, float* window, float* motion, int32_t* fresh, int32_t* head_out, hipStream_t s);
+int world_to_ego(int kind, const double* in, const double* pose, float* out, int scenes, int n, double xy_scale, double vel_scale,
+                 hipStream_t s);
+int ego_to_world(const float* plans, const double* pose, double* out, int rows, int scenes, int horizon, int dim, double xy_scale,
+                 hipStream_t s);
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);

@@ -48,6 +48,9 @@ A fifteenth keeps the plan from flickering between two manoeuvres of nearly equa
 manoeuvre the previous tick chose unless the selector's new choice is clearly better ("manoeuvre commitment v1",
 control/commit.py), one launch directly after selection whose state lives on the device; everything after it -- the warm state,
 the fallback, the controller, the caller -- follows the committed plan, the selector's own choice stays in `commit.selected`.
+A sixteenth supplies what the callers compute on the host before every tick: `navigator=Navigator(...)` with `pose=` walks the
+global plan, rotates the next waypoint into the ego frame and derives the odometry in one launch in front of the tick ("route
+planner v1", navigation.py), and the tick reads `navigator.target` and `navigator.motion`.
 """
 from __future__ import annotations
 
@@ -68,6 +71,7 @@ from .control.select import MAX_CANDIDATES, Selection, TrajectorySelector
 from .misc.constant import GuidanceType
 from .noise import DeviceNoise
 from .guide import Guide
+from .navigation import Navigator
 from .pin import Pin, pin_apply
 
 
@@ -488,7 +492,8 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
                   warm: Optional[WarmStart] = None, motion: Optional[torch.Tensor] = None,
                   controller: Optional[DeviceController] = None, velocity: Optional[torch.Tensor] = None,
                   pin: Optional[Pin] = None, guide: Optional[Guide] = None, fallback: Optional[StopShort] = None,
-                  modes: Optional[TrajectoryModes] = None, commit: Optional[ManoeuvreCommit] = None):
+                  modes: Optional[TrajectoryModes] = None, commit: Optional[ManoeuvreCommit] = None,
+                  navigator: Optional[Navigator] = None, pose=None):
     """One sampling tick: `plan_tick` decides (what each argument means is written on the TickPlan field it becomes), this
     function runs the plan.  With S = image.shape[0] scenes:
 
@@ -498,7 +503,12 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     `fallback`: the stop-short fallback (its report of this tick is `fallback.last`, a StopResult without `traj`); `modes`:
     trajectory modes of the K candidates (K > 1; the tick's ModeSet is `modes.last`, in model units; nothing returned changes);
     `commit`: manoeuvre commitment (K > 1; it takes `motion` with or without a `warm`, on every tick); `fuse`, `set_timesteps`,
-    `scale_xy`: as the module docstring says.
+    `scale_xy`: as the module docstring says.  `navigator` and `pose` (both or neither; `target` and `motion` must then be None):
+    the call runs `navigator.step(pose)` on the current stream once the tick is planned and before anything reads a tensor, and
+    proceeds exactly as if the caller had passed `target=navigator.target` and, where a `warm` or a `commit` reads the odometry,
+    `motion=navigator.motion`; a guide built on `navigator.route(...)` sees the new window.  The step is a launch in front of the
+    tick, not part of its plan: there is no TickPlan field for it and no graph key changes; weaving it into a captured graph as a
+    node is a later step.
 
     The order at the end of a tick is fixed: clamp, selection (K > 1), the commit, the modes, the copy into `warm.prev`, the
     fallback, the control launch, xy scaling -- so the warm state sees the clamped, unscaled, pinned, guided result, and the
@@ -511,9 +521,12 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
     `candidates` is the [K, S, H, D] tensor scaled like `traj`; None at K = 1, where no selector runs); with a controller
     `control` [S, 3] = (throttle, steer, brake) comes last: `(traj, control)` or `(traj, selection, control)`.  `traj` is bit for
     bit what the call without a controller returns."""
+    target, motion = _navigator_inputs(navigator, pose, image, target, motion, warm is not None or commit is not None)
     plan = plan_tick(model, scheduler, cfg, image, target, init_trajs, fuse=fuse, set_timesteps=set_timesteps, noise=noise,
                      step_noise=step_noise, candidates=candidates, selector=selector, warm=warm, motion=motion,
                      controller=controller, velocity=velocity, pin=pin, guide=guide, fallback=fallback, modes=modes, commit=commit)
+    if navigator is not None:
+        navigator.step(pose)       # fills the static target / motion / window the plan already points at
     model.eval()
     device, K, S = image.device, plan.K, plan.S
     noise, controller = plan.noise, plan.controller    # from here on the plan is the one source
@@ -585,6 +598,26 @@ def generate_traj(model, scheduler, cfg, image: torch.Tensor, target: Optional[t
             cands[..., :2] *= model.magic_num
         sel = Selection(best, sel.index, sel.cost, cands, sel.active, sel.blocked)
     return _tick_result(best, sel, control, return_selection, controller is not None)
+
+
+def _navigator_inputs(navigator: Optional[Navigator], pose, image, target, motion, reads_motion: bool):
+    """(target, motion) of a tick: the caller's without a navigator; with one its static `target` and -- where a warm start or a
+    commit reads the odometry -- `motion`, which `navigator.step(pose)` fills AFTER the tick is planned and before anything reads
+    them.  No launch here: every refusal, the plan's included, comes before the walk moves."""
+    if navigator is None:
+        if pose is not None:
+            raise ValueError("generate_traj: `pose` is what a navigator reads; pass navigator=Navigator(...) with it")
+        return target, motion
+    if not isinstance(navigator, Navigator):
+        raise TypeError(f"generate_traj: `navigator` must be a Navigator, got {type(navigator).__name__}")
+    if pose is None:
+        raise ValueError("generate_traj: a navigator needs `pose` [S, 3] = (x, y, compass), the scenes' world poses of this tick")
+    if target is not None or motion is not None:
+        raise ValueError("generate_traj: with a navigator `target` and `motion` are its outputs; pass neither")
+    if navigator.scenes != int(image.shape[0]) or navigator.device != image.device:
+        raise ValueError(f"the Navigator holds the plans of {navigator.scenes} scenes on {navigator.device}, this tick is "
+                         f"{int(image.shape[0])} scenes on {image.device}; use a navigator of its own for another batch or device")
+    return navigator.target, navigator.motion if reads_motion else None
 
 
 def _tick_result(traj, selection, control, return_selection: bool, controlled: bool):
@@ -732,6 +765,11 @@ class GraphedSampler:
     same graph, and replay k of a fresh sampler sees the state k eager ticks leave (the capture's warm-up pass, a real tick, is
     undone).  `motion` is copied into its static buffer at every call and reaches the node on every tick, with or without a `warm`.
     The call returns the committed plan, `last_selection` the committed index and `last_commit` the CommitResult of the last replay.
+    `navigator=Navigator(...)` with `pose=` per call (`generate_traj(navigator=...)`): `navigator.step(pose)` is a launch IN FRONT of
+    the graph, not a node of it -- it runs on the current stream before anything is copied into the static buffers, and the call
+    proceeds as if `target=navigator.target` (and `motion=navigator.motion` with a warm start or a commit) had been passed.  No
+    graph key changes; weaving the step in as a node is a later step.  The capture's warm-up pass does not run the step; the
+    navigator's state is snapshotted and restored around it all the same, like the controller's and the commit's.
     """
 
     MAX_GRAPHS = 4
@@ -739,7 +777,10 @@ class GraphedSampler:
     def __init__(self, model, scheduler, cfg, *, scale_xy: bool = True, noise: Optional[DeviceNoise] = None,
                  candidates: int = 1, selector: Optional[TrajectorySelector] = None, warm: Optional[WarmStart] = None,
                  controller: Optional[DeviceController] = None, fallback: Optional[StopShort] = None,
-                 modes: Optional[TrajectoryModes] = None, commit: Optional[ManoeuvreCommit] = None):
+                 modes: Optional[TrajectoryModes] = None, commit: Optional[ManoeuvreCommit] = None,
+                 navigator: Optional[Navigator] = None):
+        if navigator is not None and not isinstance(navigator, Navigator):
+            raise TypeError(f"GraphedSampler: `navigator` must be a Navigator, got {type(navigator).__name__}")
         deterministic = getattr(scheduler, "_is_ddim", False) or getattr(scheduler, "deterministic", False)
         if float(getattr(cfg.EVAL, "ETA", 0) or 0) != 0.0 or (noise is None and not deterministic):
             raise ValueError("GraphedSampler needs a deterministic sampler (DDIM with eta = 0, DPM-Solver++), or a DeviceNoise for "
@@ -754,6 +795,7 @@ class GraphedSampler:
         self.fallback = fallback
         self.modes = modes
         self.commit = commit
+        self.navigator = navigator
         self._graphs = {}                      # key -> the captured graph and its static buffers
         self._key = None
         self._graph = None                     # the graph of the last call
@@ -792,6 +834,7 @@ class GraphedSampler:
         prev = warm.prev.clone() if valid else None
         windows = None if ctl is None else ctl.state_snapshot()       # ... and pushes a sample into every PID window
         held = None if self.commit is None else self.commit.state_snapshot()      # ... and moves the commit state on one tick
+        walk = None if self.navigator is None else self.navigator.state_snapshot()      # the step ran in front: keep what it left
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):          # warm-up off the capture: lazy packs, workspaces, tile tables (and warm.prev)
@@ -807,6 +850,8 @@ class GraphedSampler:
             ctl.state_restore(windows)
         if held is not None:
             self.commit.state_restore(held)
+        if walk is not None:
+            self.navigator.state_restore(walk)
         self.model._feat_cache = None          # the perception pass must be IN the graph (new frame every tick)
         g.graph = torch.cuda.CUDAGraph()
         # thread-local capture mode: a process group's watchdog thread (multi-rank runs) may query events while this
@@ -887,12 +932,16 @@ class GraphedSampler:
     @torch.no_grad()
     def __call__(self, image: torch.Tensor, target: Optional[torch.Tensor] = None,
                  init_trajs: Optional[torch.Tensor] = None, motion: Optional[torch.Tensor] = None,
-                 velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, guide: Optional[Guide] = None) -> torch.Tensor:
+                 velocity: Optional[torch.Tensor] = None, pin: Optional[Pin] = None, guide: Optional[Guide] = None,
+                 pose=None) -> torch.Tensor:
         warm = self.warm
+        target, motion = _navigator_inputs(self.navigator, pose, image, target, motion, warm is not None or self.commit is not None)
         plan = plan_tick(self.model, self.scheduler, self.cfg, image, target, init_trajs, noise=self.noise,
                          candidates=self.candidates, selector=self.selector, warm=warm, motion=motion,
                          controller=self.controller, velocity=velocity, pin=pin, guide=guide, fallback=self.fallback, graphed=True,
                          modes=self.modes, commit=self.commit)
+        if self.navigator is not None:
+            self.navigator.step(pose)          # in front of the graph: before anything below is copied into a static buffer
         # one static buffer serves the warm start (warm ticks) and the commit node (every tick)
         motion, pin, guide = plan.motion if plan.commit_motion is None else plan.commit_motion, plan.pin, plan.guide
         if plan.start == "randn":

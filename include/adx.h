@@ -1388,6 +1388,98 @@ int adx_traj_commit(const adx_commit_cfg* c, const float* trajs, const float* co
                     int32_t* status, int32_t* follower, int32_t* blocked /* or NULL */, float* dist2, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Ego frame v1: the transform between world metres and a tick's ego frame in model units, the one the reference applies to its
+ * target point (interact.py:185-202, process_next_waypoint) and undoes for its plans (interact.py:249-260, agent_to_world).  Both
+ * launches below and route planner v1 evaluate exactly this.  Callers and fixtures depend on this definition -- a change is a new
+ * version, never an edit.
+ *
+ *   pose     fp64 [scenes][3] = (px, py, compass) in device memory: world metres and radians.  A NaN compass counts as 0.
+ *   frame    th = compass + pi/2 (pi/2 the double nearest to it), c = cos(th), s = sin(th): the device library's fp64 cos and sin.
+ *   rotate   of a world vector (dx, dy), fp64, no contraction, every product and sum rounded on its own:
+ *              r0 = c * dx + s * dy;   r1 = -(s * dx) + c * dy;   the ego vector is (r1, -r0)
+ *            -- a proper rotation of the world by compass + pi, so lengths, angles and orientation are kept.
+ *   point    of a world point (X, Y): dx = X - px, dy = Y - py, rotate, x = r1 / xy_scale, y = -r0 / xy_scale, each rounded to
+ *            fp32 once.
+ *   back     of an ego point (x, y) in model units (fp32, widened exactly): a0 = -(y * xy_scale), a1 = x * xy_scale,
+ *            X = (c * a0 - s * a1) + px, Y = (s * a0 + c * a1) + py, fp64.
+ *   rounding two evaluations of `point` that differ only in their cos and sin routines (each within 4 ulp) differ by at most one
+ *            fp32 ulp of the result plus 8 * 2^-52 * (|dx| + |dy|) / xy_scale (tests/nav_ref.py derives the 8).
+ *
+ * adx_world_to_ego: one thread per record; `in` fp64 [scenes][n][w_in] world and physical, `out` fp32 [scenes][n][w_out] in the
+ * formats the guide takes; vel_scale = dt / xy_scale, formed by the caller in fp64 (read by kinds 1 and 3 only):
+ *   kind 0  points  (X, Y)                              -> (x, y)                               Route.points, target
+ *   kind 1  discs   (cx, cy, vx, vy, r), m and m/s      -> (point(cx, cy), rotate(vx, vy) * vel_scale, r / xy_scale)
+ *   kind 2  planes  (nx, ny, b): n . p <= b in world    -> (rotate(nx, ny), (b - (nx * px + ny * py)) / xy_scale)
+ *   kind 3  boxes   (cx, cy, vx, vy, yaw, length, width); yaw the world angle of the heading
+ *                                                       -> (point(cx, cy), rotate(vx, vy) * vel_scale, rotate(cos yaw, sin yaw),
+ *                                                           length / xy_scale, width / xy_scale): adx_capsules_from_boxes's input
+ *   A radius or size that is <= 0 or NaN is divided like any other and so stays <= 0 or NaN: an empty slot stays empty.
+ *   Limits: 1 <= scenes <= 65535, 1 <= n <= 65536.
+ *
+ * adx_ego_to_world: plans fp32 [rows][horizon][dim] in model units, dim >= 2 (columns 0 and 1 are read), rows a positive multiple
+ * of scenes; row r uses pose[r % scenes] (candidate-major rows).  out fp64 [rows][horizon][2] world metres by `back`.
+ * Limits: 1 <= scenes <= 65535, 1 <= horizon <= 65536, 2 <= dim <= 16, rows * horizon <= 2^30.
+ *
+ * ADX_ERR_INVALID before any GPU work: a kind or a count out of range, a NULL pointer, xy_scale not finite and > 0, vel_scale not
+ * finite (kinds 1 and 3), an output that overlaps an input.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_EGO_POINTS 0
+#define ADX_EGO_DISCS 1
+#define ADX_EGO_PLANES 2
+#define ADX_EGO_BOXES 3
+int adx_world_to_ego(int32_t kind, const double* in, const double* pose, float* out, int32_t scenes, int32_t n, double xy_scale,
+                     double vel_scale, adx_stream s);
+int adx_ego_to_world(const float* plans, const double* pose, double* out, int32_t rows, int32_t scenes, int32_t horizon,
+                     int32_t dim, double xy_scale, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
+ * Route planner v1: what feeds a tick, on the device -- the reference's RoutePlanner.run_step (e2e_driving/planner.py:55-92) for
+ * every scene, its target point and the route ahead in this tick's ego frame, and the odometry between two ticks.  One launch, one
+ * wave per scene, no host decision; the walk along the plan lives in a device buffer the launch reads and advances through its
+ * address, so the call is capturable and the first tick is the same launch as every later one.  Callers and fixtures depend on
+ * this definition -- a change is a new version, never an edit.
+ *
+ *   route    fp64 [scenes][G][2], world metres; cmd int32 [scenes][G]; len int32 [scenes]: the points a scene's plan holds.  len
+ *            lives in device memory and cannot be refused on the host: the kernel CLAMPS it into 1..G.
+ *   pose     fp64 [scenes][3] = (px, py, compass) as ego frame v1 takes it.
+ *   state    one device buffer of adx_nav_state_bytes(scenes) = 32 * scenes bytes; per scene int32 `head`, int32 `valid`, then
+ *            fp64 (px, py, compass) of the previous tick (the compass as used: a NaN stored as 0).  All zero bytes = a fresh walk
+ *            from point 0.  `head` is the reference's deque as a cursor: the points before it are popped.  A stored head outside
+ *            0..len-1 is clamped into it.  A scene's state is read completely before any word of it is written.
+ *   walk     with n = len - head, pos = (px, py), all in fp64 without contraction:
+ *              n == 1: next = head.
+ *              otherwise cum = 0, far = -inf, to_pop = 0 and, for i = 1 .. n-1 in order: stop before i when cum > max_distance;
+ *              cum = cum + |route[head+i] - route[head+i-1]|; d = |route[head+i] - pos|; when d <= min_distance and d > far:
+ *              far = d, to_pop = i.  |v| = sqrt(v.x * v.x + v.y * v.y).  cum is the sequential sum in index order.  A NaN makes
+ *              every comparison it enters false.  Then head += min(to_pop, max(n - 2, 0)) and next = head + 1.
+ *   outputs  target fp32 [scenes][2] = point(route[next]); command int32 [scenes] = cmd[next], as stored;
+ *            window fp32 [scenes][R][2]: point(route[min(head + first + k, len - 1)]), k = 0 .. R-1, with the NEW head: first = 1
+ *            is the reference's get_future_waypoints (interact.py:174), first = 0 keeps the point just passed as well, so that a
+ *            corridor covers the segment the ego is on; head_out int32 [scenes] = the new head.
+ *   motion   fp32 [scenes][3] = (tx, ty, phi) with warm start v1's meaning, fresh int32 [scenes].  valid == 0: motion = 0 and
+ *            fresh = 1.  Otherwise fresh = 0, (tx, ty) = `point` of this tick's position in the PREVIOUS pose's frame, and
+ *            phi = d - 2 pi * ceil((d - pi) / (2 pi)) with d = compass - compass_prev: wrapped to (-pi, pi], then rounded to fp32.
+ *            The ego frame is a proper rotation of the world by compass + pi, so a point q seen from the previous pose is
+ *            R(-phi) (q - t) seen from this one: warm start v1's re-base.
+ *   update   head, valid = 1 and this tick's pose (the compass as used).
+ *
+ * adx_nav_reset makes the walk of every scene (mask NULL) or of the scenes whose mask byte is not 0 (uint8 [scenes]) fresh: one
+ * small capturable launch.  adx_nav_state_bytes is 0 for a value out of range.
+ *
+ * Limits: 1 <= scenes <= 65535, 1 <= max_points = G <= 65536, 2 <= window = R <= 32, first 0 or 1, min_distance, max_distance and
+ * xy_scale finite and > 0.  ADX_ERR_INVALID before any GPU work, each with its own text, for a value out of range, a NULL
+ * pointer, an output that overlaps an input, the state or another output, or a state that overlaps an input.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_nav_cfg {
+  int32_t scenes, max_points, window, first;
+  double min_distance, max_distance, xy_scale;
+} adx_nav_cfg;
+size_t adx_nav_state_bytes(int32_t scenes);
+int adx_nav_reset(void* state, int32_t scenes, const uint8_t* mask /* or NULL: all */, adx_stream s);
+int adx_nav_step(const adx_nav_cfg* c, const double* route, const int32_t* cmd, const int32_t* len, const double* pose, void* state,
+                 float* target, int32_t* command, float* window, float* motion, int32_t* fresh, int32_t* head_out, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
  * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
  * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
