@@ -26,6 +26,9 @@ Public surface mirrors the reference's packages:
                                                        warm start takes, navigation.py)
     OpenLoopMetrics, evaluate_open_loop               (no reference counterpart: ADE / FDE, minADE_K / minFDE_K and miss rates
                                                        against logged waypoints, on the device, evaluation.py)
+    KinematicVehicle, DriveMetrics, World, drive,     (no reference counterpart -- the reference drives CARLA --: a kinematic
+    evaluate_closed_loop                               bicycle, the closed-loop criteria of a drive and the runner that strings
+                                                       navigator, tick, vehicle and metrics together, on the device, simulation.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -54,8 +57,10 @@ from .guide import Capsules, CostField, Guide, MotionLimits, Route  # noqa: E402
 from .navigation import EgoFrame, Navigator  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
 from .evaluation import MetricsBatch, OpenLoopMetrics, evaluate_open_loop  # noqa: E402
+from .simulation import DriveMetrics, EagerTick, KinematicVehicle, World, drive, evaluate_closed_loop  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
            "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "ManoeuvreCommit", "CommitResult",
-           "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop", "Navigator", "EgoFrame"]
+           "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop", "Navigator", "EgoFrame",
+           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop"]

@@ -130,6 +130,21 @@ class NavCfg(C.Structure):
                 ("max_distance", C.c_double), ("xy_scale", C.c_double)]
 
 
+class VehicleCfg(C.Structure):
+    """adx_vehicle_cfg ("vehicle v1", include/adx.h)."""
+    _fields_ = [("scenes", i32), ("substeps", i32), ("steer_sign", i32), ("reserved", i32)] + \
+               [(n, C.c_double) for n in ("dt", "wheelbase", "accel_max", "brake_max", "drag", "roll", "v_max", "steer_max")]
+
+
+class DriveCfg(C.Structure):
+    """adx_drive_cfg ("drive metrics v1", include/adx.h)."""
+    _fields_ = [(n, i32) for n in ("scenes", "max_points", "window", "n_world_discs", "n_boxes", "n_discs", "stop_on_collision",
+                                   "max_ticks")] + \
+               [("dt", C.c_double), ("r_ego", C.c_double), ("offset", C.c_double * 4)] + \
+               [(n, C.c_double) for n in ("offroad_min", "offroad_max", "max_route_percentage", "speed_threshold", "max_time",
+                                          "completion_tol")]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -283,6 +298,12 @@ _LAZY_SIGS = {
     "adx_nav_state_bytes": (C.c_size_t, [i32]),
     "adx_nav_reset": (i32, [vp, i32, vp, vp]),
     "adx_nav_step": (i32, [C.POINTER(NavCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_vehicle_state_bytes": (C.c_size_t, [i32]),
+    "adx_vehicle_reset": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_vehicle_step": (i32, [C.POINTER(VehicleCfg), vp, vp, vp, vp, vp, vp, vp]),
+    "adx_drive_state_bytes": (C.c_size_t, [i32]),
+    "adx_drive_reset": (i32, [vp, i32, vp, vp, vp]),
+    "adx_drive_step": (i32, [C.POINTER(DriveCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "adx_world_to_ego": (i32, [i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]),
     "adx_ego_to_world": (i32, [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp]),
 }

@@ -390,6 +390,24 @@ int adx_nav_step(const adx_nav_cfg* c, const double* route, const int32_t* cmd, 
                  float* target, int32_t* command, float* window, float* motion, int32_t* fresh, int32_t* head_out, adx_stream s) {
   return adx::nav_step(c, route, cmd, len, pose, state, target, command, window, motion, fresh, head_out, (hipStream_t)s);
 }
+size_t adx_vehicle_state_bytes(int32_t scenes) { return adx::vehicle_state_bytes(scenes); }
+int adx_vehicle_reset(void* state, int32_t scenes, const double* pose, const double* speed, const uint8_t* mask, double* pose_out,
+                      float* velocity_out, float* yaw_rate_out, adx_stream s) {
+  return adx::vehicle_reset(state, scenes, pose, speed, mask, pose_out, velocity_out, yaw_rate_out, (hipStream_t)s);
+}
+int adx_vehicle_step(const adx_vehicle_cfg* c, const float* control, const int32_t* hold, void* state, double* pose, float* velocity,
+                     float* yaw_rate, adx_stream s) {
+  return adx::vehicle_step(c, control, hold, state, pose, velocity, yaw_rate, (hipStream_t)s);
+}
+size_t adx_drive_state_bytes(int32_t scenes) { return adx::drive_state_bytes(scenes); }
+int adx_drive_reset(void* state, int32_t scenes, const uint8_t* mask, int32_t* done, adx_stream s) {
+  return adx::drive_reset(state, scenes, mask, done, (hipStream_t)s);
+}
+int adx_drive_step(const adx_drive_cfg* c, const double* pose, const float* velocity, const float* yaw_rate, const double* route,
+                   const int32_t* len, const double* cum, const double* discs, const double* boxes, void* state, int32_t* done,
+                   adx_stream s) {
+  return adx::drive_step(c, pose, velocity, yaw_rate, route, len, cum, discs, boxes, state, done, (hipStream_t)s);
+}
 int adx_world_to_ego(int32_t kind, const double* in, const double* pose, float* out, int32_t scenes, int32_t n, double xy_scale,
                      double vel_scale, adx_stream s) {
   return adx::world_to_ego(kind, in, pose, out, scenes, n, xy_scale, vel_scale, (hipStream_t)s);

@@ -129,6 +129,18 @@ int world_to_ego(int kind, const double* in, const double* pose, float* out, int
                  hipStream_t s);
 int ego_to_world(const float* plans, const double* pose, double* out, int rows, int scenes, int horizon, int dim, double xy_scale,
                  hipStream_t s);
+// "Vehicle v1" (vehicle.hip)
+size_t vehicle_state_bytes(int scenes);
+int vehicle_reset(void* state, int scenes, const double* pose, const double* speed, const uint8_t* mask, double* pose_out,
+                  float* velocity_out, float* yaw_rate_out, hipStream_t s);
+int vehicle_step(const adx_vehicle_cfg* c, const float* control, const int32_t* hold, void* state, double* pose, float* velocity,
+                 float* yaw_rate, hipStream_t s);
+// "Drive metrics v1" (drive.hip)
+size_t drive_state_bytes(int scenes);
+int drive_reset(void* state, int scenes, const uint8_t* mask, int32_t* done, hipStream_t s);
+int drive_step(const adx_drive_cfg* c, const double* pose, const float* velocity, const float* yaw_rate, const double* route,
+               const int32_t* len, const double* cum, const double* discs, const double* boxes, void* state, int32_t* done,
+               hipStream_t s);
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);

@@ -1480,6 +1480,135 @@ int adx_nav_step(const adx_nav_cfg* c, const double* route, const int32_t* cmd, 
                  float* target, int32_t* command, float* window, float* motion, int32_t* fresh, int32_t* head_out, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Vehicle v1: a kinematic bicycle for every scene of a launch -- what takes a tick's (throttle, steer, brake) to the next pose, so
+ * that a loop of ticks can be closed without a simulator.  One launch, one lane per scene, no host decision; the vehicle lives in a
+ * device buffer the launch reads and advances through its address, so the call is capturable and the first step is the same launch
+ * as every later one.  It is a model of a car, not of CARLA's: no tyres, no gears, no slopes.  Callers and fixtures depend on this
+ * definition -- a change is a new version, never an edit.
+ *
+ *   state    one device buffer of adx_vehicle_state_bytes(scenes) = 40 * scenes bytes; per scene fp64 x, y, compass, speed, then
+ *            int32 `valid` and one int32 of padding (kept 0).  All zero bytes = a vehicle at the origin, compass 0, at rest, not yet
+ *            placed.  A scene's state is read completely before any word of it is written.
+ *   control  fp32 [scenes][3] = (throttle, steer, brake) as control v1 writes it.  A component that is NaN or infinite counts as 0.
+ *            Then throttle and brake are clamped into 0..1 and steer into -1..1 (control v1's throttle goes up to MAX_THROTTLE;
+ *            a pedal does not), and all three are widened to fp64 exactly.
+ *   hold     int32 [scenes] or NULL.  Where hold != 0 the scene stands still: speed = 0, yaw_rate = 0, x, y and compass kept,
+ *            valid = 1; the control is not read.
+ *   step     fp64, no contraction, every operation rounded on its own, in this order.  h = dt / substeps, formed on the host.
+ *            delta = steer * steer_max;  k = tan(delta) / wheelbase  (the device library's fp64 tan; once per step).
+ *            c0 = compass.  Then `substeps` times:
+ *              a = throttle * accel_max - brake * brake_max - drag * v;   and a = a - roll when v > 0
+ *                  (left to right: ((throttle * accel_max) - (brake * brake_max)) - (drag * v), then - roll)
+ *              v = v + a * h;   v = 0 when v < 0 (or NaN);   v = v_max when v > v_max
+ *              compass = compass + ((steer_sign * v) * k) * h           with the NEW v
+ *              x = x + (v * h) * sin(compass);   y = y - (v * h) * cos(compass)       with the NEW compass
+ *            (sin compass, -cos compass) is the world image of the ego +y unit vector under ego frame v1: `back` of (0, 1) with
+ *            xy_scale 1 is (-cos(compass + pi/2), -sin(compass + pi/2)).  steer_sign = +1 turns the vehicle towards ego -x of ego
+ *            frame v1 for a positive steer, which is what control v1 with sign_x = -1 asks for (tests/test_sim_cpu.py decides it).
+ *            yaw_rate = (compass - c0) / dt.  The compass is not wrapped: ego frame v1 and route planner v1 take any angle.
+ *   outputs  pose fp64 [scenes][3] = (x, y, compass): ego frame v1's and route planner v1's `pose`; velocity fp32 [scenes] = v and
+ *            yaw_rate fp32 [scenes], each rounded to fp32 once: control v1's `velocity`.  Then the state = (x, y, compass, v, 1, 0).
+ *   launch   64 lanes per workgroup, one lane per scene; every store to the state and to `pose` writes one 32-bit word per lane.
+ *   rounding two evaluations that differ only in their tan, sin and cos routines (the device library's within 2 ulp -- an
+ *            assumption: ROCm ships no accuracy table --, the host's within 1) differ per step by what tests/vehicle_ref.py derives.
+ *
+ * adx_vehicle_reset places vehicles: for every scene (mask NULL) or the scenes whose mask byte is not 0 (uint8 [scenes]) the state
+ * becomes (pose[s], speed[s] or 0 when speed is NULL, valid = 1), a NaN compass or speed stored as 0 and a negative speed as 0;
+ * with pose NULL the state becomes all zero (valid = 0).  The outputs pose, velocity and yaw_rate (= 0) of those scenes are
+ * written as well when the three pointers are given (all or none), so a navigator can read the start pose.  One small capturable
+ * launch.  adx_vehicle_state_bytes is 0 for a value out of range.
+ *
+ * Limits: 1 <= scenes <= 65535, 1 <= substeps <= 16; dt, wheelbase, accel_max, brake_max, v_max finite and > 0; drag, roll finite
+ * and >= 0; 0 < steer_max < 1.5 (radians: below pi/2, where tan has its pole); steer_sign +1 or -1.  ADX_ERR_INVALID before any
+ * GPU work, each with its own text, for a value out of range, a NULL pointer, an output that overlaps an input, the state or
+ * another output, or a state that overlaps an input.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_vehicle_cfg {
+  int32_t scenes, substeps, steer_sign, reserved /* 0 */;
+  double dt, wheelbase, accel_max, brake_max, drag, roll, v_max, steer_max;
+} adx_vehicle_cfg;
+size_t adx_vehicle_state_bytes(int32_t scenes);
+int adx_vehicle_reset(void* state, int32_t scenes, const double* pose /* or NULL: zeros, not placed */,
+                      const double* speed /* or NULL: 0 */, const uint8_t* mask /* or NULL: all */, double* pose_out /* or NULL */,
+                      float* velocity_out /* or NULL */, float* yaw_rate_out /* or NULL */, adx_stream s);
+int adx_vehicle_step(const adx_vehicle_cfg* c, const float* control, const int32_t* hold /* or NULL */, void* state, double* pose,
+                     float* velocity, float* yaw_rate, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
+ * Drive metrics v1: the closed-loop criteria of a drive, advanced by one tick for every scene in one launch -- route completion,
+ * cross-track error, collisions, route deviation, a stall clock, comfort, the odometer -- with every record in device memory and
+ * one read at the end.  What the reference takes from CARLA's criteria (carla_gym/core/task_actor/common/criteria: RouteDeviation
+ * and Blocked are restated; collisions are geometric because there is no physics engine to report them).  One wave per scene, no
+ * host decision, capturable.  Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ *   inputs   pose fp64 [scenes][3], velocity fp32 [scenes], yaw_rate fp32 [scenes]: vehicle v1's outputs, or a simulator's or a
+ *            log's.  A NaN compass counts as 0.  route fp64 [scenes][G][2] and len int32 [scenes] as route planner v1 takes them
+ *            (len clamped into 1..G by the kernel); cum fp64 [scenes][G]: cum[0] = 0, cum[i] = cum[i-1] + |route[i] - route[i-1]|,
+ *            summed sequentially by the caller; `length` = cum[len-1].  |v| = sqrt(v.x * v.x + v.y * v.y).
+ *            discs fp64 [scenes][M][5] = (cx, cy, vx, vy, r) and boxes fp64 [scenes][N][7] = (cx, cy, vx, vy, yaw, length, width)
+ *            in world metres AS OF THIS TICK (the velocities are not read), 0 <= M, N <= 64, NULL exactly when the count is 0.
+ *            A radius or a size that is <= 0 or NaN marks an empty slot.
+ *   state    adx_drive_state_bytes(scenes) = 192 * scenes bytes; per scene ten int32
+ *              cursor, ticks, done, flags, contact, events, contact_ticks, first_tick, first_slot, have
+ *            then nineteen fp64
+ *              px, py, v_prev, a_prev, progress, progress_max, xtrack, xtrack_max, xtrack_sum, xtrack_sq, distance, offroad,
+ *              stall, acc_max, acc_sq, jerk_max, jerk_sq, lat_max, lat_sq.
+ *            All zero bytes = a drive not yet begun.  A scene whose `done` is not 0 is FROZEN: the launch writes done[s] again and
+ *            nothing else of it.  Otherwise, in fp64 without contraction, with pos = (pose.x, pose.y):
+ *   progress len == 1: j = 0, t = 0, d = |pos - route[0]|, progress = 0.  Otherwise the cursor is clamped into 0..len-2 and for
+ *            every segment j in cursor .. min(cursor + window - 1, len - 2), a = route[j], u = route[j+1] - a, L2 = u.x * u.x +
+ *            u.y * u.y:  t = 0 when not L2 > 0, else t = ((pos.x - a.x) * u.x + (pos.y - a.y) * u.y) / L2 clamped into 0..1 (a NaN
+ *            becomes 0);  q = (a.x + t * u.x, a.y + t * u.y);  d = |pos - q|, a NaN d counting as +inf.  The winner is the smallest
+ *            d, the LOWER j on a tie.  cursor = j;  progress = cum[j] + t * sqrt(L2);  progress_max = max(progress_max, progress);
+ *            xtrack = d;  xtrack_max = max(xtrack_max, d), xtrack_sum += d, xtrack_sq += d * d.
+ *   odometer step = |pos - (px, py)| when ticks > 0, else 0;  distance += step;  then (px, py) = pos.
+ *   contact  the ego is n_discs discs of radius r_ego centred at pos + offset[k] * (sin compass, -cos compass), k < n_discs (the
+ *            device library's fp64 sin and cos).  A live disc is hit when |centre - c| < r + r_ego for some k.  A live box is hit
+ *            when the distance from a centre to the rectangle is < r_ego: e = centre - c, ux = cos yaw, uy = sin yaw,
+ *            lx = e.x * ux + e.y * uy, ly = -(e.x * uy) + e.y * ux, qx = max(|lx| - length / 2, 0), qy = max(|ly| - width / 2, 0),
+ *            |(qx, qy)| < r_ego.  hit = any slot hit.  events += hit and contact == 0 (a rising edge);  contact_ticks += hit;
+ *            contact = hit.  On the first hit of a drive first_tick = the new `ticks` (so 1 is the first step; 0 = none yet) and
+ *            first_slot = the lowest hit slot, disc j being slot j and box j slot 64 + j.
+ *   deviate  the reference's RouteDeviation with xtrack as its distance: far = xtrack > offroad_max;  when xtrack > offroad_min:
+ *            offroad += step, and share = offroad / length > max_route_percentage.  off = far or share.
+ *   stall    the reference's Blocked as a clock: stall = velocity < speed_threshold ? stall + dt : 0;  blocked = stall > max_time.
+ *            The reference keeps the time of the last valid state and reads the value 0.0 as "unset", so a vehicle that never
+ *            moves after time 0 is never blocked; that quirk is NOT reproduced.
+ *   comfort  v = velocity widened.  have >= 1: a = (v - v_prev) / dt, acc_max = max(acc_max, |a|), acc_sq += a * a.  have >= 2:
+ *            jk = (a - a_prev) / dt, jerk_max, jerk_sq likewise.  lat = v * yaw_rate on every tick: lat_max, lat_sq.  Then
+ *            v_prev = v, a_prev = a (when have >= 1), have = min(have + 1, 2).
+ *   done     ticks += 1.  Then the FIRST of these that holds sets `done`, and `flags` gets bit (n - 1) of EVERY n that holds:
+ *              1 completed   progress_max >= length - completion_tol
+ *              2 collision   hit and stop_on_collision != 0
+ *              3 off route   off
+ *              4 blocked     blocked
+ *              5 timeout     max_ticks > 0 and ticks >= max_ticks
+ *            0 = running.  done int32 [scenes] is written on every launch: an output a vehicle's `hold` can point at.
+ *   launch   one workgroup of one wave per scene.  Lanes take 64 segments at a time; one xor butterfly over (d, j) keeps the
+ *            smaller d and the lower j on a tie, and a later chunk replaces the carried winner only with a strictly smaller d.
+ *            Lane j tests disc j and box j; a ballot reduces the hit.  Lane 0 forms the record, lanes 0 .. 47 store one 32-bit
+ *            word of it each.
+ *
+ * adx_drive_reset zeroes the records of every scene (mask NULL) or of the scenes whose mask byte is not 0, and their done[s] when
+ * `done` is given: one small capturable launch.  adx_drive_state_bytes is 0 for a value out of range.
+ *
+ * Limits: 1 <= scenes <= 65535, 1 <= max_points = G <= 65536, 1 <= window <= 65536, 0 <= n_world_discs = M <= 64, 0 <= n_boxes = N
+ * <= 64, 1 <= n_discs <= 4, max_ticks >= 0; dt finite and > 0; r_ego, offroad_min, offroad_max, max_route_percentage,
+ * speed_threshold, max_time, completion_tol finite and >= 0; offsets finite.  ADX_ERR_INVALID before any GPU work, each with its own
+ * text, for a value out of range, a NULL pointer (or discs / boxes not NULL exactly when their count is 0), an output that
+ * overlaps an input, or a state that overlaps an input or `done`.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_drive_cfg {
+  int32_t scenes, max_points, window, n_world_discs, n_boxes, n_discs, stop_on_collision, max_ticks;
+  double dt, r_ego, offset[4], offroad_min, offroad_max, max_route_percentage, speed_threshold, max_time, completion_tol;
+} adx_drive_cfg;
+size_t adx_drive_state_bytes(int32_t scenes);
+int adx_drive_reset(void* state, int32_t scenes, const uint8_t* mask /* or NULL: all */, int32_t* done /* or NULL */, adx_stream s);
+int adx_drive_step(const adx_drive_cfg* c, const double* pose, const float* velocity, const float* yaw_rate, const double* route,
+                   const int32_t* len, const double* cum, const double* discs /* or NULL */, const double* boxes /* or NULL */,
+                   void* state, int32_t* done, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
  * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
  * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
