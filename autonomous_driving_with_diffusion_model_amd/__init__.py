@@ -29,6 +29,9 @@ Public surface mirrors the reference's packages:
     KinematicVehicle, DriveMetrics, World, drive,     (no reference counterpart -- the reference drives CARLA --: a kinematic
     evaluate_closed_loop                               bicycle, the closed-loop criteria of a drive and the runner that strings
                                                        navigator, tick, vehicle and metrics together, on the device, simulation.py)
+    Signals                                           (no reference counterpart -- the reference asks CARLA --: traffic lights and
+                                                       stop signs as the guide's stop lines, and the RunRedLight / RunStopSign
+                                                       criteria, on the device, signals.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -58,9 +61,10 @@ from .navigation import EgoFrame, Navigator  # noqa: E402
 from .sampling import WarmStart  # noqa: E402
 from .evaluation import MetricsBatch, OpenLoopMetrics, evaluate_open_loop  # noqa: E402
 from .simulation import DriveMetrics, EagerTick, KinematicVehicle, World, drive, evaluate_closed_loop  # noqa: E402
+from .signals import Signals  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
            "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "ManoeuvreCommit", "CommitResult",
            "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop", "Navigator", "EgoFrame",
-           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop"]
+           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop", "Signals"]

@@ -145,6 +145,12 @@ class DriveCfg(C.Structure):
                                           "completion_tol")]
 
 
+class SignalsCfg(C.Structure):
+    """adx_signals_cfg ("signals v1", include/adx.h)."""
+    _fields_ = [(n, i32) for n in ("scenes", "n_signals", "n_planes", "stop_on_yellow")] + \
+               [(n, C.c_double) for n in ("dt", "xy_scale", "margin", "probe", "min_cos", "speed_threshold")]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -304,6 +310,9 @@ _LAZY_SIGS = {
     "adx_drive_state_bytes": (C.c_size_t, [i32]),
     "adx_drive_reset": (i32, [vp, i32, vp, vp, vp]),
     "adx_drive_step": (i32, [C.POINTER(DriveCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_signals_state_bytes": (C.c_size_t, [i32]),
+    "adx_signals_reset": (i32, [vp, i32, vp, vp, i32, vp]),
+    "adx_signals_step": (i32, [C.POINTER(SignalsCfg), vp, vp, vp, vp, vp, vp, vp, vp]),
     "adx_world_to_ego": (i32, [i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]),
     "adx_ego_to_world": (i32, [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp]),
 }

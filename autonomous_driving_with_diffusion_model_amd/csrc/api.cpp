@@ -408,6 +408,14 @@ int adx_drive_step(const adx_drive_cfg* c, const double* pose, const float* velo
                    adx_stream s) {
   return adx::drive_step(c, pose, velocity, yaw_rate, route, len, cum, discs, boxes, state, done, (hipStream_t)s);
 }
+size_t adx_signals_state_bytes(int32_t scenes) { return adx::signals_state_bytes(scenes); }
+int adx_signals_reset(void* state, int32_t scenes, const uint8_t* mask, float* planes_out, int32_t n_planes, adx_stream s) {
+  return adx::signals_reset(state, scenes, mask, planes_out, n_planes, (hipStream_t)s);
+}
+int adx_signals_step(const adx_signals_cfg* c, const double* signals, const double* pose, const float* velocity, const int32_t* hold,
+                     void* state, float* planes, int32_t* phase, adx_stream s) {
+  return adx::signals_step(c, signals, pose, velocity, hold, state, planes, phase, (hipStream_t)s);
+}
 int adx_world_to_ego(int32_t kind, const double* in, const double* pose, float* out, int32_t scenes, int32_t n, double xy_scale,
                      double vel_scale, adx_stream s) {
   return adx::world_to_ego(kind, in, pose, out, scenes, n, xy_scale, vel_scale, (hipStream_t)s);

@@ -141,6 +141,11 @@ int drive_reset(void* state, int scenes, const uint8_t* mask, int32_t* done, hip
 int drive_step(const adx_drive_cfg* c, const double* pose, const float* velocity, const float* yaw_rate, const double* route,
                const int32_t* len, const double* cum, const double* discs, const double* boxes, void* state, int32_t* done,
                hipStream_t s);
+// "Signals v1" (signals.hip)
+size_t signals_state_bytes(int scenes);
+int signals_reset(void* state, int scenes, const uint8_t* mask, float* planes_out, int n_planes, hipStream_t s);
+int signals_step(const adx_signals_cfg* c, const double* signals, const double* pose, const float* velocity, const int32_t* hold,
+                 void* state, float* planes, int32_t* phase, hipStream_t s);
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);

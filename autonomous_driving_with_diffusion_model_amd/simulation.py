@@ -13,6 +13,10 @@ v1"): progress along the route and cross-track error, collisions of the ego's di
 RouteDeviation and Blocked, comfort, the odometer and `done` per scene, all in one device record per scene; `compute()` is the one
 device read.
 
+`World(discs, boxes, signals)` holds what else is on the road; its `signals` (signals.py: traffic lights and stop signs, "signals
+v1") are stepped by `drive` once per tick, bind the plans through the default guide's planes and score the reference's RunRedLight
+and RunStopSign.
+
 `drive(sampler, vehicle, metrics, ticks=, image=)` runs the loop without a host synchronisation.  THE LOOP IS BLIND: there is no
 renderer, so the images are whatever the caller supplies (one tensor for every tick, or a callable of the tick and the pose) and
 do not show what the vehicle would see.  What the loop does exercise is everything behind the camera: target conditioning, the
@@ -198,9 +202,11 @@ class KinematicVehicle:
 class World:
     """The other road users of a closed loop, in `EgoFrame`'s world formats on the device: `discs` float64 `[S, M, 5]` = (cx, cy,
     vx, vy, r) and / or `boxes` float64 `[S, N, 7]` = (cx, cy, vx, vy, yaw, length, width), M, N in 1..64 (None: none); a radius
-    or size <= 0 or NaN marks an empty slot.  `advance(dt)` moves every centre by its velocity, in place, with plain torch ops."""
+    or size <= 0 or NaN marks an empty slot.  `advance(dt)` moves every centre by its velocity, in place, with plain torch ops.
+    `signals`: the scenes' traffic lights and stop signs (a `Signals`, signals.py; None: none), which `drive` steps once per tick:
+    their stop lines join the default guide as planes, and their record scores red lights and stop signs run."""
 
-    def __init__(self, discs: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None):
+    def __init__(self, discs: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None, signals=None):
         for name, t, w in (("discs", discs, 5), ("boxes", boxes, 7)):
             if t is None:
                 continue
@@ -209,7 +215,15 @@ class World:
                 raise ValueError(f"World: {name} must be contiguous float64 [S, 1..{MAX_SLOTS}, {w}], got {_describe(t)}")
         if discs is not None and boxes is not None and (discs.shape[0] != boxes.shape[0] or discs.device != boxes.device):
             raise ValueError(f"World: discs are {_describe(discs)}, boxes {_describe(boxes)}: one scene count, one device")
-        self.discs, self.boxes = discs, boxes
+        if signals is not None:
+            from .signals import Signals
+            if not isinstance(signals, Signals):
+                raise TypeError(f"World: signals must be a Signals, got {type(signals).__name__}")
+            for name, t in (("discs", discs), ("boxes", boxes)):
+                if t is not None and (t.shape[0] != signals.scenes or t.device != signals.device):
+                    raise ValueError(f"World: {name} are {_describe(t)}, the signals hold {signals.scenes} scenes on {signals.device}: "
+                                     f"one scene count, one device")
+        self.discs, self.boxes, self.signals = discs, boxes, signals
 
     def advance(self, dt: float) -> None:
         for t in (self.discs, self.boxes):
@@ -411,6 +425,8 @@ class EagerTick:
 def _world_guide(frame: EgoFrame, world: World) -> Optional[Guide]:
     discs = None if world.discs is None else frame.discs(world.discs)
     capsules = None if world.boxes is None else Capsules.from_boxes(frame.boxes(world.boxes))
+    if world.signals is not None:
+        return Guide(discs=discs, planes=world.signals.planes, capsules=capsules)
     return None if discs is None and capsules is None else Guide(discs=discs, capsules=capsules)
 
 
@@ -419,9 +435,13 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
           guide_fn: Optional[Callable] = None, pin_fn: Optional[Callable] = None, waypoint_dt: Optional[float] = None,
           check_every: int = 0) -> int:
     """The closed loop: `ticks` times
-        guide  = guide_fn(tick, EgoFrame(vehicle.pose, ...), world)     (default with a `world`: its discs, its boxes as capsules)
+        guide  = guide_fn(tick, EgoFrame(vehicle.pose, ...), world)     (default with a `world`: its discs, its boxes as capsules,
+                                                                         the planes of its signals)
         sampler(image_t, pose=vehicle.pose, velocity=vehicle.velocity, guide=guide, pin=pin_fn(tick, vehicle.pose))
         vehicle.step(sampler.last_control, hold=metrics.done)
+        world.signals.step(vehicle.pose, vehicle.velocity, hold=metrics.done)      (with signals; the hold the vehicle saw, so a
+                                                                                    scene that ends this tick has its last
+                                                                                    movement scored)
         world.advance(vehicle.dt)
         metrics.step(vehicle.pose, vehicle.velocity, vehicle.yaw_rate, world.discs, world.boxes)
     on the current stream and without a host synchronisation, except `bool(metrics.done.all())` every `check_every` ticks (0:
@@ -430,7 +450,12 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
     `sampler`: a `GraphedSampler` built with `navigator=` and `controller=`, or an `EagerTick`; anything callable like them with a
     `last_control`.  `image`: a tensor used at every tick, or a callable `(tick, pose) -> image`.  THE LOOP IS BLIND: nothing here
     renders what the vehicle would see.  `waypoint_dt`: the seconds between two waypoints of a plan, which scales obstacle
-    velocities in the guide (default: the vehicle's dt).  Place the vehicle (`vehicle.reset(pose)`) before the first tick."""
+    velocities in the guide (default: the vehicle's dt).  Place the vehicle (`vehicle.reset(pose)`) before the first tick.
+
+    With `world.signals` the planes a tick's guide reads are those of the signals' last step -- the one after the previous tick's
+    vehicle step, which saw this tick's pose.  Signals that have not stepped since their last reset (`not signals.primed`) are
+    stepped once on the start pose before the first guide is built: time 0 of their clock.  So repeated calls with `ticks=1`
+    equal one call with `ticks=T`."""
     ticks, check_every = int(ticks), int(check_every)
     if ticks < 1 or check_every < 0:
         raise ValueError(f"drive: ticks must be >= 1 and check_every >= 0, got {ticks} and {check_every}")
@@ -444,14 +469,23 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
     if guide_fn is not None and not callable(guide_fn) or pin_fn is not None and not callable(pin_fn):
         raise TypeError("drive: guide_fn and pin_fn must be callables")
     _no_cpu(vehicle.device, "the closed loop")
+    signals = None if world is None else world.signals
+    if signals is not None and (signals.scenes != vehicle.scenes or signals.device != vehicle.device):
+        raise ValueError(f"drive: the signals hold {signals.scenes} scenes on {signals.device}, the vehicle {vehicle.scenes} on "
+                         f"{vehicle.device}")
     frame = None
     if world is not None or guide_fn is not None:
         xy_scale = getattr(getattr(sampler, "model", None), "magic_num", None)
         if xy_scale is None:
             raise ValueError("drive: a guide needs the model's xy scale; the sampler has no `model.magic_num`")
         frame = EgoFrame(vehicle.pose, float(xy_scale), vehicle.dt if waypoint_dt is None else waypoint_dt)
+        if signals is not None and (signals.xy_scale != float(xy_scale) or signals.dt != vehicle.dt):
+            raise ValueError(f"drive: the signals were built with xy_scale {signals.xy_scale} and dt {signals.dt}, the model's scale is "
+                             f"{float(xy_scale)} and the vehicle's dt {vehicle.dt}")
     done_ticks = 0
     for t in range(ticks):
+        if signals is not None and not signals.primed:
+            signals.step(vehicle.pose, vehicle.velocity, hold=metrics.done)
         guide = None
         if guide_fn is not None:
             guide = guide_fn(t, frame, world)
@@ -467,6 +501,8 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
         if control is None:
             raise ValueError("drive: the sampler produced no control; build it with controller=DeviceController(...)")
         vehicle.step(control, hold=metrics.done)
+        if signals is not None:
+            signals.step(vehicle.pose, vehicle.velocity, hold=metrics.done)
         if world is not None:
             world.advance(vehicle.dt)
         metrics.step(vehicle.pose, vehicle.velocity, vehicle.yaw_rate, None if world is None else world.discs,
@@ -480,9 +516,16 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
 def evaluate_closed_loop(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: int, image, start_pose=None,
                          start_speed=None, **kw) -> dict:
     """`drive(...)` from a fresh record and `metrics.compute()`: with `start_pose` `[S, 3]` the vehicles are placed there first
-    (`start_speed` `[S]` or at rest); the navigator's walk is the caller's to reset."""
+    (`start_speed` `[S]` or at rest); the navigator's walk is the caller's to reset.  With `world=World(signals=...)` the signals
+    are reset as well and the report gains `"signals"`: their `compute()`."""
     if start_pose is not None:
         vehicle.reset(start_pose, start_speed)
     metrics.reset()
+    signals = getattr(kw.get("world"), "signals", None)
+    if signals is not None:
+        signals.reset()
     drive(sampler, vehicle, metrics, ticks=ticks, image=image, **kw)
-    return metrics.compute()
+    report = metrics.compute()
+    if signals is not None:
+        report["signals"] = signals.compute()
+    return report

@@ -1609,6 +1609,96 @@ int adx_drive_step(const adx_drive_cfg* c, const double* pose, const float* velo
                    void* state, int32_t* done, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Signals v1: the traffic lights and stop signs of a closed loop, advanced by one tick for every scene in one launch -- which stop
+ * lines bind the ego right now, as the half-planes cost guidance v1 takes, and the two criteria the reference applies to every
+ * drive besides collisions, route deviation and blocked: RunRedLight and RunStopSign (carla_gym/core/task_actor/common/criteria/
+ * run_red_light.py, run_stop_sign.py).  One wave per scene, no host decision, capturable; the records live in device memory.
+ * Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ *   inputs   signals fp64 [scenes][N][10] in world metres and seconds, 1 <= N <= 64, slot j =
+ *              (ax, ay, bx, by, kind, reach, offset, green, yellow, red):
+ *            the stop line is the segment A B; kind 1.0 is a light, 2.0 a stop sign, anything else an EMPTY slot.  A slot is
+ *            also empty when L = |B - A| is not > 0 or reach is not > 0, and a light when one of green, yellow, red is negative or
+ *            NaN or cycle = (green + yellow) + red is not > 0.  |v| = sqrt(v.x * v.x + v.y * v.y).
+ *            pose fp64 [scenes][3] as ego frame v1 takes it (a NaN compass counts as 0), p = (pose.x, pose.y); velocity fp32
+ *            [scenes], widened exactly; hold int32 [scenes] or NULL.
+ *   state    adx_signals_state_bytes(scenes) = 64 * scenes bytes; per scene twelve int32
+ *              ticks, have, target (slot + 1; 0 = none), stop_done, red_runs, stop_runs, stops_met, first_tick, first_slot,
+ *              emitted (by this step), flags, 0
+ *            then two fp64 qx, qy: the probe of the previous step.  All zero bytes = fresh.  A scene's state is read completely
+ *            before any word of it is written.  Everything below is fp64 without contraction, every product and sum rounded on
+ *            its own, in this order; a NaN makes every comparison it enters false.
+ *   slot j   d = B - A;  t = (d.x / L, d.y / L);  n = (-t.y, t.x).  The caller orders A and B so that n points the way the
+ *            governed traffic drives: with A = c - w/2 (sin yaw, -cos yaw) and B = c + w/2 (sin yaw, -cos yaw), n is the heading
+ *            (cos yaw, sin yaw).  r = p - A;  lon = n.x * r.x + n.y * r.y;  lat = t.x * r.x + t.y * r.y.
+ *            forward = (-c, -s) of ego frame v1's (c, s) = (cos, sin)(compass + pi/2), the same two library calls;
+ *            head = n.x * forward.x + n.y * forward.y.
+ *              gate   = live && lon <= 0 && lon >= -reach && lat >= 0 && lat <= L && head > min_cos
+ *              beyond = live && lon > 0 && lat >= 0 && lat <= L
+ *   clock    a scene's first step (have == 0) is at time 0: ticks = 0.  Every later step first does ticks += 1.
+ *            tm = (double)ticks * dt.  A light: tau = fmod(tm + offset, cycle), + cycle when tau < 0; phase GREEN (1) when
+ *            tau < green, YELLOW (2) when tau < green + yellow, else RED (3).  A stop sign's phase is 4, an empty slot's 0.
+ *   red run  the reference's tail-segment test, swept over the tick.  q = p + probe * forward (q.x = p.x + probe * forward.x);
+ *            q_prev = (qx, qy) of the state; skipped on a scene's first step.  s = q_prev - A, v = q - A;
+ *            l0 = n.x * s.x + n.y * s.y;  l1 = n.x * v.x + n.y * v.y.  A crossing needs l0 <= 0 && l1 > 0; then u = l0 / (l0 - l1),
+ *            m0 = t.x * s.x + t.y * s.y, m1 = t.x * v.x + t.y * v.y, mc = m0 + u * (m1 - m0), hit = mc >= 0 && mc <= L.
+ *            hit && phase == RED adds one to red_runs, the slots taken in index order.
+ *   stops    one machine per scene, after the lights, on the state's target as the step found it:
+ *              target == 0: the lowest-index slot that is a stop sign and gated, if any, becomes the target; then stop_done = 0
+ *                           and stops_met += 1.
+ *              target != 0: velocity < speed_threshold sets stop_done = 1.  Then, when the target is not gated (any more):
+ *                           stop_runs += 1 when beyond[target] && !stop_done; the target is cleared.
+ *            So a target is taken at one step and judged from the next one on, and a sign is not taken at the step that clears
+ *            another.
+ *   first    the first infraction of a drive (red_runs == 0 && stop_runs == 0 in the state the step found) stores first_tick =
+ *            the new `ticks` and first_slot = its slot, a light's (the lowest) before the sign's.  An infraction needs an earlier
+ *            step, so first_tick == 0 says "none yet".
+ *   emit     after the machine.  A gated light emits when RED, or YELLOW with stop_on_yellow != 0.  A gated stop sign emits
+ *            unless it is the (new) target and stop_done is set.  The emitting slots, in index order, fill the first slots of
+ *            planes fp32 [scenes][P][3]: ego frame v1's kind 2 of the world plane (n.x, n.y, (n.x * ax + n.y * ay) - margin) --
+ *            "stay `margin` metres behind the line".  Every remaining slot is the inert plane (0, 0, 1).  When more than P slots
+ *            emit the lowest P are kept and bit 0 of `flags` is set for good.  emitted = the planes written, at most P.
+ *   outputs  planes; phase int32 [scenes][N]; the state with have = 1 and (qx, qy) = q.
+ *   hold     where hold != 0 the record is FROZEN (the clock included), every plane is inert and phase is still written, for the
+ *            time the step would have had.
+ *   launch   one workgroup of one wave per scene, lane j owns slot j.  A ballot of the emitting lanes and the population count of
+ *            the bits below a lane give its plane slot; the lowest set bit of the gated-stop ballot is the new target.  Lane 0
+ *            forms the record, lanes 0 .. 15 store one 32-bit word of it each.  No atomics.
+ *   differs  from the reference's two criteria, on purpose.  RunRedLight intersects a short tail segment of the ego (from 0.8 to
+ *            1.0 + 1 m of its half-length behind the centre) with the stop line of a red light of the tail's lane, at the tick's
+ *            pose, and does not count the same light twice in a row; here ONE tail point, `probe` along the heading, is swept from
+ *            its previous to its present place, so a line is not missed between two ticks, every crossing on red counts, and a
+ *            line is whatever segment the caller lays down -- nothing reads a map, and neither the lane nor the heading is
+ *            asked at a crossing (n orders the sides).  RunStopSign finds its sign through CARLA's trigger volume
+ *            and a lane look-ahead, judges the stop while the ego's location is inside the volume, and counts an infraction when
+ *            the ego is no longer affected; here the gate box (reach behind the line, the line's width, the heading test) stands
+ *            in for volume and look-ahead, and ONLY LEAVING ACROSS THE LINE counts as a run: a target left sideways or backwards
+ *            is cleared without one.  Neither criterion ends a drive; the leaderboard's factors (0.7 per light, 0.8 per sign,
+ *            leaderboard/utils/statistics_manager.py) are the caller's arithmetic.
+ *   rounding the planes differ between two evaluations as ego frame v1's kind 2 says (the b column involves no cos or sin and is
+ *            the same number); qx, qy by |probe| * 8 * 2^-52 plus an ulp of the coordinate; every integer of the record is the
+ *            same as long as head - min_cos and, with probe != 0, l0, l1, mc and mc - L stay clear of 0 (tests/signals_ref.py).
+ *
+ * adx_signals_reset zeroes the records of every scene (mask NULL) or of the scenes whose mask byte is not 0, and makes their
+ * n_planes planes inert when planes_out is given: one small capturable launch.  adx_signals_state_bytes is 0 for a value out of
+ * range.
+ *
+ * Limits: 1 <= scenes <= 65535, 1 <= n_signals = N <= 64, 1 <= n_planes = P <= 8; dt and xy_scale finite and > 0; margin and
+ * speed_threshold finite and >= 0; probe finite (the reference's tail point is -2); -1 <= min_cos < 1.  ADX_ERR_INVALID before
+ * any GPU work, each with its own text, for a value out of range, a NULL pointer, or an output (the state, planes, phase) that
+ * overlaps an input or another output.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_signals_cfg {
+  int32_t scenes, n_signals, n_planes, stop_on_yellow;
+  double dt, xy_scale, margin, probe, min_cos, speed_threshold;
+} adx_signals_cfg;
+size_t adx_signals_state_bytes(int32_t scenes);
+int adx_signals_reset(void* state, int32_t scenes, const uint8_t* mask /* or NULL: all */, float* planes_out /* or NULL */,
+                      int32_t n_planes, adx_stream s);
+int adx_signals_step(const adx_signals_cfg* c, const double* signals, const double* pose, const float* velocity,
+                     const int32_t* hold /* or NULL */, void* state, float* planes, int32_t* phase, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
  * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
  * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
