@@ -32,6 +32,9 @@ Public surface mirrors the reference's packages:
     Signals                                           (no reference counterpart -- the reference asks CARLA --: traffic lights and
                                                        stop signs as the guide's stop lines, and the RunRedLight / RunStopSign
                                                        criteria, on the device, signals.py)
+    Traffic                                           (no reference counterpart -- the reference's traffic is CARLA's autopilot and
+                                                       BasicAgent --: car-following agents on caller-laid paths that queue, stop at
+                                                       the lights and yield to the ego, on the device, traffic.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -62,9 +65,10 @@ from .sampling import WarmStart  # noqa: E402
 from .evaluation import MetricsBatch, OpenLoopMetrics, evaluate_open_loop  # noqa: E402
 from .simulation import DriveMetrics, EagerTick, KinematicVehicle, World, drive, evaluate_closed_loop  # noqa: E402
 from .signals import Signals  # noqa: E402
+from .traffic import Traffic  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
            "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "ManoeuvreCommit", "CommitResult",
            "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop", "Navigator", "EgoFrame",
-           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop", "Signals"]
+           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop", "Signals", "Traffic"]

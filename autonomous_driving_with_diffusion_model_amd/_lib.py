@@ -151,6 +151,12 @@ class SignalsCfg(C.Structure):
                [(n, C.c_double) for n in ("dt", "xy_scale", "margin", "probe", "min_cos", "speed_threshold")]
 
 
+class TrafficCfg(C.Structure):
+    """adx_traffic_cfg ("traffic v1", include/adx.h)."""
+    _fields_ = [(n, i32) for n in ("scenes", "n_agents", "n_paths", "n_points", "n_stops", "n_signals")] + \
+               [(n, C.c_double) for n in ("dt", "lane_half_width", "ego_length", "jam", "gap_min", "brake_max")]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -313,6 +319,9 @@ _LAZY_SIGS = {
     "adx_signals_state_bytes": (C.c_size_t, [i32]),
     "adx_signals_reset": (i32, [vp, i32, vp, vp, i32, vp]),
     "adx_signals_step": (i32, [C.POINTER(SignalsCfg), vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_traffic_state_bytes": (C.c_size_t, [i32, i32]),
+    "adx_traffic_reset": (i32, [C.POINTER(TrafficCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_traffic_step": (i32, [C.POINTER(TrafficCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "adx_world_to_ego": (i32, [i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]),
     "adx_ego_to_world": (i32, [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp]),
 }

@@ -416,6 +416,16 @@ int adx_signals_step(const adx_signals_cfg* c, const double* signals, const doub
                      void* state, float* planes, int32_t* phase, adx_stream s) {
   return adx::signals_step(c, signals, pose, velocity, hold, state, planes, phase, (hipStream_t)s);
 }
+size_t adx_traffic_state_bytes(int32_t scenes, int32_t n_agents) { return adx::traffic_state_bytes(scenes, n_agents); }
+int adx_traffic_reset(const adx_traffic_cfg* c, const double* paths, const int32_t* plen, const double* cum, const double* heading,
+                      const double* agents, const uint8_t* mask, void* state, double* boxes, int32_t* leader, adx_stream s) {
+  return adx::traffic_reset(c, paths, plen, cum, heading, agents, mask, state, boxes, leader, (hipStream_t)s);
+}
+int adx_traffic_step(const adx_traffic_cfg* c, const double* paths, const int32_t* plen, const double* cum, const double* heading,
+                     const double* agents, const double* stops, const int32_t* phase, const double* pose, const float* velocity,
+                     const int32_t* hold, void* state, double* boxes, int32_t* leader, adx_stream s) {
+  return adx::traffic_step(c, paths, plen, cum, heading, agents, stops, phase, pose, velocity, hold, state, boxes, leader, (hipStream_t)s);
+}
 int adx_world_to_ego(int32_t kind, const double* in, const double* pose, float* out, int32_t scenes, int32_t n, double xy_scale,
                      double vel_scale, adx_stream s) {
   return adx::world_to_ego(kind, in, pose, out, scenes, n, xy_scale, vel_scale, (hipStream_t)s);

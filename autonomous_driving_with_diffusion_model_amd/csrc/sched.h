@@ -146,6 +146,13 @@ size_t signals_state_bytes(int scenes);
 int signals_reset(void* state, int scenes, const uint8_t* mask, float* planes_out, int n_planes, hipStream_t s);
 int signals_step(const adx_signals_cfg* c, const double* signals, const double* pose, const float* velocity, const int32_t* hold,
                  void* state, float* planes, int32_t* phase, hipStream_t s);
+// "Traffic v1" (traffic.hip)
+size_t traffic_state_bytes(int scenes, int n_agents);
+int traffic_reset(const adx_traffic_cfg* c, const double* paths, const int32_t* plen, const double* cum, const double* heading,
+                  const double* agents, const uint8_t* mask, void* state, double* boxes, int32_t* leader, hipStream_t s);
+int traffic_step(const adx_traffic_cfg* c, const double* paths, const int32_t* plen, const double* cum, const double* heading,
+                 const double* agents, const double* stops, const int32_t* phase, const double* pose, const float* velocity,
+                 const int32_t* hold, void* state, double* boxes, int32_t* leader, hipStream_t s);
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);

@@ -13,9 +13,10 @@ v1"): progress along the route and cross-track error, collisions of the ego's di
 RouteDeviation and Blocked, comfort, the odometer and `done` per scene, all in one device record per scene; `compute()` is the one
 device read.
 
-`World(discs, boxes, signals)` holds what else is on the road; its `signals` (signals.py: traffic lights and stop signs, "signals
-v1") are stepped by `drive` once per tick, bind the plans through the default guide's planes and score the reference's RunRedLight
-and RunStopSign.
+`World(discs, boxes, signals, traffic)` holds what else is on the road; its `signals` (signals.py: traffic lights and stop signs,
+"signals v1") are stepped by `drive` once per tick, bind the plans through the default guide's planes and score the reference's
+RunRedLight and RunStopSign; its `traffic` (traffic.py: car-following agents, "traffic v1") is stepped after them, and its boxes
+are the world's boxes.
 
 `drive(sampler, vehicle, metrics, ticks=, image=)` runs the loop without a host synchronisation.  THE LOOP IS BLIND: there is no
 renderer, so the images are whatever the caller supplies (one tensor for every tick, or a callable of the tick and the pose) and
@@ -34,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .guide import Capsules, Guide
+from .guide import MAX_CAPSULES, Capsules, Guide
 from .navigation import MAX_POINTS, MAX_SCENES, EgoFrame, Navigator, _describe, _device, _positive
 
 STEER_SIGN = 1              # tests/test_sim_cpu.py decides it: the host Controller with sign_x = -1 converges onto an offset route
@@ -204,9 +205,11 @@ class World:
     vx, vy, r) and / or `boxes` float64 `[S, N, 7]` = (cx, cy, vx, vy, yaw, length, width), M, N in 1..64 (None: none); a radius
     or size <= 0 or NaN marks an empty slot.  `advance(dt)` moves every centre by its velocity, in place, with plain torch ops.
     `signals`: the scenes' traffic lights and stop signs (a `Signals`, signals.py; None: none), which `drive` steps once per tick:
-    their stop lines join the default guide as planes, and their record scores red lights and stop signs run."""
+    their stop lines join the default guide as planes, and their record scores red lights and stop signs run.
+    `traffic`: the scenes' reactive road users (a `Traffic`, traffic.py; None: none), which `drive` steps once per tick after the
+    signals: `boxes` must then be None, `world.boxes` is `traffic.boxes` and `advance` leaves them alone (discs still advance)."""
 
-    def __init__(self, discs: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None, signals=None):
+    def __init__(self, discs: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None, signals=None, traffic=None):
         for name, t, w in (("discs", discs, 5), ("boxes", boxes, 7)):
             if t is None:
                 continue
@@ -223,10 +226,25 @@ class World:
                 if t is not None and (t.shape[0] != signals.scenes or t.device != signals.device):
                     raise ValueError(f"World: {name} are {_describe(t)}, the signals hold {signals.scenes} scenes on {signals.device}: "
                                      f"one scene count, one device")
-        self.discs, self.boxes, self.signals = discs, boxes, signals
+        if traffic is not None:
+            from .traffic import Traffic
+            if not isinstance(traffic, Traffic):
+                raise TypeError(f"World: traffic must be a Traffic, got {type(traffic).__name__}")
+            if boxes is not None:
+                raise ValueError("World: with traffic= the boxes are the traffic's; boxes must be None")
+            if discs is not None and (discs.shape[0] != traffic.scenes or discs.device != traffic.device):
+                raise ValueError(f"World: discs are {_describe(discs)}, the traffic holds {traffic.scenes} scenes on {traffic.device}: "
+                                 f"one scene count, one device")
+            if signals is not None and (signals.scenes != traffic.scenes or signals.device != traffic.device):
+                raise ValueError(f"World: the signals hold {signals.scenes} scenes on {signals.device}, the traffic {traffic.scenes} on "
+                                 f"{traffic.device}: one scene count, one device")
+            if traffic.signals is not None and traffic.signals is not signals:
+                raise ValueError("World: the traffic reads the phases of another Signals than the world's signals=")
+            boxes = traffic.boxes
+        self.discs, self.boxes, self.signals, self.traffic = discs, boxes, signals, traffic
 
     def advance(self, dt: float) -> None:
-        for t in (self.discs, self.boxes):
+        for t in (self.discs, None if self.traffic is not None else self.boxes):
             if t is not None:
                 t[..., 0:2].add_(t[..., 2:4], alpha=float(dt))
 
@@ -442,6 +460,9 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
         world.signals.step(vehicle.pose, vehicle.velocity, hold=metrics.done)      (with signals; the hold the vehicle saw, so a
                                                                                     scene that ends this tick has its last
                                                                                     movement scored)
+        world.traffic.step(vehicle.pose, vehicle.velocity, hold=metrics.done)      (with traffic: after the signals, whose new
+                                                                                    phases it reads, and before the metrics, which
+                                                                                    see its new boxes)
         world.advance(vehicle.dt)
         metrics.step(vehicle.pose, vehicle.velocity, vehicle.yaw_rate, world.discs, world.boxes)
     on the current stream and without a host synchronisation, except `bool(metrics.done.all())` every `check_every` ticks (0:
@@ -455,7 +476,8 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
     With `world.signals` the planes a tick's guide reads are those of the signals' last step -- the one after the previous tick's
     vehicle step, which saw this tick's pose.  Signals that have not stepped since their last reset (`not signals.primed`) are
     stepped once on the start pose before the first guide is built: time 0 of their clock.  So repeated calls with `ticks=1`
-    equal one call with `ticks=T`."""
+    equal one call with `ticks=T`.  With `world.traffic` the boxes a tick's guide reads are those of the traffic's last step or
+    reset, which are valid from its construction on: it needs no priming."""
     ticks, check_every = int(ticks), int(check_every)
     if ticks < 1 or check_every < 0:
         raise ValueError(f"drive: ticks must be >= 1 and check_every >= 0, got {ticks} and {check_every}")
@@ -468,11 +490,18 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
         raise TypeError(f"drive: world must be a World, got {type(world).__name__}")
     if guide_fn is not None and not callable(guide_fn) or pin_fn is not None and not callable(pin_fn):
         raise TypeError("drive: guide_fn and pin_fn must be callables")
+    if world is not None and world.traffic is not None and guide_fn is None and world.traffic.n_agents > MAX_CAPSULES:
+        raise ValueError(f"drive: the traffic holds {world.traffic.n_agents} agents per scene and the default world guide shows the "
+                         f"planner at most {MAX_CAPSULES} boxes as capsules; pass guide_fn=, which picks the boxes the planner sees")
     _no_cpu(vehicle.device, "the closed loop")
     signals = None if world is None else world.signals
     if signals is not None and (signals.scenes != vehicle.scenes or signals.device != vehicle.device):
         raise ValueError(f"drive: the signals hold {signals.scenes} scenes on {signals.device}, the vehicle {vehicle.scenes} on "
                          f"{vehicle.device}")
+    traffic = None if world is None else world.traffic
+    if traffic is not None and (traffic.scenes != vehicle.scenes or traffic.device != vehicle.device or traffic.dt != vehicle.dt):
+        raise ValueError(f"drive: the traffic holds {traffic.scenes} scenes on {traffic.device} with dt {traffic.dt}, the vehicle "
+                         f"{vehicle.scenes} on {vehicle.device} with dt {vehicle.dt}")
     frame = None
     if world is not None or guide_fn is not None:
         xy_scale = getattr(getattr(sampler, "model", None), "magic_num", None)
@@ -503,6 +532,8 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
         vehicle.step(control, hold=metrics.done)
         if signals is not None:
             signals.step(vehicle.pose, vehicle.velocity, hold=metrics.done)
+        if traffic is not None:
+            traffic.step(vehicle.pose, vehicle.velocity, hold=metrics.done)
         if world is not None:
             world.advance(vehicle.dt)
         metrics.step(vehicle.pose, vehicle.velocity, vehicle.yaw_rate, None if world is None else world.discs,
@@ -517,15 +548,21 @@ def evaluate_closed_loop(sampler, vehicle: KinematicVehicle, metrics: DriveMetri
                          start_speed=None, **kw) -> dict:
     """`drive(...)` from a fresh record and `metrics.compute()`: with `start_pose` `[S, 3]` the vehicles are placed there first
     (`start_speed` `[S]` or at rest); the navigator's walk is the caller's to reset.  With `world=World(signals=...)` the signals
-    are reset as well and the report gains `"signals"`: their `compute()`."""
+    are reset as well and the report gains `"signals"`: their `compute()`; with `world=World(traffic=...)` the traffic is reset
+    and the report gains `"traffic"` likewise."""
     if start_pose is not None:
         vehicle.reset(start_pose, start_speed)
     metrics.reset()
     signals = getattr(kw.get("world"), "signals", None)
     if signals is not None:
         signals.reset()
+    traffic = getattr(kw.get("world"), "traffic", None)
+    if traffic is not None:
+        traffic.reset()
     drive(sampler, vehicle, metrics, ticks=ticks, image=image, **kw)
     report = metrics.compute()
     if signals is not None:
         report["signals"] = signals.compute()
+    if traffic is not None:
+        report["traffic"] = traffic.compute()
     return report

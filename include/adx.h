@@ -1699,6 +1699,114 @@ int adx_signals_step(const adx_signals_cfg* c, const double* signals, const doub
                      const int32_t* hold /* or NULL */, void* state, float* planes, int32_t* phase, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Traffic v1: the other road users of a closed loop as car-following agents on caller-laid paths, advanced by one tick for every
+ * scene in one launch -- each follows the Intelligent Driver Model behind the nearest of another agent on its path, the ego, and a
+ * stop line of signals v1 that shows red or yellow -- and written out as the boxes ego frame v1 and drive metrics v1 take.  What
+ * the reference gets from CARLA: its zombie vehicles are on autopilot and its scenario actors run BasicAgent (carla_gym/core/
+ * task_actor/scenario_actor/agents/basic_agent.py: a route plan, full brake on a vehicle hazard ahead, a red light or the
+ * destination), of which this law's brake-or-go limit is the degenerate case.  One wave per scene, no host decision, capturable;
+ * the state lives in device memory.  Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ * NO LIBRARY CALL lies on the way to any state or output word: only IEEE + - * / and sqrt, fp64 without contraction, every
+ * product and sum rounded on its own, in the order written here; a NaN makes every comparison it enters false.  So two
+ * evaluations of the contract agree in every bit.  Headings therefore come in as a table, and the ego's speed along a path is a
+ * progress rate, not a cosine.
+ *
+ *   inputs   all in device memory, world metres and seconds.
+ *            paths fp64 [scenes][Q][G][2], plen int32 [scenes][Q] (clamped into 0..G by the kernel; below 2 the path is EMPTY),
+ *            cum fp64 [scenes][Q][G] as drive metrics v1 defines it per path (cum[0] = 0, a sequential sum by the caller;
+ *            `length` of a path = cum[plen-1]), heading fp64 [scenes][Q][G]: heading[g] is the world angle of segment g -> g+1,
+ *            computed by the caller and only ever copied into a box's yaw.  1 <= Q <= 8, 2 <= G <= 64.
+ *            agents fp64 [scenes][N][9], 1 <= N <= 64, slot i =
+ *              (path, start_s, start_v, desired_v, length, width, headway, accel, brake).
+ *            A slot is EMPTY when path is not an integer in 0..Q-1 or names an empty path; when length, width, desired_v, accel
+ *            or brake is not > 0; when headway, start_s or start_v is negative or NaN; when start_s is not below its path's length.
+ *            stops fp64 [scenes][T][3] = (path, s_stop, signal slot), 0 <= T <= 16, and phase int32 [scenes][n_signals], the
+ *            output of signals v1 (2 yellow, 3 red) read as it stands at the launch: both NULL exactly when T = 0.  A stop is
+ *            INERT when its path is not the agent's, when its slot is not an integer in 0..n_signals-1, or when its phase is
+ *            neither 2 nor 3.
+ *            pose fp64 [scenes][3], pos = (pose.x, pose.y), the compass is not read; velocity fp32 [scenes] is carried for the
+ *            record only (v1 does not read it; a later version may); hold int32 [scenes] or NULL.
+ *   state    adx_traffic_state_bytes(scenes, N) = 4 * W * scenes bytes, W = 32 + 5 N + (N odd ? 1 : 0) 32-bit words per scene:
+ *              word 0 ticks, 1 have, 2 arrived, 3 ego_yields, 4 ego_hard, 5 overlaps (int32), 6..7 min_ego_gap (fp64),
+ *              8..23 se_prev[8] (fp64: the ego's arc length on path q at the previous step), 24..31 on_prev[8] (int32: whether it
+ *              was on path q then), 32.. s[N] (fp64), then v[N] (fp64), then alive[N] (int32), then a zero word when N is odd.
+ *            All zero bytes = fresh: a step that finds have == 0 first takes the state adx_traffic_reset leaves (below).  A
+ *            scene's state is read completely before any word of it is written.  Agent i is LIVE when alive[i] != 0 and its slot
+ *            is not empty at this launch.  Every agent sees the OLD s, v of every other agent (a synchronous update).
+ *   ego      for every path q that is not empty the position is projected as drive metrics v1's `progress` does it, over ALL
+ *            segments j in 0..plen-2 (no cursor, no window): a = p[j], u = p[j+1] - a, L2 = u.x * u.x + u.y * u.y;  t = 0 when
+ *            not L2 > 0, else ((pos.x - a.x) * u.x + (pos.y - a.y) * u.y) / L2 clamped into 0..1 (a NaN becomes 0);  c = (a.x +
+ *            t * u.x, a.y + t * u.y);  d = sqrt((pos.x - c.x)^2 + (pos.y - c.y)^2), a NaN d counting as +inf.  The smallest d
+ *            wins, the LOWER j on a tie.  se = cum[j] + t * sqrt(L2);  on_q = d <= lane_half_width.  When on_q holds and held at
+ *            the previous step too (on_prev[q], and have != 0): ue = max((se - se_prev[q]) / dt, 0), a NaN becoming 0; otherwise
+ *            ue = 0: a road user that has just appeared, or is crossing, counts as standing.  The new se_prev[q] = se and
+ *            on_prev[q] = on_q; an empty path's are 0.
+ *   leader   of live agent i on path p, with front = s_i + length_i / 2.  The candidates, each a rear position r and a speed u:
+ *              1. every other live agent k on path p, k = 0, 1, ..., with s_k > s_i, or s_k == s_i && k < i:
+ *                 r = s_k - length_k / 2, u = v_k;
+ *              2. the ego when on_p and se > s_i: r = se - ego_length / 2, u = ue;
+ *              3. every stop t = 0, 1, ... that is not inert and BINDS: front <= s_stop and its phase is RED, or front <= s_stop,
+ *                 its phase is YELLOW and (s_stop - front) * (2 * brake_i) >= v_i * v_i (it can still stop comfortably; otherwise
+ *                 it goes through): r = s_stop, u = 0.
+ *            The smallest r wins; a tie goes to the earlier candidate in this order.  leader int32 [scenes][N] is an output:
+ *            -1 none (or not live), 0..63 an agent, 64 the ego, 65 + t stop t.
+ *   law      f = v / desired_v;  free = 1 - (f * f) * (f * f).  With a leader: gap = r - front;
+ *            star = jam + max(0, v * headway + (v * (v - u)) / (2 * sqrt(accel * brake))) (a NaN inside max becoming 0);
+ *            g = max(gap, gap_min) (a NaN becoming gap_min);  inter = (star / g) * (star / g).  Without one inter = 0.
+ *            acc = accel * (free - inter);  acc < -brake_max sets acc = -brake_max and marks the tick HARD;  acc > accel sets
+ *            acc = accel.  v' = max(0, v + acc * dt) (a NaN becoming 0);  s' = s + v' * dt: semi-implicit, as vehicle v1.
+ *   record   ticks += 1;  ego_yields += the live agents whose leader is the ego;  ego_hard += those of them whose tick is hard
+ *            (the ego cut someone off);  overlaps += the live agents with an agent leader and gap < 0 (0 in every sane run);
+ *            min_ego_gap = min(min_ego_gap, the gaps of the agents the ego leads), +inf until it leads someone.
+ *   arrival  s' >= its path's length retires the agent: alive = 0 and arrived += 1.  A live agent stores s', v'; every other
+ *            slot stores its s, v again.
+ *   boxes    fp64 [scenes][N][7] = (cx, cy, vx, vy, yaw, length, width), drive metrics v1's format.  For an agent that is live
+ *            after the step: j = the largest index in 0..plen-2 with cum[j] <= s' (0 when there is none);  e = p[j+1] - p[j],
+ *            L = sqrt(e.x * e.x + e.y * e.y), unit = (e.x / L, e.y / L), or 0 when not L > 0;  centre = (p[j].x + (s' - cum[j]) *
+ *            unit.x, ...);  velocity = (v' * unit.x, v' * unit.y);  yaw = heading[j];  length and width as given.  An empty,
+ *            dead or retired slot is seven zeros (length 0 = empty everywhere downstream).
+ *   reset    adx_traffic_reset puts the agents of every scene (mask NULL) or of the scenes whose mask byte is not 0 at start_s,
+ *            start_v with alive = 1 (an empty slot: 0, 0, 0), zeroes the record and the ego's path memory, sets have = 1 and
+ *            min_ego_gap = +inf, WRITES THEIR BOXES, and their leader = -1 when `leader` is given: the boxes are valid before the
+ *            first step, no priming step is needed.  One small capturable launch.
+ *   hold     where hold != 0 the scene is FROZEN: no word of its state or of leader is written and its boxes are written again
+ *            from the state as it stands.
+ *   launch   one workgroup of one wave per scene, lane i owns agent i.  The scene's paths are staged into LDS once (at most 16
+ *            KB).  The ego is projected path by path, lanes over segments, with drive metrics v1's xor butterfly over (d, j).
+ *            The leader search is a uniform loop over k with a broadcast of lane k's (path, s, v, rear); the stops are a short
+ *            uniform loop.  The counters are population counts of ballots.  Lane 0 forms the record, lanes 0 .. 31 store one
+ *            32-bit word of it each; every lane stores its agent and its box one 32-bit word per instruction.  No atomics.
+ *   differs  from BasicAgent, on purpose.  It brakes fully when a vehicle is inside 9.5 m and a 45 degree cone ahead and
+ *            otherwise follows its plan with a PID; here a continuous law (IDM) gives the approach, the queue and the start-up,
+ *            and "ahead" is membership of the same path, not a cone -- nothing here reads a map.  There are no walkers and no
+ *            lane changes.  There is no junction priority: paths that cross do not see each other.  The ego is seen where it is
+ *            within lane_half_width of a path, at the speed it has made along that path since the previous step.  Agents do NOT
+ *            obey stop signs: a stop whose phase is 4 is inert.
+ *   rounding every word of the state, of boxes and of leader is the same in two evaluations: there is no library call to differ in.
+ *
+ * adx_traffic_state_bytes is 0 for a value out of range.
+ *
+ * Limits: 1 <= scenes <= 65535, 1 <= n_agents = N <= 64, 1 <= n_paths = Q <= 8, 2 <= n_points = G <= 64, 0 <= n_stops = T <= 16,
+ * n_signals <= 64 and >= 1 when T > 0 (>= 0 otherwise); dt, lane_half_width, ego_length, jam, gap_min (the floor under a gap before
+ * it is divided by) and brake_max (the hard cap on deceleration) finite and > 0.  ADX_ERR_INVALID before any GPU work, each with
+ * its own text, for a value out of range, a NULL pointer (stops and phase not NULL exactly when T > 0; hold, the mask and reset's
+ * leader may be NULL), or an output (the state, boxes, leader) that overlaps an input or another output.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_traffic_cfg {
+  int32_t scenes, n_agents, n_paths, n_points, n_stops, n_signals;
+  double dt, lane_half_width, ego_length, jam, gap_min, brake_max;
+} adx_traffic_cfg;
+size_t adx_traffic_state_bytes(int32_t scenes, int32_t n_agents);
+int adx_traffic_reset(const adx_traffic_cfg* c, const double* paths, const int32_t* plen, const double* cum, const double* heading,
+                      const double* agents, const uint8_t* mask /* or NULL: all */, void* state, double* boxes,
+                      int32_t* leader /* or NULL */, adx_stream s);
+int adx_traffic_step(const adx_traffic_cfg* c, const double* paths, const int32_t* plen, const double* cum, const double* heading,
+                     const double* agents, const double* stops /* or NULL */, const int32_t* phase /* or NULL */,
+                     const double* pose, const float* velocity, const int32_t* hold /* or NULL */, void* state, double* boxes,
+                     int32_t* leader, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
  * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
  * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
