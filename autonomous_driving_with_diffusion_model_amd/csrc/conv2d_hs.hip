@@ -486,10 +486,15 @@ __device__ __forceinline__ void hs_trace_id() {
 // 16 (pb & 1) + j -- from the patch copy of that tap's chunk, a per-lane base where the two taps come from different chunks --
 // and the A fragment of channel block cb the cell tap * 256 + plane * 128 + k-half * 64 + 16 cb + j of the stage's buffer.  The
 // two k-groups that share a ds_read_b128 lane group (MI355X: lanes 0-3, 12-15, 20-27 | ...) differ in the k-half only.  Their
-// weight cells lie 64 cells apart (0 mod 16: complementary banks, conflict-free); their patch cells lie 2 PLANE = 680 cells apart,
-// 8 mod 16, so lanes 20-27 fall on the banks of lanes 0-3 and 12-15: every patch read is 2-way (SQ_LDS_BANK_CONFLICT: a quarter
-// of the launch's LDS cycles, profiles/README.md).  A k-half pitch of 688 cells would remove it; not done yet.  Wave tile 64 channels x (2 rows x 32 columns) as 4 x 4 blocks of 16 x 16: 16
-// fragment reads and 48 MFMAs per stage; the products and their order per accumulator as in conv2d_hs3x3q_kernel.
+// weight cells lie 64 cells apart (0 mod 16: complementary banks, conflict-free).  Their patch cells lie one k-half of a patch copy
+// apart: at the 32x32x16 form's pitch of 2 PLANE = 680 cells, 8 mod 16, lanes 20-27 (columns 4-11 of the second k-half) fell on the
+// banks of lanes 0-3 and 12-15 and every patch read was 2-way (SQ_LDS_BANK_CONFLICT: a quarter of the launch's LDS cycles,
+// profiles/README.md).  So the PAIR instantiations pitch the k-halves kHsPairKHalf = 688 cells apart, the next multiple of 16: columns
+// 4-11 of the second k-half take the banks columns 0-3 and 12-15 of the first leave free; 16 cells = 256 bytes more per copy.
+// Wave tile 64 channels x (2 rows x 32 columns) as 4 x 4 blocks of 16 x 16: 16 fragment reads and 48 MFMAs per stage; the
+// products and their order per accumulator as in conv2d_hs3x3q_kernel.
+constexpr int kHsPairKHalf = 688;
+static_assert(kHsPairKHalf % 16 == 0 && kHsPairKHalf >= 2 * 10 * 34, "the k-half pitch of the PAIR form: whole bank rounds, two planes");
 template <int MODE, int STATS = 0, bool XCELLS = false, bool YCELLS = false, bool VR = false, bool PAIR = false>
 __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(const Conv2dArgs a) {
   static_assert(!PAIR || (MODE == 0 && STATS == 0), "the PAIR form is the plain 4-wave tile");
@@ -498,13 +503,16 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
   constexpr int TH = MODE == 1 ? 16 : 8;               // output rows per workgroup
   constexpr int CT = MODE == 2 ? 2 : 1;                // 64-channel slabs per workgroup
   constexpr int K = 3, PH = TH + 2, PW = 34, PLANE = PH * PW, NITEM = 2 * PLANE;
+  // cell pitch of a k-half ([hi plane][lo plane]) and of a patch copy (two k-halves); PAIR: kHsPairKHalf, 0 mod 16 (above)
+  constexpr int KHP = PAIR ? kHsPairKHalf : 2 * PLANE, COPY = 2 * KHP;
+  static_assert(KHP >= 2 * PLANE, "a k-half holds its two planes");
   constexpr int PIT = (NITEM + NT - 1) / NT;           // patch rounds = slices, one per stage while they last
   constexpr int NW = 9 * 256, WST = PAIR ? 2 * 256 : 3 * 256 * CT;      // weight cells per chunk and 64-channel slab / per stage
   constexpr int WIT = (WST + NT - 1) / NT;
   static_assert(PIT <= K, "a patch slice travels with each stage of a chunk");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   u32x4* patch = reinterpret_cast<u32x4*>(smem_raw);   // 2 x [k-half][plane][PLANE]
-  u32x4* wl = patch + 2 * 4 * PLANE;                   // 2 x [slab][kw][plane][k-half][64]
+  u32x4* wl = patch + 2 * COPY;                   // 2 x [slab][kw][plane][k-half][64]
   float* ss = reinterpret_cast<float*>(wl + 2 * WST);  // scale[64 CT], shift[64 CT], 8 words for the range reduction
   u32x4* dummy = reinterpret_cast<u32x4*>(ss + 2 * 64 * CT + 8);   // where idle threads of a partial round write
   float* bsl = reinterpret_cast<float*>(dummy + 3);                 // STATS == 2: [mean | rstd | mask scale | mask shift] x 64 CT
@@ -576,7 +584,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
     goff[k] = !ok ? kOutside
                   : XCELLS ? (uint32_t)(ioff + hg * 8 * hw * sizeof(float) + ((size_t)iy * a.W + ix) * 16)   // cell (2 chunk + hg, hi, iy, ix)
                            : (uint32_t)(ioff + (hg * 8 * hw + (size_t)iy * a.W + ix) * sizeof(float));
-    pcell[k] = e < NITEM ? hg * 2 * PLANE + p : -1;
+    pcell[k] = e < NITEM ? hg * KHP + p : -1;
   }
   // weight cells of this thread: global offset inside a stage (slab-major) and LDS cell, or the dummy
   int wsrc_off[WIT], wdst[WIT];
@@ -686,7 +694,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
     } else {
       split8(pv[set], xs, hi, lo);
     }
-    u32x4* pd = patch + buf * 4 * PLANE + pcell[k];
+    u32x4* pd = patch + buf * COPY + pcell[k];
     u32x4* d0 = pcell[k] >= 0 ? pd : dummy;
     u32x4* d1 = pcell[k] >= 0 ? pd + PLANE : dummy + 1;
     *d0 = hi;
@@ -703,7 +711,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(out[3]) : "v"(l1), "s"(inv), "v"(h1));
   };
 
-  const int pb_lane = khalf * 2 * PLANE + (rowpair * 2) * PW + l31;
+  const int pb_lane = khalf * KHP + (rowpair * 2) * PW + l31;
   const int wa_lane = slab * 768 + khalf * 64 + l31;
 
   // prologue: stage 0 complete in LDS; weights of stage 1 and the first slice of chunk 1 in flight
@@ -734,7 +742,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
       const HsPairTap t0 = hs_pair_stage(3 * g).tap[0], t1 = hs_pair_stage(3 * g).tap[1];
-      pb_g[g] = patch + kh2 * 2 * PLANE + (rowpair * 2) * PW + j + (ts ? t1.odd * 4 * PLANE + t1.kh * PW : t0.odd * 4 * PLANE + t0.kh * PW);
+      pb_g[g] = patch + kh2 * KHP + (rowpair * 2) * PW + j + (ts ? t1.odd * COPY + t1.kh * PW : t0.odd * COPY + t0.kh * PW);
     }
     const int wa_pair = ts * 256 + kh2 * 64 + j;
     auto load_runs = [&](int o0, int o1, int set) {
@@ -830,68 +838,83 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
       vout[rr] = !inside[rr] ? kOutside : (YCELLS ? vc : vf);
       vres[rr] = !inside[rr] ? kOutside : (rcells ? vc : vf);
     }
-    uint32_t rraw[4][2][8];         // residual of the lane's cell (cb, rr): 8 floats, or the hi and lo cells as they are
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int rr = 0; rr < 2; ++rr) {
-        if (rcells) {
-          const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
-          const u32x4 h4 = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vres[rr], so, 0);
-          const u32x4 l4 = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vres[rr], so + cplane, 0);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) { rraw[cb][rr][c] = h4[c]; rraw[cb][rr][4 + c] = l4[c]; }
-        } else {
-#pragma unroll
-          for (int c = 0; c < 8; ++c)
-            rraw[cb][rr][c] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, vres[rr], cbase_o + (uint32_t)(16 * cb + c) * plane_ob, 0);
-        }
-      }
     float amax = 0.f;
+    // The rest exists twice, with and without the residual path, as straight-line code behind ONE wave-uniform branch: a launch
+    // without a residual (every conv1 of layer1) used to fetch it through an empty descriptor -- 64 buffer_load_dword per lane
+    // that return zero -- which cost 5 us of the layer's 200 us launch (profiles/README.md, "Cell convs").  Such a launch keeps
+    // the ADD of the zero: x + (+0) is +0 for x = -0, so the output stays what it was bit for bit.
+    auto finish = [&](auto res_c) __attribute__((always_inline)) {
+      constexpr bool RES = decltype(res_c)::value;
+      uint32_t rraw[4][2][8];         // residual of the lane's cell (cb, rr): 8 floats, or the hi and lo cells as they are
+      if constexpr (RES) {
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
+        for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-      for (int rr = 0; rr < 2; ++rr) {
-        float o[8], r8[8];
+          for (int rr = 0; rr < 2; ++rr) {
+            if (rcells) {
+              const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
+              const u32x4 h4 = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vres[rr], so, 0);
+              const u32x4 l4 = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vres[rr], so + cplane, 0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int cl = 16 * cb + 4 * kq + i;
-          float x = (am[cb][2 * rr][i] + al[cb][2 * rr][i] * (1.f / kLoScale)) * xs_inv;
-          float y = (am[cb][2 * rr + 1][i] + al[cb][2 * rr + 1][i] * (1.f / kLoScale)) * xs_inv;
-          x = x * ss[cl] + ss[64 + cl];
-          y = y * ss[cl] + ss[64 + cl];
-          const auto sw = __builtin_amdgcn_permlane16_swap(f2u(x), f2u(y), false, false);
-          o[i] = u2f(sw[0]);
-          o[4 + i] = u2f(sw[1]);
-        }
-        if (rcells) {
-          half4(rraw[cb][rr][0], rraw[cb][rr][1], rraw[cb][rr][4], rraw[cb][rr][5], r8);
-          half4(rraw[cb][rr][2], rraw[cb][rr][3], rraw[cb][rr][6], rraw[cb][rr][7], r8 + 4);
-        } else {
+              for (int c = 0; c < 4; ++c) { rraw[cb][rr][c] = h4[c]; rraw[cb][rr][4 + c] = l4[c]; }
+            } else {
 #pragma unroll
-          for (int c = 0; c < 8; ++c) r8[c] = u2f(rraw[cb][rr][c]);
-        }
-        float lm = 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const float t = o[c] + r8[c];
-          o[c] = a.relu ? __builtin_fmaxf(t, 0.f) : t;
-          lm = fp16_amax(lm, o[c]);
-        }
-        amax = fp16_amax(amax, inside[rr] ? lm : 0.f);
-        if constexpr (YCELLS) {
-          u32x4 hi, lo;
-          split8(o, 1.f, hi, lo);
-          const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
-          __builtin_amdgcn_raw_buffer_store_b128(hi, yrsrc, vout[rr], so, 0);
-          __builtin_amdgcn_raw_buffer_store_b128(lo, yrsrc, vout[rr], so + cplane, 0);
-          asm volatile("s_nop 0" ::"v"(hi), "v"(lo));      // (cells_store32: a VALU write in the store's next issue slot)
-        } else {
-#pragma unroll
-          for (int c = 0; c < 8; ++c)
-            __builtin_amdgcn_raw_buffer_store_b32(f2u(o[c]), yrsrc, vout[rr], cbase_o + (uint32_t)(16 * cb + c) * plane_ob, 0);
-        }
+              for (int c = 0; c < 8; ++c)
+                rraw[cb][rr][c] = __builtin_amdgcn_raw_buffer_load_b32(rrsrc, vres[rr], cbase_o + (uint32_t)(16 * cb + c) * plane_ob, 0);
+            }
+          }
       }
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+          float o[8], r8[8];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int cl = 16 * cb + 4 * kq + i;
+            float x = (am[cb][2 * rr][i] + al[cb][2 * rr][i] * (1.f / kLoScale)) * xs_inv;
+            float y = (am[cb][2 * rr + 1][i] + al[cb][2 * rr + 1][i] * (1.f / kLoScale)) * xs_inv;
+            x = x * ss[cl] + ss[64 + cl];
+            y = y * ss[cl] + ss[64 + cl];
+            const auto sw = __builtin_amdgcn_permlane16_swap(f2u(x), f2u(y), false, false);
+            o[i] = u2f(sw[0]);
+            o[4 + i] = u2f(sw[1]);
+          }
+          if constexpr (!RES) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) r8[c] = 0.f;
+          } else if (rcells) {
+            half4(rraw[cb][rr][0], rraw[cb][rr][1], rraw[cb][rr][4], rraw[cb][rr][5], r8);
+            half4(rraw[cb][rr][2], rraw[cb][rr][3], rraw[cb][rr][6], rraw[cb][rr][7], r8 + 4);
+          } else {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) r8[c] = u2f(rraw[cb][rr][c]);
+          }
+          float lm = 0.f;
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const float t = o[c] + r8[c];
+            o[c] = a.relu ? __builtin_fmaxf(t, 0.f) : t;
+            lm = fp16_amax(lm, o[c]);
+          }
+          amax = fp16_amax(amax, inside[rr] ? lm : 0.f);
+          if constexpr (YCELLS) {
+            u32x4 hi, lo;
+            split8(o, 1.f, hi, lo);
+            const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
+            __builtin_amdgcn_raw_buffer_store_b128(hi, yrsrc, vout[rr], so, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(lo, yrsrc, vout[rr], so + cplane, 0);
+            asm volatile("s_nop 0" ::"v"(hi), "v"(lo));      // (cells_store32: a VALU write in the store's next issue slot)
+          } else {
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+              __builtin_amdgcn_raw_buffer_store_b32(f2u(o[c]), yrsrc, vout[rr], cbase_o + (uint32_t)(16 * cb + c) * plane_ob, 0);
+          }
+        }
+    };
+    // (the fp32-input forms -- single launches outside the executor, already over their register budget -- keep the one epilogue)
+    if (!XCELLS || a.res != nullptr) finish(std::true_type{});
+    else finish(std::false_type{});
     range_flag(a.status, out_of_fp16(amax));
     return;
   }
@@ -901,7 +924,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 256 : 512, 2) conv2d_hs3x3_kernel(
     for (int i = 0; i < 6; ++i) {
       const int s = 3 * cp + i;                 // global stage; s & 1 == i & 1 because cp is even
       const int kh = i % 3, cpar = (i / 3) & 1; // kernel row, parity of this stage's chunk
-      const u32x4* pb0 = patch + cpar * 4 * PLANE + pb_lane;
+      const u32x4* pb0 = patch + cpar * COPY + pb_lane;
       const u32x4* wa0 = wl + (i & 1) * WST + wa_lane;
       // fetch two stages ahead (weights of s+2, patch slice s+4) into the sets that were consumed last stage
       // (past the end the last stage / chunk is fetched again and its copy in the idle buffers is never read)
@@ -1939,7 +1962,8 @@ __global__ void __launch_bounds__(256) conv2d_split_reduce_kernel(const float* _
 // LDS bytes of conv2d_hs3x3_kernel<MODE, STATS>: the patch and weight buffers, the BN constants (STATS == 2: + the consumer BatchNorm's)
 static constexpr size_t hs3x3_lds(int mode, int stats, bool pair = false) {
   const int th = mode == 1 ? 16 : 8, ct = mode == 2 ? 2 : 1;
-  return (size_t)2 * 64 * (th + 2) * 34 + (size_t)2 * (pair ? 2 : 3 * ct) * 256 * 16 + (2 * 64 * ct + 8) * sizeof(float) + 48 +
+  const size_t patch = pair ?(size_t)2 * 2 * kHsPairKHalf * 16 : (size_t)2 * 64 * (th + 2) * 34;     // two copies of two k-halves
+  return patch + (size_t)2 * (pair ? 2 : 3 * ct) * 256 * 16 + (2 * 64 * ct + 8) * sizeof(float) + 48 +
          (stats == 2 ? 4 * 64 * ct * sizeof(float) : 0);
 }
 static_assert(hs3x3_lds(0, 2) <= 80 * 1024 && hs3x3_lds(1, 2) <= 160 * 1024 && hs3x3_lds(2, 2) <= 160 * 1024, "LDS budget");

@@ -31,6 +31,7 @@ namespace adx {
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
@@ -65,6 +66,8 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   static_assert(!S2 || DMA, "the stride-2 block entry stages with LDS-DMA only");
   constexpr int NT = kQNT, PW = kQPW, PLANE = DMA ? kQPlaneD : kQPlane, PP = DMA ? kQPlaneD : kQPlaneP, PIT = kQPit, WST = kQWst;
   constexpr int NPAIRS = DMA ? kQPairsD : kQPairs;
+  // the inference forms take a tile's gather offsets from what the previous visit parked in LDS (the training forms compute them)
+  constexpr bool HAND = DMA && (TRAIN == 0 || S2);
   // cell strides of the patch image: [k-group][plane][PP], or (DMA) [plane][k-group][PP]
   constexpr int GST = DMA ? PP : 2 * PP, PLST = DMA ? 4 * PP : PP;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -264,8 +267,12 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   asm volatile("" : "+s"(zero_));
   const int tl = tid + zero_;
   if constexpr (DMA && !S2) {      // (S2 addresses its weights through a descriptor and parks its gather offsets in LDS)
+    // (goff: the prologue's on a workgroup's first tile, afterwards what the previous visit parked in gnext -- read back at the
+    // loop's end, so the offsets are live from there to here and not across the epilogue)
+    if constexpr (!HAND) {
 #pragma unroll
-    for (int k = 0; k < PIT; ++k) goff[k] = goff_of(tl, k, oy0, vx0);
+      for (int k = 0; k < PIT; ++k) goff[k] = goff_of(tl, k, oy0, vx0);
+    }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int e = tl + NT * k;
@@ -292,7 +299,7 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
     // odd-sized map, and a mask per plane would have to live in registers through the stage loop
 #pragma unroll
     for (int k = 0; k < PIT; ++k) {
-      const uint32_t g10 = goff_s2(tl, k, oy0, vx0, 1, 0);
+      const uint32_t g10 = HAND ? goff[k] : goff_s2(tl, k, oy0, vx0, 1, 0);      // (HAND: the prologue's, then the previous visit's gnext)
       gpl[(0 * PIT + k) * NT + tid] = goff_s2(tl, k, oy0, vx0, 1, 1);
       gpl[(1 * PIT + k) * NT + tid] = g10;
       gpl[(2 * PIT + k) * NT + tid] = goff_s2(tl, k, oy0, vx0, 0, 1);
@@ -658,61 +665,89 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
     const int oy = oy0 + rowpair * 2 + rr;
     vcell[rr] = (col_valid && oy < a.OH) ? img_off + (uint32_t)(oy * a.OW + xl) * 16u + (uint32_t)(rw >> 1) * 2u * cplane : kOutside;
   }
-  // the residual cells of the whole tile first (one exposed latency): cell group 2 cb + (rw >> 1) of the wave's 64 channels
-  u32x4 rh[4][2], rl[4][2];
-#pragma unroll
-  for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-      const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
-      if constexpr (S2) {       // (a block entry has no residual)
-        rh[cb][rr] = u32x4{0u, 0u, 0u, 0u};
-        rl[cb][rr] = u32x4{0u, 0u, 0u, 0u};
-      } else {
-        rh[cb][rr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vcell[rr], so, 0);
-        rl[cb][rr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vcell[rr], so + cplane, 0);
-      }
-    }
   const float* sc = ssp + slab * 64;
   const float* sh = ssp + 128 + slab * 64;
   float am[2] = {0.f, 0.f};        // per row of the lane: max |x| over its stored values (adx_common.h: fp16_amax)
+  // The rest of the epilogue exists once per (residual, ReLU) -- both uniform over the launch -- as straight-line code behind
+  // wave-uniform branches: a launch without a residual (every conv1, both outputs of a block entry) neither loads 16 cells
+  // through an empty descriptor nor converts the zeros it would get back, and no stored value passes a select on `relu`.
+  // What such a launch keeps is the ADD of the zero: x + (+0) is +0 for x = -0, and the output stays what it was bit for bit.
+  auto cells_out = [&](auto res_c, auto relu_c) __attribute__((always_inline)) {
+    constexpr bool RES = decltype(res_c)::value, RELU = decltype(relu_c)::value;
+    // the residual cells of the whole tile first (one exposed latency): cell group 2 cb + (rw >> 1) of the wave's 64 channels
+    u32x4 rh[4][2], rl[4][2];
+    if constexpr (RES) {
 #pragma unroll
-  for (int cb = 0; cb < 4; ++cb)
+      for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-      float x[4], y[4];                           // pixel blocks 2 rr (columns 0-15) and 2 rr + 1 (columns 16-31): channels 16 cb + 4 kq + i
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int cl = cb * 16 + 4 * kq + i;
-        x[i] = (accm[cb][2 * rr][i] + accl[cb][2 * rr][i] * (1.f / kLoScale)) * sc[cl] + sh[cl];
-        y[i] = (accm[cb][2 * rr + 1][i] + accl[cb][2 * rr + 1][i] * (1.f / kLoScale)) * sc[cl] + sh[cl];
-      }
-      float o[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        // rows of 16 lanes: x's odd rows <-> y's even rows.  Afterwards x = channels + 0..3 and y = channels + 4..7 of the lane's cell
-        const auto sw = __builtin_amdgcn_permlane16_swap(f2u(x[i]), f2u(y[i]), false, false);
-        o[i] = u2f(sw[0]);
-        o[4 + i] = u2f(sw[1]);
-      }
-      float r8[8];
-      half4(rh[cb][rr][0], rh[cb][rr][1], rl[cb][rr][0], rl[cb][rr][1], r8);
-      half4(rh[cb][rr][2], rh[cb][rr][3], rl[cb][rr][2], rl[cb][rr][3], r8 + 4);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float tsum = o[i] + r8[i];
-        o[i] = relu ? __builtin_fmaxf(tsum, 0.f) : tsum;
-        am[rr] = fp16_amax(am[rr], o[i]);
-      }
-      u32x4 hi, lo;
-      split8(o, 1.f, hi, lo);
-      const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
-      __builtin_amdgcn_raw_buffer_store_b128(hi, yrsrc, vcell[rr], so, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(lo, yrsrc, vcell[rr], so + cplane, 0);
-      // a VALU write to the data registers of a 16-byte buffer store with an SGPR offset in the next issue slot can reach the
-      // store (conv2d_hs.hip: cells_store32); keep both operands alive across one wait state
-      asm volatile("s_nop 0" ::"v"(hi), "v"(lo));
+        for (int rr = 0; rr < 2; ++rr) {
+          const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
+          rh[cb][rr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vcell[rr], so, 0);
+          rl[cb][rr] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, vcell[rr], so + cplane, 0);
+        }
     }
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        // pixel blocks 2 rr (columns 0-15) and 2 rr + 1 (columns 16-31): channels 16 cb + 4 kq + i, two per instruction
+        // (v_pk_fma_f32: the same two fused multiply-adds per value, in the same order)
+        float x[4], y[4];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int cl = cb * 16 + 4 * kq + 2 * h;
+          const f32x2 inv2 = {1.f / kLoScale, 1.f / kLoScale};
+          const f32x2 sc2 = {sc[cl], sc[cl + 1]}, sh2 = {sh[cl], sh[cl + 1]};
+          const f32x2 xm = {accm[cb][2 * rr][2 * h], accm[cb][2 * rr][2 * h + 1]}, xl2 = {accl[cb][2 * rr][2 * h], accl[cb][2 * rr][2 * h + 1]};
+          const f32x2 ym = {accm[cb][2 * rr + 1][2 * h], accm[cb][2 * rr + 1][2 * h + 1]};
+          const f32x2 yl2 = {accl[cb][2 * rr + 1][2 * h], accl[cb][2 * rr + 1][2 * h + 1]};
+          const f32x2 xv = __builtin_elementwise_fma(__builtin_elementwise_fma(xl2, inv2, xm), sc2, sh2);      // (acc + lo / 2^11) * scale + shift
+          const f32x2 yv = __builtin_elementwise_fma(__builtin_elementwise_fma(yl2, inv2, ym), sc2, sh2);
+          x[2 * h] = xv[0]; x[2 * h + 1] = xv[1];
+          y[2 * h] = yv[0]; y[2 * h + 1] = yv[1];
+        }
+        float o[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          // rows of 16 lanes: x's odd rows <-> y's even rows.  Afterwards x = channels + 0..3 and y = channels + 4..7 of the lane's cell
+          const auto sw = __builtin_amdgcn_permlane16_swap(f2u(x[i]), f2u(y[i]), false, false);
+          o[i] = u2f(sw[0]);
+          o[4 + i] = u2f(sw[1]);
+        }
+        float r8[8];
+        if constexpr (RES) {
+          half4(rh[cb][rr][0], rh[cb][rr][1], rl[cb][rr][0], rl[cb][rr][1], r8);
+          half4(rh[cb][rr][2], rh[cb][rr][3], rl[cb][rr][2], rl[cb][rr][3], r8 + 4);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) r8[i] = 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float tsum = o[i] + r8[i];
+          o[i] = RELU ? __builtin_fmaxf(tsum, 0.f) : tsum;
+          am[rr] = fp16_amax(am[rr], o[i]);
+        }
+        u32x4 hi, lo;
+        split8(o, 1.f, hi, lo);
+        const uint32_t so = cell0 + (uint32_t)(2 * cb) * 2u * cplane;
+        __builtin_amdgcn_raw_buffer_store_b128(hi, yrsrc, vcell[rr], so, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(lo, yrsrc, vcell[rr], so + cplane, 0);
+        // a VALU write to the data registers of a 16-byte buffer store with an SGPR offset in the next issue slot can reach the
+        // store (conv2d_hs.hip: cells_store32); keep both operands alive across one wait state
+        asm volatile("s_nop 0" ::"v"(hi), "v"(lo));
+      }
+  };
+  using std::false_type;
+  using std::true_type;
+  const bool with_res = !S2 && a.res != nullptr;         // (a block entry has no residual)
+  if (relu) {
+    if (with_res) cells_out(true_type{}, true_type{});
+    else cells_out(false_type{}, true_type{});
+  } else {
+    if (with_res) cells_out(true_type{}, false_type{});
+    else cells_out(false_type{}, false_type{});
+  }
   // only pixels of the map count: the shared zero column of the virtual row and the lanes past the last image store nothing
   bad |= ((vcell[0] != kOutside) & out_of_fp16(am[0])) | ((vcell[1] != kOutside) & out_of_fp16(am[1]));
   } while (S2 && ++pass < 2);
@@ -731,6 +766,12 @@ __global__ void __launch_bounds__(kQNT, 2) conv2d_hs3x3q_kernel(const Conv2dArgs
   sp = un.sp; ct = un.ct;
   ty = sp / a.tiles_x; tx = sp - ty * a.tiles_x;
   oy0 = ty * kQTH; vx0 = tx * 32;
+  // its gather offsets (S2: of its plane (1, 0)) are what this visit parked in gnext: each thread reads its own words back, before
+  // the next visit overwrites them
+  if constexpr (HAND) {
+#pragma unroll
+    for (int k = 0; k < PIT; ++k) goff[k] = gnext[k * NT + tid];
+  }
   }
   range_flag(a.status, bad);
 }
