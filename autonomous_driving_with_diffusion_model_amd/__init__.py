@@ -35,6 +35,9 @@ Public surface mirrors the reference's packages:
     Traffic                                           (no reference counterpart -- the reference's traffic is CARLA's autopilot and
                                                        BasicAgent --: car-following agents on caller-laid paths that queue, stop at
                                                        the lights and yield to the ego, on the device, traffic.py)
+    Camera                                            (no reference counterpart -- the reference reads CARLA's RGB sensor --: the
+                                                       front camera as an analytic ray caster over the world's primitives, the
+                                                       frames `drive(image=)` feeds the encoder, on the device, camera.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -66,9 +69,10 @@ from .evaluation import MetricsBatch, OpenLoopMetrics, evaluate_open_loop  # noq
 from .simulation import DriveMetrics, EagerTick, KinematicVehicle, World, drive, evaluate_closed_loop  # noqa: E402
 from .signals import Signals  # noqa: E402
 from .traffic import Traffic  # noqa: E402
+from .camera import Camera  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
            "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "ManoeuvreCommit", "CommitResult",
            "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop", "Navigator", "EgoFrame",
-           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop", "Signals", "Traffic"]
+           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop", "Signals", "Traffic", "Camera"]

@@ -157,6 +157,14 @@ class TrafficCfg(C.Structure):
                [(n, C.c_double) for n in ("dt", "lane_half_width", "ego_length", "jam", "gap_min", "brake_max")]
 
 
+class CameraCfg(C.Structure):
+    """adx_camera_cfg ("camera v1", include/adx.h)."""
+    _fields_ = [(n, i32) for n in ("scenes", "width", "height", "n_boxes", "n_discs", "n_signals", "n_paths", "n_points")] + \
+               [(n, C.c_double) for n in ("fov", "mount_back", "cam_height", "near", "far", "half_width", "mark", "line_half",
+                                          "box_height", "disc_height", "lamp_radius", "lamp_height", "lamp_setback", "pole_radius")] + \
+               [("mean", f32 * 3), ("stdv", f32 * 3), ("palette", C.c_uint8 * 60), ("shade", C.c_uint8 * 5), ("reserved", C.c_uint8 * 7)]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -322,6 +330,9 @@ _LAZY_SIGS = {
     "adx_traffic_state_bytes": (C.c_size_t, [i32, i32]),
     "adx_traffic_reset": (i32, [C.POINTER(TrafficCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "adx_traffic_step": (i32, [C.POINTER(TrafficCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_camera_prims_bytes": (C.c_size_t, [C.POINTER(CameraCfg)]),
+    "adx_camera_default_palette": (None, [vp, vp]),
+    "adx_camera_render": (i32, [C.POINTER(CameraCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "adx_world_to_ego": (i32, [i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]),
     "adx_ego_to_world": (i32, [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp]),
 }

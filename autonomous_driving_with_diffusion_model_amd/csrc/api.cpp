@@ -426,6 +426,13 @@ int adx_traffic_step(const adx_traffic_cfg* c, const double* paths, const int32_
                      const int32_t* hold, void* state, double* boxes, int32_t* leader, adx_stream s) {
   return adx::traffic_step(c, paths, plen, cum, heading, agents, stops, phase, pose, velocity, hold, state, boxes, leader, (hipStream_t)s);
 }
+size_t adx_camera_prims_bytes(const adx_camera_cfg* c) { return adx::camera_prims_bytes(c); }
+void adx_camera_default_palette(uint8_t* palette, uint8_t* shade) { adx::camera_default_palette(palette, shade); }
+int adx_camera_render(const adx_camera_cfg* c, const double* pose, const double* boxes, const double* discs, const double* signals,
+                      const int32_t* phase, const double* roads, const int32_t* road_len, const int32_t* hold, void* prims,
+                      uint8_t* frames, float* image, int32_t* ids, float* depth, adx_stream s) {
+  return adx::camera_render(c, pose, boxes, discs, signals, phase, roads, road_len, hold, prims, frames, image, ids, depth, (hipStream_t)s);
+}
 int adx_world_to_ego(int32_t kind, const double* in, const double* pose, float* out, int32_t scenes, int32_t n, double xy_scale,
                      double vel_scale, adx_stream s) {
   return adx::world_to_ego(kind, in, pose, out, scenes, n, xy_scale, vel_scale, (hipStream_t)s);

@@ -153,6 +153,12 @@ int traffic_reset(const adx_traffic_cfg* c, const double* paths, const int32_t* 
 int traffic_step(const adx_traffic_cfg* c, const double* paths, const int32_t* plen, const double* cum, const double* heading,
                  const double* agents, const double* stops, const int32_t* phase, const double* pose, const float* velocity,
                  const int32_t* hold, void* state, double* boxes, int32_t* leader, hipStream_t s);
+// "Camera v1" (camera.hip)
+size_t camera_prims_bytes(const adx_camera_cfg* c);
+void camera_default_palette(uint8_t* palette, uint8_t* shade);
+int camera_render(const adx_camera_cfg* c, const double* pose, const double* boxes, const double* discs, const double* signals,
+                  const int32_t* phase, const double* roads, const int32_t* road_len, const int32_t* hold, void* prims, uint8_t* frames,
+                  float* image, int32_t* ids, float* depth, hipStream_t s);
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);

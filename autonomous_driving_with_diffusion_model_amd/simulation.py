@@ -18,12 +18,13 @@ device read.
 RunRedLight and RunStopSign; its `traffic` (traffic.py: car-following agents, "traffic v1") is stepped after them, and its boxes
 are the world's boxes.
 
-`drive(sampler, vehicle, metrics, ticks=, image=)` runs the loop without a host synchronisation.  THE LOOP IS BLIND: there is no
-renderer, so the images are whatever the caller supplies (one tensor for every tick, or a callable of the tick and the pose) and
-do not show what the vehicle would see.  What the loop does exercise is everything behind the camera: target conditioning, the
+`drive(sampler, vehicle, metrics, ticks=, image=)` runs the loop without a host synchronisation.  THE LOOP IS BLIND UNLESS `image=`
+IS A `Camera` (camera.py): otherwise the images are whatever the caller supplies (one tensor for every tick, or a callable of the
+tick and the pose) and do not show what the vehicle would see.  What the loop does exercise is everything behind the camera:
+target conditioning, the
 guide, pins, selection, commit, fallback, control and the navigator, tick after tick on the poses their own output produced.
-Whether a number it reports says anything about driving in a town is a property of weights and of a renderer and is not
-measurable in this repository.
+Whether a number it reports says anything about driving in a town is a property of weights -- a `Camera`'s frames are
+flat-shaded geometry, not a town -- and is not measurable in this repository.
 """
 from __future__ import annotations
 
@@ -469,8 +470,9 @@ def drive(sampler, vehicle: KinematicVehicle, metrics: DriveMetrics, *, ticks: i
     never), which ends the loop early once every scene is done.  Returns the ticks run.
 
     `sampler`: a `GraphedSampler` built with `navigator=` and `controller=`, or an `EagerTick`; anything callable like them with a
-    `last_control`.  `image`: a tensor used at every tick, or a callable `(tick, pose) -> image`.  THE LOOP IS BLIND: nothing here
-    renders what the vehicle would see.  `waypoint_dt`: the seconds between two waypoints of a plan, which scales obstacle
+    `last_control`.  `image`: a tensor used at every tick, or a callable `(tick, pose) -> image`.  THE LOOP IS BLIND unless that
+    callable is a `Camera` (camera.py), which renders what the vehicle would see from `world`.  `waypoint_dt`: the seconds
+    between two waypoints of a plan, which scales obstacle
     velocities in the guide (default: the vehicle's dt).  Place the vehicle (`vehicle.reset(pose)`) before the first tick.
 
     With `world.signals` the planes a tick's guide reads are those of the signals' last step -- the one after the previous tick's

@@ -1807,6 +1807,129 @@ int adx_traffic_step(const adx_traffic_cfg* c, const double* paths, const int32_
                      int32_t* leader, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Camera v1: the front camera of a closed loop, rendered on the device -- an analytic ray caster over exactly the primitives the
+ * loop already holds (the ground with its roads and stop lines, the world's boxes and discs, the lamps and poles of its signals),
+ * one C call per tick that writes the frame the encoder reads.  The reference closes its loop through CARLA's RGB sensor
+ * (e2e_driving/diffusion_agent.py: sensors(): 900 x 256, fov 100 degrees, 1.5 m behind the vehicle centre, 2.0 m up, pitch 0); this
+ * package rules the simulator out, so the renderer is its own.  Capturable: no allocation, no synchronisation, no host decision.
+ * Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ *   frame    the camera frame is ego frame v1 in METRES (`rotate` and `point` with xy_scale 1: x lateral, +y forward) plus z up,
+ *            moved so that the eye is the origin: a world point (X, Y) at height Z is
+ *              (x, y) = rotate(X - px, Y - py);  cam = (x, y - mount_back, Z - cam_height)
+ *            -- the eye sits at ego (0, mount_back, cam_height); the reference's mount is mount_back = -1.5, cam_height = 2.0.
+ *            The ground is the plane z = -cam_height.  v1 has no pitch and no roll.  Columns increase towards +x, rows downwards.
+ *   ray      of pixel (u, v), all fp32: dx = ((u + 0.5) - W/2) * k;  dy = 1;  dz = -(((v + 0.5) - H/2) * k);  k = 2 tan(fov / 2) / W
+ *            formed on the host in fp64 and rounded to fp32 once (square pixels).  Rays are not normalised: the parameter t of a
+ *            point t * (dx, 1, dz) is its forward depth.  A2 = dx * dx + 1;  A3 = A2 + dz * dz.
+ *   stage    the first of the call's two launches, one wave per scene: every primitive into the camera frame in fp64, no
+ *            contraction, every product and sum rounded on its own in the order written here, with ego frame v1's (c, s) -- the
+ *            same two library calls -- and each word rounded to fp32 ONCE into the table `prims` (the caller's workspace of
+ *            adx_camera_prims_bytes(cfg) bytes, 16-byte aligned).  Per scene the table is 16 int32 header words (1, n_obj, n_gnd,
+ *            0 ...), n_obj = n_boxes + n_discs + 2 n_signals OBJECT records of 16 words in the order boxes, discs, lamps, poles,
+ *            and n_gnd = n_signals + n_paths * (n_points - 1) GROUND records of 8 words in the order stop lines, road segments
+ *            (path-major).  An object record: word 0 int32 key = class << 8 | slot, 0 = EMPTY (the whole record is then zero);
+ *            words 1..4 int32 (u0, u1, v0, v1), a pixel rectangle, inclusive, outside which no ray hits the object (below);
+ *            words 5.. by class; the rest zero.  A ground record: (ax, ay, ex, ey, inv, live int32, 0, 0), EMPTY = all zero.
+ *   box j    class 5 over boxes[s][j] = (cx, cy, vx, vy, yaw, length, width), drive metrics v1's format; hl = length / 2, hw =
+ *            width / 2;  b = point(cx, cy);  a = rotate(cos yaw, sin yaw): the length axis; the width axis is (-a.y, a.x); z from
+ *            zlo = -cam_height to zhi = zlo + box_height.  The eye in the box's axes: el = -(b.x * a.x + b.y * a.y),
+ *            ew = b.x * a.y - b.y * a.x.  Words 5..12 = (a.x, a.y, -hl - el, hl - el, -hw - ew, hw - ew, zlo, zhi).  EMPTY when hl
+ *            or hw is not > 0, or the eye is inside (|el| <= hl, |ew| <= hw, zlo <= 0 <= zhi).
+ *            Pixel: dl = dx * a.x + a.y;  dw = a.x - dx * a.y;  the slab test over the axes 0 (length: dl, words 7, 8), 1 (width:
+ *            dw, words 9, 10), 2 (z: dz, words 11, 12) in this order, from tn = -inf, tf = +inf: d == 0 is handled explicitly -- a
+ *            miss unless n0 <= 0 <= n1, never a division; otherwise t1 = n0 / d, t2 = n1 / d, (lo, hi) = (t1, t2) when d > 0, else
+ *            (t2, t1); lo > tn sets tn = lo and the ENTERED FACE = 0 (-length), 1 (+length), 2 (-width), 3 (+width), 4 (top): 2 *
+ *            axis + (d > 0 ? 0 : 1), always 4 for z (strictly greater: on a tie the lower axis wins); hi < tf sets tf = hi.  A hit
+ *            when tn <= tf, at t = tn.  The id is face << 16 | 5 << 8 | j.
+ *   disc j   class 6 over discs[s][j] = (cx, cy, vx, vy, r): a vertical cylinder, c = point(cx, cy), zlo = -cam_height, zhi = zlo +
+ *            disc_height, r2 = r * r.  Words 5..9 = (c.x, c.y, r2, zlo, zhi).  EMPTY when r is not > 0 or the eye is inside
+ *            ((c.x * c.x + c.y * c.y) - r2 <= 0 and zlo <= 0 <= zhi).
+ *            Pixel: B = dx * c.x + c.y;  cr = dx * c.y - c.x (direction x centre: no cancellation between large terms, unlike
+ *            B * B - A2 * |c|^2);  disc = A2 * r2 - cr * cr.  SIDE when disc >= 0: ts = (B - sqrt(disc)) / A2, a hit when
+ *            zlo <= ts * dz <= zhi.  CAP when dz < 0: tc = zhi / dz, x = dx * tc - c.x, y = tc - c.y, a hit when x * x + y * y <= r2.
+ *            Both are candidates of the hit rule with the same id 6 << 8 | j.
+ *   lamp j   class 7, for signals[s][j] (signals v1's record) with phase[s][j] in 1..4 and L = |B - A| > 0; any other slot leaves
+ *            its lamp, pole and stop line EMPTY.  With signals v1's t = (B - A) / L and n = (-t.y, t.x) (the driving direction):
+ *            m = A + 0.5 * (B - A);  w = m + lamp_setback * n (a far-side signal);  l = (point(w), lamp_height - cam_height);
+ *            R2 = lamp_radius^2.  Words 5..9 = (l.x, l.y, l.z, R2, phase int32).  EMPTY when ((l.x * l.x + l.y * l.y) + l.z * l.z) -
+ *            R2 is not > 0 (the eye inside).  Pixel: B = (dx * l.x + l.y) + dz * l.z;  c = (l.y * dz - l.z, l.z * dx - l.x * dz,
+ *            l.x - l.y * dx);  disc = A3 * R2 - ((c.x * c.x + c.y * c.y) + c.z * c.z);  a hit when disc >= 0 at
+ *            t = (B - sqrt(disc)) / A3.
+ *   pole j   class 8: disc j's arithmetic for the cylinder of pole_radius over point(w) from the ground to the lamp's centre, zhi
+ *            = l.z (pole_radius 0: none).
+ *   line j   the stop line of a signal that is not empty, ground record j: a = point(A), e = point(B) - a, inv = 1 / (e.x * e.x +
+ *            e.y * e.y), or 0 when that is not > 0; live = 1.
+ *   road     roads fp64 [scenes][Q][G][2] and road_len int32 [scenes][Q] -- traffic v1's `paths` and `plen` as they are; a length
+ *            is clamped into 0..G and a path with fewer than 2 counted points has no segment.  Segment g of path q (g + 1 <
+ *            len), ground record n_signals + q (G - 1) + g: a stop line's arithmetic on the points g and g + 1; live = 0 when a
+ *            coordinate is NaN.
+ *   ground   a ray with dz < 0 meets the ground at tg = cam_height / (-dz), at (gx, gy) = (dx * tg, tg).  Squared distance to a
+ *            ground record by clamped projection: q = g - a;  u = (q.x * e.x + q.y * e.y) * inv;  u < 0 becomes 0, u > 1 becomes 1;
+ *            c = (q.x - u * e.x, q.y - u * e.y);  d2 = c.x * c.x + c.y * c.y.  The ground's id, in this order:
+ *              tg > far                                 1 << 8 | 1   far ground
+ *              d2 <= line_half^2 for a live stop line   4 << 8 | j   the lowest such j; wins over road and marking
+ *              dmin = the smallest d2 over the live road segments (+inf without one):
+ *              dmin < (half_width - mark)^2             2 << 8       road
+ *              dmin <= half_width^2                     3 << 8       edge marking
+ *              otherwise                                1 << 8       ground
+ *            The three squared thresholds are formed on the host in fp64 and rounded to fp32 once.
+ *   hit      a candidate counts when t > near.  The nearest t wins; on an exact tie the lower class << 8 | slot wins, the ground
+ *            (class 1 for this purpose) before every object.  Nothing hit: sky, id 0, depth +inf.  A primitive the eye is inside
+ *            is empty (stage).  A NaN makes every comparison it enters false.
+ *   pixel    fp32 only: + - * / sqrt and comparisons, each rounded on its own (no contraction, no fast-math, no library call), so
+ *            a float32 restatement run on the same table makes the same decisions (tests/camera_ref.py).
+ *   cull     words 1..4 of an object record come from the eight corners of its bounding cuboid in fp64, each projected and
+ *            widened outwards by one pixel plus 2^-20 of the corner's coordinates carried through the projection.  A corner
+ *            nearer than 0.05 m to the eye's plane, or a NaN, makes the rectangle the whole image (-1, 2^20, -1, 2^20); every
+ *            corner behind that plane makes it empty (1, 0, 1, 0).  A culled evaluation gives the plain loop's answer.
+ *   colour   flat, from palette uint8 [20][3]: 0 sky; 1 ground; 2 far ground; 3 road; 4 marking; 5 stop line; 6 + (j % 8) box j;
+ *            14 disc; 15 pole; 16 + (phase - 1) lamp.  A box face is shaded in integers, (c * shade[face]) >> 8.  A pixel's colour
+ *            is a pure function of its id and its signal's phase.  adx_camera_default_palette writes the committed default.
+ *   outputs  each optional, at least one: frames uint8 [scenes][H][W][3] (adx_resnet_forward_frames' format); image fp32
+ *            [scenes][3][H][W]: bit for bit what adx_image_normalize makes of `frames` with cfg's mean and std, ((float)c / 255 -
+ *            mean) / std; ids int32 [scenes][H][W]; depth fp32 [scenes][H][W]: t, +inf for sky.
+ *   hold     int32 [scenes] or NULL: where hold != 0 neither the scene's table nor any of its outputs is written.
+ *   launch   stage: one workgroup of one wave per scene, lane j owns box, disc and signal j, the lanes stride over the segments.
+ *            render: one workgroup of 256 threads per 64 x 16 tile of a scene; the objects whose rectangle meets the tile are
+ *            compacted into LDS by ballot in index order, the ground records are copied by tiles that reach below the horizon;
+ *            one lane per pixel, every lane of a wave on the same record.  A full, word-aligned row of frames goes out as packed
+ *            32-bit words.  No atomics.
+ *   differs  from the reference's sensor, on purpose and by far: flat-shaded geometry, not a town.  No textures, no lighting, no
+ *            fog, no shadows, no anti-aliasing, no lens model, no continuous term of any kind; the road is a distance to
+ *            polylines; other road users are cuboids, signals a sphere on a pole.  CARLA-trained weights do not transfer.
+ *   rounding two evaluations of `stage` that differ only in their cos and sin routines (each within 4 ulp) differ per position word
+ *            as ego frame v1's `point` says -- one fp32 ulp plus 8 * 2^-52 * (|dx| + |dy|) -- and per derived word by that carried
+ *            through its products (tests/camera_ref.py derives each); the render launch is exact on a given table.
+ *
+ * adx_camera_prims_bytes is 0 for a count out of range, else 4 * scenes * (16 + 16 n_obj + 8 n_gnd).
+ *
+ * Limits: 1 <= scenes <= 65535, 8 <= width <= 2048, 8 <= height <= 1024, 0 < fov < 3 rad, 0 <= n_boxes, n_discs, n_signals <= 64,
+ * 0 <= n_paths <= 8 with 2 <= n_points <= 64 (n_points = 0 when n_paths = 0); mount_back and lamp_setback finite; cam_height, near,
+ * far > near, half_width, line_half, box_height, disc_height, lamp_radius, lamp_height finite and > 0; 0 <= mark <= half_width;
+ * pole_radius finite and >= 0; mean finite, std finite and not 0.  ADX_ERR_INVALID before any GPU work, each with its own text, for
+ * a value out of range, a NULL pointer that a count above 0 needs (pose and prims always), prims not 16-byte aligned, no output at
+ * all, or an output (prims, frames, image, ids, depth) that overlaps an input or another output.
+ * -----------------------------------------------------------------------------------*/
+#define ADX_CAMERA_PALETTE 20
+typedef struct adx_camera_cfg {
+  int32_t scenes, width, height, n_boxes, n_discs, n_signals, n_paths, n_points;
+  double fov, mount_back, cam_height, near, far, half_width, mark, line_half, box_height, disc_height, lamp_radius, lamp_height,
+      lamp_setback, pole_radius;
+  float mean[3], stdv[3];
+  uint8_t palette[ADX_CAMERA_PALETTE][3];
+  uint8_t shade[5];
+  uint8_t reserved[7];
+} adx_camera_cfg;
+size_t adx_camera_prims_bytes(const adx_camera_cfg* c);
+void adx_camera_default_palette(uint8_t* palette /* [20][3] or NULL */, uint8_t* shade /* [5] or NULL */);
+int adx_camera_render(const adx_camera_cfg* c, const double* pose, const double* boxes /* or NULL */, const double* discs /* or NULL */,
+                      const double* signals /* or NULL */, const int32_t* phase /* or NULL */, const double* roads /* or NULL */,
+                      const int32_t* road_len /* or NULL */, const int32_t* hold /* or NULL */, void* prims,
+                      uint8_t* frames /* or NULL */, float* image /* or NULL */, int32_t* ids /* or NULL */,
+                      float* depth /* or NULL */, adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
  * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
  * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
