@@ -38,6 +38,11 @@ Public surface mirrors the reference's packages:
     Camera                                            (no reference counterpart -- the reference reads CARLA's RGB sensor --: the
                                                        front camera as an analytic ray caster over the world's primitives, the
                                                        frames `drive(image=)` feeds the encoder, on the device, camera.py)
+    Expert                                            (no reference counterpart -- the reference collects with CARLA's autopilot and
+                                                       a Roach expert --: a privileged driver that follows the route, queues, stops
+                                                       at lights and slows for bends, on the device, expert.py)
+    Demonstrations                                    (misc/data_collect.py's writer: a drive recorded as the frames, hindsight
+                                                       waypoints and targets TrajDataset reads, demos.py)
     DeviceController                                  (control.Controller + post_process_control for all scenes in one launch,
                                                        control/device.py)
     misc.constant.GuidanceType, misc.load_param.copy_parameters
@@ -70,9 +75,12 @@ from .simulation import DriveMetrics, EagerTick, KinematicVehicle, World, drive,
 from .signals import Signals  # noqa: E402
 from .traffic import Traffic  # noqa: E402
 from .camera import Camera  # noqa: E402
+from .expert import Expert  # noqa: E402
+from .demos import Demonstrations  # noqa: E402
 
 __all__ = ["modeling", "scheduler", "control", "misc", "config", "sampling", "DeviceNoise", "GuidanceDPMSolverMultistepScheduler",
            "TrajectorySelector", "Selection", "WarmStart", "DeviceController", "Pin", "Guide", "CostField", "MotionLimits",
            "Route", "Capsules", "StopShort", "StopResult", "TrajectoryModes", "ModeSet", "ManoeuvreCommit", "CommitResult",
            "OpenLoopMetrics", "MetricsBatch", "evaluate_open_loop", "Navigator", "EgoFrame",
-           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop", "Signals", "Traffic", "Camera"]
+           "KinematicVehicle", "DriveMetrics", "World", "EagerTick", "drive", "evaluate_closed_loop", "Signals", "Traffic", "Camera",
+           "Expert", "Demonstrations"]

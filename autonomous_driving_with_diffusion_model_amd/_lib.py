@@ -165,6 +165,13 @@ class CameraCfg(C.Structure):
                [("mean", f32 * 3), ("stdv", f32 * 3), ("palette", C.c_uint8 * 60), ("shade", C.c_uint8 * 5), ("reserved", C.c_uint8 * 7)]
 
 
+class ExpertCfg(C.Structure):
+    """adx_expert_cfg ("expert v1", include/adx.h)."""
+    _fields_ = [(n, i32) for n in ("scenes", "window", "n_boxes", "n_discs", "n_planes", "horizon", "dim", "reserved")] + \
+               [(n, C.c_double) for n in ("xy_scale", "waypoint_dt", "desired_v", "accel", "brake", "brake_max", "headway", "jam", "gap_min",
+                                          "corridor_half", "lat_accel", "look_time", "ego_front", "end_margin", "look_min")]
+
+
 class ControlCfg(C.Structure):
     _fields_ = ([(n, i32) for n in ("scenes", "horizon", "dim", "waypoints", "n_turn", "n_speed", "source", "post")] +
                 [(n, f32) for n in ("sign_x", "xy_scale", "target_scale", "turn_kp", "turn_ki", "turn_kd", "speed_kp", "speed_ki",
@@ -333,6 +340,7 @@ _LAZY_SIGS = {
     "adx_camera_prims_bytes": (C.c_size_t, [C.POINTER(CameraCfg)]),
     "adx_camera_default_palette": (None, [vp, vp]),
     "adx_camera_render": (i32, [C.POINTER(CameraCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "adx_expert_plan": (i32, [C.POINTER(ExpertCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "adx_world_to_ego": (i32, [i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, vp]),
     "adx_ego_to_world": (i32, [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp]),
 }

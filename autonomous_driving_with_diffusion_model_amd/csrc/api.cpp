@@ -433,6 +433,10 @@ int adx_camera_render(const adx_camera_cfg* c, const double* pose, const double*
                       uint8_t* frames, float* image, int32_t* ids, float* depth, adx_stream s) {
   return adx::camera_render(c, pose, boxes, discs, signals, phase, roads, road_len, hold, prims, frames, image, ids, depth, (hipStream_t)s);
 }
+int adx_expert_plan(const adx_expert_cfg* c, const float* window, const float* velocity, const float* boxes, const float* discs,
+                    const float* planes, float* plan, int32_t* leader, float* info, adx_stream s) {
+  return adx::expert_plan(c, window, velocity, boxes, discs, planes, plan, leader, info, (hipStream_t)s);
+}
 int adx_world_to_ego(int32_t kind, const double* in, const double* pose, float* out, int32_t scenes, int32_t n, double xy_scale,
                      double vel_scale, adx_stream s) {
   return adx::world_to_ego(kind, in, pose, out, scenes, n, xy_scale, vel_scale, (hipStream_t)s);

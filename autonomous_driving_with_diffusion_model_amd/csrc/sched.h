@@ -159,6 +159,9 @@ void camera_default_palette(uint8_t* palette, uint8_t* shade);
 int camera_render(const adx_camera_cfg* c, const double* pose, const double* boxes, const double* discs, const double* signals,
                   const int32_t* phase, const double* roads, const int32_t* road_len, const int32_t* hold, void* prims, uint8_t* frames,
                   float* image, int32_t* ids, float* depth, hipStream_t s);
+// "Expert v1" (expert.hip)
+int expert_plan(const adx_expert_cfg* c, const float* window, const float* velocity, const float* boxes, const float* discs,
+                const float* planes, float* plan, int32_t* leader, float* info, hipStream_t s);
 // "Stop-short fallback v1" (fallback.hip); g.motion is not looked at: the fallback re-times waypoints one by one
 int stop_short(const float* traj, const GuideRecords& g, const float* params, int param_rows, float* out, int32_t* first,
                int32_t* status, float* stop_at, int32_t* active_after, int rows, int horizon, int dim, hipStream_t s);

@@ -1930,6 +1930,100 @@ int adx_camera_render(const adx_camera_cfg* c, const double* pose, const double*
                       float* depth /* or NULL */, adx_stream s);
 
 /* ------------------------------------------------------------------------------------
+ * Expert v1: a privileged driver for every scene of a launch -- it sees the world and not the pixels: it follows the route window,
+ * queues behind whatever is nearest ahead of it in its corridor (a box, a disc, a stop plane of signals v1, the end of the route)
+ * by traffic v1's Intelligent Driver Model, slows for bends, and writes the plan control v1 takes as it is.  What the reference
+ * collects its demonstrations with is CARLA's autopilot and a Roach expert (misc/data_collect.py); this package rules the
+ * simulator out, so the expert is its own.  A STATELESS launch: one workgroup of one wave per scene, no atomics, no host decision,
+ * capturable.  Callers and fixtures depend on this definition -- a change is a new version, never an edit.
+ *
+ * NO LIBRARY CALL lies on the way to any output word: only IEEE + - * / and sqrt in fp64 without contraction, every product, sum,
+ * division and square root rounded on its own, in the order written here; headings arrive as unit vectors, curvature is Menger's,
+ * there is no trigonometry.  A NaN makes every comparison it enters false.  So two evaluations agree in every bit.
+ *
+ *   inputs   all in device memory, in a tick's ego frame (ego frame v1) and model units, fp32, every word widened exactly to fp64.
+ *            A length becomes metres by `* xy_scale`; an obstacle velocity w becomes m/s by (w * xy_scale) / waypoint_dt.
+ *            window fp32 [scenes][R][2]: route planner v1's window, 2 <= R <= 32, best with first = 0;  P[i] = (x * xy_scale,
+ *            y * xy_scale).  velocity fp32 [scenes] m/s;  v_0 = velocity when velocity > 0, else 0 (a NaN becomes 0).
+ *            boxes fp32 [scenes][N][8] = adx_world_to_ego's kind 3 (cx, cy, vx, vy, hx, hy, length, width), 0 <= N <= 64, NULL
+ *            exactly when N = 0; a slot is EMPTY unless length > 0 and width > 0.  The heading (hx, hy) is used as it stands.
+ *            discs fp32 [scenes][M][5] = kind 1 (cx, cy, vx, vy, radius), 0 <= M <= 64, NULL exactly when M = 0; EMPTY unless
+ *            radius > 0.  planes fp32 [scenes][K][3] = (nx, ny, b), signals v1's output (n . p <= b is the allowed side),
+ *            0 <= K <= 8, NULL exactly when K = 0;  bm = b * xy_scale, n as it stands.
+ *   path     segment j = 0 .. R-2:  e_j = P[j+1] - P[j];  L2_j = e.x * e.x + e.y * e.y.  A segment whose L2 is not > 0 is
+ *            DEGENERATE: len_j = 0, tau_j = (0, 0), and a projection onto it has t = 0.  Otherwise len_j = sqrt(L2_j) and
+ *            tau_j = (e.x / len_j, e.y / len_j).  cum[0] = 0, cum[j+1] = cum[j] + len_j, the sequential sum; total = cum[R-1].
+ *            The path ENDS when segment R-2 is degenerate (route planner v1 pads a window with the route's last point).
+ *   project  of a point q in metres, traffic v1's rule over all segments: a = P[j];  t = 0 on a degenerate segment, else
+ *            f = ((q.x - a.x) * e.x + (q.y - a.y) * e.y) / L2 clamped into 0..1 (a NaN becomes 0);  c = (a.x + t * e.x,
+ *            a.y + t * e.y);  d = sqrt((q.x - c.x)^2 + (q.y - c.y)^2), a NaN d counting as +inf.  The smallest d wins, the
+ *            LOWER j on a tie.  s = cum[j] + t * len_j.  It gives (s, d, j) and the point c.  The ego is the origin: (s_e,
+ *            d_e, j_e) and c_e.  ONE EXCEPTION to the clamp: on segment 0, f < 0 gives t = f -- THE PATH BEGINS WITH A RAY.
+ *            Route planner v1 pops every point within min_distance of the ego, so its window begins at the farthest of them,
+ *            up to min_distance AHEAD of the ego; clamped there, the ego and everything between it and P[0] would collapse
+ *            onto P[0].  On the ray s is negative, and arc lengths are only ever compared and subtracted.
+ *   leader   the candidates, each a rear position r -- the metres of free road ahead of the ego's front bumper -- and a speed u,
+ *            in this order; the smallest r wins, the earlier candidate on a tie; a NaN r never wins:
+ *              box i    not empty; c = (cx, cy) * xy_scale projects to (s, d, j);  hl = (length * xy_scale) / 2,
+ *                       hw = (width * xy_scale) / 2;  dt_ = |hx * tau_j.x + hy * tau_j.y|,  cr = |hx * tau_j.y - hy * tau_j.x|;
+ *                       lon = hl * dt_ + hw * cr;  lat = hl * cr + hw * dt_.  It counts when d <= corridor_half + lat and
+ *                       s - s_e > 0.  r = ((s - s_e) - lon) - ego_front;  with vel = ((vx * xy_scale) / waypoint_dt, ...):
+ *                       u = max(0, vel.x * tau_j.x + vel.y * tau_j.y), a NaN becoming 0.
+ *              disc i   the same with lon = lat = radius * xy_scale.
+ *              plane k  g(p) = (n.x * p.x + n.y * p.y) - bm.  INERT when n.x == 0 and n.y == 0, when the origin is already
+ *                       beyond it (-bm > 0), or when the path walked from the ego's projection on never passes from g <= 0 to
+ *                       g > 0.  The walk: the piece (c_e at arc s_e) -> P[j_e + 1], then the segments j_e + 1 .. R-2, each
+ *                       (P[j] at arc cum[j]) -> (P[j+1] at arc cum[j+1]).  The first piece A -> B with ga = g(A) <= 0 and
+ *                       gb = g(B) > 0 gives arc = arc_A + (ga / (ga - gb)) * (arc_B - arc_A), a linear interpolation.
+ *                       r = (arc - s_e) - ego_front;  u = 0.
+ *              the end  when the path ends:  r = ((total - s_e) - ego_front) - end_margin;  u = 0.
+ *            leader int32 [scenes] is an output: -1 none, 0..63 box i, 64..127 disc i - 64, 128 + k plane k, 136 the end.
+ *   curve    look = look_min + v_0 * look_time.  Over the interior vertices i = 1 .. R-2 whose segments i-1 and i are both not
+ *            degenerate and whose ah = cum[i] - s_e satisfies ah >= 0 and ah <= look:  ch = P[i+1] - P[i-1];
+ *            lc = sqrt(ch.x * ch.x + ch.y * ch.y);  x = |e_{i-1}.x * e_i.y - e_{i-1}.y * e_i.x|;
+ *            kappa = (2 * x) / ((len_{i-1} * len_i) * lc)  (Menger);  where kappa > 0: lim = sqrt(lat_accel / kappa).
+ *            desired = min(desired_v, the smallest lim).  Evaluated ONCE per launch, not per roll-out step.
+ *   law      traffic v1's, formula for formula, rolled out over k = 0 .. H-1 from v_0 and a_0 = 0 with the leader moving at
+ *            constant u:  f = v_k / desired;  free = 1 - (f * f) * (f * f).  With a leader:
+ *            gap = (r + u * ((double)k * waypoint_dt)) - a_k;  star = jam + max(0, v_k * headway + (v_k * (v_k - u)) /
+ *            (2 * sqrt(accel * brake))) (a NaN inside max becoming 0);  g = max(gap, gap_min) (a NaN becoming gap_min);
+ *            inter = (star / g) * (star / g).  Without one inter = 0.  acc_k = accel * (free - inter), set to -brake_max when
+ *            below it and to accel when above it.  v_{k+1} = max(0, v_k + acc_k * waypoint_dt) (a NaN becoming 0);
+ *            a_{k+1} = a_k + v_{k+1} * waypoint_dt: semi-implicit, as vehicle v1.
+ *   rows     row k is the path's point at arc A = s_e + a_k:  j = the largest index of a segment that is not degenerate and has
+ *            cum[j] <= A, or the lowest one that is not degenerate when there is none;  p = (P[j].x + (A - cum[j]) * tau_j.x,
+ *            ...).  Nothing clamps A to the segment, so beyond the last point the plan continues along the last tangent
+ *            (and before the first along the ray).  A path without any such segment gives p = P[0].  Row 0 is the ego's projection onto the path: that is what pulls
+ *            the controller back onto the route.
+ *   outputs  plan fp32 [scenes][H][D], 2 <= H <= 64, 2 <= D <= 16: columns 0 and 1 = (p.x / xy_scale, p.y / xy_scale), every
+ *            other column 0.  leader.  info fp32 [scenes][8] = (s_e, d_e, desired, r, u, acc_0, v_H, a_H), r = +inf and u = 0
+ *            without a leader.  Each word is rounded to fp32 once; a NaN is stored as 0x7fc00000.
+ *   launch   one workgroup of one wave per scene.  The window is staged into LDS once (points, then the segments, lane j segment
+ *            j, then cum by lane 0).  Lane i owns box i, disc i, plane i and curve vertex i, each with a uniform loop over the
+ *            segments; an xor butterfly takes the minimum over (r, leader code) and another over lim.  Every lane runs the
+ *            H-step roll-out redundantly and keeps a_k when k is its own index; lane k stores row k.  Vector stores only.
+ *   differs  from the reference's collectors, on purpose.  CROSSING TRAFFIC IS NOT PREDICTED: an obstacle counts only while it
+ *            is inside the corridor, at its speed along the path.  There are NO LANE CHANGES and NO OVERTAKING: a leader that
+ *            stands is queued behind for good.  THE CURVE LIMIT IS EVALUATED ONCE PER LAUNCH, at the launch's speed, and holds
+ *            for the whole roll-out.  Stop signs bind only as long as signals v1 emits their plane.  Nothing reads a map.
+ *   rounding every word of plan, leader and info is the same in two evaluations: there is no library call to differ in.
+ *
+ * Limits: 1 <= scenes <= 65535, 2 <= window = R <= 32, 0 <= n_boxes, n_discs <= 64, 0 <= n_planes <= 8, 2 <= horizon = H <= 64,
+ * 2 <= dim = D <= 16; xy_scale, waypoint_dt, desired_v, accel, brake, brake_max, headway, jam, gap_min, corridor_half, lat_accel
+ * and look_time finite and > 0; ego_front, end_margin and look_min finite and >= 0.  ADX_ERR_INVALID before any GPU work, each with
+ * its own text, for a value out of range, a NULL pointer that may not be NULL (boxes, discs, planes exactly when their count is
+ * 0), or an output (plan, leader, info) that overlaps an input or another output.
+ * -----------------------------------------------------------------------------------*/
+typedef struct adx_expert_cfg {
+  int32_t scenes, window, n_boxes, n_discs, n_planes, horizon, dim, reserved;
+  double xy_scale, waypoint_dt, desired_v, accel, brake, brake_max, headway, jam, gap_min, corridor_half, lat_accel, look_time,
+      ego_front, end_margin, look_min;
+} adx_expert_cfg;
+int adx_expert_plan(const adx_expert_cfg* c, const float* window, const float* velocity, const float* boxes /* or NULL */,
+                    const float* discs /* or NULL */, const float* planes /* or NULL */, float* plan, int32_t* leader, float* info,
+                    adx_stream s);
+
+/* ------------------------------------------------------------------------------------
  * Capsules from boxes v1: the capsule slots of cost guidance v5 from ORIENTED BOXES, one launch -- what a perception stack hands a
  * planner for the other road users.  Capturable: no allocation, no synchronisation, no host decision, so a captured tick whose
  * boxes change at every replay needs no host work.  Callers and fixtures depend on this definition -- a change is a new version,
